@@ -13,6 +13,17 @@ present.  For N>1 every rank runs the same per-GPU workload on its own game-inde
 (weak scaling; games are independent, no data-path collective) and the ranks all-gather
 their replay rows over RCCL at the end.
 
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+the headline does not need: the CPU baseline of the reference's path, the exact-f32 side run and
+the games leg (complete games from the empty board, measured games/s).
+
+--dump-outputs DIR writes the root statistics of every game slot after the last timed step
+(rank 0) as DIR/<name>.npy, float32 / float64.  Inputs are fixed by the seeds, and the step path
+orders the leaves behind the network's full-rounds cut and the hand-out of new games by slot, so two
+runs with the same arguments write the same arrays -- as long as the device output buffer has room
+for every finished game (two games per slot; it is never drained here, and a slot that finds it
+full waits in an order set by device atomics).  The run says so on stderr when a slot waited.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -208,6 +219,7 @@ def run_engine(args, precision, steps, warmup, rank, local_rank, world, dist, to
     m = {k: c1[k] - c0[k] for k in ("expansions", "nn_evals", "sum_path", "terminal_leaves", "moves_played", "cache_hits",
                                     "f32_fallback_evals", "pool_resets")}
     m.update(dt=dt, ms_total=c1["ms_total"], ms_nn_tower=c1["ms_nn_tower"], pool_high_water=c1["pool_high_water"],
+             blocked_slots=c1["blocked_slots"],
              nodes_per_slot=eng.nodes_per_slot, E=eng.E, prep_steps=prep)
     if dist is not None:
         tdev = torch.tensor([float(m["expansions"]), float(m["nn_evals"]), dt], dtype=torch.float64).cuda()
@@ -420,6 +432,33 @@ def tower_roofline(args, m, steps, precision):
             "tree_and_heads_ms_per_step": (m["ms_total"] - m["ms_nn_tower"]) / steps}
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+NPY_HEADER_BYTES = 4096  # allowance per file for the .npy header
+
+
+def dump_outputs(eng, out_dir, limit=DUMP_LIMIT_BYTES):
+    """What a caller of the step path reads after the last timed step: every slot's root statistics (Engine.roots()) and the
+    ply of its root position.  Integer arrays are written as float64 (exact); a fixed, seeded sample of the slots if the whole
+    would exceed `limit`."""
+    r = eng.roots()
+    edges = np.ascontiguousarray(eng.root_states()["edges"])  # bitmask of the edges drawn: its popcount is the ply
+    ply = np.unpackbits(edges.view(np.uint8), axis=1).sum(axis=1)
+    arrays = {"root_priors": r["priors"], "root_total_value": r["total_value"], "root_visits": r["visits"].astype(np.float64),
+              "root_stats": r["stats"].astype(np.float64), "root_q": r["q"], "root_tv": r["root_tv"],
+              "root_nv": r["root_nv"].astype(np.float64), "root_ply": ply.astype(np.float64)}
+    n = eng.n_slots
+    per_slot = sum(a.nbytes for a in arrays.values()) / n + 8
+    budget = limit - (len(arrays) + 1) * NPY_HEADER_BYTES  # + the slot index file
+    slots = np.arange(n)
+    if per_slot * n > budget:
+        slots = np.sort(np.random.RandomState(0).choice(n, int(budget // per_slot), replace=False))
+    arrays = {k: a[slots] for k, a in arrays.items()}
+    arrays["slot"] = slots.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -436,9 +475,13 @@ def main():
                          "f16x3 layer, debug build only (DBAZ_LIB=dotsboxesaz_amd/libdbaz_hip_debug.so; EXPERIMENTS.md)")
     ap.add_argument("--debug-flags", type=int, default=0, help="dbaz_config.debug_flags (1 = early join, 2 = no f32 fallback launch)")
     ap.add_argument("--nodes-per-slot", type=int, default=0, help="tree node pool per game (0 = engine default 10*(sims+2))")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline, the exact-f32 side run and the games leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write every slot's root statistics as DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-side-run", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-f32-side-run", action="store_true", help="--full without the exact-f32 side run")
     ap.add_argument("--zero-weights", action="store_true", help="diagnosis: all conv/fc weights zero (clock under load vs operand data)")
     ap.add_argument("--no-tt", action="store_true", help="switch the per-game transposition table off (kernel measurements)")
     ap.add_argument("--population", default="games", choices=["games", "random", "fresh"],
@@ -447,7 +490,7 @@ def main():
     ap.add_argument("--quick-reads", type=int, default=48, help="--population games: simulations per move of the opening plies")
     ap.add_argument("--game-plies", type=int, default=0, help="--population games: plies sampled (0 = 0.97 E, the mean game length)")
     ap.add_argument("--games-leg", type=int, default=-1,
-                    help="complete games played (per rank) AFTER the timed steps for the directly measured games/s of the "
+                    help="--full: complete games played (per rank) AFTER the timed steps for the directly measured games/s of the "
                          "metric; -1 = one game per slot (the BASELINE config's game count), 0 = skip")
     ap.add_argument("--games-leg-budget", type=float, default=240.0, help="wall-clock cap of the games leg in seconds")
     ap.add_argument("--full-games", type=int, default=0,
@@ -471,8 +514,11 @@ def main():
     if args.fresh_population:
         args.population = "fresh"
     special = args.full_games > 0 or args.train_data > 0 or args.single_tree > 0 or args.train_step > 0
+    if special and args.dump_outputs:
+        ap.error("--dump-outputs writes the outputs of the self-play step benchmark; it does not apply to --full-games, "
+                 "--train-data, --train-step or --single-tree")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not special:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not special:
         # before anything touches the GPU: the baseline forks one worker process per host core
         cpu = cpu_baseline(args.board, args.board, args.sims, args.cpu_seconds, args.channels, args.blocks)
     import torch
@@ -495,6 +541,11 @@ def main():
         single_tree_bench(args, local_rank, torch)
         return
     eng, m = run_engine(args, args.precision, args.steps, args.warmup, rank, local_rank, world, dist, torch)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+        if m["blocked_slots"]:
+            print("bench.py: %d slots waited for room in the full output buffer; which ones is set by device atomics, so the "
+                  "dumped outputs may differ from another run's" % m["blocked_slots"], file=sys.stderr)
     # replay all-gather at iteration end (multi-GPU): whatever finished + a fixed synthetic shard
     gather = None
     if dist is not None:
@@ -503,7 +554,7 @@ def main():
         gather = dict(rows=rows_total, ms=ms)
     eng.close()
     side = None
-    if args.evaluator == "resnet" and args.precision >= 1 and not args.no_f32_side_run:
+    if args.full and args.evaluator == "resnet" and args.precision >= 1 and not args.no_f32_side_run:
         st = max(20, args.steps // 6)
         # (exact-f32 steps are 6x longer: the side run keeps the cheap population; it reports the tower's f32 efficiency)
         eng0, m0 = run_engine(args, 0, st, max(5, args.warmup // 5), rank, local_rank, world, dist, torch,
@@ -513,7 +564,7 @@ def main():
     # the second half of the metric, measured directly: complete games from the empty board on every rank's slots
     leg = None
     n_leg = args.slots if args.games_leg < 0 else args.games_leg
-    if n_leg > 0:
+    if args.full and n_leg > 0:
         leg = play_complete_games(args, n_leg, args.slots, rank, local_rank, torch, budget_s=args.games_leg_budget)
         if dist is not None:
             t = torch.tensor([float(leg["games"]), leg["seconds"]], dtype=torch.float64).cuda()

@@ -43,6 +43,7 @@ enum Phase : int32_t {
     PH_READY = 3,       // reads done, waiting for the move (k_advance)
     PH_EMIT = 4,        // game finished, rows waiting for space in the output buffer
     PH_ERROR = 5,
+    PH_NEWGAME = 6,     // game finished and emitted; the next k_driver_scan hands out the next game index (slot order)
 };
 
 struct Slot {
@@ -78,7 +79,7 @@ struct Slot {
     int32_t wave_sims;       // K > 1 search: simulations selected in the current wave, waiting for expand/backup
     int32_t first_wave;      // K > 1 search: the first wave of a UCT_search call is min(K, A) wide (mcts.py:228-229)
     int32_t pool_resets;     // self-play driver: moves whose kept subtree would not have left room for the next search (fresh root instead)
-    int32_t eval_pos;        // position of this step's leaf in the evaluation list (k_select)
+    int32_t eval_pos;        // position of this step's leaf in the evaluation list (k_select, or k_order_evals with the full-rounds cut)
     int32_t pending;         // 1 = the leaf was selected in an earlier step and its evaluation put off (SearchCfg.eval_round)
 };
 
@@ -146,6 +147,7 @@ struct TreeBufs {
     float *evalP;      // [n_slots][AS]
     float *evalV;      // [n_slots]
     int32_t *eval_list;// [n_slots] compacted slots needing an NN evaluation (model 0)
+    int32_t *ev_class;  // [n_slots] full rounds only: k_select's class of each slot's leaf, for k_order_evals
     int32_t *eval_list2;// [n_slots] same for model 1 (match play)
     int32_t *n_eval;   // [4] list lengths of the two models; [2] leaves model 0's network took this step (k_head_fc, full rounds only)
     int32_t *pend;     // [n_slots][cap] ring: dropped nodes waiting for the collector (their child rows are still needed)

@@ -267,6 +267,7 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     CREATE_CHECK(dmalloc(e, &B.evalP, ns * g.AS));
     CREATE_CHECK(dmalloc(e, &B.evalV, ns));
     CREATE_CHECK(dmalloc(e, &B.eval_list, ns));
+    CREATE_CHECK(dmalloc(e, &B.ev_class, ns));
     CREATE_CHECK(dmalloc(e, &B.eval_list2, ns));
     CREATE_CHECK(dmalloc(e, &B.n_eval, 4));
     CREATE_CHECK(dmalloc(e, &B.pend, ns * g.cap, false));
@@ -611,7 +612,8 @@ static hipEvent_t next_event(dbaz_engine *e)
 // virtual loss per tree, one batched evaluation of all their leaves, expand + backup in selection order
 // with_driver (self-play with dbaz_config.selfplay_pending: every search of a game runs in these waves, the reference's
 // self_play.py:27-30 with max_async_searches = K): the driver pass -- move choice, row emission, re-root, next search's root
-// preparation -- runs first, on the same stream; a slot it starts takes its first wave in this very step
+// preparation -- runs first, on the same stream; a search it starts takes its first wave in this very step (a slot whose game
+// ended waits in PH_NEWGAME: it is given its next game by the following pass's k_driver_scan and searches from then on)
 static int sim_wave(dbaz_engine *e, bool with_driver)
 {
     hipStream_t s = e->stream;
@@ -643,8 +645,9 @@ static int sim_step(dbaz_engine *e, bool with_driver)
     e->sc.driver_concurrent = with_driver ? 1 : 0;
     if (with_driver) {
         // The driver pass (move choice, O(1) re-root, row emission, game turnover, next search's root preparation) only
-        // touches slots whose reads are done (PH_READY / PH_EMIT); k_select only touches slots that are searching and
-        // skips the ones this very pass starts (stamp).  So the pass runs on a second stream NEXT TO k_select -- both are
+        // touches slots whose reads are done (PH_READY), whose rows wait for output space (PH_EMIT) or whose game ended
+        // (PH_NEWGAME: k_driver_scan writes their game_idx, or PH_IDLE when no game is left); k_select only touches slots that
+        // are searching and skips the ones this very pass starts (stamp).  So the pass runs on a second stream NEXT TO k_select -- both are
         // short, latency-bound kernels that leave most of the chip idle.  It is joined behind the network launch (see below):
         // almost always it has finished by the time k_select has, and when it has not (small boards: a move ends somewhere
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
@@ -660,6 +663,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         e->sc.eval_defer_max = e->eval_defer_max;
     }
     tree_launch_select(s, e->g, e->sc, e->B, e->n_slots); // (the lists' counters were zeroed by the previous k_expand_backup)
+    if (e->sc.eval_round > 0) tree_launch_order_evals(s, e->B, e->n_slots, e->sc.step); // the list in slot order (deterministic cut)
     const bool late_join = with_driver && e->late_join;
     if (with_driver && !late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
     if (use_nn) {

@@ -565,7 +565,12 @@ __device__ __forceinline__ void load_rows(NodeRows<NPL> &r, uint32_t *pool, cons
 #ifndef SELECT_WAVES
 #define SELECT_WAVES 16 // games per workgroup (one wave each)
 #endif
-// returns the model (0 / 1) whose network must evaluate this game's leaf, or -1
+// full rounds only: k_select's class of each slot's leaf (TreeBufs::ev_class), read by k_order_evals
+#define EV_CLASS_DEFERRED (-2) // the leaf of an earlier step whose evaluation was put off: head of the list
+#define EV_CLASS_NEW (-3)      // a leaf selected in this step
+#define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
+
+// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, or -1
 template <int NPL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, int lane)
 {
@@ -578,17 +583,9 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         return -1;
     if (cfg.eval_round > 0 && S->pending) {
         // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
-        // It asks for its place in the list at once, i.e. usually ahead of the leaves that are still being selected (a workgroup's
-        // batched append below happens after the slowest of its 16 descents).  That is an ordering tendency, not a guarantee: the
-        // append is an atomicAdd racing with other workgroups', so a leaf CAN land behind the cut again and wait one more step.
-        // Nothing depends on it -- a put-off leaf only completes its simulation later; the game plays the same moves.
-        if (lane == 0) {
-            S->sel_step = cfg.step;
-            const int pos = atomicAdd(B.n_eval, 1);
-            B.eval_list[pos] = slot;
-            S->eval_pos = pos;
-        }
-        return -1;
+        // k_order_evals puts it at the head of the list.
+        if (lane == 0) S->sel_step = cfg.step;
+        return SEL_DEFERRED;
     }
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
     PathEnt *path = B.path + (size_t)slot * g.dmax;
@@ -839,6 +836,13 @@ __global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg
 {
     __shared__ int s_cnt[2], s_base[2];
     const int slot = blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (WAVE - 1);
+    if (cfg.eval_round > 0) { // k_order_evals writes the list
+        if (slot < n_slots) {
+            const int model = select_one<NPL>(g, cfg, B, slot, lane);
+            if (lane == 0) B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
+        }
+        return;
+    }
     if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     int model = -1;
@@ -854,11 +858,46 @@ __global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg
     }
 }
 
+// Full rounds only (SearchCfg.eval_round > 0, one model): which leaves land behind the network's cut depends on their order in
+// the list, so the list must not follow the order in which k_select's workgroups finish.  k_select leaves every slot's class in
+// ev_class; this one workgroup writes the list in slot order, the put-off leaves first, then the leaves of this step -- the same
+// list on every run.  The order starts at slot `rot`, which moves with the step: the leaves behind the cut are spread over the
+// slots as the atomic order spread them, instead of the same top slots waiting every other step.
+__global__ void __launch_bounds__(1024) k_order_evals(TreeBufs B, int n_slots, int rot)
+{
+    __shared__ int s_wsum[1024 / WAVE];
+    const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
+    int base = 0;
+    for (int cls = EV_CLASS_DEFERRED; cls >= EV_CLASS_NEW; cls--) {
+        for (int c0 = 0; c0 < n_slots; c0 += 1024) {
+            const int j = c0 + t, i = j + rot < n_slots ? j + rot : j + rot - n_slots;
+            const bool f = j < n_slots && B.ev_class[i] == cls;
+            const unsigned long long m = __ballot(f);
+            if (lane == 0) s_wsum[w] = (int)__popcll(m);
+            __syncthreads();
+            int off = 0, tot = 0;
+            for (int k = 0; k < 1024 / WAVE; k++) {
+                const int v = s_wsum[k];
+                off += k < w ? v : 0;
+                tot += v;
+            }
+            if (f) {
+                const int pos = base + off + (int)__popcll(m & ((1ull << lane) - 1ull));
+                B.eval_list[pos] = i;
+                B.slots[i].eval_pos = pos;
+            }
+            base += tot;
+            __syncthreads();
+        }
+    }
+    if (t == 0) B.n_eval[0] = base;
+}
+
 // Full rounds only (SearchCfg.eval_round > 0).  A network launch costs whole rounds of workgroups (nn.hip): 5 306 leaves are four
 // rounds of 1 280 and a remainder round that costs 40 % of a round for 3.5 % of the leaves.  When at most eval_defer_max leaves
 // would be left behind the last full round, the network kernels take only the full rounds (nn.hip cut_n: every kernel of the step
 // applies the same rule to the same count; k_head_fc leaves the count in n_eval[2]); the slots behind the cut keep their selected
-// leaf -- k_expand_backup sets Slot::pending -- and ask again in the next step, at the head of the list (select_one).  Every game
+// leaf -- k_expand_backup sets Slot::pending -- and ask again in the next step, at the head of the list (k_order_evals).  Every game
 // plays the same moves: only WHEN a slot's simulation completes changes.
 
 // ------------------------------------------------------------------------------------
@@ -1508,9 +1547,6 @@ __device__ bool try_emit(const Geo &g, const TreeBufs &B, int slot, Slot *S, uin
     return true;
 }
 
-__device__ void next_game_or_idle(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                                  uint32_t *pool, float *ldsf, double *ldsd, int lane);
-
 __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                                   uint32_t *pool, float *ldsf, double *ldsd, int lane)
 {
@@ -1531,22 +1567,6 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
     begin_search(g, cfg, B, slot, S, pool, -1, ldsf, ldsd, lane);
 }
 
-__device__ void next_game_or_idle(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                                  uint32_t *pool, float *ldsf, double *ldsd, int lane)
-{
-    long long gidx = 0;
-    if (lane == 0)
-        gidx = (long long)atomicAdd((unsigned long long *)B.next_game, 1ull);
-    gidx = __shfl(gidx, 0);
-    if (gidx >= B.last_game) {
-        S->game_idx = -1;
-        S->phase = PH_IDLE;
-        return;
-    }
-    S->quick_until = 0; // only a slot's first game has quick plies
-    fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-    start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
-}
 
 __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B)
 {
@@ -1573,8 +1593,9 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
     start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
 }
 
-// One pass of the driver for every slot whose reads are done (PH_READY) or whose finished
-// game still waits for output space (PH_EMIT).
+// One pass of the driver for every slot whose reads are done (PH_READY), whose finished game still waits for output space
+// (PH_EMIT) or whose game ended in an earlier pass (PH_NEWGAME: it starts the game k_driver_scan gave it).  A game that ends
+// here leaves the slot in PH_NEWGAME until the next pass.
 // (the slots come from k_driver_scan's list: a step in which no slot needs the driver costs two tiny launches instead
 // of one workgroup per game squeezing in between the network's workgroups)
 __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, float *ldsf, double *ldsd,
@@ -1582,13 +1603,21 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
 {
     Slot *S = B.slots + slot;
     const int phase = S->phase;
-    if (phase != PH_READY && phase != PH_EMIT)
+    if (phase != PH_READY && phase != PH_EMIT && phase != PH_NEWGAME)
         return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
     const int A = g.A, F = 3 * g.HW, rcap = g.E + 1;
+    if (phase == PH_NEWGAME) {
+        // the game index k_driver_scan handed out in this pass
+        const long long gidx = S->game_idx;
+        S->quick_until = 0; // only a slot's first game has quick plies
+        fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
+        start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        return;
+    }
     if (phase == PH_EMIT) {
-        if (try_emit(g, B, slot, S, pool, lane))
-            next_game_or_idle(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        if (try_emit(g, B, slot, S, pool, lane) && lane == 0)
+            S->phase = PH_NEWGAME;
         return;
     }
     const int root = S->root;
@@ -1678,30 +1707,60 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
     if (lane == 0) atomicAdd((unsigned long long *)B.moves_played, 1ull);
     NodeMeta nm = load_meta(pool, g, S->root);
     if (nm.flags & NF_TERMINAL) {
-        if (try_emit(g, B, slot, S, pool, lane))
-            next_game_or_idle(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
-        else
-            S->phase = PH_EMIT;
+        const bool emitted = try_emit(g, B, slot, S, pool, lane);
+        if (lane == 0)
+            S->phase = emitted ? PH_NEWGAME : PH_EMIT;
         return;
     }
     start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
 }
 
-// which slots need the driver: finished reads or a blocked emit (the pass runs after the previous step's expand/backup)
-__global__ void __launch_bounds__(256) k_driver_scan(SearchCfg cfg, TreeBufs B, int n_slots)
+// which slots need the driver: finished reads, a blocked emit or a finished game (the pass runs after the previous step's
+// expand/backup).  One workgroup walks the slots in order: the list is in slot order, and the slots whose game ended take the
+// next game indices (generate_games' chunking, self_play.py:291-306) in slot order, so that the same slot plays the same game on
+// every run; a slot left without a game goes idle.
+__global__ void __launch_bounds__(1024) k_driver_scan(SearchCfg cfg, TreeBufs B, int n_slots)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool need = false;
-    if (i < n_slots) {
-        const int phase = B.slots[i].phase;
-        need = phase == PH_EMIT || phase == PH_READY;
-    }
-    const unsigned long long m = __ballot(need);
-    const int lane = threadIdx.x & (WAVE - 1);
+    __shared__ int s_need[1024 / WAVE], s_new[1024 / WAVE];
+    const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
+    const long long next = *B.next_game;
+    long long taken = 0;
     int base = 0;
-    if (lane == 0 && m) base = atomicAdd(B.drv_count, (int)__popcll(m));
-    base = __shfl(base, 0);
-    if (need) B.drv_list[base + (int)__popcll(m & ((1ull << lane) - 1ull))] = i;
+    for (int c0 = 0; c0 < n_slots; c0 += 1024) {
+        const int i = c0 + t;
+        const int phase = i < n_slots ? B.slots[i].phase : PH_IDLE;
+        const bool fresh = phase == PH_NEWGAME;
+        const bool need = phase == PH_EMIT || phase == PH_READY || fresh;
+        const unsigned long long m = __ballot(need), mf = __ballot(fresh);
+        if (lane == 0) { s_need[w] = (int)__popcll(m); s_new[w] = (int)__popcll(mf); }
+        __syncthreads();
+        int off = 0, tot = 0, offf = 0, totf = 0;
+        for (int k = 0; k < 1024 / WAVE; k++) {
+            const int v = s_need[k], vf = s_new[k];
+            off += k < w ? v : 0;
+            tot += v;
+            offf += k < w ? vf : 0;
+            totf += vf;
+        }
+        if (need) B.drv_list[base + off + (int)__popcll(m & ((1ull << lane) - 1ull))] = i;
+        if (fresh) {
+            const long long gidx = next + taken + offf + (long long)__popcll(mf & ((1ull << lane) - 1ull));
+            Slot *S = B.slots + i;
+            if (gidx < B.last_game) {
+                S->game_idx = gidx;
+            } else {
+                S->game_idx = -1;
+                S->phase = PH_IDLE;
+            }
+        }
+        base += tot;
+        taken += totf;
+        __syncthreads();
+    }
+    if (t == 0) {
+        B.drv_count[0] = base;
+        *B.next_game = next + taken;
+    }
 }
 
 __global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B)
@@ -1937,9 +1996,14 @@ void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c,
 {
     hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B);
 }
+void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
+{
+    const int rot = (int)(((unsigned long long)(unsigned)step * 2654435761ull) % (unsigned long long)n_slots);
+    hipLaunchKernelGGL(k_order_evals, dim3(1), dim3(1024), 0, s, B, n_slots, rot);
+}
 void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
 {
-    hipLaunchKernelGGL(k_driver_scan, dim3((n_slots + 255) / 256), dim3(256), 0, s, c, B, n_slots);
+    hipLaunchKernelGGL(k_driver_scan, dim3(1), dim3(1024), 0, s, c, B, n_slots);
     hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,

@@ -208,7 +208,9 @@ int dbaz_advance(dbaz_engine *e, const int32_t *moves, int32_t reuse_tree);
 
 /* ---- D1-D3: self-play driver (self_play.py:19-156) ---------------------------------- */
 /* Start playing games first_game_idx .. first_game_idx+n_games-1; every slot takes the next
- * unplayed index when its game ends (generate_games' chunking, self_play.py:291-306). */
+ * unplayed index when its game ends (generate_games' chunking, self_play.py:291-306), handed out
+ * in slot order at the next step, so a run plays the same games on the same slots every time
+ * as long as the output buffer has room (slots that find it full wait in PH_EMIT in atomic order). */
 int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t first_game_idx);
 /* teacher forcing for parity tests: moves / Dirichlet vectors for game `game_idx`
  * (noise may be NULL).  Must be called before dbaz_selfplay_start. */

@@ -57,11 +57,12 @@ def test_replay_all_gather_over_rccl_single_rank():
 
 
 def test_bench_under_torch_distributed_run():
-    """The driver's launch line (one rank here): barrier + max-over-ranks timing + replay all-gather."""
+    """The driver's launch line (one rank here): barrier + max-over-ranks timing + replay all-gather; with --full the games leg
+    and its all-reduce over the ranks."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29632", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "6",
            "--warmup", "2", "--board", "3", "--slots", "256", "--sims", "50", "--channels", "32", "--blocks", "2",
-           "--no-cpu-baseline", "--no-f32-side-run"]
+           "--full", "--games-leg", "64", "--no-cpu-baseline", "--no-f32-side-run"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -69,6 +70,8 @@ def test_bench_under_torch_distributed_run():
     assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["replay_allgather"]["rows"] >= 256 * 8  # the synthetic shard, or the finished rows if more
     assert np.isfinite(d["roofline"]["frac"])
+    leg = d["games_leg"]
+    assert leg["games"] == 64 and leg["games_all_ranks"] == 64 and leg["seconds_max_over_ranks"] > 0 and d["games_per_sec"] > 0
 
 
 def _bench(*flags):

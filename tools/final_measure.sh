@@ -6,7 +6,7 @@ TAG=${1:-r03}
 repo=$PWD
 OUT=$repo/gpurun_out/final_$TAG
 rm -rf $OUT; mkdir -p $OUT
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench (driver command) done"
 python bench.py --gpus 1 --steps 200 --warmup 10 --games-leg 0 --no-cpu-baseline --no-f32-side-run > $OUT/bench_200_steps.json 2>/dev/null
 python bench.py --gpus 1 --steps 200 --warmup 10 --board 3 --slots 4096 --sims 100 --games-leg 0 --no-cpu-baseline --no-f32-side-run > $OUT/bench_config1_3x3_4096_100.json 2>/dev/null
