@@ -14,7 +14,8 @@ OK, EINVAL, EILLEGAL, EDEVICE, EPOOL, ESTATE = range(6)
 RESULT_NONE = 2
 EVAL_FORMULA_HASH, EVAL_FORMULA_UNIFORM, EVAL_RESNET, EVAL_SIMPLENN, EVAL_EXTERNAL = range(5)
 ABI_VERSION = 3  # DBAZ_ABI_VERSION of include/dbaz.h
-DBG_EARLY_JOIN, DBG_NO_FALLBACK = 1, 2
+DBG_EARLY_JOIN = 1
+DBG_NO_FALLBACK = 2  # reserved bit of dbaz_config.debug_flags: dbaz_create rejects it (DBAZ_EINVAL)
 
 # every symbol include/dbaz.h declares (checked by tests/test_abi.py)
 SYMBOLS = [

@@ -55,25 +55,16 @@ def _newer(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False, debug=False):
-    """debug=True: libdbaz_hip_debug.so with -DDBAZ_DEBUG (A/B tilings nn_precision 2/3/4, DBAZ_TRAIN_WGRAD_F32); objects in
-    csrc/_debug/.  Load it with DBAZ_LIB=<path> (dotsboxesaz_amd/_lib.py)."""
-    if debug:
-        return _build(force, verbose, ["-DDBAZ_DEBUG"], os.path.join(CSRC, "_debug"), os.path.join(HERE, "libdbaz_hip_debug.so"))
-    return _build(force, verbose, [], CSRC, LIB)
-
-
-def _build(force, verbose, defs, objdir, lib):
-    os.makedirs(objdir, exist_ok=True)
+def build(force=False, verbose=False):
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "dbaz.h"))
     objs, jobs = [], []
     for src, extra in UNITS:
         s = os.path.join(CSRC, src)
-        o = os.path.join(objdir, src.replace(".hip", ".o"))
+        o = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
-            jobs.append([HIPCC] + COMMON + defs + extra + ["-c", s, "-o", o])
+            jobs.append([HIPCC] + COMMON + extra + ["-c", s, "-o", o])
 
     def run(cmd):
         if verbose:
@@ -85,10 +76,10 @@ def _build(force, verbose, defs, objdir, lib):
 
     # build identity (csrc/buildinfo.cpp): recompiled whenever the hash of the sources changes
     sh = source_hash() + " nn=" + source_hash(NN_SOURCES)
-    bo, bh = os.path.join(objdir, "buildinfo.o"), os.path.join(objdir, "buildinfo.hash")
+    bo, bh = os.path.join(CSRC, "buildinfo.o"), os.path.join(CSRC, "buildinfo.hash")
     objs.append(bo)
     if force or not os.path.exists(bo) or not os.path.exists(bh) or open(bh).read() != sh:
-        jobs.append(["g++", "-O1", "-fPIC", "-c", os.path.join(CSRC, "buildinfo.cpp"), "-o", bo, '-DDBAZ_SRC_HASH="%s"' % sh] + defs)
+        jobs.append(["g++", "-O1", "-fPIC", "-c", os.path.join(CSRC, "buildinfo.cpp"), "-o", bo, '-DDBAZ_SRC_HASH="%s"' % sh])
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         outs = list(ex.map(run, jobs))
@@ -97,10 +88,10 @@ def _build(force, verbose, defs, objdir, lib):
         for o in outs:
             if o.strip():
                 print(o)
-    if jobs or force or _newer(lib, objs):
-        run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs)
-    return lib
+    if jobs or force or _newer(LIB, objs):
+        run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs)
+    return LIB
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True, debug="--debug" in sys.argv))
+    print(build(force="--force" in sys.argv, verbose=True))

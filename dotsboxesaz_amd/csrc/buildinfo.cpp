@@ -6,10 +6,5 @@
 #ifndef DBAZ_SRC_HASH
 #define DBAZ_SRC_HASH "unknown"
 #endif
-#ifdef DBAZ_DEBUG
-#define DBAZ_FLAVOUR " debug"
-#else
-#define DBAZ_FLAVOUR ""
-#endif
 
-extern "C" const char *dbaz_build_info(void) { return "src=" DBAZ_SRC_HASH DBAZ_FLAVOUR; }
+extern "C" const char *dbaz_build_info(void) { return "src=" DBAZ_SRC_HASH; }

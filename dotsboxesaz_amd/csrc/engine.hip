@@ -178,11 +178,9 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     if (cfg->max_pending_evals < 0 || cfg->max_pending_evals > 1024) return set_error(nullptr, DBAZ_EINVAL, "max_pending_evals must be in 0..1024");
     if (cfg->max_pending_evals > 1 && (cfg->evaluator == DBAZ_EVAL_EXTERNAL || cfg->match_play))
         return set_error(nullptr, DBAZ_EINVAL, "max_pending_evals > 1 needs a device evaluator and no match play");
-#ifdef DBAZ_DEBUG
-    if (cfg->nn_precision < 0 || cfg->nn_precision > 14) return set_error(nullptr, DBAZ_EINVAL, "nn_precision must be in 0..14 (debug build)");
-#else
     if (cfg->nn_precision < 0 || cfg->nn_precision > 1) return set_error(nullptr, DBAZ_EINVAL, "nn_precision must be 0 (exact f32) or 1 (f16x3)");
-#endif
+    if (cfg->debug_flags & DBAZ_DBG_NO_FALLBACK)
+        return set_error(nullptr, DBAZ_EINVAL, "debug_flags: DBAZ_DBG_NO_FALLBACK was removed (the exact-f32 safety net of nn_precision = 1 always runs)");
     if (cfg->eval_round < -1 || cfg->eval_defer_max < 0) return set_error(nullptr, DBAZ_EINVAL, "bad eval_round / eval_defer_max");
     if (cfg->selfplay_pending && cfg->max_pending_evals <= 1) return set_error(nullptr, DBAZ_EINVAL, "selfplay_pending needs max_pending_evals > 1");
     int ndev = 0;
@@ -330,8 +328,8 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     }
     B.first_game = 0;
     B.last_game = 0;
-    e->nns[0] = nn_create(g, e->n_slots * B.kmax, cfg->nn_precision, (cfg->debug_flags & DBAZ_DBG_NO_FALLBACK) != 0);
-    e->nns[1] = nn_create(g, e->n_slots, cfg->nn_precision, (cfg->debug_flags & DBAZ_DBG_NO_FALLBACK) != 0);
+    e->nns[0] = nn_create(g, e->n_slots * B.kmax, cfg->nn_precision);
+    e->nns[1] = nn_create(g, e->n_slots, cfg->nn_precision);
     e->nn = e->nns[0];
     CREATE_HIP(hipStreamSynchronize(e->stream));
     // every slot starts as an idle empty board

@@ -41,7 +41,7 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define CONV_THREADS 512 // 8 waves: two per SIMD, wave = (cout tile, half of the position tiles)
-#define MAXT 13 // position tiles (16 rows each) per workgroup (16x16x32 tiling); the 32x32x16 tiling holds 8 tiles of 32 rows
+#define MAXT 13 // position tiles (16 rows each) per workgroup
 #define MAXROWS 256
 
 struct NNState {
@@ -80,15 +80,9 @@ struct NNState {
     int S = 1, NT = 1, NTT = 7;                 // samples / position tiles per conv workgroup (NTT: compiled tile count)
     int S_small = 0, S_mid = 0, S_big = 0, cus = 256; // tail launches: samples per workgroup of the <2,2> / <4,4> / <5,5> variants (0: unused)
     size_t conv_lds = 0;
-    // f16x3 on the 32x32x16 tiling (k_tower<..., MF = 1>): its own workgroup geometry; S / NTT / conv_lds above then describe the
-    // 16x16 kernels, which remain in use for the exact-f32 fallback launch
-    int want_mf32 = 0, mf32 = 0, S_mf = 0, NT2 = 0, S_mf_tail = 0;
-    size_t conv_lds_mf = 0;
-    // f16x3 on 16x16x32 with two cout tiles per wave (k_tower<64, NT, 0, 1, 2>, 64 channels): 4 tile groups of NT_c2 tiles
-    int want_c2 = 0, c2 = 0, S_c2 = 0, NT_c2 = 0; // (its remainder goes to the one-cout-tile kernels)
+    // f16x3 with two cout tiles per wave (k_tower<64, NT, 0, 1, true>, 64 channels): 4 tile groups of NT_c2 tiles
+    int c2 = 0, S_c2 = 0, NT_c2 = 0; // (its remainder goes to the one-cout-tile kernels)
     int use_rem = 0; // f16x3, NTT == 7: the remainder sizes live in ONE launch (k_tower_rem)
-    bool no_fallback = false; // dbaz_config.debug_flags & DBAZ_DBG_NO_FALLBACK (timing runs only)
-    int variant = 5;          // VAR of the main two-cout-tile launch (conv_lds_h3_c2): 5 = shipped; the debug build selects others
     size_t conv_lds_c2 = 0;
 };
 
@@ -395,40 +389,17 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
 }
 
 // ------------------------------------------------------------------------------------
-// conv_lds_h3 with TWO 16-cout tiles per wave (MF = 2): a wave owns couts [32 (wave & 1), +32) and NTT position tiles of
-// the tile group wave >> 1, so every activation fragment it reads from LDS feeds 6 MFMAs instead of 3 -- half the LDS read
-// bytes per FLOP, fewer issue slots -- at the price of twice the weight stream per wave (four fragments per K-step).
+// conv_lds_h3 with TWO 16-cout tiles per wave: a wave owns couts [32 (wave & 1), +32) and NTT position tiles of the tile
+// group wave >> 1, so every activation fragment it reads from LDS feeds 6 MFMAs instead of 3 -- half the LDS read bytes per
+// FLOP, fewer issue slots -- at the price of four weight fragments per K-step.
 // The kernel is power-bound on real data (bench --zero-weights): not re-reading every other activation fragment
 // (timing experiment, wrong results) bought 6 %.
+//   - the block's residual input stays in f32 registers (res) of the wave that owns those outputs in every layer: no LDS decode
+//   - the layer's weight fragments reach the workgroup ONCE per K-step, by LDS-DMA into a two-slot ring behind the activation
+//     images (each wave fetches one of the step's eight 1-KB fragments), instead of four times into registers: a quarter of
+//     the L2 -> CU weight stream, four more LDS fragment reads and one workgroup barrier per K-step
+// (The alternatives measured against this body are recorded in EXPERIMENTS.md.)
 // ------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ void wpre_load_c2(WPre (&pre)[2], const f32x4 *wpk_layer, int wave, int lane)
-{
-    constexpr int N = 9 * (C / 32);
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const f32x4 *wb = wpk_layer + (size_t)((wave & 1) * 2 + c) * N * 2 * 64 + lane;
-        pre[c].h0 = wb[0];
-        pre[c].l0 = wb[64];
-        pre[c].h1 = wb[128];
-        pre[c].l1 = wb[192];
-    }
-}
-
-// VAR (A/B variants, EXPERIMENTS.md "k_tower, round 3"; the shipped kernel is VAR = 0):
-//   1  the block's residual input stays in f32 registers of the wave that owns those outputs in every layer (no LDS decode)
-//   2  the 16-byte column chunks of an LDS row are XOR-swizzled by (row >> 2) & 3: the epilogue's ds_write_b64 then conflict
-//      2-way instead of 4-way, the fragment reads stay conflict-free
-//   8  waves 4-7 (the younger wave of every SIMD, which loses every arbitration) run at s_setprio 1
-//   4  the layer's weight fragments reach the workgroup ONCE per K-step, by LDS-DMA into a two-slot ring behind the activation
-//      images (each wave fetches one of the step's eight 1-KB fragments), instead of four times into registers: a quarter of
-//      the L2 -> CU weight stream, four more LDS fragment reads and one workgroup barrier per K-step
-#define VAR_RESREG 1
-#define VAR_SWZ 2
-#define VAR_WLDS 4
-#define VAR_PRIO 8
-#define VAR_LO0 16 // timing bound only (wrong results): every lo half zero -- what operand toggling in the two cross-term MFMAs costs
-#define VAR_LO8 32 // the lo halves carry 8 significant bits instead of 11 (3 trailing zero mantissa bits; 19-bit products)
 #define WRING_UNITS 512 // 16-byte units per ring slot: 4 cout tiles x (hi, lo) x 64 lanes
 
 // LDS-DMA of 16 bytes per lane: lane's global source -> lds_dst (wave-uniform LDS byte address) + 16 * lane
@@ -442,12 +413,12 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
 }
-template <int C, int NTT, int VAR = 0>
+template <int C, int NTT>
 __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
                                                const float *__restrict__ bias, float oscale, const int *vm, int rowbase,
                                                int zbase, int W, int R, int wave, int lane, int residual, bool &ovf_out, int tbase,
                                                WPre (&pre)[2], const f32x4 *next_wpk, f32x4 (&res)[2][NTT],
-                                               unsigned long long *stamps = nullptr, f32x4 *wring = nullptr)
+                                               unsigned long long *stamps, f32x4 *wring)
 {
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
     (void)t0; (void)t1; (void)t2; (void)t3; (void)stamps;
@@ -456,6 +427,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     constexpr int KS = C / 32;       // K=32 steps per tap
     constexpr int LO = C / 8;        // unit offset of the lo halves inside a row
     constexpr int N = 9 * KS;        // pipeline steps
+    static_assert(N % 2 == 0, "the next layer's step 0 must land in slot 0");
     const int jrow = lane & 15, gq = lane >> 4;
     const int ct0 = (wave & 1) * 2;
     f32x4 acc[2][NTT];
@@ -463,46 +435,29 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     for (int c = 0; c < 2; c++)
 #pragma unroll
         for (int t = 0; t < NTT; t++) acc[c][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const f32x4 *wb0 = wpk + (size_t)ct0 * N * 2 * 64 + lane;       // packed [ct][step][hi|lo][lane] 16-byte fragments
-    const f32x4 *wb1 = wb0 + (size_t)N * 2 * 64;
-    u128h a_h[2][3], a_l[2][3];
+    // register sets of the weight fragments of steps i (i & 1) and i + 1 ((i + 1) & 1), fed from the LDS ring
+    u128h a_h[2][2], a_l[2][2];
     u128h bh[NTT], bl[NTT];
     const char *sb = reinterpret_cast<const char *>(src4);
     int ab[NTT];
-    // 16-byte unit of this lane's fragment of tile 0 for a tap at row offset offr (the tile constant t*16*S4 is an immediate;
-    // with VAR_SWZ the chunk index gq is XORed with (source row >> 2) & 3, which does not depend on the tile: 16 | tile rows)
-    const int row0 = tbase * 16 + jrow;
-    auto tap_unit = [&](int offr) -> int {
-        if constexpr (VAR & VAR_SWZ) {
-            const int su = row0 + offr;
-            return su * S4 + (gq ^ ((su >> 2) & 3));
-        } else {
-            return rowbase + offr * S4;
-        }
-    };
+    // 16-byte unit of this lane's fragment of tile 0 for a tap at row offset offr (the tile constant t*16*S4 is an immediate)
+    auto tap_unit = [&](int offr) -> int { return rowbase + offr * S4; };
     {
         const int u0 = tap_unit(-W - 1);
 #pragma unroll
         for (int t = 0; t < NTT; t++) ab[t] = ((vm[t] & 1) ? u0 : zbase + (u0 & 15) - t * 16 * S4) * 16;
     }
     STAMP(t0);
-    // VAR_WLDS: this wave's DMA piece of a step = fragment (cout tile wave >> 1, hi | lo = wave & 1); the fragments it consumes are
-    // those of cout tiles ct0, ct0 + 1: ring units (ct * 2 + hl) * 64 + lane of slot (step & 1)
+    // this wave's DMA piece of a step = fragment (cout tile wave >> 1, hi | lo = wave & 1); the fragments it consumes are those
+    // of cout tiles ct0, ct0 + 1: ring units (ct * 2 + hl) * 64 + lane of slot (step & 1)
     const f32x4 *dsrc = wpk + ((size_t)(wave >> 1) * N * 2 + (wave & 1)) * 64 + lane;
     const f32x4 *dnext = next_wpk ? next_wpk + ((size_t)(wave >> 1) * N * 2 + (wave & 1)) * 64 + lane : nullptr;
     const f32x4 *rsrc = wring + (size_t)ct0 * 2 * 64 + lane;
-    unsigned ring_dst = 0;
-    if constexpr (VAR & VAR_WLDS) {
-        static_assert(!(VAR & VAR_WLDS) || N % 2 == 0, "the next layer's step 0 must land in slot 0");
-        ring_dst = __builtin_amdgcn_readfirstlane(lds_addr(wring + (size_t)wave * 64));
-        // step 0's fragments were taken out of slot 0 BEFORE the layer barrier (below / tower_group's prologue): step 0 refills
-        // that slot at once, and a wave late out of the barrier must not find another wave's DMA there
+    const unsigned ring_dst = __builtin_amdgcn_readfirstlane(lds_addr(wring + (size_t)wave * 64));
+    // step 0's fragments were taken out of slot 0 BEFORE the layer barrier (below / tower_group's prologue): step 0 refills
+    // that slot at once, and a wave late out of the barrier must not find another wave's DMA there
 #pragma unroll
-        for (int c = 0; c < 2; c++) { a_h[c][0].f = pre[c].h0; a_l[c][0].f = pre[c].l0; }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 2; c++) { a_h[c][0].f = pre[c].h0; a_l[c][0].f = pre[c].l0; a_h[c][1].f = pre[c].h1; a_l[c][1].f = pre[c].l1; }
-    }
+    for (int c = 0; c < 2; c++) { a_h[c][0].f = pre[c].h0; a_l[c][0].f = pre[c].l0; }
 #pragma unroll
     for (int t = 0; t < NTT; t++) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4);
 #pragma unroll
@@ -510,23 +465,15 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     STAMP(t1);
 #pragma unroll
     for (int i = 0; i < N; i++) {
-        // register set of step i's weight fragments: a 3-deep ring fed from L2, or (VAR_WLDS) two sets fed from the LDS ring
-        const int cur = (VAR & VAR_WLDS) ? (i & 1) : i % 3, nxt = (VAR & VAR_WLDS) ? ((i + 1) & 1) : (i + 2) % 3;
+        const int cur = i & 1, nxt = (i + 1) & 1;
         const int ni = i + 1, ntap = ni / KS, nks = ni % KS;
-        if constexpr (VAR & VAR_WLDS) {
-            // step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the last barrier); behind the
-            // layer's last steps: the first two steps of the next layer
-            if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-            else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-            if (ni < N) { // step i + 1's fragments out of slot (i + 1) & 1 (landed and fenced by the barrier that ended step i - 1)
-                const f32x4 *r1 = rsrc + (size_t)(ni & 1) * WRING_UNITS;
-                a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];
-            }
-        } else if (i + 2 < N) {
-            a_h[0][nxt].f = wb0[(size_t)(i + 2) * 128];
-            a_l[0][nxt].f = wb0[(size_t)(i + 2) * 128 + 64];
-            a_h[1][nxt].f = wb1[(size_t)(i + 2) * 128];
-            a_l[1][nxt].f = wb1[(size_t)(i + 2) * 128 + 64];
+        // step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the last barrier); behind the
+        // layer's last steps: the first two steps of the next layer
+        if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
+        else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
+        if (ni < N) { // step i + 1's fragments out of slot (i + 1) & 1 (landed and fenced by the barrier that ended step i - 1)
+            const f32x4 *r1 = rsrc + (size_t)(ni & 1) * WRING_UNITS;
+            a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];
         }
         __builtin_amdgcn_sched_barrier(0);
         // hi*hi for both cout tiles (the next tap's addresses are computed in their shadow)
@@ -558,14 +505,12 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             if (ni < N) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + nks * 64 + LO * 16);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (VAR & VAR_WLDS) {
-            // end of step i: this wave's DMA piece has landed (vmcnt) and its ring reads of step i + 1 have returned (LDS returns in
-            // order; only the 2 * NTT activation reads issued after them may still be out) -- then every wave's have
-            if (ni < N) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (ni < N) __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        // end of step i: this wave's DMA piece has landed (vmcnt) and its ring reads of step i + 1 have returned (LDS returns in
+        // order; only the 2 * NTT activation reads issued after them may still be out) -- then every wave's have
+        if (ni < N) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (ni < N) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
     }
     STAMP(t2);
     f32x4 bv[2];
@@ -575,9 +520,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         asm volatile("" ::"v"(bv[c]));
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(VAR & VAR_WLDS)) {
-        if (next_wpk) wpre_load_c2<C>(pre, next_wpk, wave, lane);
-    } else if (next_wpk) {
+    if (next_wpk) {
         // the next layer's step 0 (slot 0: DMAed in step N - 2, fenced by that step's barrier) into registers before the layer barrier
         pre[0].h0 = rsrc[0]; pre[0].l0 = rsrc[64]; pre[1].h0 = rsrc[128]; pre[1].l0 = rsrc[192];
     }
@@ -590,41 +533,14 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     float vmax = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        // column (in halves) of this lane's 4 couts inside a row
-        int col = (ct0 + c) * 16 + gq * 4;
-        if constexpr (VAR & VAR_SWZ) col = ((((ct0 + c) * 2 + (gq >> 1)) ^ ((jrow >> 2) & 3)) * 8) + (gq & 1) * 4;
-        u32x2 rh[NTT], rl[NTT];
-        if constexpr (!(VAR & VAR_RESREG)) {
-            if (residual) {
-#pragma unroll
-                for (int t = 0; t < NTT; t++) {
-                    const int row = min((tbase + t) * 16 + jrow, R - 1);
-                    const _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
-                    rh[t] = *reinterpret_cast<const u32x2 *>(ph);
-                    rl[t] = *reinterpret_cast<const u32x2 *>(ph + C);
-                }
-            }
-        }
+        const int col = (ct0 + c) * 16 + gq * 4; // column (in halves) of this lane's 4 couts inside a row
 #pragma unroll
         for (int t = 0; t < NTT; t++) {
             const int row = (tbase + t) * 16 + jrow;
             f32x4 v = acc[c][t] * oscale + bv[c];
-            if (residual) {
-                if constexpr (VAR & VAR_RESREG) {
-                    v += res[c][t];
-                } else {
-                    union { unsigned int u; h2v h; } c0, c1, d0, d1;
-                    c0.u = rh[t][0]; c1.u = rh[t][1]; d0.u = rl[t][0]; d1.u = rl[t][1];
-                    v[0] += (float)c0.h[0] + (float)d0.h[0];
-                    v[1] += (float)c0.h[1] + (float)d0.h[1];
-                    v[2] += (float)c1.h[0] + (float)d1.h[0];
-                    v[3] += (float)c1.h[1] + (float)d1.h[1];
-                }
-            }
+            if (residual) v += res[c][t];
             v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-            if constexpr (VAR & VAR_RESREG) {
-                if (residual) res[c][t] = v; // the block's output = the next block's residual input
-            }
+            if (residual) res[c][t] = v; // the block's output = the next block's residual input
             vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
             union { h2v h[2]; u32x2 u; } oh, ol;
 #pragma unroll
@@ -634,8 +550,6 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
                 oh.h[q] = h;
                 ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f2v), h2v);
             }
-            if constexpr (VAR & VAR_LO0) ol.u = (u32x2){0u, 0u};
-            if constexpr (VAR & VAR_LO8) ol.u &= (u32x2){0xFFF8FFF8u, 0xFFF8FFF8u};
             if (row < R) {
                 _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
                 *reinterpret_cast<u32x2 *>(ph) = oh.u;
@@ -650,327 +564,6 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
 #endif
 }
 
-
-#ifdef DBAZ_DEBUG // A/B record (EXPERIMENTS.md): measured 5.6 % slower per evaluation than the shipped 8-wave kernel
-// ------------------------------------------------------------------------------------
-// MF = 3: FOUR waves per workgroup, one per SIMD with the whole register file; a wave owns all four cout tiles of a quarter of
-// the position tiles (NTT tiles): 16 accumulator tiles, 48 MFMAs per K-step.  An activation fragment then feeds 12 MFMAs and a
-// weight fragment (out of the LDS ring) 12 as well: 16 ds_read_b128 per 48 MFMAs against 12 per 24 in conv_lds_h3_c2 -- a third
-// fewer LDS fragment reads per FLOP (the kernel is power-bound: EXPERIMENTS.md).  The weight ring, the register-resident residual
-// stream and the rounding are conv_lds_h3_c2's (bit-identical results).
-// ------------------------------------------------------------------------------------
-template <int C, int NTT>
-__device__ __forceinline__ void conv_lds_h3_w4(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
-                                               const float *__restrict__ bias, float oscale, const int *vm, int zbase, int W, int R,
-                                               int wave, int lane, int residual, bool &ovf_out, int tbase, f32x4 (&pre)[8],
-                                               const f32x4 *next_wpk, f32x4 (&res)[4][NTT], f32x4 *wring)
-{
-    static_assert(C == 64, "four cout tiles per wave = 64 channels");
-    constexpr int S4 = (C + 8) / 4, KS = C / 32, LO = C / 8, N = 9 * KS;
-    static_assert(N % 2 == 0, "the next layer's step 0 must land in slot 0");
-    const int jrow = lane & 15, gq = lane >> 4;
-    f32x4 acc[4][NTT];
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-        for (int t = 0; t < NTT; t++) acc[c][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    u128h a[2][8]; // [register set][cout tile * 2 + (hi | lo)]
-    u128h bh[NTT], bl[NTT];
-    const char *sb = reinterpret_cast<const char *>(src4);
-    int ab[NTT];
-    const int rowbase = (tbase * 16 + jrow) * S4 + gq;
-    {
-        const int u0 = rowbase + (-W - 1) * S4;
-#pragma unroll
-        for (int t = 0; t < NTT; t++) ab[t] = ((vm[t] & 1) ? u0 : zbase + (u0 & 15) - t * 16 * S4) * 16;
-    }
-    // this wave's two DMA pieces of a step: the (hi, lo) fragments of cout tile `wave` (ring units (2 wave + hl) * 64 + lane)
-    const f32x4 *dsrc = wpk + (size_t)wave * N * 2 * 64 + lane;
-    const f32x4 *dnext = next_wpk ? next_wpk + (size_t)wave * N * 2 * 64 + lane : nullptr;
-    const unsigned ring_dst = __builtin_amdgcn_readfirstlane(lds_addr(wring + (size_t)wave * 2 * 64));
-    const f32x4 *rsrc = wring + lane;
-#pragma unroll
-    for (int c = 0; c < 8; c++) a[0][c].f = pre[c]; // step 0: taken out of slot 0 before the layer barrier
-#pragma unroll
-    for (int t = 0; t < NTT; t++) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4);
-#pragma unroll
-    for (int t = 0; t < NTT; t++) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + LO * 16);
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        const int cur = i & 1, nxt = cur ^ 1;
-        const int ni = i + 1, ntap = ni / KS, nks = ni % KS;
-        // step i + 2's pieces -> slot i & 1 (every wave took step i's fragments out of it before the last barrier)
-        if (i + 2 < N) {
-            glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-            glds16(dsrc + (size_t)(i + 2) * 128 + 64, ring_dst + (i & 1) * (WRING_UNITS * 16) + 1024);
-        } else if (dnext) {
-            glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-            glds16(dnext + (size_t)(i + 2 - N) * 128 + 64, ring_dst + (i & 1) * (WRING_UNITS * 16) + 1024);
-        }
-        if (ni < N) { // step i + 1's eight fragments out of slot (i + 1) & 1: at the head of the step, long back when the
-                      // activation reloads of this step are issued (lgkmcnt is a 4-bit counter)
-            const f32x4 *r1 = rsrc + (size_t)(ni & 1) * WRING_UNITS;
-#pragma unroll
-            for (int c = 0; c < 8; c++) a[nxt][c].f = r1[c * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // hi*hi
-#pragma unroll
-        for (int t = 0; t < NTT; t++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[cur][2 * c].h, bh[t].h, acc[c][t], 0, 0, 0);
-        if (ni < N && nks == 0) {
-            const int un = rowbase + ((ntap / 3 - 1) * W + (ntap % 3 - 1)) * S4;
-            const int zt = zbase + (un & 15);
-#pragma unroll
-            for (int t = 0; t < NTT; t++) ab[t] = (((vm[t] >> ntap) & 1) ? un : zt - t * 16 * S4) * 16;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // lo*hi; bh[t] is dead after its fourth MFMA -> reload it for the next step right there
-#pragma unroll
-        for (int t = 0; t < NTT; t++) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[cur][2 * c + 1].h, bh[t].h, acc[c][t], 0, 0, 0);
-            if (ni < N) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + nks * 64);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // hi*lo; same for bl[t]
-#pragma unroll
-        for (int t = 0; t < NTT; t++) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[cur][2 * c].h, bl[t].h, acc[c][t], 0, 0, 0);
-            if (ni < N) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + nks * 64 + LO * 16);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // end of step: this wave's DMA pieces have landed, its ring reads have returned (only the 2 NTT activation reloads issued
-        // after them may still be out) -- then every wave's have
-        if (ni < N) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
-            __builtin_amdgcn_s_barrier();
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    f32x4 bv[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        bv[c] = *reinterpret_cast<const f32x4 *>(bias + c * 16 + gq * 4);
-        asm volatile("" ::"v"(bv[c]));
-    }
-    if (next_wpk) { // the next layer's step 0 (slot 0: DMAed in step N - 2, fenced by that step's barrier) before the layer barrier
-#pragma unroll
-        for (int c = 0; c < 8; c++) pre[c] = rsrc[c * 64];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    float vmax = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int col = c * 16 + gq * 4;
-#pragma unroll
-        for (int t = 0; t < NTT; t++) {
-            const int row = (tbase + t) * 16 + jrow;
-            f32x4 v = acc[c][t] * oscale + bv[c];
-            if (residual) v += res[c][t];
-            v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-            if (residual) res[c][t] = v;
-            vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-            union { h2v h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const f2v x = {v[2 * q], v[2 * q + 1]};
-                const h2v h = __builtin_convertvector(x, h2v);
-                oh.h[q] = h;
-                ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f2v), h2v);
-            }
-            if (row < R) {
-                _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
-                *reinterpret_cast<u32x2 *>(ph) = oh.u;
-                *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
-            }
-        }
-    }
-    ovf_out |= vmax > F16_GUARD;
-}
-
-#endif // DBAZ_DEBUG (conv_lds_h3_w4)
-
-#ifdef DBAZ_DEBUG // A/B tiling of the debug build (tools/ab_tilings.sh); measured 2.4 % slower per evaluation (EXPERIMENTS.md)
-// ------------------------------------------------------------------------------------
-// The same f16x3 layer on v_mfma_f32_32x32x16_f16 (MF = 1).  Output tile = 32 couts x 32 positions: a wave owns one
-// 32-cout tile (wave & 1) and NTT position tiles of 32 rows (tile group wave >> 1); per K=16 step it needs ONE weight
-// fragment pair for 3 * NTT MFMAs of 32 cycles each, and every activation fragment feeds twice the MACs of the 16x16x32
-// tiling -- half the LDS read bytes and half the vector-issue slots per FLOP (the 16x16x32 form holds the issue port
-// for 8 of its 16 cycles, this one for 8 of 32).  LDS rows are [C hi | C lo | 16 B pad] = C + 4 dwords: with 17 units
-// of 16 B per row the 32 rows of a fragment fall on distinct bank slots inside every 16-lane group of ds_read_b128.
-// Lane map (cdna_hip_programming.md 3): lane l, r = l & 31, h = l >> 5: A[cout r][k = 8h + j], B[k = 8h + j][pos r];
-// D: pos = l & 31, cout = (reg & 3) + 8 (reg >> 2) + 4 h.
-// ------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int C>
-__device__ __forceinline__ void wpre_load32(WPre &pre, const f32x4 *wpk_layer, int wave, int lane)
-{
-    constexpr int N = 9 * (C / 16);
-    const f32x4 *wb = wpk_layer + (size_t)(wave & 1) * N * 2 * 64 + lane;
-    pre.h0 = wb[0];
-    pre.l0 = wb[64];
-    pre.h1 = wb[128];
-    pre.l1 = wb[192];
-}
-
-template <int C, int NTT>
-__device__ __forceinline__ void conv_lds_h3_32(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
-                                               const float *__restrict__ bias, float oscale, const int *vm, int rowbase,
-                                               int zbase, int W, int R, int wave, int lane, int residual, bool &ovf_out, int tbase,
-                                               WPre &pre, const f32x4 *next_wpk, unsigned long long *stamps = nullptr)
-{
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    (void)t0; (void)t1; (void)t2; (void)t3; (void)stamps;
-    constexpr int S4 = (C + 4) / 4;  // 16-byte units per LDS row
-    constexpr int KS = C / 16;       // K=16 steps per tap
-    constexpr int LO = C / 8;        // unit offset of the lo halves inside a row
-    constexpr int N = 9 * KS;        // pipeline steps per cout tile
-    const int jrow = lane & 31, gq = lane >> 5;
-    bool ovf = false;
-    for (int ct = wave & 1; ct < C / 32; ct += 2) {
-        f32x16 acc[NTT];
-#pragma unroll
-        for (int t = 0; t < NTT; t++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
-        const f32x4 *wbase = wpk + (size_t)ct * N * 2 * 64 + lane; // packed [ct][step][hi|lo][lane] 16-byte fragments
-        u128h a_h[3], a_l[3];
-        u128h bh[NTT], bl[NTT];
-        const char *sb = reinterpret_cast<const char *>(src4);
-        int ab[NTT]; // BYTE address of this lane's fragment for the current tap (tile constant folded out)
-#pragma unroll
-        for (int t = 0; t < NTT; t++)
-            ab[t] = ((vm[t] & 1) ? rowbase + (-W - 1) * S4 : zbase + ((rowbase + (-W - 1) * S4) & 15) - t * 32 * S4) * 16;
-        STAMP(t0);
-        if (ct == (wave & 1)) { // first cout tile of the layer: fragments were prefetched across the barrier
-            a_h[0].f = pre.h0; a_l[0].f = pre.l0; a_h[1].f = pre.h1; a_l[1].f = pre.l1;
-        } else {
-            a_h[0].f = wbase[0];
-            a_l[0].f = wbase[64];
-            a_h[1].f = wbase[128];
-            a_l[1].f = wbase[192];
-        }
-#pragma unroll
-        for (int t = 0; t < NTT; t++) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 512 * S4);
-#pragma unroll
-        for (int t = 0; t < NTT; t++) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 512 * S4 + LO * 16);
-        STAMP(t1);
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            const int cur = i % 3, nxt = (i + 2) % 3;
-            const int ni = i + 1, ntap = ni / KS, nks = ni % KS;
-            if (i + 2 < N) {
-                a_h[nxt].f = wbase[(size_t)(i + 2) * 128];
-                a_l[nxt].f = wbase[(size_t)(i + 2) * 128 + 64];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // G1: hi*hi (the next tap's addresses are computed in its shadow)
-#pragma unroll
-            for (int t = 0; t < NTT; t++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[cur].h, bh[t].h, acc[t], 0, 0, 0);
-            if (ni < N && nks == 0) {
-                const int off = ((ntap / 3 - 1) * W + (ntap % 3 - 1)) * S4;
-                const int zt = zbase + ((rowbase + off) & 15);
-#pragma unroll
-                for (int t = 0; t < NTT; t++) ab[t] = (((vm[t] >> ntap) & 1) ? rowbase + off : zt - t * 32 * S4) * 16;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // G3: lo*hi; bh[t] is dead after its MFMA -> reload it for the next step right there
-#pragma unroll
-            for (int t = 0; t < NTT; t++) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_l[cur].h, bh[t].h, acc[t], 0, 0, 0);
-                if (ni < N) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 512 * S4 + nks * 32);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // G2: hi*lo; same for bl[t]
-#pragma unroll
-            for (int t = 0; t < NTT; t++) {
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_h[cur].h, bl[t].h, acc[t], 0, 0, 0);
-                if (ni < N) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 512 * S4 + nks * 32 + LO * 16);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        STAMP(t2);
-        // bias before the cross-barrier weight prefetch (loads return in order)
-        f32x4 bv[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            bv[q] = *reinterpret_cast<const f32x4 *>(bias + ct * 32 + 8 * q + 4 * gq);
-            asm volatile("" ::"v"(bv[q]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (next_wpk && ct + 2 >= C / 32) wpre_load32<C>(pre, next_wpk, wave, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- epilogue: this lane holds, of position row (tbase + t) * 32 + jrow, the couts ct*32 + 8q + 4gq .. +3 (q = 0..3)
-        _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
-        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-        typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        u32x2 rh[NTT][4], rl[NTT][4];
-        if (residual) {
-#pragma unroll
-            for (int t = 0; t < NTT; t++) {
-                const int row = min((tbase + t) * 32 + jrow, R - 1);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const _Float16 *ph = dsth + (size_t)row * (S4 * 8) + ct * 32 + 8 * q + 4 * gq;
-                    rh[t][q] = *reinterpret_cast<const u32x2 *>(ph);
-                    rl[t][q] = *reinterpret_cast<const u32x2 *>(ph + C);
-                }
-            }
-        }
-        float vmax = 0.0f;
-#pragma unroll
-        for (int t = 0; t < NTT; t++) {
-            const int row = (tbase + t) * 32 + jrow;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                f32x4 v = (f32x4){acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]} * oscale + bv[q];
-                if (residual) {
-                    union { unsigned int u; h2v h; } c0, c1, d0, d1;
-                    c0.u = rh[t][q][0]; c1.u = rh[t][q][1]; d0.u = rl[t][q][0]; d1.u = rl[t][q][1];
-                    v[0] += (float)c0.h[0] + (float)d0.h[0];
-                    v[1] += (float)c0.h[1] + (float)d0.h[1];
-                    v[2] += (float)c1.h[0] + (float)d1.h[0];
-                    v[3] += (float)c1.h[1] + (float)d1.h[1];
-                }
-                v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-                union { h2v h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-                for (int e = 0; e < 2; e++) {
-                    const f2v x = {v[2 * e], v[2 * e + 1]};
-                    const h2v h = __builtin_convertvector(x, h2v);
-                    oh.h[e] = h;
-                    ol.h[e] = __builtin_convertvector(x - __builtin_convertvector(h, f2v), h2v);
-                }
-                if (row < R) {
-                    _Float16 *ph = dsth + (size_t)row * (S4 * 8) + ct * 32 + 8 * q + 4 * gq;
-                    *reinterpret_cast<u32x2 *>(ph) = oh.u;
-                    *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
-                }
-            }
-        }
-        ovf |= vmax > F16_GUARD;
-        STAMP(t3);
-#ifdef DBAZ_STAMP
-        if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; }
-#endif
-    }
-    ovf_out |= ovf;
-}
-
-#endif // DBAZ_DEBUG
-
 // ------------------------------------------------------------------------------------
 // The whole convolutional trunk in ONE launch per step.  A workgroup owns S samples; their
 // activations live in two ping-pong LDS images of (S*HW+1) rows x (C+8) dwords for
@@ -982,37 +575,29 @@ __device__ __forceinline__ void conv_lds_h3_32(const f32x4 *__restrict__ src4, f
 // from L2.  PREC 0: exact f32 (rows hold C floats); PREC 1: f16x3 (rows hold C hi + C lo halves
 // of the activation scaled by 2^ACT_SHIFT).
 // ------------------------------------------------------------------------------------
-// index (in halves) of channel c inside the hi part of LDS row `row` (VAR_SWZ: 16-byte chunks XORed with (row >> 2) & 3)
-template <int SWZ>
-__device__ __forceinline__ int act_col(int row, int c)
-{
-    if constexpr (SWZ) return (((c >> 3) ^ ((row >> 2) & 3)) << 3) | (c & 7);
-    else return c;
-}
-template <int C, int PREC, int STRIDE = C + 8, int SWZ = 0>
+// channel c of LDS row `row` (rows of C + 8 dwords): PREC 0 a float, PREC 1 the (hi, lo) halves at c and C + c
+template <int C, int PREC>
 __device__ __forceinline__ void act_store(float *lds, int row, int c, float v, bool &ovf)
 {
     if constexpr (PREC == 0) {
-        lds[row * STRIDE + c] = v;
+        lds[row * (C + 8) + c] = v;
     } else {
-        _Float16 *h = reinterpret_cast<_Float16 *>(lds) + (size_t)row * (STRIDE * 2);
+        _Float16 *h = reinterpret_cast<_Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
         const float x = v * ACT_SCALE;
         ovf |= fabsf(x) > F16_GUARD;
         const _Float16 hi = (_Float16)x;
-        const int cc = act_col<SWZ>(row, c);
-        h[cc] = hi;
-        h[C + cc] = (_Float16)(x - (float)hi);
+        h[c] = hi;
+        h[C + c] = (_Float16)(x - (float)hi);
     }
 }
-template <int C, int PREC, int STRIDE = C + 8, int SWZ = 0>
+template <int C, int PREC>
 __device__ __forceinline__ float act_load(const float *lds, int row, int c)
 {
     if constexpr (PREC == 0) {
-        return lds[row * STRIDE + c];
+        return lds[row * (C + 8) + c];
     } else {
-        const _Float16 *h = reinterpret_cast<const _Float16 *>(lds) + (size_t)row * (STRIDE * 2);
-        const int cc = act_col<SWZ>(row, c);
-        return ((float)h[cc] + (float)h[C + cc]) * (1.0f / ACT_SCALE);
+        const _Float16 *h = reinterpret_cast<const _Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
+        return ((float)h[c] + (float)h[C + c]) * (1.0f / ACT_SCALE);
     }
 }
 
@@ -1118,16 +703,15 @@ __device__ __forceinline__ void head_fc_fused(const Geo &g, const TowerArgs &a, 
 }
 
 // the S samples [s0, s0 + ns) of one workgroup through the whole trunk
-template <int C, int NTA, int NTB, int PREC, int MF, int VAR = 0>
+// C2: a wave = two cout tiles x a quarter of the position tiles (conv_lds_h3_c2: f16x3, 64 channels, register residual, LDS
+//     weight ring); otherwise a wave = one cout tile x half of the position tiles (conv_lds_f32 / conv_lds_h3)
+// RR: the one-cout-tile f16x3 body keeps the residual stream in registers (k_tower_rem beside a C2 main launch)
+template <int C, int NTA, int NTB, int PREC, bool C2 = false, bool RR = false>
 __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, float *lds, const int S, const int s0, const int ns)
 {
-    static_assert(MF == 0 || PREC == 1, "the alternative tilings exist for the f16x3 mode only");
-    static_assert(VAR == 0 || MF >= 2 || (MF == 0 && VAR == VAR_RESREG), "the A/B variants belong to the two-cout-tile kernel");
-    constexpr int SWZ = (VAR & VAR_SWZ) ? 1 : 0;
-    // MF: 0 = 16x16x32, a wave = one cout tile x half of the position tiles; 1 = 32x32x16; 2 = 16x16x32, a wave = two cout
-    // tiles x a quarter of the position tiles (conv_lds_h3_c2)
-    constexpr int STRIDE = MF == 1 ? C + 4 : C + 8; // dwords per LDS row (see conv_lds_h3_32 for the 32x32x16 tiling's choice)
-    constexpr int S4 = STRIDE / 4;
+    static_assert(!C2 || (PREC == 1 && NTB == 0 && !RR), "the two-cout-tile body is f16x3 with its own residual stream");
+    static_assert(!RR || PREC == 1, "the register residual belongs to the f16x3 body");
+    constexpr int S4 = (C + 8) / 4; // 16-byte units per LDS row
     const int HW = g.HW, W = g.W, H = g.H;
     const int R = ns * HW;           // valid rows in this workgroup
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NTHR = blockDim.x;
@@ -1245,8 +829,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                             ol.h[q] = __builtin_convertvector(xx - __builtin_convertvector(hh, f2v), h2v);
                         }
                         if (row < R) {
-                            int col = cto * 16 + gg * 4;
-                            if constexpr (SWZ) col = (((cto * 2 + (gg >> 1)) ^ ((jr >> 2) & 3)) * 8) + (gg & 1) * 4;
+                            const int col = cto * 16 + gg * 4;
                             _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
                             *reinterpret_cast<u32x2 *>(ph) = oh.u;
                             *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
@@ -1274,7 +857,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
 #pragma unroll
                 for (int k = 0; k < 27; k++) acc += in27[k] * *reinterpret_cast<const f32x4 *>(wl + k * C + co);
 #pragma unroll
-                for (int e = 0; e < 4; e++) act_store<C, PREC, STRIDE, SWZ>(X, row, co + e, fmaxf(acc[e], 0.0f), ovf);
+                for (int e = 0; e < 4; e++) act_store<C, PREC>(X, row, co + e, fmaxf(acc[e], 0.0f), ovf);
             }
         }
         }
@@ -1285,22 +868,17 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         }
     }
     __syncthreads();
-    // position-tile rows / lane map of the layer MFMA: 16x16x32 (row = lane & 15, k quarter = lane >> 4) or
-    // 32x32x16 (row = lane & 31, k half = lane >> 5)
-    constexpr int TR = MF == 1 ? 32 : 16;
-    const int jrow = lane & (TR - 1), gq = MF == 1 ? (lane >> 5) : (lane >> 4);
+    // position-tile rows / lane map of the layer MFMA (16x16x32): row = lane & 15, k quarter = lane >> 4
+    const int jrow = lane & 15, gq = lane >> 4;
     // per position tile: 9-bit mask of the taps whose source pixel lies inside the image
-    // 16x16x32: waves 0-3 own position tiles [0, NTA), waves 4-7 tiles [NTA, NTA+NTB)
-    // 32x32x16: the wave pair (wave >> 1) owns tiles [(wave >> 1) * NTA, +NTA), one 32-cout tile each
-    //           (NTB > 0: the older wave half takes NTA tiles per wave, the younger NTB -- tools/ab_mf32.sh)
+    // one cout tile per wave: waves 0-3 own position tiles [0, NTA), waves 4-7 tiles [NTA, NTA+NTB)
+    // C2: the wave pair (wave >> 1) owns tiles [(wave >> 1) * NTA, +NTA)
     const bool first = wave < 4;
-    const int tbase = MF == 3 ? wave * NTA // (four waves, a quarter of the position tiles each)
-                    : MF ? (NTB > 0 ? (first ? ((wave >> 1) & 1) * NTA : 2 * NTA + ((wave >> 1) & 1) * NTB) : (wave >> 1) * NTA)
-                         : (first ? 0 : NTA);
+    const int tbase = C2 ? (wave >> 1) * NTA : (first ? 0 : NTA);
     int vm[NTA];
 #pragma unroll
     for (int t = 0; t < NTA; t++) {
-        int row = (tbase + t) * TR + jrow;
+        int row = (tbase + t) * 16 + jrow;
         int pos = row % HW, y = pos / W, x = pos - y * W;
         int m = 0;
 #pragma unroll
@@ -1310,7 +888,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         }
         vm[t] = row < R ? m : 0;
     }
-    const int rowbase = (tbase * TR + jrow) * S4 + gq;
+    const int rowbase = (tbase * 16 + jrow) * S4 + gq;
     const int zbase = zu; // multiple of 16 units; the per-lane slot is added per tap
     if constexpr (PREC == 0) {
         const size_t wl = (size_t)C * C * 9;
@@ -1325,23 +903,18 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         const f32x4 *tw4 = reinterpret_cast<const f32x4 *>(a.tw);
         const size_t wl = (size_t)C * C * 9 * 2 * 2 / 16; // 16-byte units per layer (hi + lo halves)
         const int NL = 2 * a.nblocks;
-        WPre pre;
-        WPre pre2[2];
+        WPre pre;    // one cout tile per wave: the first two weight steps of the next layer
+        WPre pre2[2]; // C2: step 0 of the next layer's two cout tiles, out of the weight ring
         (void)pre2;
-        if (NL > 0) {
-            if constexpr (MF == 3) { }
-            else if constexpr (MF == 2) { if constexpr (!(VAR & VAR_WLDS)) wpre_load_c2<C>(pre2, tw4, wave, lane); }
-#ifdef DBAZ_DEBUG
-            else if constexpr (MF == 1) wpre_load32<C>(pre, tw4, wave, lane);
-#endif
-            else wpre_load<C>(pre, tw4, wave, lane);
+        if constexpr (!C2) {
+            if (NL > 0) wpre_load<C>(pre, tw4, wave, lane);
         }
         unsigned long long stamps[4] = {0, 0, 0, 0};
         unsigned long long tb0 = 0, tb1 = 0, tk0 = 0, tk1 = 0;
         (void)tb0; (void)tb1; (void)tk0; (void)tk1;
         f32x4 res[2][NTA]; // the residual stream of this wave's outputs (activation-scaled f32): conv_lds_h3_c2 / conv_lds_h3
         (void)res;
-        if constexpr (MF == 0 && PREC == 1 && (VAR & VAR_RESREG) != 0) {
+        if constexpr (RR) {
             // block 0's input = conv0's output, which other waves wrote: decode this wave's share once (one cout tile, wave & 3)
             const _Float16 *xh = reinterpret_cast<const _Float16 *>(X4);
             const int ctc = wave & 3;
@@ -1355,14 +928,13 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                 }
             }
         }
-        if constexpr (MF == 2 && (VAR & VAR_RESREG) != 0) {
+        f32x4 *wring = nullptr; // C2: two-slot weight ring behind the two activation images
+        if constexpr (C2) {
             // block 0's input = conv0's output, which other waves wrote: decode this wave's share once
             const _Float16 *xh = reinterpret_cast<const _Float16 *>(X4);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                const int ctc = (wave & 1) * 2 + c;
-                int col = ctc * 16 + gq * 4;
-                if constexpr (SWZ) col = (((ctc * 2 + (gq >> 1)) ^ ((jrow >> 2) & 3)) * 8) + (gq & 1) * 4;
+                const int col = ((wave & 1) * 2 + c) * 16 + gq * 4;
 #pragma unroll
                 for (int t = 0; t < NTA; t++) {
                     const int row = min((tbase + t) * 16 + jrow, R - 1);
@@ -1371,39 +943,6 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                     for (int e = 0; e < 4; e++) res[c][t][e] = (float)ph[e] + (float)ph[C + e];
                 }
             }
-        }
-        f32x4 *wring = nullptr; // VAR_WLDS: two-slot weight ring behind the two activation images
-        f32x4 pre8[8];          // MF = 3: the eight weight fragments of a layer's step 0
-        f32x4 res4[4][NTA];     // MF = 3: residual stream of the wave's 4 x NTA output tiles
-        (void)pre8; (void)res4;
-        if constexpr (MF == 3) {
-            wring = Y4 + img_units;
-            if (NL > 0) {
-                const f32x4 *d0 = tw4 + (size_t)wave * (9 * (C / 32)) * 2 * 64 + lane;
-                const unsigned dst = __builtin_amdgcn_readfirstlane(lds_addr(wring + (size_t)wave * 2 * 64));
-                glds16(d0, dst);
-                glds16(d0 + 64, dst + 1024);
-                glds16(d0 + 128, dst + WRING_UNITS * 16);
-                glds16(d0 + 128 + 64, dst + WRING_UNITS * 16 + 1024);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __syncthreads();
-#pragma unroll
-            for (int c = 0; c < 8; c++) pre8[c] = wring[c * 64 + lane];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __syncthreads();
-            const _Float16 *xh = reinterpret_cast<const _Float16 *>(X4);
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-#pragma unroll
-                for (int t = 0; t < NTA; t++) {
-                    const int row = min((tbase + t) * 16 + jrow, R - 1);
-                    const _Float16 *ph = xh + (size_t)row * (S4 * 8) + c * 16 + gq * 4;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) res4[c][t][e] = (float)ph[e] + (float)ph[C + e];
-                }
-        }
-        if constexpr (MF == 2 && (VAR & VAR_WLDS) != 0) {
             wring = Y4 + img_units;
             if (NL > 0) {
                 const f32x4 *d0 = tw4 + ((size_t)(wave >> 1) * (9 * (C / 32)) * 2 + (wave & 1)) * 64 + lane;
@@ -1420,31 +959,15 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
             }
             __syncthreads();
         }
-        if constexpr ((VAR & VAR_PRIO) != 0) {
-            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-        }
         STAMP(tk0);
         tL0 = tk0;
         for (int l = 0; l < NL; l++) {
             const f32x4 *src = (l & 1) ? Y4 : X4;
             f32x4 *dst = (l & 1) ? X4 : Y4;
             const f32x4 *nxt = l + 1 < NL ? tw4 + (size_t)(l + 1) * wl : nullptr;
-#ifdef DBAZ_DEBUG
-            if constexpr (MF == 3) {
-                conv_lds_h3_w4<C, NTA>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre8, nxt, res4, wring);
-            } else
-#endif
-            if constexpr (MF == 2) {
-                conv_lds_h3_c2<C, NTA, VAR>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre2, nxt, res, stamps, wring);
-#ifdef DBAZ_DEBUG
-            } else if constexpr (MF && NTB > 0) {
-                if (first) conv_lds_h3_32<C, NTA>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre, nxt, stamps);
-                else conv_lds_h3_32<C, NTB>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre, nxt, stamps);
-            } else if constexpr (MF) {
-                conv_lds_h3_32<C, NTA>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre, nxt, stamps);
-#endif
+            if constexpr (C2) {
+                conv_lds_h3_c2<C, NTA>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre2, nxt, res, stamps, wring);
             } else {
-                constexpr bool RR = (VAR & VAR_RESREG) != 0;
                 if (first) conv_lds_h3<C, NTA, RR>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, nullptr, nullptr, pre, nxt, res[0], stamps);
                 else if constexpr (NTB > 0) conv_lds_h3<C, NTB, RR>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, nullptr, nullptr, pre, nxt, reinterpret_cast<f32x4(&)[NTB]>(res[0]), stamps);
             }
@@ -1455,7 +978,6 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
             stamps[3] += tb1 - tb0;
 #endif
         }
-        if constexpr ((VAR & VAR_PRIO) != 0) __builtin_amdgcn_s_setprio(0);
 #ifdef DBAZ_STAMP
         STAMP(tk1);
         tL1 = tk1;
@@ -1488,7 +1010,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
             for (int t = grp; t < NT; t += ngrp) {
                 const int row = t * 16 + hj;
                 const int rr = min(row, R - 1);
-                const f32x4 *bp = X4 + (size_t)rr * S4 + (SWZ ? (hq ^ ((rr >> 2) & 3)) : hq);
+                const f32x4 *bp = X4 + (size_t)rr * S4 + hq;
                 f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < KS; ks++) {
@@ -1530,7 +1052,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
             const int row = tid;
             float xr[C];
 #pragma unroll
-            for (int c = 0; c < C; c++) xr[c] = act_load<C, PREC, STRIDE, SWZ>(X, row, c);
+            for (int c = 0; c < C; c++) xr[c] = act_load<C, PREC>(X, row, c);
             const int sidx = row / HW, p = row - sidx * HW;
             for (int oc = 0; oc < OC; oc++) {
                 float acc = a.hb[oc];
@@ -1579,8 +1101,8 @@ __device__ __forceinline__ int tower_split(const TowerArgs &a, int n, int &n_ful
     return 0;
 }
 
-template <int C, int NTA, int NTB, int PREC, int MF = 0, int VAR = 0>
-__global__ void __launch_bounds__(MF == 3 ? 256 : CONV_THREADS, 1) k_tower(Geo g, TowerArgs a)
+template <int C, int NTA, int NTB, int PREC, bool C2 = false>
+__global__ void __launch_bounds__(CONV_THREADS, 1) k_tower(Geo g, TowerArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int n = cut_n(*a.n_dev, a.cut_round, a.cut_defer);
@@ -1628,7 +1150,7 @@ __global__ void __launch_bounds__(MF == 3 ? 256 : CONV_THREADS, 1) k_tower(Geo g
             const int nr = n_redo;
             for (int r = 0; r < nr; r++) {
                 const int s0 = redo_grp[r] * S;
-                tower_group<C, NTA, NTB, PREC, MF, VAR>(g, a, lds, S, s0, min(S, n - s0));
+                tower_group<C, NTA, NTB, PREC, C2>(g, a, lds, S, s0, min(S, n - s0));
                 __syncthreads();
             }
             return;
@@ -1637,13 +1159,13 @@ __global__ void __launch_bounds__(MF == 3 ? 256 : CONV_THREADS, 1) k_tower(Geo g
     if (a.n_used && a.role == 0 && !a.fallback && blockIdx.x == 0 && threadIdx.x == 0) *a.n_used = n;
     const int s0 = first_sample + blockIdx.x * S;
     if (s0 >= limit) return;
-    tower_group<C, NTA, NTB, PREC, MF, VAR>(g, a, lds, S, s0, min(S, limit - s0));
+    tower_group<C, NTA, NTB, PREC, C2>(g, a, lds, S, s0, min(S, limit - s0));
 }
 
 // The remainder of a batch in ONE launch (f16x3, one-cout-tile tiling): the workgroups pick the size the split asks for --
 // <2,2> / <4,4> / <5,5> / <7,6> tiles per wave half, S_small / S_mid / S_big / S_huge samples -- instead of four launches of
 // which three leave at once (5 us each: 1 % of a 6x6 step, 4 % of a 3x3 step).
-template <int C, int RR = 0>
+template <int C, bool RR = false>
 __global__ void __launch_bounds__(CONV_THREADS, 1) k_tower_rem(Geo g, TowerArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1655,13 +1177,13 @@ __global__ void __launch_bounds__(CONV_THREADS, 1) k_tower_rem(Geo g, TowerArgs 
     const int s0 = n_full + blockIdx.x * S;
     if (s0 >= n) return;
     const int ns = min(S, n - s0);
-    // RR = 1: the bodies beside a two-cout-tile main launch keep the residual stream in registers like it (the 7-tile body then
+    // RR: the bodies beside a two-cout-tile main launch keep the residual stream in registers like it (the 7-tile body then
     // spills 28 registers around its main loop: +2 % on that body, which as a remainder round still beats a partial round of the
-    // main launch by 8 %; where the 7-tile body IS the main launch -- 9x9 -- every body of the geometry stays RR = 0)
-    if (mode == 1) tower_group<C, 2, 2, 1, 0, RR>(g, a, lds, S, s0, ns);
-    else if (mode == 2) tower_group<C, 4, 4, 1, 0, RR>(g, a, lds, S, s0, ns);
-    else if (mode == 3) tower_group<C, 5, 5, 1, 0, RR>(g, a, lds, S, s0, ns);
-    else tower_group<C, 7, 6, 1, 0, RR>(g, a, lds, S, s0, ns);
+    // main launch by 8 %; where the 7-tile body IS the main launch -- 9x9 -- every body of the geometry stays !RR)
+    if (mode == 1) tower_group<C, 2, 2, 1, false, RR>(g, a, lds, S, s0, ns);
+    else if (mode == 2) tower_group<C, 4, 4, 1, false, RR>(g, a, lds, S, s0, ns);
+    else if (mode == 3) tower_group<C, 5, 5, 1, false, RR>(g, a, lds, S, s0, ns);
+    else tower_group<C, 7, 6, 1, false, RR>(g, a, lds, S, s0, ns);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2010,28 +1532,13 @@ static T *nn_upload(NNState *nn, const std::vector<T> &h)
     return d;
 }
 
-NNState *nn_create(const Geo &g, int max_batch, int precision, bool no_fallback)
+// precision: 0 = exact f32, 1 = f16x3 (two cout tiles per wave for 64-channel networks, one otherwise)
+NNState *nn_create(const Geo &g, int max_batch, int precision)
 {
     NNState *nn = new NNState();
     nn->g = g;
     nn->max_batch = max_batch;
-    nn->no_fallback = no_fallback;
-    nn->precision = precision >= 1 ? 1 : 0;
-    // 1 = f16x3 on the default tiling (two cout tiles per wave for 64-channel networks, one otherwise)
-    nn->want_c2 = precision == 1;
-#ifdef DBAZ_DEBUG
-    // A/B tilings (debug build): 2 = the arithmetic of 1 on the 32x32x16 MFMA; 3 / 4 = two / one cout tile(s) per wave explicitly
-    // (1, 3 and 4 give bit-identical results)
-    nn->want_mf32 = precision == 2;
-    nn->want_c2 = precision == 1 || precision == 3 || precision >= 5;
-    // 5..9: the two-cout-tile kernel with VAR = 1 (register residual), 2 (swizzled columns), 3 (both), 8 (s_setprio), 11 (all)
-    // 10, 11: the weight fragments through an LDS ring (VAR 4), and that with the register residual (VAR 5)
-    // 12, 13: VAR 5 with every lo half zero (timing bound, wrong results) / with 8-bit lo halves
-    // 14: the four-wave kernel (conv_lds_h3_w4)
-    static const int var_of[] = {1, 2, 3, 8, 11, 4, 5, 21, 37, 64};
-    if (precision == 3) nn->variant = 0; // round 2's kernel: weights L2 -> registers per wave, residual decoded from LDS
-    if (precision >= 5 && precision <= 14) nn->variant = var_of[precision - 5];
-#endif
+    nn->precision = precision;
     return nn;
 }
 
@@ -2070,8 +1577,7 @@ int nn_configure(NNState *nn, int kind, int channels, int blocks, int head_chann
     int cp = channels <= 16 ? 16 : channels <= 32 ? 32 : channels <= 64 ? 64 : 128;
     if (nn->precision == 1 && cp < 32) cp = 32; // K = 32 per f16 MFMA step
     nn->kind = kind; nn->C = cp; nn->Craw = channels; nn->blocks = blocks; nn->hc = head_channels; nn->vf = value_fc;
-    nn->mf32 = (nn->precision == 1 && nn->want_mf32 && (cp == 64 || cp == 128)) ? 1 : 0; // other widths stay on 16x16x32
-    nn->c2 = (nn->precision == 1 && nn->want_c2 && !nn->mf32 && cp == 64) ? 1 : 0;
+    nn->c2 = (nn->precision == 1 && cp == 64) ? 1 : 0;
     return DBAZ_OK;
 }
 
@@ -2152,24 +1658,19 @@ static bool pack_conv(NNState *nn, const std::string &conv, const std::string &b
         if (sw > 24) sw = 24;
         if (sw < -24) sw = -24;
         const double wscale = ldexp(1.0, sw);
-        // fragment order of the layer MFMA: 16x16x32 (cout = lane & 15, k = 8 (lane >> 4) + e of a 32-wide step) or, on the
-        // 32x32x16 tiling, cout = lane & 31, k = 8 (lane >> 5) + e of a 16-wide step; packed [ct][tap][ks][hi|lo][lane][8]
-        const bool mf = nn->mf32 && C % 32 == 0;
-        const int TM = mf ? 32 : 16, TK = mf ? 16 : 32, LS = mf ? 5 : 4;
-        const int KS = C / TK;
+        // fragment order of the layer MFMA (16x16x32): cout = lane & 15, k = 8 (lane >> 4) + e of a 32-wide step
+        const int KS = C / 32;
         std::vector<_Float16> hp((size_t)C * C * 9 * 2, (_Float16)0.0f);
-        for (int ct = 0; ct < C / TM; ct++)
+        for (int ct = 0; ct < C / 16; ct++)
             for (int tap = 0; tap < 9; tap++)
                 for (int ks = 0; ks < KS; ks++)
                     for (int lane = 0; lane < 64; lane++)
                         for (int e = 0; e < 8; e++) {
-                            int co = ct * TM + (lane & (TM - 1)), ci = ks * TK + 8 * (lane >> LS) + e;
+                            int co = ct * 16 + (lane & 15), ci = ks * 32 + 8 * (lane >> 4) + e;
                             if (co >= Cr || ci >= Cr) continue;
                             float v = (float)((double)(*w)[((size_t)co * Cr + ci) * 9 + tap] * s[co] * wscale);
                             _Float16 h = (_Float16)v;
                             _Float16 l = (_Float16)(v - (float)h);
-                            if (nn->variant & 16) l = (_Float16)0.0f;            // debug variants VAR_LO0 / VAR_LO8 (see conv_lds_h3_c2)
-                            if (nn->variant & 32) { unsigned short u; memcpy(&u, &l, 2); u &= 0xFFF8; memcpy(&l, &u, 2); }
                             size_t base = ((((size_t)ct * 9 + tap) * KS + ks) * 2) * 64 * 8;
                             hp[base + (size_t)lane * 8 + e] = h;
                             hp[base + 64 * 8 + (size_t)lane * 8 + e] = l;
@@ -2203,32 +1704,13 @@ static hipError_t tower_inst(NNState *nn, hipStream_t s, const TowerArgs &ta, in
     hipLaunchKernelGGL((k_tower<C, NTA, NTB, 0>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
     return hipSuccess;
 }
-#ifdef DBAZ_DEBUG
-// the f16x3 tower on the 32x32x16 tiling: nt2 position tiles of 32 rows per wave (8 waves = 2 cout tiles x 4 tile groups)
-template <int C>
-static hipError_t tower_inst_mf(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt2, int grid, bool attr_only)
-{
-    if constexpr (C == 64 || C == 128) {
-        if (nt2 == 2) {
-            if (attr_only) return hipFuncSetAttribute((const void *)k_tower<C, 2, 0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_mf);
-            hipLaunchKernelGGL((k_tower<C, 2, 0, 1, 1>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds_mf, s, nn->g, ta);
-        } else {
-            if (attr_only) return hipFuncSetAttribute((const void *)k_tower<C, 1, 0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_mf);
-            hipLaunchKernelGGL((k_tower<C, 1, 0, 1, 1>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds_mf, s, nn->g, ta);
-        }
-        return hipSuccess;
-    } else {
-        (void)nn; (void)s; (void)ta; (void)nt2; (void)grid; (void)attr_only;
-        return hipErrorInvalidValue;
-    }
-}
-#endif
+
 // the remainder launch (f16x3, geometries whose main one-cout-tile instantiation is <7,6>)
 static hipError_t tower_dispatch_rem(NNState *nn, hipStream_t s, const TowerArgs &ta, int grid, bool attr_only)
 {
     if (nn->c2) { // beside the two-cout-tile main launch: register-resident residual in every body
-        if (attr_only) return hipFuncSetAttribute((const void *)k_tower_rem<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds);
-        hipLaunchKernelGGL((k_tower_rem<64, 1>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
+        if (attr_only) return hipFuncSetAttribute((const void *)k_tower_rem<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds);
+        hipLaunchKernelGGL((k_tower_rem<64, true>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
         return hipSuccess;
     }
 #define REM_CASE(CC)                                                                                                                  \
@@ -2244,13 +1726,12 @@ static hipError_t tower_dispatch_rem(NNState *nn, hipStream_t s, const TowerArgs
 }
 
 // two cout tiles per wave (C = 64): nt position tiles per wave, 4 tile groups
-template <int VAR>
-static hipError_t tower_dispatch_c2v(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt, int grid, bool attr_only)
+static hipError_t tower_dispatch_c2(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt, int grid, bool attr_only)
 {
 #define C2_CASE(NT)                                                                                                                   \
     case NT:                                                                                                                          \
-        if (attr_only) return hipFuncSetAttribute((const void *)k_tower<64, NT, 0, 1, 2, VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_c2); \
-        hipLaunchKernelGGL((k_tower<64, NT, 0, 1, 2, VAR>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds_c2, s, nn->g, ta);           \
+        if (attr_only) return hipFuncSetAttribute((const void *)k_tower<64, NT, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_c2); \
+        hipLaunchKernelGGL((k_tower<64, NT, 0, 1, true>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds_c2, s, nn->g, ta);           \
         return hipSuccess;
     switch (nt) {
         C2_CASE(1) C2_CASE(2) C2_CASE(3) C2_CASE(4)
@@ -2258,43 +1739,6 @@ static hipError_t tower_dispatch_c2v(NNState *nn, hipStream_t s, const TowerArgs
     }
 #undef C2_CASE
 }
-#define VAR_SHIPPED (VAR_RESREG | VAR_WLDS) // the main launch of the release library
-static hipError_t tower_dispatch_c2(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt, int grid, bool attr_only)
-{
-#ifdef DBAZ_DEBUG // A/B variants of the main launch (nn_precision 3, 5..13 of the debug build)
-    switch (nn->variant) {
-    case 0: return tower_dispatch_c2v<0>(nn, s, ta, nt, grid, attr_only);
-    case 1: return tower_dispatch_c2v<1>(nn, s, ta, nt, grid, attr_only);
-    case 2: return tower_dispatch_c2v<2>(nn, s, ta, nt, grid, attr_only);
-    case 3: return tower_dispatch_c2v<3>(nn, s, ta, nt, grid, attr_only);
-    case 8: return tower_dispatch_c2v<8>(nn, s, ta, nt, grid, attr_only);
-    case 11: return tower_dispatch_c2v<11>(nn, s, ta, nt, grid, attr_only);
-    case 4: return tower_dispatch_c2v<4>(nn, s, ta, nt, grid, attr_only);
-    case 21: return tower_dispatch_c2v<21>(nn, s, ta, nt, grid, attr_only);
-    case 37: return tower_dispatch_c2v<37>(nn, s, ta, nt, grid, attr_only);
-    case 64: // MF = 3: four waves, four cout tiles x four position tiles each (NT = 4 geometries; others stay on the 8-wave kernel)
-        if (nt == 4) {
-            if (attr_only) return hipFuncSetAttribute((const void *)k_tower<64, 4, 0, 1, 3, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_c2);
-            hipLaunchKernelGGL((k_tower<64, 4, 0, 1, 3, 5>), dim3(grid), dim3(256), nn->conv_lds_c2, s, nn->g, ta);
-            return hipSuccess;
-        }
-        break;
-    default: break;
-    }
-#endif
-    return tower_dispatch_c2v<VAR_SHIPPED>(nn, s, ta, nt, grid, attr_only);
-}
-#ifdef DBAZ_DEBUG
-static hipError_t tower_dispatch_mf(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt2, int grid, bool attr_only)
-{
-    if (nn->C == 64) return tower_inst_mf<64>(nn, s, ta, nt2, grid, attr_only);
-    if (nn->C == 128) return tower_inst_mf<128>(nn, s, ta, nt2, grid, attr_only);
-    return hipErrorInvalidValue;
-}
-
-#else
-static hipError_t tower_dispatch_mf(NNState *, hipStream_t, const TowerArgs &, int, int, bool) { return hipErrorInvalidValue; }
-#endif
 
 template <int C>
 static hipError_t tower_inst_c(NNState *nn, hipStream_t s, const TowerArgs &ta, int ntt, int grid, bool attr_only, int prec)
@@ -2666,36 +2110,11 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             nn->cus = cus;
     }
-    // 32x32x16 tiling (debug build, nn_precision = 2): 8 position tiles of 32 rows per workgroup, rows of C + 4 dwords
-    if (nn->mf32 && (C == 64 || C == 128)) {
-        auto lds_mf = [&](int S_) {
-            const size_t s4 = (C + 4) / 4;
-            const size_t img = ((((size_t)S_ * HW * s4 + 15) & ~(size_t)15) + 3 * s4) * 4;
-            const size_t need0 = (size_t)S_ * 3 * (g.H + 2) * (g.W + 2) + (size_t)27 * C;
-            const size_t nj = (size_t)(A + 15) / 16 + (size_t)(vf + 15) / 16;
-            const size_t need1 = (size_t)2 * hc * (C + 4) + (size_t)S_ * 2 * hc * HW + 16 + (size_t)S_ * (nj * 16 + 1);
-            return (img + std::max(img, std::max(need0, need1))) * 4;
-        };
-        int Sm = MAXROWS / HW;
-        if (Sm > 16) Sm = 16;
-        while (Sm > 1 && lds_mf(Sm) > lds_budget) Sm--;
-        if (Sm >= 1 && lds_mf(Sm) <= lds_budget) {
-            nn->S_mf = Sm;
-            nn->NT2 = (Sm * HW + 31) / 32 > 4 ? 2 : 1;
-            nn->conv_lds_mf = lds_mf(Sm);
-            nn->S_mf_tail = nn->NT2 == 2 ? std::min(128 / HW, Sm - 1) : 0; // <1>: 4 tiles of 32 rows
-            if (nn->S_mf_tail < 0) nn->S_mf_tail = 0;
-        } else {
-            nn->mf32 = 0;
-        }
-    } else {
-        nn->mf32 = 0;
-    }
     if (nn->c2 && C == 64) {
         int Sc = MAXROWS / HW;
         if (Sc > 16) Sc = 16;
-        // (the shipped variant keeps a two-slot weight ring of 16 KB behind the images; 1.1 KB of static LDS besides)
-        const size_t ring = (nn->variant & (4 | 64)) ? (size_t)2 * 512 * 16 : 0, budget_c2 = (size_t)160 * 1024 - 1536;
+        // (a two-slot weight ring of 16 KB behind the images; 1.1 KB of static LDS besides)
+        const size_t ring = (size_t)2 * WRING_UNITS * 16, budget_c2 = (size_t)160 * 1024 - 1536;
         while (Sc > 1 && lds_bytes(Sc) + ring > budget_c2) Sc--;
         nn->S_c2 = Sc;
         nn->NT_c2 = ((Sc * HW + 15) / 16 + 3) / 4;           // tiles per wave (4 groups)
@@ -2711,15 +2130,12 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         nn->c2 = 0;
     }
     hipError_t he = tower_dispatch(nn, nullptr, TowerArgs(), nn->NTT, 0, true);
-    nn->use_rem = (nn->precision == 1 && nn->NTT == 7 && C >= 32 && !nn->mf32) ? 1 : 0;
+    nn->use_rem = (nn->precision == 1 && nn->NTT == 7 && C >= 32) ? 1 : 0;
     // the two-cout-tile main launch keeps the residual stream in registers; its remainder bodies must round the same way, and
     // those live in k_tower_rem<64, 1>: no remainder launch, no two-cout-tile main launch
     if (!nn->use_rem) nn->c2 = 0;
     if (he == hipSuccess && nn->use_rem) he = tower_dispatch_rem(nn, nullptr, TowerArgs(), 0, true);
     if (he == hipSuccess && nn->c2) he = tower_dispatch_c2(nn, nullptr, TowerArgs(), nn->NT_c2, 0, true);
-
-    if (he == hipSuccess && nn->mf32) he = tower_dispatch_mf(nn, nullptr, TowerArgs(), 2, 0, true);
-    if (he == hipSuccess && nn->mf32) he = tower_dispatch_mf(nn, nullptr, TowerArgs(), 1, 0, true);
     if (he == hipSuccess && nn->tw32) he = tower_dispatch(nn, nullptr, TowerArgs(), nn->NTT, 0, true, 0);
     if (he == hipSuccess && nn->S_mid > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 4, 0, true);
     if (he == hipSuccess && nn->S_small > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 2, 0, true);
@@ -2778,35 +2194,25 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
         ta.S_main = ta.S = nn->S_c2; ta.S_huge = nn->S;
         (void)tower_dispatch_c2(nn, s, ta, nn->NT_c2, (max_n + nn->S_c2 - 1) / nn->S_c2, false);
     }
-    if (nn->mf32 && !nn->c2) {
-        // 32x32x16 tiling: main launch + one tail launch of half-size workgroups (same split rule, derived from n on the device)
-        ta.S_main = ta.S = nn->S_mf; ta.S_small = nn->S_mf_tail; ta.S_mid = ta.S_big = ta.S_huge = 0;
-        (void)tower_dispatch_mf(nn, s, ta, nn->NT2, (max_n + nn->S_mf - 1) / nn->S_mf, false);
-        if (nn->S_mf_tail > 0) {
-            ta.role = 1; ta.S = nn->S_mf_tail;
-            (void)tower_dispatch_mf(nn, s, ta, 1, nn->cus, false);
-        }
-    } else {
     if (!nn->c2) (void)tower_dispatch(nn, s, ta, nn->NTT, (max_n + nn->S - 1) / nn->S, false);
     if (nn->use_rem) {     // the remainder sizes in one launch (the workgroups pick theirs)
         ta.role = -1;
         (void)tower_dispatch_rem(nn, s, ta, nn->cus, false);
     } else {
-    if (nn->S_small > 0) { // tail <= cus * S_small samples: one round of <2,2> workgroups
-        ta.role = 1; ta.S = nn->S_small;
-        (void)tower_dispatch(nn, s, ta, 2, nn->cus, false);
+        if (nn->S_small > 0) { // tail <= cus * S_small samples: one round of <2,2> workgroups
+            ta.role = 1; ta.S = nn->S_small;
+            (void)tower_dispatch(nn, s, ta, 2, nn->cus, false);
+        }
+        if (nn->S_mid > 0) {   // tail <= cus * S_mid samples: one round of <4,4> workgroups
+            ta.role = 2; ta.S = nn->S_mid;
+            (void)tower_dispatch(nn, s, ta, 4, nn->cus, false);
+        }
+        if (nn->S_big > 0) {   // tail <= cus * S_big samples: one round of <5,5> workgroups
+            ta.role = 3; ta.S = nn->S_big;
+            (void)tower_dispatch(nn, s, ta, 5, nn->cus, false);
+        }
     }
-    if (nn->S_mid > 0) {   // tail <= cus * S_mid samples: one round of <4,4> workgroups
-        ta.role = 2; ta.S = nn->S_mid;
-        (void)tower_dispatch(nn, s, ta, 4, nn->cus, false);
-    }
-    if (nn->S_big > 0) {   // tail <= cus * S_big samples: one round of <5,5> workgroups
-        ta.role = 3; ta.S = nn->S_big;
-        (void)tower_dispatch(nn, s, ta, 5, nn->cus, false);
-    }
-    }
-    }
-    if (nn->precision == 1 && nn->tw32 && !nn->no_fallback) {
+    if (nn->precision == 1 && nn->tw32) {
         // safety net of the f16x3 mode: samples whose workgroup saw an activation leave f16's range are redone by the
         // exact-f32 tower (its workgroups check the per-sample flags on the device and leave at once otherwise)
         ta.role = 0; ta.S = ta.S_main = nn->S; ta.S_small = ta.S_mid = ta.S_big = ta.S_huge = 0; ta.fallback = 1;
@@ -2821,7 +2227,7 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
 void nn_round_info(const NNState *nn, int *round, int *rem_max)
 {
     *round = 0; *rem_max = 0;
-    if (!nn || nn->kind != DBAZ_EVAL_RESNET || nn->mf32) return;
+    if (!nn || nn->kind != DBAZ_EVAL_RESNET) return;
     *round = nn->cus * (nn->c2 ? nn->S_c2 : nn->S);
     const int s_rem = nn->c2 ? nn->S : std::max(nn->S_big, std::max(nn->S_mid, nn->S_small));
     *rem_max = nn->cus * s_rem;

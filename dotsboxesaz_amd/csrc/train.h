@@ -31,15 +31,15 @@ void net_free(struct dbaz_trainer *t); // train_net.hip
 
 struct dbaz_trainer {
     int dev = 0, H = 0, W = 0, HW = 0, L = 0, maxN = 0, n = 0;
-    int S = 1, Sw = 1, cus = 256;
+    int S = 1, cus = 256;
 #ifdef DBAZ_STAMP
     unsigned long long *stamps = nullptr, *stamps_wg = nullptr; // diagnostic build only (k_conv_t, k_wgrad_h3)
 #endif
     float eps = 1e-5f, momentum = 0.1f;
-    size_t conv_lds = 0, wgrad_lds = 0;
+    size_t conv_lds = 0;
     bool have_fwd = false;
     bool net_fwd = false;  // the held forward pass is a dbaz_trainer_net_forward (whole network)
-    int wgrad_h3 = 1, Swh = 1; // k_wgrad_h3 (f16x3) and its samples per chunk; 0: the exact-f32 k_wgrad
+    int Swh = 1; // samples per k_wgrad_h3 chunk
     size_t wgrad_h3_lds = 0;
     std::string err;
     float *A = nullptr, *Y = nullptr, *G = nullptr, *dA[2] = {nullptr, nullptr}, *dY = nullptr;

@@ -15,7 +15,7 @@
 //   backward   g = dA[l+1] * (A[l+1] > 0); sums of g and g*yhat      epilogue of the k_conv_t that wrote dA[l+1] (top layer: k_bn_bwd_sums)
 //                                                                    + k_bn_bwd_sums_fin (-> dgamma, dbeta)
 //              dY[l] = gamma*invstd*(g - mean(g) - yhat*mean(g*yhat)) k_bn_bwd_apply (also keeps g for the skip path)
-//              dW[l] = sum_rows A[l](row + tap) x dY[l](row)          k_wgrad_h3 (f16x3 MFMA; k_wgrad: exact f32) + k_wgrad_reduce
+//              dW[l] = sum_rows A[l](row + tap) x dY[l](row)          k_wgrad_h3 (f16x3 MFMA) + k_wgrad_reduce
 //              dA[l] = conv3x3^T(dY[l]) (+ g of the block's end)      k_conv_t with flipped / transposed fragments
 // Every f32 operand of k_conv_t is an error-compensated (hi, lo) pair of halves scaled by a power of two taken from the
 // tensor's own maximum (tracked by the kernel that produced it), so gradients of any magnitude keep f32-grade products.
@@ -650,153 +650,21 @@ __global__ void __launch_bounds__(TT) k_bn_bwd_apply(const f32x4 *__restrict__ d
 }
 
 // ------------------------------------------------------------------------------------
-// weight gradient dW[tap][cin][cout] = sum over rows of A(row + tap offset)[cin] * dY(row)[cout], exact f32 on
-// v_mfma_f32_16x16x4_f32 (m = cin, n = cout, k = 4 consecutive rows).  A workgroup stages chunks of Sw samples: dY as plain
-// rows, A into a ZERO-PADDED image (one pad column per line, one pad line per sample, guard rows in front), so that a tap is a
-// constant row offset and needs no border mask; tab[row] holds the byte offset of a dY row's window in that image.  Rows are
-// C+16 dwords (the two rows of a 32-lane read group fall on disjoint banks).  The whole 9 x 64 x 64 gradient stays in
-// registers: wave w owns cin tile w & 3 and cout tiles 2 (w >> 2), +1 for all 9 taps (18 accumulator tiles); the operands
-// of K-step k+1 are read from LDS while the 18 MFMAs of step k issue, and the next chunk's rows travel HBM -> registers
-// under the whole loop.  The workgroups' partial gradients are summed by k_wgrad_reduce.
-// ------------------------------------------------------------------------------------
-#define WG_STRIDE (TC + 16)
-#define WG_MAXLD 13 // float4 per thread and chunk: 2 images x <= 208 rows x 16 quads / 512 threads
-
-struct WgGeo { int RW, RA, PW, G; };
-__host__ __device__ inline WgGeo wg_geo(int Sw, int H, int W)
-{
-    WgGeo g;
-    g.PW = W + 1;
-    g.G = g.PW + 1;
-    g.RW = (Sw * H * W + 3) & ~3;                 // dY rows per chunk, padded to the K step
-    g.RA = 2 * g.G + Sw * (H + 1) * g.PW;          // rows of the padded A image
-    return g;
-}
-static size_t wg_lds_bytes(int Sw, int H, int W)
-{
-    const WgGeo g = wg_geo(Sw, H, W);
-    return (size_t)(g.RA + g.RW) * WG_STRIDE * 4 + (size_t)g.RW * 4;
-}
-
-__global__ void __launch_bounds__(TT, 2) k_wgrad(const float *__restrict__ act, const float *__restrict__ dy, int n, int Sw, int H, int W,
-                                                 float *__restrict__ part)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int HW = H * W;
-    const WgGeo geo = wg_geo(Sw, H, W);
-    const int RW = geo.RW, PW = geo.PW;
-    float *Ai = lds;
-    float *Di = lds + (size_t)geo.RA * WG_STRIDE;
-    int *tab = reinterpret_cast<int *>(Di + (size_t)RW * WG_STRIDE);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cit = wave & 3, ch = wave >> 2;
-    const int m16 = lane & 15, gq = lane >> 4;
-    f32x4 acc[9][2];
-#pragma unroll
-    for (int t = 0; t < 9; t++) { acc[t][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    for (int i = tid; i < geo.RA * (WG_STRIDE / 4); i += TT) reinterpret_cast<f32x4 *>(Ai)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int r = tid; r < RW; r += TT) {
-        int v = 0;
-        if (r < Sw * HW) {
-            const int sidx = r / HW, pos = r - sidx * HW, y = pos / W, x = pos - y * W;
-            v = (geo.G + sidx * (H + 1) * PW + y * PW + x - PW - 1) * WG_STRIDE * 4; // window start: tap (0,0) = row - PW - 1
-        }
-        tab[r] = v;
-    }
-    const int nchunks = (n + Sw - 1) / Sw;
-    f32x4 pf[WG_MAXLD];
-    const int img4 = RW * 16; // float4 per image
-    auto issue = [&](int chunk) {
-        const int s0 = chunk * Sw, R = min(Sw, n - s0) * HW;
-        const f32x4 *a4 = reinterpret_cast<const f32x4 *>(act) + (size_t)s0 * HW * 16;
-        const f32x4 *d4 = reinterpret_cast<const f32x4 *>(dy) + (size_t)s0 * HW * 16;
-#pragma unroll
-        for (int j = 0; j < WG_MAXLD; j++) {
-            const int i = tid + j * TT;
-            const int which = i >= img4, ii = i - which * img4;
-            pf[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (i < 2 * img4 && (ii >> 4) < R) pf[j] = which ? d4[ii] : a4[ii];
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int j = 0; j < WG_MAXLD; j++) {
-            const int i = tid + j * TT;
-            const int which = i >= img4, ii = i - which * img4;
-            if (i < 2 * img4) {
-                const int row = ii >> 4, c4 = ii & 15;
-                if (which) *reinterpret_cast<f32x4 *>(Di + (size_t)row * WG_STRIDE + c4 * 4) = pf[j];
-                else if (row < Sw * HW) // (rows of samples past the batch's end arrive as zeros; their dY rows are zero as well)
-                    *reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(Ai) + tab[row] + (PW + 1) * WG_STRIDE * 4 + c4 * 16) = pf[j];
-            }
-        }
-    };
-    __syncthreads(); // tab, zeroed image
-    if ((int)blockIdx.x < nchunks) issue(blockIdx.x);
-    int toff[9];
-#pragma unroll
-    for (int t = 0; t < 9; t++) toff[t] = ((t / 3) * PW + (t % 3)) * WG_STRIDE * 4;
-    const char *abase = reinterpret_cast<const char *>(Ai) + (cit * 16 + m16) * 4;
-    const float *dbase = Di + ch * 32 + m16;
-    const int NK = RW / 4;
-    for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        __syncthreads(); // the previous chunk's reads are done
-        commit();
-        __syncthreads();
-        if (chunk + (int)gridDim.x < nchunks) issue(chunk + gridDim.x);
-        float a0[9], a1[9], b0[2], b1[2];
-        auto load = [&](float (&av)[9], float (&bv)[2], int k, int tb) {
-            const int r = 4 * k + gq;
-            bv[0] = dbase[(size_t)r * WG_STRIDE];
-            bv[1] = dbase[(size_t)r * WG_STRIDE + 16];
-#pragma unroll
-            for (int t = 0; t < 9; t++) av[t] = *reinterpret_cast<const float *>(abase + tb + toff[t]);
-        };
-        auto mma = [&](const float (&av)[9], const float (&bv)[2]) {
-#pragma unroll
-            for (int t = 0; t < 9; t++) {
-                acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv[0], acc[t][0], 0, 0, 0);
-                acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t], bv[1], acc[t][1], 0, 0, 0);
-            }
-        };
-        int tbA = tab[gq], tbB = tab[min(4 + gq, RW - 1)], tbC = 0, tbD = 0;
-        load(a0, b0, 0, tbA);
-        for (int k = 0; k < NK; k += 2) {
-            tbC = tab[min(4 * (k + 2) + gq, RW - 1)];
-            tbD = tab[min(4 * (k + 3) + gq, RW - 1)];
-            if (k + 1 < NK) load(a1, b1, k + 1, tbB);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(a0, b0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k + 2 < NK) load(a0, b0, k + 2, tbC);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k + 1 < NK) mma(a1, b1);
-            __builtin_amdgcn_sched_barrier(0);
-            tbB = tbD;
-        }
-    }
-    // lane holds dW[tap][cin = cit*16 + 4 gq + i][cout = (2 ch + j)*16 + m16]
-    float *o = part + (size_t)blockIdx.x * 9 * TC * TC;
-#pragma unroll
-    for (int tap = 0; tap < 9; tap++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                o[((size_t)tap * TC + cit * 16 + 4 * gq + i) * TC + (2 * ch + j) * 16 + m16] = acc[tap][j][i];
-}
-
-// ------------------------------------------------------------------------------------
-// The same weight gradient on the f16 MFMA pipe (f16x3, as k_conv_t): K = 32 rows per v_mfma_f32_16x16x32_f16 step, both
-// operands (hi, lo) pairs of halves scaled by the tensors' own maxima.  The MFMA wants 8 consecutive K values (rows) of one
-// channel per lane while the images are row-major [row][channel]: gfx950's transposing LDS read (ds_read_b64_tr_b16) hands
-// every lane column i of four rows whose addresses the lanes supply, so rows need not even be contiguous -- K slot 4h + q of
-// lane group g is row 16h + 4g + q of the step for BOTH operands (any bijection is a valid K order).
+// weight gradient dW[tap][cin][cout] = sum over rows of A(row + tap offset)[cin] * dY(row)[cout] on the f16 MFMA pipe
+// (f16x3, as k_conv_t): K = 32 rows per v_mfma_f32_16x16x32_f16 step, both operands (hi, lo) pairs of halves scaled by the
+// tensors' own maxima.  A workgroup stages chunks of Sw samples; A goes into a ZERO-PADDED image (one pad column per line,
+// one pad line per sample, guard rows in front), so that a tap is a constant row offset and needs no border mask.  The MFMA
+// wants 8 consecutive K values (rows) of one channel per lane while the images are row-major [row][channel]: gfx950's
+// transposing LDS read (ds_read_b64_tr_b16) hands every lane column i of four rows whose addresses the lanes supply, so rows
+// need not even be contiguous -- K slot 4h + q of lane group g is row 16h + 4g + q of the step for BOTH operands (any
+// bijection is a valid K order).
 // Images: rows of [64 hi | 64 lo | 16 pad] halves (288 B: eight consecutive rows cover the 64 banks once).  dY is stored with
-// one zero pad column per line (K runs over H x (W+1) cells per sample: a K step is whole lines), A zero-padded as in
-// k_wgrad; tabA[row] = byte offset of a dY row's 3x3 window in the A image.  Wave w owns cin tile w & 3 and cout tiles
-// 2 (w >> 2), +1 for all 9 taps; A fragments run two taps ahead in a 3-deep ring.
+// one zero pad column per line (K runs over H x (W+1) cells per sample: a K step is whole lines); tabA[row] = byte offset of a
+// dY row's 3x3 window in the A image.  Wave w owns cin tile w & 3 and cout tiles 2 (w >> 2), +1 for all 9 taps; A fragments
+// run two taps ahead in a 3-deep ring, and the next chunk's rows travel HBM -> registers under the whole loop.  The
+// workgroups' partial gradients are summed by k_wgrad_reduce.
 // ------------------------------------------------------------------------------------
+#define WG_MAXLD 13 // float4 per thread and chunk: 2 images x <= 208 rows x 16 quads / 512 threads
 #define WH_SB 288 // bytes per image row
 typedef short s4v __attribute__((__vector_size__(4 * sizeof(short))));
 union FragH { s4v s[2]; f16x8 h; };
@@ -1097,20 +965,14 @@ extern "C" int dbaz_trainer_create(int32_t rows, int32_t cols, int32_t channels,
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) t->cus = prop.multiProcessorCount;
     t->S = 256 / t->HW;
-    t->Sw = 1; // samples per k_wgrad chunk: as many as the prefetch registers (208 rows) and 150 KB of LDS hold
-    while ((t->Sw + 1) * t->HW <= 208 && wg_lds_bytes(t->Sw + 1, t->H, t->W) <= 150 * 1024) t->Sw++;
     {
         const int S4 = (TC + 8) / 4;
         const int zu = (t->S * t->HW * S4 + 15) & ~15;
         t->conv_lds = (size_t)(zu + 3 * S4) * 16 + (size_t)(TT / 64) * 2 * TC * 8 + 16; // image + zero rows + the epilogue's column-sum slots
-        t->wgrad_lds = wg_lds_bytes(t->Sw, t->H, t->W);
+        // samples per k_wgrad_h3 chunk: as many as the prefetch registers (208 rows) and 150 KB of LDS hold
         t->Swh = 1;
         while ((t->Swh + 1) * t->HW <= 208 && wh_lds_bytes(t->Swh + 1, t->H, t->W) <= 150 * 1024) t->Swh++;
         t->wgrad_h3_lds = wh_lds_bytes(t->Swh, t->H, t->W);
-        t->wgrad_h3 = 1;
-#ifdef DBAZ_DEBUG
-        if (getenv("DBAZ_TRAIN_WGRAD_F32")) t->wgrad_h3 = 0; // debug build: the exact-f32 weight gradient kernel (A/B reference)
-#endif
     }
     const size_t ae = act_elems(t);
     hipError_t e = hipSuccess;
@@ -1136,7 +998,6 @@ extern "C" int dbaz_trainer_create(int32_t rows, int32_t cols, int32_t channels,
     alloc((void **)&t->stamps_wg, (size_t)(t->cus + 1) * 64 * 8);
 #endif
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_conv_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->conv_lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->wgrad_lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_h3<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->wgrad_h3_lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_wgrad_h3<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->wgrad_h3_lds);
     if (e != hipSuccess) {
@@ -1213,7 +1074,7 @@ int tower_backward_rows(dbaz_trainer *t, const float *const *bn_w, float *const 
     const long long M = (long long)n * HW;
     const int grid = (n + t->S - 1) / t->S;
     const int rb = red_blocks(M);
-    const int Sw = t->wgrad_h3 ? t->Swh : t->Sw;
+    const int Sw = t->Swh;
     const int nchunks = (n + Sw - 1) / Sw;
     const int wg = std::min(t->cus, nchunks);
     unsigned *dymax = t->amax + L + 1;
@@ -1250,22 +1111,20 @@ int tower_backward_rows(dbaz_trainer *t, const float *const *bn_w, float *const 
         ca.stamp_out = t->stamps;
 #endif
         hipLaunchKernelGGL(k_conv_t, dim3(grid), dim3(TT), t->conv_lds, s, ca);
-        if (t->wgrad_h3 && t->W == 7)
+        if (t->W == 7)
             hipLaunchKernelGGL((k_wgrad_h3<8>), dim3(wg), dim3(TT), t->wgrad_h3_lds, s, t->A + ae * l, t->dY, t->amax + l, dymax, n, Sw, t->H,
                                t->W, t->wg_part
 #ifdef DBAZ_STAMP
                                , t->stamps_wg
 #endif
                                );
-        else if (t->wgrad_h3)
+        else
             hipLaunchKernelGGL((k_wgrad_h3<0>), dim3(wg), dim3(TT), t->wgrad_h3_lds, s, t->A + ae * l, t->dY, t->amax + l, dymax, n, Sw, t->H,
                                t->W, t->wg_part
 #ifdef DBAZ_STAMP
                                , t->stamps_wg
 #endif
                                );
-        else
-            hipLaunchKernelGGL(k_wgrad, dim3(wg), dim3(TT), t->wgrad_lds, s, t->A + ae * l, t->dY, n, Sw, t->H, t->W, t->wg_part);
         // weight gradient totals + conv bias gradient + (last C workgroups) the BatchNorm-backward totals of the layer below
         hipLaunchKernelGGL(k_wgrad_reduce, dim3(9 * TC * TC / 64 + TC + (fin.nparts ? TC : 0)), dim3(256), 0, s, t->wg_part, wg, g_conv_w[l], t->part,
                            rb, g_conv_b[l], fin);

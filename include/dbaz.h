@@ -44,7 +44,7 @@ extern "C" {
 
 /* dbaz_config.debug_flags */
 #define DBAZ_DBG_EARLY_JOIN 1u  /* join the driver pass in front of the network launch (round 2's first order) */
-#define DBAZ_DBG_NO_FALLBACK 2u /* skip the exact-f32 safety-net launch of nn_precision = 1 (timing runs only) */
+#define DBAZ_DBG_NO_FALLBACK 2u /* reserved: formerly skipped the exact-f32 safety net of nn_precision = 1; dbaz_create rejects it */
 #define DBAZ_DBG_LAZY_GC 4u     /* node collector recycles dropped nodes only when fewer than 64 indices are available (A/B) */
 #define DBAZ_RESULT_NONE 2
 
@@ -74,8 +74,7 @@ typedef struct {
     uint64_t seed;          /* Philox key for move sampling / Dirichlet noise */
     int32_t max_out_rows;   /* capacity of the finished-sample buffer; 0 = max(4096, 2*n_slots*(E+1)) */
     int32_t nn_precision;   /* 0 = exact f32 MFMA; 1 = f16x3 split MFMA (f32-grade; an evaluation whose activations leave
-                             * f16's range is redone in exact f32 on the device, counters.f32_fallback_evals).  (A library built
-                             * with -DDBAZ_DEBUG also accepts the A/B tilings 2, 3, 4 of tools/ab_tilings.sh.) */
+                             * f16's range is redone in exact f32 on the device, counters.f32_fallback_evals) */
     int32_t match_play;     /* two-model match play (self_play.compute_elo, :309-344): the evaluator of a move's
                                search is model (root.to_play XOR game_idx&1) */
     int32_t evaluator2;     /* DBAZ_EVAL_* of model 1 (match play) */
@@ -125,7 +124,7 @@ typedef struct {
 
 const char *dbaz_last_error(const dbaz_engine *e); /* e may be NULL: error of the last dbaz_create */
 int dbaz_version(void);            /* DBAZ_ABI_VERSION the library was built with */
-const char *dbaz_build_info(void); /* "src=<sha256[:16] of csrc/ + include/dbaz.h> nn=<the same of the network kernels>[ debug]": ties profiles/ counter files to a build */
+const char *dbaz_build_info(void); /* "src=<sha256[:16] of csrc/ + include/dbaz.h> nn=<the same of the network kernels>": ties profiles/ counter files to a build */
 int dbaz_nodes_per_slot(const dbaz_engine *e); /* the node pool size in effect (dbaz_config.nodes_per_slot = 0: the default rule) */
 
 int dbaz_create(const dbaz_config *cfg, dbaz_engine **out);

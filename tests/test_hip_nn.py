@@ -210,6 +210,16 @@ def test_f16x3_fallback_only_touches_the_overflowing_samples():
     e.close()
 
 
+def test_no_fallback_debug_flag_is_rejected():
+    """debug_flags bit 2 (DBAZ_DBG_NO_FALLBACK) used to skip the exact-f32 safety net, so overflowing f16x3 evaluations came
+    back as success; the bit stays reserved and dbaz_create rejects it."""
+    from dotsboxesaz_amd import _lib
+    from dotsboxesaz_amd.engine import Engine
+    with pytest.raises(_lib.DbazError) as ei:
+        Engine(6, 6, 8, evaluator="resnet", debug_flags=2)
+    assert ei.value.code == _lib.EINVAL and "DBAZ_DBG_NO_FALLBACK" in str(ei.value)
+
+
 def test_f16x3_simplenn_still_reports_range_overflow():
     """SimpleNN has no f32 safety net: out-of-range activations remain a loud error."""
     from dotsboxesaz_amd import _lib
