@@ -25,7 +25,6 @@ double nn_flops_per_sample(const NNState *nn);
 // samples of one full round of the main tower launch (CUs x samples per workgroup), and the largest left-over that nn_forward
 // would hand to a remainder launch (0: no remainder launches for this geometry)
 void nn_round_info(const NNState *nn, int *round, int *rem_max);
-const char *nn_tower_kernel_name(const NNState *nn);
 // f16x3 mode: non-zero once an activation exceeded f16's range (results invalid: use precision 0)
 int nn_overflowed(NNState *nn);
 // f16x3 mode of ResNetZero: samples whose f16x3 evaluation left f16's range and were redone in exact f32

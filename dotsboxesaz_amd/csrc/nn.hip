@@ -7,13 +7,15 @@
 // SimpleNN (reference dots_boxes_nn.py:61-98, 3x3 boards): BN follows the ReLU.
 //
 // Kernels
-//   k_tower<C,NTA,NTB,PREC>  the whole ResNetZero trunk in ONE launch: conv0, the 2*blocks
-//                            conv3x3 layers and both 1x1 head convs; the S samples of a
-//                            workgroup stay in two ping-pong LDS images, weights stream from L2
-//   k_simple_trunk<PREC>     the same for SimpleNN's conv0..conv4 (256 channels)
+//   k_tower<C,NTA,NTB,PREC,C2>  the whole ResNetZero network in ONE launch: conv0, the 2*blocks
+//                            conv3x3 layers, both 1x1 head convs and the head FCs + softmax / tanh
+//                            (head_fc_fused); the S samples of a workgroup stay in two ping-pong
+//                            LDS images, weights stream from L2
+//   k_tower_rem<C,RR>        the samples behind the main launch's last full round (f16x3)
+//   k_simple_trunk<PREC>     SimpleNN's conv0..conv4 (256 channels), LDS-resident like k_tower
 //   k_dense                  SimpleNN's FC layers (f32 MFMA GEMM, 16 samples per workgroup)
-//   k_head_fc                head FCs + softmax / tanh (f32 MFMA GEMM, 16 samples per workgroup)
-// conv_lds_f32 / conv_lds_h3 are the per-layer device functions (LDS -> LDS).
+//   k_head_fc                SimpleNN's head FCs + softmax / tanh (f32 MFMA GEMM, 16 samples per workgroup)
+// conv_lds_f32 / conv_lds_h3 / conv_lds_h3_c2 are the per-layer device functions (LDS -> LDS).
 //
 // The conv layer is an implicit GEMM  Out^T[cout][pos] = W[cout][tap,cin] * In[tap,cin][pos].
 // A operand = weights, pre-packed on the host in fragment order and streamed from L2 straight
@@ -29,6 +31,7 @@
 // PREC 1: "f16x3" -- every f32 operand is an error-compensated (hi, lo) pair of halves on
 //         v_mfma_f32_16x16x32_f16 with f32 accumulation (see conv_lds_h3).
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -66,12 +69,12 @@ struct NNState {
     float osc0 = 1.0f;                          // f16x3: 2^-sw0
     float *hwp = nullptr;                       // f16x3: head conv weights packed as MFMA fragments [ct][ks][hi|lo][lane][8 halves]
     float hosc = 1.0f;                          // f16x3: 2^-(sw_h + ACT_SHIFT)
-    float *hact = nullptr;                      // [batch][2][hc*HW]
     float *wfc = nullptr, *bfc = nullptr;       // head FC GEMM: packed weights [ntp+ntv][KP/16][64][4], bias [(ntp+ntv)*16]
-    int KP = 0, RS4 = 0, ntp = 0, ntv = 0;
-    size_t fc_lds = 0;
-    float *wv1 = nullptr, *bv1 = nullptr;       // [vf], [1]
+    int KP = 0, ntp = 0, ntv = 0;
+    float *wv1 = nullptr, *bv1 = nullptr;       // value FC1 [vf], [1]
     // SimpleNN
+    float *hact = nullptr;                      // fc1's output, twice per sample: k_head_fc's input [batch][2][256]
+    size_t fc_lds = 0;                          // k_head_fc's dynamic LDS
     float *sn_s0 = nullptr, *sn_t0 = nullptr, *sn_ts = nullptr, *sn_tt = nullptr;
     float *sn_flat = nullptr, *sn_h1 = nullptr;
     float *sn_w0 = nullptr, *sn_b0 = nullptr, *sn_ps0 = nullptr, *sn_pt0 = nullptr; // fc0
@@ -183,12 +186,69 @@ __device__ __forceinline__ void conv_lds_f32(const f32x4 *__restrict__ src4, f32
 // [C halves hi | C halves lo | 32 B pad] = (C+8) dwords.
 // ------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define ACT_SHIFT 5
 #define ACT_SCALE 32.0f
 #define F16_GUARD 60000.0f
 
 union u128h { f32x4 f; f16x8 h; };
+
+// channel c of LDS row `row` (rows of C + 8 dwords): PREC 0 a float, PREC 1 the (hi, lo) halves at c and C + c
+template <int C, int PREC>
+__device__ __forceinline__ void act_store(float *lds, int row, int c, float v, bool &ovf)
+{
+    if constexpr (PREC == 0) {
+        lds[row * (C + 8) + c] = v;
+    } else {
+        _Float16 *h = reinterpret_cast<_Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
+        const float x = v * ACT_SCALE;
+        ovf |= fabsf(x) > F16_GUARD;
+        const _Float16 hi = (_Float16)x;
+        h[c] = hi;
+        h[C + c] = (_Float16)(x - (float)hi);
+    }
+}
+template <int C, int PREC>
+__device__ __forceinline__ float act_load(const float *lds, int row, int c)
+{
+    if constexpr (PREC == 0) {
+        return lds[row * (C + 8) + c];
+    } else {
+        const _Float16 *h = reinterpret_cast<const _Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
+        return ((float)h[c] + (float)h[C + c]) * (1.0f / ACT_SCALE);
+    }
+}
+
+// ---- the f16x3 epilogue pieces shared by conv_lds_h3, conv_lds_h3_c2 and tower_group (lane map of the 16x16x32 MFMA:
+// jrow = lane & 15 is the position row inside a tile, gq = lane >> 4 selects 4 consecutive couts)
+__device__ __forceinline__ f32x4 relu4(f32x4 v)
+{
+    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+    return v;
+}
+__device__ __forceinline__ float max4(f32x4 v) { return fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])); }
+
+// 4 consecutive couts of one image row, activation-scaled: hi = rn_f16(v), lo = rn_f16(v - hi) on packed pairs
+// (v_cvt_pk_f16_f32 / v_pk_add_f32); the hi halves go to ph, the lo halves to ph + C, as two 8-byte stores (!valid: a row
+// behind the workgroup's last, nothing is written)
+template <int C>
+__device__ __forceinline__ void h3_store(_Float16 *ph, bool valid, f32x4 v)
+{
+    union { f16x2 h[2]; u32x2 u; } oh, ol;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const f32x2 x = {v[2 * q], v[2 * q + 1]};
+        const f16x2 h = __builtin_convertvector(x, f16x2);
+        oh.h[q] = h;
+        ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), f16x2);
+    }
+    if (valid) {
+        *reinterpret_cast<u32x2 *>(ph) = oh.u;
+        *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
+    }
+}
 
 #ifdef DBAZ_STAMP
 // diagnostic build only (never shipped): per-wave cycle sums of the layer phases
@@ -317,10 +377,8 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
         __builtin_amdgcn_sched_barrier(0);
         // ---- epilogue: scale back, bias, residual, ReLU, split into halves.
         // All residual reads are issued first (one LDS round trip for the whole wave, not one per
-        // tile); the (hi, lo) split uses gfx950's packed round-to-nearest converts; one running max
-        // replaces per-value range checks.
+        // tile); the (hi, lo) split is h3_store's; one running max replaces per-value range checks.
         _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
-        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         u32x2 rh[NTT], rl[NTT];
         if constexpr (!RR) {
             if (residual) {
@@ -342,8 +400,7 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
                 if constexpr (RR) {
                     v += res[t];
                 } else {
-                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                    union { unsigned int u; h2 h; } c0, c1, d0, d1;
+                    union { unsigned int u; f16x2 h; } c0, c1, d0, d1;
                     c0.u = rh[t][0]; c1.u = rh[t][1]; d0.u = rl[t][0]; d1.u = rl[t][1];
                     v[0] += (float)c0.h[0] + (float)d0.h[0];
                     v[1] += (float)c0.h[1] + (float)d0.h[1];
@@ -351,7 +408,7 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
                     v[3] += (float)c1.h[1] + (float)d1.h[1];
                 }
             }
-            v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+            v = relu4(v);
             if constexpr (RR) {
                 if (residual) res[t] = v; // the block's output = the next block's residual input
             }
@@ -360,24 +417,9 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
                     *reinterpret_cast<const f32x4 *>(post_t + ct * 16 + gq * 4);
                 vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
             } else {
-                vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+                vmax = fmaxf(vmax, max4(v));
             }
-            // hi = rn_f16(v), lo = rn_f16(v - hi) on packed pairs: v_cvt_pk_f16_f32 / v_pk_add_f32
-            typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-            typedef float f2v __attribute__((ext_vector_type(2)));
-            union { h2v h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const f2v x = {v[2 * q], v[2 * q + 1]};
-                const h2v h = __builtin_convertvector(x, h2v);
-                oh.h[q] = h;
-                ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f2v), h2v);
-            }
-            if (row < R) {
-                _Float16 *ph = dsth + (size_t)row * (S4 * 8) + ct * 16 + gq * 4;
-                *reinterpret_cast<u32x2 *>(ph) = oh.u;
-                *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
-            }
+            h3_store<C>(dsth + (size_t)row * (S4 * 8) + ct * 16 + gq * 4, row < R, v);
         }
         ovf |= vmax > F16_GUARD;
         STAMP(t3);
@@ -527,9 +569,6 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     __builtin_amdgcn_sched_barrier(0);
     // ---- epilogue (as conv_lds_h3): lane holds couts (ct0 + c) * 16 + 4 gq .. +3 of position row (tbase + t) * 16 + jrow
     _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    typedef float f2v __attribute__((ext_vector_type(2)));
     float vmax = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; c++) {
@@ -539,22 +578,10 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             const int row = (tbase + t) * 16 + jrow;
             f32x4 v = acc[c][t] * oscale + bv[c];
             if (residual) v += res[c][t];
-            v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+            v = relu4(v);
             if (residual) res[c][t] = v; // the block's output = the next block's residual input
-            vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-            union { h2v h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const f2v x = {v[2 * q], v[2 * q + 1]};
-                const h2v h = __builtin_convertvector(x, h2v);
-                oh.h[q] = h;
-                ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f2v), h2v);
-            }
-            if (row < R) {
-                _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
-                *reinterpret_cast<u32x2 *>(ph) = oh.u;
-                *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
-            }
+            vmax = fmaxf(vmax, max4(v));
+            h3_store<C>(dsth + (size_t)row * (S4 * 8) + col, row < R, v);
         }
     }
     ovf_out |= vmax > F16_GUARD;
@@ -575,32 +602,6 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
 // from L2.  PREC 0: exact f32 (rows hold C floats); PREC 1: f16x3 (rows hold C hi + C lo halves
 // of the activation scaled by 2^ACT_SHIFT).
 // ------------------------------------------------------------------------------------
-// channel c of LDS row `row` (rows of C + 8 dwords): PREC 0 a float, PREC 1 the (hi, lo) halves at c and C + c
-template <int C, int PREC>
-__device__ __forceinline__ void act_store(float *lds, int row, int c, float v, bool &ovf)
-{
-    if constexpr (PREC == 0) {
-        lds[row * (C + 8) + c] = v;
-    } else {
-        _Float16 *h = reinterpret_cast<_Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
-        const float x = v * ACT_SCALE;
-        ovf |= fabsf(x) > F16_GUARD;
-        const _Float16 hi = (_Float16)x;
-        h[c] = hi;
-        h[C + c] = (_Float16)(x - (float)hi);
-    }
-}
-template <int C, int PREC>
-__device__ __forceinline__ float act_load(const float *lds, int row, int c)
-{
-    if constexpr (PREC == 0) {
-        return lds[row * (C + 8) + c];
-    } else {
-        const _Float16 *h = reinterpret_cast<const _Float16 *>(lds) + (size_t)row * ((C + 8) * 2);
-        return ((float)h[c] + (float)h[C + c]) * (1.0f / ACT_SCALE);
-    }
-}
-
 // Full rounds only (engine: self-play stepping): the leaves the network takes from a list of n -- every kernel of a step applies
 // the same rule to the same count, so no launch of its own is needed for it (see "Full rounds only" in tree.hip)
 __device__ __forceinline__ int cut_n(int n, int round, int defer_max)
@@ -624,7 +625,8 @@ struct TowerArgs {
     float hosc;
     const float *w0p;        // f16x3: packed (hi, lo) fragments of w0 over k = tap*3 + c, padded to 32 (nullptr: VALU conv0)
     float osc0;
-    float *hact;             // out: [sample][2*hc*HW] (unused since the head FCs run inside the tower, kept for diagnostics)
+    unsigned long long *stamp_out; // diagnostic build only.  Its place fixes the kernel-argument offsets of the fields below:
+                             // 8 bytes lower, hipcc fetches the FC weights with flat instead of global loads
     // head FCs + softmax / tanh inside the tower workgroup (head_fc_fused)
     const float *wfc, *bfc;  // packed FC weights [ntp+ntv][KP/16][64][4], bias [(ntp+ntv)*16]
     const float *wv1, *bv1;  // value FC1 [vf], [1]
@@ -638,8 +640,8 @@ struct TowerArgs {
     // tail handling (see nn_forward): role 0 = main launch, 1 / 2 = tail launches with fewer samples per workgroup
     int role, S_main, S_small, S_mid, S_big, S_huge, cus;
     int cut_round, cut_defer; // cut_n's rule for this step's list (0: every leaf)
-    unsigned long long *stamp_out; // diagnostic build only
 };
+static_assert(offsetof(TowerArgs, wfc) == 136, "see stamp_out: the fields from wfc on keep these kernel-argument offsets");
 
 // ------------------------------------------------------------------------------------
 // Head FCs + softmax / tanh for the S samples of a tower workgroup, straight from the head activations it has just staged in LDS
@@ -775,8 +777,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                 for (int i = tid; i < R * 16; i += NTHR) {
                     const int row = i >> 4, kk = (i & 15) * 2;
                     const int rb = rowbase_s[row];
-                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                    h2 hi, lo;
+                    f16x2 hi, lo;
 #pragma unroll
                     for (int q = 0; q < 2; q++) {
                         const int k = kk + q;
@@ -789,8 +790,8 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                         hi[q] = (_Float16)v;
                         lo[q] = (_Float16)(v - (float)hi[q]);
                     }
-                    *reinterpret_cast<h2 *>(Mh + (size_t)row * (MU * 8) + kk) = hi;
-                    *reinterpret_cast<h2 *>(Mh + (size_t)row * (MU * 8) + 32 + kk) = lo;
+                    *reinterpret_cast<f16x2 *>(Mh + (size_t)row * (MU * 8) + kk) = hi;
+                    *reinterpret_cast<f16x2 *>(Mh + (size_t)row * (MU * 8) + 32 + kk) = lo;
                 }
                 __syncthreads();
                 const int jr = lane & 15, gg = lane >> 4;
@@ -815,25 +816,9 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al.h, bh.h, acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah.h, bl.h, acc, 0, 0, 0);
                         f32x4 v = acc * a.osc0 + bv; // activation-scaled
-                        v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-                        vmax = fmaxf(vmax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-                        typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-                        typedef float f2v __attribute__((ext_vector_type(2)));
-                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                        union { h2v h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-                        for (int q = 0; q < 2; q++) {
-                            const f2v xx = {v[2 * q], v[2 * q + 1]};
-                            const h2v hh = __builtin_convertvector(xx, h2v);
-                            oh.h[q] = hh;
-                            ol.h[q] = __builtin_convertvector(xx - __builtin_convertvector(hh, f2v), h2v);
-                        }
-                        if (row < R) {
-                            const int col = cto * 16 + gg * 4;
-                            _Float16 *ph = dsth + (size_t)row * (S4 * 8) + col;
-                            *reinterpret_cast<u32x2 *>(ph) = oh.u;
-                            *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
-                        }
+                        v = relu4(v);
+                        vmax = fmaxf(vmax, max4(v));
+                        h3_store<C>(dsth + (size_t)row * (S4 * 8) + cto * 16 + gg * 4, row < R, v);
                     }
                     ovf |= vmax > F16_GUARD;
                 }
@@ -914,35 +899,26 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         (void)tb0; (void)tb1; (void)tk0; (void)tk1;
         f32x4 res[2][NTA]; // the residual stream of this wave's outputs (activation-scaled f32): conv_lds_h3_c2 / conv_lds_h3
         (void)res;
-        if constexpr (RR) {
-            // block 0's input = conv0's output, which other waves wrote: decode this wave's share once (one cout tile, wave & 3)
+        if constexpr (RR || C2) {
+            // block 0's input = conv0's output, which other waves wrote: decode this wave's share once -- the cout tile
+            // wave & 3 (RR) or the two tiles of its parity (C2)
             const _Float16 *xh = reinterpret_cast<const _Float16 *>(X4);
-            const int ctc = wave & 3;
-            if (ctc < C / 16) {
 #pragma unroll
-                for (int t = 0; t < NTA; t++) {
-                    const int row = min((tbase + t) * 16 + jrow, R - 1);
-                    const _Float16 *ph = xh + (size_t)row * (S4 * 8) + ctc * 16 + gq * 4;
+            for (int c = 0; c < (C2 ? 2 : 1); c++) {
+                const int col = (C2 ? (wave & 1) * 2 + c : wave & 3) * 16 + gq * 4;
+                if (col < C) {
 #pragma unroll
-                    for (int e = 0; e < 4; e++) res[0][t][e] = (float)ph[e] + (float)ph[C + e];
+                    for (int t = 0; t < NTA; t++) {
+                        const int row = min((tbase + t) * 16 + jrow, R - 1);
+                        const _Float16 *ph = xh + (size_t)row * (S4 * 8) + col;
+#pragma unroll
+                        for (int e = 0; e < 4; e++) res[c][t][e] = (float)ph[e] + (float)ph[C + e];
+                    }
                 }
             }
         }
         f32x4 *wring = nullptr; // C2: two-slot weight ring behind the two activation images
         if constexpr (C2) {
-            // block 0's input = conv0's output, which other waves wrote: decode this wave's share once
-            const _Float16 *xh = reinterpret_cast<const _Float16 *>(X4);
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const int col = ((wave & 1) * 2 + c) * 16 + gq * 4;
-#pragma unroll
-                for (int t = 0; t < NTA; t++) {
-                    const int row = min((tbase + t) * 16 + jrow, R - 1);
-                    const _Float16 *ph = xh + (size_t)row * (S4 * 8) + col;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) res[c][t][e] = (float)ph[e] + (float)ph[C + e];
-                }
-            }
             wring = Y4 + img_units;
             if (NL > 0) {
                 const f32x4 *d0 = tw4 + ((size_t)(wave >> 1) * (9 * (C / 32)) * 2 + (wave & 1)) * 64 + lane;
@@ -1374,26 +1350,21 @@ __global__ void __launch_bounds__(256) k_dense(DenseArgs h)
 }
 
 // ------------------------------------------------------------------------------------
-// heads
+// heads (SimpleNN; ResNetZero's run inside the tower workgroup: head_fc_fused)
 // ------------------------------------------------------------------------------------
 // Head FCs as one batched GEMM on f32 MFMA: a workgroup takes 16 samples;
 //   Out^T[out][sample] = Wfc[out][k] * hact^T[k][sample]
 // with A = FC weights pre-packed in fragment order ([job][k/16][lane][4], streamed from L2) and
-// B = the 16 samples' head activations staged in LDS (row stride = 2 mod 16 float4 units:
-// conflict-free ds_read_b128).  Jobs 0..ntp-1 are 16-output tiles of the policy FC, jobs
-// ntp.. of the value FC0.  Then softmax over the A logits (= exp(log_softmax), nn.py:159) and
-// tanh(FC1(relu(FC0))) per sample.
+// B = the 16 samples' head activations.  Jobs 0..ntp-1 are 16-output tiles of the policy FC, job
+// ntp holds the value FC (one output).  Then softmax over the A logits (= exp(log_softmax),
+// nn.py:159) and tanh(value_fc(x)) per sample (dots_boxes_nn.py:95: no hidden value layer).
 struct HeadArgs {
     const int32_t *list, *n_dev;
     const float *hact;      // [sample][2][K]
     const float *wfc;       // packed [ntp+ntv][KC][64][4]
     const float *bfc;       // [(ntp+ntv)*16] bias per GEMM output (0 for padding)
-    const float *wv1, *bv1; // value FC1 [vf], [1]
     float *P, *V;
-    int K, KP /*K padded to 16*/, RS4 /*LDS row stride, float4 units*/, ntp, ntv, vf, AS;
-    int value_direct; // SimpleNN: value = tanh(value_fc(x)), no hidden layer
-    int cut_round, cut_defer; // cut_n's rule (0: every leaf); n_used (optional) receives the count the step's network took
-    int32_t *n_used;
+    int K, KP /*K padded to 16*/, ntp, ntv, AS;
 };
 
 // K is split over the 4 waves (wave w owns the 16-wide k chunks kc = w, w+4, ...).  Nothing is staged:
@@ -1441,8 +1412,7 @@ __global__ void __launch_bounds__(256) k_head_fc(Geo g, HeadArgs h)
 {
     extern __shared__ __attribute__((aligned(16))) float ldsf[];
     constexpr int SPW = 16 * HEAD_MT; // samples per workgroup
-    const int n = cut_n(*h.n_dev, h.cut_round, h.cut_defer);
-    if (h.n_used && blockIdx.x == 0 && threadIdx.x == 0) *h.n_used = n; // k_expand_backup: list positions >= n ask again next step
+    const int n = *h.n_dev;
     const int j0 = blockIdx.x * SPW;
     if (j0 >= n) return;
     const int ns = min(SPW, n - j0);
@@ -1506,10 +1476,7 @@ __global__ void __launch_bounds__(256) k_head_fc(Geo g, HeadArgs h)
         for (int o = lane; o < A; o += 64) sum += expf(l[o] - mx);
         for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
         for (int o = lane; o < A; o += 64) h.P[(size_t)dst * h.AS + o] = expf(l[o] - mx) / sum;
-        float hv = 0.0f;
-        for (int u = lane; u < h.vf; u += 64) hv += fmaxf(l[h.ntp * 16 + u], 0.0f) * h.wv1[u];
-        for (int s = 32; s > 0; s >>= 1) hv += __shfl_xor(hv, s);
-        if (lane == 0) h.V[dst] = h.value_direct ? tanhf(l[h.ntp * 16]) : tanhf(hv + h.bv1[0]);
+        if (lane == 0) h.V[dst] = tanhf(l[h.ntp * 16]);
     }
 }
 
@@ -1616,6 +1583,62 @@ static bool bn_affine(NNState *nn, const std::string &p, int n, std::vector<doub
     return true;
 }
 
+// The f16x3 A operand of a weight matrix [couts][K] (16 | couts, 32 | K): the weights times 2^sw -- max|w| lands in
+// [2^13, 2^14), sw within +-24 -- rounded to float, split into (hi, lo) halves and laid out as the layer MFMA (16x16x32) reads
+// them: [couts/16][K/32][hi|lo][lane][8 halves] with cout = lane & 15, k = 8 (lane >> 4) + e of a 32-wide step.  Returns the
+// halves as the floats that are uploaded, and sw.  w(cout, k) is the BN-folded weight in double; it is asked for
+// cout < couts_used and k < k_used only, the padding stays zero (pack_conv's K is [tap][cin padded to C]: no single bound
+// describes its padding, so its w returns 0.0 there, which packs to the same zero halves and leaves max|w| alone).
+// pack_conv folds in double inside w; conv0 and the head convs hand in the folded weights already rounded to float (the
+// ones their VALU paths multiply with).
+template <typename F>
+static std::vector<float> pack_h3(int couts, int K, int couts_used, int k_used, F w, int &sw)
+{
+    double mx = 0;
+    for (int co = 0; co < couts_used; co++)
+        for (int k = 0; k < k_used; k++) mx = std::max(mx, fabs(w(co, k)));
+    sw = 0;
+    if (mx > 0) { int e; frexp(mx, &e); sw = 14 - e; }
+    sw = std::max(-24, std::min(24, sw));
+    const double wscale = ldexp(1.0, sw);
+    const int KS = K / 32;
+    std::vector<_Float16> hp((size_t)couts * K * 2, (_Float16)0.0f);
+    for (int ct = 0; ct < couts / 16; ct++)
+        for (int ks = 0; ks < KS; ks++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int e = 0; e < 8; e++) {
+                    const int co = ct * 16 + (lane & 15), k = ks * 32 + 8 * (lane >> 4) + e;
+                    if (co >= couts_used || k >= k_used) continue;
+                    const float v = (float)(w(co, k) * wscale);
+                    const _Float16 h = (_Float16)v;
+                    const size_t base = (((size_t)ct * KS + ks) * 2) * 64 * 8;
+                    hp[base + (size_t)lane * 8 + e] = h;
+                    hp[base + 64 * 8 + (size_t)lane * 8 + e] = (_Float16)(v - (float)h);
+                }
+    std::vector<float> asf(hp.size() / 2);
+    memcpy(asf.data(), hp.data(), hp.size() * 2);
+    return asf;
+}
+
+// The A operand of the 16-sample f32 MFMA GEMMs (k_dense, k_head_fc, head_fc_fused): [jobs][KP/16][64][4] with GEMM output
+// o = job * 16 + (lane & 15), k = kc * 16 + 4 (lane >> 4) + e.  row(o) is the K weights of output o, nullptr for a padding
+// output; k in [K, KP) is zero.
+template <typename F>
+static std::vector<float> pack_fc(int jobs, int KP, int K, F row)
+{
+    const int KC = KP / 16;
+    std::vector<float> pk((size_t)jobs * KC * 64 * 4, 0.0f);
+    for (int o = 0; o < jobs * 16; o++) {
+        const float *r = row(o);
+        if (!r) continue;
+        for (int k = 0; k < K; k++) {
+            const int job = o / 16, kc = k / 16, lane = (o & 15) + 16 * (k % 16 / 4), e = k % 4;
+            pk[(((size_t)job * KC + kc) * 64 + lane) * 4 + e] = r[k];
+        }
+    }
+    return pk;
+}
+
 // conv3x3 [C][C][3][3] + following BN -> packed fragment order [C/16][9][C/16][64][4]
 static bool pack_conv(NNState *nn, const std::string &conv, const std::string &bn, int C, std::vector<float> &pk_all,
                       std::vector<float> &bias_all, std::string &err, bool fold = true, std::vector<float> *pk32_all = nullptr,
@@ -1647,36 +1670,13 @@ static bool pack_conv(NNState *nn, const std::string &conv, const std::string &b
     if (pk32_all) pk32_all->insert(pk32_all->end(), pk.begin(), pk.end());
     if (bias32_all) bias32_all->insert(bias32_all->end(), bias.begin(), bias.end());
     if (nn->precision == 1) {
-        // f16x3: folded weights scaled by 2^sw so that max|w| lands in [2^13, 2^14), split into
-        // (hi, lo) halves, packed [ct][tap][ks][hi|lo][lane][8]; bias carries the activation scale
-        double mx = 0;
-        for (int co = 0; co < Cr; co++)
-            for (int ci = 0; ci < Cr; ci++)
-                for (int tap = 0; tap < 9; tap++) mx = std::max(mx, fabs((double)(*w)[((size_t)co * Cr + ci) * 9 + tap] * s[co]));
-        int sw = 0;
-        if (mx > 0) { int e; frexp(mx, &e); sw = 14 - e; }
-        if (sw > 24) sw = 24;
-        if (sw < -24) sw = -24;
-        const double wscale = ldexp(1.0, sw);
-        // fragment order of the layer MFMA (16x16x32): cout = lane & 15, k = 8 (lane >> 4) + e of a 32-wide step
-        const int KS = C / 32;
-        std::vector<_Float16> hp((size_t)C * C * 9 * 2, (_Float16)0.0f);
-        for (int ct = 0; ct < C / 16; ct++)
-            for (int tap = 0; tap < 9; tap++)
-                for (int ks = 0; ks < KS; ks++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int e = 0; e < 8; e++) {
-                            int co = ct * 16 + (lane & 15), ci = ks * 32 + 8 * (lane >> 4) + e;
-                            if (co >= Cr || ci >= Cr) continue;
-                            float v = (float)((double)(*w)[((size_t)co * Cr + ci) * 9 + tap] * s[co] * wscale);
-                            _Float16 h = (_Float16)v;
-                            _Float16 l = (_Float16)(v - (float)h);
-                            size_t base = ((((size_t)ct * 9 + tap) * KS + ks) * 2) * 64 * 8;
-                            hp[base + (size_t)lane * 8 + e] = h;
-                            hp[base + 64 * 8 + (size_t)lane * 8 + e] = l;
-                        }
-        const float *as_f = reinterpret_cast<const float *>(hp.data());
-        pk_all.insert(pk_all.end(), as_f, as_f + hp.size() / 2);
+        // f16x3: K runs [tap][cin], i.e. packed [ct][tap][ks][hi|lo][lane][8]; bias carries the activation scale
+        int sw;
+        const std::vector<float> hp = pack_h3(C, 9 * C, Cr, 9 * C, [&](int co, int k) {
+            const int tap = k / C, ci = k % C;
+            return ci < Cr ? (double)(*w)[((size_t)co * Cr + ci) * 9 + tap] * s[co] : 0.0;
+        }, sw);
+        pk_all.insert(pk_all.end(), hp.begin(), hp.end());
         for (int co = 0; co < C; co++) bias[co] *= ACT_SCALE;
         bias_all.insert(bias_all.end(), bias.begin(), bias.end());
         nn->osc_host.push_back((float)ldexp(1.0, -sw)); // acc = 2^(sw+ACT_SHIFT) * sum ; keep 2^ACT_SHIFT
@@ -1762,21 +1762,6 @@ static hipError_t tower_dispatch(NNState *nn, hipStream_t s, const TowerArgs &ta
     }
 }
 
-// packs a Linear [O][K] for the 16-sample MFMA GEMM: [O/16][K/16][64][4]
-static std::vector<float> pack_dense(const std::vector<float> &w, int O, int K)
-{
-    const int KC = K / 16;
-    std::vector<float> pk((size_t)O * K, 0.0f);
-    for (int job = 0; job < O / 16; job++)
-        for (int kc = 0; kc < KC; kc++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 4; e++) {
-                    int o = job * 16 + (lane & 15), k = kc * 16 + 4 * (lane >> 4) + e;
-                    pk[(((size_t)job * KC + kc) * 64 + lane) * 4 + e] = w[(size_t)o * K + k];
-                }
-    return pk;
-}
-
 static int dense_rs4(int K)
 {
     int rs4 = K / 4;
@@ -1839,11 +1824,11 @@ static int commit_simplenn(NNState *nn, std::string &err)
         std::vector<double> s0, t0, s1, t1;
         if (!bn_affine(nn, "bn_fc0", 512, s0, t0, err)) return DBAZ_EINVAL;
         if (!bn_affine(nn, "bn_fc1", 256, s1, t1, err)) return DBAZ_EINVAL;
-        nn->sn_w0 = nn_upload(nn, pack_dense(*w0, 512, 1024));
+        nn->sn_w0 = nn_upload(nn, pack_fc(512 / 16, 1024, 1024, [&](int o) { return w0->data() + (size_t)o * 1024; }));
         nn->sn_b0 = nn_upload(nn, *b0);
         nn->sn_ps0 = nn_upload(nn, f32v(s0));
         nn->sn_pt0 = nn_upload(nn, f32v(t0));
-        nn->sn_w1 = nn_upload(nn, pack_dense(*w1, 256, 512));
+        nn->sn_w1 = nn_upload(nn, pack_fc(256 / 16, 512, 512, [&](int o) { return w1->data() + (size_t)o * 512; }));
         nn->sn_b1 = nn_upload(nn, *b1);
         nn->sn_ps1 = nn_upload(nn, f32v(s1));
         nn->sn_pt1 = nn_upload(nn, f32v(t1));
@@ -1854,26 +1839,15 @@ static int commit_simplenn(NNState *nn, std::string &err)
         auto bp = sd_get(nn, "policy_fc.bias", 32, err); if (!bp) return DBAZ_EINVAL;
         auto wv = sd_get(nn, "value_fc.weight", 256, err); if (!wv) return DBAZ_EINVAL;
         auto bv = sd_get(nn, "value_fc.bias", 1, err); if (!bv) return DBAZ_EINVAL;
-        const int K = 256, KC = K / 16, ntp = 2, ntv = 1, NJ = 3;
-        std::vector<float> pk((size_t)NJ * KC * 64 * 4, 0.0f), bias((size_t)NJ * 16, 0.0f);
-        for (int job = 0; job < NJ; job++)
-            for (int kc = 0; kc < KC; kc++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 4; e++) {
-                        int o = (job < ntp ? job : 0) * 16 + (lane & 15), k = kc * 16 + 4 * (lane >> 4) + e;
-                        float v = 0.0f;
-                        if (job < ntp) v = (*wp)[(size_t)o * K + k];
-                        else if ((lane & 15) == 0) v = (*wv)[k];
-                        pk[(((size_t)job * KC + kc) * 64 + lane) * 4 + e] = v;
-                    }
+        const int K = 256, ntp = 2, ntv = 1, NJ = 3; // outputs 0..31: the policy, 32: the value, the rest of job 2: padding
+        std::vector<float> bias((size_t)NJ * 16, 0.0f);
         for (int i = 0; i < 32; i++) bias[i] = (*bp)[i];
         bias[32] = (*bv)[0];
-        nn->wfc = nn_upload(nn, pk);
+        nn->wfc = nn_upload(nn, pack_fc(NJ, K, K, [&](int o) -> const float * {
+            return o < 32 ? wp->data() + (size_t)o * K : o == 32 ? wv->data() : nullptr;
+        }));
         nn->bfc = nn_upload(nn, bias);
-        std::vector<float> one(1, 0.0f);
-        nn->wv1 = nn_upload(nn, one);
-        nn->bv1 = nn_upload(nn, one);
-        nn->KP = K; nn->ntp = ntp; nn->ntv = ntv; nn->RS4 = dense_rs4(K);
+        nn->KP = K; nn->ntp = ntp; nn->ntv = ntv;
         nn->fc_lds = ((size_t)4 * 16 * HEAD_MT * NJ * 16 + (size_t)16 * HEAD_MT * (NJ * 16 + 1)) * 4;
     }
     nn->sn_flat = nn_alloc<float>(nn, (size_t)nn->max_batch * 1024);
@@ -1928,32 +1902,13 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         nn->w0 = nn_upload(nn, pk);
         nn->b0 = nn_upload(nn, bias);
         nn->w0p = nullptr;
-        if (nn->precision == 1 && C >= 32) {
-            double mx = 0;
-            for (float v : pk) mx = std::max(mx, fabs((double)v));
-            int sw = 0;
-            if (mx > 0) { int e; frexp(mx, &e); sw = 14 - e; }
-            sw = std::max(-24, std::min(24, sw));
-            const double wscale = ldexp(1.0, sw);
-            const int n_ct = C / 16;
-            std::vector<_Float16> hp((size_t)n_ct * 2 * 64 * 8, (_Float16)0.0f);
-            for (int ct = 0; ct < n_ct; ct++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 8; e++) {
-                        const int co = ct * 16 + (lane & 15), k = 8 * (lane >> 4) + e;
-                        if (k >= 27) continue;
-                        const float v = (float)((double)pk[(size_t)k * C + co] * wscale);
-                        const _Float16 h = (_Float16)v;
-                        const size_t base = (size_t)ct * 2 * 64 * 8;
-                        hp[base + (size_t)lane * 8 + e] = h;
-                        hp[base + 64 * 8 + (size_t)lane * 8 + e] = (_Float16)(v - (float)h);
-                    }
-            std::vector<float> asf(hp.size() / 2);
-            memcpy(asf.data(), hp.data(), hp.size() * 2);
-            nn->w0p = nn_upload(nn, asf);
+        if (nn->precision == 1 && C >= 32) { // one K=32 step over k = tap*3 + c
+            int sw;
+            nn->w0p = nn_upload(nn, pack_h3(C, 32, C, 27, [&](int co, int k) { return (double)pk[(size_t)k * C + co]; }, sw));
             nn->osc0 = (float)ldexp(1.0, -sw);
         }
     }
+    // tower: 2*blocks conv3x3 + BN folded
     {
         std::vector<float> pk_all, bias_all, pk32_all, bias32_all;
         const bool both = nn->precision == 1 && C >= 32; // f16x3 handles keep the exact-f32 operands too (safety net)
@@ -2004,75 +1959,37 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         nn->hwp = nullptr;
         const int OCP = (2 * hc + 15) & ~15, n_ct = OCP / 16;
         if (nn->precision == 1 && C >= 32 && (n_ct == 1 || n_ct == 2 || n_ct == 4 || n_ct == 8)) {
-            // same operand format as the tower layers (pack_conv): weights * 2^sw_h split into halves
-            double mx = 0;
-            for (float v : hw) mx = std::max(mx, fabs((double)v));
-            int sw = 0;
-            if (mx > 0) { int e; frexp(mx, &e); sw = 14 - e; }
-            sw = std::max(-24, std::min(24, sw));
-            const double wscale = ldexp(1.0, sw);
-            const int KS = C / 32;
-            std::vector<_Float16> hp((size_t)n_ct * KS * 2 * 64 * 8, (_Float16)0.0f);
-            for (int ct = 0; ct < n_ct; ct++)
-                for (int ks = 0; ks < KS; ks++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int e = 0; e < 8; e++) {
-                            const int oc = ct * 16 + (lane & 15), ci = ks * 32 + 8 * (lane >> 4) + e;
-                            if (oc >= 2 * hc) continue;
-                            const float v = (float)((double)hw[(size_t)oc * C + ci] * wscale);
-                            const _Float16 h = (_Float16)v;
-                            const size_t base = (((size_t)ct * KS + ks) * 2) * 64 * 8;
-                            hp[base + (size_t)lane * 8 + e] = h;
-                            hp[base + 64 * 8 + (size_t)lane * 8 + e] = (_Float16)(v - (float)h);
-                        }
-            std::vector<float> asf(hp.size() / 2);
-            memcpy(asf.data(), hp.data(), hp.size() * 2);
-            nn->hwp = nn_upload(nn, asf);
+            // same operand format as the tower layers with a single tap: K = cin
+            int sw;
+            nn->hwp = nn_upload(nn, pack_h3(OCP, C, 2 * hc, C, [&](int oc, int ci) { return (double)hw[(size_t)oc * C + ci]; }, sw));
             nn->hosc = (float)ldexp(1.0, -(sw + ACT_SHIFT));
         }
+    }
+    // head FCs: policy FC and value FC0 as the jobs of one GEMM, value FC1 as it is
+    {
         auto wp = sd_get(nn, "policy_head.fc.weight", (size_t)A * K, err); if (!wp) return DBAZ_EINVAL;
         auto bp = sd_get(nn, "policy_head.fc.bias", A, err); if (!bp) return DBAZ_EINVAL;
         auto w0 = sd_get(nn, "value_head.fc0.weight", (size_t)vf * K, err); if (!w0) return DBAZ_EINVAL;
         auto b0 = sd_get(nn, "value_head.fc0.bias", vf, err); if (!b0) return DBAZ_EINVAL;
         auto w1 = sd_get(nn, "value_head.fc1.weight", vf, err); if (!w1) return DBAZ_EINVAL;
         auto b1 = sd_get(nn, "value_head.fc1.bias", 1, err); if (!b1) return DBAZ_EINVAL;
-        const int KP = (K + 15) & ~15, KC = KP / 16;
-        const int ntp = (A + 15) / 16, ntv = (vf + 15) / 16, NJ = ntp + ntv;
-        std::vector<float> pk((size_t)NJ * KC * 64 * 4, 0.0f), bias((size_t)NJ * 16, 0.0f);
-        for (int job = 0; job < NJ; job++) {
-            const bool pol = job < ntp;
-            const int tile = pol ? job : job - ntp, nout = pol ? A : vf;
-            const std::vector<float> &wm = pol ? *wp : *w0;
-            for (int kc = 0; kc < KC; kc++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 4; e++) {
-                        int o = tile * 16 + (lane & 15), k = kc * 16 + 4 * (lane >> 4) + e;
-                        if (o < nout && k < K) pk[(((size_t)job * KC + kc) * 64 + lane) * 4 + e] = wm[(size_t)o * K + k];
-                    }
-            for (int i = 0; i < 16; i++) {
-                int o = tile * 16 + i;
-                if (o < nout) bias[job * 16 + i] = pol ? (*bp)[o] : (*b0)[o];
-            }
-        }
-        nn->wfc = nn_upload(nn, pk);
+        const int KP = (K + 15) & ~15, ntp = (A + 15) / 16, ntv = (vf + 15) / 16, NJ = ntp + ntv;
+        // a limit of the engine, not of a kernel: at most 31 sixteen-output FC jobs
+        if (NJ >= 32) { err = "head FC tile does not fit LDS"; return DBAZ_EINVAL; }
+        // jobs 0..ntp-1: 16-output tiles of the policy FC, jobs ntp..: of the value FC0
+        std::vector<float> bias((size_t)NJ * 16, 0.0f);
+        for (int o = 0; o < A; o++) bias[o] = (*bp)[o];
+        for (int o = 0; o < vf; o++) bias[ntp * 16 + o] = (*b0)[o];
+        nn->wfc = nn_upload(nn, pack_fc(NJ, KP, K, [&](int o) -> const float * {
+            if (o < ntp * 16) return o < A ? wp->data() + (size_t)o * K : nullptr;
+            return o - ntp * 16 < vf ? w0->data() + (size_t)(o - ntp * 16) * K : nullptr;
+        }));
         nn->bfc = nn_upload(nn, bias);
         nn->wv1 = nn_upload(nn, *w1);
         nn->bv1 = nn_upload(nn, *b1);
         nn->KP = KP; nn->ntp = ntp; nn->ntv = ntv;
-        int rs4 = KP / 4;
-        rs4 = ((rs4 + 15) / 16) * 16 + 2; // = 2 mod 16 float4 units
-        nn->RS4 = rs4;
-        nn->fc_lds = ((size_t)4 * 16 * HEAD_MT * NJ * 16 + (size_t)16 * HEAD_MT * (NJ * 16 + 1)) * 4;
-        if (nn->fc_lds > 158 * 1024) { err = "head FC tile does not fit LDS"; return DBAZ_EINVAL; }
-        if (hipFuncSetAttribute((const void *)k_head_fc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->fc_lds) != hipSuccess) {
-            err = "hipFuncSetAttribute(k_head_fc) failed"; return DBAZ_EDEVICE;
-        }
     }
-    // k_head_fc reads whole 16-float chunks: up to 15 floats past a row's K when K % 16 != 0 (their weights are
-    // zero, so the values only have to be finite): slack at the end, everything zero-initialised
-    nn->hact = nn_alloc<float>(nn, (size_t)nn->max_batch * 2 * K + 16);
-    if (nn->hact) (void)hipMemset(nn->hact, 0, ((size_t)nn->max_batch * 2 * K + 16) * sizeof(float));
-    if (!nn->hact || !nn->wv1 || !nn->w0) { err = "hipMalloc failed (network buffers)"; return DBAZ_EDEVICE; }
+    if (!nn->wfc || !nn->wv1 || !nn->w0) { err = "hipMalloc failed (network buffers)"; return DBAZ_EDEVICE; }
     // conv workgroup geometry: S whole samples, NT position tiles of 16 rows (<= MAXT)
     const size_t lds_budget = 158 * 1024; // of 160 KiB: two ping-pong activation images
     // the idle image doubles as staging for conv0 (padded planes + 27*C weights) and the head convs
@@ -2096,15 +2013,13 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
     // tail variants: <2,2> holds 64 rows, <4,4> 128 rows, <5,5> 160 rows
     nn->S_small = nn->S_mid = nn->S_big = 0;
     if (nn->NTT == 7) {
+        // S >= 1, so S_big >= 0; the two below it go negative where the one above is 0 (a single sample of > 160 rows)
         nn->S_big = std::min(160 / HW, nn->S - 1);
-        nn->S_mid = std::min(128 / HW, nn->S_big - 1);
-        nn->S_small = std::min(64 / HW, nn->S_mid - 1);
-        if (nn->S_big < 0) nn->S_big = 0;
+        nn->S_mid = std::max(0, std::min(128 / HW, nn->S_big - 1));
+        nn->S_small = std::max(0, std::min(64 / HW, nn->S_mid - 1));
     } else if (nn->NTT == 4) {
         nn->S_small = std::min(64 / HW, nn->S - 1);
     }
-    if (nn->S_mid < 0) nn->S_mid = 0;
-    if (nn->S_small < 0) nn->S_small = 0;
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
@@ -2149,7 +2064,7 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
                 float *P, float *V, int AS, hipEvent_t ev_begin, hipEvent_t ev_end, int cut_round, int cut_defer, int32_t *n_used)
 {
     const Geo &g = nn->g;
-    const int hc = nn->hc, HW = g.HW;
+    const int hc = nn->hc;
     if (max_n > nn->max_batch) max_n = nn->max_batch;
     if (nn->kind == DBAZ_EVAL_SIMPLENN) {
         SimpleArgs sa;
@@ -2170,15 +2085,14 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
         d1.out = nn->hact; d1.K = 512; d1.O = 256; d1.RS4 = dense_rs4(512); d1.dup = 1;
         hipLaunchKernelGGL(k_dense, dim3((max_n + 15) / 16), dim3(256), (size_t)16 * d1.RS4 * 16, s, d1);
         HeadArgs ha;
-        ha.list = list_dev; ha.n_dev = n_dev; ha.hact = nn->hact; ha.wfc = nn->wfc; ha.bfc = nn->bfc; ha.wv1 = nn->wv1; ha.bv1 = nn->bv1;
-        ha.P = P; ha.V = V; ha.K = 256; ha.KP = 256; ha.RS4 = nn->RS4; ha.ntp = nn->ntp; ha.ntv = nn->ntv; ha.vf = 0; ha.AS = AS;
-        ha.value_direct = 1; ha.cut_round = 0; ha.cut_defer = 0; ha.n_used = nullptr;
+        ha.list = list_dev; ha.n_dev = n_dev; ha.hact = nn->hact; ha.wfc = nn->wfc; ha.bfc = nn->bfc;
+        ha.P = P; ha.V = V; ha.K = 256; ha.KP = 256; ha.ntp = nn->ntp; ha.ntv = nn->ntv; ha.AS = AS;
         hipLaunchKernelGGL(k_head_fc, dim3((max_n + 16 * HEAD_MT - 1) / (16 * HEAD_MT)), dim3(256), nn->fc_lds, s, g, ha);
         return;
     }
     TowerArgs ta;
     ta.feat = feat; ta.list = list_dev; ta.n_dev = n_dev; ta.in_s = nn->in_s; ta.in_t = nn->in_t; ta.w0 = nn->w0; ta.b0 = nn->b0;
-    ta.tw = nn->tw; ta.tb = nn->tb; ta.tosc = nn->tosc; ta.hw = nn->hw; ta.hb = nn->hb; ta.hwp = nn->hwp; ta.hosc = nn->hosc; ta.w0p = nn->w0p; ta.osc0 = nn->osc0; ta.hact = nn->hact;
+    ta.tw = nn->tw; ta.tb = nn->tb; ta.tosc = nn->tosc; ta.hw = nn->hw; ta.hb = nn->hb; ta.hwp = nn->hwp; ta.hosc = nn->hosc; ta.w0p = nn->w0p; ta.osc0 = nn->osc0;
     ta.overflow = nn->overflow; ta.ovf_flags = nn->ovf_flags; ta.fallback = 0; ta.S = nn->S; ta.nblocks = nn->blocks; ta.hc = hc;
     ta.wfc = nn->wfc; ta.bfc = nn->bfc; ta.wv1 = nn->wv1; ta.bv1 = nn->bv1; ta.P = P; ta.V = V; ta.KP = nn->KP; ta.ntp = nn->ntp;
     ta.ntv = nn->ntv; ta.vf = nn->vf; ta.AS = AS; ta.n_used = n_used;
@@ -2221,7 +2135,6 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
     }
     if (ev_end) (void)hipEventRecord(ev_end, s);
     // (the head FCs, softmax and tanh ran inside the tower workgroups: head_fc_fused)
-    (void)HW;
 }
 
 void nn_round_info(const NNState *nn, int *round, int *rem_max)
@@ -2244,8 +2157,6 @@ double nn_flops_per_sample(const NNState *nn)
     f += 2.0 * 2.0 * HW * C * hc + 2.0 * K * g.A + 2.0 * K * nn->vf + 2.0 * nn->vf;
     return f;
 }
-
-const char *nn_tower_kernel_name(const NNState *nn) { (void)nn; return "k_tower"; }
 
 // diagnostic build: copies the stamp sums of the last launch to the host
 int nn_read_stamps(NNState *nn, unsigned long long *out, int n_wg)

@@ -896,7 +896,7 @@ __global__ void __launch_bounds__(1024) k_order_evals(TreeBufs B, int n_slots, i
 // Full rounds only (SearchCfg.eval_round > 0).  A network launch costs whole rounds of workgroups (nn.hip): 5 306 leaves are four
 // rounds of 1 280 and a remainder round that costs 40 % of a round for 3.5 % of the leaves.  When at most eval_defer_max leaves
 // would be left behind the last full round, the network kernels take only the full rounds (nn.hip cut_n: every kernel of the step
-// applies the same rule to the same count; k_head_fc leaves the count in n_eval[2]); the slots behind the cut keep their selected
+// applies the same rule to the same count; k_tower leaves the count in n_eval[2]); the slots behind the cut keep their selected
 // leaf -- k_expand_backup sets Slot::pending -- and ask again in the next step, at the head of the list (k_order_evals).  Every game
 // plays the same moves: only WHEN a slot's simulation completes changes.
 
