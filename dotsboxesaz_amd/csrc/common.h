@@ -135,6 +135,8 @@ struct SearchCfg {
                              // (dropped nodes then live on as transposition twins until their memory is needed); 0 = two per simulation
 };
 
+struct GState; // rules.h
+
 // device buffer bundle handed to the tree kernels
 struct TreeBufs {
     uint32_t *nodes;   // [n_slots][cap][node_dw]
@@ -187,6 +189,9 @@ struct TreeBufs {
     const double *script_noise;  // [n_script][E+1][A] or null
     const uint8_t *script_has_noise; // [n_script]
     int n_script;
+    // start positions of this run's games (dbaz_selfplay_set_start): game g is born as start_states[(g / games_per_start) % n_starts]
+    const GState *start_states; // [n_starts] ready-made states (built and checked on the host); n_starts == 0: the empty board
+    int n_starts, games_per_start;
 };
 
 #define HIP_CHECK_RET(e, call)                                                                 \

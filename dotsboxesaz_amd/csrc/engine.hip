@@ -16,6 +16,7 @@
 #include "common.h"
 #include "nn.h"
 #include "replay.h"
+#include "rules.h"
 #include "tree.h"
 
 static thread_local std::string g_create_error; // message of a failed dbaz_create (no handle to keep it in); per thread
@@ -54,6 +55,11 @@ struct dbaz_engine {
     int64_t script_first = -1;
     int n_script = 0;
     std::vector<int32_t> ff_plies, ff_reads, quick_plies;
+    // start positions of the next dbaz_selfplay_start (dbaz_selfplay_set_start): checked host copy until that call uploads it
+    std::vector<GState> start_states;
+    int start_gps = 1;
+    GState *start_dev = nullptr; // the one table buffer of the handle, reallocated only when a larger book arrives
+    size_t start_cap = 0;        // entries
     SlotSummary *d_sum = nullptr;
     bool selfplay = false;
     bool late_join = false; // the driver pass is joined behind the network launch instead of in front of it (sim_step)
@@ -349,6 +355,7 @@ extern "C" void dbaz_destroy(dbaz_engine *e)
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->stage) (void)hipFree(e->stage);
     if (e->replay_dev) (void)hipFree(e->replay_dev);
+    if (e->start_dev) (void)hipFree(e->start_dev);
     for (int i = 0; i < DBAZ_MAX_DATASETS; i++) if (e->rds_all[i]) rds_destroy(e->rds_all[i]);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     if (e->ev_t0) (void)hipEventDestroy(e->ev_t0);
@@ -577,6 +584,7 @@ extern "C" int dbaz_set_positions(dbaz_engine *e, const int16_t *moves, const in
     if ((moves == nullptr) != (offsets == nullptr)) return set_error(e, DBAZ_EINVAL, "moves and offsets must both be given");
     e->selfplay = false;
     e->search_open = false;
+    e->B.start_states = nullptr; e->B.n_starts = 0; e->B.games_per_start = 1; // a finished run's table is not in effect here
     const int16_t *d_m = nullptr;
     const int32_t *d_o = nullptr;
     if (offsets) {
@@ -969,6 +977,43 @@ extern "C" int dbaz_selfplay_fastforward(dbaz_engine *e, const int32_t *plies)
     return DBAZ_OK;
 }
 
+extern "C" int dbaz_selfplay_set_start(dbaz_engine *e, const int16_t *moves, const int32_t *offsets, int32_t n_starts,
+                                       int32_t games_per_start)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (n_starts < 0 || n_starts > DBAZ_MAX_STARTS)
+        return set_error(e, DBAZ_EINVAL, "n_starts = %d is outside 0..%d", n_starts, DBAZ_MAX_STARTS);
+    if (games_per_start < 1) return set_error(e, DBAZ_EINVAL, "games_per_start = %d must be >= 1", games_per_start);
+    if (n_starts > 0 && !offsets) return set_error(e, DBAZ_EINVAL, "offsets must be given for n_starts > 0");
+    if (e->selfplay) {
+        // the running games' kernels read the table of their own dbaz_selfplay_start: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    const Geo &g = e->g;
+    std::vector<GState> states((size_t)n_starts);
+    for (int s = 0; s < n_starts; s++) {
+        const int lo = offsets[s], hi = offsets[s + 1];
+        if (lo < 0 || hi < lo) return set_error(e, DBAZ_EINVAL, "offsets must not be negative or descending (start %d: %d..%d)", s, lo, hi);
+        if (hi > lo && !moves) return set_error(e, DBAZ_EINVAL, "moves must be given (start %d has %d)", s, hi - lo);
+        GState st;
+        gs_init(g, st);
+        for (int i = lo; i < hi; i++) {
+            if (gs_play(g, st, moves[i], nullptr) < 0)
+                return set_error(e, DBAZ_EILLEGAL, "Illegal move %d (start %d, ply %d)", (int)moves[i], s, i - lo);
+        }
+        if (gs_result(st) != DBAZ_RESULT_NONE)
+            return set_error(e, DBAZ_EINVAL, "start %d is a finished game (result %d after %d plies)", s, gs_result(st), hi - lo);
+        states[s] = st;
+    }
+    e->start_states.swap(states);
+    e->start_gps = games_per_start;
+    return DBAZ_OK;
+}
+
 extern "C" int dbaz_selfplay_stagger(dbaz_engine *e, const int32_t *first_reads)
 {
     if (!e || !first_reads) return e ? set_error(e, DBAZ_EINVAL, "null argument") : DBAZ_EINVAL;
@@ -998,9 +1043,30 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
         return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
     if (e->sc.match_play && (e->sc.evaluator2 == DBAZ_EVAL_RESNET || e->sc.evaluator2 == DBAZ_EVAL_SIMPLENN) && !nn_ready(e->nns[1]))
         return set_error(e, DBAZ_ESTATE, "network weights of model 1 not committed (dbaz_nn_select_model(1), dbaz_nn_commit)");
+    if (!e->start_states.empty() && !e->ff_plies.empty()) {
+        e->start_states.clear();
+        e->ff_plies.clear();
+        return set_error(e, DBAZ_EINVAL, "dbaz_selfplay_set_start and dbaz_selfplay_fastforward both name the games' first position; both dropped");
+    }
+    if (!e->start_states.empty() && first_game_idx < 0)
+        return set_error(e, DBAZ_EINVAL, "start positions are assigned by the absolute game index: first_game_idx = %lld < 0", (long long)first_game_idx);
     TreeBufs &B = e->B;
     hipStream_t s = e->stream;
     HIP_CHECK_RET(e, hipStreamSynchronize(s));
+    // start table: consumed here; without one every game is born on the empty board
+    B.start_states = nullptr; B.n_starts = 0; B.games_per_start = 1;
+    if (!e->start_states.empty()) {
+        const size_t n = e->start_states.size();
+        if (n > e->start_cap) {
+            if (e->start_dev) HIP_CHECK_RET(e, hipFree(e->start_dev));
+            e->start_dev = nullptr; e->start_cap = 0;
+            HIP_CHECK_RET(e, hipMalloc((void **)&e->start_dev, n * sizeof(GState)));
+            e->start_cap = n;
+        }
+        HIP_CHECK_RET(e, hipMemcpy(e->start_dev, e->start_states.data(), n * sizeof(GState), hipMemcpyHostToDevice));
+        B.start_states = e->start_dev; B.n_starts = (int)n; B.games_per_start = e->start_gps;
+        e->start_states.clear();
+    }
     B.first_game = first_game_idx;
     B.last_game = first_game_idx + n_games;
     long long next = first_game_idx + std::min<int64_t>(n_games, e->n_slots);

@@ -1407,7 +1407,7 @@ __device__ int reroot(const Geo &g, const TreeBufs &B, int slot, Slot *S, uint32
     return 0;
 }
 
-// reset slot to a fresh game from the empty board (create_root_uct_node(BoxesState()))
+// reset slot to a fresh game from the empty board (create_root_uct_node(BoxesState())) or from its entry of the start table
 __device__ void fresh_game(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                            uint32_t *pool, long long game_idx, int lane)
 {
@@ -1415,7 +1415,10 @@ __device__ void fresh_game(const Geo &g, const SearchCfg &cfg, const TreeBufs &B
     gs_init(g, st);
     int ff = S->ff_plies;
     int plies = 0;
-    if (ff > 0) {
+    if (B.n_starts > 0) {
+        // play_games(game_state, idxs): the start table's entry of this game (uniform over the lanes; never combined with ff_plies)
+        st = B.start_states[(game_idx / B.games_per_start) % B.n_starts];
+    } else if (ff > 0) {
         // synthetic mid-game population (benchmark only): uniformly random legal plies
         uint2 key = make_uint2((uint32_t)cfg.seed ^ 0xA5A5A5A5u, (uint32_t)(cfg.seed >> 32));
         for (int t = 0; t < ff; t++) {

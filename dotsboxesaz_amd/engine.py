@@ -291,6 +291,23 @@ class Engine:
         assert pl.shape == (self.n_slots,)
         self._ck(self._L.dbaz_selfplay_quickplay(self.h, _p(pl), int(reads)))
 
+    def selfplay_set_start(self, move_lists, games_per_start=1):
+        """Start positions of the NEXT selfplay_start (SelfPlay.play_games(game_state, idxs)): move_lists is a list of move
+        sequences from the empty board (one flat sequence = one start for every game; None or [] = none, the empty board).
+        Game g starts from move_lists[(g // games_per_start) % len(move_lists)], g being the absolute game index; move_idx,
+        temperature schedule and scripts count plies from the start position.  ValueError for an illegal move (names start
+        and ply), DbazError for a finished start or while games are being played."""
+        if move_lists is None or len(move_lists) == 0:
+            self._ck(self._L.dbaz_selfplay_set_start(self.h, None, None, 0, int(games_per_start)))
+            return
+        if np.ndim(move_lists[0]) == 0:
+            move_lists = [move_lists]
+        off = np.zeros(len(move_lists) + 1, np.int32)
+        off[1:] = np.cumsum([len(m) for m in move_lists])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(m, np.int16).ravel() for m in move_lists] +
+                                                   [np.zeros(1, np.int16)]), np.int16)
+        self._ck(self._L.dbaz_selfplay_set_start(self.h, _p(flat), _p(off), len(move_lists), int(games_per_start)))
+
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
 

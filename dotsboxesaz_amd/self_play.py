@@ -28,6 +28,41 @@ def shard_games(n_games, world_size, rank):
     return first, base + (1 if rank < extra else 0)
 
 
+def start_index(game_idx, n_starts, games_per_start=1):
+    """Which start position of a book of n_starts game `game_idx` (the ABSOLUTE index; scalar or numpy array) begins from:
+    games_per_start consecutive games share a start, and the book wraps round (dbaz_selfplay_set_start)."""
+    return (np.asarray(game_idx) // int(games_per_start)) % int(n_starts)
+
+
+def start_moves(game_state, rows, cols):
+    """The move sequence from the empty board that dbaz_selfplay_set_start needs, of a reference-style game_state (the
+    mirror BoxesState records it in `_moves`) or of a plain move sequence.  None / a state on the empty board: [].
+    TypeError for a position that does not say how it was reached (a set of edges determines neither to_play nor
+    boxes_to_close); ValueError for a state of another board size."""
+    if game_state is None:
+        return []
+    moves = getattr(game_state, "_moves", None)
+    if moves is not None:
+        dim = getattr(game_state, "_dim", None)
+        if dim is not None and tuple(dim) != (rows, cols):
+            raise ValueError("game_state is a %dx%d board, the engine plays %dx%d" % (dim[0], dim[1], rows, cols))
+        return [int(m) for m in moves]
+    if hasattr(game_state, "board") or hasattr(game_state, "get_features"):
+        if hasattr(game_state, "board"):
+            played = np.asarray(game_state.board) // 255  # what get_features shows (dots_boxes_game.py:96-100)
+            shape = played.shape[-2:]
+        else:
+            feats = np.asarray(game_state.get_features())
+            played, shape = feats[:2], feats.shape[-2:]
+        if tuple(shape) != (rows + 1, cols + 1):
+            raise ValueError("game_state is a %dx%d board, the engine plays %dx%d" % (shape[0] - 1, shape[1] - 1, rows, cols))
+        if not played.any():
+            return []
+        raise TypeError("game_state is not the empty board and does not record its moves (`_moves`, as dotsboxesaz_amd.game."
+                        "BoxesState does): the edges alone determine neither to_play nor boxes_to_close")
+    return [int(m) for m in game_state]  # a plain move sequence
+
+
 def engine_kwargs_from_params(params, async_searches=False):
     """Pull the hot-path knobs out of a reference-style params dict (configuration.py:82-100).
 
@@ -87,19 +122,23 @@ class SelfPlay:
         self.engine = getattr(nn, "engine", nn)
         self.samples = None
 
-    def play_games_sync(self, games_idxs):
+    def play_games_sync(self, games_idxs, game_state=None):
+        """game_state: the position every game starts from (self_play.py:51-55; None = the empty board); move_idx and the
+        temperature schedule count from it."""
         idx = np.asarray(list(games_idxs), dtype=np.int64)
+        moves = start_moves(game_state, self.engine.rows, self.engine.cols)
         if len(idx) == 0:
             return
         if not np.array_equal(idx, np.arange(idx[0], idx[0] + len(idx))):
             raise ValueError("game indices must be a contiguous range")
+        self.engine.selfplay_set_start([moves] if moves else None)
         self.engine.selfplay_start(len(idx), int(idx[0]))
         self.engine.run()
         got = self.engine.fetch_samples()
         self.samples = got if self.samples is None else {k: np.concatenate([self.samples[k], got[k]]) for k in got}
 
     async def play_games(self, game_state, games_idxs, show_progress=False):
-        self.play_games_sync(games_idxs)
+        self.play_games_sync(games_idxs, game_state)
 
     def get_datasets(self, generation, with_features=True):
         e = self.engine
@@ -118,7 +157,8 @@ def write_dataset(file_name, key, df):
 
 
 def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_workers=None, games_per_workers=10,
-                   rows=None, cols=None, n_slots=None, device=0, dist=None, nn_precision=None, async_searches=False):
+                   rows=None, cols=None, n_slots=None, device=0, dist=None, nn_precision=None, async_searches=False,
+                   start_states=None, games_per_start=1):
     """Reference: self_play.generate_games (self_play.py:291-306) called from coach.selfplay
     (coach.py:27-29).  Plays n_games with generation-1's weights (random init for generation 0,
     self_play.py:187-190) and appends the samples (+ `training` = 0) to key "fresh".
@@ -130,7 +170,10 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     nn_precision: None = the engine's default for the network (ResNetZero: 1, the f16x3 mode every published number of this
     repository is measured in; 0 = exact f32 MFMA, 2.6x slower).
     async_searches: honour params.self_play.mcts.max_async_searches (see engine_kwargs_from_params; default: sequential search
-    per game, batching across games)."""
+    per game, batching across games).
+    start_states: a book of start positions (move sequences from the empty board, or mirror BoxesStates): game g starts from
+    start_states[start_index(g, len(start_states), games_per_start)], g being the absolute game index, so a game's rows stay
+    a function of (seed, game index) however the games are sharded over ranks.  None: the empty board."""
     from .engine import Engine
     game = _get(params, "game")
     if rows is None:
@@ -148,6 +191,8 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     try:
         if model.kind in ("resnet", "simplenn"):
             eng.load_state_dict(model.state_dict(), model.kind, **model.shape)
+        if start_states is not None and len(start_states) and count > 0:
+            eng.selfplay_set_start([start_moves(st, rows, cols) for st in start_states], games_per_start)
         packed = collect_rows_device(eng, count, first)
         if dist is not None and world > 1:
             packed, _ = all_gather_rows(packed, dist)
@@ -315,13 +360,16 @@ def match_winners(samples, generations):
 
 
 def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=None, cols=None, n_slots=None, device=0,
-                nn_precision=None):
+                nn_precision=None, openings=None):
     """Reference: self_play.compute_elo(elo_params, [params0, params1], [gen0, gen1], (elo0, elo1)).
     The two models play elo_params.n_games games against each other on the GPU: the model of the
     player to move at the root runs that move's whole search (self_play.py:59,237-239), seats are
     swapped on odd games, the `self_play_override` of elo_params applies (no tree reuse, no noise,
     1200 reads in the shipped configuration, configuration.py:107-113).
     nn_precision: as in generate_games (None = f16x3 for ResNetZero).
+    openings: a book of start positions (move sequences or mirror BoxesStates) instead of n_games games from the empty board:
+    games 2k and 2k+1 start from opening k % len(openings), so with the seat swap of odd games every opening is played once per
+    seating.
     Returns (elo0, elo1, n1 / number of decided games)."""
     from .engine import Engine
     p0, p1 = params
@@ -350,6 +398,8 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     try:
         for i, mdl in enumerate(models):
             eng.load_state_dict(mdl.state_dict(), mdl.kind, model=i, **mdl.shape)
+        if openings is not None and len(openings):
+            eng.selfplay_set_start([start_moves(st, rows, cols) for st in openings], 2)
         eng.selfplay_start(n_games, 0)
         eng.run()
         got = eng.fetch_samples()

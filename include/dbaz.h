@@ -211,6 +211,25 @@ int dbaz_advance(dbaz_engine *e, const int32_t *moves, int32_t reuse_tree);
  * in slot order at the next step, so a run plays the same games on the same slots every time
  * as long as the output buffer has room (slots that find it full wait in PH_EMIT in atomic order). */
 int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t first_game_idx);
+/* Start positions of the next dbaz_selfplay_start (SelfPlay.play_games(game_state, idxs),
+ * self_play.py:51-55,76-80): start s is the position reached from the empty board by
+ * moves[offsets[s] .. offsets[s+1]).  Game g starts from start (g / games_per_start) % n_starts,
+ * g being the ABSOLUTE game index (>= 0).  n_starts = 1 is the reference's contract (one game_state for
+ * all games); n_starts > 1 is an opening book.  n_starts = 0 (moves, offsets may be NULL) clears.
+ * move_idx, the temperature schedule, scripts and the Philox streams count plies from the start position;
+ * the first row of a game has move = -1.
+ * Like dbaz_selfplay_script it applies to the next dbaz_selfplay_start only and is consumed by it.
+ * Checked on the host with the rules the kernels run, before anything reaches the device:
+ *   an illegal move in a start                                   -> DBAZ_EILLEGAL (names start and ply)
+ *   a start that is already finished (the reference would record a game without rows; refused here),
+ *   n_starts < 0 or > DBAZ_MAX_STARTS, games_per_start < 1, offsets negative or descending
+ *                                                                -> DBAZ_EINVAL
+ *   games of an earlier dbaz_selfplay_start still being played   -> DBAZ_ESTATE
+ * A failed call leaves the starts of the previous successful call (if not yet consumed) in place.
+ * Together with dbaz_selfplay_fastforward the next dbaz_selfplay_start returns DBAZ_EINVAL and drops both. */
+#define DBAZ_MAX_STARTS 65536
+int dbaz_selfplay_set_start(dbaz_engine *e, const int16_t *moves, const int32_t *offsets,
+                            int32_t n_starts, int32_t games_per_start);
 /* teacher forcing for parity tests: moves / Dirichlet vectors for game `game_idx`
  * (noise may be NULL).  Must be called before dbaz_selfplay_start. */
 int dbaz_selfplay_script(dbaz_engine *e, int64_t game_idx, const int16_t *moves, int32_t n_moves,
