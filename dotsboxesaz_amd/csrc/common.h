@@ -135,6 +135,10 @@ struct SearchCfg {
                              // (dropped nodes then live on as transposition twins until their memory is needed); 0 = two per simulation
 };
 
+// the two families of built-in evaluators (DBAZ_EVAL_EXTERNAL is neither)
+__host__ __device__ inline bool eval_is_nn(int ev) { return ev == DBAZ_EVAL_RESNET || ev == DBAZ_EVAL_SIMPLENN; }
+__host__ __device__ inline bool eval_is_formula(int ev) { return ev == DBAZ_EVAL_FORMULA_HASH || ev == DBAZ_EVAL_FORMULA_UNIFORM; }
+
 struct GState; // rules.h
 
 // device buffer bundle handed to the tree kernels

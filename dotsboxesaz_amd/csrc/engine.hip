@@ -291,14 +291,12 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     B.tt = nullptr;
     B.tt_mask = 0;
     {
-        auto nn_ev = [](int ev) { return ev == DBAZ_EVAL_RESNET || ev == DBAZ_EVAL_SIMPLENN; };
         // off in two-model match play, like the reference (self_play.py:230): a kept twin may belong to the other model
         // transposition_cache = 2 forces the table on for the formula evaluators too (their (p, v) is a pure function
         // of the same key): the hit path -- twin's prior row, v from its meta block, re-insertion at re-root -- then runs
         // under the oracle-pinned searches of the test-suite
-        const bool formula_ev = cfg->evaluator == DBAZ_EVAL_FORMULA_HASH || cfg->evaluator == DBAZ_EVAL_FORMULA_UNIFORM;
-        if (!cfg->match_play && ((cfg->transposition_cache == 0 && nn_ev(cfg->evaluator)) ||
-                                 (cfg->transposition_cache == 2 && (nn_ev(cfg->evaluator) || formula_ev)))) {
+        if (!cfg->match_play && ((cfg->transposition_cache == 0 && eval_is_nn(cfg->evaluator)) ||
+                                 (cfg->transposition_cache == 2 && (eval_is_nn(cfg->evaluator) || eval_is_formula(cfg->evaluator))))) {
             size_t tcap = 64;
             // (measured round 2: 1x / 2x / 16x the pool size give 38.5 / 38.6 / 38.6 % hits on the headline workload)
             while (tcap < 2 * (size_t)g.cap) tcap <<= 1; // <= 50 % load even when every node of the pool is a distinct position
@@ -623,7 +621,7 @@ static hipEvent_t next_event(dbaz_engine *e)
 static int sim_wave(dbaz_engine *e, bool with_driver)
 {
     hipStream_t s = e->stream;
-    const bool use_nn = e->sc.evaluator == DBAZ_EVAL_RESNET || e->sc.evaluator == DBAZ_EVAL_SIMPLENN;
+    const bool use_nn = eval_is_nn(e->sc.evaluator);
     e->sc.step = (int)(e->steps & 0x3FFFFFFF) + 1;
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
@@ -644,9 +642,8 @@ static int sim_step(dbaz_engine *e, bool with_driver)
 {
     if (e->B.kmax > 1 && (!with_driver || e->cfg.selfplay_pending)) return sim_wave(e, with_driver);
     hipStream_t s = e->stream;
-    auto is_nn = [](int ev) { return ev == DBAZ_EVAL_RESNET || ev == DBAZ_EVAL_SIMPLENN; };
-    const bool use_nn = is_nn(e->sc.evaluator);
-    const bool use_nn2 = e->sc.match_play && is_nn(e->sc.evaluator2);
+    const bool use_nn = eval_is_nn(e->sc.evaluator);
+    const bool use_nn2 = e->sc.match_play && eval_is_nn(e->sc.evaluator2);
     e->sc.step = (int)(e->steps & 0x3FFFFFFF) + 1; // never 0 (a fresh Slot's stamp)
     e->sc.driver_concurrent = with_driver ? 1 : 0;
     if (with_driver) {
@@ -757,13 +754,19 @@ extern "C" int dbaz_set_pending(dbaz_engine *e, int32_t k, int32_t virtual_visit
     return DBAZ_OK;
 }
 
+// a search that the engine runs by itself needs a device evaluator, and a network evaluator its committed weights
+static int search_preconditions(dbaz_engine *e, const char *external_msg)
+{
+    if (e->sc.evaluator == DBAZ_EVAL_EXTERNAL) return set_error(e, DBAZ_ESTATE, "%s", external_msg);
+    if (eval_is_nn(e->sc.evaluator) && !nn_ready(e->nns[0]))
+        return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
+    return DBAZ_OK;
+}
+
 extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const double *noise, double time_limit_s)
 {
     if (!e) return DBAZ_EINVAL;
-    if (e->sc.evaluator == DBAZ_EVAL_EXTERNAL)
-        return set_error(e, DBAZ_ESTATE, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup");
-    if ((e->sc.evaluator == DBAZ_EVAL_RESNET || e->sc.evaluator == DBAZ_EVAL_SIMPLENN) && !nn_ready(e->nns[0]))
-        return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
+    if (int r = search_preconditions(e, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup")) return r;
     // end_time = time.time() + (time_limit or 120), mcts.py:201-203
     const auto t_end = std::chrono::steady_clock::now() + std::chrono::duration<double>(time_limit_s > 0 ? time_limit_s : 120.0);
     int r = dbaz_search_begin(e, num_reads, noise);
@@ -796,10 +799,7 @@ extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const
 extern "C" int dbaz_search(dbaz_engine *e, const int32_t *num_reads, const double *noise)
 {
     if (!e) return DBAZ_EINVAL;
-    if (e->sc.evaluator == DBAZ_EVAL_EXTERNAL)
-        return set_error(e, DBAZ_ESTATE, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup");
-    if ((e->sc.evaluator == DBAZ_EVAL_RESNET || e->sc.evaluator == DBAZ_EVAL_SIMPLENN) && !nn_ready(e->nns[0]))
-        return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
+    if (int r = search_preconditions(e, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup")) return r;
     int r = dbaz_search_begin(e, num_reads, noise);
     if (r) return r;
     for (;;) {
@@ -1038,10 +1038,8 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
 {
     if (!e || n_games < 0) return e ? set_error(e, DBAZ_EINVAL, "bad argument") : DBAZ_EINVAL;
     USE_DEVICE(e);
-    if (e->sc.evaluator == DBAZ_EVAL_EXTERNAL) return set_error(e, DBAZ_ESTATE, "self-play needs a device evaluator");
-    if ((e->sc.evaluator == DBAZ_EVAL_RESNET || e->sc.evaluator == DBAZ_EVAL_SIMPLENN) && !nn_ready(e->nns[0]))
-        return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
-    if (e->sc.match_play && (e->sc.evaluator2 == DBAZ_EVAL_RESNET || e->sc.evaluator2 == DBAZ_EVAL_SIMPLENN) && !nn_ready(e->nns[1]))
+    if (int r = search_preconditions(e, "self-play needs a device evaluator")) return r;
+    if (e->sc.match_play && eval_is_nn(e->sc.evaluator2) && !nn_ready(e->nns[1]))
         return set_error(e, DBAZ_ESTATE, "network weights of model 1 not committed (dbaz_nn_select_model(1), dbaz_nn_commit)");
     if (!e->start_states.empty() && !e->ff_plies.empty()) {
         e->start_states.clear();

@@ -51,6 +51,9 @@ __device__ __forceinline__ NodeMeta load_meta(uint32_t *pool, const Geo &g, int 
     return m;
 }
 
+// expanded and not terminal: a node select_leaf descends through (`while current.is_expanded`, mcts.py:107)
+__device__ __forceinline__ bool is_inner(int flags) { return (flags & NF_EXPANDED) && !(flags & NF_TERMINAL); }
+
 __device__ __forceinline__ uint32_t pack_dw9(int move, int to_play, int just_played)
 {
     return ((uint32_t)(uint16_t)(int16_t)move) | ((uint32_t)(to_play & 0xFF) << 16) |
@@ -372,7 +375,7 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
         for (int i = lane; i < A; i += WAVE)
             ldsf[i] = prepped ? (float)rp[i] : Prow[i];
         __syncthreads();
-        float cpsum = np_pairwise_sum<float>(ldsf, A, lane);
+        float cpsum = np_pairwise_sum(ldsf, A, lane);
         probs_f64 = !(cpsum != 0.0f);
         __syncthreads();
         for (int i = lane; i < A; i += WAVE) {
@@ -382,7 +385,7 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
         for (int i = lane; i < A; i += WAVE)
             ldsd[i] = rp[i];
         __syncthreads();
-        double cpsum = np_pairwise_sum<double>(ldsd, A, lane);
+        double cpsum = np_pairwise_sum(ldsd, A, lane);
         probs_f64 = true;
         __syncthreads();
         for (int i = lane; i < A; i += WAVE)
@@ -511,17 +514,6 @@ __device__ __forceinline__ bool cand_beats(double xa, int ia, bool ha, double xb
     return xa > xb || (xa == xb && ia < ib);
 }
 
-// The four rows of a node (this lane's children i = lane + 64 j) and its meta block are fetched
-// together -- the descent then costs ONE dependent memory round trip per tree level (the next
-// node's rows are requested the moment the child index is known, which itself comes out of the
-// prefetched C row by shuffle) instead of four (rows in two dependent strides, C[best], meta).
-#ifdef DBAZ_STAMP
-// diagnostic build only (tools/stamp_select.sh): cycle stamps of a k_select wave, printed for a few slots
-#define TSTAMP(var) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory")
-#else
-#define TSTAMP(var) do { } while (0)
-#endif
-
 // pb_c's N-dependent factor  log((N + base + 1) / base) + cpuct  and  sqrt(N)  (mcts.py:92-94) from the
 // host-libm tables.  N is wave-uniform: the loads are unconditional scalar loads (clamped index) so that
 // they can be in flight together with the node's rows; beyond the table the device computes the terms
@@ -540,6 +532,10 @@ __device__ __forceinline__ void select_tab_fix(const SearchCfg &cfg, int N, doub
     }
 }
 
+// The four rows of a node (this lane's children i = lane + 64 j) and its meta block are fetched
+// together -- the descent then costs ONE dependent memory round trip per tree level (the next
+// node's rows are requested the moment the child index is known, which itself comes out of the
+// prefetched C row by shuffle) instead of four (rows in two dependent strides, C[best], meta).
 template <int NPL>
 struct NodeRows {
     float P[NPL], W[NPL];
@@ -562,78 +558,65 @@ __device__ __forceinline__ void load_rows(NodeRows<NPL> &r, uint32_t *pool, cons
     }
 }
 
-#ifndef SELECT_WAVES
-#define SELECT_WAVES 16 // games per workgroup (one wave each)
-#endif
-// full rounds only: k_select's class of each slot's leaf (TreeBufs::ev_class), read by k_order_evals
-#define EV_CLASS_DEFERRED (-2) // the leaf of an earlier step whose evaluation was put off: head of the list
-#define EV_CLASS_NEW (-3)      // a leaf selected in this step
-#define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
-
-// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, or -1
-template <int NPL>
-__device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, int lane)
+// path[depth] = (node, the move that led into it, its player to move): what backup needs of a path node
+__device__ __forceinline__ void path_put(PathEnt *path, int depth, int node, int in_move, const NodeMeta &m, int lane)
 {
-    Slot *S = B.slots + slot;
-    const unsigned long long pw = *reinterpret_cast<volatile const unsigned long long *>(&S->phase); // phase | stamp << 32
-    const int phase = (int)(unsigned)pw;
-    if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
-        return -1;
-    if ((int)(unsigned)(pw >> 32) == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
-        return -1;
-    if (cfg.eval_round > 0 && S->pending) {
-        // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
-        // k_order_evals puts it at the head of the list.
-        if (lane == 0) S->sel_step = cfg.step;
-        return SEL_DEFERRED;
+    if (lane == 0) {
+        PathEnt pe;
+        pe.node = node; pe.move_in = (int16_t)in_move; pe.to_play = (int16_t)m.st.to_play;
+        path[depth] = pe;
     }
-    uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    PathEnt *path = B.path + (size_t)slot * g.dmax;
+}
+
+// get_features of a leaf as float32 planes (nn_batch_builder + nn.py:157)
+__device__ __forceinline__ void write_features(const Geo &g, const GState &st, float *dst, int lane)
+{
+    for (int i = lane; i < 3 * g.HW; i += WAVE) dst[i] = (float)gs_feature(g, st, i);
+}
+
+// One descent from the root to a leaf (select_leaf, mcts.py:105-114), shared by the one-leaf-per-game step and by the
+// K-pending search: UCB scan, wave argmax in numpy's order, path entry, lazy child creation, VIRTUAL_LOSS on every
+// node left, and the one-round-trip prefetch of the next level.  vv = 1 (K-pending search with virtual_visits) counts
+// the visit of every edge taken, the root's included, NOW instead of at backup; vv = 0 folds away at the call site.
+// The leaf's own path entry, path[depth], is the caller's.
+struct Leaf {
+    int cur, depth, in_move, err;
+    int root_to_play;
+    NodeMeta m;
+};
+
+template <int NPL>
+__device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool,
+                                        PoolState &q, PathEnt *path, const unsigned vv, int lane)
+{
     const double *rprior = B.root_prior + (size_t)slot * g.AS;
     const int A = g.A;
-
-    unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts_mem = 0, ts_tab = 0, ts_ucb = 0, ts_arg = 0, tq0 = 0, tq1 = 0;
-    (void)ts0; (void)ts1; (void)ts2; (void)ts3; (void)ts_mem; (void)ts_tab; (void)ts_ucb; (void)ts_arg; (void)tq0; (void)tq1;
-    TSTAMP(ts0);
     const int root = S->root;
-    int cur = root, depth = 0, in_move = -1;
-    PoolState q = pool_load(S);
-    GcBatch<GC_PER_STEP> gcb; // the collector's share of this simulation: rows requested now, consumed after the descent
-    gcb.k = 0;
-    if (cfg.gc_lazy <= 0 || q.n_free + (g.cap - q.n_nodes) < cfg.gc_lazy) gc_issue<GC_PER_STEP>(gcb, g, B, slot, pool, q, lane);
-    int Nself = S->root_N;
+    int cur = root, depth = 0, err = 0;
+    const int root_N = S->root_N;
     NodeMeta m = load_meta(pool, g, root);
     NodeRows<NPL> R;
     load_rows<NPL>(R, pool, g, root, lane);
     double pbc_cur, sq_cur;
-    select_tab(cfg, B, Nself, pbc_cur, sq_cur);
-    select_tab_fix(cfg, Nself, pbc_cur, sq_cur);
+    select_tab(cfg, B, root_N, pbc_cur, sq_cur);
+    select_tab_fix(cfg, root_N, pbc_cur, sq_cur);
     double rp[NPL]; // float64 root priors (root_prep), used for the root level only
 #pragma unroll
     for (int j = 0; j < NPL; j++) rp[j] = (lane + WAVE * j < A) ? rprior[lane + WAVE * j] : 0.0;
-    in_move = m.move;
-    // match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the
-    // whole search of this move; odd games swap the seats (the reference shuffles them by worker pid)
-    const int model = cfg.match_play ? ((m.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
-    if ((m.flags & NF_EXPANDED) && !(m.flags & NF_TERMINAL)) {
-        if (lane == 0)
-            S->root_W = S->root_W - 1.0f; // current.total_value -= VIRTUAL_LOSS (root slot)
+    int in_move = m.move;
+    const int root_to_play = m.st.to_play;
+    if (lane == 0) {
+        if (vv) S->root_N = root_N + 1;
+        if (is_inner(m.flags)) S->root_W = S->root_W - 1.0f; // current.total_value -= VIRTUAL_LOSS (root slot)
     }
-    int err = 0, need_eval = -1;
-    TSTAMP(ts1);
-    while ((m.flags & NF_EXPANDED) && !(m.flags & NF_TERMINAL)) {
+    while (is_inner(m.flags)) {
         uint32_t *nd = node_ptr(pool, g, cur);
         float *Wrow = reinterpret_cast<float *>(nd + META_DW + g.AS);
         uint32_t *NSrow = nd + META_DW + 2 * g.AS;
         int32_t *Crow = reinterpret_cast<int32_t *>(nd + META_DW + 3 * g.AS);
         // children_ucb_score, mcts.py:91-99 (float64 throughout); the N-dependent terms were requested
         // together with this node's rows (select_tab)
-        TSTAMP(tq0);
         const double pbc0 = pbc_cur, sq = sq_cur;
-#ifdef DBAZ_STAMP
-        asm volatile("" ::"v"(pbc0), "v"(sq));
-        TSTAMP(tq1); ts_tab += tq1 - tq0;
-#endif
         // Branch-free scan of this lane's children (word j of the played / sentinel masks holds child lane + 64 j)
         const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
         double bx = 0.0;
@@ -669,10 +652,6 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
             bc = take ? R.C[j] : bc;
             have = have || take;
         }
-#ifdef DBAZ_STAMP
-        asm volatile("" ::"v"(bx), "v"(bj));
-        TSTAMP(tq0); ts_ucb += tq0 - tq1;
-#endif
         int bi;
         if (__ballot(have && bx != bx) == 0ull) {
             // no NaN anywhere (always, in practice): wave maximum, then the lowest child index that attains it
@@ -696,10 +675,6 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
                 if (cand_beats(ox, oi, oh != 0, rx, bi, rh)) { rx = ox; bi = oi; rh = true; }
             }
         }
-#ifdef DBAZ_STAMP
-        asm volatile("" ::"v"(bi));
-        TSTAMP(tq1); ts_arg += tq1 - tq0;
-#endif
         // the lane that owns child bi holds it as ITS running best (lanes scan their children in index order and
         // the wave-wide winner is some lane's own best), so its bw / bns / bc are the winner's W, N|sign and C
         // bi and everything read from its owner lane are wave-uniform: say so (scalar branches and loads below)
@@ -708,11 +683,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         bw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bw), owner));
         bns = (uint32_t)__builtin_amdgcn_readlane((int)bns, owner);
         int child = __builtin_amdgcn_readlane(bc, owner);
-        if (lane == 0) {
-            PathEnt pe;
-            pe.node = cur; pe.move_in = (int16_t)in_move; pe.to_play = (int16_t)m.st.to_play;
-            path[depth] = pe;
-        }
+        path_put(path, depth, cur, in_move, m, lane);
         depth++;
         if (child < 0) {
             // DictWithDefault.__missing__ -> UCTNode(game_state.play(move)), mcts.py:53-54
@@ -724,7 +695,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
             bool same = (st.to_play == st.just_played);
             if (lane == 0) {
                 Crow[bi] = child;
-                NSrow[bi] = same ? NS_SAME : 0u; // child_player_changed slot (mcts.py:119), visits = 0
+                NSrow[bi] = (same ? NS_SAME : 0u) | vv; // child_player_changed slot (mcts.py:119); visits = 0, or the pending one
             }
             init_node(pool, g, child, st, cur, bi, m.deepness + 1, lane);
             NodeMeta cm;
@@ -735,10 +706,6 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
             cur = child; in_move = bi; m = cm;
             break;
         }
-#ifdef DBAZ_STAMP
-        unsigned long long tl0, tl1;
-        TSTAMP(tl0); // includes the drain of this level's stores (path entry)
-#endif
         // everything the next level needs is requested at once: the child's pb_c / sqrt terms (its visit count is
         // already known from this node's N row), its meta block and its four rows
         const int nchild = (int)(bns & NS_MASK);
@@ -747,32 +714,68 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         NodeMeta cm = load_meta(pool, g, child);
         load_rows<NPL>(R, pool, g, child, lane); // rows of an unexpanded node are ignored
         select_tab_fix(cfg, nchild, pbc_nx, sq_nx);
-#ifdef DBAZ_STAMP
-        TSTAMP(tl1);
-        ts_mem += tl1 - tl0;
-#endif
-        if ((cm.flags & NF_EXPANDED) && !(cm.flags & NF_TERMINAL)) {
-            if (lane == owner)
-                Wrow[bi] = bw - 1.0f; // VIRTUAL_LOSS on the node being left next iteration
-            Nself = nchild;
+        if (lane == owner) {
+            if (vv) NSrow[bi] = bns + 1u;                       // the visit of the edge into `child`, counted now
+            if (is_inner(cm.flags)) Wrow[bi] = bw - 1.0f;      // VIRTUAL_LOSS on the node being left next iteration
+        }
+        if (is_inner(cm.flags)) {
             pbc_cur = pbc_nx;
             sq_cur = sq_nx;
         }
         cur = child; in_move = bi; m = cm;
     }
-    TSTAMP(ts2);
-    if (err) {
-        if (lane == 0) { S->error = err; S->phase = PH_ERROR; }
+    Leaf lf;
+    lf.cur = cur; lf.depth = depth; lf.in_move = in_move; lf.err = err; lf.root_to_play = root_to_play; lf.m = m;
+    return lf;
+}
+
+#ifndef SELECT_WAVES
+#define SELECT_WAVES 16 // games per workgroup (one wave each)
+#endif
+// full rounds only: k_select's class of each slot's leaf (TreeBufs::ev_class), read by k_order_evals
+#define EV_CLASS_DEFERRED (-2) // the leaf of an earlier step whose evaluation was put off: head of the list
+#define EV_CLASS_NEW (-3)      // a leaf selected in this step
+#define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
+
+// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, or -1
+template <int NPL>
+__device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, int lane)
+{
+    Slot *S = B.slots + slot;
+    const unsigned long long pw = *reinterpret_cast<volatile const unsigned long long *>(&S->phase); // phase | stamp << 32
+    const int phase = (int)(unsigned)pw;
+    if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
+        return -1;
+    if ((int)(unsigned)(pw >> 32) == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
+        return -1;
+    if (cfg.eval_round > 0 && S->pending) {
+        // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
+        // k_order_evals puts it at the head of the list.
+        if (lane == 0) S->sel_step = cfg.step;
+        return SEL_DEFERRED;
+    }
+    uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
+    PathEnt *path = B.path + (size_t)slot * g.dmax;
+    PoolState q = pool_load(S);
+    GcBatch<GC_PER_STEP> gcb; // the collector's share of this simulation: rows requested now, consumed after the descent
+    gcb.k = 0;
+    if (cfg.gc_lazy <= 0 || q.n_free + (g.cap - q.n_nodes) < cfg.gc_lazy) gc_issue<GC_PER_STEP>(gcb, g, B, slot, pool, q, lane);
+    const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, 0u, lane);
+    if (lf.err) {
+        if (lane == 0) { S->error = lf.err; S->phase = PH_ERROR; }
         return -1;
     }
+    const NodeMeta &m = lf.m;
+    const int cur = lf.cur;
+    // match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the
+    // whole search of this move; odd games swap the seats (the reference shuffles them by worker pid)
+    const int model = cfg.match_play ? ((lf.root_to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
     gc_finish<GC_PER_STEP>(gcb, g, B, slot, q, lane);
+    path_put(path, lf.depth, cur, lf.in_move, m, lane);
     if (lane == 0) {
-        PathEnt pe;
-        pe.node = cur; pe.move_in = (int16_t)in_move; pe.to_play = (int16_t)m.st.to_play;
-        path[depth] = pe;
         S->leaf = cur;
         S->sel_step = cfg.step;
-        S->path_len = depth + 1;
+        S->path_len = lf.depth + 1;
         S->leaf_terminal = (m.flags & NF_TERMINAL) ? 1 : 0;
         S->leaf_result = m.result;
         S->leaf_to_play = m.st.to_play;
@@ -780,13 +783,11 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         S->model = model;
         if (q.n_nodes > S->pool_high) S->pool_high = q.n_nodes;
     }
+    int need_eval = -1;
     if (!(m.flags & NF_TERMINAL)) {
-        // get_features of the leaf as float32 planes (nn_batch_builder + nn.py:157)
-        float *f = B.feat + (size_t)slot * 3 * g.HW;
-        for (int i = lane; i < 3 * g.HW; i += WAVE)
-            f[i] = (float)gs_feature(g, m.st, i);
+        write_features(g, m.st, B.feat + (size_t)slot * 3 * g.HW, lane);
         const int ev = model ? cfg.evaluator2 : cfg.evaluator;
-        if (ev == DBAZ_EVAL_RESNET || ev == DBAZ_EVAL_SIMPLENN) need_eval = model;
+        if (eval_is_nn(ev)) need_eval = model;
         int hit = -1;
         // (the table exists for network evaluators, and for the formula evaluators when forced on -- transposition_cache
         // = 2 -- so that the hit path can be compared with the oracle bit for bit)
@@ -805,7 +806,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
                 const int idx = (int)(unsigned)__shfl(ent, pl);
                 if (idx >= 0 && idx < q.n_nodes && idx != cur) {
                     const NodeMeta tm = load_meta(pool, g, idx);
-                    if ((tm.flags & NF_EXPANDED) && !(tm.flags & NF_TERMINAL) && tm.st.e0 == m.st.e0 && tm.st.e1 == m.st.e1 &&
+                    if (is_inner(tm.flags) && tm.st.e0 == m.st.e0 && tm.st.e1 == m.st.e1 &&
                         tm.st.e2 == m.st.e2 && tm.st.e3 == m.st.e3 && tt_mover_b2c(tm.st) == mb) {
                         hit = idx;
                         // still in use: stamp the entry with the current epoch (old epochs are the preferred victims)
@@ -818,12 +819,6 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         }
         if (lane == 0) S->leaf_hit = hit;
     }
-#ifdef DBAZ_STAMP
-    TSTAMP(ts3);
-    if (lane == 0 && (slot & 511) == 0)
-        printf("SEL slot %d depth %d root %llu descent %llu leaf %llu mem %llu tab %llu ucb %llu arg %llu\n", slot, depth, ts1 - ts0, ts2 - ts1,
-               ts3 - ts2, ts_mem, ts_tab, ts_ucb, ts_arg);
-#endif
     return need_eval;
 }
 
@@ -919,151 +914,33 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    const double *rprior = B.root_prior + (size_t)slot * g.AS;
     const int A = g.A, K = B.kmax;
     int width = min(max(cfg.pending, 1), K);
     if (S->first_wave) width = min(width, A);                 // max_pend = min(max_pending_evals, len(valid_moves))
     int n_sims = phase == PH_EXPAND_ROOT ? 1 : min(width, S->sims_left);
     PoolState q = pool_load(S);
-    const int root = S->root;
+    const unsigned vv = cfg.virtual_visits ? 1u : 0u; // the visit is counted at selection (backup then adds the value only)
     int err = 0, done = 0;
     for (int k = 0; k < n_sims && !err; k++) {
         PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
         pool_collect<GC_PER_STEP>(g, B, slot, pool, q, lane);
-        int cur = root, depth = 0, in_move;
-        int Nself = S->root_N;
-        NodeMeta m = load_meta(pool, g, root);
-        NodeRows<NPL> R;
-        load_rows<NPL>(R, pool, g, root, lane);
-        double pbc_cur, sq_cur;
-        select_tab(cfg, B, Nself, pbc_cur, sq_cur);
-        select_tab_fix(cfg, Nself, pbc_cur, sq_cur);
-        double rp[NPL];
-#pragma unroll
-        for (int j = 0; j < NPL; j++) rp[j] = (lane + WAVE * j < A) ? rprior[lane + WAVE * j] : 0.0;
-        in_move = m.move;
-        const unsigned vv = cfg.virtual_visits ? 1u : 0u;
-        if (lane == 0) {
-            S->root_N = Nself + (int)vv;                        // virtual_visits: the visit is counted now (backup adds the value only)
-            if ((m.flags & NF_EXPANDED) && !(m.flags & NF_TERMINAL)) S->root_W = S->root_W - 1.0f;
-        }
-        while ((m.flags & NF_EXPANDED) && !(m.flags & NF_TERMINAL)) {
-            uint32_t *nd = node_ptr(pool, g, cur);
-            float *Wrow = reinterpret_cast<float *>(nd + META_DW + g.AS);
-            uint32_t *NSrow = nd + META_DW + 2 * g.AS;
-            int32_t *Crow = reinterpret_cast<int32_t *>(nd + META_DW + 3 * g.AS);
-            const double pbc0 = pbc_cur, sq = sq_cur;
-            const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
-            double bx = 0.0;
-            int bj = 0;
-            float bw = 0.0f;
-            uint32_t bns = 0;
-            int bc = -1;
-            bool have = false;
-#pragma unroll
-            for (int j = 0; j < NPL; j++) {
-                const int i = lane + WAVE * j;
-                const bool in = i < A;
-                const double P = (cur == root) ? rp[j] : (double)R.P[j];
-                const float w = R.W[j];
-                const uint32_t ns = R.NS[j];
-                const int n = (int)(ns & NS_MASK);
-                const double sgn = (ns & NS_SAME) ? 1.0 : -1.0;
-                const double t = sq / (double)(n + 1);
-                const double pb_c = pbc0 * t;
-                const double prior_score = pb_c * P;
-                double value_score = (double)w / (double)(1 + n);
-                value_score = value_score * sgn;
-                const double score = prior_score + value_score;
-                const bool valid = in && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
-                const double inval = valid ? 0.0 : 1.0;
-                const double x = -1e12 * inval + score;
-                const bool take = in && (!have || (bx == bx && !(x <= bx)));
-                bx = take ? x : bx;
-                bj = take ? j : bj;
-                bw = take ? w : bw;
-                bns = take ? ns : bns;
-                bc = take ? R.C[j] : bc;
-                have = have || take;
-            }
-            int bi = have ? lane + WAVE * bj : 0x7fffffff;
-            {   // numpy argmax order (first maximum; the first NaN wins): generic butterfly
-                double rx = bx;
-                bool rh = have;
-                for (int o = 32; o > 0; o >>= 1) {
-                    double ox = __shfl_xor(rx, o);
-                    int oi = __shfl_xor(bi, o);
-                    int oh = __shfl_xor((int)rh, o);
-                    if (cand_beats(ox, oi, oh != 0, rx, bi, rh)) { rx = ox; bi = oi; rh = true; }
-                }
-            }
-            bi = __builtin_amdgcn_readfirstlane(bi);
-            const int owner = bi & (WAVE - 1);
-            bw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bw), owner));
-            bns = (uint32_t)__builtin_amdgcn_readlane((int)bns, owner);
-            int child = __builtin_amdgcn_readlane(bc, owner);
-            if (lane == 0) {
-                PathEnt pe;
-                pe.node = cur; pe.move_in = (int16_t)in_move; pe.to_play = (int16_t)m.st.to_play;
-                path[depth] = pe;
-            }
-            depth++;
-            if (child < 0) {
-                child = pool_alloc(g, B, slot, pool, q, lane);
-                if (child < 0) { err = DBAZ_EPOOL; depth--; break; }
-                GState st = m.st;
-                int r = gs_play(g, st, bi, nullptr);
-                if (r < 0) { err = DBAZ_EILLEGAL; depth--; break; }
-                bool same = (st.to_play == st.just_played);
-                if (lane == 0) {
-                    Crow[bi] = child;
-                    NSrow[bi] = (same ? NS_SAME : 0u) | vv;   // child_player_changed slot; the pending visit
-                }
-                init_node(pool, g, child, st, cur, bi, m.deepness + 1, lane);
-                NodeMeta cm;
-                cm.st = st; cm.parent = cur; cm.move = bi;
-                cm.result = gs_result(st);
-                cm.flags = (cm.result != DBAZ_RESULT_NONE) ? NF_TERMINAL : 0;
-                cm.deepness = m.deepness + 1;
-                cur = child; in_move = bi; m = cm;
-                break;
-            }
-            const int nchild = (int)(bns & NS_MASK);
-            double pbc_nx, sq_nx;
-            select_tab(cfg, B, nchild, pbc_nx, sq_nx);
-            NodeMeta cm = load_meta(pool, g, child);
-            load_rows<NPL>(R, pool, g, child, lane);
-            select_tab_fix(cfg, nchild, pbc_nx, sq_nx);
-            if (lane == owner) {
-                if (vv) NSrow[bi] = bns + 1u;                   // the visit of the edge into `child`, counted now
-                if ((cm.flags & NF_EXPANDED) && !(cm.flags & NF_TERMINAL)) Wrow[bi] = bw - 1.0f; // VIRTUAL_LOSS on the node left next
-            }
-            if ((cm.flags & NF_EXPANDED) && !(cm.flags & NF_TERMINAL)) {
-                Nself = nchild;
-                pbc_cur = pbc_nx;
-                sq_cur = sq_nx;
-            }
-            cur = child; in_move = bi; m = cm;
-        }
+        const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, vv, lane);
+        err = lf.err;
         if (err) break;
         // leaf bookkeeping of simulation k
+        const NodeMeta &m = lf.m;
         const bool term = (m.flags & NF_TERMINAL) != 0;
         const bool dup = !term && (m.flags & NF_INFLIGHT);
+        path_put(path, lf.depth, lf.cur, lf.in_move, m, lane);
         if (lane == 0) {
-            PathEnt pe;
-            pe.node = cur; pe.move_in = (int16_t)in_move; pe.to_play = (int16_t)m.st.to_play;
-            path[depth] = pe;
             SimRec sr;
-            sr.leaf = cur; sr.path_len = depth + 1; sr.terminal = term ? 1 : 0; sr.result = m.result; sr.to_play = m.st.to_play;
+            sr.leaf = lf.cur; sr.path_len = lf.depth + 1; sr.terminal = term ? 1 : 0; sr.result = m.result; sr.to_play = m.st.to_play;
             sr.dup = dup ? 1 : 0;
             B.simrec[(size_t)slot * K + k] = sr;
             if (!term && !dup)
-                node_ptr(pool, g, cur)[11] = pack_dw11(m.flags | NF_INFLIGHT, m.result, m.deepness);
+                node_ptr(pool, g, lf.cur)[11] = pack_dw11(m.flags | NF_INFLIGHT, m.result, m.deepness);
         }
-        if (!term && !dup) {
-            float *f = B.feat_m + ((size_t)slot * K + k) * 3 * g.HW;
-            for (int i = lane; i < 3 * g.HW; i += WAVE) f[i] = (float)gs_feature(g, m.st, i);
-        }
+        if (!term && !dup) write_features(g, m.st, B.feat_m + ((size_t)slot * K + k) * 3 * g.HW, lane);
         done = k + 1;
         // the next simulation of this wave reads what this one wrote (same wavefront: program order + a drain)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1090,8 +967,7 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     const Slot *S = B.slots + slot;
     if (S->phase == PH_ERROR) return;
     const int K = B.kmax, n = S->wave_sims;
-    const bool nn_ev = cfg.evaluator == DBAZ_EVAL_RESNET || cfg.evaluator == DBAZ_EVAL_SIMPLENN;
-    if (!nn_ev || S->sel_step != cfg.step) return;
+    if (!eval_is_nn(cfg.evaluator) || S->sel_step != cfg.step) return;
     for (int k0 = 0; k0 < n; k0 += WAVE) {
         const int k = k0 + lane;
         bool need = false;
@@ -1107,6 +983,77 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     }
 }
 
+// ------------------------------------------------------------------------------------
+// _search tail, the pieces both search modes share: prior masking (mcts.py:189-196) + expand (:116-119),
+// backup (:121-132), the per-simulation statistics, and the end of a step's work on a slot
+// ------------------------------------------------------------------------------------
+// P row of the leaf = child_priors * valid, renormalised as the reference does; returns v.  The priors and the value come
+// from the formula of evaluator `ev`, or from ep[A] / *evv.  ldsf must be free (wave-cooperative).
+__device__ __forceinline__ float expand_priors(const Geo &g, const GState &st, int ev, const float *ep, const float *evv, float *Prow,
+                                               float *ldsf, int lane)
+{
+    const bool formula = eval_is_formula(ev);
+    uint64_t h = 0;
+    if (formula) h = formula_hash(st);
+    for (int i = lane; i < g.A; i += WAVE) {
+        float p = formula ? formula_p(h, i, ev) : ep[i];
+        ldsf[i] = p * (gs_valid(g, st, i) ? 1.0f : 0.0f); // child_priors * valid
+    }
+    __syncthreads();
+    float s = np_pairwise_sum<float>(ldsf, g.A, lane);
+    const bool renorm = (s > 0.0f) && (s != 1.0f);
+    for (int i = lane; i < g.A; i += WAVE)
+        Prow[i] = renorm ? ldsf[i] / s : ldsf[i];
+    return formula ? formula_v(h, ev) : *evv;
+}
+
+// every path node (root ... leaf) gets W += v_n + VIRTUAL_LOSS, and N += 1 unless the visits were counted at selection
+__device__ __forceinline__ void backup_path(const Geo &g, uint32_t *pool, Slot *S, const PathEnt *path, int plen, int leaf_to_play, float v,
+                                            bool count_visits, int lane)
+{
+    for (int d = lane; d < plen; d += WAVE) {
+        PathEnt pe = path[d];
+        float vn = (pe.to_play == leaf_to_play) ? v : -v;
+        float add = vn + 1.0f;
+        if (d == 0) {
+            S->root_W = S->root_W + add;
+            if (count_visits) S->root_N = S->root_N + 1;
+        } else {
+            uint32_t *pn = node_ptr(pool, g, path[d - 1].node);
+            float *Wr = reinterpret_cast<float *>(pn + META_DW + g.AS);
+            uint32_t *NSr = pn + META_DW + 2 * g.AS;
+            Wr[pe.move_in] = Wr[pe.move_in] + add;
+            if (count_visits) NSr[pe.move_in] = NSr[pe.move_in] + 1u;
+        }
+    }
+}
+
+// statistics of one finished simulation; served = its leaf needed no evaluation of its own (transposition hit / duplicate leaf)
+__device__ __forceinline__ void count_sim(Slot *S, int term, bool served, int path_len, int deepness)
+{
+    S->terminal_count += term;
+    if (deepness > S->max_deepness) S->max_deepness = deepness;
+    S->n_search += 1;
+    S->sum_path += path_len;
+    S->n_term += term;
+    S->n_eval += (term || served) ? 0 : 1;
+    S->n_hit += served ? 1 : 0;
+}
+
+// a slot's step ends: the root expansion (uncounted, mcts.py:207-208) hands over to the simulations, `sims` of which are done otherwise
+__device__ __forceinline__ void end_step(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool, int phase,
+                                         int sims, float *ldsf, double *ldsd, int lane)
+{
+    if (phase == PH_EXPAND_ROOT) {
+        root_prep(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        if (lane == 0) set_phase_stamped(S, S->sims_left > 0 ? PH_SIMS : PH_READY, cfg.step);
+    } else if (lane == 0) {
+        int left = S->sims_left - sims;
+        S->sims_left = left;
+        if (left <= 0) set_phase_stamped(S, PH_READY, cfg.step);
+    }
+}
+
 __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg cfg, TreeBufs B)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1118,10 +1065,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
     if (S->sel_step != cfg.step) return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    const int A = g.A, K = B.kmax, n = S->wave_sims;
-    const int ev = cfg.evaluator;
-    const bool formula = ev == DBAZ_EVAL_FORMULA_HASH || ev == DBAZ_EVAL_FORMULA_UNIFORM;
-    int sims_left = S->sims_left;
+    const int K = B.kmax, n = S->wave_sims;
     for (int k = 0; k < n; k++) {
         const SimRec sr = B.simrec[(size_t)slot * K + k];
         const PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
@@ -1133,62 +1077,21 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
         } else if (lm.flags & NF_EXPANDED) {
             v = __uint_as_float(nd[12]); // expanded by an earlier simulation of this wave (sr.dup): same (p, v)
         } else {
-            float *Prow = reinterpret_cast<float *>(nd + META_DW);
-            uint64_t h = 0;
-            if (formula) h = formula_hash(lm.st);
-            const float *ep = B.evalP_m + ((size_t)slot * K + k) * g.AS;
-            __syncthreads();
-            for (int i = lane; i < A; i += WAVE) {
-                float p = formula ? formula_p(h, i, ev) : ep[i];
-                ldsf[i] = p * (gs_valid(g, lm.st, i) ? 1.0f : 0.0f);
-            }
-            __syncthreads();
-            float s = np_pairwise_sum<float>(ldsf, A, lane);
-            const bool renorm = (s > 0.0f) && (s != 1.0f);
-            for (int i = lane; i < A; i += WAVE) Prow[i] = renorm ? ldsf[i] / s : ldsf[i];
-            v = formula ? formula_v(h, ev) : B.evalV_m[(size_t)slot * K + k];
+            __syncthreads(); // ldsf is reused from the simulation before
+            v = expand_priors(g, lm.st, cfg.evaluator, B.evalP_m + ((size_t)slot * K + k) * g.AS, B.evalV_m + (size_t)slot * K + k,
+                              reinterpret_cast<float *>(nd + META_DW), ldsf, lane);
             if (lane == 0) nd[12] = __float_as_uint(v);
         }
         if (lane == 0) nd[11] = pack_dw11((lm.flags | NF_EXPANDED) & ~NF_INFLIGHT, lm.result, lm.deepness);
-        // backup: W += v_n + VIRTUAL_LOSS on every path node; N += 1 here (the reference) or already at selection (virtual_visits)
-        const int tp = lm.st.to_play;
-        for (int d = lane; d < sr.path_len; d += WAVE) {
-            PathEnt pe = path[d];
-            float vn = (pe.to_play == tp) ? v : -v;
-            float add = vn + 1.0f;
-            if (d == 0) {
-                S->root_W = S->root_W + add;
-                if (!cfg.virtual_visits) S->root_N = S->root_N + 1;
-            } else {
-                uint32_t *pn = node_ptr(pool, g, path[d - 1].node);
-                float *Wr = reinterpret_cast<float *>(pn + META_DW + g.AS);
-                Wr[pe.move_in] = Wr[pe.move_in] + add;
-                if (!cfg.virtual_visits) pn[META_DW + 2 * g.AS + pe.move_in] += 1u;
-            }
-        }
-        if (lane == 0) {
-            const int term = sr.terminal;
-            S->terminal_count += term;
-            if (lm.deepness > S->max_deepness) S->max_deepness = lm.deepness;
-            S->n_search += 1;
-            S->sum_path += sr.path_len;
-            S->n_term += term;
-            S->n_eval += (term || sr.dup) ? 0 : 1;
-            S->n_hit += sr.dup ? 1 : 0;
-        }
-        if (phase != PH_EXPAND_ROOT) sims_left--;
+        // N += 1 here (the reference) or already at selection (virtual_visits)
+        backup_path(g, pool, S, path, sr.path_len, lm.st.to_play, v, !cfg.virtual_visits, lane);
+        if (lane == 0) count_sim(S, sr.terminal, sr.dup != 0, sr.path_len, lm.deepness);
         // the next simulation's path shares nodes with this one (same wavefront: program order + a drain)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    if (phase == PH_EXPAND_ROOT) {
-        root_prep(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
-        if (lane == 0) set_phase_stamped(S, S->sims_left > 0 ? PH_SIMS : PH_READY, cfg.step);
-    } else if (lane == 0) {
-        S->sims_left = sims_left;
-        if (sims_left <= 0) set_phase_stamped(S, PH_READY, cfg.step);
-    }
+    end_step(g, cfg, B, slot, S, pool, phase, n, ldsf, ldsd, lane);
     if (lane == 0) S->wave_sims = 0;
 }
 
@@ -1222,9 +1125,8 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
     if (!(lm.flags & NF_TERMINAL)) {
         float *Prow = reinterpret_cast<float *>(nd + META_DW);
         const int ev = (cfg.match_play && S->model) ? cfg.evaluator2 : cfg.evaluator;
-        const bool formula = ev == DBAZ_EVAL_FORMULA_HASH || ev == DBAZ_EVAL_FORMULA_UNIFORM;
         if (B.tt) hit = S->leaf_hit;
-        if (cfg.eval_round > 0 && hit < 0 && !formula) {
+        if (cfg.eval_round > 0 && hit < 0 && !eval_is_formula(ev)) {
             // behind this step's cut: the network has not seen the leaf; keep it and ask again next step
             const bool late = S->eval_pos >= B.n_eval[2];
             if (lane == 0) S->pending = late ? 1 : 0;
@@ -1237,19 +1139,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
             for (int i = lane; i < A; i += WAVE) Prow[i] = Psrc[i];
             v = __uint_as_float(tw[12]);
         } else {
-            uint64_t h = 0;
-            if (formula) h = formula_hash(lm.st);
-            const float *ep = B.evalP + (size_t)slot * g.AS;
-            for (int i = lane; i < A; i += WAVE) {
-                float p = formula ? formula_p(h, i, ev) : ep[i];
-                ldsf[i] = p * (gs_valid(g, lm.st, i) ? 1.0f : 0.0f); // child_priors * valid
-            }
-            __syncthreads();
-            float s = np_pairwise_sum<float>(ldsf, A, lane);
-            const bool renorm = (s > 0.0f) && (s != 1.0f);
-            for (int i = lane; i < A; i += WAVE)
-                Prow[i] = renorm ? ldsf[i] / s : ldsf[i];
-            v = formula ? formula_v(h, ev) : B.evalV[slot];
+            v = expand_priors(g, lm.st, ev, B.evalP + (size_t)slot * g.AS, B.evalV + slot, Prow, ldsf, lane);
         }
         if (B.tt && lane == 0) {
             nd[12] = __float_as_uint(v); // a later twin reads the value here
@@ -1271,42 +1161,10 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
     }
     if (lane == 0)
         nd[11] = pack_dw11(lm.flags | NF_EXPANDED, lm.result, lm.deepness);
-    // backup: every path node (root ... leaf) gets W += v_n + VIRTUAL_LOSS, N += 1
-    const int tp = lm.st.to_play;
-    for (int d = lane; d < plen; d += WAVE) {
-        PathEnt pe = path[d];
-        float vn = (pe.to_play == tp) ? v : -v;
-        float add = vn + 1.0f;
-        if (d == 0) {
-            S->root_W = S->root_W + add;
-            S->root_N = S->root_N + 1;
-        } else {
-            uint32_t *pn = node_ptr(pool, g, path[d - 1].node);
-            float *Wr = reinterpret_cast<float *>(pn + META_DW + g.AS);
-            uint32_t *NSr = pn + META_DW + 2 * g.AS;
-            Wr[pe.move_in] = Wr[pe.move_in] + add;
-            NSr[pe.move_in] = NSr[pe.move_in] + 1u;
-        }
-    }
+    backup_path(g, pool, S, path, plen, lm.st.to_play, v, true, lane);
     __syncthreads();
-    if (lane == 0) {
-        const int term = (lm.flags & NF_TERMINAL) ? 1 : 0;
-        S->terminal_count += term;
-        if (lm.deepness > S->max_deepness) S->max_deepness = lm.deepness;
-        S->n_search += 1;
-        S->sum_path += plen;
-        S->n_term += term;
-        S->n_eval += (term || hit >= 0) ? 0 : 1;
-        S->n_hit += hit >= 0 ? 1 : 0;
-    }
-    if (phase == PH_EXPAND_ROOT) {
-        root_prep(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
-        if (lane == 0) set_phase_stamped(S, S->sims_left > 0 ? PH_SIMS : PH_READY, cfg.step);
-    } else if (lane == 0) {
-        int left = S->sims_left - 1;
-        S->sims_left = left;
-        if (left <= 0) set_phase_stamped(S, PH_READY, cfg.step);
-    }
+    if (lane == 0) count_sim(S, (lm.flags & NF_TERMINAL) ? 1 : 0, hit >= 0, plen, lm.deepness);
+    end_step(g, cfg, B, slot, S, pool, phase, 1, ldsf, ldsd, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1798,7 +1656,7 @@ __global__ void k_get_roots(Geo g, TreeBufs B, int n_slots, double *priors, floa
         if (priors) {
             double p;
             if (S->root_prepped) p = B.root_prior[(size_t)slot * g.AS + i];
-            else p = (rm.flags & NF_EXPANDED) && !(rm.flags & NF_TERMINAL)
+            else p = is_inner(rm.flags)
                          ? (double)reinterpret_cast<const float *>(nd + META_DW)[i] : 0.0;
             priors[(size_t)slot * A + i] = p;
         }
