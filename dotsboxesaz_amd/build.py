@@ -35,7 +35,7 @@ def source_files():
 
 def source_hash(only=None):
     """sha256 (16 hex digits) over the kernel sources and headers: what dbaz_build_info() of a library built from them reports
-    as src=...; only=("nn.hip", "nn.h", "common.h") gives the nn=... hash of the network kernels alone."""
+    as src=...; only=NN_SOURCES gives the nn=... hash of the network kernels alone."""
     h = hashlib.sha256()
     for f in source_files():
         if only is not None and os.path.basename(f) not in only:
@@ -45,7 +45,7 @@ def source_hash(only=None):
     return h.hexdigest()[:16]
 
 
-NN_SOURCES = ("nn.hip", "nn.h", "common.h")
+NN_SOURCES = ("nn.hip", "nn.h", "common.h", "tower_perm.h")
 
 
 def _newer(target, deps):

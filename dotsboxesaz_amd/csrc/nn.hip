@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "nn.h"
+#include "tower_perm.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -69,6 +70,7 @@ struct NNState {
     float osc0 = 1.0f;                          // f16x3: 2^-sw0
     float *hwp = nullptr;                       // f16x3: head conv weights packed as MFMA fragments [ct][ks][hi|lo][lane][8 halves]
     float hosc = 1.0f;                          // f16x3: 2^-(sw_h + ACT_SHIFT)
+    unsigned char *tperm = nullptr;             // two-cout-tile body: row table of its position tiles (tower_perm.h), nullptr: natural order
     float *wfc = nullptr, *bfc = nullptr;       // head FC GEMM: packed weights [ntp+ntv][KP/16][64][4], bias [(ntp+ntv)*16]
     int KP = 0, ntp = 0, ntv = 0;
     float *wv1 = nullptr, *bv1 = nullptr;       // value FC1 [vf], [1]
@@ -455,13 +457,33 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
 }
-template <int C, int NTT>
+// PAT: the taps this wave pair's tiles 0 and 1 never need (tower_perm.h: under the row table every real row of such a tile lies on
+// one border of the board, so three of its taps read nothing but the zero region).  A dropped (tile, tap) issues no MFMA, no
+// fragment address and no fragment read -- compile-time, because the counted wait at the end of a step must name the number of
+// activation reads that were really issued behind the ring reads.  The MFMAs that remain on an accumulator keep their order and
+// a dropped one would have added +-0 to it: the results are the same bits.  PAT_NONE: natural row order, nothing dropped;
+// otherwise rb[t] = 16-byte unit of this lane's row of tile t (+ gq) and rowbase / tbase are unused.
+#define PAT_NONE 4
+__host__ __device__ constexpr int pat_drop(int pat, int t)
+{
+    constexpr int top = 0007, bottom = 0700, left = 0111, right = 0444;
+    return pat == PAT_NONE || t > 1 ? 0
+         : t == 0 ? (pat < 2 ? top : bottom)
+                  : (pat == 0 || pat == 3 ? left : right);
+}
+static_assert(pat_drop(0, 0) == TP_TOP && pat_drop(0, 1) == TP_LEFT && pat_drop(1, 0) == TP_TOP && pat_drop(1, 1) == TP_RIGHT &&
+              pat_drop(2, 0) == TP_BOTTOM && pat_drop(2, 1) == TP_RIGHT && pat_drop(3, 0) == TP_BOTTOM && pat_drop(3, 1) == TP_LEFT,
+              "the kernel's patterns are those the row table is built and verified for (tower_perm.h)");
+
+template <int C, int NTT, int PAT = PAT_NONE>
 __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
                                                const float *__restrict__ bias, float oscale, const int *vm, int rowbase,
                                                int zbase, int W, int R, int wave, int lane, int residual, bool &ovf_out, int tbase,
                                                WPre (&pre)[2], const f32x4 *next_wpk, f32x4 (&res)[2][NTT],
-                                               unsigned long long *stamps, f32x4 *wring)
+                                               unsigned long long *stamps, f32x4 *wring, const int *rb = nullptr)
 {
+    constexpr bool PERM = PAT != PAT_NONE;
+    static_assert(!PERM || NTT == 4, "the row table is built for 4 tiles per wave pair");
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
     (void)t0; (void)t1; (void)t2; (void)t3; (void)stamps;
     static_assert(C == 64, "two cout tiles per wave x two wave parities = 64 channels");
@@ -484,11 +506,30 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     int ab[NTT];
     // 16-byte unit of this lane's fragment of tile 0 for a tap at row offset offr (the tile constant t*16*S4 is an immediate)
     auto tap_unit = [&](int offr) -> int { return rowbase + offr * S4; };
-    {
-        const int u0 = tap_unit(-W - 1);
+    // PERM: a tile's rows are wherever the table put them, so every tile has its own unit (and no tile immediate)
+    auto kept = [](int t, int tap) constexpr -> bool { return !((pat_drop(PAT, t) >> tap) & 1); };
+    auto n_kept = [&](int tap) constexpr -> int { int n = 0; for (int t = 0; t < NTT; t++) n += kept(t, tap) ? 1 : 0; return n; };
+    auto tile_off = [](int t) constexpr -> int { return PERM ? 0 : t * 256 * S4; };
+    auto set_ab = [&](int tap) {
+        if constexpr (PERM) {
+            // (the addresses are the same in every layer: kept opaque, or hipcc computes all 36 ahead of the layer loop and
+            // parks them in scratch)
+            int offu = ((tap / 3 - 1) * W + (tap % 3 - 1)) * S4;
+            asm volatile("" : "+s"(offu));
 #pragma unroll
-        for (int t = 0; t < NTT; t++) ab[t] = ((vm[t] & 1) ? u0 : zbase + (u0 & 15) - t * 16 * S4) * 16;
-    }
+            for (int t = 0; t < NTT; t++)
+                if (kept(t, tap)) {
+                    const int un = rb[t] + offu;
+                    ab[t] = (((vm[t] >> tap) & 1) ? un : zbase + (un & 15)) * 16;
+                }
+        } else {
+            const int un = tap_unit((tap / 3 - 1) * W + (tap % 3 - 1));
+            const int zt = zbase + (un & 15);
+#pragma unroll
+            for (int t = 0; t < NTT; t++) ab[t] = (((vm[t] >> tap) & 1) ? un : zt - t * 16 * S4) * 16;
+        }
+    };
+    set_ab(0);
     STAMP(t0);
     // this wave's DMA piece of a step = fragment (cout tile wave >> 1, hi | lo = wave & 1); the fragments it consumes are those
     // of cout tiles ct0, ct0 + 1: ring units (ct * 2 + hl) * 64 + lane of slot (step & 1)
@@ -501,14 +542,16 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
 #pragma unroll
     for (int c = 0; c < 2; c++) { a_h[c][0].f = pre[c].h0; a_l[c][0].f = pre[c].l0; }
 #pragma unroll
-    for (int t = 0; t < NTT; t++) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4);
+    for (int t = 0; t < NTT; t++)
+        if (kept(t, 0)) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + tile_off(t));
 #pragma unroll
-    for (int t = 0; t < NTT; t++) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + LO * 16);
+    for (int t = 0; t < NTT; t++)
+        if (kept(t, 0)) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + tile_off(t) + LO * 16);
     STAMP(t1);
 #pragma unroll
     for (int i = 0; i < N; i++) {
         const int cur = i & 1, nxt = (i + 1) & 1;
-        const int ni = i + 1, ntap = ni / KS, nks = ni % KS;
+        const int tap = i / KS, ni = i + 1, ntap = ni / KS, nks = ni % KS;
         // step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the last barrier); behind the
         // layer's last steps: the first two steps of the next layer
         if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
@@ -520,37 +563,41 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         __builtin_amdgcn_sched_barrier(0);
         // hi*hi for both cout tiles (the next tap's addresses are computed in their shadow)
 #pragma unroll
-        for (int t = 0; t < NTT; t++) {
-            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[0][cur].h, bh[t].h, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[1][cur].h, bh[t].h, acc[1][t], 0, 0, 0);
-        }
-        if (ni < N && nks == 0) {
-            const int un = tap_unit((ntap / 3 - 1) * W + (ntap % 3 - 1));
-            const int zt = zbase + (un & 15);
-#pragma unroll
-            for (int t = 0; t < NTT; t++) ab[t] = (((vm[t] >> ntap) & 1) ? un : zt - t * 16 * S4) * 16;
-        }
+        for (int t = 0; t < NTT; t++)
+            if (kept(t, tap)) {
+                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[0][cur].h, bh[t].h, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[1][cur].h, bh[t].h, acc[1][t], 0, 0, 0);
+            }
+        if (ni < N && nks == 0) set_ab(ntap);
         __builtin_amdgcn_sched_barrier(0);
         // lo*hi; bh[t] is dead after its second MFMA -> reload it for the next step right there
 #pragma unroll
         for (int t = 0; t < NTT; t++) {
-            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_l[0][cur].h, bh[t].h, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_l[1][cur].h, bh[t].h, acc[1][t], 0, 0, 0);
-            if (ni < N) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + nks * 64);
+            if (kept(t, tap)) {
+                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_l[0][cur].h, bh[t].h, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_l[1][cur].h, bh[t].h, acc[1][t], 0, 0, 0);
+            }
+            if (ni < N && kept(t, ntap)) bh[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + tile_off(t) + nks * 64);
             __builtin_amdgcn_sched_barrier(0);
         }
         // hi*lo; same for bl[t]
 #pragma unroll
         for (int t = 0; t < NTT; t++) {
-            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[0][cur].h, bl[t].h, acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[1][cur].h, bl[t].h, acc[1][t], 0, 0, 0);
-            if (ni < N) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + t * 256 * S4 + nks * 64 + LO * 16);
+            if (kept(t, tap)) {
+                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[0][cur].h, bl[t].h, acc[0][t], 0, 0, 0);
+                acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_h[1][cur].h, bl[t].h, acc[1][t], 0, 0, 0);
+            }
+            if (ni < N && kept(t, ntap)) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + tile_off(t) + nks * 64 + LO * 16);
             __builtin_amdgcn_sched_barrier(0);
         }
         // end of step i: this wave's DMA piece has landed (vmcnt) and its ring reads of step i + 1 have returned (LDS returns in
-        // order; only the 2 * NTT activation reads issued after them may still be out) -- then every wave's have
-        if (ni < N) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // order; only the activation reads issued after them -- two per tile that keeps the next step's tap -- may still be
+        // out) -- then every wave's have
+        if (ni >= N) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (n_kept(ntap) == NTT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
+        else if (n_kept(ntap) == NTT - 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT - 2) : "memory");
+        else if (n_kept(ntap) == NTT - 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT > 4 ? 2 * NTT - 4 : 0) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (no pattern drops more than two tiles at a tap)
         if (ni < N) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -568,6 +615,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     }
     __builtin_amdgcn_sched_barrier(0);
     // ---- epilogue (as conv_lds_h3): lane holds couts (ct0 + c) * 16 + 4 gq .. +3 of position row (tbase + t) * 16 + jrow
+    // (PERM: of the table's row, unit rb[t] - gq; the centre tap of a row is inside the image, so vm[t] != 0 <=> row < R)
     _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
     float vmax = 0.0f;
 #pragma unroll
@@ -575,13 +623,17 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         const int col = (ct0 + c) * 16 + gq * 4; // column (in halves) of this lane's 4 couts inside a row
 #pragma unroll
         for (int t = 0; t < NTT; t++) {
-            const int row = (tbase + t) * 16 + jrow;
             f32x4 v = acc[c][t] * oscale + bv[c];
             if (residual) v += res[c][t];
             v = relu4(v);
             if (residual) res[c][t] = v; // the block's output = the next block's residual input
             vmax = fmaxf(vmax, max4(v));
-            h3_store<C>(dsth + (size_t)row * (S4 * 8) + col, row < R, v);
+            if constexpr (PERM) {
+                h3_store<C>(dsth + (rb[t] - gq) * 8 + col, vm[t] != 0, v);
+            } else {
+                const int row = (tbase + t) * 16 + jrow;
+                h3_store<C>(dsth + (size_t)row * (S4 * 8) + col, row < R, v);
+            }
         }
     }
     ovf_out |= vmax > F16_GUARD;
@@ -640,6 +692,7 @@ struct TowerArgs {
     // tail handling (see nn_forward): role 0 = main launch, 1 / 2 = tail launches with fewer samples per workgroup
     int role, S_main, S_small, S_mid, S_big, S_huge, cus;
     int cut_round, cut_defer; // cut_n's rule for this step's list (0: every leaf)
+    const unsigned char *perm; // two-cout-tile main launch: row table [16 tiles][16 lanes] (tower_perm.h), nullptr: natural order
 };
 static_assert(offsetof(TowerArgs, wfc) == 136, "see stamp_out: the fields from wfc on keep these kernel-argument offsets");
 
@@ -860,10 +913,24 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
     // C2: the wave pair (wave >> 1) owns tiles [(wave >> 1) * NTA, +NTA)
     const bool first = wave < 4;
     const int tbase = C2 ? (wave >> 1) * NTA : (first ? 0 : NTA);
+    // C2 with a row table (a.perm, 4 tiles per wave pair): lane jrow of tile T works on row perm[T * 16 + jrow] instead, so that
+    // tiles 0 and 1 of every wave pair hold rows of one border only and drop its taps (tower_perm.h); the LDS images stay in
+    // natural order, only the layer MFMAs, their residual stream and their epilogue follow the table
+    constexpr bool PERMOK = C2 && NTA == 4;
+    bool perm_on = false;
+    if constexpr (PERMOK) perm_on = a.perm != nullptr;
     int vm[NTA];
+    int rb[NTA]; // perm_on: 16-byte unit of the lane's row of tile t, + gq
+    int rrow[NTA]; // perm_on: that row, clamped to the workgroup's last (residual decode)
+    (void)rb; (void)rrow;
 #pragma unroll
     for (int t = 0; t < NTA; t++) {
         int row = (tbase + t) * 16 + jrow;
+        if constexpr (PERMOK) {
+            if (perm_on) row = a.perm[row];
+            rb[t] = row * S4 + gq;
+            rrow[t] = min(row, R - 1);
+        }
         int pos = row % HW, y = pos / W, x = pos - y * W;
         int m = 0;
 #pragma unroll
@@ -909,7 +976,8 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
                 if (col < C) {
 #pragma unroll
                     for (int t = 0; t < NTA; t++) {
-                        const int row = min((tbase + t) * 16 + jrow, R - 1);
+                        int row = min((tbase + t) * 16 + jrow, R - 1);
+                        if constexpr (PERMOK) row = rrow[t];
                         const _Float16 *ph = xh + (size_t)row * (S4 * 8) + col;
 #pragma unroll
                         for (int e = 0; e < 4; e++) res[c][t][e] = (float)ph[e] + (float)ph[C + e];
@@ -937,11 +1005,24 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         }
         STAMP(tk0);
         tL0 = tk0;
+        const int pat = perm_on ? __builtin_amdgcn_readfirstlane(wave >> 1) : PAT_NONE;
+        (void)pat;
         for (int l = 0; l < NL; l++) {
             const f32x4 *src = (l & 1) ? Y4 : X4;
             f32x4 *dst = (l & 1) ? X4 : Y4;
             const f32x4 *nxt = l + 1 < NL ? tw4 + (size_t)(l + 1) * wl : nullptr;
-            if constexpr (C2) {
+            if constexpr (PERMOK) {
+                // one code stream per wave pair (wave-uniform; the pairs meet again at the barriers, which count arrivals)
+#define C2_PAT(P) conv_lds_h3_c2<C, NTA, P>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre2, nxt, res, stamps, wring, rb)
+                switch (pat) {
+                case 0: C2_PAT(0); break;
+                case 1: C2_PAT(1); break;
+                case 2: C2_PAT(2); break;
+                case 3: C2_PAT(3); break;
+                default: C2_PAT(PAT_NONE); break;
+                }
+#undef C2_PAT
+            } else if constexpr (C2) {
                 conv_lds_h3_c2<C, NTA>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, pre2, nxt, res, stamps, wring);
             } else {
                 if (first) conv_lds_h3<C, NTA, RR>(src, dst, tw4 + (size_t)l * wl, a.tb + l * C, a.tosc[l], vm, rowbase, zbase, W, R, wave, lane, l & 1, ovf, tbase, nullptr, nullptr, pre, nxt, res[0], stamps);
@@ -2044,6 +2125,15 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
     } else {
         nn->c2 = 0;
     }
+    nn->tperm = nullptr;
+    if (nn->c2 && nn->NT_c2 == 4) {
+        // the row order in which the body's edge tiles can drop the taps of their border (constant for the geometry)
+        int tab[TOWER_PERM_ROWS];
+        if (tower_perm_build(g.H, g.W, nn->S_c2, tab) > 0) {
+            nn->tperm = nn_upload(nn, std::vector<unsigned char>(tab, tab + TOWER_PERM_ROWS));
+            if (!nn->tperm) { err = "hipMalloc failed (row table)"; return DBAZ_EDEVICE; }
+        }
+    }
     hipError_t he = tower_dispatch(nn, nullptr, TowerArgs(), nn->NTT, 0, true);
     nn->use_rem = (nn->precision == 1 && nn->NTT == 7 && C >= 32) ? 1 : 0;
     // the two-cout-tile main launch keeps the residual stream in registers; its remainder bodies must round the same way, and
@@ -2101,6 +2191,7 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
     ta.S_main = nn->S; ta.S_small = nn->S_small; ta.S_mid = nn->S_mid; ta.S_big = nn->S_big; ta.S_huge = 0; ta.cus = nn->cus;
     ta.cut_round = cut_round; ta.cut_defer = cut_defer;
     ta.role = 0; ta.S = nn->S;
+    ta.perm = nn->c2 ? nn->tperm : nullptr;
     if (nn->c2) {
         // two cout tiles per wave (default for 64 channels) for the FULL rounds; what is left behind the last full round goes
         // to one round of the one-cout-tile kernels, whose workgroups come in finer sizes (1, 2, 3 samples, or all S of them
