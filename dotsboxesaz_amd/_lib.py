@@ -32,6 +32,8 @@ SYMBOLS = [
     "dbaz_trainer_net_forward", "dbaz_trainer_net_backward",
     "dbaz_bn2d_workspace_bytes", "dbaz_bn2d_forward", "dbaz_bn2d_backward",
     "dbaz_az_loss_workspace_bytes", "dbaz_az_loss", "dbaz_sgd_step",
+    "dbaz_solver_last_error", "dbaz_solver_create", "dbaz_solver_destroy", "dbaz_solver_solve", "dbaz_solver_info", "dbaz_solver_table",
+    "dbaz_solver_score",
 ]
 
 
@@ -161,10 +163,19 @@ def load():
     L.dbaz_az_loss_workspace_bytes.argtypes = []
     L.dbaz_az_loss.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp]
     L.dbaz_sgd_step.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, vp]
+    L.dbaz_solver_last_error.argtypes = [vp]
+    L.dbaz_solver_last_error.restype = C.c_char_p
+    L.dbaz_solver_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.dbaz_solver_destroy.argtypes = [vp]
+    L.dbaz_solver_destroy.restype = None
+    L.dbaz_solver_solve.argtypes = [vp, i32]
+    L.dbaz_solver_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i32)]
+    L.dbaz_solver_table.argtypes = [vp, vp, i64, i64]
+    L.dbaz_solver_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",
-                        "dbaz_az_loss_workspace_bytes"):
+                        "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy"):
             fn.restype = C.c_int
     L.dbaz_bn2d_workspace_bytes.restype = C.c_int64
     L.dbaz_az_loss_workspace_bytes.restype = C.c_int64

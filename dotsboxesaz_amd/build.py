@@ -24,6 +24,7 @@ UNITS = [
     ("replay.hip", ["-ffp-contract=off"]),  # Kahan-compensated float64 means (pandas group_mean)
     ("train.hip", []),
     ("train_net.hip", []),
+    ("solver.hip", []),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -1,0 +1,32 @@
+// solver.h -- geometry of the exact small-board solver (solver.hip), host + device.
+// Kept apart from common.h / nn.h: the solver needs no dbaz_engine and none of the search or network definitions.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/dbaz.h"
+
+#define SOLVER_MAX_E 31              // table int8 D[2^E] of at most 2 GiB
+#define SOLVER_MAX_BOXES 16          // 2*R*C + R + C <= 31  =>  R*C <= 12
+#define SOLVER_NO_BOX 0x80000000u    // bit 31 is never set in a mask (E <= 31): a box mask that never matches
+#define SOLVER_MIN_LOW 4             // low_bits of the subcube kernel: 16-byte vectors of table entries
+#define SOLVER_MAX_LOW 16            // 64 KB of LDS, low masks as uint16
+#define SOLVER_MAX_HIGH 20           // high patterns of one solve: a work list of at most 2^20 workgroups over all launches
+#define SOLVER_THREADS 512
+
+// Compact edge i = rank of the edge's action index p*H*W + l*W + c among the real edges (ascending); a position's mask has
+// bit i set when edge i is drawn.  Passed by value to the kernels.
+struct SolverGeo {
+    int32_t rows, cols, HW, A, E, n_boxes;
+    uint32_t other[SOLVER_MAX_E][2];  // per edge: the three OTHER edges of each box it borders (SOLVER_NO_BOX: no such box)
+    uint32_t box[SOLVER_MAX_BOXES];   // the four edges of every box
+    uint8_t action[SOLVER_MAX_E + 1]; // compact edge -> action index
+};
+
+// Q of drawing free edge e in position m, given D of the successor: the mover continues after a capture.
+__host__ __device__ __forceinline__ int solver_move_q(uint32_t o0, uint32_t o1, uint32_t m, int d_next)
+{
+    const int c = (int)((m & o0) == o0) + (int)((m & o1) == o1);
+    return c ? c + d_next : -d_next;
+}

@@ -1,0 +1,363 @@
+// solver.hip -- exact solver for small Dots & Boxes boards (E <= 31 real edges): retrograde analysis on the GPU and a kernel
+// that scores feature rows against the solved table.  No dbaz_engine, no search or network code.
+//
+// Table: int8 D[2^E] in HBM.  D[mask] = best achievable (mover's boxes) - (opponent's boxes) over the boxes still open, optimal
+// play by both sides, from the edge set `mask` (compact edge order, solver.h).  It depends on the mask only.
+//   D[full] = 0;   for a free edge e completing c boxes:  Q = c + D[mask|e] if c > 0 (the mover continues), else -D[mask|e];
+//   D[mask] = max Q.   A state with k edges reads only states with k + 1 edges.
+//
+// k_solver_subcube: a workgroup owns one pattern of the high E - L bits and solves the 2^L subcube of the low L bits in LDS.
+//   A. successors that set a HIGH bit were written by earlier launches: for every free high edge the workgroup streams the
+//      2^L-byte subcube of that successor from HBM, 16 consecutive entries per lane, and keeps the running maximum in LDS;
+//   B. successors that set a LOW bit are in LDS: popcount layers L .. 0 of the low bits, one barrier each; the low masks of a
+//      layer come from a popcount-sorted list, so every lane of a wave has a state to solve;
+//   C. the finished subcube goes to HBM in 16-byte stores.
+// One launch per popcount layer of the high bits (E - L + 1 launches).
+// k_solver_layer: the plain form, one thread per mask and one launch per popcount layer of all E bits (A/B partner).
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "solver.h"
+
+struct dbaz_solver {
+    SolverGeo g;
+    int dev = 0;
+    int8_t *D = nullptr;     // [2^E]
+    hipStream_t stream = nullptr;
+    bool solved = false;
+    int low_bits = 0;        // of the last solve (-1: plain kernel)
+    double solve_ms = -1.0;
+    int d0 = -128;
+    std::string err;
+};
+
+static thread_local std::string g_solver_error; // message of a failed dbaz_solver_create (no handle to keep it in); per thread
+
+static int serr(dbaz_solver *s, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (s ? s->err : g_solver_error) = buf;
+    return code;
+}
+
+#define SOLVER_HIP(s, call)                                                                                         \
+    do {                                                                                                            \
+        hipError_t _err = (call);                                                                                   \
+        if (_err != hipSuccess) return serr(s, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+    } while (0)
+
+// ------------------------------------------------------------------------------------
+// kernels
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k)
+{
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m >= (1u << g.E) || __popc(m) != k) return;
+    int best = k == g.E ? 0 : -128;
+    for (int e = 0; e < g.E; e++) {
+        if ((m >> e) & 1u) continue;
+        best = max(best, solver_move_q(g.other[e][0], g.other[e][1], m, (int)D[m | (1u << e)]));
+    }
+    D[m] = (int8_t)best;
+}
+
+__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, int8_t *D, int L, const uint32_t *__restrict__ hi_list,
+                                                                   const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [2^L]
+    const uint32_t tid = threadIdx.x;
+    const uint32_t hi = hi_list[blockIdx.x];
+    const uint32_t base = hi << L, nlow = 1u << L;
+    const int nh = g.E - L;
+
+    // A: running maximum over the moves that draw a high edge
+    for (uint32_t chunk = tid * 16u; chunk < nlow; chunk += SOLVER_THREADS * 16u) {
+        int best[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) best[j] = -128;
+        for (int h = 0; h < nh; h++) {
+            if ((hi >> h) & 1u) continue;
+            const int e = L + h;
+            const uint32_t o0 = g.other[e][0], o1 = g.other[e][1];
+            const uint4 v = *reinterpret_cast<const uint4 *>(D + ((size_t)(base | (1u << e)) + chunk));
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const int d = (int)(int8_t)(w[j >> 2] >> ((j & 3) * 8));
+                best[j] = max(best[j], solver_move_q(o0, o1, base | (chunk + j), d));
+            }
+        }
+        uint32_t p[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            p[q] = (uint32_t)(uint8_t)best[4 * q] | (uint32_t)(uint8_t)best[4 * q + 1] << 8 | (uint32_t)(uint8_t)best[4 * q + 2] << 16 |
+                   (uint32_t)(uint8_t)best[4 * q + 3] << 24;
+        *reinterpret_cast<uint4 *>(sd + chunk) = make_uint4(p[0], p[1], p[2], p[3]);
+    }
+    __syncthreads();
+
+    // B: the moves that draw a low edge, by popcount layers of the low bits
+    const uint32_t full = (1u << g.E) - 1u;
+    for (int k = L; k >= 0; k--) {
+        for (uint32_t i = low_off[k] + tid; i < low_off[k + 1]; i += SOLVER_THREADS) {
+            const uint32_t low = low_perm[i], m = base | low;
+            int best = (int)sd[low];
+            for (int b = 0; b < L; b++) {
+                const uint32_t bit = 1u << b;
+                if (low & bit) continue;
+                best = max(best, solver_move_q(g.other[b][0], g.other[b][1], m, (int)sd[low | bit]));
+            }
+            sd[low] = (int8_t)(m == full ? 0 : best);
+        }
+        __syncthreads();
+    }
+
+    // C
+    for (uint32_t chunk = tid * 16u; chunk < nlow; chunk += SOLVER_THREADS * 16u)
+        *reinterpret_cast<uint4 *>(D + ((size_t)base + chunk)) = *reinterpret_cast<const uint4 *>(sd + chunk);
+}
+
+__device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
+
+// One thread per feature row x int16 [3*HW] (planes 0, 1: edges; plane 2: the mover's doubled boxes_to_close).
+__global__ void __launch_bounds__(256) k_solver_score(SolverGeo g, const int8_t *__restrict__ D, const int16_t *__restrict__ x,
+                                                      const float *__restrict__ pi, int n, int8_t *__restrict__ value,
+                                                      int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const int16_t *xr = x + (size_t)r * 3 * g.HW;
+    uint32_t m = 0;
+    for (int i = 0; i < g.E; i++)
+        if (xr[g.action[i]] != 0) m |= 1u << i;
+    int closed = 0;
+    for (int b = 0; b < g.n_boxes; b++) closed += (int)((m & g.box[b]) == g.box[b]);
+    const int B = g.rows * g.cols;
+    const int own_b2c = (int)xr[2 * g.HW];
+    const int mine = (B - own_b2c) / 2, theirs = closed - mine;
+    const int opp_b2c = B - 2 * theirs;
+    const int margin = mine - theirs;
+    const int d = (int)D[m];
+    int8_t *qr = q + (size_t)r * g.A;
+    for (int a = 0; a < g.A; a++) qr[a] = -128;
+    diff[r] = (int8_t)d;
+    // get_result (dots_boxes_game.py:51-59): a finished game, early end included
+    int res = DBAZ_RESULT_NONE;
+    if (own_b2c == 0 && opp_b2c == 0) res = 0;
+    else if (own_b2c < 0) res = 1;
+    else if (opp_b2c < 0) res = -1;
+    if (res != DBAZ_RESULT_NONE) {
+        value[r] = (int8_t)res;
+        if (mass) mass[r] = 0.0f;
+        return;
+    }
+    const int v = sgn(margin + d);
+    float sum = 0.0f;
+    for (int i = 0; i < g.E; i++) { // ascending action order
+        if ((m >> i) & 1u) continue;
+        const int qq = solver_move_q(g.other[i][0], g.other[i][1], m, (int)D[m | (1u << i)]);
+        const int a = g.action[i];
+        qr[a] = (int8_t)qq;
+        if (pi && sgn(margin + qq) == v) sum += pi[(size_t)r * g.A + a];
+    }
+    value[r] = (int8_t)v;
+    if (mass) mass[r] = sum;
+}
+
+// ------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------
+static void solver_geometry(int rows, int cols, SolverGeo &g)
+{
+    const int H = rows + 1, W = cols + 1, HW = H * W;
+    g = SolverGeo();
+    g.rows = rows; g.cols = cols; g.HW = HW; g.A = 2 * HW;
+    int index[DBAZ_MAX_A];
+    int E = 0;
+    for (int a = 0; a < g.A; a++) {
+        const int p = a / HW, l = (a % HW) / W, c = a % W;
+        const bool real = p == 0 ? c < cols : l < rows; // sentinels: board[0,:,W-1] and board[1,H-1,:]
+        index[a] = real ? E : -1;
+        if (real) g.action[E++] = (uint8_t)a;
+    }
+    g.E = E;
+    for (int e = 0; e < SOLVER_MAX_E; e++) g.other[e][0] = g.other[e][1] = SOLVER_NO_BOX;
+    int used[SOLVER_MAX_E] = {0};
+    for (int l = 0; l < rows; l++)
+        for (int c = 0; c < cols; c++) {
+            const int ed[4] = {index[l * W + c], index[(l + 1) * W + c], index[HW + l * W + c], index[HW + l * W + c + 1]};
+            uint32_t bm = 0;
+            for (int j = 0; j < 4; j++) bm |= 1u << ed[j];
+            g.box[g.n_boxes++] = bm;
+            for (int j = 0; j < 4; j++) g.other[ed[j]][used[ed[j]]++] = bm & ~(1u << ed[j]);
+        }
+}
+
+// masks of `bits` bits in ascending popcount order; off[k] .. off[k + 1] holds popcount k
+static void popcount_order(int bits, std::vector<uint32_t> &perm, std::vector<uint32_t> &off)
+{
+    const uint32_t n = 1u << bits;
+    off.assign(bits + 2, 0);
+    for (uint32_t m = 0; m < n; m++) off[__builtin_popcount(m) + 1]++;
+    for (int k = 0; k <= bits; k++) off[k + 1] += off[k];
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);
+    perm.resize(n);
+    for (uint32_t m = 0; m < n; m++) perm[at[__builtin_popcount(m)]++] = m;
+}
+
+// 12 of 24 bits (3x3), 14 of 31 (3x4) measured fastest: small subcubes leave more workgroups per launch
+static int default_low_bits(int E) { return std::min(14, std::max(E / 2, std::min(E, 8))); }
+
+extern "C" const char *dbaz_solver_last_error(const dbaz_solver *s) { return s ? s->err.c_str() : g_solver_error.c_str(); }
+
+extern "C" void dbaz_solver_destroy(dbaz_solver *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->dev);
+    if (s->D) (void)hipFree(s->D);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+extern "C" int dbaz_solver_create(int32_t rows, int32_t cols, int32_t device, dbaz_solver **out)
+{
+    if (!out) return serr(nullptr, DBAZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (rows < 1 || cols < 1) return serr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    const long long E = 2ll * rows * cols + rows + cols;
+    if (E > SOLVER_MAX_E)
+        return serr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld edges: the solver's table holds 2^E bytes, E <= %d", rows, cols, E, SOLVER_MAX_E);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return serr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+    dbaz_solver *s = new dbaz_solver();
+    s->dev = device;
+    solver_geometry(rows, cols, s->g);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreate(&s->stream);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_solver_subcube, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
+    if (e != hipSuccess) {
+        const std::string msg = hipGetErrorString(e);
+        dbaz_solver_destroy(s);
+        return serr(nullptr, DBAZ_EDEVICE, "solver setup failed: %s", msg.c_str());
+    }
+    *out = s;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_solver_solve(dbaz_solver *s, int32_t low_bits)
+{
+    if (!s) return DBAZ_EINVAL;
+    const int E = s->g.E;
+    const bool plain = low_bits == -1;
+    const int L = low_bits == 0 ? default_low_bits(E) : low_bits;
+    if (!plain && (L < SOLVER_MIN_LOW || L > SOLVER_MAX_LOW || L > E || E - L > SOLVER_MAX_HIGH))
+        return serr(s, DBAZ_EINVAL, "low_bits %d: E = %d needs max(%d, E - %d) <= low_bits <= min(E, %d) (0 = default, -1 = plain kernel)",
+                    low_bits, E, SOLVER_MIN_LOW, SOLVER_MAX_HIGH, SOLVER_MAX_LOW);
+    SOLVER_HIP(s, hipSetDevice(s->dev));
+    const size_t bytes = (size_t)1 << E;
+    if (!s->D) {
+        const hipError_t e = hipMalloc((void **)&s->D, bytes);
+        if (e != hipSuccess) {
+            s->D = nullptr;
+            (void)hipGetLastError();
+            return serr(s, DBAZ_EDEVICE, "table of %zu bytes: %s", bytes, hipGetErrorString(e));
+        }
+    }
+    s->solved = false;
+    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
+    uint16_t *low_dev = nullptr;
+    std::vector<uint32_t> hperm, hoff;
+    if (!plain) {
+        std::vector<uint32_t> lperm, loff;
+        popcount_order(L, lperm, loff);
+        popcount_order(E - L, hperm, hoff);
+        std::vector<uint16_t> l16(lperm.begin(), lperm.end());
+        hipError_t e = hipMalloc((void **)&hi_dev, hperm.size() * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&low_dev, l16.size() * 2);
+        if (e == hipSuccess) e = hipMalloc((void **)&off_dev, loff.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(hi_dev); (void)hipFree(low_dev); (void)hipFree(off_dev);
+            (void)hipGetLastError();
+            return serr(s, DBAZ_EDEVICE, "solver work lists: %s", hipGetErrorString(e));
+        }
+    }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev0, s->stream);
+    if (e == hipSuccess) {
+        if (plain) {
+            const unsigned grid = (unsigned)((bytes + 255) / 256);
+            for (int k = E; k >= 0; k--) k_solver_layer<<<grid, 256, 0, s->stream>>>(s->g, s->D, k);
+        } else {
+            for (int k = E - L; k >= 0; k--)
+                k_solver_subcube<<<hoff[k + 1] - hoff[k], SOLVER_THREADS, (size_t)1 << L, s->stream>>>(s->g, s->D, L, hi_dev + hoff[k], low_dev, off_dev);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev1, s->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(ev1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+    int8_t d0 = 0;
+    if (e == hipSuccess) e = hipMemcpy(&d0, s->D, 1, hipMemcpyDeviceToHost);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(hi_dev); (void)hipFree(low_dev); (void)hipFree(off_dev);
+    if (e != hipSuccess) return serr(s, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
+    s->solved = true;
+    s->low_bits = plain ? -1 : L;
+    s->solve_ms = ms;
+    s->d0 = d0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_solver_info(const dbaz_solver *s, int32_t *n_edges, int64_t *table_bytes, double *solve_ms, int32_t *d0)
+{
+    if (!s) return DBAZ_EINVAL;
+    if (n_edges) *n_edges = s->g.E;
+    if (table_bytes) *table_bytes = (int64_t)1 << s->g.E;
+    if (solve_ms) *solve_ms = s->solve_ms;
+    if (d0) *d0 = s->d0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_solver_table(dbaz_solver *s, int8_t *host_dst, int64_t first, int64_t count)
+{
+    if (!s) return DBAZ_EINVAL;
+    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_solver_table before dbaz_solver_solve");
+    const int64_t n = (int64_t)1 << s->g.E;
+    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
+        return serr(s, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+    if (count == 0) return DBAZ_OK;
+    SOLVER_HIP(s, hipSetDevice(s->dev));
+    SOLVER_HIP(s, hipMemcpy(host_dst, s->D + first, (size_t)count, hipMemcpyDeviceToHost));
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_solver_score(dbaz_solver *s, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
+                                 int8_t *q_dev, float *policy_mass_dev, void *stream)
+{
+    if (!s) return DBAZ_EINVAL;
+    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_solver_score before dbaz_solver_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !value_dev || !diff_dev || !q_dev)) || (pi_dev && !policy_mass_dev))
+        return serr(s, DBAZ_EINVAL, "dbaz_solver_score: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    SOLVER_HIP(s, hipSetDevice(s->dev));
+    k_solver_score<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(s->g, s->D, x_dev, pi_dev, n, value_dev, diff_dev, q_dev,
+                                                                     pi_dev ? policy_mass_dev : nullptr);
+    SOLVER_HIP(s, hipGetLastError());
+    return DBAZ_OK;
+}

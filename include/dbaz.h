@@ -387,6 +387,37 @@ int dbaz_sgd_step(int32_t n_tensors, const void *const *params, const void *cons
                   void *table_dev, const int32_t *chunk_tensor_dev, const int32_t *chunk_off_dev, int32_t n_chunks, float lr,
                   float momentum, float weight_decay, void *stream);
 
+/* ---- exact solver for small boards: true values and optimal moves from a solved table -------------------
+ * The reference has no counterpart.  For a board with E = 2*rows*cols + rows + cols <= 31 real edges the table int8 D[2^E]
+ * lives in HBM: D[mask] = best achievable (mover's boxes) - (opponent's boxes) over the boxes still open under optimal play
+ * by both sides.  Bit i of a mask is the i-th real edge in ascending order of its action index p*H*W + l*W + c (the sentinel
+ * slots of the action space are not edges).  The solver needs no dbaz_engine; one handle per board size and GPU. */
+typedef struct dbaz_solver dbaz_solver;
+const char *dbaz_solver_last_error(const dbaz_solver *s); /* s == NULL: why dbaz_solver_create failed */
+/* E > 31 or rows, cols < 1 -> DBAZ_EINVAL before the device is touched; the table is allocated by the first solve */
+int dbaz_solver_create(int32_t rows, int32_t cols, int32_t device, dbaz_solver **out);
+void dbaz_solver_destroy(dbaz_solver *s);
+/* Retrograde analysis on the GPU; returns when the table is complete.  low_bits: 0 = default; L = a workgroup solves the
+ * 2^L subcube of the low L mask bits in LDS (max(4, E - 20) <= L <= min(E, 16)); -1 = the plain kernel, one launch per
+ * popcount layer of all 2^E masks (A/B partner).  Every form writes the same bytes.  A table that cannot be allocated is
+ * DBAZ_EDEVICE; the handle stays usable. */
+int dbaz_solver_solve(dbaz_solver *s, int32_t low_bits);
+/* any pointer may be NULL.  solve_ms: HIP-event time of the last solve's kernels (-1 before); d0 = D[0], the empty board's
+ * score difference for the first player (-128 before the first solve) */
+int dbaz_solver_info(const dbaz_solver *s, int32_t *n_edges, int64_t *table_bytes, double *solve_ms, int32_t *d0);
+/* host copy of D[first .. first + count) */
+int dbaz_solver_table(dbaz_solver *s, int8_t *host_dst, int64_t first, int64_t count);
+/* Scores n feature rows x int16 [n][3*H*W] as datasets and replay rows hold them (get_features, dots_boxes_game.py:96-100:
+ * planes 0, 1 = edges, plane 2 = the mover's doubled boxes_to_close); pi float32 [n][A] may be NULL (then policy_mass too).
+ * All DEVICE pointers, QUEUED on the caller's stream (a hipStream_t) like dbaz_dataset_batch_on.
+ *   value [n]        true result for the mover under optimal play: sign(margin + D[mask]), margin = mover's - opponent's boxes
+ *   diff  [n]        D[mask]
+ *   q     [n][A]     c + D[next] / -D[next] of every legal action; -128 for drawn edges and sentinel slots
+ *   policy_mass [n]  sum of pi[a], ascending a in float32, over the legal a with sign(margin + q[a]) == value
+ * A finished game (early end included) gets value = get_result, q all -128 and policy_mass 0. */
+int dbaz_solver_score(dbaz_solver *s, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
+                      int8_t *q_dev, float *policy_mass_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
