@@ -47,6 +47,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CONV_THREADS 512 // 8 waves: two per SIMD, wave = (cout tile, half of the position tiles)
 #define MAXT 13 // position tiles (16 rows each) per workgroup
 #define MAXROWS 256
+#define MAXS 16 // samples per workgroup: the columns of head_fc_fused's MFMA, the entries of slot_s
 
 struct NNState {
     Geo g;
@@ -794,7 +795,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         float *wl = Y + S * PP;       // [27][C]   (VALU path only)
         bool mfma0 = false; // the im2col image (10 units per row) must fit behind the padded planes in the idle image
         if constexpr (PREC == 1) mfma0 = a.w0p != nullptr && ((((S * PP + 3) / 4 + 1) & ~1) + S * HW * 10 <= img_units);
-        __shared__ int slot_s[16];    // sample -> slot (S <= 13)
+        __shared__ int slot_s[MAXS];  // sample -> slot (S <= MAXS: nn_commit)
         __shared__ int rowbase_s[MAXROWS]; // position row -> offset of its 3x3 window in the padded planes
         for (int i = tid; i < ns * PP; i += NTHR) pad[i] = 0.0f;
         if (tid < ns) slot_s[tid] = a.list ? a.list[s0 + tid] : s0 + tid;
@@ -2085,8 +2086,20 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
     };
     int S = (16 * MAXT) / HW;
     if (S < 1) S = 1;
+    // the samples of a workgroup are the 16 columns of head_fc_fused's MFMA and the 16 entries of slot_s: boards of at most 12
+    // positions (1x1 ... 2x3) would take 17 ... 52, and samples 16.. of a full workgroup then got no logits at all
+    if (S > MAXS) S = MAXS;
     while (S > 1 && lds_bytes(S) > lds_budget) S--;
     if (lds_bytes(S) > lds_budget) { err = "board / channels / head_channels too large for the LDS-resident tower"; return DBAZ_EINVAL; }
+    // k_tower_rem carries the static LDS of its four bodies (4 x (slot_s + rowbase_s)) on top of the images: where the remainder
+    // launch would be used and the two do not fit into 160 KiB together, the workgroups take one sample less (128 channels with
+    // 144 rows: 3x3, 5x5, 2x2 ... boards, whose commit failed in hipFuncSetAttribute before).  Conservative: without the
+    // two-cout-tile main launch the remainder bodies hold at most S_big < S samples, so a dynamic-LDS size of its own for that
+    // launch, lds_bytes(S_big), would fit as well and leave the main launch its sample
+    if (nn->precision == 1 && C >= 32) {
+        const size_t rem_static = 4 * (MAXS + MAXROWS) * sizeof(int); // slot_s + rowbase_s in each of its four bodies: 4 352 B, what hipcc reports for every k_tower_rem
+        while (S > 1 && (S * HW + 15) / 16 > 8 && lds_bytes(S) + rem_static > (size_t)160 * 1024) S--;
+    }
     nn->S = S;
     nn->NT = (S * HW + 15) / 16;
     nn->conv_lds = lds_bytes(S);
@@ -2145,7 +2158,11 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
     if (he == hipSuccess && nn->S_mid > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 4, 0, true);
     if (he == hipSuccess && nn->S_small > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 2, 0, true);
     if (he == hipSuccess && nn->S_big > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 5, 0, true);
-    if (he != hipSuccess) { err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(he); return DBAZ_EDEVICE; }
+    if (he != hipSuccess) {
+        (void)hipGetLastError(); // (not left behind for the next hipGetLastError() of an unrelated call)
+        err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(he);
+        return DBAZ_EDEVICE;
+    }
     nn->ready = true;
     return DBAZ_OK;
 }

@@ -357,6 +357,47 @@ def test_f16x3_on_trained_like_statistics_20x64(seed):
     assert res[1][1] <= max(4 * t64, 2e-5)                      # as close to the float64 truth as a float32 evaluation is
 
 
+@pytest.mark.parametrize("precision", [0, 1])
+def test_whole_network_in_logit_space_vs_float64(precision):
+    """The whole network -- tower, both heads, softmax and tanh -- where an error is not squeezed by the softmax or the tanh:
+    log p and atanh v against float64, bounded by K times what torch's own float32 evaluation leaves (the criterion and the K of
+    tests/test_hip_nn_elementwise.py; this covers the value head, which the probe head of that file does not).  6x6, 20 x 64,
+    trained-like statistics, 300 positions: the <4,4> remainder in f16x3, the <2,2> one in exact f32 at 256 compute units.
+    Compared: log p where p >= 1e-30 (f32 softmax outputs keep their relative precision down to 1.2e-38; log_softmax of torch
+    has no such floor) and atanh v where |v| <= 0.99 (beyond, one f32 spacing of v, 6e-8, times atanh' = 1 / (1 - v^2) > 50
+    exceeds the 1e-6 scale that is measured)."""
+    from oracle import nn_probe
+    torch.manual_seed(7)
+    m = nn_ref.ResNetZeroRef(6, 6, 64, 20)
+    nn_ref.trained_like_(m, _positions(6, 6, 256, 7), 7)
+    n = 300
+    X = _positions(6, 6, n, 107)
+    m64 = nn_ref.ResNetZeroRef(6, 6, 64, 20).double()
+    m64.load_state_dict({k: v.double() for k, v in m.state_dict().items()})
+    m64.train(False)
+    m.train(False)
+    with torch.no_grad():
+        lp64, v64 = [t.numpy() for t in m64(torch.tensor(X, dtype=torch.float64))]
+        lp32, v32 = [t.numpy().astype(np.float64) for t in m(torch.tensor(X))]
+    e = engine_for(6, 6, m, n_slots=512, precision=precision)
+    p, v = e.predict(X)
+    c = e.counters()
+    e.close()
+    assert c["f32_fallback_evals"] == 0
+    mp, mv = np.exp(lp64) >= 1e-30, np.abs(v64) <= 0.99
+    assert mp.mean() > 0.9 and mv.mean() > 0.5, (mp.mean(), mv.mean())
+    assert (p[mp] > 0).all() and (np.abs(v[mv]) < 1).all()
+    with np.errstate(divide="ignore"):
+        lp = np.log(p.astype(np.float64))
+    e_p, e32_p = np.abs(lp - lp64)[mp].max(), np.abs(lp32 - lp64)[mp].max()
+    e_v, e32_v = np.abs(np.arctanh(v.astype(np.float64)) - np.arctanh(v64))[mv].max(), np.abs(np.arctanh(v32) - np.arctanh(v64))[mv].max()
+    print("RATIO whole network 6x6 20x64 trained-like, nn_precision %d: log p E_hip %.2e E_32 %.2e ratio %.2f; atanh v E_hip %.2e E_32 %.2e "
+          "ratio %.2f (%.1f %% of the logits, %.1f %% of the values compared)"
+          % (precision, e_p, e32_p, e_p / e32_p, e_v, e32_v, e_v / e32_v, 100 * mp.mean(), 100 * mv.mean()))
+    assert e_p <= nn_probe.K[precision] * e32_p, (e_p, e32_p)
+    assert e_v <= nn_probe.K[precision] * e32_v, (e_v, e32_v)
+
+
 def test_f16x3_after_three_generations_of_training(tmp_path):
     """A checkpoint that really was TRAINED: three generations of the generation loop (self-play on the engine in f16x3 -> replay in
     HBM -> optimizer steps -> weights back into the engine) at 6x6 with the 20 x 64 network, then the engine's f16x3 (p, v) for the
