@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("DBAZ_LIB") or os.path.join(_HERE, "libdbaz_hip.so")  
 
 OK, EINVAL, EILLEGAL, EDEVICE, EPOOL, ESTATE = range(6)
 RESULT_NONE = 2
-EVAL_FORMULA_HASH, EVAL_FORMULA_UNIFORM, EVAL_RESNET, EVAL_SIMPLENN, EVAL_EXTERNAL = range(5)
+EVAL_FORMULA_HASH, EVAL_FORMULA_UNIFORM, EVAL_RESNET, EVAL_SIMPLENN, EVAL_EXTERNAL, EVAL_SOLVER = range(6)
 ABI_VERSION = 3  # DBAZ_ABI_VERSION of include/dbaz.h
 DBG_EARLY_JOIN = 1
 DBG_NO_FALLBACK = 2  # reserved bit of dbaz_config.debug_flags: dbaz_create rejects it (DBAZ_EINVAL)
@@ -33,7 +33,7 @@ SYMBOLS = [
     "dbaz_bn2d_workspace_bytes", "dbaz_bn2d_forward", "dbaz_bn2d_backward",
     "dbaz_az_loss_workspace_bytes", "dbaz_az_loss", "dbaz_sgd_step",
     "dbaz_solver_last_error", "dbaz_solver_create", "dbaz_solver_destroy", "dbaz_solver_solve", "dbaz_solver_info", "dbaz_solver_table",
-    "dbaz_solver_score",
+    "dbaz_solver_score", "dbaz_perfect_policy", "dbaz_attach_solver",
 ]
 
 
@@ -172,6 +172,8 @@ def load():
     L.dbaz_solver_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i32)]
     L.dbaz_solver_table.argtypes = [vp, vp, i64, i64]
     L.dbaz_solver_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.dbaz_perfect_policy.argtypes = [vp, i32, vp, C.c_uint64, vp, vp, vp]
+    L.dbaz_attach_solver.argtypes = [vp, i32, vp, C.c_uint64, i32]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",

@@ -17,6 +17,7 @@
 #include "nn.h"
 #include "replay.h"
 #include "rules.h"
+#include "solver.h"
 #include "tree.h"
 
 static thread_local std::string g_create_error; // message of a failed dbaz_create (no handle to keep it in); per thread
@@ -35,6 +36,10 @@ struct dbaz_engine {
     NNState *nn = nullptr;   // the model that dbaz_nn_* calls address (nns[cur_model])
     NNState *nns[2] = {nullptr, nullptr};
     int cur_model = 0;
+    // DBAZ_EVAL_SOLVER: the borrowed table of each model (dbaz_attach_solver), its pick seed and read ceiling
+    const dbaz_solver *solver[2] = {nullptr, nullptr};
+    uint64_t solver_seed[2] = {0, 0};
+    ReadCaps read_caps = {{0, 0}};
     // staging (device) for the boundary
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -176,8 +181,9 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
         return set_error(nullptr, DBAZ_EINVAL, "board %dx%d unsupported (A must be <= %d)", cfg->rows, cfg->cols, DBAZ_MAX_A);
     if (cfg->n_slots < 1) return set_error(nullptr, DBAZ_EINVAL, "n_slots must be >= 1");
     if (cfg->mcts_num_read < 0 || cfg->cpuct_base <= 0) return set_error(nullptr, DBAZ_EINVAL, "bad search parameters");
-    if (cfg->evaluator < 0 || cfg->evaluator > DBAZ_EVAL_EXTERNAL) return set_error(nullptr, DBAZ_EINVAL, "bad evaluator");
-    if (cfg->match_play && (cfg->evaluator2 < 0 || cfg->evaluator2 >= DBAZ_EVAL_EXTERNAL || cfg->evaluator == DBAZ_EVAL_EXTERNAL))
+    if (cfg->evaluator < 0 || cfg->evaluator > DBAZ_EVAL_SOLVER) return set_error(nullptr, DBAZ_EINVAL, "bad evaluator");
+    if (cfg->match_play && (cfg->evaluator2 < 0 || cfg->evaluator2 > DBAZ_EVAL_SOLVER || cfg->evaluator2 == DBAZ_EVAL_EXTERNAL ||
+                            cfg->evaluator == DBAZ_EVAL_EXTERNAL))
         return set_error(nullptr, DBAZ_EINVAL, "match play needs two device evaluators");
     if (cfg->n_temp < 0 || cfg->n_temp > 8) return set_error(nullptr, DBAZ_EINVAL, "n_temp must be in 0..8");
     if (cfg->transposition_cache < 0 || cfg->transposition_cache > 2) return set_error(nullptr, DBAZ_EINVAL, "transposition_cache must be 0, 1 or 2");
@@ -625,12 +631,15 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     e->sc.step = (int)(e->steps & 0x3FFFFFFF) + 1;
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
-    if (with_driver) tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots);
+    if (with_driver) tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, e->read_caps);
     tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots);
     if (use_nn) {
         nn_forward(e->nns[0], s, e->B.feat_m, e->B.list_m, e->B.n_eval, e->n_slots * e->B.kmax, e->B.evalP_m, e->B.evalV_m, e->g.AS, nullptr, nullptr);
         e->nn_launches++;
     }
+    if (e->sc.evaluator == DBAZ_EVAL_SOLVER)
+        solver_forward(e->solver[0], s, e->B.feat_m, e->B.list_m, e->B.n_eval, e->n_slots * e->B.kmax, e->solver_seed[0], e->B.evalP_m,
+                       e->B.evalV_m, e->g.AS);
     tree_launch_expand_backup_multi(s, e->g, e->sc, e->B, e->n_slots);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
@@ -656,7 +665,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
         HIP_CHECK_RET(e, hipEventRecord(e->ev_fork, s));
         HIP_CHECK_RET(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots);
+        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, e->read_caps);
         HIP_CHECK_RET(e, hipEventRecord(e->ev_join, e->stream2));
     }
     // full rounds only (tree.hip, above k_select): self-play stepping, one network, one leaf per slot
@@ -680,6 +689,12 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         nn_forward(e->nns[1], s, e->B.feat, e->B.eval_list2, e->B.n_eval + 1, e->n_slots, e->B.evalP, e->B.evalV, e->g.AS, nullptr, nullptr);
         e->nn_launches++;
     }
+    // the solved table serves its model's list the same way (a slot is on one list only: the two launches write disjoint rows)
+    if (e->sc.evaluator == DBAZ_EVAL_SOLVER)
+        solver_forward(e->solver[0], s, e->B.feat, e->B.eval_list, e->B.n_eval, e->n_slots, e->solver_seed[0], e->B.evalP, e->B.evalV, e->g.AS);
+    if (e->sc.match_play && e->sc.evaluator2 == DBAZ_EVAL_SOLVER)
+        solver_forward(e->solver[1], s, e->B.feat, e->B.eval_list2, e->B.n_eval + 1, e->n_slots, e->solver_seed[1], e->B.evalP, e->B.evalV,
+                       e->g.AS);
     // the driver pass may run on under the network: nothing there reads what it writes (leaf lists and features come from
     // k_select, which skipped the slots the pass starts); k_expand_backup does (it clears the pass's slot list).
     // 3x3: 11.9 -> 13.2 M expansions/s, 6x6: +1.5 %, 9x9: +2.8 % against joining in front of the network
@@ -734,7 +749,7 @@ extern "C" int dbaz_search_begin(dbaz_engine *e, const int32_t *num_reads, const
     int r = upload_search_inputs(e, num_reads, noise, &d_reads);
     if (r) return r;
     e->sc.step = 0;
-    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads);
+    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads, e->read_caps);
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
     int mx = e->sc.mcts_num_read;
@@ -754,12 +769,35 @@ extern "C" int dbaz_set_pending(dbaz_engine *e, int32_t k, int32_t virtual_visit
     return DBAZ_OK;
 }
 
-// a search that the engine runs by itself needs a device evaluator, and a network evaluator its committed weights
+// a search that the engine runs by itself needs a device evaluator, a network evaluator its committed weights and a solver
+// evaluator its table
 static int search_preconditions(dbaz_engine *e, const char *external_msg)
 {
     if (e->sc.evaluator == DBAZ_EVAL_EXTERNAL) return set_error(e, DBAZ_ESTATE, "%s", external_msg);
     if (eval_is_nn(e->sc.evaluator) && !nn_ready(e->nns[0]))
         return set_error(e, DBAZ_ESTATE, "network weights not committed (dbaz_nn_commit)");
+    for (int m = 0; m <= (e->sc.match_play ? 1 : 0); m++)
+        if ((m ? e->sc.evaluator2 : e->sc.evaluator) == DBAZ_EVAL_SOLVER && !e->solver[m])
+            return set_error(e, DBAZ_ESTATE, "model %d: no solved table attached (dbaz_attach_solver)", m);
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s, uint64_t pick_seed, int32_t solver_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    if (!s) return set_error(e, DBAZ_EINVAL, "null solver");
+    if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
+    if ((model ? e->sc.evaluator2 : e->sc.evaluator) != DBAZ_EVAL_SOLVER)
+        return set_error(e, DBAZ_EINVAL, "model %d: its evaluator is not DBAZ_EVAL_SOLVER", model);
+    if (solver_reads < 0) return set_error(e, DBAZ_EINVAL, "solver_reads must be >= 0");
+    bool solved = false;
+    if (!solver_serves(s, e->g.rows, e->g.cols, e->cfg.device, &solved))
+        return set_error(e, DBAZ_EINVAL, "the solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
+                         e->g.cols, e->cfg.device);
+    if (!solved) return set_error(e, DBAZ_ESTATE, "dbaz_attach_solver before dbaz_solver_solve");
+    e->solver[model] = s;
+    e->solver_seed[model] = pick_seed;
+    e->read_caps.cap[model] = solver_reads;
     return DBAZ_OK;
 }
 
@@ -1104,7 +1142,7 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
         e->ff_plies.clear();
     }
     e->sc.step = 0; // searches started here carry stamp 0, which no step ever has
-    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots);
+    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots, e->read_caps);
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(s));
     e->selfplay = true;

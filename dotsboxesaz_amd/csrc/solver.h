@@ -30,3 +30,10 @@ __host__ __device__ __forceinline__ int solver_move_q(uint32_t o0, uint32_t o1, 
     const int c = (int)((m & o0) == o0) + (int)((m & o1) == o1);
     return c ? c + d_next : -d_next;
 }
+
+// The solved table as an evaluator of the search engine (engine.hip; kernel and contract: k_solver_eval in solver.hip).
+// solver_serves: the handle is of this board and device (*solved: its table is complete).  solver_forward has nn_forward's
+// contract (nn.h) on float feature planes: rows feat[list[j]], j < *n_dev <= max_n, to P[list[j] * AS + a] and V[list[j]].
+bool solver_serves(const dbaz_solver *s, int rows, int cols, int device, bool *solved);
+void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat, const int32_t *list_dev, const int32_t *n_dev, int max_n,
+                    uint64_t pick_seed, float *P, float *V, int AS);

@@ -1,5 +1,6 @@
-// solver.hip -- exact solver for small Dots & Boxes boards (E <= 31 real edges): retrograde analysis on the GPU and a kernel
-// that scores feature rows against the solved table.  No dbaz_engine, no search or network code.
+// solver.hip -- exact solver for small Dots & Boxes boards (E <= 31 real edges): retrograde analysis on the GPU, a kernel that
+// scores feature rows against the solved table and one that serves the table as a (p, v) evaluator (k_solver_eval; the engine
+// launches it through solver.h).  No dbaz_engine, no search or network code.
 //
 // Table: int8 D[2^E] in HBM.  D[mask] = best achievable (mover's boxes) - (opponent's boxes) over the boxes still open, optimal
 // play by both sides, from the edge set `mask` (compact edge order, solver.h).  It depends on the mask only.
@@ -127,6 +128,28 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
 
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
 
+// What a feature row says beyond its mask: margin = (mover's boxes) - (opponent's boxes), and get_result
+// (dots_boxes_game.py:51-59) of a finished game, early end included (DBAZ_RESULT_NONE otherwise).  own_b2c = plane 2, the
+// mover's doubled boxes_to_close.  Shared by k_solver_score and k_solver_eval.
+struct RowFacts {
+    int margin, res;
+};
+__device__ __forceinline__ RowFacts solver_row_facts(const SolverGeo &g, uint32_t m, int own_b2c)
+{
+    int closed = 0;
+    for (int b = 0; b < g.n_boxes; b++) closed += (int)((m & g.box[b]) == g.box[b]);
+    const int B = g.rows * g.cols;
+    const int mine = (B - own_b2c) / 2, theirs = closed - mine;
+    const int opp_b2c = B - 2 * theirs;
+    RowFacts f;
+    f.margin = mine - theirs;
+    f.res = DBAZ_RESULT_NONE;
+    if (own_b2c == 0 && opp_b2c == 0) f.res = 0;
+    else if (own_b2c < 0) f.res = 1;
+    else if (opp_b2c < 0) f.res = -1;
+    return f;
+}
+
 // One thread per feature row x int16 [3*HW] (planes 0, 1: edges; plane 2: the mover's doubled boxes_to_close).
 __global__ void __launch_bounds__(256) k_solver_score(SolverGeo g, const int8_t *__restrict__ D, const int16_t *__restrict__ x,
                                                       const float *__restrict__ pi, int n, int8_t *__restrict__ value,
@@ -138,24 +161,14 @@ __global__ void __launch_bounds__(256) k_solver_score(SolverGeo g, const int8_t 
     uint32_t m = 0;
     for (int i = 0; i < g.E; i++)
         if (xr[g.action[i]] != 0) m |= 1u << i;
-    int closed = 0;
-    for (int b = 0; b < g.n_boxes; b++) closed += (int)((m & g.box[b]) == g.box[b]);
-    const int B = g.rows * g.cols;
-    const int own_b2c = (int)xr[2 * g.HW];
-    const int mine = (B - own_b2c) / 2, theirs = closed - mine;
-    const int opp_b2c = B - 2 * theirs;
-    const int margin = mine - theirs;
+    const RowFacts f = solver_row_facts(g, m, (int)xr[2 * g.HW]);
+    const int margin = f.margin;
     const int d = (int)D[m];
     int8_t *qr = q + (size_t)r * g.A;
     for (int a = 0; a < g.A; a++) qr[a] = -128;
     diff[r] = (int8_t)d;
-    // get_result (dots_boxes_game.py:51-59): a finished game, early end included
-    int res = DBAZ_RESULT_NONE;
-    if (own_b2c == 0 && opp_b2c == 0) res = 0;
-    else if (own_b2c < 0) res = 1;
-    else if (opp_b2c < 0) res = -1;
-    if (res != DBAZ_RESULT_NONE) {
-        value[r] = (int8_t)res;
+    if (f.res != DBAZ_RESULT_NONE) {
+        value[r] = (int8_t)f.res;
         if (mass) mass[r] = 0.0f;
         return;
     }
@@ -170,6 +183,58 @@ __global__ void __launch_bounds__(256) k_solver_score(SolverGeo g, const int8_t 
     }
     value[r] = (int8_t)v;
     if (mass) mass[r] = sum;
+}
+
+// splitmix64 finaliser of mask ^ seed * golden ratio: which of a position's optimal moves a seeded evaluator picks
+__device__ __forceinline__ uint64_t solver_pick_mix(uint32_t mask, uint64_t seed)
+{
+    uint64_t x = (uint64_t)mask ^ (seed * 0x9E3779B97F4A7C15ull);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+// The table as a (p, v) evaluator with nn_forward's contract (nn.h): rows x[list[j]], j < min(*n_dev, max_n) (list == nullptr:
+// identity, n_dev == nullptr: max_n rows), T = int16 (dataset rows) or float (TreeBufs.feat planes); a one-hot policy row goes to
+// P[list[j] * stride ..+stride) and v = sign(margin + D[mask]) to V[list[j]].  One wavefront per row, lane i = compact edge i:
+// the mask is a ballot over planes 0 / 1, every free lane reads D of its successor, the wave maximum of Q names the optimal set,
+// and the pick is its k-th member in ascending edge order (k = 0, or solver_pick_mix % n_opt with a seed).  One-hot, not uniform
+// over the optimal set: DESIGN 4.6.  A finished position gets p = 0 and v = get_result.
+#define SOLVER_EVAL_WAVES 4
+template <typename T>
+__global__ void __launch_bounds__(64 * SOLVER_EVAL_WAVES) k_solver_eval(SolverGeo g, const int8_t *__restrict__ D, const T *__restrict__ x,
+                                                                        const int32_t *__restrict__ list, const int32_t *__restrict__ n_dev,
+                                                                        int max_n, uint64_t pick_seed, float *__restrict__ P,
+                                                                        float *__restrict__ V, int stride)
+{
+    const int lane = threadIdx.x & 63;
+    const int n = n_dev ? min(*n_dev, max_n) : max_n;
+    for (int j = blockIdx.x * SOLVER_EVAL_WAVES + (threadIdx.x >> 6); j < n; j += gridDim.x * SOLVER_EVAL_WAVES) {
+        const int r = list ? list[j] : j;
+        if ((unsigned)r >= (unsigned)max_n) continue; // never outside the caller's buffers
+        const T *xr = x + (size_t)r * 3 * g.HW;
+        const bool edge = lane < g.E;
+        const bool drawn = edge && xr[g.action[edge ? lane : 0]] != (T)0;
+        const uint32_t m = (uint32_t)__ballot(drawn);
+        const RowFacts f = solver_row_facts(g, m, (int)xr[2 * g.HW]);
+        const bool open = f.res == DBAZ_RESULT_NONE;
+        const bool cand = open && edge && !drawn;
+        int q = -1024;
+        if (cand) q = solver_move_q(g.other[lane][0], g.other[lane][1], m, (int)D[m | (1u << lane)]);
+        int best = q;
+        for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+        uint32_t opt = (uint32_t)__ballot(cand && q == best);
+        int pick_a = -1;
+        if (opt) {
+            int k = pick_seed ? (int)(solver_pick_mix(m, pick_seed) % (uint64_t)__popc(opt)) : 0;
+            for (; k > 0; k--) opt &= opt - 1u;
+            pick_a = (int)g.action[__ffs((int)opt) - 1];
+        }
+        float *pr = P + (size_t)r * stride;
+        for (int a = lane; a < stride; a += 64) pr[a] = a == pick_a ? 1.0f : 0.0f;
+        if (lane == 0) V[r] = open ? (float)sgn(f.margin + (int)D[m]) : (float)f.res;
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -360,4 +425,37 @@ extern "C" int dbaz_solver_score(dbaz_solver *s, int32_t n, const int16_t *x_dev
                                                                      pi_dev ? policy_mass_dev : nullptr);
     SOLVER_HIP(s, hipGetLastError());
     return DBAZ_OK;
+}
+
+template <typename T>
+static void launch_eval(const dbaz_solver *s, hipStream_t stream, const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n,
+                        uint64_t pick_seed, float *P, float *V, int stride)
+{
+    const int blocks = std::min((max_n + SOLVER_EVAL_WAVES - 1) / SOLVER_EVAL_WAVES, 4096);
+    k_solver_eval<T><<<blocks, 64 * SOLVER_EVAL_WAVES, 0, stream>>>(s->g, s->D, x, list_dev, n_dev, max_n, pick_seed, P, V, stride);
+}
+
+extern "C" int dbaz_perfect_policy(dbaz_solver *s, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev, void *stream)
+{
+    if (!s) return DBAZ_EINVAL;
+    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_perfect_policy before dbaz_solver_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev))) return serr(s, DBAZ_EINVAL, "dbaz_perfect_policy: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    SOLVER_HIP(s, hipSetDevice(s->dev));
+    launch_eval<int16_t>(s, (hipStream_t)stream, x_dev, nullptr, nullptr, n, pick_seed, p_dev, v_dev, s->g.A);
+    SOLVER_HIP(s, hipGetLastError());
+    return DBAZ_OK;
+}
+
+// ---- the engine's side (solver.h): the table behind the evaluator boundary
+bool solver_serves(const dbaz_solver *s, int rows, int cols, int device, bool *solved)
+{
+    *solved = s->solved;
+    return s->g.rows == rows && s->g.cols == cols && s->dev == device;
+}
+
+void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat, const int32_t *list_dev, const int32_t *n_dev, int max_n,
+                    uint64_t pick_seed, float *P, float *V, int AS)
+{
+    launch_eval<float>(s, stream, feat, list_dev, n_dev, max_n, pick_seed, P, V, AS);
 }

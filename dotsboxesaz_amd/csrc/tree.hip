@@ -450,7 +450,7 @@ __device__ __forceinline__ int rule_num_reads(const Geo &g, const SearchCfg &cfg
 
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
 __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                             uint32_t *pool, int num_reads, float *ldsf, double *ldsd, int lane)
+                             uint32_t *pool, int num_reads, const ReadCaps &rc, float *ldsf, double *ldsd, int lane)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
     if (rm.flags & NF_TERMINAL) { // play_game never searches a terminal root
@@ -460,6 +460,10 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     }
     if (num_reads < 0) {
         num_reads = rule_num_reads(g, cfg, rm.st);
+        // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads); the model of a
+        // move's search is chosen as select_one chooses it
+        const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
+        if ((model ? cfg.evaluator2 : cfg.evaluator) == DBAZ_EVAL_SOLVER && rc.cap[model] > 0) num_reads = min(num_reads, rc.cap[model]);
         // benchmark population (dbaz_selfplay_stagger): the slot's first search is cut short so that the slots'
         // move boundaries are spread over a whole search instead of all falling into the same step
         // (dbaz_selfplay_quickplay: the opening plies of the slot's first game are searched with a small budget -- a cheap way
@@ -486,7 +490,7 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, TreeBufs B, const int32_t *num_reads)
+__global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, TreeBufs B, const int32_t *num_reads, ReadCaps rc)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
@@ -495,7 +499,7 @@ __global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, Tre
     if (S->phase == PH_ERROR || S->game_idx < 0)
         return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    begin_search(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, ldsf, ldsd, lane);
+    begin_search(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, rc, ldsf, ldsd, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -787,7 +791,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     if (!(m.flags & NF_TERMINAL)) {
         write_features(g, m.st, B.feat + (size_t)slot * 3 * g.HW, lane);
         const int ev = model ? cfg.evaluator2 : cfg.evaluator;
-        if (eval_is_nn(ev)) need_eval = model;
+        if (eval_uses_list(ev)) need_eval = model;
         int hit = -1;
         // (the table exists for network evaluators, and for the formula evaluators when forced on -- transposition_cache
         // = 2 -- so that the hit path can be compared with the oracle bit for bit)
@@ -967,7 +971,7 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     const Slot *S = B.slots + slot;
     if (S->phase == PH_ERROR) return;
     const int K = B.kmax, n = S->wave_sims;
-    if (!eval_is_nn(cfg.evaluator) || S->sel_step != cfg.step) return;
+    if (!eval_uses_list(cfg.evaluator) || S->sel_step != cfg.step) return;
     for (int k0 = 0; k0 < n; k0 += WAVE) {
         const int k = k0 + lane;
         bool need = false;
@@ -1409,7 +1413,7 @@ __device__ bool try_emit(const Geo &g, const TreeBufs &B, int slot, Slot *S, uin
 }
 
 __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                                  uint32_t *pool, float *ldsf, double *ldsd, int lane)
+                                  uint32_t *pool, const ReadCaps &rc, float *ldsf, double *ldsd, int lane)
 {
     // play_game loop head (self_play.py:57-66): temperature schedule, sims budget, search
     const int i = S->move_idx;
@@ -1425,11 +1429,11 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
         __syncthreads();
         __threadfence_block();
     }
-    begin_search(g, cfg, B, slot, S, pool, -1, ldsf, ldsd, lane);
+    begin_search(g, cfg, B, slot, S, pool, -1, rc, ldsf, ldsd, lane);
 }
 
 
-__global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B)
+__global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B, ReadCaps rc)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
@@ -1451,7 +1455,7 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
         return;
     }
     fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-    start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+    start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
 }
 
 // One pass of the driver for every slot whose reads are done (PH_READY), whose finished game still waits for output space
@@ -1459,8 +1463,8 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
 // here leaves the slot in PH_NEWGAME until the next pass.
 // (the slots come from k_driver_scan's list: a step in which no slot needs the driver costs two tiny launches instead
 // of one workgroup per game squeezing in between the network's workgroups)
-__device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, float *ldsf, double *ldsd,
-                            int lane)
+__device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const ReadCaps &rc, float *ldsf,
+                            double *ldsd, int lane)
 {
     Slot *S = B.slots + slot;
     const int phase = S->phase;
@@ -1473,7 +1477,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
         const long long gidx = S->game_idx;
         S->quick_until = 0; // only a slot's first game has quick plies
         fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-        start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
         return;
     }
     if (phase == PH_EMIT) {
@@ -1573,7 +1577,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             S->phase = emitted ? PH_NEWGAME : PH_EMIT;
         return;
     }
-    start_move_search(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+    start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
 }
 
 // which slots need the driver: finished reads, a blocked emit or a finished game (the pass runs after the previous step's
@@ -1624,14 +1628,14 @@ __global__ void __launch_bounds__(1024) k_driver_scan(SearchCfg cfg, TreeBufs B,
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B)
+__global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B, ReadCaps rc)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int lane = threadIdx.x;
     const int n = *B.drv_count;
     for (int li = blockIdx.x; li < n; li += gridDim.x) {
-        advance_one(g, cfg, B, B.drv_list[li], ldsf, ldsd, lane);
+        advance_one(g, cfg, B, B.drv_list[li], rc, ldsf, ldsd, lane);
         __syncthreads();
     }
 }
@@ -1813,9 +1817,9 @@ __global__ void k_rules(Geo g, int op, int n, uint64_t *edges, int16_t *b2c2, in
 // host launchers
 // ------------------------------------------------------------------------------------
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
-                              const int32_t *num_reads_dev)
+                              const int32_t *num_reads_dev, ReadCaps rc)
 {
-    hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev);
+    hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev, rc);
 }
 void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
 {
@@ -1853,19 +1857,19 @@ void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c,
 {
     hipLaunchKernelGGL(k_advance_manual, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, moves_dev, reuse);
 }
-void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc)
 {
-    hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B);
+    hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, rc);
 }
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
 {
     const int rot = (int)(((unsigned long long)(unsigned)step * 2654435761ull) % (unsigned long long)n_slots);
     hipLaunchKernelGGL(k_order_evals, dim3(1), dim3(1024), 0, s, B, n_slots, rot);
 }
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc)
 {
     hipLaunchKernelGGL(k_driver_scan, dim3(1), dim3(1024), 0, s, c, B, n_slots);
-    hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B);
+    hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, rc);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,

@@ -34,16 +34,22 @@ class Engine:
     Parameters mirror the reference's configuration (configuration.py:82-100):
     mcts_num_read, cpuct=(c, base), noise=(alpha, coeff), temperature={ply: T},
     reuse_tree.  `evaluator` is one of "formula", "uniform", "resnet", "simplenn",
-    "external".  nn_precision: None = 1 (f16x3 split MFMA, f32-grade) for "resnet", 0 (exact f32 MFMA) otherwise.
+    "external", "solver".  nn_precision: None = 1 (f16x3 split MFMA, f32-grade) for "resnet", 0 (exact f32 MFMA) otherwise.
+    evaluator="solver" (or evaluator2="solver" in match play): perfect play from the solved table of `solver`, a solved
+    dotsboxesaz_amd.solver.Solver of this board and device (boards of at most 31 edges); the Engine keeps a reference to it.
+    solver_seed picks among equally good moves (0 = the lowest action), solver_reads > 0 caps the driver rule's reads of the
+    searches the table serves (attach_solver).
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
-                  "resnet": _lib.EVAL_RESNET, "simplenn": _lib.EVAL_SIMPLENN, "external": _lib.EVAL_EXTERNAL}
+                  "resnet": _lib.EVAL_RESNET, "simplenn": _lib.EVAL_SIMPLENN, "external": _lib.EVAL_EXTERNAL,
+                  "solver": _lib.EVAL_SOLVER}
 
     def __init__(self, rows, cols, n_slots, mcts_num_read=800, cpuct=(1.25, 19652), noise=(0.0, 0.0),
                  temperature=None, reuse_tree=True, evaluator="formula", nodes_per_slot=0, seed=0, device=0,
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
-                 max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0):
+                 max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
+                 solver_reads=0):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -85,6 +91,15 @@ class Engine:
         if rc != _lib.OK:
             _lib.check(None, rc)
         self.nodes_per_slot = int(self._L.dbaz_nodes_per_slot(self.h))  # the pool size in effect (0 asked for the default rule)
+        self._solvers = {}
+        if solver is not None:
+            try:
+                for model in range(2 if cfg.match_play else 1):
+                    if (cfg.evaluator2 if model else cfg.evaluator) == _lib.EVAL_SOLVER:
+                        self.attach_solver(solver, model, solver_seed, solver_reads)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -99,6 +114,13 @@ class Engine:
 
     def _ck(self, rc):
         _lib.check(self.h, rc)
+
+    def attach_solver(self, solver, model=0, seed=0, reads=0):
+        """dbaz_attach_solver: model 0 / 1 (its evaluator must be "solver") answers from `solver`'s table, which the engine
+        borrows -- the Solver is kept alive with the Engine.  seed: which of several optimal moves gets the prior (0 = the lowest
+        action index); reads > 0: searches the table serves run min(driver rule, reads) reads."""
+        self._ck(self._L.dbaz_attach_solver(self.h, int(model), solver.h, C.c_uint64(int(seed)), int(reads)))
+        self._solvers[int(model)] = solver
 
     # ---------------------------------------------------------------- rules (G1-G6)
     def rules_init(self, n):

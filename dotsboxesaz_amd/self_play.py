@@ -409,3 +409,64 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     e0, e1 = elo_rating2(elos[0], elos[1], n0, n1, K=30)
     decided = n0 + n1
     return e0, e1, (n1 / decided if decided else float("nan"))
+
+
+def solver_match(params, generation, n_games, rows, cols, openings=None, solver=None, solver_seed=0, solver_reads=2, nn_class=None,
+                 n_slots=None, device=0, nn_precision=None):
+    """The network against perfect play: the absolute measure next to compute_elo's relative one, on boards the exact solver
+    holds (at most 31 edges).  The network of `params` / `generation` is model 0, the solved table (dotsboxesaz_amd.solver) model
+    1; seats and book as in compute_elo: the network moves first in even games, games 2k and 2k+1 start from opening
+    k % len(openings).  solver: a solved Solver of the board (reuse it: a solve costs 2^E bytes); solver_seed picks among the
+    table's equally good moves; the table's searches run min(rule, solver_reads) reads (one already finds its move).
+    Returns dict(games, wins, draws, losses -- the network's --, theory = {"win", "draw", "loss"}: games whose start is that
+    result for the network's seat under perfect play, held = games in which the network got at least that result, held_rate,
+    f32_fallback_evals of the engine's counters, samples = the rows of the games)."""
+    from .engine import Engine
+    from .solver import Solver
+    own = solver is None
+    if own:
+        solver = Solver(rows, cols, device).solve()
+    cls = nn_class or _get(_get(params, "nn"), "model_class")
+    model = cls(params)
+    if generation != 0:
+        model.load_parameters(generation)
+    n_games = int(n_games)
+    kw = engine_kwargs_from_params(params)
+    # the shipped match configuration (configuration.py:107-113): every move from a fresh root -- a reused subtree would carry the
+    # other model's priors, and the table's one-hot prior only binds the search from a root whose expansion was counted -- no noise
+    kw.update(reuse_tree=False, noise=(0.0, 0.0))
+    eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=model.kind, evaluator2="solver", match_play=True,
+                 device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads, **kw)
+    try:
+        eng.load_state_dict(model.state_dict(), model.kind, model=0, **model.shape)
+        if openings is not None and len(openings):
+            eng.selfplay_set_start([start_moves(st, rows, cols) for st in openings], 2)
+        eng.selfplay_start(n_games, 0)
+        eng.run()
+        got = eng.fetch_samples()
+        counters = eng.counters()
+    finally:
+        eng.close()
+    out = match_vs_theory(got, solver)
+    out["f32_fallback_evals"] = int(counters["f32_fallback_evals"])
+    out["samples"] = got  # the match's rows (Engine.fetch_samples), e.g. for solver.score_samples
+    if own:
+        solver.close()
+    return out
+
+
+def match_vs_theory(samples, solver):
+    """Rows of a match in which model 0 met a perfect model 1 (seats: model = player XOR (game_idx & 1)) -> solver_match's
+    counts.  Per game: the network's result is the first row's z seen from the network's seat, the theoretical result of the
+    start is Solver.score of the first row, seen from the same seat."""
+    first = np.nonzero(samples["move_idx"] == 0)[0]
+    g = samples["game_idx"][first]
+    seat_is_mover = (samples["player"][first] ^ (g & 1)) == 0  # the network is to move in the first row
+    sign = np.where(seat_is_mover, 1, -1)
+    z = samples["z"][first].astype(np.int64) * sign
+    theory = solver.score(np.asarray(samples["x"])[first].reshape(len(first), solver.F))["value"].astype(np.int64) * sign
+    held = int((z >= theory).sum())
+    n = len(first)
+    return dict(games=n, wins=int((z > 0).sum()), draws=int((z == 0).sum()), losses=int((z < 0).sum()),
+                theory=dict(win=int((theory > 0).sum()), draw=int((theory == 0).sum()), loss=int((theory < 0).sum())),
+                held=held, held_rate=held / n if n else float("nan"))

@@ -123,6 +123,24 @@ class Solver:
         return out
 
 
+    def policy(self, x, seed=0):
+        """The table as an evaluator: x as in score() -> (p float32 [n, A], v float32 [n]).  p is one-hot on an optimal move (all
+        zero for a finished game), v the true result for the mover.  seed = 0 picks the optimal move with the lowest action
+        index, any other seed one that is a fixed function of position and seed (include/dbaz.h, dbaz_perfect_policy)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        n = int(xt.shape[0])
+        p = torch.empty((n, self.A), dtype=torch.float32, device=dev)
+        v = torch.empty(n, dtype=torch.float32, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_perfect_policy(self.h, C.c_int32(n), ptr(xt), C.c_uint64(int(seed)), ptr(p), ptr(v),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return (p.cpu().numpy(), v.cpu().numpy()) if as_numpy else (p, v)
+
+
 def score_samples(samples, solver=None, rows=None, cols=None, device=0):
     """Scores the rows Engine.fetch_samples() / generate_games return (x, pi, played, z) against the solved table.
     Per row: value (true result for the mover), policy_mass (search policy on result-preserving moves), played_optimal (the
@@ -166,6 +184,55 @@ def _margin(solver, x):
     return 2 * mine - closed
 
 
+def _random_rows(solver, n, seed=0):
+    """n feature rows int16 [n, 3*H*W]: every edge drawn with a per-row probability, boxes shared out so that the row is a
+    position of an unfinished game wherever one exists with those edges."""
+    rs = np.random.RandomState(seed)
+    H, W, HW = solver.H, solver.W, solver.H * solver.W
+    x = np.zeros((n, solver.F), np.int16)
+    drawn = rs.rand(n, solver.n_edges) < rs.rand(n, 1)
+    x[:, solver.actions] = drawn
+    x[:, [a for a in range(solver.A) if a not in set(solver.actions.tolist())]] = 1  # sentinel slots, as get_features has them
+    e = x[:, :2 * HW] != 0
+    closed = np.zeros(n, np.int64)
+    for l in range(solver.rows):
+        for c in range(solver.cols):
+            closed += e[:, l * W + c] & e[:, (l + 1) * W + c] & e[:, HW + l * W + c] & e[:, HW + l * W + c + 1]
+    mine = closed // 2
+    x[:, 2 * HW:] = (solver.rows * solver.cols - 2 * mine)[:, None]
+    return x
+
+
+def _policy_bench(solver, n):
+    """HIP-event milliseconds of one dbaz_perfect_policy and one dbaz_solver_score call on the same n rows: median of 5 after a warm-up"""
+    import torch
+    dev = torch.device("cuda", solver.device)
+    x = torch.as_tensor(_random_rows(solver, n)).to(dev)
+    p = torch.empty((n, solver.A), dtype=torch.float32, device=dev)
+    v = torch.empty(n, dtype=torch.float32, device=dev)
+    value, diff = torch.empty(n, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    q = torch.empty((n, solver.A), dtype=torch.int8, device=dev)
+    L, ptr = solver._L, lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+
+    def timed(call):  # the output buffers exist: the events enclose the kernel alone
+        ms = []
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for i in range(6):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                solver._ck(call(stream))
+                t1.record()
+                t1.synchronize()
+                if i:  # the first run warms up
+                    ms.append(t0.elapsed_time(t1))
+        return round(float(np.median(ms)), 4)
+
+    policy_ms = timed(lambda st: L.dbaz_perfect_policy(solver.h, C.c_int32(n), ptr(x), C.c_uint64(0), ptr(p), ptr(v), st))
+    score_ms = timed(lambda st: L.dbaz_solver_score(solver.h, C.c_int32(n), ptr(x), None, ptr(value), ptr(diff), ptr(q), None, st))
+    return dict(policy_bench_rows=int(n), policy_ms=policy_ms, score_ms=score_ms)
+
+
 def main(argv=None):
     import argparse
     import json
@@ -174,14 +241,19 @@ def main(argv=None):
     ap.add_argument("--cols", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--low-bits", type=int, default=0, help="0 = default, L = LDS subcube of 2^L masks, -1 = plain kernel")
+    ap.add_argument("--policy-bench", type=int, default=0, metavar="N",
+                    help="HIP-event time of dbaz_perfect_policy and dbaz_solver_score on the same N random positions (median of 5)")
     a = ap.parse_args(argv)
     s = Solver(a.rows, a.cols, a.device).solve(a.low_bits)
     x0 = np.zeros((1, 3, s.H, s.W), np.int16)
     x0[:, 2] = a.rows * a.cols
     q = s.score(x0)["q"][0]
     i = s.info()
-    print(json.dumps(dict(rows=a.rows, cols=a.cols, E=i["n_edges"], table_bytes=i["table_bytes"], solve_ms=round(i["solve_ms"], 3),
-                          d0=i["d0"], first_move_q={int(act): int(q[act]) for act in s.actions})))
+    out = dict(rows=a.rows, cols=a.cols, E=i["n_edges"], table_bytes=i["table_bytes"], solve_ms=round(i["solve_ms"], 3),
+               d0=i["d0"], first_move_q={int(act): int(q[act]) for act in s.actions})
+    if a.policy_bench > 0:
+        out.update(_policy_bench(s, a.policy_bench))
+    print(json.dumps(out))
     s.close()
 
 

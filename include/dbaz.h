@@ -54,6 +54,7 @@ extern "C" {
 #define DBAZ_EVAL_RESNET 2          /* ResNetZero, HIP MFMA kernels (nn.py:108-122) */
 #define DBAZ_EVAL_SIMPLENN 3        /* SimpleNN, 3x3 boards (dots_boxes_nn.py:61-98) */
 #define DBAZ_EVAL_EXTERNAL 4        /* caller supplies (p, v) per leaf: dbaz_select / dbaz_expand_backup */
+#define DBAZ_EVAL_SOLVER 5          /* perfect play from a solved table (boards of at most 31 edges): dbaz_attach_solver */
 
 typedef struct dbaz_engine dbaz_engine;
 
@@ -77,7 +78,7 @@ typedef struct {
                              * f16's range is redone in exact f32 on the device, counters.f32_fallback_evals) */
     int32_t match_play;     /* two-model match play (self_play.compute_elo, :309-344): the evaluator of a move's
                                search is model (root.to_play XOR game_idx&1) */
-    int32_t evaluator2;     /* DBAZ_EVAL_* of model 1 (match play) */
+    int32_t evaluator2;     /* DBAZ_EVAL_* of model 1 (match play; any kind but DBAZ_EVAL_EXTERNAL) */
     int32_t transposition_cache; /* 0 = on for network evaluators (default), 1 = off, 2 = on for network AND formula
                              * evaluators (parity tests of the hit path).  The reference caches (p, v) by position hash
                              * (utils/proxies.py:35-43); results are identical either way */
@@ -417,6 +418,26 @@ int dbaz_solver_table(dbaz_solver *s, int8_t *host_dst, int64_t first, int64_t c
  * A finished game (early end included) gets value = get_result, q all -128 and policy_mass 0. */
 int dbaz_solver_score(dbaz_solver *s, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
                       int8_t *q_dev, float *policy_mass_dev, void *stream);
+
+/* The table as a policy/value evaluator: for n feature rows (as above) a ONE-HOT policy p float32 [n][A] on an optimal move
+ * and v float32 [n] = sign(margin + D[mask]), the true result for the mover.  Among the n_opt moves whose q is the maximum the
+ * pick is the k-th in ascending action order: k = 0 for pick_seed = 0, otherwise k = mix(mask, pick_seed) mod n_opt with the
+ * splitmix64 finaliser  x = mask ^ pick_seed * 0x9E3779B97F4A7C15;  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ * x *= 0x94D049BB133111EB; x ^= x >> 31  (64-bit, wrapping) -- a pure function of position and seed.  A finished game gets
+ * p = 0 and v = get_result.  DEVICE pointers, QUEUED on the caller's stream like dbaz_solver_score; DBAZ_ESTATE before a solve. */
+int dbaz_perfect_policy(dbaz_solver *s, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev /*[n][A]*/, float *v_dev,
+                       void *stream);
+/* The same evaluator behind the engine's evaluator boundary: model (0, or 1 = dbaz_config.evaluator2 in match play) of a handle
+ * created with DBAZ_EVAL_SOLVER for that model answers its leaves from s's table -- searches, self-play and match play against a
+ * network or formula evaluator run unchanged, with perfect priors and values.  The engine BORROWS the table: s must outlive the
+ * engine's use of it, dbaz_destroy does not free it.  The transposition cache and the full-rounds cut stay off for this kind.
+ * solver_reads > 0: searches served by this model under the driver's rule (num_reads == NULL, self-play) run
+ * min(rule, solver_reads) reads -- one read already finds the move; 0 = the rule; explicit num_reads are never touched.
+ *   s not solved                                              -> DBAZ_ESTATE
+ *   s of another board size or device, model not 0 / 1, the model's evaluator not DBAZ_EVAL_SOLVER, solver_reads < 0
+ *                                                             -> DBAZ_EINVAL
+ * dbaz_search / dbaz_search_timed / dbaz_selfplay_start before the attach -> DBAZ_ESTATE. */
+int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s, uint64_t pick_seed, int32_t solver_reads);
 
 #ifdef __cplusplus
 }
