@@ -41,13 +41,23 @@
 
 #include "nn.h"
 #include "tower_perm.h"
+#include "tower_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define CONV_THREADS 512 // 8 waves: two per SIMD, wave = (cout tile, half of the position tiles)
-#define MAXT 13 // position tiles (16 rows each) per workgroup
-#define MAXROWS 256
-#define MAXS 16 // samples per workgroup: the columns of head_fc_fused's MFMA, the entries of slot_s
+// (MAXT, MAXROWS, MAXS and WRING_UNITS: tower_plan.h, with the plan that depends on them)
+
+struct TowerArgs;
+typedef void (*TowerKernel)(Geo, TowerArgs);
+// one launch of nn_forward's tower, fixed at commit
+struct TowerLaunch {
+    TowerKernel kernel;
+    size_t lds;             // dynamic LDS
+    int role, S;            // TowerArgs::role and ::S of the launch
+    enum Grid { PER_GROUP, ONE_ROUND, ONE_ROUND_AT_MOST } grid; // ceil(max_n / S), cus, the smaller of the two
+    bool fallback;          // the exact-f32 launch behind the f16x3 launches
+};
 
 struct NNState {
     Geo g;
@@ -83,13 +93,11 @@ struct NNState {
     float *sn_w0 = nullptr, *sn_b0 = nullptr, *sn_ps0 = nullptr, *sn_pt0 = nullptr; // fc0
     float *sn_w1 = nullptr, *sn_b1 = nullptr, *sn_ps1 = nullptr, *sn_pt1 = nullptr; // fc1
     size_t sn_lds = 0;
-    int S = 1, NT = 1, NTT = 7;                 // samples / position tiles per conv workgroup (NTT: compiled tile count)
-    int S_small = 0, S_mid = 0, S_big = 0, cus = 256; // tail launches: samples per workgroup of the <2,2> / <4,4> / <5,5> variants (0: unused)
-    size_t conv_lds = 0;
-    // f16x3 with two cout tiles per wave (k_tower<64, NT, 0, 1, true>, 64 channels): 4 tile groups of NT_c2 tiles
-    int c2 = 0, S_c2 = 0, NT_c2 = 0; // (its remainder goes to the one-cout-tile kernels)
-    int use_rem = 0; // f16x3, NTT == 7: the remainder sizes live in ONE launch (k_tower_rem)
-    size_t conv_lds_c2 = 0;
+    int sn_S = 4;                               // samples per k_simple_trunk workgroup
+    // ResNetZero: which body evaluates which samples (tower_plan.h) and the launches that follow from it, in nn_forward's order
+    TowerPlan plan;
+    int cus = 256;
+    std::vector<TowerLaunch> launches;
 };
 
 // ------------------------------------------------------------------------------------
@@ -445,8 +453,6 @@ __device__ __forceinline__ void conv_lds_h3(const f32x4 *__restrict__ src4, f32x
 //     the L2 -> CU weight stream, four more LDS fragment reads and one workgroup barrier per K-step
 // (The alternatives measured against this body are recorded in EXPERIMENTS.md.)
 // ------------------------------------------------------------------------------------
-#define WRING_UNITS 512 // 16-byte units per ring slot: 4 cout tiles x (hi, lo) x 64 lanes
-
 // LDS-DMA of 16 bytes per lane: lane's global source -> lds_dst (wave-uniform LDS byte address) + 16 * lane
 __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst)
 {
@@ -1144,19 +1150,10 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
 #endif
 }
 
-// which launch takes the samples behind the last full round of the main launch: 0 = the main launch itself, 1..4 = one
-// round of workgroups with S_small / S_mid / S_big / S_huge samples each (every launch derives this from n on the device)
+// tower_split (tower_plan.h) on the launch's arguments
 __device__ __forceinline__ int tower_split(const TowerArgs &a, int n, int &n_full)
 {
-    const int per_round = a.cus * a.S_main;
-    n_full = per_round > 0 ? (n / per_round) * per_round : 0;
-    const int tail = n - n_full;
-    if (tail <= 0) return 0;
-    if (a.S_small > 0 && tail <= a.cus * a.S_small) return 1;
-    if (a.S_mid > 0 && tail <= a.cus * a.S_mid) return 2;
-    if (a.S_big > 0 && tail <= a.cus * a.S_big) return 3;
-    if (a.S_huge > 0 && tail <= a.cus * a.S_huge) return 4; // (main = two cout tiles per wave: 4 = one round of the one-cout-tile kernel)
-    return 0;
+    return tower_split(a.cus, a.S_main, a.S_small, a.S_mid, a.S_big, a.S_huge, n, n_full);
 }
 
 template <int C, int NTA, int NTB, int PREC, bool C2 = false>
@@ -1622,11 +1619,7 @@ int nn_configure(NNState *nn, int kind, int channels, int blocks, int head_chann
     if (blocks < 0 || head_channels < 1 || value_fc < 1 || value_fc > 64) { err = "bad network shape"; return DBAZ_EINVAL; }
     nn_free_device(nn);
     nn->sd.clear();
-    // the MFMA tile wants 16 | C: narrower nets run zero-padded (padded channels stay exactly 0)
-    int cp = channels <= 16 ? 16 : channels <= 32 ? 32 : channels <= 64 ? 64 : 128;
-    if (nn->precision == 1 && cp < 32) cp = 32; // K = 32 per f16 MFMA step
-    nn->kind = kind; nn->C = cp; nn->Craw = channels; nn->blocks = blocks; nn->hc = head_channels; nn->vf = value_fc;
-    nn->c2 = (nn->precision == 1 && cp == 64) ? 1 : 0;
+    nn->kind = kind; nn->C = tower_padded_channels(channels, nn->precision); nn->Craw = channels; nn->blocks = blocks; nn->hc = head_channels; nn->vf = value_fc;
     return DBAZ_OK;
 }
 
@@ -1769,79 +1762,62 @@ static bool pack_conv(NNState *nn, const std::string &conv, const std::string &b
     return true;
 }
 
-// launches (or, with attr_only, raises the dynamic-LDS limit of) the instantiation for (C, NTT, PREC)
-template <int C, int NTA, int NTB>
-static hipError_t tower_inst(NNState *nn, hipStream_t s, const TowerArgs &ta, int grid, bool attr_only, int prec)
-{
-    if constexpr (C >= 32) {
-        if (prec == 1) {
-            if (attr_only)
-                return hipFuncSetAttribute((const void *)k_tower<C, NTA, NTB, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds);
-            hipLaunchKernelGGL((k_tower<C, NTA, NTB, 1>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
-            return hipSuccess;
-        }
-    }
-    if (attr_only)
-        return hipFuncSetAttribute((const void *)k_tower<C, NTA, NTB, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds);
-    hipLaunchKernelGGL((k_tower<C, NTA, NTB, 0>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
-    return hipSuccess;
-}
-
-// the remainder launch (f16x3, geometries whose main one-cout-tile instantiation is <7,6>)
-static hipError_t tower_dispatch_rem(NNState *nn, hipStream_t s, const TowerArgs &ta, int grid, bool attr_only)
-{
-    if (nn->c2) { // beside the two-cout-tile main launch: register-resident residual in every body
-        if (attr_only) return hipFuncSetAttribute((const void *)k_tower_rem<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds);
-        hipLaunchKernelGGL((k_tower_rem<64, true>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);
-        return hipSuccess;
-    }
-#define REM_CASE(CC)                                                                                                                  \
-    case CC:                                                                                                                          \
-        if (attr_only) return hipFuncSetAttribute((const void *)k_tower_rem<CC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds); \
-        hipLaunchKernelGGL((k_tower_rem<CC>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds, s, nn->g, ta);                            \
-        return hipSuccess;
-    switch (nn->C) {
-        REM_CASE(32) REM_CASE(64) REM_CASE(128)
-    default: return hipErrorInvalidValue;
-    }
-#undef REM_CASE
-}
-
-// two cout tiles per wave (C = 64): nt position tiles per wave, 4 tile groups
-static hipError_t tower_dispatch_c2(NNState *nn, hipStream_t s, const TowerArgs &ta, int nt, int grid, bool attr_only)
-{
-#define C2_CASE(NT)                                                                                                                   \
-    case NT:                                                                                                                          \
-        if (attr_only) return hipFuncSetAttribute((const void *)k_tower<64, NT, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->conv_lds_c2); \
-        hipLaunchKernelGGL((k_tower<64, NT, 0, 1, true>), dim3(grid), dim3(CONV_THREADS), nn->conv_lds_c2, s, nn->g, ta);           \
-        return hipSuccess;
-    switch (nt) {
-        C2_CASE(1) C2_CASE(2) C2_CASE(3) C2_CASE(4)
-    default: return hipErrorInvalidValue;
-    }
-#undef C2_CASE
-}
-
+// The tower kernels by what the plan asks for; nullptr: no such instantiation (nn_commit fails).
+// ntt: tiles per wave (7 -> <7,6>, 5 -> <5,5>, 4 -> <4,4>, 2 -> <2,2>).  f16x3 has no <5,5> kernel: S_big > 0 needs NTT == 7,
+// which with f16x3 is use_rem, and the 5-tile body then lives in k_tower_rem.
 template <int C>
-static hipError_t tower_inst_c(NNState *nn, hipStream_t s, const TowerArgs &ta, int ntt, int grid, bool attr_only, int prec)
+static TowerKernel tower_kernel_c(int ntt, int prec)
 {
+    if (prec == 1) {
+        if constexpr (C >= 32) {
+            switch (ntt) {
+            case 2: return k_tower<C, 2, 2, 1>;
+            case 4: return k_tower<C, 4, 4, 1>;
+            case 7: return k_tower<C, 7, 6, 1>;
+            }
+        }
+        return nullptr;
+    }
     switch (ntt) {
-    case 2: return tower_inst<C, 2, 2>(nn, s, ta, grid, attr_only, prec);
-    case 4: return tower_inst<C, 4, 4>(nn, s, ta, grid, attr_only, prec);
-    case 5: return tower_inst<C, 5, 5>(nn, s, ta, grid, attr_only, prec);
-    default: return tower_inst<C, 7, 6>(nn, s, ta, grid, attr_only, prec);
+    case 2: return k_tower<C, 2, 2, 0>;
+    case 4: return k_tower<C, 4, 4, 0>;
+    case 5: return k_tower<C, 5, 5, 0>;
+    case 7: return k_tower<C, 7, 6, 0>;
     }
+    return nullptr;
 }
-// ntt: tiles per wave of the instantiation (7 -> <7,6>, 5 -> <5,5>, 4 -> <4,4>, 2 -> <2,2>); prec < 0: the handle's
-static hipError_t tower_dispatch(NNState *nn, hipStream_t s, const TowerArgs &ta, int ntt, int grid, bool attr_only, int prec = -1)
+static TowerKernel tower_kernel(int C, int ntt, int prec)
 {
-    if (prec < 0) prec = nn->precision;
-    switch (nn->C) {
-    case 16: return tower_inst_c<16>(nn, s, ta, ntt, grid, attr_only, prec);
-    case 32: return tower_inst_c<32>(nn, s, ta, ntt, grid, attr_only, prec);
-    case 64: return tower_inst_c<64>(nn, s, ta, ntt, grid, attr_only, prec);
-    default: return tower_inst_c<128>(nn, s, ta, ntt, grid, attr_only, prec);
+    switch (C) {
+    case 16: return tower_kernel_c<16>(ntt, prec);
+    case 32: return tower_kernel_c<32>(ntt, prec);
+    case 64: return tower_kernel_c<64>(ntt, prec);
+    case 128: return tower_kernel_c<128>(ntt, prec);
     }
+    return nullptr;
+}
+// the remainder launch (f16x3, geometries whose main one-cout-tile instantiation is <7,6>); rr: beside the two-cout-tile main
+// launch, register-resident residual in every body
+static TowerKernel tower_kernel_rem(int C, bool rr)
+{
+    if (rr) return C == 64 ? k_tower_rem<64, true> : nullptr;
+    switch (C) {
+    case 32: return k_tower_rem<32>;
+    case 64: return k_tower_rem<64>;
+    case 128: return k_tower_rem<128>;
+    }
+    return nullptr;
+}
+// two cout tiles per wave (C = 64): nt position tiles per wave, 4 tile groups
+static TowerKernel tower_kernel_c2(int nt)
+{
+    switch (nt) {
+    case 1: return k_tower<64, 1, 0, 1, true>;
+    case 2: return k_tower<64, 2, 0, 1, true>;
+    case 3: return k_tower<64, 3, 0, 1, true>;
+    case 4: return k_tower<64, 4, 0, 1, true>;
+    }
+    return nullptr;
 }
 
 static int dense_rs4(int K)
@@ -1939,8 +1915,7 @@ static int commit_simplenn(NNState *nn, std::string &err)
     if (!nn->sn_flat || !nn->sn_h1 || !nn->hact || !nn->wfc) { err = "hipMalloc failed (SimpleNN buffers)"; return DBAZ_EDEVICE; }
     // LDS: two images of S*16 rows x 264 dwords (+ zero regions); S = 4 -> 141 KB
     const size_t s4 = (C + 8) / 4;
-    nn->S = 4;
-    nn->sn_lds = 2 * ((((size_t)nn->S * g.HW * s4 + 15) & ~(size_t)15) + 3 * s4) * 16;
+    nn->sn_lds = 2 * ((((size_t)nn->sn_S * g.HW * s4 + 15) & ~(size_t)15) + 3 * s4) * 16;
     hipError_t he = hipFuncSetAttribute(nn->precision == 1 ? (const void *)k_simple_trunk<1> : (const void *)k_simple_trunk<0>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)nn->sn_lds);
     if (he == hipSuccess) he = hipFuncSetAttribute((const void *)k_dense, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * dense_rs4(1024) * 16);
@@ -2072,92 +2047,45 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         nn->KP = KP; nn->ntp = ntp; nn->ntv = ntv;
     }
     if (!nn->wfc || !nn->wv1 || !nn->w0) { err = "hipMalloc failed (network buffers)"; return DBAZ_EDEVICE; }
-    // conv workgroup geometry: S whole samples, NT position tiles of 16 rows (<= MAXT)
-    const size_t lds_budget = 158 * 1024; // of 160 KiB: two ping-pong activation images
-    // the idle image doubles as staging for conv0 (padded planes + 27*C weights) and the head convs
-    auto lds_bytes = [&](int S_) {
-        const size_t s4 = (C + 8) / 4;
-        const size_t img = ((((size_t)S_ * HW * s4 + 15) & ~(size_t)15) + 3 * s4) * 4; // floats, incl. zero region
-        const size_t need0 = (size_t)S_ * 3 * (g.H + 2) * (g.W + 2) + (size_t)27 * C;
-        // head phase: conv1x1 weights (VALU path) + staged head activations + 16 floats of slack + the FC logits of the samples
-        const size_t nj = (size_t)(A + 15) / 16 + (size_t)(vf + 15) / 16;
-        const size_t need1 = (size_t)2 * hc * (C + 4) + (size_t)S_ * 2 * hc * HW + 16 + (size_t)S_ * (nj * 16 + 1);
-        return (img + std::max(img, std::max(need0, need1))) * 4;
-    };
-    int S = (16 * MAXT) / HW;
-    if (S < 1) S = 1;
-    // the samples of a workgroup are the 16 columns of head_fc_fused's MFMA and the 16 entries of slot_s: boards of at most 12
-    // positions (1x1 ... 2x3) would take 17 ... 52, and samples 16.. of a full workgroup then got no logits at all
-    if (S > MAXS) S = MAXS;
-    while (S > 1 && lds_bytes(S) > lds_budget) S--;
-    if (lds_bytes(S) > lds_budget) { err = "board / channels / head_channels too large for the LDS-resident tower"; return DBAZ_EINVAL; }
-    // k_tower_rem carries the static LDS of its four bodies (4 x (slot_s + rowbase_s)) on top of the images: where the remainder
-    // launch would be used and the two do not fit into 160 KiB together, the workgroups take one sample less (128 channels with
-    // 144 rows: 3x3, 5x5, 2x2 ... boards, whose commit failed in hipFuncSetAttribute before).  Conservative: without the
-    // two-cout-tile main launch the remainder bodies hold at most S_big < S samples, so a dynamic-LDS size of its own for that
-    // launch, lds_bytes(S_big), would fit as well and leave the main launch its sample
-    if (nn->precision == 1 && C >= 32) {
-        const size_t rem_static = 4 * (MAXS + MAXROWS) * sizeof(int); // slot_s + rowbase_s in each of its four bodies: 4 352 B, what hipcc reports for every k_tower_rem
-        while (S > 1 && (S * HW + 15) / 16 > 8 && lds_bytes(S) + rem_static > (size_t)160 * 1024) S--;
-    }
-    nn->S = S;
-    nn->NT = (S * HW + 15) / 16;
-    nn->conv_lds = lds_bytes(S);
-    nn->NTT = nn->NT > 8 ? 7 : (nn->NT > 4 ? 4 : 2); // tiles per wave; two waves cover 2*NTT >= NT tiles
-    // tail variants: <2,2> holds 64 rows, <4,4> 128 rows, <5,5> 160 rows
-    nn->S_small = nn->S_mid = nn->S_big = 0;
-    if (nn->NTT == 7) {
-        // S >= 1, so S_big >= 0; the two below it go negative where the one above is 0 (a single sample of > 160 rows)
-        nn->S_big = std::min(160 / HW, nn->S - 1);
-        nn->S_mid = std::max(0, std::min(128 / HW, nn->S_big - 1));
-        nn->S_small = std::max(0, std::min(64 / HW, nn->S_mid - 1));
-    } else if (nn->NTT == 4) {
-        nn->S_small = std::min(64 / HW, nn->S - 1);
-    }
+    TowerPlan &tp = nn->plan;
+    if (const char *why = tower_plan_build(g.H, g.W, C, hc, vf, nn->precision, tp)) { err = why; return DBAZ_EINVAL; }
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             nn->cus = cus;
     }
-    if (nn->c2 && C == 64) {
-        int Sc = MAXROWS / HW;
-        if (Sc > 16) Sc = 16;
-        // (a two-slot weight ring of 16 KB behind the images; 1.1 KB of static LDS besides)
-        const size_t ring = (size_t)2 * WRING_UNITS * 16, budget_c2 = (size_t)160 * 1024 - 1536;
-        while (Sc > 1 && lds_bytes(Sc) + ring > budget_c2) Sc--;
-        nn->S_c2 = Sc;
-        nn->NT_c2 = ((Sc * HW + 15) / 16 + 3) / 4;           // tiles per wave (4 groups)
-        nn->conv_lds_c2 = lds_bytes(Sc) + ring;
-        // worth it only where its 4 x NT_c2 tiles are filled about as well as the one-cout-tile kernel's NT (9x9: 200 of 256
-        // rows against 200 of 208)
-        const double fill_c2 = (double)Sc * HW / (64.0 * nn->NT_c2), fill_1 = (double)nn->S * HW / (16.0 * nn->NT);
-        // (0.9: 3x3 boards, 15 samples in 16 tiles against 13 in 13 -- their steps never fill a round of the main launch, but its
-        // remainder bodies keep the residual stream in registers, which is worth 1.3 % there)
-        if (fill_c2 < 0.9 * fill_1) nn->c2 = 0;
-        if (nn->NT_c2 < 1 || nn->NT_c2 > 4 || lds_bytes(Sc) + ring > budget_c2) nn->c2 = 0;
-    } else {
-        nn->c2 = 0;
-    }
     nn->tperm = nullptr;
-    if (nn->c2 && nn->NT_c2 == 4) {
+    if (tp.c2 && tp.NT_c2 == 4) {
         // the row order in which the body's edge tiles can drop the taps of their border (constant for the geometry)
         int tab[TOWER_PERM_ROWS];
-        if (tower_perm_build(g.H, g.W, nn->S_c2, tab) > 0) {
+        if (tower_perm_build(g.H, g.W, tp.S_c2, tab) > 0) {
             nn->tperm = nn_upload(nn, std::vector<unsigned char>(tab, tab + TOWER_PERM_ROWS));
             if (!nn->tperm) { err = "hipMalloc failed (row table)"; return DBAZ_EDEVICE; }
         }
     }
-    hipError_t he = tower_dispatch(nn, nullptr, TowerArgs(), nn->NTT, 0, true);
-    nn->use_rem = (nn->precision == 1 && nn->NTT == 7 && C >= 32) ? 1 : 0;
-    // the two-cout-tile main launch keeps the residual stream in registers; its remainder bodies must round the same way, and
-    // those live in k_tower_rem<64, 1>: no remainder launch, no two-cout-tile main launch
-    if (!nn->use_rem) nn->c2 = 0;
-    if (he == hipSuccess && nn->use_rem) he = tower_dispatch_rem(nn, nullptr, TowerArgs(), 0, true);
-    if (he == hipSuccess && nn->c2) he = tower_dispatch_c2(nn, nullptr, TowerArgs(), nn->NT_c2, 0, true);
-    if (he == hipSuccess && nn->tw32) he = tower_dispatch(nn, nullptr, TowerArgs(), nn->NTT, 0, true, 0);
-    if (he == hipSuccess && nn->S_mid > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 4, 0, true);
-    if (he == hipSuccess && nn->S_small > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 2, 0, true);
-    if (he == hipSuccess && nn->S_big > 0) he = tower_dispatch(nn, nullptr, TowerArgs(), 5, 0, true);
+    // the launches of a step, in the order nn_forward issues them
+    std::vector<TowerLaunch> &L = nn->launches;
+    L.clear();
+    // two cout tiles per wave (default for 64 channels) for the FULL rounds; what is left behind the last full round goes
+    // to one round of the one-cout-tile kernels, whose workgroups come in finer sizes (1, 2, 3 samples, or all S of them
+    // as role 4) -- or stays with this launch if it is more than such a round holds
+    if (tp.c2) L.push_back({tower_kernel_c2(tp.NT_c2), tp.conv_lds_c2, 0, tp.S_main(), TowerLaunch::PER_GROUP, false});
+    else L.push_back({tower_kernel(C, tp.NTT, nn->precision), tp.conv_lds, 0, tp.S_main(), TowerLaunch::PER_GROUP, false});
+    if (tp.use_rem) { // the remainder sizes in one launch (the workgroups pick theirs; TowerArgs::S stays the main launch's)
+        L.push_back({tower_kernel_rem(C, tp.c2 != 0), tp.conv_lds, -1, tp.S_main(), TowerLaunch::ONE_ROUND, false});
+    } else {          // tail <= cus * S_x samples: one round of <2,2> / <4,4> / <5,5> workgroups
+        const int tail_S[3] = {tp.S_small, tp.S_mid, tp.S_big}, tail_ntt[3] = {2, 4, 5};
+        for (int i = 0; i < 3; i++)
+            if (tail_S[i] > 0) L.push_back({tower_kernel(C, tail_ntt[i], nn->precision), tp.conv_lds, i + 1, tail_S[i], TowerLaunch::ONE_ROUND, false});
+    }
+    // safety net of the f16x3 mode: samples whose workgroup saw an activation leave f16's range are redone by the
+    // exact-f32 tower (its workgroups check the per-sample flags on the device and leave at once otherwise)
+    if (nn->tw32) L.push_back({tower_kernel(C, tp.NTT, 0), tp.conv_lds, 0, tp.S, TowerLaunch::ONE_ROUND_AT_MOST, true});
+    hipError_t he = hipSuccess;
+    for (const TowerLaunch &l : L) {
+        if (!l.kernel) { err = "no tower kernel for this geometry"; return DBAZ_EINVAL; }
+        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds);
+    }
     if (he != hipSuccess) {
         (void)hipGetLastError(); // (not left behind for the next hipGetLastError() of an unrelated call)
         err = std::string("hipFuncSetAttribute: ") + hipGetErrorString(he);
@@ -2177,9 +2105,9 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
         SimpleArgs sa;
         sa.feat = feat; sa.list = list_dev; sa.n_dev = n_dev; sa.w0 = nn->w0; sa.b0 = nn->b0; sa.s0 = nn->sn_s0; sa.t0 = nn->sn_t0;
         sa.tw = nn->tw; sa.tb = nn->tb; sa.ts = nn->sn_ts; sa.tt = nn->sn_tt; sa.tosc = nn->tosc; sa.flat = nn->sn_flat;
-        sa.overflow = nn->overflow; sa.S = nn->S;
+        sa.overflow = nn->overflow; sa.S = nn->sn_S;
         if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        const int grid = (max_n + nn->S - 1) / nn->S;
+        const int grid = (max_n + nn->sn_S - 1) / nn->sn_S;
         if (nn->precision == 1) hipLaunchKernelGGL(k_simple_trunk<1>, dim3(grid), dim3(CONV_THREADS), nn->sn_lds, s, g, sa);
         else hipLaunchKernelGGL(k_simple_trunk<0>, dim3(grid), dim3(CONV_THREADS), nn->sn_lds, s, g, sa);
         if (ev_end) (void)hipEventRecord(ev_end, s);
@@ -2200,46 +2128,24 @@ void nn_forward(NNState *nn, hipStream_t s, const float *feat, const int32_t *li
     TowerArgs ta;
     ta.feat = feat; ta.list = list_dev; ta.n_dev = n_dev; ta.in_s = nn->in_s; ta.in_t = nn->in_t; ta.w0 = nn->w0; ta.b0 = nn->b0;
     ta.tw = nn->tw; ta.tb = nn->tb; ta.tosc = nn->tosc; ta.hw = nn->hw; ta.hb = nn->hb; ta.hwp = nn->hwp; ta.hosc = nn->hosc; ta.w0p = nn->w0p; ta.osc0 = nn->osc0;
-    ta.overflow = nn->overflow; ta.ovf_flags = nn->ovf_flags; ta.fallback = 0; ta.S = nn->S; ta.nblocks = nn->blocks; ta.hc = hc;
+    ta.overflow = nn->overflow; ta.ovf_flags = nn->ovf_flags; ta.nblocks = nn->blocks; ta.hc = hc;
     ta.wfc = nn->wfc; ta.bfc = nn->bfc; ta.wv1 = nn->wv1; ta.bv1 = nn->bv1; ta.P = P; ta.V = V; ta.KP = nn->KP; ta.ntp = nn->ntp;
     ta.ntv = nn->ntv; ta.vf = nn->vf; ta.AS = AS; ta.n_used = n_used;
     ta.stamp_out = nn->stamp_out;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    ta.S_main = nn->S; ta.S_small = nn->S_small; ta.S_mid = nn->S_mid; ta.S_big = nn->S_big; ta.S_huge = 0; ta.cus = nn->cus;
-    ta.cut_round = cut_round; ta.cut_defer = cut_defer;
-    ta.role = 0; ta.S = nn->S;
-    ta.perm = nn->c2 ? nn->tperm : nullptr;
-    if (nn->c2) {
-        // two cout tiles per wave (default for 64 channels) for the FULL rounds; what is left behind the last full round goes
-        // to one round of the one-cout-tile kernels, whose workgroups come in finer sizes (1, 2, 3 samples, or all S of them
-        // as role 4) -- or stays with this launch if it is more than such a round holds
-        ta.S_main = ta.S = nn->S_c2; ta.S_huge = nn->S;
-        (void)tower_dispatch_c2(nn, s, ta, nn->NT_c2, (max_n + nn->S_c2 - 1) / nn->S_c2, false);
-    }
-    if (!nn->c2) (void)tower_dispatch(nn, s, ta, nn->NTT, (max_n + nn->S - 1) / nn->S, false);
-    if (nn->use_rem) {     // the remainder sizes in one launch (the workgroups pick theirs)
-        ta.role = -1;
-        (void)tower_dispatch_rem(nn, s, ta, nn->cus, false);
-    } else {
-        if (nn->S_small > 0) { // tail <= cus * S_small samples: one round of <2,2> workgroups
-            ta.role = 1; ta.S = nn->S_small;
-            (void)tower_dispatch(nn, s, ta, 2, nn->cus, false);
+    const TowerPlan &tp = nn->plan;
+    ta.S_main = tp.S_main(); ta.S_small = tp.S_small; ta.S_mid = tp.S_mid; ta.S_big = tp.S_big; ta.S_huge = tp.S_huge();
+    ta.cus = nn->cus; ta.cut_round = cut_round; ta.cut_defer = cut_defer;
+    ta.perm = tp.c2 ? nn->tperm : nullptr;
+    for (const TowerLaunch &l : nn->launches) {
+        ta.role = l.role; ta.S = l.S; ta.fallback = l.fallback;
+        if (l.fallback) { // alone behind the f16x3 launches: no split, the exact-f32 operands
+            ta.S_main = l.S; ta.S_small = ta.S_mid = ta.S_big = ta.S_huge = 0;
+            ta.tw = nn->tw32; ta.tb = nn->tb32; ta.w0p = nullptr; ta.hwp = nullptr;
         }
-        if (nn->S_mid > 0) {   // tail <= cus * S_mid samples: one round of <4,4> workgroups
-            ta.role = 2; ta.S = nn->S_mid;
-            (void)tower_dispatch(nn, s, ta, 4, nn->cus, false);
-        }
-        if (nn->S_big > 0) {   // tail <= cus * S_big samples: one round of <5,5> workgroups
-            ta.role = 3; ta.S = nn->S_big;
-            (void)tower_dispatch(nn, s, ta, 5, nn->cus, false);
-        }
-    }
-    if (nn->precision == 1 && nn->tw32) {
-        // safety net of the f16x3 mode: samples whose workgroup saw an activation leave f16's range are redone by the
-        // exact-f32 tower (its workgroups check the per-sample flags on the device and leave at once otherwise)
-        ta.role = 0; ta.S = ta.S_main = nn->S; ta.S_small = ta.S_mid = ta.S_big = ta.S_huge = 0; ta.fallback = 1;
-        ta.tw = nn->tw32; ta.tb = nn->tb32; ta.w0p = nullptr; ta.hwp = nullptr;
-        (void)tower_dispatch(nn, s, ta, nn->NTT, std::min((max_n + nn->S - 1) / nn->S, nn->cus), false, 0);
+        const int groups = (max_n + l.S - 1) / l.S;
+        const int grid = l.grid == TowerLaunch::PER_GROUP ? groups : l.grid == TowerLaunch::ONE_ROUND ? nn->cus : std::min(groups, nn->cus);
+        hipLaunchKernelGGL(l.kernel, dim3(grid), dim3(CONV_THREADS), l.lds, s, g, ta);
     }
     if (ev_end) (void)hipEventRecord(ev_end, s);
     // (the head FCs, softmax and tanh ran inside the tower workgroups: head_fc_fused)
@@ -2249,8 +2155,9 @@ void nn_round_info(const NNState *nn, int *round, int *rem_max)
 {
     *round = 0; *rem_max = 0;
     if (!nn || nn->kind != DBAZ_EVAL_RESNET) return;
-    *round = nn->cus * (nn->c2 ? nn->S_c2 : nn->S);
-    const int s_rem = nn->c2 ? nn->S : std::max(nn->S_big, std::max(nn->S_mid, nn->S_small));
+    const TowerPlan &tp = nn->plan;
+    *round = nn->cus * tp.S_main();
+    const int s_rem = tp.c2 ? tp.S : std::max(tp.S_big, std::max(tp.S_mid, tp.S_small));
     *rem_max = nn->cus * s_rem;
 }
 

@@ -1,21 +1,21 @@
 """Launch plan of the HIP inference tower, restated on the host.
 
-TEST INFRASTRUCTURE (oracle) -- plain-integer restatement of the host arithmetic of csrc/nn.hip that decides WHICH kernel
-body evaluates WHICH samples of a batch:
-  nn_configure   channel padding (16 / 32 / 64 / 128; f16x3 pads narrower networks to 32)
-  nn_commit      lds_bytes, S / NT / NTT, S_small / S_mid / S_big, S_c2 / NT_c2, the choice of the two-cout-tile body, use_rem
-  tower_split    the split of a batch of n samples into full rounds of the main launch and a tail
-  nn_forward     which launches exist and what role each has
-  tower_perm.h   whether the two-cout-tile body walks its rows through the table or in natural order (the counting part)
+TEST INFRASTRUCTURE (oracle) -- plain-integer restatement of the host arithmetic that decides WHICH kernel body evaluates
+WHICH samples of a batch:
+  csrc/tower_plan.h  tower_padded_channels (16 / 32 / 64 / 128; f16x3 pads narrower networks to 32), tower_lds_bytes,
+                     tower_plan_build (S / NT / NTT, S_small / S_mid / S_big, S_c2 / NT_c2, the choice of the two-cout-tile
+                     body, use_rem, both LDS sizes) and tower_split (full rounds of the main launch and a tail)
+  csrc/nn.hip        nn_commit's launch list: which launches exist and what role each has
+  csrc/tower_perm.h  whether the two-cout-tile body walks its rows through the table or in natural order (the counting part)
 
 Nothing here looks at the device: tests take the compute-unit count from torch and hand it in, then assert that the plan of a
-batch size contains the bodies the case is named after.  tests/test_nn_probe_ref.py pins the restatement to the figures the
-comments of nn.hip and DESIGN.md state.
+batch size contains the bodies the case is named after.
 
-What ties this file to the device is thin, and deliberately so (the engine's ABI does not report which body ran): the pinned
-figures, the row-table verdicts compiled from tower_perm.h, and f32_fallback_evals == len(Plan.redone()) in the safety-net
-test.  If tower_split or nn_commit and this restatement drift apart, the GPU cases still check whichever body really ran
-against float64, but the body names in their ids and in EXPERIMENTS.md are then wrong: change the two together."""
+The tie to the engine: tower_plan.h is host-only C++ that nn.hip uses unchanged, and tests/test_tower_plan.py compiles it with
+g++ and compares every field of its plan, every error, its constants and tower_split with this file, over every accepted board,
+channel count, precision and four head shapes.  tests/test_nn_probe_ref.py pins the figures the comments and DESIGN.md state
+and compares the row-table verdicts with tower_perm.h; the safety-net test asserts f32_fallback_evals == len(Plan.redone()).
+What stays untested against the device is the launch list alone (the engine's ABI does not report which body ran)."""
 import collections
 
 MAXT = 13                       # position tiles (16 rows) per workgroup of the one-cout-tile kernels
@@ -26,7 +26,7 @@ LDS_BUDGET_C2 = 160 * 1024 - 1536
 LDS_TOTAL = 160 * 1024
 MAXS = 16                       # samples per workgroup: the columns of the head FC's MFMA, the entries of slot_s
 REM_STATIC_LDS = 4 * (MAXS + MAXROWS) * 4   # k_tower_rem: slot_s[16] + rowbase_s[MAXROWS] ints in each of its four bodies
-TILES = {2: (2, 2), 4: (4, 4), 5: (5, 5), 7: (7, 6)}    # ntt -> <NTA, NTB> of tower_inst_c
+TILES = {2: (2, 2), 4: (4, 4), 5: (5, 5), 7: (7, 6)}    # ntt -> <NTA, NTB> of tower_kernel
 DBAZ_MAX_A = 256
 
 Launch = collections.namedtuple("Launch", "body first count S")
@@ -102,6 +102,7 @@ class Plan:
             S -= 1
         self.S = S
         self.NT = (S * HW + 15) // 16
+        self.conv_lds, self.conv_lds_c2 = lds_bytes(S), 0
         self.NTT = 7 if self.NT > 8 else 4 if self.NT > 4 else 2
         self.S_small = self.S_mid = self.S_big = 0
         if self.NTT == 7:
@@ -116,6 +117,7 @@ class Plan:
             while Sc > 1 and lds_bytes(Sc) + WRING_BYTES > LDS_BUDGET_C2:
                 Sc -= 1
             self.S_c2 = Sc
+            self.conv_lds_c2 = lds_bytes(Sc) + WRING_BYTES
             self.NT_c2 = ((Sc * HW + 15) // 16 + 3) // 4
             fill_c2 = float(Sc * HW) / (64.0 * self.NT_c2) if self.NT_c2 else 0.0
             fill_1 = float(S * HW) / (16.0 * self.NT)
@@ -127,7 +129,7 @@ class Plan:
         self.use_rem = 1 if precision == 1 and self.NTT == 7 and C >= 32 else 0
         if not self.use_rem:
             self.c2 = 0
-        # (nn_commit builds the table before use_rem clears c2; the table is only handed to the kernel where c2 survives)
+        # (nn_commit builds the table after the plan: only where c2 survives)
         self.perm = bool(self.c2 and self.NT_c2 == 4 and perm_table_applies(H, W, self.S_c2))
         self.S_main = self.S_c2 if self.c2 else S
         self.S_huge = S if self.c2 else 0
@@ -248,12 +250,13 @@ def reachable(head_channels=(16,), value_fc=(8,)):
 
 
 def compiled():
-    """Every instantiation the three dispatchers can name"""
+    """Every instantiation the three lookups (tower_kernel, tower_kernel_c2, tower_kernel_rem) can name; f16x3 has no <5,5>
+    kernel of its own (S_big > 0 with f16x3 is use_rem: the 5-tile body is k_tower_rem's)"""
     out = []
     for C in (16, 32, 64, 128):
         for a, b in TILES.values():
             out.append("tower_dispatch k_tower<%d,%d,%d,0>" % (C, a, b))
-            if C >= 32:
+            if C >= 32 and (a, b) != (5, 5):
                 out.append("tower_dispatch k_tower<%d,%d,%d,1>" % (C, a, b))
     for nt in (1, 2, 3, 4):
         out.append("tower_dispatch_c2 k_tower<64,%d,0,1,true>" % nt)

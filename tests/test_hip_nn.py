@@ -147,6 +147,34 @@ def test_f16x3_split_precision_mode(rows, cols, ch, nb, n, precision=1):
     e0.close()
 
 
+@pytest.mark.parametrize("rows,cols,ch,precision,c2,perm,use_rem", [
+    (3, 3, 64, 1, 1, True, 1),      # two-cout-tile main body with the row table
+    (6, 5, 64, 1, 0, False, 1),     # two-cout-tile body rejected by the fill rule
+    (2, 2, 32, 0, 0, False, 0)])    # exact f32: no remainder kernel, <2,2> / <4,4> / <5,5> launches of their own
+def test_commit_twice_gives_the_same_network(rows, cols, ch, precision, c2, perm, use_rem):
+    """dbaz_nn_commit again on the same handle, without dbaz_nn_configure: the plan (csrc/tower_plan.h) starts from the network's
+    shape alone, not from what the last commit left, so the same launches evaluate the batch -- one full round of the main launch
+    and the first tail body -- and (p, v) are the same bytes."""
+    from oracle import nn_plan
+    m = nn_ref.ResNetZeroRef(rows, cols, ch, 2)
+    plan = nn_plan.Plan(rows, cols, ch, m.cfg["head_channels"], m.cfg["value_fc"], precision,
+                        torch.cuda.get_device_properties(0).multi_processor_count)
+    assert (plan.c2, plan.perm, plan.use_rem) == (c2, perm, use_rem)
+    tails = plan.tail_bodies()
+    n = plan.n_for(tails[0][1], 1) if tails else plan.round + 1
+    assert len(plan.launches(n)) == 2
+    torch.manual_seed(rows * 31 + cols + ch)
+    nn_ref.randomize_bn(m, 5)
+    e = engine_for(rows, cols, m, n_slots=n, precision=precision)
+    X = _positions(rows, cols, n, 5)
+    p, v = e.predict(X)
+    e._ck(e._L.dbaz_nn_commit(e.h))
+    p2, v2 = e.predict(X)
+    e.close()
+    assert np.isfinite(p).all() and np.abs(p.sum(1) - 1.0).max() < 1e-5
+    assert p.tobytes() == p2.tobytes() and v.tobytes() == v2.tobytes()
+
+
 def _scaled_block_net(K):
     """ResNetZero whose FUNCTION is that of an ordinary random-init net, but whose activations between conv1 and
     conv2 of block 1 are K times larger (bn1 scaled by K, conv2's weights by 1/K; ReLU is positively homogeneous)."""

@@ -96,9 +96,7 @@ def test_plan_reachable_instantiations():
     since a workgroup holds at most 16 samples (1x1 and 1x3 reached them with 16 samples in 64 and 128 rows)"""
     got = nn_plan.reachable()
     dead = [nm for nm in nn_plan.compiled() if nm not in got]
-    assert dead == ["tower_dispatch k_tower<32,5,5,1>",
-                    "tower_dispatch k_tower<64,5,5,1>", "tower_dispatch k_tower<128,5,5,1>",
-                    "tower_dispatch_c2 k_tower<64,1,0,1,true>", "tower_dispatch_c2 k_tower<64,2,0,1,true>",
+    assert dead == ["tower_dispatch_c2 k_tower<64,1,0,1,true>", "tower_dispatch_c2 k_tower<64,2,0,1,true>",
                     "tower_dispatch_rem k_tower_rem<32>/<7,6>", "tower_dispatch_rem k_tower_rem<64>/<7,6>",
                     "tower_dispatch_rem k_tower_rem<128>/<7,6>"]
     assert set(got) <= set(nn_plan.compiled())
