@@ -25,6 +25,7 @@ UNITS = [
     ("train.hip", []),
     ("train_net.hip", []),
     ("solver.hip", []),
+    ("endgame.hip", []),
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/dbaz.h"
 
 #define SOLVER_MAX_E 31              // table int8 D[2^E] of at most 2 GiB
@@ -29,6 +31,37 @@ __host__ __device__ __forceinline__ int solver_move_q(uint32_t o0, uint32_t o1, 
 {
     const int c = (int)((m & o0) == o0) + (int)((m & o1) == o1);
     return c ? c + d_next : -d_next;
+}
+
+// What a feature row says beyond its edges: margin = (mover's boxes) - (opponent's boxes), and get_result
+// (dots_boxes_game.py:51-59) of a finished game, early end included (DBAZ_RESULT_NONE otherwise).  n_boxes = R*C, closed = boxes
+// with all four edges drawn, own_b2c = plane 2, the mover's doubled boxes_to_close.  Shared by solver.hip and endgame.hip.
+struct RowFacts {
+    int margin, res;
+};
+__host__ __device__ __forceinline__ RowFacts solver_facts(int n_boxes, int closed, int own_b2c)
+{
+    const int mine = (n_boxes - own_b2c) / 2, theirs = closed - mine;
+    const int opp_b2c = n_boxes - 2 * theirs;
+    RowFacts f;
+    f.margin = mine - theirs;
+    f.res = DBAZ_RESULT_NONE;
+    if (own_b2c == 0 && opp_b2c == 0) f.res = 0;
+    else if (own_b2c < 0) f.res = 1;
+    else if (opp_b2c < 0) f.res = -1;
+    return f;
+}
+
+// masks of `bits` bits in ascending popcount order; off[k] .. off[k + 1] holds popcount k
+static inline void popcount_order(int bits, std::vector<uint32_t> &perm, std::vector<uint32_t> &off)
+{
+    const uint32_t n = 1u << bits;
+    off.assign(bits + 2, 0);
+    for (uint32_t m = 0; m < n; m++) off[__builtin_popcount(m) + 1]++;
+    for (int k = 0; k <= bits; k++) off[k + 1] += off[k];
+    std::vector<uint32_t> at(off.begin(), off.end() - 1);
+    perm.resize(n);
+    for (uint32_t m = 0; m < n; m++) perm[at[__builtin_popcount(m)]++] = m;
 }
 
 // The solved table as an evaluator of the search engine (engine.hip; kernel and contract: k_solver_eval in solver.hip).

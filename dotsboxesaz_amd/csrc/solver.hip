@@ -128,26 +128,13 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
 
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
 
-// What a feature row says beyond its mask: margin = (mover's boxes) - (opponent's boxes), and get_result
-// (dots_boxes_game.py:51-59) of a finished game, early end included (DBAZ_RESULT_NONE otherwise).  own_b2c = plane 2, the
-// mover's doubled boxes_to_close.  Shared by k_solver_score and k_solver_eval.
-struct RowFacts {
-    int margin, res;
-};
+// solver_facts (solver.h) of a position given as a mask: the closed boxes come from the box masks.  Shared by k_solver_score and
+// k_solver_eval.
 __device__ __forceinline__ RowFacts solver_row_facts(const SolverGeo &g, uint32_t m, int own_b2c)
 {
     int closed = 0;
     for (int b = 0; b < g.n_boxes; b++) closed += (int)((m & g.box[b]) == g.box[b]);
-    const int B = g.rows * g.cols;
-    const int mine = (B - own_b2c) / 2, theirs = closed - mine;
-    const int opp_b2c = B - 2 * theirs;
-    RowFacts f;
-    f.margin = mine - theirs;
-    f.res = DBAZ_RESULT_NONE;
-    if (own_b2c == 0 && opp_b2c == 0) f.res = 0;
-    else if (own_b2c < 0) f.res = 1;
-    else if (opp_b2c < 0) f.res = -1;
-    return f;
+    return solver_facts(g.rows * g.cols, closed, own_b2c);
 }
 
 // One thread per feature row x int16 [3*HW] (planes 0, 1: edges; plane 2: the mover's doubled boxes_to_close).
@@ -264,18 +251,6 @@ static void solver_geometry(int rows, int cols, SolverGeo &g)
             g.box[g.n_boxes++] = bm;
             for (int j = 0; j < 4; j++) g.other[ed[j]][used[ed[j]]++] = bm & ~(1u << ed[j]);
         }
-}
-
-// masks of `bits` bits in ascending popcount order; off[k] .. off[k + 1] holds popcount k
-static void popcount_order(int bits, std::vector<uint32_t> &perm, std::vector<uint32_t> &off)
-{
-    const uint32_t n = 1u << bits;
-    off.assign(bits + 2, 0);
-    for (uint32_t m = 0; m < n; m++) off[__builtin_popcount(m) + 1]++;
-    for (int k = 0; k <= bits; k++) off[k + 1] += off[k];
-    std::vector<uint32_t> at(off.begin(), off.end() - 1);
-    perm.resize(n);
-    for (uint32_t m = 0; m < n; m++) perm[at[__builtin_popcount(m)]++] = m;
 }
 
 // 12 of 24 bits (3x3), 14 of 31 (3x4) measured fastest: small subcubes leave more workgroups per launch

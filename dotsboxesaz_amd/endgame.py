@@ -1,0 +1,196 @@
+"""Exact endgame solver for any board (A <= 256): true values of positions with at most 16 free edges.
+
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --bench 4096 [--free 16]
+
+The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
+over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .solver import ILLEGAL, _margin, edge_actions
+
+MAX_FREE = 16  # ENDGAME_MAX_FREE
+
+
+class Endgame:
+    """Endgame scorer of one board size on one GPU.  A > 256 or max_free outside 1 .. 16 raises DbazError before the device is
+    touched."""
+
+    def __init__(self, rows, cols, device=0, max_free=MAX_FREE):
+        self._L = _lib.load()
+        self.rows, self.cols, self.device, self.max_free = int(rows), int(cols), int(device), int(max_free)
+        self.H, self.W = self.rows + 1, self.cols + 1
+        self.A, self.F = 2 * self.H * self.W, 3 * self.H * self.W
+        self.h = C.c_void_p()
+        rc = self._L.dbaz_endgame_create(self.rows, self.cols, self.device, self.max_free, C.byref(self.h))
+        if rc != _lib.OK:
+            self.h = None
+            self._ck(rc)
+        self.max_free = self.max_free or MAX_FREE
+        self.actions = edge_actions(self.rows, self.cols)
+        self.n_edges = len(self.actions)
+
+    def _ck(self, rc):
+        if rc != _lib.OK:
+            msg = self._L.dbaz_endgame_last_error(self.h)
+            raise _lib.DbazError(rc, msg.decode() if msg else "error %d" % rc)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dbaz_endgame_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def score(self, x, pi=None):
+        """x: feature rows int16 [n, 3*H*W] (or [n, 3, H, W]); pi: optional float32 [n, A].  numpy arrays or torch tensors on
+        the handle's device; the outputs come back as the same kind, queued on torch's current stream.  Returns dict(value int8
+        [n], diff int8 [n], q int8 [n, A], policy_mass float32 [n] or None, n_free int16 [n], solved bool [n]); a row with
+        n_free > max_free is not solved: value 0, diff -128, q all -128, policy_mass 0."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        n = int(xt.shape[0])
+        pt = None
+        if pi is not None:
+            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
+            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
+            if int(pt.shape[0]) != n:
+                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
+        value = torch.empty(n, dtype=torch.int8, device=dev)
+        diff = torch.empty(n, dtype=torch.int8, device=dev)
+        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_endgame_score(self.h, C.c_int32(n), ptr(xt), ptr(pt), ptr(value), ptr(diff), ptr(q), ptr(mass), ptr(n_free),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=n_free <= self.max_free)
+        if as_numpy:
+            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+        return out
+
+
+def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FREE, device=0):
+    """Scores the rows Engine.fetch_samples() / generate_games return (x, pi, played, z) on any board: the counterpart of
+    solver.score_samples for the rows with at most max_free free edges.
+    Per row: value, policy_mass, played_optimal (False for rows without a move and for unsolved rows), n_free, solved.
+    Means: optimal_policy_mass and played_optimal_rate over the solved rows of unfinished positions, z_agreement over the solved
+    rows, coverage = the share of rows solved.  by_free: arrays of length max_free + 1 indexed by the number of free edges --
+    rows (solved rows of that depth), played_optimal_rate, optimal_policy_mass, z_agreement (NaN where there is no row).
+    endgame: an Endgame of the rows' board size (its max_free holds).  Without one the board size comes from rows / cols, or from
+    x's shape [n, 3, H, W]; flat rows [n, 3*H*W] alone do not tell it."""
+    x = np.asarray(samples["x"])
+    if endgame is None:
+        if rows is None or cols is None:
+            if x.ndim != 4:
+                raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or endgame=Endgame(rows, cols)")
+            rows, cols = x.shape[2] - 1, x.shape[3] - 1
+        endgame = Endgame(rows, cols, device, max_free)
+    g, n = endgame, len(x)
+    x = x.reshape(n, g.F)
+    r = g.score(x, np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
+    solved, n_free = r["solved"], r["n_free"].astype(np.int64)
+    played = np.asarray(samples["played"]).astype(np.int64).reshape(n)
+    has_move = (played >= 0) & (played < g.A)
+    q_played = np.where(has_move, r["q"][np.arange(n), np.clip(played, 0, g.A - 1)], ILLEGAL).astype(np.int64)
+    open_ = solved & (r["q"] != ILLEGAL).any(axis=1)  # solved and not a finished game
+    played_optimal = has_move & (q_played != ILLEGAL) & (np.sign(_margin(g, x) + q_played) == r["value"])
+    z_ok = np.asarray(samples["z"]).reshape(n) == r["value"]
+    mass = r["policy_mass"].astype(np.float64)
+
+    def mean(values, where):
+        return float(values[where].sum() / where.sum()) if where.any() else float("nan")
+
+    depth = [solved & (n_free == f) for f in range(g.max_free + 1)]
+    by_free = dict(rows=np.array([int(d.sum()) for d in depth], np.int64),
+                   played_optimal_rate=np.array([mean(played_optimal, d & open_) for d in depth]),
+                   optimal_policy_mass=np.array([mean(mass, d & open_) for d in depth]),
+                   z_agreement=np.array([mean(z_ok, d) for d in depth]))
+    return dict(value=r["value"], policy_mass=r["policy_mass"], played_optimal=played_optimal, n_free=r["n_free"], solved=solved,
+                optimal_policy_mass=mean(mass, open_), played_optimal_rate=mean(played_optimal, open_), z_agreement=mean(z_ok, solved),
+                coverage=float(solved.mean()) if n else 0.0, by_free=by_free)
+
+
+def random_rows(rows, cols, n, free, seed=0):
+    """n feature rows int16 [n, 3*H*W] with free[i] (or free, a number) free edges in row i: all other edges drawn, at random;
+    the closed boxes shared out so that the row is a position of an unfinished game wherever one exists with those edges."""
+    rs = np.random.RandomState(seed)
+    H, W = rows + 1, cols + 1
+    HW, acts = H * W, edge_actions(rows, cols)
+    free = np.broadcast_to(np.asarray(free, np.int64), (n,))
+    x = np.ones((n, 3 * HW), np.int16)  # sentinel slots are 1, as get_features has them
+    x[:, acts] = np.argsort(rs.rand(n, len(acts)), axis=1) >= free[:, None]  # a random permutation's first `free` edges stay free
+    e = x[:, :2 * HW] != 0
+    closed = np.zeros(n, np.int64)
+    for l in range(rows):
+        for c in range(cols):
+            closed += e[:, l * W + c] & e[:, (l + 1) * W + c] & e[:, HW + l * W + c] & e[:, HW + l * W + c + 1]
+    x[:, 2 * HW:] = (rows * cols - 2 * (closed // 2))[:, None]
+    return x
+
+
+def _bench(g, n, free):
+    """HIP-event milliseconds of one dbaz_endgame_score call on n rows that all have `free` free edges, and on n rows with n_free
+    uniform in 0 .. 16: outputs preallocated, median of 5 after a warm-up"""
+    import torch
+    dev = torch.device("cuda", g.device)
+    value, diff = torch.empty(n, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    q = torch.empty((n, g.A), dtype=torch.int8, device=dev)
+    n_free = torch.empty(n, dtype=torch.int16, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+
+    def timed(x):
+        ms = []
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for i in range(6):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                g._ck(g._L.dbaz_endgame_score(g.h, C.c_int32(n), ptr(x), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), stream))
+                t1.record()
+                t1.synchronize()
+                if i:  # the first run warms up
+                    ms.append(t0.elapsed_time(t1))
+        return float(np.median(ms))
+
+    out = dict(bench_rows=int(n), free=int(free))
+    mixed = np.random.RandomState(1).randint(0, MAX_FREE + 1, n)
+    for name, f in (("deep", free), ("mixed", np.minimum(mixed, g.n_edges))):
+        x = torch.as_tensor(random_rows(g.rows, g.cols, n, np.minimum(f, g.n_edges))).to(dev)
+        ms = timed(x)
+        assert np.array_equal(n_free.cpu().numpy(), np.broadcast_to(np.minimum(f, g.n_edges), (n,)))
+        out[name + "_ms"] = round(ms, 4)
+        out[name + "_rows_per_s"] = round(n / (ms * 1e-3))
+    return out
+
+
+def main(argv=None):
+    import argparse
+    import json
+    ap = argparse.ArgumentParser(description="time the endgame solver on generated rows and print one JSON line")
+    ap.add_argument("--rows", type=int, default=6)
+    ap.add_argument("--cols", type=int, default=6)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--max-free", type=int, default=MAX_FREE)
+    ap.add_argument("--bench", type=int, default=4096, metavar="N", help="rows per timed call (median of 5 after a warm-up)")
+    ap.add_argument("--free", type=int, default=MAX_FREE, help="free edges of every row of the first batch")
+    a = ap.parse_args(argv)
+    g = Endgame(a.rows, a.cols, a.device, a.max_free)
+    out = dict(rows=a.rows, cols=a.cols, E=g.n_edges, max_free=g.max_free)
+    out.update(_bench(g, a.bench, a.free))
+    print(json.dumps(out))
+    g.close()
+
+
+if __name__ == "__main__":
+    main()

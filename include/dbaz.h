@@ -439,6 +439,24 @@ int dbaz_perfect_policy(dbaz_solver *s, int32_t n, const int16_t *x_dev, uint64_
  * dbaz_search / dbaz_search_timed / dbaz_selfplay_start before the attach -> DBAZ_ESTATE. */
 int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s, uint64_t pick_seed, int32_t solver_reads);
 
+/* ---- exact endgame solver for any board: true values of positions with few free edges ---------------------
+ * The reference has no counterpart.  D of the solver above depends only on which edges are still free, so a position with F free
+ * edges on ANY board with A <= DBAZ_MAX_A is a game over the 2^F subsets of those edges; for F <= max_free <= 16 one workgroup
+ * solves it in LDS.  No table, no solve step, no dbaz_engine; one handle per board size and GPU. */
+typedef struct dbaz_endgame dbaz_endgame;
+const char *dbaz_endgame_last_error(const dbaz_endgame *g); /* g == NULL: why dbaz_endgame_create failed */
+/* max_free: 0 = 16.  rows, cols < 1, A > DBAZ_MAX_A or max_free outside 0 .. 16 -> DBAZ_EINVAL before the device is touched */
+int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_endgame **out);
+void dbaz_endgame_destroy(dbaz_endgame *g);
+/* Scores n feature rows (x, pi as for dbaz_solver_score); DEVICE pointers, QUEUED on the caller's stream; the grid is n.
+ *   n_free [n]       F, the number of free real edges of the row
+ *   value, diff, q, policy_mass as dbaz_solver_score writes them, diff = D[0] of the subgame (the same number as the table's
+ *   D[mask]); a finished game (early end included) gets value = get_result, q all -128 and policy_mass 0.
+ * A row with F > max_free is NOT solved: value 0, diff -128, q all -128, policy_mass 0.  pi_dev == NULL: mass_dev is not written.
+ * n == 0 is a no-op. */
+int dbaz_endgame_score(dbaz_endgame *g, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
+                       int8_t *q_dev /*[n][A]*/, float *mass_dev, int16_t *n_free_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
