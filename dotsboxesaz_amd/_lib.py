@@ -34,7 +34,8 @@ SYMBOLS = [
     "dbaz_az_loss_workspace_bytes", "dbaz_az_loss", "dbaz_sgd_step",
     "dbaz_solver_last_error", "dbaz_solver_create", "dbaz_solver_destroy", "dbaz_solver_solve", "dbaz_solver_info", "dbaz_solver_table",
     "dbaz_solver_score", "dbaz_perfect_policy", "dbaz_attach_solver",
-    "dbaz_endgame_last_error", "dbaz_endgame_create", "dbaz_endgame_destroy", "dbaz_endgame_score",
+    "dbaz_endgame_last_error", "dbaz_endgame_create", "dbaz_endgame_destroy", "dbaz_endgame_score", "dbaz_exact_policy", "dbaz_exact_policy_from", "dbaz_attach_endgame",
+    "dbaz_get_endgame_stats",
 ]
 
 
@@ -181,13 +182,18 @@ def load():
     L.dbaz_endgame_destroy.argtypes = [vp]
     L.dbaz_endgame_destroy.restype = None
     L.dbaz_endgame_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dbaz_exact_policy.argtypes = [vp, i32, vp, C.c_uint64, vp, vp, vp, vp]
+    L.dbaz_exact_policy_from.argtypes = [vp, i32, vp, i32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_float), vp]
+    L.dbaz_attach_endgame.argtypes = [vp, i32, vp, C.c_uint64, i32]
+    L.dbaz_get_endgame_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",
-                        "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy", "dbaz_endgame_last_error", "dbaz_endgame_destroy"):
+                        "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy", "dbaz_endgame_last_error", "dbaz_endgame_destroy", "dbaz_get_endgame_stats"):
             fn.restype = C.c_int
     L.dbaz_bn2d_workspace_bytes.restype = C.c_int64
     L.dbaz_az_loss_workspace_bytes.restype = C.c_int64
+    L.dbaz_get_endgame_stats.restype = None
     _lib = L
     return L
 

@@ -21,3 +21,43 @@ struct EndgameGeo {
     const uint16_t *perm;
     const uint32_t *off;
 };
+
+// ---- one game's table as an evaluator inside the search (engine.hip / tree.hip; kernels: k_endgame_table, k_endgame_eval) --------
+// D depends only on which edges are free: once a search root has F0 <= max_free free edges, every position that can follow it in
+// that game is a subset of those edges.  The slot keeps the root's 2^F0-byte table in HBM and answers the leaves by lookup.
+//
+// begin_search (tree.hip) leaves a request for every search that starts under a model with an endgame attached; k_endgame_table,
+// one workgroup per slot, returns at once where there is none.
+struct EndgameReq {
+    uint64_t free_edges[4]; // the root's free real edges by action index
+    int64_t game;           // Slot::game_idx
+    int32_t want;           // 1: a search has started; cleared by k_endgame_table
+    int32_t model;          // the model that searches (its pick seed serves the leaves)
+};
+
+// Header of a slot's table.  The table serves a position of game `game` whose free edges are a subset of free_edges; compact edge
+// j = the j-th of free_edges in ascending action order, bit j of a table index = compact edge j has been drawn since.
+struct EndgameSlotHdr {
+    uint64_t free_edges[4];
+    int64_t game;                            // validity stamp: the slot's game when the table was solved
+    int32_t valid, F0;
+    int32_t model, pad;
+    uint32_t other[ENDGAME_MAX_FREE][2];     // solver_move_q's box masks over the compact edges
+    uint8_t act[ENDGAME_MAX_FREE];           // compact edge -> action index
+};
+
+// what the search side asks (tree.hip): does the slot's table serve the leaves of a search of game `game`
+__host__ __device__ __forceinline__ bool endgame_hdr_serves(const EndgameSlotHdr &h, int64_t game) { return h.valid != 0 && h.game == game; }
+
+struct dbaz_endgame;
+// the engine's side, like solver_serves / solver_forward (solver.h)
+bool endgame_serves(const dbaz_endgame *g, int rows, int cols, int device, int *max_free);
+size_t endgame_table_stride(const dbaz_endgame *g); // bytes of one slot's table region: max(16, 2^max_free)
+// stats [2]: tables solved, leaves served (cumulative, device)
+void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
+                    unsigned long long *stats);
+// nn_forward's contract on float feature planes: rows feat[list[j]], j < *n_dev <= max_n, of slot list[j] / per_slot, to
+// P[list[j] * AS + a] and V[list[j]]; seeds [2]: the pick seed of each model
+void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
+                     const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
+                     int AS, unsigned long long *stats);

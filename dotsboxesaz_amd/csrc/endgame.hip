@@ -1,6 +1,6 @@
 // endgame.hip -- exact endgame solver for ANY board the engine supports (A <= 256): a position with F <= 16 free edges is a game
-// over the 2^F subsets of those edges, and one workgroup solves it in LDS.  No table in HBM, no solve step, no
-// dbaz_engine, no search or network code.
+// over the 2^F subsets of those edges, and one workgroup solves it in LDS.  No solve step, no dbaz_engine, no
+// search or network code: the engine reaches the evaluator kernels below through the four functions at the end (endgame.h).
 //
 // k_endgame_score, one workgroup per feature row x int16 [3*HW] (planes 0, 1: edges; plane 2: the mover's doubled boxes_to_close):
 //   1. setup: lane i < E looks at real edge i; the free ones are ranked in ascending action order (ballot + per-wave counts):
@@ -10,9 +10,12 @@
 //   2. solve: D[mask] of solver.hip over the 2^F masks of the compact edges, popcount layers F .. 0, one barrier each; the masks
 //      of a layer come from the popcount-sorted list of F bits (built on the host at handle creation), so every lane has a state.
 //   3. outputs with dbaz_solver_score's meaning, plus n_free.
+// k_endgame_policy: steps 1 and 2, then a one-hot optimal move and the true value per row (dbaz_exact_policy).
+// k_endgame_table / k_endgame_eval: a search root's table kept per slot in HBM, and the leaves of that game answered from it.
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -45,59 +48,59 @@ static int gerr(dbaz_endgame *g, int code, const char *fmt, ...)
     } while (0)
 
 // ------------------------------------------------------------------------------------
-// kernel
+// kernels
 // ------------------------------------------------------------------------------------
 static __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
 
-__global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g, const int16_t *__restrict__ x, const float *__restrict__ pi,
-                                                                   int8_t *__restrict__ value, int8_t *__restrict__ diff,
-                                                                   int8_t *__restrict__ q, float *__restrict__ mass,
-                                                                   int16_t *__restrict__ n_free)
+#define ENDGAME_TABLE_GRID 1024 // workgroups of k_endgame_table: four rounds of the chip at two per CU
+
+// static LDS of one workgroup, next to the dynamic int8 table [2^max_free]
+struct EndgameLds {
+    int16_t cidx[DBAZ_MAX_A];               // action -> compact edge, -1: drawn or a sentinel slot
+    uint32_t other[ENDGAME_MAX_FREE][2];
+    uint8_t act[ENDGAME_MAX_FREE];          // compact edge -> action
+    int wave[DBAZ_MAX_A / 64];
+    int closed;
+};
+
+// step 1 of the header comment for one position; returns F, the same in every thread.  F > g.max_free: nothing but F is valid
+// (the caller returns; no thread is left behind a barrier).  Otherwise L is complete and visible to the whole workgroup.
+// drawn(a): is the edge (or sentinel slot) of action index a drawn -- a feature row, or the free-edge mask of a search root
+struct RowEdges {
+    const int16_t *xr;
+    __device__ __forceinline__ bool operator()(int a) const { return xr[a] != 0; }
+};
+struct MaskEdges {
+    uint64_t free_edges[4];
+    __device__ __forceinline__ bool operator()(int a) const { return !((free_edges[a >> 6] >> (a & 63)) & 1ull); }
+};
+
+template <typename Edges>
+static __device__ __forceinline__ int endgame_setup(const EndgameGeo &g, const Edges &drawn, EndgameLds &L)
 {
-    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [2^max_free]
-    __shared__ int16_t s_cidx[DBAZ_MAX_A];                      // action -> compact edge, -1: drawn or a sentinel slot
-    __shared__ uint32_t s_other[ENDGAME_MAX_FREE][2];
-    __shared__ uint8_t s_act[ENDGAME_MAX_FREE];                 // compact edge -> action
-    __shared__ int s_wave[DBAZ_MAX_A / 64];
-    __shared__ int s_closed;
-
     const int tid = threadIdx.x, lane = tid & 63;
-    const size_t r = blockIdx.x;
-    const int16_t *xr = x + r * 3 * (size_t)g.HW;
-
-    // 1. the free real edges, ranked
-    if (tid < DBAZ_MAX_A) s_cidx[tid] = -1;
-    if (tid == 0) s_closed = 0;
+    if (tid < DBAZ_MAX_A) L.cidx[tid] = -1;
+    if (tid == 0) L.closed = 0;
     const int a_mine = tid < g.E ? (int)g.action[tid] : 0;
-    const bool is_free = tid < g.E && xr[a_mine] == 0;
+    const bool is_free = tid < g.E && !drawn(a_mine);
     const uint64_t bal = __ballot(is_free);
-    if (tid < DBAZ_MAX_A && lane == 0) s_wave[tid >> 6] = __popcll(bal);
+    if (tid < DBAZ_MAX_A && lane == 0) L.wave[tid >> 6] = __popcll(bal);
     __syncthreads();
     int F = 0, before = 0;
     for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
-        F += s_wave[w];
-        if (w < (tid >> 6)) before += s_wave[w];
+        F += L.wave[w];
+        if (w < (tid >> 6)) before += L.wave[w];
     }
-    int8_t *qr = q + r * (size_t)g.A;
-    if (F > g.max_free) { // not solved: n_free says why
-        for (int a = tid; a < g.A; a += ENDGAME_THREADS) qr[a] = -128;
-        if (tid == 0) {
-            value[r] = 0;
-            diff[r] = -128;
-            if (mass) mass[r] = 0.0f;
-            n_free[r] = (int16_t)F;
-        }
-        return;
-    }
+    if (F > g.max_free) return F;
     const int j = before + __popcll(bal & ((1ull << lane) - 1ull));
     if (is_free) {
-        s_cidx[a_mine] = (int16_t)j;
-        s_act[j] = (uint8_t)a_mine;
+        L.cidx[a_mine] = (int16_t)j;
+        L.act[j] = (uint8_t)a_mine;
     }
     const int W = g.cols + 1, B = g.rows * g.cols;
     for (int b = tid; b < B; b += ENDGAME_THREADS) {
         const int at = (b / g.cols) * W + b % g.cols;
-        if (xr[at] != 0 && xr[at + W] != 0 && xr[g.HW + at] != 0 && xr[g.HW + at + 1] != 0) atomicAdd(&s_closed, 1);
+        if (drawn(at) && drawn(at + W) && drawn(g.HW + at) && drawn(g.HW + at + 1)) atomicAdd(&L.closed, 1);
     }
     __syncthreads();
     if (is_free)
@@ -107,20 +110,26 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g,
             if (nb[0] >= 0) {
                 o = 0;
                 for (int i = 0; i < 3; i++) {
-                    const int c = s_cidx[nb[i]];
+                    const int c = L.cidx[nb[i]];
                     if (c >= 0) o |= 1u << c;
                 }
             }
-            s_other[j][k] = o;
+            L.other[j][k] = o;
         }
     __syncthreads();
+    return F;
+}
 
-    // 2. the subgame, by popcount layers; the box masks are the same for every lane: keep them in scalar registers
+// step 2: the subgame of the F compact edges into sd[2^F], by popcount layers; the box masks are the same for every lane: keep
+// them in scalar registers.  Ends behind a barrier: sd is complete for the whole workgroup.
+static __device__ __forceinline__ void endgame_solve(const EndgameGeo &g, int F, const EndgameLds &L, int8_t *sd)
+{
+    const int tid = threadIdx.x;
     uint32_t o0[ENDGAME_MAX_FREE], o1[ENDGAME_MAX_FREE];
 #pragma unroll
     for (int b = 0; b < ENDGAME_MAX_FREE; b++) {
-        o0[b] = b < F ? __builtin_amdgcn_readfirstlane(s_other[b][0]) : SOLVER_NO_BOX;
-        o1[b] = b < F ? __builtin_amdgcn_readfirstlane(s_other[b][1]) : SOLVER_NO_BOX;
+        o0[b] = b < F ? __builtin_amdgcn_readfirstlane(L.other[b][0]) : SOLVER_NO_BOX;
+        o1[b] = b < F ? __builtin_amdgcn_readfirstlane(L.other[b][1]) : SOLVER_NO_BOX;
     }
     const uint32_t full = (1u << F) - 1u;
     const uint16_t *list = g.perm + full;
@@ -141,15 +150,66 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g,
         }
         __syncthreads();
     }
+}
+
+// The evaluator's epilogue, one wavefront per position, lane = one compact edge of it (at most 64): cand = the lane's edge is
+// free and the game is open, q its worth, action its action index.  Returns the picked action in every lane (-1: no candidate):
+// the k-th member of the optimal set in ascending lane (= action) order, k = 0 without a seed, otherwise
+// solver_pick_mix(key, seed) % n_opt with key = XOR over the free real edges a of 1 << (a & 63) -- a function of the position
+// alone, whatever subgame the lanes are numbered in.
+static __device__ __forceinline__ int endgame_pick(bool cand, int q, int action, uint64_t pick_seed)
+{
+    int best = cand ? q : -1024;
+    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
+    uint64_t opt = __ballot(cand && q == best);
+    if (!opt) return -1;
+    int k = 0;
+    if (pick_seed) {
+        uint32_t lo = cand ? (uint32_t)(1ull << (action & 63)) : 0u, hi = cand ? (uint32_t)((1ull << (action & 63)) >> 32) : 0u;
+        for (int o = 32; o > 0; o >>= 1) {
+            lo ^= (uint32_t)__shfl_xor((int)lo, o);
+            hi ^= (uint32_t)__shfl_xor((int)hi, o);
+        }
+        k = (int)(solver_pick_mix(((uint64_t)hi << 32) | lo, pick_seed) % (uint64_t)__popcll(opt));
+    }
+    for (; k > 0; k--) opt &= opt - 1ull;
+    return __shfl(action, __ffsll((long long)opt) - 1);
+}
+
+__global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g, const int16_t *__restrict__ x, const float *__restrict__ pi,
+                                                                   int8_t *__restrict__ value, int8_t *__restrict__ diff,
+                                                                   int8_t *__restrict__ q, float *__restrict__ mass,
+                                                                   int16_t *__restrict__ n_free)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [2^max_free]
+    __shared__ EndgameLds L;
+
+    const int tid = threadIdx.x;
+    const size_t r = blockIdx.x;
+    const int16_t *xr = x + r * 3 * (size_t)g.HW;
+
+    const int F = endgame_setup(g, RowEdges{xr}, L);
+    int8_t *qr = q + r * (size_t)g.A;
+    if (F > g.max_free) { // not solved: n_free says why
+        for (int a = tid; a < g.A; a += ENDGAME_THREADS) qr[a] = -128;
+        if (tid == 0) {
+            value[r] = 0;
+            diff[r] = -128;
+            if (mass) mass[r] = 0.0f;
+            n_free[r] = (int16_t)F;
+        }
+        return;
+    }
+    endgame_solve(g, F, L, sd);
 
     // 3. outputs
-    const RowFacts f = solver_facts(B, s_closed, (int)xr[2 * g.HW]);
+    const RowFacts f = solver_facts(g.rows * g.cols, L.closed, (int)xr[2 * g.HW]);
     const bool open = f.res == DBAZ_RESULT_NONE;
     const int d0 = (int)sd[0];
     const int v = open ? sgn(f.margin + d0) : f.res;
     for (int a = tid; a < g.A; a += ENDGAME_THREADS) {
-        const int c = s_cidx[a];
-        qr[a] = (int8_t)(open && c >= 0 ? solver_move_q(s_other[c][0], s_other[c][1], 0u, (int)sd[1u << c]) : -128);
+        const int c = L.cidx[a];
+        qr[a] = (int8_t)(open && c >= 0 ? solver_move_q(L.other[c][0], L.other[c][1], 0u, (int)sd[1u << c]) : -128);
     }
     if (tid == 0) {
         value[r] = (int8_t)v;
@@ -158,11 +218,187 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g,
         if (mass) {
             float sum = 0.0f;
             for (int c = 0; open && c < F; c++) { // ascending action order
-                const int qq = solver_move_q(s_other[c][0], s_other[c][1], 0u, (int)sd[1u << c]);
-                if (sgn(f.margin + qq) == v) sum += pi[r * (size_t)g.A + s_act[c]];
+                const int qq = solver_move_q(L.other[c][0], L.other[c][1], 0u, (int)sd[1u << c]);
+                if (sgn(f.margin + qq) == v) sum += pi[r * (size_t)g.A + L.act[c]];
             }
             mass[r] = sum;
         }
+    }
+}
+
+// The solver as a (p, v) evaluator, every row solved from scratch (the counterpart of k_solver_eval without a table): one
+// workgroup per row, k_endgame_score's setup and solve, then wave 0 picks with lane j = compact edge j.  p [n][A]: one-hot on the
+// pick; v = sign(margin + D[0]).  A finished game: p = 0, v = get_result.  F > max_free: p = 0, v = 0, solved = 0.
+__global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_policy(EndgameGeo g, const int16_t *__restrict__ x, uint64_t pick_seed,
+                                                                    float *__restrict__ P, float *__restrict__ V,
+                                                                    uint8_t *__restrict__ solved)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [2^max_free]
+    __shared__ EndgameLds L;
+    __shared__ int s_pick;
+
+    const int tid = threadIdx.x;
+    const size_t r = blockIdx.x;
+    const int16_t *xr = x + r * 3 * (size_t)g.HW;
+    float *pr = P + r * (size_t)g.A;
+
+    const int F = endgame_setup(g, RowEdges{xr}, L);
+    if (F > g.max_free) {
+        for (int a = tid; a < g.A; a += ENDGAME_THREADS) pr[a] = 0.0f;
+        if (tid == 0) {
+            V[r] = 0.0f;
+            solved[r] = 0;
+        }
+        return;
+    }
+    endgame_solve(g, F, L, sd);
+
+    const RowFacts f = solver_facts(g.rows * g.cols, L.closed, (int)xr[2 * g.HW]);
+    const bool open = f.res == DBAZ_RESULT_NONE;
+    if (tid < 64) {
+        const bool cand = open && tid < F;
+        const int qq = cand ? solver_move_q(L.other[tid][0], L.other[tid][1], 0u, (int)sd[1u << tid]) : 0;
+        const int pick = endgame_pick(cand, qq, cand ? (int)L.act[tid] : 0, pick_seed);
+        if (tid == 0) s_pick = pick;
+    }
+    __syncthreads();
+    const int pick = s_pick;
+    for (int a = tid; a < g.A; a += ENDGAME_THREADS) pr[a] = a == pick ? 1.0f : 0.0f;
+    if (tid == 0) {
+        V[r] = (float)(open ? sgn(f.margin + (int)sd[0]) : f.res);
+        solved[r] = 1;
+    }
+}
+
+// One game's table for the search (endgame.h): one workgroup per slot that needs a table.  The grid is at most
+// ENDGAME_TABLE_GRID workgroups, each looking at the slots blockIdx.x, + gridDim.x, ...: a slot without a request costs one word
+// read (a workgroup holds 64 KB of LDS, so one workgroup per idle slot would go through the chip in many rounds).  A request whose position the slot's table still serves -- same game, free edges a subset of
+// the table's -- keeps the table; one with F > max_free drops it; any other is solved, k_endgame_score's setup and solve, and goes
+// from LDS to the slot's region in 16-byte stores together with the header.
+__global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_table(EndgameGeo g, EndgameReq *__restrict__ req, EndgameSlotHdr *__restrict__ hdr,
+                                                                   int8_t *__restrict__ tables, size_t stride, int n_slots,
+                                                                   unsigned long long *__restrict__ stats)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [max(16, 2^max_free)]
+    __shared__ EndgameLds L;
+
+    const int tid = threadIdx.x;
+    for (size_t slot = blockIdx.x; slot < (size_t)n_slots; slot += gridDim.x) {
+    EndgameReq *rq = req + slot;
+    EndgameSlotHdr *h = hdr + slot;
+    if (!*(volatile const int32_t *)&rq->want) continue; // the same answer in every thread: nobody has written yet
+    MaskEdges me;
+    bool subset = true;
+    int F = 0;
+    for (int w = 0; w < 4; w++) {
+        me.free_edges[w] = rq->free_edges[w];
+        subset = subset && (me.free_edges[w] & ~h->free_edges[w]) == 0ull;
+        F += __popcll(me.free_edges[w]);
+    }
+    const int64_t game = rq->game;
+    const int model = rq->model;
+    const bool keep = h->valid != 0 && h->game == game && subset;
+    __syncthreads(); // every thread has read the request and the header
+    if (tid == 0) {
+        rq->want = 0;
+        h->model = model;
+        if (!keep && F > g.max_free) h->valid = 0;
+    }
+    if (keep || F > g.max_free) continue;
+
+    endgame_setup(g, me, L);
+    endgame_solve(g, F, L, sd);
+
+    const int n16 = max(1, (1 << F) >> 4);
+    uint4 *dst = reinterpret_cast<uint4 *>(tables + slot * stride);
+    const uint4 *src = reinterpret_cast<const uint4 *>(sd);
+    for (int i = tid; i < n16; i += ENDGAME_THREADS) dst[i] = src[i];
+    if (tid < F) {
+        h->other[tid][0] = L.other[tid][0];
+        h->other[tid][1] = L.other[tid][1];
+        h->act[tid] = L.act[tid];
+    }
+    if (tid == 0) {
+        for (int w = 0; w < 4; w++) h->free_edges[w] = me.free_edges[w];
+        h->game = game;
+        h->F0 = F;
+        h->valid = 1;
+        atomicAdd(stats, 1ull);
+    }
+    __syncthreads(); // the next slot of this workgroup reuses L and sd
+    }
+}
+
+// requests for k_endgame_table from feature rows (dbaz_exact_policy_from): one thread per root row
+__global__ void k_endgame_requests(EndgameGeo g, const int16_t *__restrict__ x, int n, EndgameReq *__restrict__ req)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int16_t *xr = x + (size_t)r * 3 * g.HW;
+    EndgameReq rq;
+    for (int w = 0; w < 4; w++) rq.free_edges[w] = 0ull;
+    for (int i = 0; i < g.E; i++) {
+        const int a = (int)g.action[i];
+        if (xr[a] == 0) rq.free_edges[a >> 6] |= 1ull << (a & 63);
+    }
+    rq.game = r;
+    rq.want = 1;
+    rq.model = 0;
+    req[r] = rq;
+}
+
+// A slot's table as a (p, v) evaluator with k_solver_eval's contract: rows x[list[j]], j < min(*n_dev, max_n), of slot
+// list[j] / per_slot; T = float (TreeBufs.feat planes) or int16.  One wavefront per row, lane j = compact edge j of the slot's
+// table: the drawn ones ballot into the subgame mask, every free lane reads T[mask | 1 << j], endgame_pick names the move;
+// v = sign(margin + T[mask]).  A finished position gets p = 0 and v = get_result; a row of a slot without a valid table p = 0, v = 0.
+#define ENDGAME_EVAL_WAVES 4
+template <typename T>
+__global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(EndgameGeo g, const EndgameSlotHdr *__restrict__ hdr,
+                                                                          const int8_t *__restrict__ tables, size_t tab_stride,
+                                                                          const T *__restrict__ x, const int32_t *__restrict__ list,
+                                                                          const int32_t *__restrict__ n_dev, int max_n, int per_slot,
+                                                                          uint64_t seed0, uint64_t seed1, float *__restrict__ P,
+                                                                          float *__restrict__ V, int stride, unsigned long long *__restrict__ stats)
+{
+    const int lane = threadIdx.x & 63;
+    const int n = n_dev ? min(*n_dev, max_n) : max_n;
+    if (stats && blockIdx.x == 0 && threadIdx.x == 0 && n > 0) atomicAdd(stats + 1, (unsigned long long)n);
+    const int W = g.cols + 1, B = g.rows * g.cols;
+    for (int j = blockIdx.x * ENDGAME_EVAL_WAVES + (threadIdx.x >> 6); j < n; j += gridDim.x * ENDGAME_EVAL_WAVES) {
+        const int r = list ? list[j] : j;
+        if ((unsigned)r >= (unsigned)max_n) continue; // never outside the caller's buffers
+        const size_t slot = (size_t)(r / per_slot);
+        const EndgameSlotHdr *h = hdr + slot;
+        const int F0 = min(h->F0, g.max_free);
+        const T *xr = x + (size_t)r * 3 * g.HW;
+        float *pr = P + (size_t)r * stride;
+        if (!h->valid) { // no table (the engine never lists such a leaf; dbaz_exact_policy_from: a root with F > max_free)
+            for (int i = lane; i < stride; i += 64) pr[i] = 0.0f;
+            if (lane == 0) V[r] = 0.0f;
+            continue;
+        }
+        const bool edge = lane < F0;
+        const int a = edge ? (int)h->act[lane] : 0;
+        const bool drawn = edge && xr[a] != (T)0;
+        const uint32_t m = (uint32_t)__ballot(drawn);
+        int closed = 0;
+        for (int b0 = 0; b0 < B; b0 += 64) {
+            const int b = b0 + lane;
+            bool c = false;
+            if (b < B) {
+                const int at = (b / g.cols) * W + b % g.cols;
+                c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[g.HW + at] != (T)0 && xr[g.HW + at + 1] != (T)0;
+            }
+            closed += __popcll(__ballot(c));
+        }
+        const RowFacts f = solver_facts(B, closed, (int)xr[2 * g.HW]);
+        const bool open = f.res == DBAZ_RESULT_NONE;
+        const int8_t *Tb = tables + slot * tab_stride;
+        const bool cand = open && edge && !drawn;
+        const int q = cand ? solver_move_q(h->other[lane][0], h->other[lane][1], m, (int)Tb[m | (1u << lane)]) : 0;
+        const int pick = endgame_pick(cand, q, a, h->model ? seed1 : seed0);
+        for (int i = lane; i < stride; i += 64) pr[i] = i == pick ? 1.0f : 0.0f;
+        if (lane == 0) V[r] = (float)(open ? sgn(f.margin + (int)Tb[m]) : f.res);
     }
 }
 
@@ -238,6 +474,10 @@ extern "C" int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, i
     }
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_endgame_score, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_endgame_policy, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_endgame_table, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
     if (e != hipSuccess) {
         const std::string msg = hipGetErrorString(e);
         (void)hipGetLastError();
@@ -265,5 +505,100 @@ extern "C" int dbaz_endgame_score(dbaz_endgame *g, int32_t n, const int16_t *x_d
     k_endgame_score<<<(unsigned)n, ENDGAME_THREADS, (size_t)1 << g->g.max_free, (hipStream_t)stream>>>(g->g, x_dev, pi_dev, value_dev, diff_dev, q_dev,
                                                                                                       pi_dev ? mass_dev : nullptr, n_free_dev);
     ENDGAME_HIP(g, hipGetLastError());
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_exact_policy(dbaz_endgame *g, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev,
+                                 uint8_t *solved_dev, void *stream)
+{
+    if (!g) return DBAZ_EINVAL;
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !solved_dev))) return gerr(g, DBAZ_EINVAL, "dbaz_exact_policy: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    k_endgame_policy<<<(unsigned)n, ENDGAME_THREADS, (size_t)1 << g->g.max_free, (hipStream_t)stream>>>(g->g, x_dev, pick_seed, p_dev, v_dev,
+                                                                                                       solved_dev);
+    ENDGAME_HIP(g, hipGetLastError());
+    return DBAZ_OK;
+}
+
+// ---- the engine's side (endgame.h): one game's table behind the evaluator boundary
+bool endgame_serves(const dbaz_endgame *g, int rows, int cols, int device, int *max_free)
+{
+    *max_free = g->g.max_free;
+    return g->g.rows == rows && g->g.cols == cols && g->dev == device;
+}
+
+size_t endgame_table_stride(const dbaz_endgame *g) { return std::max<size_t>(16, (size_t)1 << g->g.max_free); }
+
+void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
+                    unsigned long long *stats)
+{
+    const size_t stride = endgame_table_stride(g);
+    k_endgame_table<<<(unsigned)std::min(n_slots, ENDGAME_TABLE_GRID), ENDGAME_THREADS, stride, stream>>>(g->g, req, hdr, tables, stride, n_slots,
+                                                                                                    stats);
+}
+
+void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
+                     const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
+                     int AS, unsigned long long *stats)
+{
+    const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
+    k_endgame_eval<float><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(g->g, hdr, tables, endgame_table_stride(g), feat, list_dev, n_dev, max_n,
+                                                                        per_slot, seed0, seed1, P, V, AS, stats);
+}
+
+// The table path on its own: the yardstick of k_endgame_table / k_endgame_eval against dbaz_exact_policy, the int16 form of the
+// evaluator, and the place where the two kernels are timed.
+extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const int16_t *roots_dev, int32_t per_root, const int16_t *x_dev,
+                                      uint64_t pick_seed, float *p_dev, float *v_dev, float *ms_out, void *stream)
+{
+    if (!g) return DBAZ_EINVAL;
+    if (n_roots < 0 || per_root < 1 || (long long)n_roots * per_root > 0x7fffffffll || (n_roots > 0 && (!roots_dev || !x_dev || !p_dev || !v_dev)))
+        return gerr(g, DBAZ_EINVAL, "dbaz_exact_policy_from: bad argument (n_roots = %d, per_root = %d)", n_roots, per_root);
+    if (ms_out) ms_out[0] = ms_out[1] = 0.0f;
+    if (n_roots == 0) return DBAZ_OK;
+    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t stride = endgame_table_stride(g), n = (size_t)n_roots;
+    void *buf[4] = {nullptr, nullptr, nullptr, nullptr}; // tables, headers, requests, stats
+    const size_t bytes[4] = {n * stride, n * sizeof(EndgameSlotHdr), n * sizeof(EndgameReq), 16};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; i++) {
+        e = hipMalloc(&buf[i], bytes[i]);
+        if (e != hipSuccess) buf[i] = nullptr;
+        else if (i) e = hipMemsetAsync(buf[i], 0, bytes[i], s);
+    }
+    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    if (e == hipSuccess) {
+        k_endgame_requests<<<(unsigned)((n_roots + 255) / 256), 256, 0, s>>>(g->g, roots_dev, n_roots, (EndgameReq *)buf[2]);
+        e = hipEventRecord(ev[0], s);
+    }
+    if (e == hipSuccess) {
+        endgame_tables(g, s, (EndgameReq *)buf[2], (EndgameSlotHdr *)buf[1], (int8_t *)buf[0], n_roots, (unsigned long long *)buf[3]);
+        e = hipEventRecord(ev[1], s);
+    }
+    if (e == hipSuccess) {
+        const int max_n = n_roots * per_root;
+        const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
+        k_endgame_eval<int16_t><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, s>>>(g->g, (const EndgameSlotHdr *)buf[1], (const int8_t *)buf[0], stride, x_dev,
+                                                                         nullptr, nullptr, max_n, per_root, pick_seed, pick_seed, p_dev, v_dev,
+                                                                         g->g.A, nullptr);
+        e = hipEventRecord(ev[2], s);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventSynchronize(ev[2]); // the scratch buffers go away below
+    if (e == hipSuccess && ms_out) {
+        e = hipEventElapsedTime(&ms_out[0], ev[0], ev[1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms_out[1], ev[1], ev[2]);
+    }
+    for (hipEvent_t v : ev)
+        if (v) (void)hipEventDestroy(v);
+    for (void *b : buf)
+        if (b) (void)hipFree(b);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return gerr(g, DBAZ_EDEVICE, "dbaz_exact_policy_from (%d roots x %zu bytes): %s", n_roots, stride, hipGetErrorString(e));
+    }
     return DBAZ_OK;
 }

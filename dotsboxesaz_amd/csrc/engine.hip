@@ -17,6 +17,7 @@
 #include "nn.h"
 #include "replay.h"
 #include "rules.h"
+#include "endgame.h"
 #include "solver.h"
 #include "tree.h"
 
@@ -39,7 +40,16 @@ struct dbaz_engine {
     // DBAZ_EVAL_SOLVER: the borrowed table of each model (dbaz_attach_solver), its pick seed and read ceiling
     const dbaz_solver *solver[2] = {nullptr, nullptr};
     uint64_t solver_seed[2] = {0, 0};
-    ReadCaps read_caps = {{0, 0}};
+    ReadCaps read_caps = {{0, 0}, {0, 0}};
+    EndgameStart eg_start = {nullptr, {0, 0}};
+    size_t eg_stride = 0; // bytes per slot of eg_tables as allocated: every attached handle must have this stride
+    EndgameBufs G = {nullptr, nullptr, nullptr, {0, 0}};
+    // dbaz_attach_endgame: the borrowed endgame solver of each model, its pick seed; one table region and header per slot
+    const dbaz_endgame *endgame[2] = {nullptr, nullptr};
+    uint64_t endgame_seed[2] = {0, 0};
+    int8_t *eg_tables = nullptr;
+    EndgameSlotHdr *eg_hdr = nullptr;
+    unsigned long long *eg_stats = nullptr; // [2] tables solved, leaves served
     // staging (device) for the boundary
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -96,6 +106,8 @@ static int set_error(dbaz_engine *e, int code, const char *fmt, ...)
     do {                                                                                \
         if (e) HIP_CHECK_RET(e, hipSetDevice((e)->cfg.device));                         \
     } while (0)
+
+static int endgame_drop_tables(dbaz_engine *e);
 
 extern "C" const char *dbaz_last_error(const dbaz_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 extern "C" int dbaz_version(void) { return DBAZ_ABI_VERSION; }
@@ -602,6 +614,7 @@ extern "C" int dbaz_set_positions(dbaz_engine *e, const int16_t *moves, const in
         HIP_CHECK_RET(e, hipMemcpyAsync(po, offsets, (size_t)(e->n_slots + 1) * 4, hipMemcpyHostToDevice, e->stream));
         d_m = pm; d_o = po;
     }
+    if (int r = endgame_drop_tables(e)) return r;
     tree_launch_set_positions(e->stream, e->g, e->sc, e->B, e->n_slots, d_m, d_o);
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
@@ -618,6 +631,34 @@ static hipEvent_t next_event(dbaz_engine *e)
     return e->ev_pool[e->ev_used++];
 }
 
+// ---- one game's endgame table per slot (endgame.h, dbaz_attach_endgame) ----
+// k_endgame_table for every slot, on the stream that has just started searches (begin_search's requests): a slot without a request
+// is one workgroup that returns at once
+static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
+{
+    const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
+    if (g) endgame_tables(g, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats);
+}
+
+// the leaves k_select / k_select_multi put on eg_list, where solver_forward serves its lists
+static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
+{
+    const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
+    if (g)
+        endgame_forward(g, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3, e->n_slots * per_slot, per_slot, e->endgame_seed[0],
+                        e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
+}
+
+// new positions or a new run: no table of an earlier game may serve them
+static int endgame_drop_tables(dbaz_engine *e)
+{
+    if (e->eg_hdr) {
+        HIP_CHECK_RET(e, hipMemsetAsync(e->eg_hdr, 0, sizeof(EndgameSlotHdr) * (size_t)e->n_slots, e->stream));
+        HIP_CHECK_RET(e, hipMemsetAsync(e->eg_start.req, 0, sizeof(EndgameReq) * (size_t)e->n_slots, e->stream));
+    }
+    return DBAZ_OK;
+}
+
 // one WAVE of up to K simulations for every searching tree (max_pending_evals = K > 1): K sequential selections with
 // virtual loss per tree, one batched evaluation of all their leaves, expand + backup in selection order
 // with_driver (self-play with dbaz_config.selfplay_pending: every search of a game runs in these waves, the reference's
@@ -631,8 +672,11 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     e->sc.step = (int)(e->steps & 0x3FFFFFFF) + 1;
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
-    if (with_driver) tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, e->read_caps);
-    tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots);
+    if (with_driver) {
+        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+        endgame_solve_tables(e, s);
+    }
+    tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
     if (use_nn) {
         nn_forward(e->nns[0], s, e->B.feat_m, e->B.list_m, e->B.n_eval, e->n_slots * e->B.kmax, e->B.evalP_m, e->B.evalV_m, e->g.AS, nullptr, nullptr);
         e->nn_launches++;
@@ -640,7 +684,8 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     if (e->sc.evaluator == DBAZ_EVAL_SOLVER)
         solver_forward(e->solver[0], s, e->B.feat_m, e->B.list_m, e->B.n_eval, e->n_slots * e->B.kmax, e->solver_seed[0], e->B.evalP_m,
                        e->B.evalV_m, e->g.AS);
-    tree_launch_expand_backup_multi(s, e->g, e->sc, e->B, e->n_slots);
+    endgame_eval_leaves(e, s, e->B.feat_m, e->B.kmax, e->B.evalP_m, e->B.evalV_m);
+    tree_launch_expand_backup_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     return DBAZ_OK;
@@ -665,7 +710,9 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
         HIP_CHECK_RET(e, hipEventRecord(e->ev_fork, s));
         HIP_CHECK_RET(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, e->read_caps);
+        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+        // the searches this pass starts do not select in this step; the join below orders their tables before the next k_select
+        endgame_solve_tables(e, e->stream2);
         HIP_CHECK_RET(e, hipEventRecord(e->ev_join, e->stream2));
     }
     // full rounds only (tree.hip, above k_select): self-play stepping, one network, one leaf per slot
@@ -674,7 +721,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         e->sc.eval_round = e->eval_round;
         e->sc.eval_defer_max = e->eval_defer_max;
     }
-    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots); // (the lists' counters were zeroed by the previous k_expand_backup)
+    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots, e->G); // (the lists' counters were zeroed by the previous k_expand_backup)
     if (e->sc.eval_round > 0) tree_launch_order_evals(s, e->B, e->n_slots, e->sc.step); // the list in slot order (deterministic cut)
     const bool late_join = with_driver && e->late_join;
     if (with_driver && !late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
@@ -695,11 +742,12 @@ static int sim_step(dbaz_engine *e, bool with_driver)
     if (e->sc.match_play && e->sc.evaluator2 == DBAZ_EVAL_SOLVER)
         solver_forward(e->solver[1], s, e->B.feat, e->B.eval_list2, e->B.n_eval + 1, e->n_slots, e->solver_seed[1], e->B.evalP, e->B.evalV,
                        e->g.AS);
+    endgame_eval_leaves(e, s, e->B.feat, 1, e->B.evalP, e->B.evalV);
     // the driver pass may run on under the network: nothing there reads what it writes (leaf lists and features come from
     // k_select, which skipped the slots the pass starts); k_expand_backup does (it clears the pass's slot list).
     // 3x3: 11.9 -> 13.2 M expansions/s, 6x6: +1.5 %, 9x9: +2.8 % against joining in front of the network
     if (late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
-    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots);
+    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots, e->G);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     return DBAZ_OK;
@@ -749,7 +797,8 @@ extern "C" int dbaz_search_begin(dbaz_engine *e, const int32_t *num_reads, const
     int r = upload_search_inputs(e, num_reads, noise, &d_reads);
     if (r) return r;
     e->sc.step = 0;
-    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads, e->read_caps);
+    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads, StartArgs{e->read_caps, e->eg_start});
+    endgame_solve_tables(e, e->stream); // every slot is looked at again: the positions may have changed
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
     int mx = e->sc.mcts_num_read;
@@ -799,6 +848,80 @@ extern "C" int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s,
     e->solver_seed[model] = pick_seed;
     e->read_caps.cap[model] = solver_reads;
     return DBAZ_OK;
+}
+
+extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!g) return set_error(e, DBAZ_EINVAL, "null endgame solver");
+    if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
+    const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
+    if (ev == DBAZ_EVAL_EXTERNAL || ev == DBAZ_EVAL_SOLVER || (model == 1 && !e->sc.match_play))
+        return set_error(e, DBAZ_EINVAL, "model %d: an endgame solver attaches to a network or formula evaluator the engine runs itself", model);
+    if (endgame_reads < 0) return set_error(e, DBAZ_EINVAL, "endgame_reads must be >= 0");
+    int max_free = 0;
+    if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
+                         e->g.cols, e->cfg.device);
+    // the slot regions are sized by the first attach and never resized: any later handle, for either model, must fit them exactly
+    if (e->eg_tables && endgame_table_stride(g) != e->eg_stride)
+        return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold %zu bytes each (the max_free of its first dbaz_attach_endgame); "
+                         "every later attach, for either model, needs the same max_free", max_free, e->eg_stride);
+    if (e->eg_tables) {
+        // a re-attach: tables solved under the handle it replaces do not serve on (headers and requests are dropped); a search
+        // that is running goes on with its model's evaluator until its next root
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = endgame_drop_tables(e)) return r;
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    }
+    if (!e->eg_tables) {
+        // the slot tables: n_slots x 2^max_free bytes, plus headers, requests and the leaf list; nothing is kept when one fails
+        const size_t ns = e->n_slots, stride = endgame_table_stride(g);
+        void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const size_t bytes[6] = {ns * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4,
+                                 ns * (size_t)e->B.kmax * 4, 16};
+        hipError_t err = hipStreamSynchronize(e->stream);
+        for (int i = 0; i < 6 && err == hipSuccess; i++) {
+            err = hipMalloc(&p[i], bytes[i]);
+            if (err != hipSuccess) p[i] = nullptr;
+            else if (i) err = hipMemset(p[i], 0, bytes[i]);
+        }
+        if (err != hipSuccess) {
+            for (void *q : p) if (q) (void)hipFree(q);
+            (void)hipGetLastError();
+            return set_error(e, DBAZ_EDEVICE, "endgame tables of %zu slots x %zu bytes: %s", ns, stride, hipGetErrorString(err));
+        }
+        for (void *q : p) e->allocs.push_back(q);
+        e->eg_tables = (int8_t *)p[0];
+        e->eg_hdr = (EndgameSlotHdr *)p[1];
+        e->G.hdr = e->eg_hdr;
+        e->eg_start.req = (EndgameReq *)p[2];
+        e->eg_stride = stride;
+        e->G.list = (int32_t *)p[3];
+        e->G.leaf = (int32_t *)p[4];
+        e->eg_stats = (unsigned long long *)p[5];
+    }
+    e->endgame[model] = g;
+    e->endgame_seed[model] = pick_seed;
+    e->G.model[model] = 1;
+    e->read_caps.eg_cap[model] = endgame_reads;
+    e->eg_start.max_free[model] = max_free;
+    return DBAZ_OK;
+}
+
+extern "C" void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_solved, int64_t *leaves_served)
+{
+    unsigned long long st[2] = {0, 0};
+    if (e && e->eg_stats) {
+        (void)hipSetDevice(e->cfg.device);
+        (void)hipStreamSynchronize(e->stream);
+        if (e->stream2) (void)hipStreamSynchronize(e->stream2);
+        (void)hipMemcpy(st, e->eg_stats, sizeof st, hipMemcpyDeviceToHost);
+    }
+    if (tables_solved) *tables_solved = (int64_t)st[0];
+    if (leaves_served) *leaves_served = (int64_t)st[1];
 }
 
 extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const double *noise, double time_limit_s)
@@ -1142,7 +1265,9 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
         e->ff_plies.clear();
     }
     e->sc.step = 0; // searches started here carry stamp 0, which no step ever has
-    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots, e->read_caps);
+    if (int r = endgame_drop_tables(e)) return r;
+    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+    endgame_solve_tables(e, s);
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(s));
     e->selfplay = true;

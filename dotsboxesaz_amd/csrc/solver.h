@@ -52,6 +52,18 @@ __host__ __device__ __forceinline__ RowFacts solver_facts(int n_boxes, int close
     return f;
 }
 
+// splitmix64 finaliser of key ^ seed * golden ratio: which of a position's optimal moves a seeded evaluator picks (key: the
+// solver's mask of the position; the endgame solver's XOR of 1 << (a & 63) over the free edges a).  Shared by solver.hip and
+// endgame.hip.
+__host__ __device__ __forceinline__ uint64_t solver_pick_mix(uint64_t key, uint64_t seed)
+{
+    uint64_t x = key ^ (seed * 0x9E3779B97F4A7C15ull);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
 // masks of `bits` bits in ascending popcount order; off[k] .. off[k + 1] holds popcount k
 static inline void popcount_order(int bits, std::vector<uint32_t> &perm, std::vector<uint32_t> &off)
 {

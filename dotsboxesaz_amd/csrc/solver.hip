@@ -172,16 +172,6 @@ __global__ void __launch_bounds__(256) k_solver_score(SolverGeo g, const int8_t 
     if (mass) mass[r] = sum;
 }
 
-// splitmix64 finaliser of mask ^ seed * golden ratio: which of a position's optimal moves a seeded evaluator picks
-__device__ __forceinline__ uint64_t solver_pick_mix(uint32_t mask, uint64_t seed)
-{
-    uint64_t x = (uint64_t)mask ^ (seed * 0x9E3779B97F4A7C15ull);
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
 // The table as a (p, v) evaluator with nn_forward's contract (nn.h): rows x[list[j]], j < min(*n_dev, max_n) (list == nullptr:
 // identity, n_dev == nullptr: max_n rows), T = int16 (dataset rows) or float (TreeBufs.feat planes); a one-hot policy row goes to
 // P[list[j] * stride ..+stride) and v = sign(margin + D[mask]) to V[list[j]].  One wavefront per row, lane i = compact edge i:

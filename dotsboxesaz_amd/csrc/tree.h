@@ -2,29 +2,66 @@
 #pragma once
 #include "common.h"
 
+struct EndgameReq;     // endgame.h
+struct EndgameSlotHdr; // endgame.h
+
 // Evaluators that answer through the evaluation list: k_select / k_select_multi append their leaves to eval_list / eval_list2 /
 // list_m, a launch between select and expand fills evalP / evalV, and expand reads (p, v) from there -- the networks and the
 // solved table (DBAZ_EVAL_SOLVER, solver.hip).  eval_is_nn stays the narrower "a network": transposition cache, full rounds.
 __host__ __device__ inline bool eval_uses_list(int ev) { return eval_is_nn(ev) || ev == DBAZ_EVAL_SOLVER; }
 
-// dbaz_attach_solver's solver_reads per model: > 0 = ceiling on the driver rule's read budget of a search that model serves
+// A leaf's (p, v): computed at expansion by the formula of its evaluator, or read from evalP / evalV, where a launch between
+// select and expand or the host put them.  from_table: the leaf is answered from its slot's endgame table (EndgameBufs below),
+// whatever the evaluator.
+__host__ __device__ inline bool leaf_reads_eval_buffers(int ev, bool from_table) { return from_table || !eval_is_formula(ev); }
+// the transposition probe and insert apply to leaves that the engine's own evaluator of the model answers
+__host__ __device__ inline bool leaf_uses_transpositions(int ev, bool from_table) { return !from_table && ev != DBAZ_EVAL_EXTERNAL; }
+
+// Read ceilings of the driver rule per model (> 0: a search under the rule runs min(rule, cap) reads; 0: the rule):
+//   cap     dbaz_attach_solver's solver_reads, for a search that model's solved table serves
+//   eg_cap  dbaz_attach_endgame's endgame_reads, for a search whose root has at most EndgameStart::max_free free edges
 struct ReadCaps {
     int32_t cap[2];
+    int32_t eg_cap[2];
+};
+
+// What begin_search needs of the endgame tables (endgame.h; all zero until dbaz_attach_endgame): where it leaves the request for
+// the slot's table when a search starts, and each model's max_free (0: no endgame solver attached to that model).
+struct EndgameStart {
+    EndgameReq *req; // [n_slots]
+    int32_t max_free[2];
+};
+
+// the arguments of the kernels that start searches (k_search_begin, k_selfplay_start, k_advance_auto), next to the configuration
+struct StartArgs {
+    ReadCaps caps;
+    EndgameStart eg;
+};
+
+// One game's endgame table per slot as an evaluator inside the search (endgame.h; all zero until dbaz_attach_endgame): a leaf of a
+// slot whose searching model has one attached and whose table serves the slot's game goes on `list` -- not on eval_list /
+// eval_list2 / list_m -- and expand reads its (p, v) from evalP / evalV whatever the evaluator.  The list's length is n_eval[3].
+struct EndgameBufs {
+    const EndgameSlotHdr *hdr; // [n_slots]
+    int32_t *list;             // [n_slots * kmax] slots, or slot * kmax + k in a wave
+    int32_t *leaf;             // [n_slots * kmax] 1 = the leaf (of simulation k) is answered from the table
+    int32_t model[2];          // 1 = the model has an endgame solver attached
 };
 
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
-                              const int32_t *num_reads_dev, ReadCaps rc);
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots);
+                              const int32_t *num_reads_dev, StartArgs sa);
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step);
-void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots);
-void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots);
-void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots);
+void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
+void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
+                                     const EndgameBufs &G = EndgameBufs());
+void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                const int16_t *moves_dev, const int32_t *offsets_dev);
 void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                 const int32_t *moves_dev, int reuse);
-void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc);
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc);
+void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa);
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa);
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,
                            uint64_t *edges, int16_t *b2c2, int8_t *to_play, int8_t *just_played, int8_t *result,

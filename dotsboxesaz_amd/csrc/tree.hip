@@ -12,6 +12,7 @@
 // Numerics follow numpy (NEP 50) exactly: UCB in float64, statistics in float32/int32,
 // float32 prior sums with numpy's pairwise summation.  This TU is compiled with
 // -ffp-contract=off: a fused multiply-add would change the roundings.
+#include "endgame.h"
 #include "rules.h"
 #include "tree.h"
 
@@ -450,7 +451,7 @@ __device__ __forceinline__ int rule_num_reads(const Geo &g, const SearchCfg &cfg
 
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
 __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                             uint32_t *pool, int num_reads, const ReadCaps &rc, float *ldsf, double *ldsd, int lane)
+                             uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
     if (rm.flags & NF_TERMINAL) { // play_game never searches a terminal root
@@ -463,7 +464,9 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
         // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads); the model of a
         // move's search is chosen as select_one chooses it
         const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
-        if ((model ? cfg.evaluator2 : cfg.evaluator) == DBAZ_EVAL_SOLVER && rc.cap[model] > 0) num_reads = min(num_reads, rc.cap[model]);
+        if ((model ? cfg.evaluator2 : cfg.evaluator) == DBAZ_EVAL_SOLVER && sa.caps.cap[model] > 0) num_reads = min(num_reads, sa.caps.cap[model]);
+        // the same for a search whose leaves the slot's endgame table will answer (dbaz_attach_endgame's endgame_reads)
+        if (sa.caps.eg_cap[model] > 0 && gs_count_valid(g, rm.st) <= sa.eg.max_free[model]) num_reads = min(num_reads, sa.caps.eg_cap[model]);
         // benchmark population (dbaz_selfplay_stagger): the slot's first search is cut short so that the slots'
         // move boundaries are spread over a whole search instead of all falling into the same step
         // (dbaz_selfplay_quickplay: the opening plies of the slot's first game are searched with a small budget -- a cheap way
@@ -479,6 +482,21 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
             }
         }
     }
+    if (sa.eg.req) {
+        // a search starts: k_endgame_table (next on this stream) solves or re-checks the slot's table before the first selection
+        const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
+        if (sa.eg.max_free[model] > 0 && lane == 0) {
+            EndgameReq rq;
+            rq.free_edges[0] = ~(rm.st.e0 | g.sentinel[0]) & g.amask[0];
+            rq.free_edges[1] = ~(rm.st.e1 | g.sentinel[1]) & g.amask[1];
+            rq.free_edges[2] = ~(rm.st.e2 | g.sentinel[2]) & g.amask[2];
+            rq.free_edges[3] = ~(rm.st.e3 | g.sentinel[3]) & g.amask[3];
+            rq.game = S->game_idx;
+            rq.want = 1;
+            rq.model = model;
+            sa.eg.req[slot] = rq;
+        }
+    }
     S->sims_left = num_reads;
     S->first_wave = 1;
     S->wave_sims = 0;
@@ -490,7 +508,7 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, TreeBufs B, const int32_t *num_reads, ReadCaps rc)
+__global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, TreeBufs B, const int32_t *num_reads, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
@@ -499,7 +517,7 @@ __global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, Tre
     if (S->phase == PH_ERROR || S->game_idx < 0)
         return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    begin_search(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, rc, ldsf, ldsd, lane);
+    begin_search(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, sa, ldsf, ldsd, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -740,10 +758,11 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
 #define EV_CLASS_DEFERRED (-2) // the leaf of an earlier step whose evaluation was put off: head of the list
 #define EV_CLASS_NEW (-3)      // a leaf selected in this step
 #define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
+#define SEL_ENDGAME 3          // select_one: the leaf is answered from the slot's endgame table (eg_list)
 
-// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, or -1
+// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, SEL_ENDGAME, or -1
 template <int NPL>
-__device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, int lane)
+__device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
     Slot *S = B.slots + slot;
     const unsigned long long pw = *reinterpret_cast<volatile const unsigned long long *>(&S->phase); // phase | stamp << 32
@@ -788,14 +807,19 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         if (q.n_nodes > S->pool_high) S->pool_high = q.n_nodes;
     }
     int need_eval = -1;
+    // a leaf under a valid table of this game is answered from it, whatever the evaluator: not on the evaluation lists (so never
+    // counted in or deferred by the full-rounds cut), no transposition probe
+    const bool eg = !(m.flags & NF_TERMINAL) && G.hdr && G.model[model] && endgame_hdr_serves(G.hdr[slot], S->game_idx);
+    if (G.hdr && lane == 0) G.leaf[slot] = eg ? 1 : 0;
     if (!(m.flags & NF_TERMINAL)) {
         write_features(g, m.st, B.feat + (size_t)slot * 3 * g.HW, lane);
         const int ev = model ? cfg.evaluator2 : cfg.evaluator;
-        if (eval_uses_list(ev)) need_eval = model;
+        if (eg) need_eval = SEL_ENDGAME;
+        else if (eval_uses_list(ev)) need_eval = model;
         int hit = -1;
         // (the table exists for network evaluators, and for the formula evaluators when forced on -- transposition_cache
         // = 2 -- so that the hit path can be compared with the oracle bit for bit)
-        if (B.tt && ev != DBAZ_EVAL_EXTERNAL) {
+        if (B.tt && leaf_uses_transpositions(ev, eg)) {
             // lanes 0..TT_PROBES-1 read the probe window; a candidate is verified against the live tree
             const uint64_t h = formula_hash(m.st);
             const unsigned long long *tt = B.tt + (size_t)slot * ((size_t)B.tt_mask + 1);
@@ -831,29 +855,31 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 // the workgroup come from an LDS counter): a per-wave atomicAdd on the single list counter serialises
 // 8192 same-address atomics per step and was most of this kernel's duration.
 template <int NPL>
-__global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots)
+__global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
-    __shared__ int s_cnt[2], s_base[2];
+    __shared__ int s_cnt[3], s_base[3]; // the two models' lists and eg_list
     const int slot = blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (WAVE - 1);
-    if (cfg.eval_round > 0) { // k_order_evals writes the list
-        if (slot < n_slots) {
-            const int model = select_one<NPL>(g, cfg, B, slot, lane);
-            if (lane == 0) B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
-        }
-        return;
-    }
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     int model = -1;
-    if (slot < n_slots) model = select_one<NPL>(g, cfg, B, slot, lane);
+    if (slot < n_slots) model = select_one<NPL>(g, cfg, B, G, slot, lane);
+    int cls = model == SEL_ENDGAME ? 2 : ((model == 0 || model == 1) ? model : -1);
+    if (cfg.eval_round > 0) { // k_order_evals writes the network's list
+        if (slot < n_slots && lane == 0) B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
+        if (cls != 2) cls = -1;
+    }
     int my = -1;
-    if (model >= 0 && lane == 0) my = atomicAdd(&s_cnt[model], 1);
+    if (cls >= 0 && lane == 0) my = atomicAdd(&s_cnt[cls], 1);
     __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(B.n_eval + threadIdx.x, s_cnt[threadIdx.x]);
+    if (threadIdx.x < 3 && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(B.n_eval + (threadIdx.x == 2 ? 3 : threadIdx.x), s_cnt[threadIdx.x]);
     __syncthreads();
     if (my >= 0) {
-        (model ? B.eval_list2 : B.eval_list)[s_base[model] + my] = slot;
-        B.slots[slot].eval_pos = s_base[model] + my;
+        if (cls == 2) {
+            G.list[s_base[2] + my] = slot;
+        } else {
+            (cls ? B.eval_list2 : B.eval_list)[s_base[cls] + my] = slot;
+            B.slots[slot].eval_pos = s_base[cls] + my;
+        }
     }
 }
 
@@ -912,7 +938,7 @@ __global__ void __launch_bounds__(1024) k_order_evals(TreeBufs B, int n_slots, i
 // count it has itself incremented.
 // ------------------------------------------------------------------------------------
 template <int NPL>
-__device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, int lane)
+__device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
     Slot *S = B.slots + slot;
     const int phase = S->phase;
@@ -924,6 +950,7 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
     int n_sims = phase == PH_EXPAND_ROOT ? 1 : min(width, S->sims_left);
     PoolState q = pool_load(S);
     const unsigned vv = cfg.virtual_visits ? 1u : 0u; // the visit is counted at selection (backup then adds the value only)
+    const bool eg = G.hdr && G.model[0] && endgame_hdr_serves(G.hdr[slot], S->game_idx); // the slot's leaves come from its table
     int err = 0, done = 0;
     for (int k = 0; k < n_sims && !err; k++) {
         PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
@@ -940,6 +967,7 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
             SimRec sr;
             sr.leaf = lf.cur; sr.path_len = lf.depth + 1; sr.terminal = term ? 1 : 0; sr.result = m.result; sr.to_play = m.st.to_play;
             sr.dup = dup ? 1 : 0;
+            if (G.hdr) G.leaf[(size_t)slot * K + k] = (eg && !term && !dup) ? 1 : 0;
             B.simrec[(size_t)slot * K + k] = sr;
             if (!term && !dup)
                 node_ptr(pool, g, lf.cur)[11] = pack_dw11(m.flags | NF_INFLIGHT, m.result, m.deepness);
@@ -961,29 +989,34 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
 }
 
 template <int NPL>
-__global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, TreeBufs B, int n_slots)
+__global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot >= n_slots) return;
-    select_multi_one<NPL>(g, cfg, B, slot, lane);
+    select_multi_one<NPL>(g, cfg, B, G, slot, lane);
     __syncthreads();
     // evaluation list: the wave's simulations that need the network, in simulation order
     const Slot *S = B.slots + slot;
     if (S->phase == PH_ERROR) return;
     const int K = B.kmax, n = S->wave_sims;
-    if (!eval_uses_list(cfg.evaluator) || S->sel_step != cfg.step) return;
+    const bool lists = eval_uses_list(cfg.evaluator);
+    if ((!lists && !G.hdr) || S->sel_step != cfg.step) return;
     for (int k0 = 0; k0 < n; k0 += WAVE) {
         const int k = k0 + lane;
-        bool need = false;
+        bool need = false, eg = false;
         if (k < n) {
             const SimRec sr = B.simrec[(size_t)slot * K + k];
-            need = !sr.terminal && !sr.dup;
+            eg = G.hdr && G.leaf[(size_t)slot * K + k] != 0; // never set for a terminal or duplicate leaf
+            need = lists && !sr.terminal && !sr.dup && !eg;
         }
-        const unsigned long long mk = __ballot(need);
-        int base = 0;
+        const unsigned long long mk = __ballot(need), me = __ballot(eg);
+        int base = 0, ebase = 0;
         if (lane == 0 && mk) base = atomicAdd(B.n_eval, (int)__popcll(mk));
+        if (lane == 0 && me) ebase = atomicAdd(B.n_eval + 3, (int)__popcll(me));
         base = __shfl(base, 0);
+        ebase = __shfl(ebase, 0);
         if (need) B.list_m[base + (int)__popcll(mk & ((1ull << lane) - 1ull))] = slot * K + k;
+        if (eg) G.list[ebase + (int)__popcll(me & ((1ull << lane) - 1ull))] = slot * K + k;
     }
 }
 
@@ -993,10 +1026,10 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
 // ------------------------------------------------------------------------------------
 // P row of the leaf = child_priors * valid, renormalised as the reference does; returns v.  The priors and the value come
 // from the formula of evaluator `ev`, or from ep[A] / *evv.  ldsf must be free (wave-cooperative).
-__device__ __forceinline__ float expand_priors(const Geo &g, const GState &st, int ev, const float *ep, const float *evv, float *Prow,
-                                               float *ldsf, int lane)
+__device__ __forceinline__ float expand_priors(const Geo &g, const GState &st, int ev, bool from_table, const float *ep, const float *evv,
+                                               float *Prow, float *ldsf, int lane)
 {
-    const bool formula = eval_is_formula(ev);
+    const bool formula = !leaf_reads_eval_buffers(ev, from_table);
     uint64_t h = 0;
     if (formula) h = formula_hash(st);
     for (int i = lane; i < g.A; i += WAVE) {
@@ -1032,15 +1065,16 @@ __device__ __forceinline__ void backup_path(const Geo &g, uint32_t *pool, Slot *
     }
 }
 
-// statistics of one finished simulation; served = its leaf needed no evaluation of its own (transposition hit / duplicate leaf)
-__device__ __forceinline__ void count_sim(Slot *S, int term, bool served, int path_len, int deepness)
+// statistics of one finished simulation; served = its leaf needed no evaluation of its own (transposition hit / duplicate leaf);
+// eg = answered from the slot's endgame table: neither an evaluation nor a hit
+__device__ __forceinline__ void count_sim(Slot *S, int term, bool served, bool eg, int path_len, int deepness)
 {
     S->terminal_count += term;
     if (deepness > S->max_deepness) S->max_deepness = deepness;
     S->n_search += 1;
     S->sum_path += path_len;
     S->n_term += term;
-    S->n_eval += (term || served) ? 0 : 1;
+    S->n_eval += (term || served || eg) ? 0 : 1;
     S->n_hit += served ? 1 : 0;
 }
 
@@ -1058,12 +1092,12 @@ __device__ __forceinline__ void end_step(const Geo &g, const SearchCfg &cfg, con
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg cfg, TreeBufs B)
+__global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int slot = blockIdx.x, lane = threadIdx.x;
-    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.drv_count[0] = 0; } // (drv_count: self-play in waves)
+    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; } // (drv_count: self-play in waves)
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
@@ -1072,6 +1106,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
     const int K = B.kmax, n = S->wave_sims;
     for (int k = 0; k < n; k++) {
         const SimRec sr = B.simrec[(size_t)slot * K + k];
+        const bool eg = G.hdr && !sr.terminal && !sr.dup && G.leaf[(size_t)slot * K + k] != 0;
         const PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
         NodeMeta lm = load_meta(pool, g, sr.leaf);
         uint32_t *nd = node_ptr(pool, g, sr.leaf);
@@ -1082,14 +1117,14 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
             v = __uint_as_float(nd[12]); // expanded by an earlier simulation of this wave (sr.dup): same (p, v)
         } else {
             __syncthreads(); // ldsf is reused from the simulation before
-            v = expand_priors(g, lm.st, cfg.evaluator, B.evalP_m + ((size_t)slot * K + k) * g.AS, B.evalV_m + (size_t)slot * K + k,
+            v = expand_priors(g, lm.st, cfg.evaluator, eg, B.evalP_m + ((size_t)slot * K + k) * g.AS, B.evalV_m + (size_t)slot * K + k,
                               reinterpret_cast<float *>(nd + META_DW), ldsf, lane);
             if (lane == 0) nd[12] = __float_as_uint(v);
         }
         if (lane == 0) nd[11] = pack_dw11((lm.flags | NF_EXPANDED) & ~NF_INFLIGHT, lm.result, lm.deepness);
         // N += 1 here (the reference) or already at selection (virtual_visits)
         backup_path(g, pool, S, path, sr.path_len, lm.st.to_play, v, !cfg.virtual_visits, lane);
-        if (lane == 0) count_sim(S, sr.terminal, sr.dup != 0, sr.path_len, lm.deepness);
+        if (lane == 0) count_sim(S, sr.terminal, sr.dup != 0, eg, sr.path_len, lm.deepness);
         // the next simulation's path shares nodes with this one (same wavefront: program order + a drain)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1102,14 +1137,14 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
 // ------------------------------------------------------------------------------------
 // _search tail: prior masking (mcts.py:189-196), expand (:116-119), backup (:121-132)
 // ------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B)
+__global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int slot = blockIdx.x, lane = threadIdx.x;
     // the step's last kernel resets the per-step counters for the next one (the evaluation lists were consumed by the network
     // launches before it, the driver list by the pass joined before them): no memset launches between the kernels
-    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.drv_count[0] = 0; }
+    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; }
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
@@ -1126,11 +1161,12 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
     uint32_t *nd = node_ptr(pool, g, leaf);
     float v;
     int hit = -1;
+    const bool eg = !(lm.flags & NF_TERMINAL) && G.hdr && G.leaf[slot] != 0; // (p, v) came from the slot's endgame table, whatever the evaluator
     if (!(lm.flags & NF_TERMINAL)) {
         float *Prow = reinterpret_cast<float *>(nd + META_DW);
         const int ev = (cfg.match_play && S->model) ? cfg.evaluator2 : cfg.evaluator;
         if (B.tt) hit = S->leaf_hit;
-        if (cfg.eval_round > 0 && hit < 0 && !eval_is_formula(ev)) {
+        if (cfg.eval_round > 0 && hit < 0 && !eval_is_formula(ev) && !eg) {
             // behind this step's cut: the network has not seen the leaf; keep it and ask again next step
             const bool late = S->eval_pos >= B.n_eval[2];
             if (lane == 0) S->pending = late ? 1 : 0;
@@ -1143,11 +1179,11 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
             for (int i = lane; i < A; i += WAVE) Prow[i] = Psrc[i];
             v = __uint_as_float(tw[12]);
         } else {
-            v = expand_priors(g, lm.st, ev, B.evalP + (size_t)slot * g.AS, B.evalV + slot, Prow, ldsf, lane);
+            v = expand_priors(g, lm.st, ev, eg, B.evalP + (size_t)slot * g.AS, B.evalV + slot, Prow, ldsf, lane);
         }
         if (B.tt && lane == 0) {
             nd[12] = __float_as_uint(v); // a later twin reads the value here
-            if (hit < 0) {
+            if (hit < 0 && !eg) {
                 // insert: first empty / stale-epoch / same-tag entry of the probe window, else a hash-chosen victim
                 const uint64_t h = formula_hash(lm.st);
                 unsigned long long *tt = B.tt + (size_t)slot * ((size_t)B.tt_mask + 1);
@@ -1167,7 +1203,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, Tr
         nd[11] = pack_dw11(lm.flags | NF_EXPANDED, lm.result, lm.deepness);
     backup_path(g, pool, S, path, plen, lm.st.to_play, v, true, lane);
     __syncthreads();
-    if (lane == 0) count_sim(S, (lm.flags & NF_TERMINAL) ? 1 : 0, hit >= 0, plen, lm.deepness);
+    if (lane == 0) count_sim(S, (lm.flags & NF_TERMINAL) ? 1 : 0, hit >= 0, eg, plen, lm.deepness);
     end_step(g, cfg, B, slot, S, pool, phase, 1, ldsf, ldsd, lane);
 }
 
@@ -1413,7 +1449,7 @@ __device__ bool try_emit(const Geo &g, const TreeBufs &B, int slot, Slot *S, uin
 }
 
 __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                                  uint32_t *pool, const ReadCaps &rc, float *ldsf, double *ldsd, int lane)
+                                  uint32_t *pool, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
 {
     // play_game loop head (self_play.py:57-66): temperature schedule, sims budget, search
     const int i = S->move_idx;
@@ -1429,11 +1465,11 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
         __syncthreads();
         __threadfence_block();
     }
-    begin_search(g, cfg, B, slot, S, pool, -1, rc, ldsf, ldsd, lane);
+    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane);
 }
 
 
-__global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B, ReadCaps rc)
+__global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
@@ -1455,7 +1491,7 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
         return;
     }
     fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-    start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
+    start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
 }
 
 // One pass of the driver for every slot whose reads are done (PH_READY), whose finished game still waits for output space
@@ -1463,7 +1499,7 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
 // here leaves the slot in PH_NEWGAME until the next pass.
 // (the slots come from k_driver_scan's list: a step in which no slot needs the driver costs two tiny launches instead
 // of one workgroup per game squeezing in between the network's workgroups)
-__device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const ReadCaps &rc, float *ldsf,
+__device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const StartArgs &sa, float *ldsf,
                             double *ldsd, int lane)
 {
     Slot *S = B.slots + slot;
@@ -1477,7 +1513,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
         const long long gidx = S->game_idx;
         S->quick_until = 0; // only a slot's first game has quick plies
         fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-        start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
+        start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
         return;
     }
     if (phase == PH_EMIT) {
@@ -1577,7 +1613,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             S->phase = emitted ? PH_NEWGAME : PH_EMIT;
         return;
     }
-    start_move_search(g, cfg, B, slot, S, pool, rc, ldsf, ldsd, lane);
+    start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
 }
 
 // which slots need the driver: finished reads, a blocked emit or a finished game (the pass runs after the previous step's
@@ -1628,14 +1664,14 @@ __global__ void __launch_bounds__(1024) k_driver_scan(SearchCfg cfg, TreeBufs B,
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B, ReadCaps rc)
+__global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int lane = threadIdx.x;
     const int n = *B.drv_count;
     for (int li = blockIdx.x; li < n; li += gridDim.x) {
-        advance_one(g, cfg, B, B.drv_list[li], rc, ldsf, ldsd, lane);
+        advance_one(g, cfg, B, B.drv_list[li], sa, ldsf, ldsd, lane);
         __syncthreads();
     }
 }
@@ -1817,35 +1853,35 @@ __global__ void k_rules(Geo g, int op, int n, uint64_t *edges, int16_t *b2c2, in
 // host launchers
 // ------------------------------------------------------------------------------------
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
-                              const int32_t *num_reads_dev, ReadCaps rc)
+                              const int32_t *num_reads_dev, StartArgs sa)
 {
-    hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev, rc);
+    hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev, sa);
 }
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     switch ((g.A + WAVE - 1) / WAVE) {
-    case 1: hipLaunchKernelGGL(k_select<1>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots); break;
-    case 2: hipLaunchKernelGGL(k_select<2>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots); break;
-    case 3: hipLaunchKernelGGL(k_select<3>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots); break;
-    default: hipLaunchKernelGGL(k_select<4>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots); break;
+    case 1: hipLaunchKernelGGL(k_select<1>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
+    case 2: hipLaunchKernelGGL(k_select<2>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
+    case 3: hipLaunchKernelGGL(k_select<3>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
+    default: hipLaunchKernelGGL(k_select<4>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
     }
 }
-void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     switch ((g.A + WAVE - 1) / WAVE) {
-    case 1: hipLaunchKernelGGL(k_select_multi<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots); break;
-    case 2: hipLaunchKernelGGL(k_select_multi<2>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots); break;
-    case 3: hipLaunchKernelGGL(k_select_multi<3>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots); break;
-    default: hipLaunchKernelGGL(k_select_multi<4>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots); break;
+    case 1: hipLaunchKernelGGL(k_select_multi<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+    case 2: hipLaunchKernelGGL(k_select_multi<2>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+    case 3: hipLaunchKernelGGL(k_select_multi<3>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+    default: hipLaunchKernelGGL(k_select_multi<4>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
     }
 }
-void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
-    hipLaunchKernelGGL(k_expand_backup_multi, dim3(n_slots), dim3(WAVE), 0, s, g, c, B);
+    hipLaunchKernelGGL(k_expand_backup_multi, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
-void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots)
+void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
-    hipLaunchKernelGGL(k_expand_backup, dim3(n_slots), dim3(WAVE), 0, s, g, c, B);
+    hipLaunchKernelGGL(k_expand_backup, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                const int16_t *moves_dev, const int32_t *offsets_dev)
@@ -1857,19 +1893,19 @@ void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c,
 {
     hipLaunchKernelGGL(k_advance_manual, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, moves_dev, reuse);
 }
-void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc)
+void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
-    hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, rc);
+    hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
 {
     const int rot = (int)(((unsigned long long)(unsigned)step * 2654435761ull) % (unsigned long long)n_slots);
     hipLaunchKernelGGL(k_order_evals, dim3(1), dim3(1024), 0, s, B, n_slots, rot);
 }
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, ReadCaps rc)
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
     hipLaunchKernelGGL(k_driver_scan, dim3(1), dim3(1024), 0, s, c, B, n_slots);
-    hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, rc);
+    hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,

@@ -1,6 +1,7 @@
 """Exact endgame solver for any board (A <= 256): true values of positions with at most 16 free edges.
 
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --bench 4096 [--free 16]
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0]
 
 The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
 over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
@@ -79,6 +80,49 @@ class Endgame:
             out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
         return out
 
+    def policy(self, x, seed=0):
+        """The solver as a policy/value evaluator (dbaz_exact_policy), every row solved from scratch: x as for score().  Returns
+        (p float32 [n, A] one-hot on an optimal move, v float32 [n] the true result for the mover, solved bool [n]); the pick among
+        equally good moves is the first in action order for seed 0, otherwise a function of the position and the seed alone.
+        A finished game gets p = 0 and v = its result; a row with more than max_free free edges p = 0, v = 0, solved False."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        n = int(xt.shape[0])
+        p = torch.empty((n, self.A), dtype=torch.float32, device=dev)
+        v = torch.empty(n, dtype=torch.float32, device=dev)
+        solved = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_exact_policy(self.h, C.c_int32(n), ptr(xt), C.c_uint64(int(seed)), ptr(p), ptr(v), ptr(solved),
+                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = (p, v, solved != 0)
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+    def policy_from(self, roots, x, seed=0):
+        """The table path the search uses, on its own (dbaz_exact_policy_from): roots int16 [m, 3*H*W], x int16 [m, k, 3*H*W] --
+        x[i] are positions that draw further edges of roots[i] (the root itself included).  Root i's subgame is solved once, its k
+        rows are answered from the table.  Returns (p [m, k, A], v [m, k]), equal to policy(x, seed)'s wherever roots[i] has at
+        most max_free free edges (p = 0, v = 0 elsewhere).  self.last_ms = HIP-event milliseconds of (table kernel, lookup kernel)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        conv = lambda t: torch.as_tensor(np.ascontiguousarray(t, dtype=np.int16) if not isinstance(t, torch.Tensor) else t).to(device=dev, dtype=torch.int16)  # noqa: E731
+        rt = conv(roots).reshape(-1, self.F).contiguous()
+        m = int(rt.shape[0])
+        xt = conv(x).reshape(m, -1, self.F).contiguous() if m else conv(x).reshape(0, 1, self.F)
+        k = int(xt.shape[1])
+        p = torch.empty((m, k, self.A), dtype=torch.float32, device=dev)
+        v = torch.empty((m, k), dtype=torch.float32, device=dev)
+        ms = (C.c_float * 2)()
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_exact_policy_from(self.h, C.c_int32(m), ptr(rt), C.c_int32(k), ptr(xt), C.c_uint64(int(seed)), ptr(p), ptr(v), ms,
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self.last_ms = (float(ms[0]), float(ms[1]))
+        return (p.cpu().numpy(), v.cpu().numpy()) if as_numpy else (p, v)
+
 
 def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FREE, device=0):
     """Scores the rows Engine.fetch_samples() / generate_games return (x, pi, played, z) on any board: the counterpart of
@@ -149,14 +193,20 @@ def _bench(g, n, free):
     n_free = torch.empty(n, dtype=torch.int16, device=dev)
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
 
-    def timed(x):
+    p, v = torch.empty((n, g.A), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    solved = torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def timed(x, policy=False):
         ms = []
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             for i in range(6):
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record()
-                g._ck(g._L.dbaz_endgame_score(g.h, C.c_int32(n), ptr(x), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), stream))
+                if policy:
+                    g._ck(g._L.dbaz_exact_policy(g.h, C.c_int32(n), ptr(x), C.c_uint64(7), ptr(p), ptr(v), ptr(solved), stream))
+                else:
+                    g._ck(g._L.dbaz_endgame_score(g.h, C.c_int32(n), ptr(x), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), stream))
                 t1.record()
                 t1.synchronize()
                 if i:  # the first run warms up
@@ -171,6 +221,55 @@ def _bench(g, n, free):
         assert np.array_equal(n_free.cpu().numpy(), np.broadcast_to(np.minimum(f, g.n_edges), (n,)))
         out[name + "_ms"] = round(ms, 4)
         out[name + "_rows_per_s"] = round(n / (ms * 1e-3))
+        out[name + "_policy_ms"] = round(timed(x, policy=True), 4)  # dbaz_exact_policy: the same solve, the evaluator's epilogue
+        # the search's two kernels on the same rows: k_endgame_table (n tables), k_endgame_eval (n leaves, each its own root)
+        both = []
+        for i in range(6):
+            g.policy_from(x, x.reshape(n, 1, -1), 7)
+            if i:
+                both.append(g.last_ms)
+        out[name + "_table_ms"] = round(float(np.median([b[0] for b in both])), 4)
+        out[name + "_eval_ms"] = round(float(np.median([b[1] for b in both])), 4)
+    return out
+
+
+def _selfplay_bench(a):
+    """n complete self-play games with a random-init ResNetZero (noise, tree reuse: bench.py --full-games' engine), once without
+    and once with the endgame tables attached: games/s, network evaluations per game, tables solved.  Each figure is the median
+    of a.repeats runs after one warm-up run."""
+    import time
+    import torch
+    from . import nn as dnn
+    from .engine import Engine
+
+    def play(g):
+        eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=a.reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
+                     device=a.device, endgame=g, endgame_reads=a.endgame_reads)
+        torch.manual_seed(0)
+        model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
+        eng.load_state_dict(model.state_dict(), "resnet", **model.shape)
+        runs = []
+        for i in range(a.repeats + 1):
+            solved0 = eng.endgame_stats()[0]
+            eng.sync()
+            t0 = time.perf_counter()
+            eng.selfplay_start(a.selfplay_bench, 0)
+            eng.run()
+            n_rows = len(eng.fetch_samples()["z"])
+            dt = time.perf_counter() - t0
+            c = eng.counters()
+            if i:  # the first run warms up
+                runs.append(dict(games_per_s=c["games_finished"] / dt, nn_evals_per_game=c["nn_evals"] / max(1, c["games_finished"]),
+                                 rows_per_game=n_rows / max(1, c["games_finished"]), tables_solved=eng.endgame_stats()[0] - solved0,
+                                 seconds=dt))
+        eng.close()
+        return {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+
+    g = Endgame(a.rows, a.cols, a.device, a.max_free)
+    out = dict(rows=a.rows, cols=a.cols, games=a.selfplay_bench, slots=a.slots, reads=a.reads, max_free=g.max_free,
+               endgame_reads=a.endgame_reads, table_bytes=a.slots * max(16, 1 << g.max_free), plain=play(None), endgame=play(g))
+    out["speedup"] = out["endgame"]["games_per_s"] / out["plain"]["games_per_s"]
+    g.close()
     return out
 
 
@@ -184,7 +283,19 @@ def main(argv=None):
     ap.add_argument("--max-free", type=int, default=MAX_FREE)
     ap.add_argument("--bench", type=int, default=4096, metavar="N", help="rows per timed call (median of 5 after a warm-up)")
     ap.add_argument("--free", type=int, default=MAX_FREE, help="free edges of every row of the first batch")
+    ap.add_argument("--selfplay-bench", type=int, default=0, metavar="N",
+                    help="play N complete self-play games with a random-init ResNetZero, with and without the endgame tables attached")
+    ap.add_argument("--slots", type=int, default=0, help="--selfplay-bench: engine slots (default min(N, 8192))")
+    ap.add_argument("--reads", type=int, default=800, help="--selfplay-bench: mcts_num_read")
+    ap.add_argument("--endgame-reads", type=int, default=0, help="--selfplay-bench: read cap of the searches the tables serve (0: none)")
+    ap.add_argument("--channels", type=int, default=64)
+    ap.add_argument("--blocks", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5, help="--selfplay-bench: timed runs per configuration (median)")
     a = ap.parse_args(argv)
+    if a.selfplay_bench > 0:
+        a.slots = a.slots or min(a.selfplay_bench, 8192)
+        print(json.dumps(_selfplay_bench(a)))
+        return
     g = Endgame(a.rows, a.cols, a.device, a.max_free)
     out = dict(rows=a.rows, cols=a.cols, E=g.n_edges, max_free=g.max_free)
     out.update(_bench(g, a.bench, a.free))

@@ -39,6 +39,10 @@ class Engine:
     dotsboxesaz_amd.solver.Solver of this board and device (boards of at most 31 edges); the Engine keeps a reference to it.
     solver_seed picks among equally good moves (0 = the lowest action), solver_reads > 0 caps the driver rule's reads of the
     searches the table serves (attach_solver).
+    endgame=Endgame(rows, cols, max_free) (dotsboxesaz_amd.endgame): the models in endgame_models, whatever network or formula
+    evaluates them, answer every leaf under a search root with at most max_free free edges from that root's exact table, solved
+    once per game (attach_endgame); endgame_seed picks among equally good moves, endgame_reads > 0 caps the driver rule's reads of
+    the searches the tables serve.  The Engine keeps a reference to the handle.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -49,7 +53,7 @@ class Engine:
                  temperature=None, reuse_tree=True, evaluator="formula", nodes_per_slot=0, seed=0, device=0,
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
-                 solver_reads=0):
+                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -100,6 +104,14 @@ class Engine:
             except Exception:
                 self.close()
                 raise
+        self._endgames = {}
+        if endgame is not None:
+            try:
+                for model in endgame_models:
+                    self.attach_endgame(endgame, model, endgame_seed, endgame_reads)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -121,6 +133,21 @@ class Engine:
         action index); reads > 0: searches the table serves run min(driver rule, reads) reads."""
         self._ck(self._L.dbaz_attach_solver(self.h, int(model), solver.h, C.c_uint64(int(seed)), int(reads)))
         self._solvers[int(model)] = solver
+
+    def attach_endgame(self, endgame, model=0, seed=0, reads=0):
+        """dbaz_attach_endgame: model 0 / 1 (any evaluator but "external" and "solver") answers the leaves under a search root with
+        at most endgame.max_free free edges from that root's exact table, which the engine solves once per game and keeps per slot
+        (n_slots x 2^max_free bytes of device memory).  The Endgame is borrowed and kept alive with the Engine.  seed: which of
+        several optimal moves gets the prior (0 = the lowest action index); reads > 0: searches the tables serve run
+        min(driver rule, reads) reads."""
+        self._ck(self._L.dbaz_attach_endgame(self.h, int(model), endgame.h, C.c_uint64(int(seed)), int(reads)))
+        self._endgames[int(model)] = endgame
+
+    def endgame_stats(self):
+        """(tables_solved, leaves_served) since the first attach_endgame; (0, 0) without one"""
+        t, n = C.c_int64(), C.c_int64()
+        self._L.dbaz_get_endgame_stats(self.h, C.byref(t), C.byref(n))
+        return int(t.value), int(n.value)
 
     # ---------------------------------------------------------------- rules (G1-G6)
     def rules_init(self, n):

@@ -456,6 +456,49 @@ void dbaz_endgame_destroy(dbaz_endgame *g);
  * n == 0 is a no-op. */
 int dbaz_endgame_score(dbaz_endgame *g, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
                        int8_t *q_dev /*[n][A]*/, float *mass_dev, int16_t *n_free_dev, void *stream);
+/* The endgame solver as a policy/value evaluator, the counterpart of dbaz_perfect_policy on any board: every row is solved from
+ * scratch (the solve of dbaz_endgame_score), then p float32 [n][A] is ONE-HOT on an optimal move and v float32 [n] =
+ * sign(margin + D[0]).  Among the n_opt moves whose q is the maximum the pick is the k-th in ascending action order: k = 0 for
+ * pick_seed = 0, otherwise k = mix(key, pick_seed) mod n_opt with dbaz_perfect_policy's finaliser and key = the XOR over the
+ * row's free real edges a of 1 << (a & 63) (64-bit) -- a function of the position alone, so every path to a position picks the
+ * same move.  With pick_seed = 0 the outputs equal dbaz_perfect_policy's wherever both apply.
+ *   solved [n]       1, or 0 for a row with F > max_free, which gets p = 0 and v = 0
+ * A finished game (early end included) with F <= max_free gets p = 0, v = get_result and solved = 1.
+ * DEVICE pointers, QUEUED on the caller's stream; the grid is n; n == 0 is a no-op.  (Not named dbaz_endgame_*: that family is
+ * the scorer's and stays as it is.) */
+int dbaz_exact_policy(dbaz_endgame *g, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev /*[n][A]*/, float *v_dev,
+                      uint8_t *solved_dev, void *stream);
+/* The same (p, v) through the TABLE path the search uses (below), on its own: root i's subgame is solved once into a scratch table
+ * (k_endgame_table), then the rows x[i * per_root .. (i + 1) * per_root) int16 -- positions that draw further edges of root i, the
+ * root itself included; the caller's duty, another row gets a meaningless but harmless answer -- are answered from it by lookup
+ * (k_endgame_eval).  p [n_roots * per_root][A], v [n_roots * per_root] equal dbaz_exact_policy's on those rows bit for bit; the
+ * rows of a root with F > max_free get p = 0, v = 0.  ms_out (host, may be NULL): HIP-event milliseconds of the table kernel [0]
+ * and of the lookup kernel [1].  DEVICE pointers; queued on the caller's stream, but the call allocates n_roots x max(16,
+ * 2^max_free) bytes of scratch and returns only when the kernels are done (DBAZ_EDEVICE when the scratch cannot be had). */
+int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const int16_t *roots_dev, int32_t per_root, const int16_t *x_dev,
+                           uint64_t pick_seed, float *p_dev, float *v_dev, float *ms_out /*[2]*/, void *stream);
+/* The endgame solver inside the search: once a search ROOT of a slot has F0 <= max_free free edges, every later
+ * position of that game is a subset of those edges.  The engine solves the root's subgame once, keeps the 2^F0-byte table in the
+ * slot's region in HBM (n_slots x max(16, 2^max_free) bytes, allocated by the first attach: 8 192 slots x 64 KB = 512 MiB) and
+ * answers every later leaf of that game -- this search's and those of the game's later moves -- by lookup with dbaz_exact_policy's
+ * (p, v), bit for bit.  Such a leaf never reaches the model's own evaluator, network or formula: it is not on the evaluation lists,
+ * not counted in or deferred by the full-rounds cut, skips the transposition probe and is not counted in dbaz_counters.nn_evals.
+ * Every other leaf is handled as without the attach; in particular a leaf with F <= max_free under a root with F > max_free still
+ * goes to the model's evaluator (the table is rooted at search roots only).  A table is valid for the slot's current game only.
+ * model: 0, or 1 = the second model in match play.  The engine BORROWS g: it must outlive the engine's use of it.
+ * endgame_reads > 0: a search under the driver's rule (num_reads == NULL, self-play) whose root has F <= max_free runs
+ * min(rule, endgame_reads) reads; 0 = the rule; explicit num_reads are never touched.
+ * With reuse_tree = 0 and no noise a game ends with the theoretical result of the first root that had a table, from that move on
+ * (4.6's one-hot argument with its fresh-root condition); with tree reuse or noise only the served leaves' (p, v) are exact.
+ *   the model's evaluator DBAZ_EVAL_EXTERNAL or DBAZ_EVAL_SOLVER, model not 0 / 1 (1 without match play), g of another board size
+ *   or device, endgame_reads < 0                                  -> DBAZ_EINVAL
+ *   a max_free other than that of the handle's FIRST attach (either model; the slot regions are sized once) -> DBAZ_EINVAL
+ * A later attach with the same max_free replaces the model's solver, seed and endgame_reads and drops every slot's table.
+ *   the slot tables cannot be allocated                           -> DBAZ_EDEVICE; the engine stays usable without the attach */
+int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t pick_seed, int32_t endgame_reads);
+/* cumulative since the first attach: tables solved (one per game and model side that reaches F <= max_free), leaves answered from
+ * them; waits for the engine's queued work.  Either pointer may be NULL.  (Not named dbaz_endgame_*, like dbaz_exact_policy.) */
+void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_solved, int64_t *leaves_served);
 
 #ifdef __cplusplus
 }
