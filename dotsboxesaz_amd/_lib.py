@@ -35,7 +35,7 @@ SYMBOLS = [
     "dbaz_solver_last_error", "dbaz_solver_create", "dbaz_solver_destroy", "dbaz_solver_solve", "dbaz_solver_info", "dbaz_solver_table",
     "dbaz_solver_score", "dbaz_perfect_policy", "dbaz_attach_solver",
     "dbaz_endgame_last_error", "dbaz_endgame_create", "dbaz_endgame_destroy", "dbaz_endgame_score", "dbaz_exact_policy", "dbaz_exact_policy_from", "dbaz_attach_endgame",
-    "dbaz_get_endgame_stats",
+    "dbaz_get_endgame_stats", "dbaz_exact_targets", "dbaz_dataset_exact_targets",
 ]
 
 
@@ -186,6 +186,8 @@ def load():
     L.dbaz_exact_policy_from.argtypes = [vp, i32, vp, i32, vp, C.c_uint64, vp, vp, C.POINTER(C.c_float), vp]
     L.dbaz_attach_endgame.argtypes = [vp, i32, vp, C.c_uint64, i32]
     L.dbaz_get_endgame_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.dbaz_exact_targets.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.dbaz_dataset_exact_targets.argtypes = [vp, vp, i32, i32, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",

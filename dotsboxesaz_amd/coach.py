@@ -41,8 +41,13 @@ class NullWriter:
 
 
 class Coach:
-    def __init__(self, params, rows, cols, device=0, n_slots=None, dist=None, nn_precision=1):
+    def __init__(self, params, rows, cols, device=0, n_slots=None, dist=None, nn_precision=1, exact_targets=None, exact_pi="restrict",
+                 exact_z=True):
+        """exact_targets: an endgame.Endgame of the board, or True for one with max_free = 16 -- the train and the validation
+        dataset of every generation get the solved z (exact_z) and pi (exact_pi) on their late rows (train_data.ReplayDataset)."""
         self.params, self.rows, self.cols = params, int(rows), int(cols)
+        self.exact_targets, self.exact_pi, self.exact_z = exact_targets, exact_pi, exact_z
+        self.exact_stats = None
         self.device, self.dist, self.n_slots, self.nn_precision = device, dist, n_slots, nn_precision
         self.model_class = _get(_get(params, "nn"), "model_class")
         self.engine = None
@@ -96,8 +101,14 @@ class Coach:
             tp["symmetries"] = TD.SymmetriesGenerator(self.engine)
         writer = writer or NullWriter()
 
-        train_ds = self.store.dataset(train=True, min_generation=gmin, n_samples=int(n_samples * split), pos_average=avg)
-        val_ds = self.store.dataset(train=False, min_generation=gmin, n_samples=int(n_samples * (1 - split)), pos_average=avg)
+        if self.exact_targets is True:
+            from .endgame import Endgame
+            self.exact_targets = Endgame(self.rows, self.cols, self.device)
+        exact = dict(exact=self.exact_targets, exact_pi=self.exact_pi, exact_z=self.exact_z) if self.exact_targets is not None else {}
+        # both datasets: the train and the validation loss are measured against the same targets
+        train_ds = self.store.dataset(train=True, min_generation=gmin, n_samples=int(n_samples * split), pos_average=avg, **exact)
+        val_ds = self.store.dataset(train=False, min_generation=gmin, n_samples=int(n_samples * (1 - split)), pos_average=avg, **exact)
+        self.exact_stats = train_ds.exact_stats
         self.store.drop_before(gmin)  # (the window's lower edge only moves forward: older rows would stay in HBM for nothing)
         return wrapper.train(train_ds, val_ds if len(val_ds) else None, writer, generation)
 
@@ -112,6 +123,8 @@ class Coach:
                 rec["selfplay"] = self.selfplay(g)
             start_train = False
             rec["last_batch_idx"] = self.train_nn(g, writer)
+            if self.exact_targets is not None:
+                rec["exact_targets"] = self.exact_stats
             if g > 0:
                 elo_params = _get(self.params, "elo")
                 if elo_params is not None:

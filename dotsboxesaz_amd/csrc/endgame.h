@@ -61,3 +61,9 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
 void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
                      const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
                      int AS, unsigned long long *stats);
+
+// ---- exact training targets (dbaz_exact_targets, include/dbaz.h): rows x_stride shorts apart, relabelled in place, queued on
+// `stream`.  stats_host [4 + 17] (may be NULL) as dbaz_dataset_exact_targets documents it: asking for it waits for the stream.
+// The message of a failure is dbaz_endgame_last_error(g)'s.
+int endgame_targets(dbaz_endgame *g, hipStream_t stream, int32_t n, const int16_t *x, int x_stride, int pi_mode, int z_mode, float *pi, float *z,
+                    int16_t *n_free, float *mass, uint8_t *relabelled, int64_t *stats_host);

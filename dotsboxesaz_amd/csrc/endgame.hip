@@ -12,6 +12,8 @@
 //   3. outputs with dbaz_solver_score's meaning, plus n_free.
 // k_endgame_policy: steps 1 and 2, then a one-hot optimal move and the true value per row (dbaz_exact_policy).
 // k_endgame_table / k_endgame_eval: a search root's table kept per slot in HBM, and the leaves of that game answered from it.
+// k_endgame_candidates / k_endgame_list / k_endgame_targets: exact training targets (dbaz_exact_targets): the rows with
+//   F <= max_free listed deepest first, then steps 1 and 2 per listed row and the solved z and pi written in place.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -21,10 +23,23 @@
 
 #include "endgame.h"
 
+// counters of one dbaz_exact_targets call (device): rows per F <= max_free, the append cursors of k_endgame_list, and the
+// statistics of the dataset form -- [0] finished rows left alone, [1] rows whose z differed from v, [2 + F] rows relabelled
+struct TargetCounters {
+    uint32_t hist[ENDGAME_MAX_FREE + 1];
+    uint32_t cursor[ENDGAME_MAX_FREE + 1];
+    unsigned long long stats[ENDGAME_MAX_FREE + 3];
+};
+
 struct dbaz_endgame {
     EndgameGeo g;
     int dev = 0;
     void *bufs[4] = {nullptr, nullptr, nullptr, nullptr}; // action, nbr, perm, off
+    // scratch of dbaz_exact_targets, grown on demand: the candidate list and n_free per row; the counters
+    int32_t *tg_list = nullptr;
+    int16_t *tg_nfree = nullptr;
+    size_t tg_cap = 0;
+    TargetCounters *tg_cnt = nullptr;
     std::string err;
 };
 
@@ -75,9 +90,11 @@ struct MaskEdges {
     __device__ __forceinline__ bool operator()(int a) const { return !((free_edges[a >> 6] >> (a & 63)) & 1ull); }
 };
 
-template <typename Edges>
+// THREADS: the workgroup's size, at least one lane per action slot
+template <typename Edges, int THREADS = ENDGAME_THREADS>
 static __device__ __forceinline__ int endgame_setup(const EndgameGeo &g, const Edges &drawn, EndgameLds &L)
 {
+    static_assert(THREADS >= DBAZ_MAX_A && THREADS % 64 == 0, "one lane per action slot");
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < DBAZ_MAX_A) L.cidx[tid] = -1;
     if (tid == 0) L.closed = 0;
@@ -98,7 +115,7 @@ static __device__ __forceinline__ int endgame_setup(const EndgameGeo &g, const E
         L.act[j] = (uint8_t)a_mine;
     }
     const int W = g.cols + 1, B = g.rows * g.cols;
-    for (int b = tid; b < B; b += ENDGAME_THREADS) {
+    for (int b = tid; b < B; b += THREADS) {
         const int at = (b / g.cols) * W + b % g.cols;
         if (drawn(at) && drawn(at + W) && drawn(g.HW + at) && drawn(g.HW + at + 1)) atomicAdd(&L.closed, 1);
     }
@@ -122,6 +139,7 @@ static __device__ __forceinline__ int endgame_setup(const EndgameGeo &g, const E
 
 // step 2: the subgame of the F compact edges into sd[2^F], by popcount layers; the box masks are the same for every lane: keep
 // them in scalar registers.  Ends behind a barrier: sd is complete for the whole workgroup.
+template <int THREADS = ENDGAME_THREADS>
 static __device__ __forceinline__ void endgame_solve(const EndgameGeo &g, int F, const EndgameLds &L, int8_t *sd)
 {
     const int tid = threadIdx.x;
@@ -136,7 +154,7 @@ static __device__ __forceinline__ void endgame_solve(const EndgameGeo &g, int F,
     const uint32_t *off = g.off + F * ENDGAME_OFF_STRIDE;
     for (int k = F; k >= 0; k--) {
         const uint32_t end = off[k + 1];
-        for (uint32_t i = off[k] + tid; i < end; i += ENDGAME_THREADS) {
+        for (uint32_t i = off[k] + tid; i < end; i += THREADS) {
             const uint32_t low = list[i];
             int best = -128;
 #pragma unroll
@@ -402,6 +420,142 @@ __global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(Endgam
     }
 }
 
+// ---- exact training targets (dbaz_exact_targets) --------------------------------------------------------------
+// Most rows of a training window have F > max_free and the rest have F spread over 0 .. max_free, so the rows are sorted out
+// before anything is solved.  k_endgame_candidates, one wavefront per row and no table: F from the edge planes, n_free and the
+// "untouched" side outputs of every row, and the histogram of the F <= max_free (per workgroup in LDS, then one atomic per
+// occupied bin).  x_stride: shorts between two rows (3*HW for dense rows, the dataset's padded rows are further apart).
+#define ENDGAME_CAND_WAVES 4
+__global__ void __launch_bounds__(64 * ENDGAME_CAND_WAVES) k_endgame_candidates(EndgameGeo g, const int16_t *__restrict__ x, int x_stride, int n,
+                                                                                int16_t *__restrict__ n_free, float *__restrict__ mass,
+                                                                                uint8_t *__restrict__ relabelled, TargetCounters *__restrict__ cnt)
+{
+    __shared__ uint32_t s_hist[ENDGAME_MAX_FREE + 1];
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x <= ENDGAME_MAX_FREE) s_hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int r = blockIdx.x * ENDGAME_CAND_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * ENDGAME_CAND_WAVES) {
+        const int16_t *xr = x + (size_t)r * x_stride;
+        int F = 0;
+        for (int i0 = 0; i0 < g.E; i0 += 64) {
+            const int i = i0 + lane;
+            F += __popcll(__ballot(i < g.E && xr[g.action[i]] == 0));
+        }
+        if (lane == 0) {
+            n_free[r] = (int16_t)F;
+            if (mass) mass[r] = 0.0f;
+            if (relabelled) relabelled[r] = 0;
+            if (F <= g.max_free) atomicAdd(&s_hist[F], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x <= ENDGAME_MAX_FREE && s_hist[threadIdx.x]) atomicAdd(&cnt->hist[threadIdx.x], s_hist[threadIdx.x]);
+}
+
+// The candidate list from n_free and the finished histogram: the rows with F <= max_free, deepest first (bucket F starts behind
+// the rows of every deeper bucket).  One thread per row; the lanes of a wavefront that share an F take their places with one
+// atomic.  The order inside a bucket is whatever the atomics give: every row is relabelled on its own, so no output depends on it.
+__global__ void __launch_bounds__(256) k_endgame_list(int max_free, int n, const int16_t *__restrict__ n_free, TargetCounters *__restrict__ cnt,
+                                                      int32_t *__restrict__ list)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const int F = r < n ? (int)n_free[r] : max_free + 1;
+    uint32_t start = 0; // of bucket f while the loop goes down
+    for (int f = max_free; f >= 0; f--) {
+        const uint64_t same = __ballot(F == f);
+        if (same) {
+            const int first = __ffsll((long long)same) - 1;
+            uint32_t at = 0;
+            if (lane == first) at = atomicAdd(&cnt->cursor[f], (uint32_t)__popcll(same));
+            at = (uint32_t)__shfl((int)at, first);
+            if (F == f) list[start + at + (uint32_t)__popcll(same & ((1ull << lane) - 1ull))] = r;
+        }
+        start += cnt->hist[f];
+    }
+}
+
+// One workgroup per listed row of the class f_lo .. g.max_free (the host passes the class's upper end as the geometry's max_free:
+// the dynamic table sd holds 2^max_free bytes): k_endgame_score's setup and solve, then the rule of include/dbaz.h in place.
+// The grid is fixed (the host does not know the counts); workgroup b takes the class's rows b, b + gridDim.x, ... of the
+// deepest-first list, so every workgroup gets the same mix of depths.  Wave 0, lane c = compact edge c: the result-preserving set as a ballot, and S in ascending action order
+// -- the float32 additions of k_endgame_score's policy_mass, in every lane.  The statistics are kept per workgroup in LDS.
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_endgame_targets(EndgameGeo g, int f_lo, TargetCounters *__restrict__ cnt, const int32_t *__restrict__ list,
+                                                             int n, const int16_t *__restrict__ x, int x_stride, int pi_mode, int z_mode,
+                                                             float *pi, float *z, float *__restrict__ mass, uint8_t *__restrict__ relabelled,
+                                                             int want_stats)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [max(16, 2^g.max_free)]
+    __shared__ EndgameLds L;
+    __shared__ uint32_t s_members;
+    __shared__ float s_sum;
+    __shared__ uint32_t s_stats[ENDGAME_MAX_FREE + 3];
+
+    const int tid = threadIdx.x;
+    uint32_t begin = 0, count = 0;
+    for (int f = ENDGAME_MAX_FREE; f >= f_lo; f--) {
+        const uint32_t h = cnt->hist[f];
+        if (f > g.max_free) begin += h;
+        else count += h;
+    }
+    if (tid < ENDGAME_MAX_FREE + 3) s_stats[tid] = 0;
+    __syncthreads();
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const int r = list[begin + i];
+        if ((unsigned)r >= (unsigned)n) continue; // never outside the caller's buffers (the same answer in every thread)
+        const int16_t *xr = x + (size_t)r * x_stride;
+        float *pr = pi ? pi + (size_t)r * g.A : nullptr;
+        const int F = endgame_setup<RowEdges, THREADS>(g, RowEdges{xr}, L);
+        if (F > g.max_free) { // not a row of this class: cannot happen with a list built from the same rows
+            __syncthreads();
+            continue;
+        }
+        endgame_solve<THREADS>(g, F, L, sd);
+
+        const RowFacts f = solver_facts(g.rows * g.cols, L.closed, (int)xr[2 * g.HW]);
+        const bool open = f.res == DBAZ_RESULT_NONE;
+        if (open) {
+            const int v = sgn(f.margin + (int)sd[0]);
+            if (tid < 64) {
+                const bool edge = tid < F;
+                const int qq = edge ? solver_move_q(L.other[tid][0], L.other[tid][1], 0u, (int)sd[1u << tid]) : 0;
+                const uint32_t members = (uint32_t)__ballot(edge && sgn(f.margin + qq) == v);
+                const float p = pr && edge ? pr[L.act[tid]] : 0.0f;
+                float sum = 0.0f;
+                for (int c = 0; c < F; c++) {
+                    const float pc = __shfl(p, c);
+                    if ((members >> c) & 1u) sum += pc;
+                }
+                if (tid == 0) {
+                    s_members = members;
+                    s_sum = sum;
+                }
+            }
+            __syncthreads();
+            const uint32_t members = s_members;
+            const float sum = s_sum;
+            if (pi_mode) {
+                const bool uniform = pi_mode == 1 || !(sum > 0.0f);
+                const float share = 1.0f / (float)__popc(members);
+                for (int a = tid; a < g.A; a += THREADS) {
+                    const int c = L.cidx[a];
+                    const bool member = c >= 0 && ((members >> c) & 1u);
+                    pr[a] = member ? (uniform ? share : pr[a] / sum) : 0.0f;
+                }
+            }
+            if (tid == 0) {
+                if (z && z[r] != (float)v) s_stats[1]++;
+                s_stats[2 + F]++;
+                if (z_mode) z[r] = (float)v;
+                if (mass) mass[r] = sum;
+                if (relabelled) relabelled[r] = 1;
+            }
+        } else if (tid == 0) s_stats[0]++;
+        __syncthreads(); // the next row of this workgroup reuses L and sd
+    }
+    if (want_stats && tid < ENDGAME_MAX_FREE + 3 && s_stats[tid]) atomicAdd(&cnt->stats[tid], (unsigned long long)s_stats[tid]);
+}
+
 // ------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------
@@ -412,6 +566,8 @@ extern "C" void dbaz_endgame_destroy(dbaz_endgame *g)
     if (!g) return;
     (void)hipSetDevice(g->dev);
     for (void *b : g->bufs)
+        if (b) (void)hipFree(b);
+    for (void *b : {(void *)g->tg_list, (void *)g->tg_nfree, (void *)g->tg_cnt})
         if (b) (void)hipFree(b);
     delete g;
 }
@@ -478,6 +634,8 @@ extern "C" int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, i
         e = hipFuncSetAttribute((const void *)k_endgame_policy, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_endgame_table, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_endgame_targets<ENDGAME_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
     if (e != hipSuccess) {
         const std::string msg = hipGetErrorString(e);
         (void)hipGetLastError();
@@ -519,6 +677,80 @@ extern "C" int dbaz_exact_policy(dbaz_endgame *g, int32_t n, const int16_t *x_de
                                                                                                        solved_dev);
     ENDGAME_HIP(g, hipGetLastError());
     return DBAZ_OK;
+}
+
+// ---- exact training targets: dense rows through the C ABI, the engine's resident dataset through endgame.h
+// The classes of F one k_endgame_targets launch serves, deepest first: the table of a class takes 2^f_hi bytes of LDS, so the
+// shallow classes fit more workgroups on a CU, and 256 threads cover every popcount layer of F <= 10 (C(10, 5) = 252 masks) in one
+// pass.  grid: eight times what the chip holds at once (256 CUs x the workgroups per CU that LDS and wave slots admit) -- a CU
+// that is done with a workgroup takes the next one, which evens out CUs of different pace; measured in DESIGN.md 5.
+struct TargetClass {
+    int f_lo, f_hi, threads, grid;
+};
+static const TargetClass kTargetClasses[] = {{16, 16, ENDGAME_THREADS, 4096}, {14, 15, ENDGAME_THREADS, 8192}, {11, 13, ENDGAME_THREADS, 8192},
+                                             {0, 10, 256, 16384}};
+
+int endgame_targets(dbaz_endgame *g, hipStream_t s, int32_t n, const int16_t *x, int x_stride, int pi_mode, int z_mode, float *pi, float *z,
+                    int16_t *n_free, float *mass, uint8_t *relabelled, int64_t *stats_host)
+{
+    if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1)
+        return gerr(g, DBAZ_EINVAL, "exact targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode, z_mode);
+    if (n < 0 || (n > 0 && (!x || (pi_mode != 0 && !pi) || (z_mode != 0 && !z))))
+        return gerr(g, DBAZ_EINVAL, "exact targets: bad argument (n = %d; a mode other than keep needs its array)", n);
+    if (stats_host) std::fill(stats_host, stats_host + 4 + ENDGAME_MAX_FREE + 1, (int64_t)0);
+    if (n == 0) return DBAZ_OK;
+    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    if (!g->tg_cnt) ENDGAME_HIP(g, hipMalloc((void **)&g->tg_cnt, sizeof(TargetCounters)));
+    if ((size_t)n > g->tg_cap) { // hipFree waits for the kernels that still use the old scratch
+        if (g->tg_list) (void)hipFree(g->tg_list);
+        if (g->tg_nfree) (void)hipFree(g->tg_nfree);
+        g->tg_list = nullptr;
+        g->tg_nfree = nullptr;
+        g->tg_cap = 0;
+        const size_t cap = (size_t)n + (size_t)n / 2;
+        ENDGAME_HIP(g, hipMalloc((void **)&g->tg_list, cap * sizeof(int32_t)));
+        ENDGAME_HIP(g, hipMalloc((void **)&g->tg_nfree, cap * sizeof(int16_t)));
+        g->tg_cap = cap;
+    }
+    int16_t *nf = n_free ? n_free : g->tg_nfree;
+    ENDGAME_HIP(g, hipMemsetAsync(g->tg_cnt, 0, sizeof(TargetCounters), s));
+    const int cand_blocks = std::min((n + ENDGAME_CAND_WAVES - 1) / ENDGAME_CAND_WAVES, 16384);
+    k_endgame_candidates<<<cand_blocks, 64 * ENDGAME_CAND_WAVES, 0, s>>>(g->g, x, x_stride, n, nf, mass, relabelled, g->tg_cnt);
+    k_endgame_list<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->g.max_free, n, nf, g->tg_cnt, g->tg_list);
+    for (const TargetClass &c : kTargetClasses) {
+        if (c.f_lo > g->g.max_free) continue;
+        EndgameGeo gc = g->g;
+        gc.max_free = std::min(c.f_hi, g->g.max_free);
+        const size_t lds = std::max<size_t>(16, (size_t)1 << gc.max_free);
+        const unsigned grid = (unsigned)std::min(n, c.grid);
+        if (c.threads == 256)
+            k_endgame_targets<256><<<grid, 256, lds, s>>>(gc, c.f_lo, g->tg_cnt, g->tg_list, n, x, x_stride, pi_mode, z_mode, pi, z, mass, relabelled,
+                                                          stats_host != nullptr);
+        else
+            k_endgame_targets<ENDGAME_THREADS><<<grid, ENDGAME_THREADS, lds, s>>>(gc, c.f_lo, g->tg_cnt, g->tg_list, n, x, x_stride, pi_mode, z_mode, pi,
+                                                                                  z, mass, relabelled, stats_host != nullptr);
+    }
+    ENDGAME_HIP(g, hipGetLastError());
+    if (stats_host) {
+        unsigned long long st[ENDGAME_MAX_FREE + 3];
+        ENDGAME_HIP(g, hipMemcpyAsync(st, g->tg_cnt->stats, sizeof st, hipMemcpyDeviceToHost, s));
+        ENDGAME_HIP(g, hipStreamSynchronize(s));
+        stats_host[0] = n;
+        stats_host[2] = (int64_t)st[0];
+        stats_host[3] = (int64_t)st[1];
+        for (int f = 0; f <= ENDGAME_MAX_FREE; f++) {
+            stats_host[4 + f] = (int64_t)st[2 + f];
+            stats_host[1] += (int64_t)st[2 + f];
+        }
+    }
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_exact_targets(dbaz_endgame *g, int32_t n, const int16_t *x_dev, int32_t pi_mode, int32_t z_mode, float *pi_dev, float *z_dev,
+                                  int16_t *n_free_dev, float *mass_dev, uint8_t *relabelled_dev, void *stream)
+{
+    if (!g) return DBAZ_EINVAL;
+    return endgame_targets(g, (hipStream_t)stream, n, x_dev, 3 * g->g.HW, pi_mode, z_mode, pi_dev, z_dev, n_free_dev, mass_dev, relabelled_dev, nullptr);
 }
 
 // ---- the engine's side (endgame.h): one game's table behind the evaluator boundary

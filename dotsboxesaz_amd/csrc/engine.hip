@@ -1558,6 +1558,28 @@ extern "C" int dbaz_dataset_fetch(dbaz_engine *e, int16_t *x, float *pi, float *
     RDS(e);
     RDS_RET(e, rds_fetch(e->rds, e->stream, x, pi, z, _err));
 }
+extern "C" int dbaz_dataset_exact_targets(dbaz_engine *e, dbaz_endgame *g, int32_t pi_mode, int32_t z_mode, int64_t *stats_host)
+{
+    RDS(e);
+    if (!g) return set_error(e, DBAZ_EINVAL, "null endgame solver");
+    int max_free = 0;
+    if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
+                         e->g.cols, e->cfg.device);
+    if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1) return set_error(e, DBAZ_EINVAL, "pi_mode must be 0..2 and z_mode 0..1");
+    std::string err;
+    int16_t *x = nullptr;
+    float *pi = nullptr, *z = nullptr;
+    int x_stride = 0;
+    int64_t n = 0;
+    if (int rc = rds_arrays(e->rds, &x, &x_stride, &pi, &z, &n, err)) return set_error(e, rc, "%s", err.c_str());
+    if (n > 0x7fffffffll) return set_error(e, DBAZ_EINVAL, "a dataset of %lld rows: exact targets address rows with 32 bits", (long long)n);
+    int64_t stats[4 + ENDGAME_MAX_FREE + 1];
+    if (int rc = endgame_targets(g, e->stream, (int32_t)n, x, x_stride, pi_mode, z_mode, pi, z, nullptr, nullptr, nullptr, stats))
+        return set_error(e, rc, "%s", dbaz_endgame_last_error(g));
+    if (stats_host) memcpy(stats_host, stats, sizeof stats);
+    return DBAZ_OK;
+}
 extern "C" int dbaz_dataset_batch(dbaz_engine *e, const int32_t *idx, int32_t n, int32_t sym, float *boards_dev, float *pi_dev,
                                   float *z_dev)
 {

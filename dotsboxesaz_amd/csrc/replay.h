@@ -17,6 +17,8 @@ int rds_add_rows(ReplayDS *d, hipStream_t s, const void *rows_dev, int64_t n_row
 // order_host: dataset order as a permutation of the staged rows (nullptr = staging order)
 int rds_finish(ReplayDS *d, hipStream_t s, int pos_average, const int32_t *order_host, int64_t *n_out, std::string &err);
 int64_t rds_size(const ReplayDS *d);
+// the finished dataset's device arrays: x int16 rows *x_stride shorts apart, pi float32 [n][A], z float32 [n]
+int rds_arrays(ReplayDS *d, int16_t **x, int *x_stride, float **pi, float **z, int64_t *n_out, std::string &err);
 int rds_fetch(ReplayDS *d, hipStream_t s, int16_t *x, float *pi, float *z, std::string &err);
 // on_caller_stream: queued on `s` = the caller's own stream, nothing synchronised (indices validated on the host)
 int rds_batch(ReplayDS *d, hipStream_t s, const int32_t *idx_host, int n, int sym, float *boards_dev, float *pi_dev,

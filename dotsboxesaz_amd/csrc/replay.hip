@@ -527,6 +527,17 @@ int rds_finish(ReplayDS *d, hipStream_t s, int pos_average, const int32_t *order
     return DBAZ_OK;
 }
 
+int rds_arrays(ReplayDS *d, int16_t **x, int *x_stride, float **pi, float **z, int64_t *n_out, std::string &err)
+{
+    if (!d->finished) { err = "no dataset: call dbaz_dataset_finish first"; return DBAZ_ESTATE; }
+    *x = (int16_t *)d->ds_x.p;
+    *x_stride = d->FP;
+    *pi = (float *)d->ds_pi.p;
+    *z = (float *)d->ds_z.p;
+    *n_out = d->n_out;
+    return DBAZ_OK;
+}
+
 int rds_fetch(ReplayDS *d, hipStream_t s, int16_t *x, float *pi, float *z, std::string &err)
 {
     if (!d->finished) { err = "no dataset: call dbaz_dataset_finish first"; return DBAZ_ESTATE; }

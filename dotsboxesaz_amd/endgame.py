@@ -2,6 +2,7 @@
 
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --bench 4096 [--free 16]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0]
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --targets-bench 262144
 
 The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
 over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
@@ -14,6 +15,16 @@ from . import _lib
 from .solver import ILLEGAL, _margin, edge_actions
 
 MAX_FREE = 16  # ENDGAME_MAX_FREE
+PI_MODES = {"keep": 0, "uniform": 1, "restrict": 2}  # dbaz_exact_targets' pi_mode
+
+
+def target_modes(pi_mode, z_mode):
+    """(pi_mode, z_mode) of dbaz_exact_targets from a name ("keep", "uniform", "restrict") or number, and a truth value"""
+    if isinstance(pi_mode, str):
+        if pi_mode not in PI_MODES:
+            raise ValueError("pi_mode %r: one of %s" % (pi_mode, sorted(PI_MODES)))
+        pi_mode = PI_MODES[pi_mode]
+    return int(pi_mode), int(z_mode)
 
 
 class Endgame:
@@ -79,6 +90,40 @@ class Endgame:
         if as_numpy:
             out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
         return out
+
+    def targets(self, x, pi, z, pi_mode="restrict", z_mode=True):
+        """Exact training targets (dbaz_exact_targets): x as for score(), pi float32 [n, A], z float32 [n] (or [n, 1]).  Rows of
+        unfinished games with at most max_free free edges get z = the true result for the mover (z_mode) and pi on the moves that
+        keep it -- "uniform": equal shares; "restrict": the given pi renormalised over them (uniform where it has no mass there);
+        "keep": pi as it is.  Every other row comes back bit for bit.  Returns (pi', z', info) with info = dict(n_free int16 [n],
+        mass float32 [n]: pi's mass on those moves before the relabel, relabelled bool [n]); numpy in, numpy out, or torch tensors
+        on the handle's device in and out, queued on torch's current stream.  The caller's arrays are never modified."""
+        import torch
+        pm, zm = target_modes(pi_mode, z_mode)
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        n = int(xt.shape[0])
+        z_shape = tuple(z.shape)
+
+        def own(t, cols):  # a contiguous float32 copy on the device that this call may write
+            t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float32) if not isinstance(t, torch.Tensor) else t)
+            return t.to(device=dev, dtype=torch.float32).reshape(-1, cols).clone(memory_format=torch.contiguous_format)
+        pt, zt = own(pi, self.A), own(z, 1).reshape(-1)
+        if int(pt.shape[0]) != n or int(zt.shape[0]) != n:
+            raise ValueError("x has %d rows, pi %d, z %d" % (n, pt.shape[0], zt.shape[0]))
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev)
+        relabelled = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_exact_targets(self.h, C.c_int32(n), ptr(xt), C.c_int32(pm), C.c_int32(zm), ptr(pt), ptr(zt), ptr(n_free), ptr(mass),
+                                                ptr(relabelled), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        info = dict(n_free=n_free, mass=mass, relabelled=relabelled != 0)
+        zt = zt.reshape(z_shape)
+        if as_numpy:
+            return pt.cpu().numpy(), zt.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+        return pt, zt, info
 
     def policy(self, x, seed=0):
         """The solver as a policy/value evaluator (dbaz_exact_policy), every row solved from scratch: x as for score().  Returns
@@ -233,6 +278,55 @@ def _bench(g, n, free):
     return out
 
 
+def _targets_bench(g, n):
+    """HIP-event milliseconds of one dbaz_exact_targets call ("restrict", solved z) next to one dbaz_endgame_score call on the same
+    n rows, alternating in the same run: outputs preallocated, median of 5 after a warm-up.  Two batches of random_rows: n_free
+    uniform in 0 .. 16, and a self-play-like mix with 70 % of the rows at n_free in 17 .. 40 (which neither call solves)."""
+    import torch
+    dev = torch.device("cuda", g.device)
+    value, diff = torch.empty(n, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    q = torch.empty((n, g.A), dtype=torch.int8, device=dev)
+    n_free = torch.empty(n, dtype=torch.int16, device=dev)
+    mass = torch.empty(n, dtype=torch.float32, device=dev)
+    relabelled = torch.empty(n, dtype=torch.uint8, device=dev)
+    rs = np.random.RandomState(1)
+    pi0 = torch.as_tensor(rs.rand(n, g.A).astype(np.float32)).to(dev)
+    z0 = torch.as_tensor((np.arange(n) % 3 - 1).astype(np.float32)).to(dev)
+    pi, z = pi0.clone(), z0.clone()
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    uniform = rs.randint(0, MAX_FREE + 1, n)
+    mix = np.where(rs.rand(n) < 0.7, rs.randint(MAX_FREE + 1, 41, n), rs.randint(0, MAX_FREE + 1, n))
+    out = dict(targets_bench_rows=int(n))
+    for name, f in (("uniform", uniform), ("mix", mix)):
+        f = np.minimum(f, g.n_edges)
+        x = torch.as_tensor(random_rows(g.rows, g.cols, n, f)).to(dev)
+        ms = dict(targets=[], score=[])
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for i in range(6):
+                pi.copy_(pi0)  # the call relabels in place: every run starts from the same rows
+                z.copy_(z0)
+                for which in ("targets", "score"):
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    if which == "targets":
+                        g._ck(g._L.dbaz_exact_targets(g.h, C.c_int32(n), ptr(x), C.c_int32(2), C.c_int32(1), ptr(pi), ptr(z), ptr(n_free), ptr(mass),
+                                                      ptr(relabelled), stream))
+                    else:
+                        g._ck(g._L.dbaz_endgame_score(g.h, C.c_int32(n), ptr(x), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), stream))
+                    t1.record()
+                    t1.synchronize()
+                    if i:  # the first run warms up
+                        ms[which].append(t0.elapsed_time(t1))
+        assert np.array_equal(n_free.cpu().numpy(), f)
+        out[name + "_solvable"] = int((f <= g.max_free).sum())
+        out[name + "_relabelled"] = int(relabelled.sum().item())
+        out[name + "_targets_ms"] = round(float(np.median(ms["targets"])), 4)
+        out[name + "_score_ms"] = round(float(np.median(ms["score"])), 4)
+        out[name + "_targets_rows_per_s"] = round(n / (out[name + "_targets_ms"] * 1e-3))
+    return out
+
+
 def _selfplay_bench(a):
     """n complete self-play games with a random-init ResNetZero (noise, tree reuse: bench.py --full-games' engine), once without
     and once with the endgame tables attached: games/s, network evaluations per game, tables solved.  Each figure is the median
@@ -285,6 +379,8 @@ def main(argv=None):
     ap.add_argument("--free", type=int, default=MAX_FREE, help="free edges of every row of the first batch")
     ap.add_argument("--selfplay-bench", type=int, default=0, metavar="N",
                     help="play N complete self-play games with a random-init ResNetZero, with and without the endgame tables attached")
+    ap.add_argument("--targets-bench", type=int, default=0, metavar="N",
+                    help="time dbaz_exact_targets next to dbaz_endgame_score on N generated rows: n_free uniform in 0 .. 16, and a self-play-like mix")
     ap.add_argument("--slots", type=int, default=0, help="--selfplay-bench: engine slots (default min(N, 8192))")
     ap.add_argument("--reads", type=int, default=800, help="--selfplay-bench: mcts_num_read")
     ap.add_argument("--endgame-reads", type=int, default=0, help="--selfplay-bench: read cap of the searches the tables serve (0: none)")
@@ -298,7 +394,7 @@ def main(argv=None):
         return
     g = Endgame(a.rows, a.cols, a.device, a.max_free)
     out = dict(rows=a.rows, cols=a.cols, E=g.n_edges, max_free=g.max_free)
-    out.update(_bench(g, a.bench, a.free))
+    out.update(_targets_bench(g, a.targets_bench) if a.targets_bench > 0 else _bench(g, a.bench, a.free))
     print(json.dumps(out))
     g.close()
 

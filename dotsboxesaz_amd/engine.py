@@ -482,6 +482,17 @@ class Engine:
         self._ck(self._L.dbaz_dataset_fetch(self.h, C.c_void_p(_p(x)), C.c_void_p(_p(pi)), C.c_void_p(_p(z))))
         return x, pi, z
 
+    def dataset_exact_targets(self, endgame, pi_mode="restrict", z_mode=True):
+        """dbaz_dataset_exact_targets: the selected dataset's rows of unfinished games with at most endgame.max_free free edges
+        get their solved z and pi in place (Endgame.targets' rule and mode names); returns when done.  Returns dict(rows,
+        relabelled, finished: rows within max_free left alone because the game was over, z_changed: relabelled rows whose z
+        differed from the solved value, by_free: int64 [17], the relabelled rows per number of free edges)."""
+        from .endgame import target_modes
+        pm, zm = target_modes(pi_mode, z_mode)
+        st = np.zeros(4 + 17, dtype=np.int64)
+        self._ck(self._L.dbaz_dataset_exact_targets(self.h, endgame.h, C.c_int32(pm), C.c_int32(zm), C.c_void_p(_p(st))))
+        return dict(rows=int(st[0]), relabelled=int(st[1]), finished=int(st[2]), z_changed=int(st[3]), by_free=st[4:].copy())
+
     def dataset_batch(self, idx, sym=0):
         """Rows idx of the dataset under symmetry sym as torch CUDA tensors
         (boards float32 [n,3,H,W], pi [n,A], z [n,1]) -- written by the HIP kernel, no host copy; asynchronous, ordered on torch's

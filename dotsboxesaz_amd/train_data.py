@@ -47,9 +47,11 @@ class ReplayStore:
         self.chunks.append(dict(generation=int(generation), rows=rows, n=n, train_locs=train_locs.astype(np.int32),
                                 val_locs=np.nonzero(mask)[0].astype(np.int32)))
 
-    def dataset(self, train=True, min_generation=0, n_samples=int(1e12), pos_average=False, slot=None):
-        """slot: which of the engine's resident datasets to build into (default: 0 for train, 1 for validation)."""
-        return ReplayDataset(self, train, min_generation, n_samples, pos_average, slot)
+    def dataset(self, train=True, min_generation=0, n_samples=int(1e12), pos_average=False, slot=None, exact=None, exact_pi="restrict",
+                exact_z=True):
+        """slot: which of the engine's resident datasets to build into (default: 0 for train, 1 for validation).
+        exact: an endgame.Endgame of the board -- the finished dataset's late rows get their solved targets (ReplayDataset)."""
+        return ReplayDataset(self, train, min_generation, n_samples, pos_average, slot, exact, exact_pi, exact_z)
 
     def drop_before(self, generation):
         """Releases the rows of generations older than `generation`.  The reference's HDF file only grows; here the window lives in
@@ -63,9 +65,13 @@ class ReplayStore:
 
 class ReplayDataset:
     """utils.HDFStoreDataset over rows in HBM.  Building it runs the HIP dataset kernels; an engine
-    handle keeps up to four datasets resident (`slot`); building into a slot replaces its content."""
+    handle keeps up to four datasets resident (`slot`); building into a slot replaces its content.
+    exact: an endgame.Endgame -- right after the build the rows of unfinished games with at most exact.max_free free edges are
+    relabelled in place with the solved result (exact_z) and the moves that keep it (exact_pi: "keep", "uniform", "restrict"),
+    Engine.dataset_exact_targets; with pos_average it is the merged rows that are relabelled.  exact_stats: its counts, or None."""
 
-    def __init__(self, store, train=True, min_generation=0, n_samples=int(1e12), pos_average=False, slot=None):
+    def __init__(self, store, train=True, min_generation=0, n_samples=int(1e12), pos_average=False, slot=None, exact=None, exact_pi="restrict",
+                 exact_z=True):
         e = self.engine = store.engine
         self.slot = (0 if train else 1) if slot is None else int(slot)
         e.dataset_select(self.slot)
@@ -91,6 +97,15 @@ class ReplayDataset:
         self.n = e.dataset_finish(pos_average, order if len(order) else None)
         self.pos_average = bool(pos_average)
         self._host = None
+        self.exact_stats = self.relabel(exact, exact_pi, exact_z) if exact is not None else None
+
+    def relabel(self, endgame, pi_mode="restrict", z_mode=True):
+        """Engine.dataset_exact_targets on this dataset; the host copy behind __getitem__ is dropped with the old targets"""
+        e = self.engine
+        e.dataset_select(self.slot)
+        self._host = None
+        self.exact_stats = e.dataset_exact_targets(endgame, pi_mode, z_mode)
+        return self.exact_stats
 
     def __len__(self):
         return self.n

@@ -477,6 +477,30 @@ int dbaz_exact_policy(dbaz_endgame *g, int32_t n, const int16_t *x_dev, uint64_t
  * 2^max_free) bytes of scratch and returns only when the kernels are done (DBAZ_EDEVICE when the scratch cannot be had). */
 int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const int16_t *roots_dev, int32_t per_root, const int16_t *x_dev,
                            uint64_t pick_seed, float *p_dev, float *v_dev, float *ms_out /*[2]*/, void *stream);
+/* Exact training targets: the solved result and the result-preserving moves written over the z and pi of late rows.
+ * One row: x int16 [3*H*W], pi float32 [A], z float32.  F = its free real edges; margin, the finished-game test, D and q[a] as
+ * dbaz_endgame_score has them.  The row is left untouched, bit for bit, if F > max_free or the game is over (early end included).
+ * Otherwise v = sign(margin + D[0]) and O = { free real edges a : sign(margin + q[a]) == v }, never empty, and
+ *   z_mode 1: z = (float)v                          z_mode 0: z stays
+ *   pi_mode 0: pi stays
+ *   pi_mode 1 (uniform): pi[a] = 1.0f / |O| on O and 0.0f in every other of the A slots
+ *   pi_mode 2 (restrict): S = the float32 sum of pi[a] over O in ascending a (dbaz_endgame_score's policy_mass);
+ *                         S > 0: pi[a] = pi[a] / S on O and 0.0f elsewhere; otherwise the uniform form
+ * Side outputs per row, each pointer may be NULL: n_free = F (every row); mass = S before the relabel (0 for an untouched row
+ * and without pi_dev); relabelled = 1 for a row the rule applies to, whatever the modes.
+ * Dense rows, DEVICE pointers, QUEUED on the caller's stream; the list of rows to solve and its counters are scratch of the
+ * handle that grows on demand, so one call at a time per handle.  n == 0 is a no-op.
+ *   a mode out of range, pi_mode != 0 with pi_dev == NULL, z_mode != 0 with z_dev == NULL -> DBAZ_EINVAL
+ * (Not named dbaz_endgame_*, like dbaz_exact_policy.) */
+int dbaz_exact_targets(dbaz_endgame *g, int32_t n, const int16_t *x_dev, int32_t pi_mode, int32_t z_mode, float *pi_dev /*in/out [n][A]*/,
+                       float *z_dev /*in/out [n]*/, int16_t *n_free_dev, float *mass_dev, uint8_t *relabelled_dev, void *stream);
+/* The same rule over the selected resident dataset (dbaz_dataset_select / dbaz_dataset_finish), in place, on the handle's stream;
+ * returns when done.  Later dbaz_dataset_fetch / dbaz_dataset_batch calls read the relabelled arrays; with pos_average the merged
+ * rows are relabelled (the targets are a function of the features alone).  stats_host (may be NULL) int64 [4 + 17]: rows in the
+ * dataset, rows relabelled, rows with F <= max_free left alone because the game was over, relabelled rows whose z before
+ * differed from v, then the relabelled rows per F = 0 .. 16.
+ *   no finished dataset in the slot -> DBAZ_ESTATE;  g of another board size or device, a mode out of range -> DBAZ_EINVAL */
+int dbaz_dataset_exact_targets(dbaz_engine *e, dbaz_endgame *g, int32_t pi_mode, int32_t z_mode, int64_t *stats_host);
 /* The endgame solver inside the search: once a search ROOT of a slot has F0 <= max_free free edges, every later
  * position of that game is a subset of those edges.  The engine solves the root's subgame once, keeps the 2^F0-byte table in the
  * slot's region in HBM (n_slots x max(16, 2^max_free) bytes, allocated by the first attach: 8 192 slots x 64 KB = 512 MiB) and
