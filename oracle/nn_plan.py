@@ -83,13 +83,20 @@ class Plan:
         self.rows, self.cols, self.H, self.W, self.HW = rows, cols, H, W, HW
         self.C, self.precision, self.cus = C, precision, cus
 
-        def lds_bytes(S):
+        def lds_parts(S):
+            """floats: one image, what conv0 stages in the idle image, what the head phase keeps there"""
             s4 = (C + 8) // 4
             img = (((S * HW * s4 + 15) & ~15) + 3 * s4) * 4
             need0 = S * 3 * (H + 2) * (W + 2) + 27 * C
             nj = (A + 15) // 16 + (vf + 15) // 16
             need1 = 2 * hc * (C + 4) + S * 2 * hc * HW + 16 + S * (nj * 16 + 1)
+            return img, need0, need1
+
+        def lds_bytes(S):
+            img, need0, need1 = lds_parts(S)
             return (img + max(img, need0, need1)) * 4
+
+        self.lds_parts = lds_parts
 
         S = min(MAXS, max(1, 16 * MAXT // HW))
         while S > 1 and lds_bytes(S) > LDS_BUDGET:
