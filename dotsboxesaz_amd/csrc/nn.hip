@@ -261,6 +261,9 @@ __device__ __forceinline__ void h3_store(_Float16 *ph, bool valid, f32x4 v)
     }
 }
 
+// words per wave of stamp_out: 0-4 the layer phases, 5-8 the workgroup's phases and its clock, 10-12 the step ends of
+// conv_lds_h3_c2 (DMA wait, step barrier, and the cost of one stamp, each summed over the layers)
+#define STAMP_WORDS 16
 #ifdef DBAZ_STAMP
 // diagnostic build only (never shipped): per-wave cycle sums of the layer phases
 #define STAMP(var)                                                                      \
@@ -464,6 +467,26 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) char *)p;
 }
+// s_waitcnt vmcnt(vm) [lgkmcnt(LG), LG >= 0] with vm a constant of the unrolled K-loop (the immediates must be literal)
+template <int VM, int LG>
+__device__ __forceinline__ void wait_vm_lgkm()
+{
+    if constexpr (LG < 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(VM), "n"(LG) : "memory");
+}
+template <int LG>
+__device__ __forceinline__ void wait_step(int vm)
+{
+    switch (vm) {
+    case 0: wait_vm_lgkm<0, LG>(); break;
+    case 1: wait_vm_lgkm<1, LG>(); break;
+    case 2: wait_vm_lgkm<2, LG>(); break;
+    case 3: wait_vm_lgkm<3, LG>(); break;
+    case 4: wait_vm_lgkm<4, LG>(); break;
+    case 5: wait_vm_lgkm<5, LG>(); break;
+    default: wait_vm_lgkm<6, LG>(); break; // DBAZ_RING_P <= 8
+    }
+}
 // PAT: the taps this wave pair's tiles 0 and 1 never need (tower_perm.h: under the row table every real row of such a tile lies on
 // one border of the board, so three of its taps read nothing but the zero region).  A dropped (tile, tap) issues no MFMA, no
 // fragment address and no fragment read -- compile-time, because the counted wait at the end of a step must name the number of
@@ -482,6 +505,30 @@ static_assert(pat_drop(0, 0) == TP_TOP && pat_drop(0, 1) == TP_LEFT && pat_drop(
               pat_drop(2, 0) == TP_BOTTOM && pat_drop(2, 1) == TP_RIGHT && pat_drop(3, 0) == TP_BOTTOM && pat_drop(3, 1) == TP_LEFT,
               "the kernel's patterns are those the row table is built and verified for (tower_perm.h)");
 
+// The deep weight ring.  The two slots behind the images give the DMA of step i + 2 ONE K-step to land (issued at the start of
+// step i, awaited at its end), and a K-step (384 ... 768 cycles of MFMA issue per SIMD) is about what an Infinity-Cache hit
+// takes.  The room for more slots is the layer's DESTINATION image: the residual stream is in registers, so nothing reads that
+// image between the layer barrier and the epilogue, which rewrites every data column of every valid row (rows behind them and
+// the two pad units of a row are never read).  Steps 2 .. N - 1 of a layer therefore stream through NS = P slots at the start
+// of dst4, P = prefetch distance; steps 0 and 1 stay in the two slots behind the images, which are filled during the PREVIOUS
+// layer (its image is this layer's source until the layer barrier, so nothing of this layer may be issued into it earlier).
+#ifndef DBAZ_RING_P
+#define DBAZ_RING_P 3 // 2: the two-slot ring alone; 3 measured best, 4 and 6 a little behind it (EXPERIMENTS.md 1)
+#endif
+static_assert(DBAZ_RING_P >= 2 && DBAZ_RING_P <= 8, "prefetch distance");
+// slots a body of ntt tiles per wave pair keeps in its destination image: tower_plan_build picks that body for more than
+// 64 * (ntt - 1) rows (NT_c2 = ceil(ceil(rows / 16) / 4)), and the slots must end inside those rows -- before the zero region,
+// which starts behind S * HW rows.  Fewer than 3 slots: 0, the two-slot ring as it was (nn_commit checks the rows again).
+__host__ __device__ constexpr int wring_deep_slots(int ntt)
+{
+    const int units = (64 * (ntt - 1) + 1) * ((64 + 8) / 4);
+    int p = DBAZ_RING_P;
+    while (p > 2 && p * WRING_UNITS > units) p--;
+    return p > 2 ? p : 0;
+}
+static_assert(DBAZ_RING_P != 3 || (wring_deep_slots(4) == 3 && wring_deep_slots(3) == 3 && wring_deep_slots(2) == 0 && wring_deep_slots(1) == 0),
+              "4 and 3 tiles per wave pair hold the three slots, the smaller bodies keep the two-slot ring");
+
 template <int C, int NTT, int PAT = PAT_NONE>
 __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
                                                const float *__restrict__ bias, float oscale, const int *vm, int rowbase,
@@ -491,9 +538,12 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
 {
     constexpr bool PERM = PAT != PAT_NONE;
     static_assert(!PERM || NTT == 4, "the row table is built for 4 tiles per wave pair");
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    (void)t0; (void)t1; (void)t2; (void)t3; (void)stamps;
+    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, ua = 0, uc = 0, ud = 0;
+    (void)t0; (void)t1; (void)t2; (void)t3; (void)ua; (void)uc; (void)ud; (void)stamps;
+    unsigned w_dma = 0, w_bar = 0, w_cal = 0; // (32-bit sums: eight more 64-bit ones spilled SGPRs into scratch inside the K-loop)
+    (void)w_dma; (void)w_bar; (void)w_cal;
     static_assert(C == 64, "two cout tiles per wave x two wave parities = 64 channels");
+    constexpr int NS = wring_deep_slots(NTT); // slots of the deep ring at the start of dst4 (0: the two-slot ring alone)
     constexpr int S4 = (C + 8) / 4;  // 16-byte units per LDS row
     constexpr int KS = C / 32;       // K=32 steps per tap
     constexpr int LO = C / 8;        // unit offset of the lo halves inside a row
@@ -537,13 +587,26 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         }
     };
     set_ab(0);
+    STAMP(ua); // (two stamps back to back: what one stamp costs, to be taken off the step-end figures below)
     STAMP(t0);
+#ifdef DBAZ_STAMP
+    w_cal = (unsigned)(t0 - ua);
+#endif
     // this wave's DMA piece of a step = fragment (cout tile wave >> 1, hi | lo = wave & 1); the fragments it consumes are those
     // of cout tiles ct0, ct0 + 1: ring units (ct * 2 + hl) * 64 + lane of slot (step & 1)
     const f32x4 *dsrc = wpk + ((size_t)(wave >> 1) * N * 2 + (wave & 1)) * 64 + lane;
     const f32x4 *dnext = next_wpk ? next_wpk + ((size_t)(wave >> 1) * N * 2 + (wave & 1)) * 64 + lane : nullptr;
     const f32x4 *rsrc = wring + (size_t)ct0 * 2 * 64 + lane;
     const unsigned ring_dst = __builtin_amdgcn_readfirstlane(lds_addr(wring + (size_t)wave * 64));
+    // deep ring: the same pieces and fragments, slot (step % NS) of the destination image.  The two slots behind the images are
+    // refilled in EVERY layer, the last one fetching its own steps 0 and 1 again for nobody, so that the DMAs in flight at a
+    // step's end, and with them the counted waits, are the same in all layers
+    const f32x4 *dnx = (next_wpk ? next_wpk : wpk) + ((size_t)(wave >> 1) * N * 2 + (wave & 1)) * 64 + lane;
+    const f32x4 *rsrc_i = dst4 + (size_t)ct0 * 2 * 64 + lane;
+    const unsigned ring_dst_i = __builtin_amdgcn_readfirstlane(lds_addr(dst4 + (size_t)wave * 64));
+    (void)dnx; (void)rsrc_i; (void)ring_dst_i; (void)dnext;
+    static_assert(NS == 0 || (NS >= 3 && N - NS >= 1 && NS * WRING_UNITS <= (64 * (NTT - 1) + 1) * S4),
+                  "the slots end inside the rows every workgroup of this body has; the next layer's steps 0 and 1 are issued from step 1 on");
     // step 0's fragments were taken out of slot 0 BEFORE the layer barrier (below / tower_group's prologue): step 0 refills
     // that slot at once, and a wave late out of the barrier must not find another wave's DMA there
 #pragma unroll
@@ -561,10 +624,23 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         const int tap = i / KS, ni = i + 1, ntap = ni / KS, nks = ni % KS;
         // step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the last barrier); behind the
         // layer's last steps: the first two steps of the next layer
-        if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-        else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-        if (ni < N) { // step i + 1's fragments out of slot (i + 1) & 1 (landed and fenced by the barrier that ended step i - 1)
-            const f32x4 *r1 = rsrc + (size_t)(ni & 1) * WRING_UNITS;
+        if constexpr (NS == 0) {
+            if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
+            else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
+        } else {
+            // deep ring: step i + NS's piece -> slot i % NS of the destination image.  Its last occupant, step i, was read into
+            // registers at the start of step i - 1 and fenced by that step's barrier; in steps 0 and 1 it had none in this layer,
+            // and the image's readers of the previous layer are behind the layer barrier.  Step 0 also issues steps 2 .. NS - 1,
+            // which could not go out earlier for that reason.  Behind the layer's last step: steps 0 and 1 of the next layer
+            // into the two slots behind the images (free since the barrier of step 0), nothing in the steps after that.
+            if (i == 0)
+#pragma unroll
+                for (int j = 2; j < NS; j++) glds16(dsrc + (size_t)j * 128, ring_dst_i + j * (WRING_UNITS * 16));
+            if (i + NS < N) glds16(dsrc + (size_t)(i + NS) * 128, ring_dst_i + (i % NS) * (WRING_UNITS * 16));
+            else if (i + NS - N < 2) glds16(dnx + (size_t)(i + NS - N) * 128, ring_dst + (i + NS - N) * (WRING_UNITS * 16));
+        }
+        if (ni < N) { // step i + 1's fragments out of its slot (landed and fenced by the barrier that ended step i - 1)
+            const f32x4 *r1 = NS > 0 && ni >= 2 ? rsrc_i + (size_t)(ni % NS) * WRING_UNITS : rsrc + (size_t)(ni & 1) * WRING_UNITS;
             a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -600,13 +676,47 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         // end of step i: this wave's DMA piece has landed (vmcnt) and its ring reads of step i + 1 have returned (LDS returns in
         // order; only the activation reads issued after them -- two per tile that keeps the next step's tap -- may still be
         // out) -- then every wave's have
-        if (ni >= N) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n_kept(ntap) == NTT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
-        else if (n_kept(ntap) == NTT - 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT - 2) : "memory");
-        else if (n_kept(ntap) == NTT - 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT > 4 ? 2 * NTT - 4 : 0) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (no pattern drops more than two tiles at a tap)
+        // (stamped build: ua = the last MFMA is issued, ua -> uc = the return from the step-end wait, uc -> ud = from the step
+        // barrier, each with the cost of one stamp on top; a stamp drains lgkmcnt itself, so the first holds the LDS reads too)
+        STAMP(ua);
+        if constexpr (NS == 0) {
+            if (ni >= N) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else if (n_kept(ntap) == NTT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
+            else if (n_kept(ntap) == NTT - 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT - 2) : "memory");
+            else if (n_kept(ntap) == NTT - 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT > 4 ? 2 * NTT - 4 : 0) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (no pattern drops more than two tiles at a tap)
+        } else {
+            // deep ring: the DMAs are the only vector-memory instructions of a wave inside the K-loop and land in the order of
+            // their issue, so vmcnt(k) = "all but the k youngest have landed".  What has to have landed at the end of step i is
+            // the piece the NEXT step reads into registers: step i + 2, or the next layer's step 0 (taken into pre behind the
+            // loop, so fenced by the barrier of step N - 2) and step 1 (read behind the layer barrier).  n0, n1 = those two:
+            //
+            //   step i             issues         in flight at its end, oldest first     must have landed   vmcnt
+            //   0                  2 .. NS        2 .. NS                                2                  NS - 2
+            //   1 .. N-NS-1        i + NS         i+2 .. i+NS                            i + 2              NS - 2
+            //   N-NS               n0             N-NS+2 .. N-1, n0                      N-NS+2             NS - 2
+            //   N-NS+1             n1             N-NS+3 .. N-1, n0, n1                  N-NS+3             NS - 2
+            //   N-NS+k, k >= 2     --             N-NS+k+2 .. N-1, n0, n1                N-NS+k+2           NS - 1 - k
+            //   N-2                --             n0, n1                                 n0                 1
+            //   N-1                --             n1                                     n1                 0
+            //
+            // (rows 4 and 5 with N-NS+k+2 > N-1 are the last two; every count is min(NS - 2, N - 1 - i), and vmcnt is 0 at the
+            // start of a layer: the last step waits for everything, tower_group's prologue too)
+            const int vmw = NS - 2 < N - 1 - i ? NS - 2 : N - 1 - i;
+            if (ni >= N) wait_step<-1>(vmw);
+            else if (n_kept(ntap) == NTT) wait_step<2 * NTT>(vmw);
+            else if (n_kept(ntap) == NTT - 1) wait_step<2 * NTT - 2>(vmw);
+            else if (n_kept(ntap) == NTT - 2) wait_step<(2 * NTT > 4 ? 2 * NTT - 4 : 0)>(vmw);
+            else wait_step<0>(vmw);
+        }
+        STAMP(uc);
         if (ni < N) __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
+        STAMP(ud);
+#ifdef DBAZ_STAMP
+        w_dma += (unsigned)(uc - ua);
+        if (ni < N) w_bar += (unsigned)(ud - uc);
+#endif
     }
     STAMP(t2);
     f32x4 bv[2];
@@ -646,7 +756,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     ovf_out |= vmax > F16_GUARD;
     STAMP(t3);
 #ifdef DBAZ_STAMP
-    if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; }
+    if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; stamps[4] += w_dma; stamps[5] += w_bar; stamps[6] += w_cal; }
 #endif
 }
 
@@ -968,7 +1078,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         if constexpr (!C2) {
             if (NL > 0) wpre_load<C>(pre, tw4, wave, lane);
         }
-        unsigned long long stamps[4] = {0, 0, 0, 0};
+        unsigned long long stamps[7] = {0, 0, 0, 0, 0, 0, 0};
         unsigned long long tb0 = 0, tb1 = 0, tk0 = 0, tk1 = 0;
         (void)tb0; (void)tb1; (void)tk0; (void)tk1;
         f32x4 res[2][NTA]; // the residual stream of this wave's outputs (activation-scaled f32): conv_lds_h3_c2 / conv_lds_h3
@@ -1046,8 +1156,9 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         STAMP(tk1);
         tL1 = tk1;
         if (a.stamp_out && lane == 0) {
-            unsigned long long *o = a.stamp_out + ((size_t)blockIdx.x * 8 + wave) * 10;
+            unsigned long long *o = a.stamp_out + ((size_t)blockIdx.x * 8 + wave) * STAMP_WORDS;
             o[0] = stamps[0]; o[1] = stamps[1]; o[2] = stamps[2]; o[3] = stamps[3]; o[4] = tk1 - tk0;
+            o[10] = stamps[4]; o[11] = stamps[5]; o[12] = stamps[6];
         }
 #endif
     }
@@ -1141,7 +1252,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
 #ifdef DBAZ_STAMP
     STAMP(tE1);
     if (PREC == 1 && a.stamp_out && lane == 0) {
-        unsigned long long *o = a.stamp_out + ((size_t)blockIdx.x * 8 + wave) * 10;
+        unsigned long long *o = a.stamp_out + ((size_t)blockIdx.x * 8 + wave) * STAMP_WORDS;
         o[5] = tL0 - tE0; // conv0 phase (staging, VALU conv, zero regions)
         o[6] = tE1 - tL1; // head conv1x1 phase + output
         o[7] = tE1 - tE0; // whole workgroup
@@ -1992,8 +2103,8 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
         if (!nn->tw || !nn->tb || !nn->tosc || !nn->overflow) { err = "hipMalloc failed (tower weights)"; return DBAZ_EDEVICE; }
         (void)hipMemset(nn->overflow, 0, 16);
 #ifdef DBAZ_STAMP
-        nn->stamp_out = nn_alloc<unsigned long long>(nn, (size_t)nn->max_batch * 8 * 10);
-        (void)hipMemset(nn->stamp_out, 0, (size_t)nn->max_batch * 8 * 10 * 8);
+        nn->stamp_out = nn_alloc<unsigned long long>(nn, (size_t)nn->max_batch * 8 * STAMP_WORDS);
+        (void)hipMemset(nn->stamp_out, 0, (size_t)nn->max_batch * 8 * STAMP_WORDS * 8);
 #endif
     }
     // heads: conv1x1 + BN folded, rows [policy hc | value hc]
@@ -2069,6 +2180,11 @@ int nn_commit(NNState *nn, hipStream_t s, std::string &err)
     // two cout tiles per wave (default for 64 channels) for the FULL rounds; what is left behind the last full round goes
     // to one round of the one-cout-tile kernels, whose workgroups come in finer sizes (1, 2, 3 samples, or all S of them
     // as role 4) -- or stays with this launch if it is more than such a round holds
+    // (the deep weight ring of that body lies inside the rows of its destination image: wring_deep_slots)
+    if (tp.c2 && (size_t)wring_deep_slots(tp.NT_c2) * WRING_UNITS > (size_t)tp.S_c2 * g.HW * ((C + 8) / 4)) {
+        err = "the weight ring does not fit the activation image";
+        return DBAZ_EINVAL;
+    }
     if (tp.c2) L.push_back({tower_kernel_c2(tp.NT_c2), tp.conv_lds_c2, 0, tp.S_main(), TowerLaunch::PER_GROUP, false});
     else L.push_back({tower_kernel(C, tp.NTT, nn->precision), tp.conv_lds, 0, tp.S_main(), TowerLaunch::PER_GROUP, false});
     if (tp.use_rem) { // the remainder sizes in one launch (the workgroups pick theirs; TowerArgs::S stays the main launch's)
@@ -2177,7 +2293,7 @@ double nn_flops_per_sample(const NNState *nn)
 int nn_read_stamps(NNState *nn, unsigned long long *out, int n_wg)
 {
     if (!nn || !nn->stamp_out) return -1;
-    return (int)hipMemcpy(out, nn->stamp_out, (size_t)n_wg * 8 * 10 * 8, hipMemcpyDeviceToHost);
+    return (int)hipMemcpy(out, nn->stamp_out, (size_t)n_wg * 8 * STAMP_WORDS * 8, hipMemcpyDeviceToHost);
 }
 
 // f16x3 mode, networks WITHOUT the exact-f32 safety net (SimpleNN; ResNetZero narrower than 32 channels never runs

@@ -1,13 +1,16 @@
 #!/bin/bash
 # Diagnostic build of the library with in-kernel cycle stamps in nn.hip and train.hip (k_conv_t; train_net.hip shares the handle's layout) (-DDBAZ_STAMP), into build/stamp/ (not shipped,
 # git-ignored; it travels to the GPU box with the snapshot).  Use with DBAZ_LIB=$PWD/build/stamp/libdbaz_hip.so.
+# RING_P=2 tools/build_stamp.sh: the same with the two-slot weight ring alone (-DDBAZ_RING_P=2), into build/stamp_p2/.
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p build/stamp
+out=build/stamp${RING_P:+_p$RING_P}
+mkdir -p $out
 python -m dotsboxesaz_amd.build > /dev/null
 for f in engine nn train train_net; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DDBAZ_STAMP -c dotsboxesaz_amd/csrc/$f.hip -o build/stamp/$f.o &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DDBAZ_STAMP ${RING_P:+-DDBAZ_RING_P=$RING_P} -c dotsboxesaz_amd/csrc/$f.hip -o $out/$f.o &
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/stamp/libdbaz_hip.so dotsboxesaz_amd/csrc/tree.o build/stamp/engine.o build/stamp/nn.o dotsboxesaz_amd/csrc/replay.o build/stamp/train.o build/stamp/train_net.o dotsboxesaz_amd/csrc/buildinfo.o
-echo build/stamp/libdbaz_hip.so
+c=dotsboxesaz_amd/csrc
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libdbaz_hip.so $c/tree.o $out/engine.o $out/nn.o $c/replay.o $out/train.o $out/train_net.o $c/solver.o $c/endgame.o $c/buildinfo.o
+echo $out/libdbaz_hip.so
