@@ -47,7 +47,7 @@ def source_hash(only=None):
     return h.hexdigest()[:16]
 
 
-NN_SOURCES = ("nn.hip", "nn.h", "common.h", "tower_perm.h", "tower_plan.h")
+NN_SOURCES = ("nn.hip", "nn.h", "common.h", "h3_split.h", "tower_perm.h", "tower_plan.h")
 
 
 def _newer(target, deps):

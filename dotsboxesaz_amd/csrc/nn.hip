@@ -39,6 +39,7 @@
 #include <string>
 #include <vector>
 
+#include "h3_split.h"
 #include "nn.h"
 #include "tower_perm.h"
 #include "tower_plan.h"
@@ -197,9 +198,7 @@ __device__ __forceinline__ void conv_lds_f32(const f32x4 *__restrict__ src4, f32
 // [C halves hi | C halves lo | 32 B pad] = (C+8) dwords.
 // ------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// (f16x2, f32x2, u32x2: h3_split.h)
 #define ACT_SHIFT 5
 #define ACT_SCALE 32.0f
 #define F16_GUARD 60000.0f
@@ -240,24 +239,24 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v)
     return v;
 }
 __device__ __forceinline__ float max4(f32x4 v) { return fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])); }
+// the running guard maximum as two v_max3_f32 (the same maximum: v comes out of relu4, no NaN among the operands)
+__device__ __forceinline__ float max_acc(float m, f32x4 v) { return fmaxf(fmaxf(fmaxf(fmaxf(m, v[0]), v[1]), v[2]), v[3]); }
+// compile-time flag of a generic lambda (conv_lds_h3_c2's epilogue with and without the residual)
+template <bool B> struct Flag { static constexpr bool value = B; };
 
-// 4 consecutive couts of one image row, activation-scaled: hi = rn_f16(v), lo = rn_f16(v - hi) on packed pairs
-// (v_cvt_pk_f16_f32 / v_pk_add_f32); the hi halves go to ph, the lo halves to ph + C, as two 8-byte stores (!valid: a row
-// behind the workgroup's last, nothing is written)
-template <int C>
+// 4 consecutive couts of one image row, activation-scaled: hi = rn_f16(v), lo = rn_f16(v - hi) (h3_split.h); the hi halves go
+// to ph, the lo halves to ph + C, as two 8-byte stores (!valid: a row behind the workgroup's last, nothing is written).
+// MIX: lo by v_fma_mixlo_f16 / v_fma_mixhi_f16 (conv_lds_h3_c2's epilogue, where it pays); otherwise the two-rounding spelling:
+// the one-cout-tile bodies measured no faster with the mix form.  The same bits either way (tests/test_hip_h3_split.py).
+template <int C, bool MIX = false>
 __device__ __forceinline__ void h3_store(_Float16 *ph, bool valid, f32x4 v)
 {
-    union { f16x2 h[2]; u32x2 u; } oh, ol;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const f32x2 x = {v[2 * q], v[2 * q + 1]};
-        const f16x2 h = __builtin_convertvector(x, f16x2);
-        oh.h[q] = h;
-        ol.h[q] = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), f16x2);
-    }
+    u32x2 hi, lo;
+    if constexpr (MIX) h3_split(v, hi, lo);
+    else h3_split_ref(v, hi, lo);
     if (valid) {
-        *reinterpret_cast<u32x2 *>(ph) = oh.u;
-        *reinterpret_cast<u32x2 *>(ph + C) = ol.u;
+        *reinterpret_cast<u32x2 *>(ph) = hi;
+        *reinterpret_cast<u32x2 *>(ph + C) = lo;
     }
 }
 
@@ -559,20 +558,21 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     // register sets of the weight fragments of steps i (i & 1) and i + 1 ((i + 1) & 1), fed from the LDS ring
     u128h a_h[2][2], a_l[2][2];
     u128h bh[NTT], bl[NTT];
+    f32x4 bv[2];
+    constexpr int BSTEP = NS > 0 ? N - 2 : N - 1; // the step that loads bv
     const char *sb = reinterpret_cast<const char *>(src4);
     int ab[NTT];
-    // 16-byte unit of this lane's fragment of tile 0 for a tap at row offset offr (the tile constant t*16*S4 is an immediate)
-    auto tap_unit = [&](int offr) -> int { return rowbase + offr * S4; };
-    // PERM: a tile's rows are wherever the table put them, so every tile has its own unit (and no tile immediate)
+    // 16-byte unit of this lane's fragment for a tap: rowbase + the tap's offset for tile 0 (the tile constant t*16*S4 is an
+    // immediate); PERM: a tile's rows are wherever the table put them, so every tile has its own unit (and no tile immediate)
     auto kept = [](int t, int tap) constexpr -> bool { return !((pat_drop(PAT, t) >> tap) & 1); };
     auto n_kept = [&](int tap) constexpr -> int { int n = 0; for (int t = 0; t < NTT; t++) n += kept(t, tap) ? 1 : 0; return n; };
     auto tile_off = [](int t) constexpr -> int { return PERM ? 0 : t * 256 * S4; };
     auto set_ab = [&](int tap) {
+        // (the addresses are the same in every layer: kept opaque, or hipcc computes all 36 ahead of the layer loop and parks
+        // them in scratch -- with or without the row table)
+        int offu = ((tap / 3 - 1) * W + (tap % 3 - 1)) * S4;
+        asm volatile("" : "+s"(offu));
         if constexpr (PERM) {
-            // (the addresses are the same in every layer: kept opaque, or hipcc computes all 36 ahead of the layer loop and
-            // parks them in scratch)
-            int offu = ((tap / 3 - 1) * W + (tap % 3 - 1)) * S4;
-            asm volatile("" : "+s"(offu));
 #pragma unroll
             for (int t = 0; t < NTT; t++)
                 if (kept(t, tap)) {
@@ -580,7 +580,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
                     ab[t] = (((vm[t] >> tap) & 1) ? un : zbase + (un & 15)) * 16;
                 }
         } else {
-            const int un = tap_unit((tap / 3 - 1) * W + (tap % 3 - 1));
+            const int un = rowbase + offu;
             const int zt = zbase + (un & 15);
 #pragma unroll
             for (int t = 0; t < NTT; t++) ab[t] = (((vm[t] >> tap) & 1) ? un : zt - t * 16 * S4) * 16;
@@ -639,6 +639,13 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             if (i + NS < N) glds16(dsrc + (size_t)(i + NS) * 128, ring_dst_i + (i % NS) * (WRING_UNITS * 16));
             else if (i + NS - N < 2) glds16(dnx + (size_t)(i + NS - N) * 128, ring_dst + (i + NS - N) * (WRING_UNITS * 16));
         }
+        // the epilogue's bias (b0, b1: this lane's 4 couts of its two cout tiles), both loads back to back BEHIND the step's DMA,
+        // two steps (deep ring) or one step (two-slot ring) before the epilogue needs them: no L2 round trip behind the last MFMA
+        if (i == BSTEP) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < 2; c++) bv[c] = *reinterpret_cast<const f32x4 *>(bias + (ct0 + c) * 16 + gq * 4);
+        }
         if (ni < N) { // step i + 1's fragments out of its slot (landed and fenced by the barrier that ended step i - 1)
             const f32x4 *r1 = NS > 0 && ni >= 2 ? rsrc_i + (size_t)(ni % NS) * WRING_UNITS : rsrc + (size_t)(ni & 1) * WRING_UNITS;
             a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];
@@ -686,10 +693,11 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             else if (n_kept(ntap) == NTT - 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT > 4 ? 2 * NTT - 4 : 0) : "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (no pattern drops more than two tiles at a tap)
         } else {
-            // deep ring: the DMAs are the only vector-memory instructions of a wave inside the K-loop and land in the order of
-            // their issue, so vmcnt(k) = "all but the k youngest have landed".  What has to have landed at the end of step i is
-            // the piece the NEXT step reads into registers: step i + 2, or the next layer's step 0 (taken into pre behind the
-            // loop, so fenced by the barrier of step N - 2) and step 1 (read behind the layer barrier).  n0, n1 = those two:
+            // deep ring: the DMAs and the two bias loads of step N - 2 are the only vector-memory instructions of a wave inside
+            // the K-loop and return in the order of their issue, so vmcnt(k) = "all but the k youngest have landed".  What has to
+            // have landed at the end of step i is the piece the NEXT step reads into registers: step i + 2, or the next layer's
+            // step 0 (taken into pre behind the loop, so fenced by the barrier of step N - 2) and step 1 (read behind the layer
+            // barrier).  n0, n1 = those two:
             //
             //   step i             issues         in flight at its end, oldest first     must have landed   vmcnt
             //   0                  2 .. NS        2 .. NS                                2                  NS - 2
@@ -697,12 +705,14 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             //   N-NS               n0             N-NS+2 .. N-1, n0                      N-NS+2             NS - 2
             //   N-NS+1             n1             N-NS+3 .. N-1, n0, n1                  N-NS+3             NS - 2
             //   N-NS+k, k >= 2     --             N-NS+k+2 .. N-1, n0, n1                N-NS+k+2           NS - 1 - k
-            //   N-2                --             n0, n1                                 n0                 1
-            //   N-1                --             n1                                     n1                 0
+            //   N-2                b0, b1         n0, n1, b0, b1                         n0                 3
+            //   N-1                --             n1, b0, b1                             n1, b0, b1         0
             //
-            // (rows 4 and 5 with N-NS+k+2 > N-1 are the last two; every count is min(NS - 2, N - 1 - i), and vmcnt is 0 at the
-            // start of a layer: the last step waits for everything, tower_group's prologue too)
-            const int vmw = NS - 2 < N - 1 - i ? NS - 2 : N - 1 - i;
+            // (rows 4 and 5 with N-NS+k+2 > N-1 are the last two; b0, b1 = the two bias loads of step N - 2, issued behind its
+            // DMA (at NS = 3 that is n1; at NS > 3 the step issues nothing else), which leave two more loads out behind n0;
+            // every count is min(NS - 2, N - 1 - i), + 2 in step N - 2, and vmcnt is 0 at the start of a layer: the last step
+            // waits for everything, tower_group's prologue too)
+            const int vmw = (NS - 2 < N - 1 - i ? NS - 2 : N - 1 - i) + (i == BSTEP ? 2 : 0);
             if (ni >= N) wait_step<-1>(vmw);
             else if (n_kept(ntap) == NTT) wait_step<2 * NTT>(vmw);
             else if (n_kept(ntap) == NTT - 1) wait_step<2 * NTT - 2>(vmw);
@@ -719,13 +729,6 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
 #endif
     }
     STAMP(t2);
-    f32x4 bv[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        bv[c] = *reinterpret_cast<const f32x4 *>(bias + (ct0 + c) * 16 + gq * 4);
-        asm volatile("" ::"v"(bv[c]));
-    }
-    __builtin_amdgcn_sched_barrier(0);
     if (next_wpk) {
         // the next layer's step 0 (slot 0: DMAed in step N - 2, fenced by that step's barrier) into registers before the layer barrier
         pre[0].h0 = rsrc[0]; pre[0].l0 = rsrc[64]; pre[1].h0 = rsrc[128]; pre[1].l0 = rsrc[192];
@@ -734,26 +737,33 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     // ---- epilogue (as conv_lds_h3): lane holds couts (ct0 + c) * 16 + 4 gq .. +3 of position row (tbase + t) * 16 + jrow
     // (PERM: of the table's row, unit rb[t] - gq; the centre tap of a row is inside the image, so vm[t] != 0 <=> row < R)
     _Float16 *dsth = reinterpret_cast<_Float16 *>(dst4);
-    float vmax = 0.0f;
+    // one of two straight epilogues under ONE wave-uniform branch on the layer's parity: a runtime `if (residual)` per tile
+    // became selects between v and v + res, and the add ran on the layers without a residual too
+    auto epi = [&](auto res_flag) {
+        constexpr bool RES = decltype(res_flag)::value; // the second layer of a block
+        float vmax = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int col = (ct0 + c) * 16 + gq * 4; // column (in halves) of this lane's 4 couts inside a row
+        for (int c = 0; c < 2; c++) {
+            const int col = (ct0 + c) * 16 + gq * 4; // column (in halves) of this lane's 4 couts inside a row
 #pragma unroll
-        for (int t = 0; t < NTT; t++) {
-            f32x4 v = acc[c][t] * oscale + bv[c];
-            if (residual) v += res[c][t];
-            v = relu4(v);
-            if (residual) res[c][t] = v; // the block's output = the next block's residual input
-            vmax = fmaxf(vmax, max4(v));
-            if constexpr (PERM) {
-                h3_store<C>(dsth + (rb[t] - gq) * 8 + col, vm[t] != 0, v);
-            } else {
-                const int row = (tbase + t) * 16 + jrow;
-                h3_store<C>(dsth + (size_t)row * (S4 * 8) + col, row < R, v);
+            for (int t = 0; t < NTT; t++) {
+                f32x4 v = acc[c][t] * oscale + bv[c];
+                if constexpr (RES) v += res[c][t];
+                v = relu4(v);
+                if constexpr (RES) res[c][t] = v; // the block's output = the next block's residual input
+                vmax = max_acc(vmax, v);
+                if constexpr (PERM) {
+                    h3_store<C, true>(dsth + (rb[t] - gq) * 8 + col, vm[t] != 0, v);
+                } else {
+                    const int row = (tbase + t) * 16 + jrow;
+                    h3_store<C, true>(dsth + (size_t)row * (S4 * 8) + col, row < R, v);
+                }
             }
         }
-    }
-    ovf_out |= vmax > F16_GUARD;
+        ovf_out |= vmax > F16_GUARD;
+    };
+    if (residual) epi(Flag<true>{});
+    else epi(Flag<false>{});
     STAMP(t3);
 #ifdef DBAZ_STAMP
     if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; stamps[4] += w_dma; stamps[5] += w_bar; stamps[6] += w_cal; }
