@@ -20,6 +20,7 @@
 // Every f32 operand of k_conv_t is an error-compensated (hi, lo) pair of halves scaled by a power of two taken from the
 // tensor's own maximum (tracked by the kernel that produced it), so gradients of any magnitude keep f32-grade products.
 #include "train.h"
+#include "train_reduce.h"
 
 static thread_local std::string g_train_error; // message of a failed dbaz_trainer_create / dbaz_bn2d_* call; per thread
 
@@ -369,7 +370,7 @@ __global__ void __launch_bounds__(TT, 4) k_conv_t(ConvArgs a)
         f32x4 *out4 = reinterpret_cast<f32x4 *>(a.out) + g0;
         // column sums in f64 beside the store: (out, out^2) for the forward convs -- BatchNorm's batch statistics -- or, for the
         // input-gradient convs, (g, g * yhat) of the NEXT layer down (g = out where that layer's ReLU let the value through):
-        // what k_bn_stats / k_bn_bwd_sums read the tensor again for (9.8 and 20.3 us per layer)
+        // what a statistics pass of its own / k_bn_bwd_sums read the tensor again for (9.8 and 20.3 us per layer)
         double st[2][4] = {};
         f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = mu;
         if (a.bs_part) {
@@ -456,49 +457,9 @@ __global__ void __launch_bounds__(TT, 4) k_conv_t(ConvArgs a)
 
 // ------------------------------------------------------------------------------------
 // column sums over the rows of [M][C] tensors, f64: the workgroup's 512 threads = 32 row lanes x 16 channel quads write one
-// partial row per workgroup; the *_fin kernels (colsum_total) add the rows up.
+// partial row per workgroup (colsum_store<K, 16, TT>); the *_fin kernels, one workgroup per channel, add the rows up
+// (train_reduce.h).
 // ------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void block_colsum_store(double (&s)[K][4], double *part /*[blocks][K][C]*/)
-{
-    __shared__ double red[TT / 16][K][4 * 16 + 1];
-    const int tid = threadIdx.x, cq = tid & 15, rl = tid >> 4;
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) red[rl][k][cq * 4 + e] = s[k][e];
-    __syncthreads();
-    if (tid < K * TC) {
-        const int k = tid / TC, c = tid - k * TC;
-        double v = 0.0;
-        for (int r = 0; r < TT / 16; r++) v += red[r][k][c];
-        part[((size_t)blockIdx.x * K + k) * TC + c] = v;
-    }
-}
-
-// the partial rows' totals of channel blockIdx.x (grid: C workgroups of 512 threads, one row lane each): tot[k].  One level, no
-// last-arriver: a __threadfence costs ~20 us here too (it writes back what the previous kernel left dirty in the XCD's L2).
-template <int K>
-__device__ __forceinline__ void colsum_total(const double *part, int nparts, double *tot /* LDS [K] */)
-{
-    __shared__ double red[TT / 64][K];
-    const int tid = threadIdx.x, c = blockIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double v = 0.0;
-        for (int bb = tid; bb < nparts; bb += TT) v += part[((size_t)bb * K + k) * TC + c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((tid & 63) == 0) red[tid >> 6][k] = v;
-    }
-    __syncthreads();
-    if (tid < K) {
-        double v = 0.0;
-        for (int w = 0; w < TT / 64; w++) v += red[w][tid];
-        tot[tid] = v;
-    }
-    __syncthreads();
-}
 
 __device__ __forceinline__ void block_atomic_max(float mx, unsigned *amax)
 {
@@ -517,21 +478,12 @@ __device__ __forceinline__ void block_atomic_max(float mx, unsigned *amax)
 __global__ void __launch_bounds__(TT) k_bn_stats_fin(const double *part, int nparts, long long M, float eps, float momentum, float *mean,
                                                      float *invstd, float *run_mean, float *run_var)
 {
-    __shared__ double tot[2];
-    colsum_total<2>(part, nparts, tot);
-    if (threadIdx.x == 0) {
-        const int c = blockIdx.x;
-        const double m = tot[0] / (double)M;
-        double var = tot[1] / (double)M - m * m;
-        if (var < 0.0) var = 0.0;
-        mean[c] = (float)m;
-        invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (run_mean) run_mean[c] = (float)((1.0 - momentum) * (double)run_mean[c] + (double)momentum * m);
-        if (run_var) {
-            const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-            run_var[c] = (float)((1.0 - momentum) * (double)run_var[c] + (double)momentum * unb);
-        }
-    }
+    __shared__ double wt[TT / 64][2];
+    const int c = blockIdx.x;
+    block_col_totals<2, TT>(part + c, TC, 2 * TC, nparts, wt);
+    if (threadIdx.x == 0)
+        bn_finish_stats(waves_in_order(wt, 0), waves_in_order(wt, 1), M, eps, momentum, mean + c, invstd + c, run_mean ? run_mean + c : nullptr,
+                        run_var ? run_var + c : nullptr);
 }
 
 // A_out = relu(gamma * (y - mean) * invstd + beta (+ res)); tracks max(A_out); writes the ReLU mask (quad_mask)
@@ -594,21 +546,27 @@ __global__ void __launch_bounds__(TT) k_bn_bwd_sums(const f32x4 *__restrict__ dA
             s[1][e] += (double)g * (double)yh;
         }
     }
-    block_colsum_store<2>(s, part);
+    colsum_store<2, 16, TT>(s, part);
+}
+
+// channel c's totals of sum(g), sum(g * yhat) over the [b][2][C] partial rows -> sums for pass 2, dbeta, dgamma; clears the max|dY|
+// word.  The caller owns wt and says how ITS wave totals are combined: tot(k) is k_bn_bwd_sums_fin's 8 left to right,
+// k_wgrad_reduce's 4 pairwise.
+template <int THREADS, int P, class Combine>
+__device__ __forceinline__ void bn_bwd_sums_finish(const double *part, int nparts, int c, double *sums, float *dbeta, float *dgamma, unsigned *zero,
+                                                   double (&wt)[THREADS / 64][P], Combine tot)
+{
+    block_col_totals<2, THREADS>(part + c, TC, 2 * TC, nparts, wt);
+    if (threadIdx.x == 0) {
+        bn_finish_bwd(tot(0), tot(1), sums, c, TC + c, dbeta + c, dgamma + c);
+        if (c == 0) *zero = 0u;
+    }
 }
 
 __global__ void __launch_bounds__(TT) k_bn_bwd_sums_fin(const double *part, int nparts, double *sums, float *dbeta, float *dgamma, unsigned *zero)
 {
-    __shared__ double tot[2];
-    colsum_total<2>(part, nparts, tot);
-    if (threadIdx.x == 0) {
-        const int c = blockIdx.x;
-        sums[c] = tot[0];
-        sums[TC + c] = tot[1];
-        dbeta[c] = (float)tot[0];
-        dgamma[c] = (float)tot[1];
-    }
-    if (threadIdx.x == 0 && blockIdx.x == 0) *zero = 0u;
+    __shared__ double wt[TT / 64][2];
+    bn_bwd_sums_finish<TT>(part, nparts, blockIdx.x, sums, dbeta, dgamma, zero, wt, [&](int k) { return waves_in_order(wt, k); });
 }
 
 // backward, pass 2: dY = gamma * invstd * (g - sum(g)/M - yhat * sum(g*yhat)/M); keeps g (skip path of a block's end);
@@ -646,7 +604,7 @@ __global__ void __launch_bounds__(TT) k_bn_bwd_apply(const f32x4 *__restrict__ d
         if (g4) g4[r * 16 + cq] = g;
     }
     block_atomic_max(mx, amax);
-    block_colsum_store<1>(s, part);
+    colsum_store<1, 16, TT>(s, part);
 }
 
 // ------------------------------------------------------------------------------------
@@ -872,35 +830,15 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce(const float *__restrict__ 
         // sum(g), sum(g * yhat) of the layer below (partial rows left by the input-gradient conv that ran before this launch) ->
         // sums for k_bn_bwd_apply, dbeta, dgamma; clears the max|dY| word (a launch of its own before: 5 us per layer)
         const int c = blockIdx.x - (9 * TC * TC / 64 + TC);
-        double v0 = 0.0, v1 = 0.0;
-        for (int bb = threadIdx.x; bb < fin.nparts; bb += 256) {
-            v0 += fin.part[((size_t)bb * 2) * TC + c];
-            v1 += fin.part[((size_t)bb * 2 + 1) * TC + c];
-        }
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) { v0 += __shfl_xor(v0, sh); v1 += __shfl_xor(v1, sh); }
-        if (o == 0) { red[j][0] = v0; red[j][1] = v1; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double t0 = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), t1 = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-            fin.sums[c] = t0;
-            fin.sums[TC + c] = t1;
-            fin.dbeta[c] = (float)t0;
-            fin.dgamma[c] = (float)t1;
-            if (c == 0) *fin.zero = 0u;
-        }
+        bn_bwd_sums_finish<256>(fin.part, fin.nparts, c, fin.sums, fin.dbeta, fin.dgamma, fin.zero, red,
+                                [&](int k) { return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]); });
         return;
     }
     if (blockIdx.x >= 9 * TC * TC / 64) {
         // C workgroups: the conv bias gradient of channel c = the total of k_bn_bwd_apply's partial sums of dY (a launch
         // of its own before: 4.8 us per layer)
         const int c = blockIdx.x - 9 * TC * TC / 64;
-        double v = 0.0;
-        for (int bb = threadIdx.x; bb < bias_nparts; bb += 256) v += bias_part[(size_t)bb * TC + c];
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
-        if (o == 0) red[j][0] = v;
-        __syncthreads();
+        block_col_totals<1, 256>(bias_part + c, 0, TC, bias_nparts, red);
         if (threadIdx.x == 0) dbias[c] = (float)((red[0][0] + red[1][0]) + (red[2][0] + red[3][0]));
         return;
     }
@@ -1194,9 +1132,7 @@ __device__ __forceinline__ void bn2d_block_store(double (&s)[K], double *part, i
     const int lane = threadIdx.x, w = threadIdx.y;
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        double v = s[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        const double v = wave_sum(s[k]);
         if (lane == 0) red[w][k] = v;
     }
     __syncthreads();
@@ -1220,39 +1156,15 @@ __global__ void __launch_bounds__(512) k_bn2d_stats(const float *__restrict__ x,
     bn2d_block_store<2>(s, part, C);
 }
 
-// one workgroup of 64 threads per channel: totals of the K partial sums -> tot[k] (all lanes)
-template <int K>
-__device__ __forceinline__ void bn2d_total(const double *part, int nb, double (&tot)[K])
-{
-    const int c = blockIdx.x, lane = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double v = 0.0;
-        for (int b = lane; b < nb; b += 64) v += part[((size_t)c * nb + b) * K + k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        tot[k] = v;
-    }
-}
-
+// the *_fin kernels: one workgroup of 64 threads per channel totals its nb partial rows part[c][b][2]
 __global__ void __launch_bounds__(64) k_bn2d_stats_fin(const double *part, int nb, long long M, float eps, float momentum, float *mean,
                                                        float *invstd, float *run_mean, float *run_var)
 {
+    const int c = blockIdx.x;
     double tot[2];
-    bn2d_total<2>(part, nb, tot);
-    if (threadIdx.x == 0) {
-        const int c = blockIdx.x;
-        const double m = tot[0] / (double)M;
-        double var = tot[1] / (double)M - m * m;
-        if (var < 0.0) var = 0.0;
-        mean[c] = (float)m;
-        invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (run_mean) run_mean[c] = (float)((1.0 - momentum) * (double)run_mean[c] + (double)momentum * m);
-        if (run_var) {
-            const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-            run_var[c] = (float)((1.0 - momentum) * (double)run_var[c] + (double)momentum * unb);
-        }
-    }
+    col_wave_sums<2, 64>(part + (size_t)c * nb * 2, 1, 2, nb, threadIdx.x, tot);
+    if (threadIdx.x == 0)
+        bn_finish_stats(tot[0], tot[1], M, eps, momentum, mean + c, invstd + c, run_mean ? run_mean + c : nullptr, run_var ? run_var + c : nullptr);
 }
 
 // out = gamma * (x - mean) * invstd + beta, ReLU if asked; rows r = n * C + c of HW floats, 8 rows per workgroup pass
@@ -1290,15 +1202,10 @@ __global__ void __launch_bounds__(512) k_bn2d_bwd_sums(const float *__restrict__
 
 __global__ void __launch_bounds__(64) k_bn2d_bwd_fin(const double *part, int nb, double *sums /*[C][2]*/, float *dgamma, float *dbeta)
 {
+    const int c = blockIdx.x;
     double tot[2];
-    bn2d_total<2>(part, nb, tot);
-    if (threadIdx.x == 0) {
-        const int c = blockIdx.x;
-        sums[c * 2] = tot[0];
-        sums[c * 2 + 1] = tot[1];
-        dbeta[c] = (float)tot[0];
-        dgamma[c] = (float)tot[1];
-    }
+    col_wave_sums<2, 64>(part + (size_t)c * nb * 2, 1, 2, nb, threadIdx.x, tot);
+    if (threadIdx.x == 0) bn_finish_bwd(tot[0], tot[1], sums, c * 2, c * 2 + 1, dbeta + c, dgamma + c);
 }
 
 __global__ void __launch_bounds__(512) k_bn2d_bwd_apply(const float *__restrict__ dout, const float *__restrict__ out, const float *__restrict__ x,
@@ -1318,6 +1225,15 @@ __global__ void __launch_bounds__(512) k_bn2d_bwd_apply(const float *__restrict_
     }
 }
 
+// batch statistics of x [n][C][HW]: partial rows into ws (C * BN_NB * 2 doubles), then the finish
+static void launch_bn2d_statistics(hipStream_t s, const float *x, int n, int C, int HW, double *ws, float eps, float momentum, float *mean,
+                                   float *invstd, float *run_mean, float *run_var)
+{
+    const int nb = std::min(BN_NB, (n + 7) / 8);
+    hipLaunchKernelGGL(k_bn2d_stats, dim3(C, nb), dim3(64, 8), 0, s, x, n, C, HW, ws);
+    hipLaunchKernelGGL(k_bn2d_stats_fin, dim3(C), dim3(64), 0, s, ws, nb, (long long)n * HW, eps, momentum, mean, invstd, run_mean, run_var);
+}
+
 // workspace (caller-owned DEVICE memory, 8-byte aligned): C * BN_NB * 2 doubles of partials + C * 2 doubles of sums
 extern "C" int64_t dbaz_bn2d_workspace_bytes(int32_t channels) { return (int64_t)channels * (BN_NB * 2 + 2) * 8; }
 
@@ -1331,10 +1247,8 @@ extern "C" int dbaz_bn2d_forward(const float *x, int32_t n, int32_t channels, in
     if (n < 1 || channels < 1 || hw < 1) return terr(nullptr, DBAZ_EINVAL, "bn2d: n, channels and H*W must be >= 1");
     hipStream_t s = (hipStream_t)stream;
     double *part = reinterpret_cast<double *>(workspace);
-    const int nb = std::min(BN_NB, (n + 7) / 8);
-    const long long rows = (long long)n * channels, M = (long long)n * hw;
-    hipLaunchKernelGGL(k_bn2d_stats, dim3(channels, nb), dim3(64, 8), 0, s, x, n, channels, hw, part);
-    hipLaunchKernelGGL(k_bn2d_stats_fin, dim3(channels), dim3(64), 0, s, part, nb, M, eps, momentum, save_mean, save_invstd, run_mean, run_var);
+    const long long rows = (long long)n * channels;
+    launch_bn2d_statistics(s, x, n, channels, hw, part, eps, momentum, save_mean, save_invstd, run_mean, run_var);
     hipLaunchKernelGGL(k_bn2d_apply, dim3((unsigned)std::min<long long>((rows + 7) / 8, 4096)), dim3(64, 8), 0, s, x, out, rows, channels, hw,
                        save_mean, save_invstd, gamma, beta, relu);
     hipError_t e = hipGetLastError();
@@ -1385,9 +1299,7 @@ void train_bn_backward_apply_rows(dbaz_trainer *t, hipStream_t s, const float *d
 void train_bn2d_statistics(dbaz_trainer *t, hipStream_t s, const float *x, int n, int C, int HW, double *ws, float *mean, float *invstd,
                            float *run_mean, float *run_var)
 {
-    const int nb = std::min(BN_NB, (n + 7) / 8);
-    hipLaunchKernelGGL(k_bn2d_stats, dim3(C, nb), dim3(64, 8), 0, s, x, n, C, HW, ws);
-    hipLaunchKernelGGL(k_bn2d_stats_fin, dim3(C), dim3(64), 0, s, ws, nb, (long long)n * HW, t->eps, t->momentum, mean, invstd, run_mean, run_var);
+    launch_bn2d_statistics(s, x, n, C, HW, ws, t->eps, t->momentum, mean, invstd, run_mean, run_var);
 }
 
 // ------------------------------------------------------------------------------------

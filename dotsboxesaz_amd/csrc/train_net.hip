@@ -1,6 +1,7 @@
 // train_net.hip -- the rest of ResNetZero's training-mode pass around the residual tower of train.hip, and the two entry points
 // that run the WHOLE network of the optimizer step: dbaz_trainer_net_forward / dbaz_trainer_net_backward.
 #include "train.h"
+#include "train_reduce.h"
 
 // ====================================================================================
 // The whole network of the training step on this library (nn.py:108-122 under model.train(True)):
@@ -155,52 +156,6 @@ static int gemm_splits(int K, int splits) // the z extent launch_gemm uses
     return (K + kchunk - 1) / kchunk;
 }
 
-// column sums of a NET_WG-thread workgroup whose thread (rl, cq) = (tid / CQ, tid % CQ) holds K x 4 doubles of channel quad cq:
-// one partial row [K][4 CQ] per workgroup
-template <int K, int CQ>
-__device__ __forceinline__ void net_colsum_store(double (&s)[K][4], double *part)
-{
-    constexpr int RL = NET_WG / CQ;
-    __shared__ double red[RL][K][4 * CQ + 1];
-    const int tid = threadIdx.x, cq = tid % CQ, rl = tid / CQ;
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) red[rl][k][cq * 4 + e] = s[k][e];
-    __syncthreads();
-    if (tid < K * 4 * CQ) {
-        const int k = tid / (4 * CQ), c = tid - k * 4 * CQ;
-        double v = 0.0;
-        for (int r = 0; r < RL; r++) v += red[r][k][c];
-        part[((size_t)blockIdx.x * K + k) * 4 * CQ + c] = v;
-    }
-}
-// total of column c of the partial rows part[nparts][ncols] (all threads of a NET_WG workgroup call; result in every thread)
-__device__ __forceinline__ double net_col_total(const double *part, int nparts, int ncols, int c)
-{
-    __shared__ double red[NET_WG / 64];
-    __syncthreads();
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nparts; b += NET_WG) v += part[(size_t)b * ncols + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < NET_WG / 64; w++) t += red[w];
-    return t;
-}
-
-// total of column c of part[nparts][ncols] by one wave (every lane gets it)
-__device__ __forceinline__ double wave_col_total(const double *part, int nparts, int ncols, int c)
-{
-    double v = 0.0;
-    for (int b = threadIdx.x & 63; b < nparts; b += 64) v += part[(size_t)b * ncols + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ---- stem forward: Y0[row][o] = b0[o] + sum_{ci,tap} W0[o][ci][tap] * xhat[n][ci][pos + tap], xhat = bn_input(x) inside the
 // board and 0 outside (the conv pads the NORMALIZED input); partial sums of Y0, Y0^2 for bn0.  Thread = (row lane, channel quad)
 // with its quad's 27 x 4 weights in registers; a workgroup normalizes STEM_S samples at a time into LDS (read from global by
@@ -257,7 +212,7 @@ __global__ void __launch_bounds__(NET_WG) k_stem_conv(const float *__restrict__ 
             for (int e = 0; e < 4; e++) { const double d = acc[e]; s[0][e] += d; s[1][e] += d * d; }
         }
     }
-    net_colsum_store<2, 16>(s, part);
+    colsum_store<2, 16, NET_WG>(s, part);
 }
 
 // ---- heads: packed parameters.  Wh[c][o] = conv weight of output o (policy 0..15, value 16..31) and input c; bh[o];
@@ -322,7 +277,7 @@ __global__ void __launch_bounds__(NET_WG) k_head_conv(const f32x4 *__restrict__ 
                 for (int e = 0; e < 4; e++) { const double d = acc[u][e]; s[0][e] += d; s[1][e] += d * d; }
             }
     }
-    net_colsum_store<2, 8>(s, part);
+    colsum_store<2, 8, NET_WG>(s, part);
 }
 
 // batch statistics of the 32 head channels (grid: 32 workgroups); running statistics of the policy head's bn (channels 0..15) and
@@ -330,21 +285,14 @@ __global__ void __launch_bounds__(NET_WG) k_head_conv(const f32x4 *__restrict__ 
 __global__ void __launch_bounds__(NET_WG) k_head_stats_fin(const double *part, int nparts, long long M, float eps, float momentum, float *mean,
                                                            float *invstd, float *ph_rm, float *ph_rv, float *vh_rm, float *vh_rv)
 {
+    __shared__ double wt[NET_WG / 64][2];
     const int c = blockIdx.x;
-    const double t0 = net_col_total(part, nparts, 2 * HC2, c), t1 = net_col_total(part, nparts, 2 * HC2, HC2 + c);
+    block_col_totals<2, NET_WG>(part + c, HC2, 2 * HC2, nparts, wt); // partial rows [b][2][32]
     if (threadIdx.x == 0) {
-        const double m = t0 / (double)M;
-        double var = t1 / (double)M - m * m;
-        if (var < 0.0) var = 0.0;
-        mean[c] = (float)m;
-        invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
         float *rm = c < HC ? ph_rm : vh_rm, *rv = c < HC ? ph_rv : vh_rv;
         const int cc = c < HC ? c : c - HC;
-        if (rm) rm[cc] = (float)((1.0 - momentum) * (double)rm[cc] + (double)momentum * m);
-        if (rv) {
-            const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-            rv[cc] = (float)((1.0 - momentum) * (double)rv[cc] + (double)momentum * unb);
-        }
+        bn_finish_stats(waves_in_order(wt, 0), waves_in_order(wt, 1), M, eps, momentum, mean + c, invstd + c, rm ? rm + cc : nullptr,
+                        rv ? rv + cc : nullptr);
     }
 }
 
@@ -466,7 +414,7 @@ __global__ void __launch_bounds__(64) k_head_small_fin(const double *part, int n
                                                        float *g_vh_f1w, float *g_vh_f1b)
 {
     const int ncol = NOp + VF + 1, c = blockIdx.x;
-    const double t = wave_col_total(part, nparts, ncol, c);
+    const double t = col_wave_sum<64>(part + c, ncol, nparts, threadIdx.x);
     if (threadIdx.x == 0) {
         if (c < A) g_ph_fb[c] = (float)t;
         else if (c < A + VF) g_vh_f0b[c - A] = (float)t;
@@ -510,19 +458,17 @@ __global__ void __launch_bounds__(NET_WG) k_head_bn_bwd_sums(const f32x4 *__rest
             s[1][e] += (double)g * (double)yh;
         }
     }
-    net_colsum_store<2, 8>(s, part);
+    colsum_store<2, 8, NET_WG>(s, part);
 }
 __global__ void __launch_bounds__(NET_WG) k_head_bn_bwd_fin(const double *part, int nparts, double *sums, float *g_ph_w, float *g_ph_b, float *g_vh_w,
                                                             float *g_vh_b)
 {
+    __shared__ double wt[NET_WG / 64][2];
     const int c = blockIdx.x;
-    const double t0 = net_col_total(part, nparts, 2 * HC2, c), t1 = net_col_total(part, nparts, 2 * HC2, HC2 + c);
-    if (threadIdx.x == 0) {
-        sums[c] = t0;
-        sums[HC2 + c] = t1;
-        if (c < HC) { g_ph_b[c] = (float)t0; g_ph_w[c] = (float)t1; }
-        else { g_vh_b[c - HC] = (float)t0; g_vh_w[c - HC] = (float)t1; }
-    }
+    block_col_totals<2, NET_WG>(part + c, HC2, 2 * HC2, nparts, wt);
+    if (threadIdx.x == 0)
+        bn_finish_bwd(waves_in_order(wt, 0), waves_in_order(wt, 1), sums, c, HC2 + c, c < HC ? g_ph_b + c : g_vh_b + (c - HC),
+                      c < HC ? g_ph_w + c : g_vh_w + (c - HC));
 }
 // pass 2 (in place): dYh = gamma invstd (g - sum(g)/M - yhat sum(g yhat)/M); partial sums of dYh (the conv biases' gradient)
 __global__ void __launch_bounds__(NET_WG) k_head_bn_bwd_apply(f32x4 *__restrict__ dh4, const f32x4 *__restrict__ hh4, const f32x4 *__restrict__ yh4,
@@ -552,7 +498,7 @@ __global__ void __launch_bounds__(NET_WG) k_head_bn_bwd_apply(f32x4 *__restrict_
         }
         dh4[r * 8 + oq] = o;
     }
-    net_colsum_store<1, 8>(s, part);
+    colsum_store<1, 8, NET_WG>(s, part);
 }
 
 // dA[row][c] = sum_o dYh[row][o] Wh[c][o] (the gradient entering the tower, in rows); two rows per pass
@@ -588,22 +534,16 @@ __global__ void __launch_bounds__(NET_WG) k_head_conv_bwd_data(const f32x4 *__re
 __global__ void __launch_bounds__(NET_WG) k_head_wgrad_fin(const float *__restrict__ part, int splits, const double *bias_part, int bias_nparts,
                                                            float *g_ph_cw, float *g_vh_cw, float *g_ph_cb, float *g_vh_cb)
 {
-    __shared__ double red[16][17];
     const int nb_w = HC2 * TC / 16;
     if ((int)blockIdx.x >= nb_w) {
         const int c = ((int)blockIdx.x - nb_w) * 4 + (threadIdx.x >> 6);
-        const double t = wave_col_total(bias_part, bias_nparts, HC2, c);
+        const double t = col_wave_sum<64>(bias_part + c, HC2, bias_nparts, threadIdx.x & 63);
         if ((threadIdx.x & 63) == 0) { if (c < HC) g_ph_cb[c] = (float)t; else g_vh_cb[c - HC] = (float)t; }
         return;
     }
-    const int oi = threadIdx.x & 15, lanep = threadIdx.x >> 4, i = blockIdx.x * 16 + oi; // i = o * 64 + c
-    double t = 0.0;
-    for (int z = lanep; z < splits; z += 16) t += (double)part[(size_t)z * HC2 * TC + i];
-    red[lanep][oi] = t;
-    __syncthreads();
-    if (lanep == 0) {
-        double v = 0.0;
-        for (int r = 0; r < 16; r++) v += red[r][oi];
+    const int i = blockIdx.x * 16 + (threadIdx.x & 15); // i = o * 64 + c
+    const double v = splitk16_total(part + i, (size_t)HC2 * TC, splits);
+    if (threadIdx.x < 16) {
         const int o = i / TC, c = i - o * TC;
         if (o < HC) g_ph_cw[o * TC + c] = (float)v; else g_vh_cw[(o - HC) * TC + c] = (float)v;
     }
@@ -635,17 +575,9 @@ __global__ void __launch_bounds__(NET_WG) k_stem_val(const float *__restrict__ x
 // Gsum[k][o] = sum over the workgroups' partials (grid: 36 x 4 workgroups, thread = (partial lane of 16, o of 16))
 __global__ void __launch_bounds__(NET_WG) k_stem_fin1(const float *__restrict__ part, int nparts, float *__restrict__ Gsum)
 {
-    __shared__ double red[16][17];
-    const int k = blockIdx.x >> 2, o = (blockIdx.x & 3) * 16 + (threadIdx.x & 15), j = threadIdx.x >> 4;
-    double t = 0.0;
-    for (int b = j; b < nparts; b += 16) t += (double)part[((size_t)b * 36 + k) * TC + o];
-    red[j][threadIdx.x & 15] = t;
-    __syncthreads();
-    if (j == 0) {
-        double v = 0.0;
-        for (int r = 0; r < 16; r++) v += red[r][threadIdx.x & 15];
-        Gsum[k * TC + o] = (float)v;
-    }
+    const int k = blockIdx.x >> 2, o = (blockIdx.x & 3) * 16 + (threadIdx.x & 15);
+    const double v = splitk16_total(part + k * TC + o, (size_t)36 * TC, nparts);
+    if (threadIdx.x < 16) Gsum[k * TC + o] = (float)v;
 }
 // conv0's weight and bias gradients, bn_input's weight and bias gradients
 __global__ void __launch_bounds__(NET_WG) k_stem_fin2(const float *__restrict__ Gsum, const float *__restrict__ w0, const float *in_w, const float *in_b,
@@ -654,24 +586,23 @@ __global__ void __launch_bounds__(NET_WG) k_stem_fin2(const float *__restrict__ 
 {
     // grid of 5: workgroups 0..2 = bn_input's gradient for input channel ci, 3 = conv0's weight gradient, 4 = its bias gradient
     // (one workgroup doing the five in turn was five global round trips behind each other: 23 us)
-    __shared__ double rg[NET_WG], rb[NET_WG / 64];
+    __shared__ double rg[NET_WG], wt[NET_WG / 64][2];
     const int tid = threadIdx.x;
     if (blockIdx.x < 3) {
         const int ci = blockIdx.x;
-        double a = 0.0, b = 0.0;
+        double ab[2] = {0.0, 0.0};
         for (int i = tid; i < TC * 9; i += NET_WG) {
             const int o = i / 9, t = i - o * 9;
             const double w = (double)w0[o * 27 + ci * 9 + t];
-            a += w * (double)Gsum[(ci * 9 + t) * TC + o];
-            b += w * (double)Gsum[(27 + t) * TC + o];
+            ab[0] += w * (double)Gsum[(ci * 9 + t) * TC + o];
+            ab[1] += w * (double)Gsum[(27 + t) * TC + o];
         }
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) { a += __shfl_xor(a, sh); b += __shfl_xor(b, sh); }
-        if ((tid & 63) == 0) { rg[tid >> 6] = a; rb[tid >> 6] = b; }
-        __syncthreads();
+        ab[0] = wave_sum(ab[0]);
+        ab[1] = wave_sum(ab[1]);
+        wave_totals_store(ab, wt);
         if (tid == 0) {
-            g_in_w[ci] = (float)((rg[0] + rg[1]) + (rg[2] + rg[3]));
-            g_in_b[ci] = (float)((rb[0] + rb[1]) + (rb[2] + rb[3]));
+            g_in_w[ci] = (float)((wt[0][0] + wt[1][0]) + (wt[2][0] + wt[3][0]));
+            g_in_b[ci] = (float)((wt[0][1] + wt[1][1]) + (wt[2][1] + wt[3][1]));
         }
     } else if (blockIdx.x == 3) {
         for (int i = tid; i < TC * 27; i += NET_WG) {

@@ -90,6 +90,27 @@ def test_network_forward_backward_vs_float64(board, nb, n):
         check(k, sh[k], s32[k], s64[k], 2e-6)
 
 
+@pytest.mark.parametrize("board,nb,n", [((6, 6), 2, 37), ((2, 3), 1, 9)])
+def test_network_step_is_bit_reproducible(board, nb, n):
+    """The same whole-network step twice on the same model and batch: logp, v, every parameter gradient and every running statistic
+    are equal bit for bit -- no reduction of the training kernels uses a float atomic, and the association of every sum is fixed
+    by the code ("Column sums and the BatchNorm finish")."""
+    from dotsboxesaz_amd import train_tower
+    rows, cols = board
+    model = make_model(rows, cols, nb, 11 * nb + n)
+    x, pi, z = batch(rows, cols, n, model.policy_head.fc.out_features, 5 + n)
+    assert train_tower.net_supported(copy.deepcopy(model).cuda().train(True), x.cuda())
+    p1, v1, _, g1, s1, _ = run(model, x, pi, z, torch.float32, "cuda", hip_tower=True, hip_heads=True)
+    p2, v2, _, g2, s2, _ = run(model, x, pi, z, torch.float32, "cuda", hip_tower=True, hip_heads=True)
+    assert torch.equal(p1, p2), "logp"
+    assert torch.equal(v1, v2), "v"
+    assert g1.keys() == g2.keys() and s1.keys() == s2.keys() and len(g1) > 0 and len(s1) > 0
+    for k in g1:
+        assert torch.equal(g1[k], g2[k]), k
+    for k in s1:
+        assert torch.equal(s1[k], s2[k]), k
+
+
 def test_hip_heads_are_the_default_and_fall_back_cleanly():
     """training_forward picks the whole-network path for the shipped shape, the tower-only path when the heads differ."""
     from dotsboxesaz_amd import nn as dnn, train as T, train_tower
