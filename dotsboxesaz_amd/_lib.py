@@ -28,7 +28,7 @@ SYMBOLS = [
     "dbaz_get_counters", "dbaz_timing_begin", "dbaz_timing_end", "dbaz_fetch_samples", "dbaz_replay_rows_dev",
     "dbaz_replay_rows_clear", "dbaz_dataset_select", "dbaz_dataset_begin", "dbaz_dataset_add_rows", "dbaz_dataset_finish", "dbaz_dataset_fetch", "dbaz_dataset_batch", "dbaz_dataset_batch_on",
     "dbaz_symmetry_apply", "dbaz_symmetry_table",
-    "dbaz_trainer_last_error", "dbaz_trainer_create", "dbaz_trainer_destroy", "dbaz_trainer_forward", "dbaz_trainer_backward",
+    "dbaz_trainer_last_error", "dbaz_trainer_board_supported", "dbaz_trainer_create", "dbaz_trainer_destroy", "dbaz_trainer_forward", "dbaz_trainer_backward",
     "dbaz_trainer_net_forward", "dbaz_trainer_net_backward",
     "dbaz_bn2d_workspace_bytes", "dbaz_bn2d_forward", "dbaz_bn2d_backward",
     "dbaz_az_loss_workspace_bytes", "dbaz_az_loss", "dbaz_sgd_step",
@@ -152,6 +152,7 @@ def load():
     L.dbaz_replay_rows_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32)]
     L.dbaz_trainer_last_error.argtypes = [vp]
     L.dbaz_trainer_last_error.restype = C.c_char_p
+    L.dbaz_trainer_board_supported.argtypes = [i32, i32]
     L.dbaz_trainer_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.dbaz_trainer_destroy.argtypes = [vp]
     L.dbaz_trainer_destroy.restype = None

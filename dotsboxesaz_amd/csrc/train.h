@@ -21,10 +21,7 @@ typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 typedef float f2v __attribute__((ext_vector_type(2)));
 union u128h { f32x4 f; f16x8 h; };
 
-#define TT 512          // threads per workgroup of the conv / wgrad kernels: 8 waves, two per SIMD
-#define TC 64           // channels (the two-cout-tile MFMA tiling is written for 64)
-#define TL_MAX 64       // conv layers of a tower (2 * blocks)
-#define RED_BLOCKS 256  // workgroups of the column-sum kernels
+#include "train_plan.h" // TT, TC, TL_MAX, RED_BLOCKS and every launch size: host-only arithmetic, compiled by the CPU tests too
 
 struct dbaz_net_buffers;
 void net_free(struct dbaz_trainer *t); // train_net.hip
@@ -32,6 +29,7 @@ void net_free(struct dbaz_trainer *t); // train_net.hip
 struct dbaz_trainer {
     int dev = 0, H = 0, W = 0, HW = 0, L = 0, maxN = 0, n = 0;
     int S = 1, cus = 256;
+    TrainPlan plan;    // the launch plan of the board (train_plan.h); S, Swh and the LDS sizes below are copies
 #ifdef DBAZ_STAMP
     unsigned long long *stamps = nullptr, *stamps_wg = nullptr; // diagnostic build only (k_conv_t, k_wgrad_h3)
 #endif
@@ -84,7 +82,6 @@ __device__ __forceinline__ float wave_max(float v)
 #define BN_NB 64        // k_bn2d_*: sample slices (blockIdx.y) per channel
 
 static inline size_t act_elems(const dbaz_trainer *t) { return (size_t)t->maxN * t->HW * TC; }
-static inline int red_blocks(long long M) { return (int)std::max(1LL, std::min((long long)RED_BLOCKS, (M + 31) / 32)); }
 
 // ---- train.hip, called by train_net.hip
 // The tower on rows: A[0] (t->A, NHWC rows, max|A[0]| in t->amax[0]) -> A[L].  t->amax[1..] must be zero.

@@ -622,27 +622,8 @@ __global__ void __launch_bounds__(TT) k_bn_bwd_apply(const f32x4 *__restrict__ d
 // run two taps ahead in a 3-deep ring, and the next chunk's rows travel HBM -> registers under the whole loop.  The
 // workgroups' partial gradients are summed by k_wgrad_reduce.
 // ------------------------------------------------------------------------------------
-#define WG_MAXLD 13 // float4 per thread and chunk: 2 images x <= 208 rows x 16 quads / 512 threads
-#define WH_SB 288 // bytes per image row
 typedef short s4v __attribute__((__vector_size__(4 * sizeof(short))));
 union FragH { s4v s[2]; f16x8 h; };
-
-struct WhGeo { int RK, RA, PW, G, NK; };
-__host__ __device__ inline WhGeo wh_geo(int Sw, int H, int W)
-{
-    WhGeo g;
-    g.PW = W + 1;
-    g.G = g.PW + 1;
-    g.NK = (Sw * H * g.PW + 31) / 32;              // K steps per chunk
-    g.RK = g.NK * 32;                              // rows of the dY image
-    g.RA = 2 * g.G + Sw * (H + 1) * g.PW;          // rows of the padded A image (the last window ends at row Sw*(H+1)*PW + G)
-    return g;
-}
-static size_t wh_lds_bytes(int Sw, int H, int W)
-{
-    const WhGeo g = wh_geo(Sw, H, W);
-    return (size_t)(g.RA + g.RK) * WH_SB + (size_t)g.RK * 4 + (size_t)Sw * H * W * 4;
-}
 
 typedef s4v __attribute__((address_space(3))) *lds_s4v_ptr;
 // transposing read at a 32-bit LDS byte address
@@ -886,32 +867,41 @@ extern "C" void dbaz_trainer_destroy(dbaz_trainer *t)
     delete t;
 }
 
+// 1 where dbaz_trainer_create accepts the board, 0 (and the reason in dbaz_trainer_last_error(NULL)) where it refuses it.  Host
+// arithmetic only: touches no device.
+extern "C" int dbaz_trainer_board_supported(int32_t rows, int32_t cols)
+{
+    TrainPlan plan;
+    char why[256];
+    if (train_plan_build(rows, cols, plan, why, sizeof(why))) return 1;
+    terr(nullptr, DBAZ_EINVAL, "%s", why);
+    return 0;
+}
+
 extern "C" int dbaz_trainer_create(int32_t rows, int32_t cols, int32_t channels, int32_t blocks, int32_t max_batch, int32_t device,
                                    dbaz_trainer **out)
 {
     if (!out) return terr(nullptr, DBAZ_EINVAL, "null argument");
     *out = nullptr;
     if (channels != TC) return terr(nullptr, DBAZ_EINVAL, "the training tower is built for %d channels (got %d)", TC, channels);
-    if (rows < 1 || cols < 1 || (rows + 1) * (cols + 1) > 196) return terr(nullptr, DBAZ_EINVAL, "board %dx%d unsupported", rows, cols);
+    // the launch plan of the board (train_plan.h): boards the kernels cannot hold are refused here, before any allocation or launch
+    TrainPlan plan;
+    char why[256];
+    if (!train_plan_build(rows, cols, plan, why, sizeof(why))) return terr(nullptr, DBAZ_EINVAL, "%s", why);
     if (blocks < 1 || 2 * blocks > TL_MAX) return terr(nullptr, DBAZ_EINVAL, "blocks must be in 1..%d", TL_MAX / 2);
     if (max_batch < 1) return terr(nullptr, DBAZ_EINVAL, "max_batch must be >= 1");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return terr(nullptr, DBAZ_EDEVICE, "no HIP device %d", device);
     dbaz_trainer *t = new dbaz_trainer();
-    t->dev = device; t->H = rows + 1; t->W = cols + 1; t->HW = t->H * t->W; t->L = 2 * blocks; t->maxN = max_batch;
+    t->dev = device; t->H = plan.H; t->W = plan.W; t->HW = plan.HW; t->L = 2 * blocks; t->maxN = max_batch;
     if (hipSetDevice(device) != hipSuccess) { delete t; return terr(nullptr, DBAZ_EDEVICE, "hipSetDevice(%d) failed", device); }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) t->cus = prop.multiProcessorCount;
-    t->S = 256 / t->HW;
-    {
-        const int S4 = (TC + 8) / 4;
-        const int zu = (t->S * t->HW * S4 + 15) & ~15;
-        t->conv_lds = (size_t)(zu + 3 * S4) * 16 + (size_t)(TT / 64) * 2 * TC * 8 + 16; // image + zero rows + the epilogue's column-sum slots
-        // samples per k_wgrad_h3 chunk: as many as the prefetch registers (208 rows) and 150 KB of LDS hold
-        t->Swh = 1;
-        while ((t->Swh + 1) * t->HW <= 208 && wh_lds_bytes(t->Swh + 1, t->H, t->W) <= 150 * 1024) t->Swh++;
-        t->wgrad_h3_lds = wh_lds_bytes(t->Swh, t->H, t->W);
-    }
+    t->plan = plan;
+    t->S = plan.S;
+    t->conv_lds = plan.conv_lds;
+    t->Swh = plan.Swh;
+    t->wgrad_h3_lds = plan.wgrad_h3_lds;
     const size_t ae = act_elems(t);
     hipError_t e = hipSuccess;
     auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
@@ -963,16 +953,6 @@ extern "C" int dbaz_debug_trainer_stamps(dbaz_trainer *t, unsigned long long *ou
 }
 #endif
 
-// k_bn_apply: workgroups of 256 threads x 4 quads per pass; as few passes as 1 024 workgroups allow, and a grid that
-// divides the tensor into WHOLE passes (1 024 workgroups left 3.06 passes at batch 4 096: a fourth latency round for 6 % of the rows)
-static int bn_apply_grid(long long n4)
-{
-    const long long per = 256 * 4;
-    const long long passes = std::max<long long>(1, (n4 + 1024 * per - 1) / (1024 * per));
-    return (int)std::max<long long>(1, (n4 + per * passes - 1) / (per * passes));
-}
-
-
 void tower_forward_rows(dbaz_trainer *t, int n, const float *const *conv_w, const float *const *conv_b, const float *const *bn_w,
                         const float *const *bn_b, float *const *run_mean, float *const *run_var, hipStream_t s)
 {
@@ -982,7 +962,7 @@ void tower_forward_rows(dbaz_trainer *t, int n, const float *const *conv_w, cons
     PackArgs pa;
     for (int l = 0; l < L; l++) pa.w[l] = conv_w[l];
     hipLaunchKernelGGL(k_pack_w, dim3(L, 2, 4), dim3(TT), 0, s, pa, t->wpk, t->wsc, L);
-    const int grid = (n + t->S - 1) / t->S;
+    const int grid = train_conv_grid(t->plan, n);
     const long long n4 = M * 16;
     const int ab = bn_apply_grid(n4);
     for (int l = 0; l < L; l++) {
@@ -1010,11 +990,10 @@ int tower_backward_rows(dbaz_trainer *t, const float *const *bn_w, float *const 
     const int L = t->L, HW = t->HW, n = t->n;
     const size_t ae = act_elems(t);
     const long long M = (long long)n * HW;
-    const int grid = (n + t->S - 1) / t->S;
+    const int grid = train_conv_grid(t->plan, n);
     const int rb = red_blocks(M);
     const int Sw = t->Swh;
-    const int nchunks = (n + Sw - 1) / Sw;
-    const int wg = std::min(t->cus, nchunks);
+    const int wg = train_wgrad_grid(t->plan, t->cus, n);
     unsigned *dymax = t->amax + L + 1;
     int cur = 0;
     for (int l = L - 1; l >= 0; l--) {
@@ -1049,7 +1028,7 @@ int tower_backward_rows(dbaz_trainer *t, const float *const *bn_w, float *const 
         ca.stamp_out = t->stamps;
 #endif
         hipLaunchKernelGGL(k_conv_t, dim3(grid), dim3(TT), t->conv_lds, s, ca);
-        if (t->W == 7)
+        if (t->plan.pwc == 8)
             hipLaunchKernelGGL((k_wgrad_h3<8>), dim3(wg), dim3(TT), t->wgrad_h3_lds, s, t->A + ae * l, t->dY, t->amax + l, dymax, n, Sw, t->H,
                                t->W, t->wg_part
 #ifdef DBAZ_STAMP

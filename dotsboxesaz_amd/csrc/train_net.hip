@@ -15,7 +15,6 @@
 // ====================================================================================
 #define HC 16          // channels per head (configuration.py: inner_channels 16)
 #define HC2 (2 * HC)   // the two heads side by side in one row
-#define NET_WG 256
 
 struct dbaz_net_buffers {
     int hc = 0, A = 0, VF = 0, NO = 0, NOp = 0, KF = 0, maxN = 0;
@@ -146,21 +145,15 @@ static void launch_gemm(hipStream_t s, const float *A, long long sam, long long 
     GemmArgs g;
     g.A = A; g.sam = sam; g.sak = sak; g.B = B; g.sbk = sbk; g.sbn = sbn; g.C = C; g.ldc = ldc; g.c_split = c_split; g.bias = bias;
     g.M = M; g.N = N; g.K = K;
-    g.kchunk = ((K + splits - 1) / splits + 31) / 32 * 32;
-    const int z = (K + g.kchunk - 1) / g.kchunk;
+    g.kchunk = gemm_kchunk(K, splits);
+    const int z = gemm_splits(K, splits);
     hipLaunchKernelGGL(k_gemm_f32, dim3((N + 63) / 64, (M + 63) / 64, z), dim3(NET_WG), 0, s, g);
-}
-static int gemm_splits(int K, int splits) // the z extent launch_gemm uses
-{
-    const int kchunk = ((K + splits - 1) / splits + 31) / 32 * 32;
-    return (K + kchunk - 1) / kchunk;
 }
 
 // ---- stem forward: Y0[row][o] = b0[o] + sum_{ci,tap} W0[o][ci][tap] * xhat[n][ci][pos + tap], xhat = bn_input(x) inside the
 // board and 0 outside (the conv pads the NORMALIZED input); partial sums of Y0, Y0^2 for bn0.  Thread = (row lane, channel quad)
 // with its quad's 27 x 4 weights in registers; a workgroup normalizes STEM_S samples at a time into LDS (read from global by
 // each of a row's 16 threads, the 27 inputs made the kernel load-issue-bound: 109 us).
-#define STEM_S 4
 __global__ void __launch_bounds__(NET_WG) k_stem_conv(const float *__restrict__ x, const float *in_mean, const float *in_invstd,
                                                       const float *in_w, const float *in_b, const float *__restrict__ w0,
                                                       const float *__restrict__ b0, f32x4 *__restrict__ y4, int n, int H, int W, double *part)
@@ -635,13 +628,6 @@ void net_free(dbaz_trainer *t)
 // offsets (floats) into dbaz_net_buffers::st and (doubles) into ::ws
 enum { ST_IN_MEAN = 0, ST_IN_INVSTD = 4, ST_MEAN0 = 8, ST_INVSTD0 = 72, ST_MEAN_H = 136, ST_INVSTD_H = 168, ST_BH = 200, ST_WH = 256,
        ST_FLOATS = 256 + TC * HC2 };
-#define NET_HB 1024  // workgroups of the head row kernels
-#define NET_OB 256   // workgroups of k_head_out_bwd
-#define NET_SB 2048  // workgroups of k_stem_conv
-#define FC_SPLITS 16   // fc weight gradient: K = batch
-#define FCF_SPLITS 4   // fc forward: K = 32 HW
-#define HW_SPLITS 392
-#define STEM_SPLITS 392
 enum { WS_IN = 0, WS_HP1 = 3 * BN_NB * 2 + 16, WS_HP2 = WS_HP1 + NET_SB * 2 * TC }; // (HP1 also holds k_stem_conv's NET_SB rows of [2][64])
 
 static int net_alloc(dbaz_trainer *t, int A, int VF)
@@ -714,7 +700,7 @@ extern "C" int dbaz_trainer_net_forward(dbaz_trainer *t, int32_t n, const float 
     // stem: bn_input's batch statistics, conv0 on the normalized input (+ bn0's statistics), bn0 + ReLU -> A[0]
     train_bn2d_statistics(t, s, x, n, 3, HW, b->ws + WS_IN, st + ST_IN_MEAN, st + ST_IN_INVSTD, R ? R->bn_input_mean : nullptr,
                           R ? R->bn_input_var : nullptr);
-    const int sb = std::min(NET_SB, (n + STEM_S - 1) / STEM_S);
+    const int sb = net_stem_grid(n);
     hipLaunchKernelGGL(k_stem_conv, dim3(sb), dim3(NET_WG), (size_t)(STEM_S * 3 + 9) * HW * 4, s, x, st + ST_IN_MEAN, st + ST_IN_INVSTD, P->bn_input_w,
                        P->bn_input_b, P->conv0_w, P->conv0_b, reinterpret_cast<f32x4 *>(b->Y0), n, t->H, t->W, b->ws + WS_HP1);
     train_bn_forward_rows(t, s, b->ws + WS_HP1, sb, M, st + ST_MEAN0, st + ST_INVSTD0, R ? R->bn0_mean : nullptr, R ? R->bn0_var : nullptr, b->Y0,
@@ -723,16 +709,16 @@ extern "C" int dbaz_trainer_net_forward(dbaz_trainer *t, int32_t n, const float 
     // heads
     hipLaunchKernelGGL(k_head_pack, dim3(256), dim3(NET_WG), 0, s, P->ph_conv_w, P->ph_conv_b, P->vh_conv_w, P->vh_conv_b, P->ph_fc_w, P->ph_fc_b,
                        P->vh_fc0_w, P->vh_fc0_b, st + ST_WH, st + ST_BH, b->Wc, b->bc, HW, A, VF, NOp);
-    const int hb = (int)std::min<long long>(NET_HB, (M + 127) / 128);
+    const int hb = net_head_conv_grid(M);
     hipLaunchKernelGGL(k_head_conv, dim3(hb), dim3(NET_WG), 0, s, reinterpret_cast<const f32x4 *>(t->A + ae * L), st + ST_WH, st + ST_BH,
                        reinterpret_cast<f32x4 *>(b->Yh), M, b->ws + WS_HP1);
     hipLaunchKernelGGL(k_head_stats_fin, dim3(HC2), dim3(NET_WG), 0, s, b->ws + WS_HP1, hb, M, t->eps, t->momentum, st + ST_MEAN_H, st + ST_INVSTD_H,
                        R ? R->ph_mean : nullptr, R ? R->ph_var : nullptr, R ? R->vh_mean : nullptr, R ? R->vh_var : nullptr);
-    hipLaunchKernelGGL(k_head_bn_apply, dim3((int)std::min<long long>(1024, (M * 8 + NET_WG - 1) / NET_WG)), dim3(NET_WG), 0, s,
+    hipLaunchKernelGGL(k_head_bn_apply, dim3(net_head_bn_apply_grid(M)), dim3(NET_WG), 0, s,
                        reinterpret_cast<const f32x4 *>(b->Yh), reinterpret_cast<f32x4 *>(b->Hh), M * 8, st + ST_MEAN_H, st + ST_INVSTD_H, P->ph_bn_w,
                        P->ph_bn_b, P->vh_bn_w, P->vh_bn_b);
     launch_gemm(s, b->Hh, KF, 1, b->Wc, 1, KF, b->gemm_part, NOp, n, NO, KF, b->bc, FCF_SPLITS, (long long)t->maxN * NOp);
-    hipLaunchKernelGGL(k_head_out, dim3(std::min(1024, (n + 3) / 4)), dim3(NET_WG), 0, s, b->gemm_part, gemm_splits(KF, FCF_SPLITS),
+    hipLaunchKernelGGL(k_head_out, dim3(net_head_out_grid(n)), dim3(NET_WG), 0, s, b->gemm_part, gemm_splits(KF, FCF_SPLITS),
                        (long long)t->maxN * NOp, b->logits, n, A, VF, NOp, P->vh_fc1_w, P->vh_fc1_b, logp, v, b->logp, b->v);
     HIPCHK(t, hipGetLastError());
     t->n = n;
@@ -765,17 +751,17 @@ extern "C" int dbaz_trainer_net_backward(dbaz_trainer *t, const float *x, const 
     hipLaunchKernelGGL(k_fc_wgrad_fin, dim3(512), dim3(NET_WG), 0, s, b->gemm_part, gemm_splits(n, FC_SPLITS), (long long)NO * KF, HW, A, VF, G->ph_fc_w,
                        G->vh_fc0_w);
     launch_gemm(s, b->dlg, NOp, 1, b->Wc, KF, 1, b->dHh, KF, n, KF, NO, nullptr, 1, 0);
-    const int hb2 = (int)std::min<long long>(NET_HB, (M + 31) / 32);
+    const int hb2 = net_head_rows_grid(M);
     hipLaunchKernelGGL(k_head_bn_bwd_sums, dim3(hb2), dim3(NET_WG), 0, s, reinterpret_cast<const f32x4 *>(b->dHh), reinterpret_cast<const f32x4 *>(b->Hh),
                        reinterpret_cast<const f32x4 *>(b->Yh), M, st + ST_MEAN_H, st + ST_INVSTD_H, hp1);
     hipLaunchKernelGGL(k_head_bn_bwd_fin, dim3(HC2), dim3(NET_WG), 0, s, hp1, hb2, b->sums_h, G->ph_bn_w, G->ph_bn_b, G->vh_bn_w, G->vh_bn_b);
     hipLaunchKernelGGL(k_head_bn_bwd_apply, dim3(hb2), dim3(NET_WG), 0, s, reinterpret_cast<f32x4 *>(b->dHh), reinterpret_cast<const f32x4 *>(b->Hh),
                        reinterpret_cast<const f32x4 *>(b->Yh), M, st + ST_MEAN_H, st + ST_INVSTD_H, P->ph_bn_w, P->vh_bn_w, b->sums_h, hp2);
-    const int hsplits = (int)std::min<long long>(HW_SPLITS, (M + 31) / 32);
+    const int hsplits = net_head_wgrad_splits(M);
     launch_gemm(s, b->dHh, 1, HC2, t->A + ae * L, TC, 1, b->gemm_part, TC, HC2, TC, (int)M, nullptr, hsplits, (long long)HC2 * TC);
     hipLaunchKernelGGL(k_head_wgrad_fin, dim3(HC2 * TC / 16 + HC2 / 4), dim3(NET_WG), 0, s, b->gemm_part, gemm_splits((int)M, hsplits), hp2, hb2, G->ph_conv_w,
                        G->vh_conv_w, G->ph_conv_b, G->vh_conv_b);
-    hipLaunchKernelGGL(k_head_conv_bwd_data, dim3((int)std::min<long long>(1024, (M + 31) / 32)), dim3(NET_WG), 0, s,
+    hipLaunchKernelGGL(k_head_conv_bwd_data, dim3(net_head_bwd_data_grid(M)), dim3(NET_WG), 0, s,
                        reinterpret_cast<const f32x4 *>(b->dHh), st + ST_WH, reinterpret_cast<f32x4 *>(t->dA[0]), M);
     // tower; its bottom conv leaves bn0's backward sums
     BelowTower below;
@@ -787,7 +773,7 @@ extern "C" int dbaz_trainer_net_backward(dbaz_trainer *t, const float *x, const 
     unsigned *dymax = t->amax + L + 1;
     train_bn_backward_apply_rows(t, s, t->dA[cur], b->mask0, b->Y0, M, st + ST_MEAN0, st + ST_INVSTD0, P->bn0_w, t->sums, t->dY, dymax, t->part);
     hipLaunchKernelGGL(k_stem_val, dim3(2048), dim3(NET_WG), 0, s, x, st + ST_IN_MEAN, st + ST_IN_INVSTD, M, t->H, t->W, b->val);
-    const int ssplits = (int)std::min<long long>(STEM_SPLITS, (M + 31) / 32);
+    const int ssplits = net_stem_wgrad_splits(M);
     launch_gemm(s, b->val, 1, 36, t->dY, TC, 1, b->stem_part, TC, 36, TC, (int)M, nullptr, ssplits, (long long)36 * TC);
     hipLaunchKernelGGL(k_stem_fin1, dim3(36 * 4), dim3(NET_WG), 0, s, b->stem_part, gemm_splits((int)M, ssplits), b->Gsum);
     hipLaunchKernelGGL(k_stem_fin2, dim3(5), dim3(NET_WG), 0, s, b->Gsum, P->conv0_w, P->bn_input_w, P->bn_input_b, t->part, rb, G->conv0_w, G->conv0_b,

@@ -164,10 +164,14 @@ def _conv_ok(conv, ch):
 
 def supported(model, x):
     """The HIP tower handles ResNetZero containers with 64 channels on a float32 CUDA/HIP tensor whose blocks are exactly what
-    csrc/train.hip computes: 3x3 pad-1 convs with bias, BatchNorm2d with torch's default eps / momentum, affine, running statistics.
+    csrc/train.hip computes: 3x3 pad-1 convs with bias, BatchNorm2d with torch's default eps / momentum, affine, running statistics,
+    on a board the trainer accepts (dbaz_trainer_board_supported).
     Anything else stays on torch (train.training_forward)."""
     r = getattr(model, "resnet", None)
     if not (x.is_cuda and x.dtype == torch.float32 and r is not None and len(r.resblocks) > 0 and r.conv0.out_channels == 64):
+        return False
+    # the board: what dbaz_trainer_create would refuse (more than 196 positions, long thin boards) stays on torch
+    if x.dim() != 4 or not _lib.load().dbaz_trainer_board_supported(x.shape[2] - 1, x.shape[3] - 1):
         return False
     # the BatchNorm2d layers outside the blocks run on dbaz_bn2d_* (any eps / momentum, but a number); a bare block stack has none
     outer = [getattr(model, "bn_input", None), getattr(r, "bn0", None), getattr(getattr(model, "policy_head", None), "bn0", None),

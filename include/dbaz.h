@@ -314,6 +314,9 @@ int dbaz_symmetry_table(int32_t rows, int32_t cols, int32_t sym, int32_t *lut_ou
  * (a hipStream_t, NULL = the default stream).  One handle holds the activations of ONE forward pass for its backward. */
 typedef struct dbaz_trainer dbaz_trainer;
 const char *dbaz_trainer_last_error(const dbaz_trainer *t); /* t == NULL: why dbaz_trainer_create failed */
+/* 1 where dbaz_trainer_create accepts a rows x cols board, 0 where it refuses it (more than 196 positions, or a long thin board
+ * whose weight-gradient images exceed a workgroup's LDS); the reason: dbaz_trainer_last_error(NULL).  Host arithmetic, no device. */
+int dbaz_trainer_board_supported(int32_t rows, int32_t cols);
 int dbaz_trainer_create(int32_t rows, int32_t cols, int32_t channels /* 64 */, int32_t blocks, int32_t max_batch,
                         int32_t device, dbaz_trainer **out);
 void dbaz_trainer_destroy(dbaz_trainer *t);
