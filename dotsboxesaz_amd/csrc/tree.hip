@@ -133,15 +133,16 @@ __device__ __forceinline__ int ring_at(int i, int cap) { return i >= cap ? i - c
 // stack.  Wave-cooperative, wave-uniform state.  Two halves so that the row loads of the batch (all in flight
 // together) can overlap other work of the wave: gc_issue reserves the entries and requests their child rows,
 // gc_finish consumes them.  Only entries that were on the ring at gc_issue are read.
-template <int NB>
+// NJ: the child rows' words per lane that can hold a child (ceil(A / 64) where the caller knows it, else all four)
+template <int NB, int NJ = 4>
 struct GcBatch {
     int k;
     int node[NB];
-    int32_t c[NB][4];
+    int32_t c[NB][NJ];
 };
 
-template <int NB>
-__device__ __forceinline__ void gc_issue(GcBatch<NB> &b, const Geo &g, const TreeBufs &B, int slot, uint32_t *pool, PoolState &q, int lane)
+template <int NB, int NJ>
+__device__ __forceinline__ void gc_issue(GcBatch<NB, NJ> &b, const Geo &g, const TreeBufs &B, int slot, uint32_t *pool, PoolState &q, int lane)
 {
     const int avail = q.tail - q.head;
     b.k = avail < NB ? (avail > 0 ? avail : 0) : NB;
@@ -154,7 +155,7 @@ __device__ __forceinline__ void gc_issue(GcBatch<NB> &b, const Geo &g, const Tre
     for (int t = 0; t < NB; t++) {
         const int32_t *Crow = reinterpret_cast<const int32_t *>(node_ptr(pool, g, b.node[t]) + META_DW + 3 * g.AS);
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
+        for (int j = 0; j < NJ; j++) {
             const int i = lane + WAVE * j;
             b.c[t][j] = (t < b.k && i < g.A) ? Crow[i] : -1;
         }
@@ -162,8 +163,8 @@ __device__ __forceinline__ void gc_issue(GcBatch<NB> &b, const Geo &g, const Tre
     q.head += b.k;
 }
 
-template <int NB>
-__device__ __forceinline__ void gc_finish(const GcBatch<NB> &b, const Geo &g, const TreeBufs &B, int slot, PoolState &q, int lane)
+template <int NB, int NJ>
+__device__ __forceinline__ void gc_finish(const GcBatch<NB, NJ> &b, const Geo &g, const TreeBufs &B, int slot, PoolState &q, int lane)
 {
     if (b.k == 0) return;
     int32_t *pend = B.pend + (size_t)slot * g.cap, *fl = B.freel + (size_t)slot * g.cap;
@@ -172,7 +173,7 @@ __device__ __forceinline__ void gc_finish(const GcBatch<NB> &b, const Geo &g, co
     for (int t = 0; t < NB; t++) {
         if (t < b.k) {
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
+            for (int j = 0; j < NJ; j++) {
                 if (WAVE * j < g.A) {
                     const bool has = b.c[t][j] >= 0;
                     const unsigned long long m = __ballot(has);
@@ -193,8 +194,8 @@ template <int NB>
 __device__ __forceinline__ void pool_collect(const Geo &g, const TreeBufs &B, int slot, uint32_t *pool, PoolState &q, int lane)
 {
     GcBatch<NB> b;
-    gc_issue<NB>(b, g, B, slot, pool, q, lane);
-    gc_finish<NB>(b, g, B, slot, q, lane);
+    gc_issue(b, g, B, slot, pool, q, lane);
+    gc_finish(b, g, B, slot, q, lane);
 }
 
 // UCTNode creation needs an index: recycled first, then fresh, then whatever the collector can still find
@@ -766,10 +767,11 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 {
     Slot *S = B.slots + slot;
     const unsigned long long pw = *reinterpret_cast<volatile const unsigned long long *>(&S->phase); // phase | stamp << 32
-    const int phase = (int)(unsigned)pw;
+    // (one address for the whole wave: say so, and the branches on it are scalar)
+    const int phase = __builtin_amdgcn_readfirstlane((int)(unsigned)pw), stamp = __builtin_amdgcn_readfirstlane((int)(unsigned)(pw >> 32));
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
         return -1;
-    if ((int)(unsigned)(pw >> 32) == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
+    if (stamp == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
         return -1;
     if (cfg.eval_round > 0 && S->pending) {
         // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
@@ -780,9 +782,9 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
     PathEnt *path = B.path + (size_t)slot * g.dmax;
     PoolState q = pool_load(S);
-    GcBatch<GC_PER_STEP> gcb; // the collector's share of this simulation: rows requested now, consumed after the descent
+    GcBatch<GC_PER_STEP, NPL> gcb; // the collector's share of this simulation: rows requested now, consumed after the descent
     gcb.k = 0;
-    if (cfg.gc_lazy <= 0 || q.n_free + (g.cap - q.n_nodes) < cfg.gc_lazy) gc_issue<GC_PER_STEP>(gcb, g, B, slot, pool, q, lane);
+    if (cfg.gc_lazy <= 0 || q.n_free + (g.cap - q.n_nodes) < cfg.gc_lazy) gc_issue(gcb, g, B, slot, pool, q, lane);
     const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, 0u, lane);
     if (lf.err) {
         if (lane == 0) { S->error = lf.err; S->phase = PH_ERROR; }
@@ -793,7 +795,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     // match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the
     // whole search of this move; odd games swap the seats (the reference shuffles them by worker pid)
     const int model = cfg.match_play ? ((lf.root_to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
-    gc_finish<GC_PER_STEP>(gcb, g, B, slot, q, lane);
+    gc_finish(gcb, g, B, slot, q, lane);
     path_put(path, lf.depth, cur, lf.in_move, m, lane);
     if (lane == 0) {
         S->leaf = cur;
@@ -850,13 +852,31 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     return need_eval;
 }
 
-// One wave per game, SELECT_WAVES games per workgroup.  The leaves that need a network evaluation are
+// One wave per game.  Two forms; tree_launch_select picks by cfg.eval_round, and neither form serves the other's path.
+//
+// Sixteen games (SELECT_WAVES) per workgroup wherever this kernel writes the evaluation lists itself (cfg.eval_round == 0:
+// match play, two networks, the manual search calls).  The leaves that need a network evaluation are
 // appended to the per-model lists with ONE global atomic per workgroup and model (positions inside
 // the workgroup come from an LDS counter): a per-wave atomicAdd on the single list counter serialises
 // 8192 same-address atomics per step and was most of this kernel's duration.
-template <int NPL>
-__global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
+//
+// ONE (full rounds only, cfg.eval_round > 0): one game per workgroup.  There this kernel appends to no network list -- it leaves
+// ev_class[slot] for k_order_evals -- so nothing is left to share between the games of a workgroup: no LDS counters, no barrier,
+// and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare endgame
+// leaf goes onto eg_list with the wave's own atomic.
+template <int NPL, bool ONE>
+__global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
+    if (ONE) {
+        const int slot = blockIdx.x, lane = threadIdx.x;
+        if (slot >= n_slots) return;
+        const int model = select_one<NPL>(g, cfg, B, G, slot, lane);
+        if (lane == 0) {
+            B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
+            if (model == SEL_ENDGAME) G.list[atomicAdd(B.n_eval + 3, 1)] = slot;
+        }
+        return;
+    }
     __shared__ int s_cnt[3], s_base[3]; // the two models' lists and eg_list
     const int slot = blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (WAVE - 1);
     if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
@@ -864,10 +884,6 @@ __global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg
     int model = -1;
     if (slot < n_slots) model = select_one<NPL>(g, cfg, B, G, slot, lane);
     int cls = model == SEL_ENDGAME ? 2 : ((model == 0 || model == 1) ? model : -1);
-    if (cfg.eval_round > 0) { // k_order_evals writes the network's list
-        if (slot < n_slots && lane == 0) B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
-        if (cls != 2) cls = -1;
-    }
     int my = -1;
     if (cls >= 0 && lane == 0) my = atomicAdd(&s_cnt[cls], 1);
     __syncthreads();
@@ -888,34 +904,107 @@ __global__ void __launch_bounds__(WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg
 // ev_class; this one workgroup writes the list in slot order, the put-off leaves first, then the leaves of this step -- the same
 // list on every run.  The order starts at slot `rot`, which moves with the step: the leaves behind the cut are spread over the
 // slots as the atomic order spread them, instead of the same top slots waiting every other step.
-__global__ void __launch_bounds__(1024) k_order_evals(TreeBufs B, int n_slots, int rot)
+//
+// The scan kernels (this one and k_driver_scan) are one workgroup of SCAN_T threads that hands every flagged item its rank in item
+// order.  A thread takes item c * SCAN_T + t of each of the NG chunks of a group: the caller issues all NG loads first (they are
+// independent, so they cost one memory round trip, not NG), and scan_ranks turns the flags of all chunks and all NCLS classes
+// into ranks with ONE exchange through LDS: per-wave popcounts in (class, chunk, wave) order, an exclusive scan of that table by
+// the first wave, two barriers.  More items than SCAN_T * NG are taken group after group.
+#define SCAN_T 1024
+#define SCAN_W (SCAN_T / WAVE)
+#define SCAN_NG 8       // chunks per group: the values a thread holds in registers at once ...
+#define SCAN_NG_SMALL 2 // ... and the instance for at most SCAN_T * SCAN_NG_SMALL slots, which does not pay for eight
+
+// fl[cls] bit c: this thread's item of chunk c is in class cls.  rank[cls][c]: the number of class-cls items of the group in front
+// of it (chunk, then thread order); tot[cls]: all of them.  s_pre: NCLS * NG * SCAN_W + 1 ints, free again after the call only
+// behind a barrier.
+template <int NCLS, int NG>
+__device__ __forceinline__ void scan_ranks(int *s_pre, const unsigned (&fl)[NCLS], int (&rank)[NCLS][NG], int (&tot)[NCLS])
 {
-    __shared__ int s_wsum[1024 / WAVE];
+    constexpr int E = NCLS * NG * SCAN_W, PER = E / WAVE;
+    static_assert(E % WAVE == 0, "the first wave scans E / WAVE table entries per lane");
     const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
-    int base = 0;
-    for (int cls = EV_CLASS_DEFERRED; cls >= EV_CLASS_NEW; cls--) {
-        for (int c0 = 0; c0 < n_slots; c0 += 1024) {
-            const int j = c0 + t, i = j + rot < n_slots ? j + rot : j + rot - n_slots;
-            const bool f = j < n_slots && B.ev_class[i] == cls;
-            const unsigned long long m = __ballot(f);
-            if (lane == 0) s_wsum[w] = (int)__popcll(m);
-            __syncthreads();
-            int off = 0, tot = 0;
-            for (int k = 0; k < 1024 / WAVE; k++) {
-                const int v = s_wsum[k];
-                off += k < w ? v : 0;
-                tot += v;
-            }
-            if (f) {
-                const int pos = base + off + (int)__popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int cls = 0; cls < NCLS; cls++) {
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            const unsigned long long m = __ballot((fl[cls] >> c) & 1u);
+            rank[cls][c] = (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) s_pre[(cls * NG + c) * SCAN_W + w] = (int)__popcll(m);
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        int v[PER], sum = 0;
+#pragma unroll
+        for (int k = 0; k < PER; k++) { v[k] = s_pre[lane * PER + k]; sum += v[k]; }
+        int inc = sum;
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const int up = __shfl_up(inc, o);
+            inc += lane >= o ? up : 0;
+        }
+        int ex = inc - sum;
+#pragma unroll
+        for (int k = 0; k < PER; k++) { s_pre[lane * PER + k] = ex; ex += v[k]; }
+        if (lane == WAVE - 1) s_pre[E] = inc;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int cls = 0; cls < NCLS; cls++) {
+        const int first = s_pre[cls * NG * SCAN_W];
+#pragma unroll
+        for (int c = 0; c < NG; c++) rank[cls][c] += s_pre[(cls * NG + c) * SCAN_W + w] - first;
+        tot[cls] = s_pre[(cls + 1) * NG * SCAN_W] - first; // (the entry behind the last class is the grand total)
+    }
+}
+
+template <int NG>
+__global__ void __launch_bounds__(SCAN_T) k_order_evals(TreeBufs B, int n_slots, int rot)
+{
+    __shared__ int s_pre[2 * NG * SCAN_W + 1], s_def[SCAN_W];
+    const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
+    const bool one_group = n_slots <= SCAN_T * NG;
+    // this step's leaves start behind ALL put-off leaves: with more than one group these are counted first
+    int n_def = 0;
+    if (!one_group) {
+        int n = 0;
+        for (int i = t; i < n_slots; i += SCAN_T) n += B.ev_class[i] == EV_CLASS_DEFERRED ? 1 : 0;
+        for (int o = WAVE / 2; o > 0; o >>= 1) n += __shfl_xor(n, o);
+        if (lane == 0) s_def[w] = n;
+        __syncthreads();
+        for (int k = 0; k < SCAN_W; k++) n_def += s_def[k];
+    }
+    int base_def = 0, base_new = 0;
+    for (int g0 = 0; g0 < n_slots; g0 += SCAN_T * NG) {
+        int cl[NG];
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            const int j = g0 + c * SCAN_T + t, i = j + rot < n_slots ? j + rot : j + rot - n_slots;
+            cl[c] = j < n_slots ? B.ev_class[i] : -1;
+        }
+        unsigned fl[2] = {0u, 0u};
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            fl[0] |= (cl[c] == EV_CLASS_DEFERRED ? 1u : 0u) << c;
+            fl[1] |= (cl[c] == EV_CLASS_NEW ? 1u : 0u) << c;
+        }
+        int rank[2][NG], tot[2];
+        scan_ranks<2, NG>(s_pre, fl, rank, tot);
+        if (one_group) n_def = tot[0];
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            if ((fl[0] | fl[1]) >> c & 1u) {
+                const int j = g0 + c * SCAN_T + t, i = j + rot < n_slots ? j + rot : j + rot - n_slots;
+                const int pos = (fl[0] >> c & 1u) ? base_def + rank[0][c] : n_def + base_new + rank[1][c];
                 B.eval_list[pos] = i;
                 B.slots[i].eval_pos = pos;
             }
-            base += tot;
-            __syncthreads();
         }
+        base_def += tot[0];
+        base_new += tot[1];
+        if (g0 + SCAN_T * NG < n_slots) __syncthreads(); // s_pre is written again
     }
-    if (t == 0) B.n_eval[0] = base;
+    if (t == 0) B.n_eval[0] = base_def + base_new;
 }
 
 // Full rounds only (SearchCfg.eval_round > 0).  A network launch costs whole rounds of workgroups (nn.hip): 5 306 leaves are four
@@ -1137,7 +1226,10 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
 // ------------------------------------------------------------------------------------
 // _search tail: prior masking (mcts.py:189-196), expand (:116-119), backup (:121-132)
 // ------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(WAVE) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
+// Four waves per SIMD (second launch bound: at most 128 registers), so that 8 192 slots are two rounds of one-wave workgroups
+// instead of 2.67.  What does not fit is the float64 pow / log / cos of the Dirichlet sampler inlined through end_step ->
+// root_prep -> rng_gamma: the allocator spills there, once per move, and nowhere on the path of an ordinary simulation.
+__global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
@@ -1620,43 +1712,63 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
 // expand/backup).  One workgroup walks the slots in order: the list is in slot order, and the slots whose game ended take the
 // next game indices (generate_games' chunking, self_play.py:291-306) in slot order, so that the same slot plays the same game on
 // every run; a slot left without a game goes idle.
-__global__ void __launch_bounds__(1024) k_driver_scan(SearchCfg cfg, TreeBufs B, int n_slots)
+//
+// The phase words lie one to a Slot, a cache line each: 8 192 of them through ONE compute unit cost more than the scan (31 us,
+// all loads in flight, against 27 us for eight round trips).  So many small workgroups read them first -- k_driver_flags leaves
+// every slot's class in drv_list[i], densely -- and the scan reads that.  Its compacted list goes into the same array: an
+// entry's position is never behind its slot index, and a group's flags are all read before its first store.
+#define DRV_NEEDS 1 // the slot needs the driver
+#define DRV_FRESH 2 // ... and waits for a game index
+__global__ void __launch_bounds__(WAVE) k_driver_flags(TreeBufs B, int n_slots)
 {
-    __shared__ int s_need[1024 / WAVE], s_new[1024 / WAVE];
-    const int t = threadIdx.x, lane = t & (WAVE - 1), w = t / WAVE;
+    const int i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n_slots) return;
+    const int phase = B.slots[i].phase;
+    const bool fresh = phase == PH_NEWGAME;
+    B.drv_list[i] = (phase == PH_EMIT || phase == PH_READY || fresh ? DRV_NEEDS : 0) | (fresh ? DRV_FRESH : 0);
+}
+
+template <int NG>
+__global__ void __launch_bounds__(SCAN_T) k_driver_scan(SearchCfg cfg, TreeBufs B, int n_slots)
+{
+    __shared__ int s_pre[2 * NG * SCAN_W + 1];
+    const int t = threadIdx.x;
     const long long next = *B.next_game;
     long long taken = 0;
     int base = 0;
-    for (int c0 = 0; c0 < n_slots; c0 += 1024) {
-        const int i = c0 + t;
-        const int phase = i < n_slots ? B.slots[i].phase : PH_IDLE;
-        const bool fresh = phase == PH_NEWGAME;
-        const bool need = phase == PH_EMIT || phase == PH_READY || fresh;
-        const unsigned long long m = __ballot(need), mf = __ballot(fresh);
-        if (lane == 0) { s_need[w] = (int)__popcll(m); s_new[w] = (int)__popcll(mf); }
-        __syncthreads();
-        int off = 0, tot = 0, offf = 0, totf = 0;
-        for (int k = 0; k < 1024 / WAVE; k++) {
-            const int v = s_need[k], vf = s_new[k];
-            off += k < w ? v : 0;
-            tot += v;
-            offf += k < w ? vf : 0;
-            totf += vf;
+    for (int g0 = 0; g0 < n_slots; g0 += SCAN_T * NG) {
+        int cl[NG];
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            const int i = g0 + c * SCAN_T + t;
+            cl[c] = i < n_slots ? B.drv_list[i] : 0;
         }
-        if (need) B.drv_list[base + off + (int)__popcll(m & ((1ull << lane) - 1ull))] = i;
-        if (fresh) {
-            const long long gidx = next + taken + offf + (long long)__popcll(mf & ((1ull << lane) - 1ull));
-            Slot *S = B.slots + i;
-            if (gidx < B.last_game) {
-                S->game_idx = gidx;
-            } else {
-                S->game_idx = -1;
-                S->phase = PH_IDLE;
+        unsigned fl[2] = {0u, 0u}; // needs the driver; of those, waits for a game
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            fl[0] |= (cl[c] & DRV_NEEDS ? 1u : 0u) << c;
+            fl[1] |= (cl[c] & DRV_FRESH ? 1u : 0u) << c;
+        }
+        int rank[2][NG], tot[2];
+        scan_ranks<2, NG>(s_pre, fl, rank, tot);
+#pragma unroll
+        for (int c = 0; c < NG; c++) {
+            const int i = g0 + c * SCAN_T + t;
+            if (fl[0] >> c & 1u) B.drv_list[base + rank[0][c]] = i;
+            if (fl[1] >> c & 1u) {
+                const long long gidx = next + taken + (long long)rank[1][c];
+                Slot *S = B.slots + i;
+                if (gidx < B.last_game) {
+                    S->game_idx = gidx;
+                } else {
+                    S->game_idx = -1;
+                    S->phase = PH_IDLE;
+                }
             }
         }
-        base += tot;
-        taken += totf;
-        __syncthreads();
+        base += tot[0];
+        taken += tot[1];
+        if (g0 + SCAN_T * NG < n_slots) __syncthreads(); // s_pre is written again
     }
     if (t == 0) {
         B.drv_count[0] = base;
@@ -1859,11 +1971,22 @@ void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, c
 }
 void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
-    switch ((g.A + WAVE - 1) / WAVE) {
-    case 1: hipLaunchKernelGGL(k_select<1>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
-    case 2: hipLaunchKernelGGL(k_select<2>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
-    case 3: hipLaunchKernelGGL(k_select<3>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
-    default: hipLaunchKernelGGL(k_select<4>, dim3((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), dim3(WAVE * SELECT_WAVES), 0, s, g, c, B, n_slots, G); break;
+    const int npl = (g.A + WAVE - 1) / WAVE;
+    if (c.eval_round > 0) { // k_order_evals writes the network's list: one game per workgroup
+        switch (npl) {
+        case 1: hipLaunchKernelGGL((k_select<1, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        case 2: hipLaunchKernelGGL((k_select<2, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        case 3: hipLaunchKernelGGL((k_select<3, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        default: hipLaunchKernelGGL((k_select<4, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        }
+        return;
+    }
+    const dim3 grid((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), block(WAVE * SELECT_WAVES);
+    switch (npl) {
+    case 1: hipLaunchKernelGGL((k_select<1, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    case 2: hipLaunchKernelGGL((k_select<2, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    case 3: hipLaunchKernelGGL((k_select<3, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    default: hipLaunchKernelGGL((k_select<4, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
     }
 }
 void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
@@ -1900,11 +2023,14 @@ void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c,
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
 {
     const int rot = (int)(((unsigned long long)(unsigned)step * 2654435761ull) % (unsigned long long)n_slots);
-    hipLaunchKernelGGL(k_order_evals, dim3(1), dim3(1024), 0, s, B, n_slots, rot);
+    if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_order_evals<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
+    else hipLaunchKernelGGL(k_order_evals<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
 }
 void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
-    hipLaunchKernelGGL(k_driver_scan, dim3(1), dim3(1024), 0, s, c, B, n_slots);
+    hipLaunchKernelGGL(k_driver_flags, dim3((n_slots + WAVE - 1) / WAVE), dim3(WAVE), 0, s, B, n_slots);
+    if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_driver_scan<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
+    else hipLaunchKernelGGL(k_driver_scan<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
     hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
