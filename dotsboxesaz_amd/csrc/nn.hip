@@ -261,7 +261,8 @@ __device__ __forceinline__ void h3_store(_Float16 *ph, bool valid, f32x4 v)
 }
 
 // words per wave of stamp_out: 0-4 the layer phases, 5-8 the workgroup's phases and its clock, 10-12 the step ends of
-// conv_lds_h3_c2 (DMA wait, step barrier, and the cost of one stamp, each summed over the layers)
+// conv_lds_h3_c2 (DMA wait, step barrier, and the cost of one stamp, each summed over the layers), 13 its step heads (return
+// from the step barrier -> the step's first MFMA is issued)
 #define STAMP_WORDS 16
 #ifdef DBAZ_STAMP
 // diagnostic build only (never shipped): per-wave cycle sums of the layer phases
@@ -527,6 +528,77 @@ __host__ __device__ constexpr int wring_deep_slots(int ntt)
 }
 static_assert(DBAZ_RING_P != 3 || (wring_deep_slots(4) == 3 && wring_deep_slots(3) == 3 && wring_deep_slots(2) == 0 && wring_deep_slots(1) == 0),
               "4 and 3 tiles per wave pair hold the three slots, the smaller bodies keep the two-slot ring");
+// vmcnt of the deep ring's wait at the end of step i of n (ns slots, the two bias loads issued in step bstep): the table in
+// conv_lds_h3_c2.  A wave's vector-memory instructions keep the order of their issue wherever inside their step they stand, so
+// the counts do not depend on where a stream puts its step heads.
+// (One expression for the function and the K-loop, which spells it through the macro: called as a function there, hipcc orders
+// two instructions of the streams without a late head differently, and those keep their listing.)
+#define WRING_VMCNT(i, ns, n, bstep) (((ns) - 2 < (n) - 1 - (i) ? (ns) - 2 : (n) - 1 - (i)) + ((i) == (bstep) ? 2 : 0))
+__host__ __device__ constexpr int wring_vmcnt(int i, int ns, int n, int bstep) { return WRING_VMCNT(i, ns, n, bstep); }
+constexpr bool wring_vmcnt_rows(int ns, int n, int lo, int hi, int want) // steps lo .. hi wait with vmcnt(want)
+{
+    for (int i = lo; i <= hi; i++)
+        if (wring_vmcnt(i, ns, n, n - 2) != want) return false;
+    return true;
+}
+static_assert(wring_vmcnt_rows(3, 18, 0, 0, 1), "step 0: 2, 3 in flight, 2 must have landed");
+static_assert(wring_vmcnt_rows(3, 18, 1, 14, 1), "steps 1 .. N-NS-1: i+2, i+3 in flight, i+2 must have landed");
+static_assert(wring_vmcnt_rows(3, 18, 15, 15, 1), "step N-NS: N-1, n0 in flight, N-1 must have landed");
+static_assert(wring_vmcnt_rows(3, 18, 16, 16, 3), "step N-2: n0, n1, b0, b1 in flight, n0 must have landed");
+static_assert(wring_vmcnt_rows(3, 18, 17, 17, 0), "step N-1: n1, b0, b1 must have landed");
+static_assert(wring_vmcnt_rows(4, 18, 0, 14, 2) && wring_vmcnt_rows(4, 18, 15, 15, 2) && wring_vmcnt_rows(4, 18, 16, 16, 3) &&
+              wring_vmcnt_rows(4, 18, 17, 17, 0), "NS = 4: rows 1-4 leave two pieces out, step N-2 n1, b0, b1, the last step nothing");
+
+// Staggered step heads (patterned streams only).  Waves w and w + 4 share a SIMD, run the same steps between the same barriers
+// and so leave every step barrier together: both issue their ring DMA piece and their four ring reads at that instant, and the
+// matrix pipe has nothing in it.  One half of the workgroup (a compile-time property of the stream: patterns 0, 1 = waves 0-3,
+// patterns 2, 3 = waves 4-7) therefore issues that head block BEHIND its hi*hi phase, in the shadow of its own MFMAs and while
+// its partner's are under way.  0: every head behind the barrier; 1: waves 4-7 late; 2: waves 0-3 late (EXPERIMENTS.md 1).
+#ifndef DBAZ_STAGGER
+#define DBAZ_STAGGER 2 // waves 0-3 late: 3.4 % of the step against 2.7 % with waves 4-7 late (EXPERIMENTS.md 1)
+#endif
+static_assert(DBAZ_STAGGER >= 0 && DBAZ_STAGGER <= 2, "which half of the workgroup issues its step heads late");
+
+// The head block of step i of conv_lds_h3_c2's K-loop (a macro, not a lambda: with a lambda hipcc schedules the prologue of
+// EVERY body differently, and the bodies without a late head must keep their instruction stream):
+//  - the step's DMA.  Two-slot ring: step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the
+//    last barrier); behind the layer's last steps: the first two steps of the next layer.  Deep ring: step i + NS's piece ->
+//    slot i % NS of the destination image.  Its last occupant, step i, was read into registers during step i - 1 and fenced by
+//    that step's barrier; in steps 0 and 1 it had none in this layer, and the image's readers of the previous layer are behind
+//    the layer barrier.  Step 0 also issues steps 2 .. NS - 1, which could not go out earlier for that reason.  Behind the
+//    layer's last step: steps 0 and 1 of the next layer into the two slots behind the images (free since the barrier of step
+//    0), nothing in the steps after that;
+//  - the epilogue's bias (b0, b1: this lane's 4 couts of its two cout tiles), both loads back to back BEHIND the DMA of step
+//    BSTEP, two steps (deep ring) or one step (two-slot ring) before the epilogue needs them: no L2 round trip behind the last MFMA;
+//  - step i + 1's fragments out of their slot (landed and fenced by the barrier that ended step i - 1).
+// It stands behind the step barrier, or (LATE, see DBAZ_STAGGER) behind the step's hi*hi phase and in front of its first
+// activation reload:
+//  - the slot the DMA overwrites was drained by the ring reads of step i - 1, which that step's end wait retired and its
+//    barrier fenced wherever in the step they were issued;
+//  - the ring reads stay older than every activation reload of their step, so the counted lgkmcnt at the step end (two per
+//    tile that keeps the next tap) names the same reads;
+//  - the vector-memory instructions of a wave keep their order, so the vmcnt table stands; a late DMA lands up to one hi*hi
+//    phase later, against a budget of more than one K-step.
+#define C2_STEP_HEAD()                                                                                                          \
+    do {                                                                                                                        \
+        if constexpr (NS == 0) {                                                                                                \
+            if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));                       \
+            else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));                 \
+        } else {                                                                                                                \
+            if (i == 0)                                                                                                         \
+                _Pragma("unroll") for (int j = 2; j < NS; j++) glds16(dsrc + (size_t)j * 128, ring_dst_i + j * (WRING_UNITS * 16)); \
+            if (i + NS < N) glds16(dsrc + (size_t)(i + NS) * 128, ring_dst_i + (i % NS) * (WRING_UNITS * 16));                  \
+            else if (i + NS - N < 2) glds16(dnx + (size_t)(i + NS - N) * 128, ring_dst + (i + NS - N) * (WRING_UNITS * 16));    \
+        }                                                                                                                       \
+        if (i == BSTEP) {                                                                                                       \
+            __builtin_amdgcn_sched_barrier(0);                                                                                  \
+            _Pragma("unroll") for (int c = 0; c < 2; c++) bv[c] = *reinterpret_cast<const f32x4 *>(bias + (ct0 + c) * 16 + gq * 4); \
+        }                                                                                                                       \
+        if (ni < N) {                                                                                                           \
+            const f32x4 *r1 = NS > 0 && ni >= 2 ? rsrc_i + (size_t)(ni % NS) * WRING_UNITS : rsrc + (size_t)(ni & 1) * WRING_UNITS; \
+            a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];                    \
+        }                                                                                                                       \
+    } while (0)
 
 template <int C, int NTT, int PAT = PAT_NONE>
 __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f32x4 *dst4, const f32x4 *__restrict__ wpk /*layer*/,
@@ -539,8 +611,12 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     static_assert(!PERM || NTT == 4, "the row table is built for 4 tiles per wave pair");
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, ua = 0, uc = 0, ud = 0;
     (void)t0; (void)t1; (void)t2; (void)t3; (void)ua; (void)uc; (void)ud; (void)stamps;
-    unsigned w_dma = 0, w_bar = 0, w_cal = 0; // (32-bit sums: eight more 64-bit ones spilled SGPRs into scratch inside the K-loop)
-    (void)w_dma; (void)w_bar; (void)w_cal;
+    unsigned long long uh = 0;
+    (void)uh;
+    unsigned w_dma = 0, w_bar = 0, w_cal = 0, w_head = 0; // (32-bit sums: eight more 64-bit ones spilled SGPRs into scratch inside the K-loop)
+    (void)w_dma; (void)w_bar; (void)w_cal; (void)w_head;
+    // the stream's step heads stand behind its hi*hi phase (DBAZ_STAGGER)
+    constexpr bool LATE = PERM && (DBAZ_STAGGER == 1 ? PAT >= 2 : DBAZ_STAGGER == 2 ? PAT < 2 : false);
     static_assert(C == 64, "two cout tiles per wave x two wave parities = 64 channels");
     constexpr int NS = wring_deep_slots(NTT); // slots of the deep ring at the start of dst4 (0: the two-slot ring alone)
     constexpr int S4 = (C + 8) / 4;  // 16-byte units per LDS row
@@ -618,39 +694,20 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     for (int t = 0; t < NTT; t++)
         if (kept(t, 0)) bl[t].f = *reinterpret_cast<const f32x4 *>(sb + ab[t] + tile_off(t) + LO * 16);
     STAMP(t1);
+#ifdef DBAZ_STAMP
+    ud = t1;
+#endif
 #pragma unroll
     for (int i = 0; i < N; i++) {
         const int cur = i & 1, nxt = (i + 1) & 1;
         const int tap = i / KS, ni = i + 1, ntap = ni / KS, nks = ni % KS;
-        // step i + 2's piece -> slot i & 1 (every wave read step i's fragments out of it before the last barrier); behind the
-        // layer's last steps: the first two steps of the next layer
-        if constexpr (NS == 0) {
-            if (i + 2 < N) glds16(dsrc + (size_t)(i + 2) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-            else if (dnext) glds16(dnext + (size_t)(i + 2 - N) * 128, ring_dst + (i & 1) * (WRING_UNITS * 16));
-        } else {
-            // deep ring: step i + NS's piece -> slot i % NS of the destination image.  Its last occupant, step i, was read into
-            // registers at the start of step i - 1 and fenced by that step's barrier; in steps 0 and 1 it had none in this layer,
-            // and the image's readers of the previous layer are behind the layer barrier.  Step 0 also issues steps 2 .. NS - 1,
-            // which could not go out earlier for that reason.  Behind the layer's last step: steps 0 and 1 of the next layer
-            // into the two slots behind the images (free since the barrier of step 0), nothing in the steps after that.
-            if (i == 0)
-#pragma unroll
-                for (int j = 2; j < NS; j++) glds16(dsrc + (size_t)j * 128, ring_dst_i + j * (WRING_UNITS * 16));
-            if (i + NS < N) glds16(dsrc + (size_t)(i + NS) * 128, ring_dst_i + (i % NS) * (WRING_UNITS * 16));
-            else if (i + NS - N < 2) glds16(dnx + (size_t)(i + NS - N) * 128, ring_dst + (i + NS - N) * (WRING_UNITS * 16));
-        }
-        // the epilogue's bias (b0, b1: this lane's 4 couts of its two cout tiles), both loads back to back BEHIND the step's DMA,
-        // two steps (deep ring) or one step (two-slot ring) before the epilogue needs them: no L2 round trip behind the last MFMA
-        if (i == BSTEP) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int c = 0; c < 2; c++) bv[c] = *reinterpret_cast<const f32x4 *>(bias + (ct0 + c) * 16 + gq * 4);
-        }
-        if (ni < N) { // step i + 1's fragments out of its slot (landed and fenced by the barrier that ended step i - 1)
-            const f32x4 *r1 = NS > 0 && ni >= 2 ? rsrc_i + (size_t)(ni % NS) * WRING_UNITS : rsrc + (size_t)(ni & 1) * WRING_UNITS;
-            a_h[0][nxt].f = r1[0]; a_l[0][nxt].f = r1[64]; a_h[1][nxt].f = r1[128]; a_l[1][nxt].f = r1[192];
-        }
+        if constexpr (!LATE) C2_STEP_HEAD();
         __builtin_amdgcn_sched_barrier(0);
+        // (stamped build: ud -> uh = the step's head, from the return of the step barrier to where its first MFMA is issued.  The
+        // stamp drains lgkmcnt like every other, so behind an early head it holds the return of the four ring reads as well,
+        // which the first MFMA does not wait for: an upper bound of what the head costs.  A stamp that does not wait for its
+        // clock value is no way out: the stamped build spills the value from its SGPRs at once.)
+        STAMP(uh);
         // hi*hi for both cout tiles (the next tap's addresses are computed in their shadow)
 #pragma unroll
         for (int t = 0; t < NTT; t++)
@@ -660,6 +717,10 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             }
         if (ni < N && nks == 0) set_ab(ntap);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (LATE) {
+            C2_STEP_HEAD();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // lo*hi; bh[t] is dead after its second MFMA -> reload it for the next step right there
 #pragma unroll
         for (int t = 0; t < NTT; t++) {
@@ -686,6 +747,9 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
         // (stamped build: ua = the last MFMA is issued, ua -> uc = the return from the step-end wait, uc -> ud = from the step
         // barrier, each with the cost of one stamp on top; a stamp drains lgkmcnt itself, so the first holds the LDS reads too)
         STAMP(ua);
+#ifdef DBAZ_STAMP
+        w_head += (unsigned)(uh - ud); // (ud: the return from the last step barrier, t1 in step 0)
+#endif
         if constexpr (NS == 0) {
             if (ni >= N) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if (n_kept(ntap) == NTT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(%0)" ::"n"(2 * NTT) : "memory");
@@ -712,7 +776,7 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
             // DMA (at NS = 3 that is n1; at NS > 3 the step issues nothing else), which leave two more loads out behind n0;
             // every count is min(NS - 2, N - 1 - i), + 2 in step N - 2, and vmcnt is 0 at the start of a layer: the last step
             // waits for everything, tower_group's prologue too)
-            const int vmw = (NS - 2 < N - 1 - i ? NS - 2 : N - 1 - i) + (i == BSTEP ? 2 : 0);
+            const int vmw = WRING_VMCNT(i, NS, N, BSTEP); // = wring_vmcnt(i, NS, N, BSTEP), whose rows are asserted above
             if (ni >= N) wait_step<-1>(vmw);
             else if (n_kept(ntap) == NTT) wait_step<2 * NTT>(vmw);
             else if (n_kept(ntap) == NTT - 1) wait_step<2 * NTT - 2>(vmw);
@@ -766,9 +830,11 @@ __device__ __forceinline__ void conv_lds_h3_c2(const f32x4 *__restrict__ src4, f
     else epi(Flag<false>{});
     STAMP(t3);
 #ifdef DBAZ_STAMP
-    if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; stamps[4] += w_dma; stamps[5] += w_bar; stamps[6] += w_cal; }
+    if (stamps) { stamps[0] += t1 - t0; stamps[1] += t2 - t1; stamps[2] += t3 - t2; stamps[4] += w_dma; stamps[5] += w_bar; stamps[6] += w_cal; stamps[7] += w_head; }
 #endif
 }
+
+#undef C2_STEP_HEAD
 
 // ------------------------------------------------------------------------------------
 // The whole convolutional trunk in ONE launch per step.  A workgroup owns S samples; their
@@ -1088,7 +1154,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         if constexpr (!C2) {
             if (NL > 0) wpre_load<C>(pre, tw4, wave, lane);
         }
-        unsigned long long stamps[7] = {0, 0, 0, 0, 0, 0, 0};
+        unsigned long long stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         unsigned long long tb0 = 0, tb1 = 0, tk0 = 0, tk1 = 0;
         (void)tb0; (void)tb1; (void)tk0; (void)tk1;
         f32x4 res[2][NTA]; // the residual stream of this wave's outputs (activation-scaled f32): conv_lds_h3_c2 / conv_lds_h3
@@ -1168,7 +1234,7 @@ __device__ __forceinline__ void tower_group(const Geo &g, const TowerArgs &a, fl
         if (a.stamp_out && lane == 0) {
             unsigned long long *o = a.stamp_out + ((size_t)blockIdx.x * 8 + wave) * STAMP_WORDS;
             o[0] = stamps[0]; o[1] = stamps[1]; o[2] = stamps[2]; o[3] = stamps[3]; o[4] = tk1 - tk0;
-            o[10] = stamps[4]; o[11] = stamps[5]; o[12] = stamps[6];
+            o[10] = stamps[4]; o[11] = stamps[5]; o[12] = stamps[6]; o[13] = stamps[7];
         }
 #endif
     }

@@ -53,6 +53,15 @@ print("(MFMA floor per SIMD and layer: 2 waves x 360 MFMAs x 16 = 11520 cycles)"
 for w in range(8):
     print("wave", w, "step-end wait / step barrier per layer, stamps taken off:",
           ["%.0f" % (o[:, w, i].mean() / 40 - c * o[:, w, 12].mean() / 40) for i, c in ((10, 18), (11, 17))])
+# step heads: return from the step barrier (step 0: the layer's first fragment reads are issued) -> the step's first MFMA is
+# issued, 18 per layer, one stamp's cost taken off each.  The stamp drains lgkmcnt, so behind a head that stands at the start of
+# its step the interval holds the return of the four ring reads too (an upper bound of the head's cost); a stream whose head
+# stands behind its hi*hi phase (DBAZ_STAGGER) has nothing but the stamp there.
+print("step heads (step barrier -> first MFMA issued), 18 per layer; cycles per layer and wave, raw / stamps taken off / per step:")
+for w in range(8):
+    raw = o[:, w, 13].mean() / 40
+    net = raw - 18 * o[:, w, 12].mean() / 40
+    print("wave", w, "head %6.0f / %6.0f / %5.1f   = %4.1f %% of the layer" % (raw, net, net / 18, 100 * net / (o[:, w, 4].mean() / 40)))
 whole = o[..., 7].mean()
 print("whole workgroup %.0f cycles: conv0 phase %.0f (%.1f %%), 40 layers %.0f (%.1f %%), head convs + output %.0f (%.1f %%)"
       % (whole, o[..., 5].mean(), 100 * o[..., 5].mean() / whole, tot.mean(), 100 * tot.mean() / whole, o[..., 6].mean(),
