@@ -36,6 +36,8 @@ SYMBOLS = [
     "dbaz_solver_score", "dbaz_perfect_policy", "dbaz_attach_solver",
     "dbaz_endgame_last_error", "dbaz_endgame_create", "dbaz_endgame_destroy", "dbaz_endgame_score", "dbaz_exact_policy", "dbaz_exact_policy_from", "dbaz_attach_endgame",
     "dbaz_get_endgame_stats", "dbaz_exact_targets", "dbaz_dataset_exact_targets",
+    "dbaz_deep_last_error", "dbaz_deep_create", "dbaz_deep_destroy", "dbaz_deep_solve", "dbaz_deep_info", "dbaz_deep_table",
+    "dbaz_deep_score", "dbaz_deep_policy",
 ]
 
 
@@ -189,10 +191,21 @@ def load():
     L.dbaz_get_endgame_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.dbaz_exact_targets.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.dbaz_dataset_exact_targets.argtypes = [vp, vp, i32, i32, vp]
+    L.dbaz_deep_last_error.argtypes = [vp]
+    L.dbaz_deep_last_error.restype = C.c_char_p
+    L.dbaz_deep_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+    L.dbaz_deep_destroy.argtypes = [vp]
+    L.dbaz_deep_destroy.restype = None
+    L.dbaz_deep_solve.argtypes = [vp, vp, i32]
+    L.dbaz_deep_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i32)]
+    L.dbaz_deep_table.argtypes = [vp, vp, i64, i64]
+    L.dbaz_deep_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dbaz_deep_policy.argtypes = [vp, i32, vp, C.c_uint64, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",
-                        "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy", "dbaz_endgame_last_error", "dbaz_endgame_destroy", "dbaz_get_endgame_stats"):
+                        "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy", "dbaz_endgame_last_error", "dbaz_endgame_destroy", "dbaz_get_endgame_stats",
+                        "dbaz_deep_last_error", "dbaz_deep_destroy"):
             fn.restype = C.c_int
     L.dbaz_bn2d_workspace_bytes.restype = C.c_int64
     L.dbaz_az_loss_workspace_bytes.restype = C.c_int64

@@ -170,29 +170,7 @@ static __device__ __forceinline__ void endgame_solve(const EndgameGeo &g, int F,
     }
 }
 
-// The evaluator's epilogue, one wavefront per position, lane = one compact edge of it (at most 64): cand = the lane's edge is
-// free and the game is open, q its worth, action its action index.  Returns the picked action in every lane (-1: no candidate):
-// the k-th member of the optimal set in ascending lane (= action) order, k = 0 without a seed, otherwise
-// solver_pick_mix(key, seed) % n_opt with key = XOR over the free real edges a of 1 << (a & 63) -- a function of the position
-// alone, whatever subgame the lanes are numbered in.
-static __device__ __forceinline__ int endgame_pick(bool cand, int q, int action, uint64_t pick_seed)
-{
-    int best = cand ? q : -1024;
-    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o));
-    uint64_t opt = __ballot(cand && q == best);
-    if (!opt) return -1;
-    int k = 0;
-    if (pick_seed) {
-        uint32_t lo = cand ? (uint32_t)(1ull << (action & 63)) : 0u, hi = cand ? (uint32_t)((1ull << (action & 63)) >> 32) : 0u;
-        for (int o = 32; o > 0; o >>= 1) {
-            lo ^= (uint32_t)__shfl_xor((int)lo, o);
-            hi ^= (uint32_t)__shfl_xor((int)hi, o);
-        }
-        k = (int)(solver_pick_mix(((uint64_t)hi << 32) | lo, pick_seed) % (uint64_t)__popcll(opt));
-    }
-    for (; k > 0; k--) opt &= opt - 1ull;
-    return __shfl(action, __ffsll((long long)opt) - 1);
-}
+// endgame_pick, the evaluator's epilogue (one wavefront per position, lane = one compact edge): solver.h
 
 __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_score(EndgameGeo g, const int16_t *__restrict__ x, const float *__restrict__ pi,
                                                                    int8_t *__restrict__ value, int8_t *__restrict__ diff,

@@ -15,6 +15,9 @@
 //   C. the finished subcube goes to HBM in 16-byte stores.
 // One launch per popcount layer of the high bits (E - L + 1 launches).
 // k_solver_layer: the plain form, one thread per mask and one launch per popcount layer of all E bits (A/B partner).
+//
+// The second half of the file (dbaz_deep_*) runs the same two kernels on the subgame of ONE position of any board, F <= 31 free
+// edges, and answers feature rows from that table (k_deep_score, k_deep_policy).
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -22,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "position_geo.h"
 #include "solver.h"
 
 struct dbaz_solver {
@@ -423,4 +427,384 @@ void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat,
                     uint64_t pick_seed, float *P, float *V, int AS)
 {
     launch_eval<float>(s, stream, feat, list_dev, n_dev, max_n, pick_seed, P, V, AS);
+}
+
+// ====================================================================================
+// Deep endgames: ONE position with F <= 31 free edges on any board (A <= DBAZ_MAX_A), solved by the kernels above
+// ====================================================================================
+// D depends only on which edges are free, so the position is a game over the 2^F subsets of its free edges, and every position
+// that can follow it is an entry of the same table.  position_geometry (position_geo.h) turns the root row into a SolverGeo --
+// E = F, `other` over the compact edges -- and k_solver_subcube / k_solver_layer solve it into int8 T[2^F] in HBM as they solve a
+// whole board; they read g.E and g.other only.  k_deep_score / k_deep_policy then answer feature rows from the table.
+//
+// A row is SERVED when its free real edges are a subset of the root's.  One wavefront per row, lane j = compact edge j of the
+// root (F0 <= 31 < 64): the drawn ones ballot into `mask`, a free lane reads T[mask | 1 << j] and forms Q with solver_move_q;
+// margin and the finished-game test are solver_facts on the boxes counted from planes 0 / 1, as in endgame.hip.
+static_assert(POSITION_NO_BOX == SOLVER_NO_BOX && POSITION_MAX_FREE == SOLVER_MAX_E, "position_geo.h restates solver.h");
+
+#define DEEP_DEFAULT_FREE 24 // 16 MiB, the size of the solved 3x3 board
+#define DEEP_WAVES 4
+
+// the table's root, by value in the kernel arguments
+struct DeepRoot {
+    int32_t rows, cols, HW, A, F;
+    uint64_t free_edges[4];               // the root's free real edges by action index
+    uint32_t other[SOLVER_MAX_E][2];      // solver_move_q's box masks over the compact edges
+    uint8_t act[SOLVER_MAX_E + 1];        // compact edge -> action index
+};
+
+struct dbaz_deep {
+    int rows = 0, cols = 0, dev = 0, max_free = 0;
+    SolverGeo g;                          // of the last root: E = F and `other`
+    DeepRoot root;
+    int8_t *T = nullptr;                  // [2^max_free]; the last root's table is its first 2^F bytes
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t used = nullptr;            // behind the last kernel that reads T on a caller's stream: the next solve waits for it
+    bool solved = false;
+    // the popcount-ordered work lists of the last (F, L) that used k_solver_subcube: they depend on nothing else
+    int list_F = -1, list_L = -1;
+    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
+    uint16_t *low_dev = nullptr;
+    size_t hi_cap = 0, low_cap = 0;       // entries
+    std::vector<uint32_t> hoff;
+    double solve_ms = -1.0;
+    int d0 = -128;
+    std::string err;
+};
+
+static thread_local std::string g_deep_error; // message of a failed dbaz_deep_create; per thread
+
+static int derr(dbaz_deep *d, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (d ? d->err : g_deep_error) = buf;
+    return code;
+}
+
+#define DEEP_HIP(d, call)                                                                                           \
+    do {                                                                                                            \
+        hipError_t _err = (call);                                                                                   \
+        if (_err != hipSuccess) return derr(d, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+    } while (0)
+
+// What one wavefront finds out about its row, the same in every lane unless noted.
+struct DeepRow {
+    uint64_t row_free[4]; // the row's free real edges by action index
+    int n_free;
+    bool served, open;
+    uint32_t m;           // the drawn compact edges of the root
+    RowFacts f;
+    bool cand;            // per lane: compact edge `lane` is free and the game is open
+    int a, q;             // per lane: the edge's action index; its worth (cand only)
+};
+
+template <typename T>
+static __device__ __forceinline__ DeepRow deep_row(const DeepRoot &R, const int8_t *__restrict__ Tb, const T *__restrict__ xr, int lane)
+{
+    DeepRow d;
+    const int W = R.cols + 1, B = R.rows * R.cols;
+    d.n_free = 0;
+    d.served = true;
+#pragma unroll
+    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+        const int a = w * 64 + lane;
+        bool is_free = false;
+        if (a < R.A) {
+            const int p = a / R.HW, l = (a % R.HW) / W, c = a % W;
+            const bool real = p == 0 ? c < R.cols : l < R.rows; // sentinels: board[0,:,W-1] and board[1,H-1,:]
+            is_free = real && xr[a] == (T)0;
+        }
+        d.row_free[w] = __ballot(is_free);
+        d.n_free += __popcll(d.row_free[w]);
+        d.served = d.served && (d.row_free[w] & ~R.free_edges[w]) == 0ull;
+    }
+    const bool edge = lane < R.F;
+    d.a = edge ? (int)R.act[lane] : 0;
+    const bool drawn = edge && xr[d.a] != (T)0;
+    d.m = (uint32_t)__ballot(drawn);
+    int closed = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b = b0 + lane;
+        bool c = false;
+        if (b < B) {
+            const int at = (b / R.cols) * W + b % R.cols;
+            c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[R.HW + at] != (T)0 && xr[R.HW + at + 1] != (T)0;
+        }
+        closed += __popcll(__ballot(c));
+    }
+    d.f = solver_facts(B, closed, (int)xr[2 * R.HW]);
+    d.open = d.f.res == DBAZ_RESULT_NONE;
+    d.cand = d.served && d.open && edge && !drawn;
+    d.q = d.cand ? solver_move_q(R.other[lane][0], R.other[lane][1], d.m, (int)Tb[d.m | (1u << lane)]) : 0;
+    return d;
+}
+
+// dbaz_endgame_score's outputs of the served rows, plus `served`.  q[a] goes out once per action slot: the lane of slot a finds
+// the slot's compact edge as the rank of a in the root's edge set and fetches that lane's Q.  policy_mass: every lane walks the
+// compact edges in ascending order and adds the members' pi in float32 -- k_endgame_score's additions, hence its bits.
+__global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_score(DeepRoot R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x,
+                                                                const float *__restrict__ pi, int n, int8_t *__restrict__ value,
+                                                                int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass,
+                                                                int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
+        const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
+        const int t = d.served ? (int)Tb[d.m] : -128;
+        const int v = !d.served ? 0 : d.open ? sgn(d.f.margin + t) : d.f.res;
+        int8_t *qr = q + (size_t)r * R.A;
+        int before = 0; // root edges in the words below
+#pragma unroll
+        for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+            const int a = w * 64 + lane;
+            const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
+            const int qc = __shfl(d.q, c & 63);
+            const bool is_cand = d.served && d.open && ((d.row_free[w] >> lane) & 1ull);
+            if (a < R.A) qr[a] = (int8_t)(is_cand ? qc : -128);
+            before += __popcll(R.free_edges[w]);
+        }
+        float sum = 0.0f;
+        if (mass) {
+            const float p = d.cand ? pi[(size_t)r * R.A + d.a] : 0.0f;
+            const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
+            for (int c = 0; c < R.F; c++) { // ascending action order
+                const float pc = __shfl(p, c);
+                if ((members >> c) & 1u) sum += pc;
+            }
+        }
+        if (lane == 0) {
+            value[r] = (int8_t)v;
+            diff[r] = (int8_t)t;
+            n_free[r] = (int16_t)d.n_free;
+            served[r] = d.served ? 1 : 0;
+            if (mass) mass[r] = sum;
+        }
+    }
+}
+
+// The table as a (p, v) evaluator with dbaz_exact_policy's outputs: one-hot on endgame_pick's move, v the true result.  A finished
+// game: p = 0, v = get_result; a row that is not served: p = 0, v = 0.
+__global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_policy(DeepRoot R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x, int n,
+                                                                 uint64_t pick_seed, float *__restrict__ P, float *__restrict__ V,
+                                                                 uint8_t *__restrict__ served)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
+        const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
+        const int pick = endgame_pick(d.cand, d.q, d.a, pick_seed);
+        float *pr = P + (size_t)r * R.A;
+        for (int a = lane; a < R.A; a += 64) pr[a] = a == pick ? 1.0f : 0.0f;
+        if (lane == 0) {
+            V[r] = !d.served ? 0.0f : (float)(d.open ? sgn(d.f.margin + (int)Tb[d.m]) : d.f.res);
+            served[r] = d.served ? 1 : 0;
+        }
+    }
+}
+
+extern "C" const char *dbaz_deep_last_error(const dbaz_deep *d) { return d ? d->err.c_str() : g_deep_error.c_str(); }
+
+extern "C" void dbaz_deep_destroy(dbaz_deep *d)
+{
+    if (!d) return;
+    (void)hipSetDevice(d->dev);
+    for (void *b : {(void *)d->T, (void *)d->hi_dev, (void *)d->low_dev, (void *)d->off_dev})
+        if (b) (void)hipFree(b);
+    for (hipEvent_t e : {d->ev0, d->ev1, d->used})
+        if (e) (void)hipEventDestroy(e);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}
+
+extern "C" int dbaz_deep_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_deep **out)
+{
+    if (!out) return derr(nullptr, DBAZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (rows < 1 || cols < 1) return derr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    const long long A = 2ll * (rows + 1ll) * (cols + 1ll);
+    if (A > DBAZ_MAX_A) return derr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
+    if (max_free < 0 || max_free > SOLVER_MAX_E)
+        return derr(nullptr, DBAZ_EINVAL, "max_free %d: a position's table holds 2^F bytes, 1 <= max_free <= %d (0 = %d)", max_free, SOLVER_MAX_E,
+                    DEEP_DEFAULT_FREE);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return derr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+    dbaz_deep *d = new dbaz_deep();
+    d->rows = rows; d->cols = cols; d->dev = device;
+    d->max_free = max_free == 0 ? DEEP_DEFAULT_FREE : max_free;
+    d->g = SolverGeo();
+    d->root = DeepRoot();
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreate(&d->stream);
+    if (e == hipSuccess) e = hipEventCreate(&d->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&d->ev1);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->used, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_solver_subcube, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
+    if (e != hipSuccess) {
+        const std::string msg = hipGetErrorString(e);
+        (void)hipGetLastError();
+        dbaz_deep_destroy(d);
+        return derr(nullptr, DBAZ_EDEVICE, "deep endgame setup failed: %s", msg.c_str());
+    }
+    *out = d;
+    return DBAZ_OK;
+}
+
+// the work lists of (F, L) on the handle: built and copied only when the pair differs from the last solve's
+static int deep_work_lists(dbaz_deep *d, int F, int L)
+{
+    if (d->list_F == F && d->list_L == L) return DBAZ_OK;
+    d->list_F = d->list_L = -1;
+    std::vector<uint32_t> lperm, loff, hperm;
+    popcount_order(L, lperm, loff);
+    popcount_order(F - L, hperm, d->hoff);
+    const std::vector<uint16_t> l16(lperm.begin(), lperm.end());
+    if (hperm.size() > d->hi_cap) {
+        if (d->hi_dev) (void)hipFree(d->hi_dev);
+        d->hi_dev = nullptr;
+        d->hi_cap = 0;
+        DEEP_HIP(d, hipMalloc((void **)&d->hi_dev, hperm.size() * 4));
+        d->hi_cap = hperm.size();
+    }
+    if (l16.size() > d->low_cap) {
+        if (d->low_dev) (void)hipFree(d->low_dev);
+        d->low_dev = nullptr;
+        d->low_cap = 0;
+        DEEP_HIP(d, hipMalloc((void **)&d->low_dev, l16.size() * 2));
+        d->low_cap = l16.size();
+    }
+    if (!d->off_dev) DEEP_HIP(d, hipMalloc((void **)&d->off_dev, (SOLVER_MAX_LOW + 2) * 4));
+    DEEP_HIP(d, hipMemcpy(d->hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice));
+    DEEP_HIP(d, hipMemcpy(d->low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice));
+    DEEP_HIP(d, hipMemcpy(d->off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice));
+    d->list_F = F;
+    d->list_L = L;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_deep_solve(dbaz_deep *d, const int16_t *root_row_host, int32_t low_bits)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (!root_row_host) return derr(d, DBAZ_EINVAL, "dbaz_deep_solve: null root row");
+    d->solved = false; // whatever happens below, the old table is not handed out again
+    PositionGeo pg;
+    position_geometry(d->rows, d->cols, root_row_host, pg);
+    const int F = pg.F;
+    if (F > d->max_free)
+        return derr(d, DBAZ_EINVAL, "the root has %d free edges: this handle's table holds 2^%d bytes (max_free <= %d)", F, d->max_free, SOLVER_MAX_E);
+    const bool plain = low_bits == -1 || F < SOLVER_MIN_LOW;
+    const int L = low_bits == 0 ? default_low_bits(F) : low_bits;
+    if (!plain && (L < SOLVER_MIN_LOW || L > SOLVER_MAX_LOW || L > F || F - L > SOLVER_MAX_HIGH))
+        return derr(d, DBAZ_EINVAL, "low_bits %d: F = %d needs max(%d, F - %d) <= low_bits <= min(F, %d) (0 = default, -1 = plain kernel)",
+                    low_bits, F, SOLVER_MIN_LOW, SOLVER_MAX_HIGH, SOLVER_MAX_LOW);
+    DEEP_HIP(d, hipSetDevice(d->dev));
+    if (!d->T) {
+        const size_t bytes = (size_t)1 << d->max_free;
+        const hipError_t e = hipMalloc((void **)&d->T, bytes);
+        if (e != hipSuccess) {
+            d->T = nullptr;
+            (void)hipGetLastError();
+            return derr(d, DBAZ_EDEVICE, "table of %zu bytes: %s", bytes, hipGetErrorString(e));
+        }
+    }
+    if (!plain) {
+        const int rc = deep_work_lists(d, F, L);
+        if (rc != DBAZ_OK) {
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    d->root = DeepRoot();
+    d->root.rows = d->rows; d->root.cols = d->cols;
+    d->root.HW = (d->rows + 1) * (d->cols + 1); d->root.A = 2 * d->root.HW; d->root.F = F;
+    d->g = SolverGeo();
+    d->g.rows = d->rows; d->g.cols = d->cols; d->g.HW = d->root.HW; d->g.A = d->root.A; d->g.E = F;
+    for (int w = 0; w < 4; w++) d->root.free_edges[w] = pg.free_edges[w];
+    for (int j = 0; j < SOLVER_MAX_E; j++) {
+        d->root.act[j] = pg.act[j];
+        for (int k = 0; k < 2; k++) d->root.other[j][k] = d->g.other[j][k] = pg.other[j][k];
+    }
+    hipError_t e = hipStreamWaitEvent(d->stream, d->used, 0); // rows still being answered from the old table
+    if (e == hipSuccess) e = hipEventRecord(d->ev0, d->stream);
+    if (e == hipSuccess) {
+        if (plain) {
+            const unsigned grid = (unsigned)((((size_t)1 << F) + 255) / 256);
+            for (int k = F; k >= 0; k--) k_solver_layer<<<grid, 256, 0, d->stream>>>(d->g, d->T, k);
+        } else {
+            for (int k = F - L; k >= 0; k--)
+                k_solver_subcube<<<d->hoff[k + 1] - d->hoff[k], SOLVER_THREADS, (size_t)1 << L, d->stream>>>(d->g, d->T, L, d->hi_dev + d->hoff[k],
+                                                                                                            d->low_dev, d->off_dev);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(d->ev1, d->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(d->ev1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, d->ev0, d->ev1);
+    int8_t d0 = 0;
+    if (e == hipSuccess) e = hipMemcpy(&d0, d->T, 1, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return derr(d, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
+    d->solved = true;
+    d->solve_ms = ms;
+    d->d0 = d0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_deep_info(const dbaz_deep *d, int32_t *n_free, int64_t *table_bytes, double *solve_ms, int32_t *d0)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (n_free) *n_free = d->solved ? d->root.F : -1;
+    if (table_bytes) *table_bytes = (int64_t)1 << d->max_free;
+    if (solve_ms) *solve_ms = d->solve_ms;
+    if (d0) *d0 = d->solved ? d->d0 : -128;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_deep_table(dbaz_deep *d, int8_t *host_dst, int64_t first, int64_t count)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_table before a successful dbaz_deep_solve");
+    const int64_t n = (int64_t)1 << d->root.F;
+    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
+        return derr(d, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+    if (count == 0) return DBAZ_OK;
+    DEEP_HIP(d, hipSetDevice(d->dev));
+    DEEP_HIP(d, hipMemcpy(host_dst, d->T + first, (size_t)count, hipMemcpyDeviceToHost));
+    return DBAZ_OK;
+}
+
+static unsigned deep_blocks(int n) { return (unsigned)std::min((n + DEEP_WAVES - 1) / DEEP_WAVES, 16384); }
+
+extern "C" int dbaz_deep_score(dbaz_deep *d, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev, int8_t *q_dev,
+                               float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_score before a successful dbaz_deep_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !value_dev || !diff_dev || !q_dev || !n_free_dev || !served_dev)) || (pi_dev && !mass_dev))
+        return derr(d, DBAZ_EINVAL, "dbaz_deep_score: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    DEEP_HIP(d, hipSetDevice(d->dev));
+    k_deep_score<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->root, d->T, x_dev, pi_dev, n, value_dev, diff_dev, q_dev,
+                                                                             pi_dev ? mass_dev : nullptr, n_free_dev, served_dev);
+    DEEP_HIP(d, hipGetLastError());
+    DEEP_HIP(d, hipEventRecord(d->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev, uint8_t *served_dev,
+                                void *stream)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_policy before a successful dbaz_deep_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !served_dev))) return derr(d, DBAZ_EINVAL, "dbaz_deep_policy: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    DEEP_HIP(d, hipSetDevice(d->dev));
+    k_deep_policy<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->root, d->T, x_dev, n, pick_seed, p_dev, v_dev, served_dev);
+    DEEP_HIP(d, hipGetLastError());
+    DEEP_HIP(d, hipEventRecord(d->used, (hipStream_t)stream));
+    return DBAZ_OK;
 }

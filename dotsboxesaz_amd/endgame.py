@@ -3,9 +3,12 @@
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --bench 4096 [--free 16]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --targets-bench 262144
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --deep-bench 4096 [--free 24]
 
 The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
 over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
+DeepEndgame goes further, up to 31 free edges: one root position solved into a table in HBM by the small-board solver's kernels
+(csrc/solver.hip), and the root and every position after it answered from that table; score_game_tails uses it per game.
 """
 import ctypes as C
 
@@ -169,25 +172,9 @@ class Endgame:
         return (p.cpu().numpy(), v.cpu().numpy()) if as_numpy else (p, v)
 
 
-def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FREE, device=0):
-    """Scores the rows Engine.fetch_samples() / generate_games return (x, pi, played, z) on any board: the counterpart of
-    solver.score_samples for the rows with at most max_free free edges.
-    Per row: value, policy_mass, played_optimal (False for rows without a move and for unsolved rows), n_free, solved.
-    Means: optimal_policy_mass and played_optimal_rate over the solved rows of unfinished positions, z_agreement over the solved
-    rows, coverage = the share of rows solved.  by_free: arrays of length max_free + 1 indexed by the number of free edges --
-    rows (solved rows of that depth), played_optimal_rate, optimal_policy_mass, z_agreement (NaN where there is no row).
-    endgame: an Endgame of the rows' board size (its max_free holds).  Without one the board size comes from rows / cols, or from
-    x's shape [n, 3, H, W]; flat rows [n, 3*H*W] alone do not tell it."""
-    x = np.asarray(samples["x"])
-    if endgame is None:
-        if rows is None or cols is None:
-            if x.ndim != 4:
-                raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or endgame=Endgame(rows, cols)")
-            rows, cols = x.shape[2] - 1, x.shape[3] - 1
-        endgame = Endgame(rows, cols, device, max_free)
-    g, n = endgame, len(x)
-    x = x.reshape(n, g.F)
-    r = g.score(x, np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
+def _row_report(g, x, samples, r):
+    """score_endgames' report from the scored rows r (value, q, policy_mass, n_free, solved) of x [n, 3*H*W]; g: the handle"""
+    n = len(x)
     solved, n_free = r["solved"], r["n_free"].astype(np.int64)
     played = np.asarray(samples["played"]).astype(np.int64).reshape(n)
     has_move = (played >= 0) & (played < g.A)
@@ -210,6 +197,184 @@ def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FRE
                 coverage=float(solved.mean()) if n else 0.0, by_free=by_free)
 
 
+def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FREE, device=0):
+    """Scores the rows Engine.fetch_samples() / generate_games return (x, pi, played, z) on any board: the counterpart of
+    solver.score_samples for the rows with at most max_free free edges.
+    Per row: value, policy_mass, played_optimal (False for rows without a move and for unsolved rows), n_free, solved.
+    Means: optimal_policy_mass and played_optimal_rate over the solved rows of unfinished positions, z_agreement over the solved
+    rows, coverage = the share of rows solved.  by_free: arrays of length max_free + 1 indexed by the number of free edges --
+    rows (solved rows of that depth), played_optimal_rate, optimal_policy_mass, z_agreement (NaN where there is no row).
+    endgame: an Endgame of the rows' board size (its max_free holds).  Without one the board size comes from rows / cols, or from
+    x's shape [n, 3, H, W]; flat rows [n, 3*H*W] alone do not tell it."""
+    x = np.asarray(samples["x"])
+    if endgame is None:
+        if rows is None or cols is None:
+            if x.ndim != 4:
+                raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or endgame=Endgame(rows, cols)")
+            rows, cols = x.shape[2] - 1, x.shape[3] - 1
+        endgame = Endgame(rows, cols, device, max_free)
+    g, n = endgame, len(x)
+    x = x.reshape(n, g.F)
+    r = g.score(x, np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
+    return _row_report(g, x, samples, r)
+
+
+DEEP_FREE = 24  # dbaz_deep_create's default max_free: a table of 16 MiB
+
+
+class DeepEndgame:
+    """One solved table per position (dbaz_deep_*): solve(root_x) solves the subgame of a root position with at
+    most max_free <= 31 free edges into a table of 2^F bytes in HBM; score() and policy() then answer the root and every position
+    that follows it from that table.  A > 256 or max_free outside 1 .. 31 raises DbazError before the device is touched."""
+
+    def __init__(self, rows, cols, device=0, max_free=DEEP_FREE):
+        self._L = _lib.load()
+        self.rows, self.cols, self.device, self.max_free = int(rows), int(cols), int(device), int(max_free)
+        self.H, self.W = self.rows + 1, self.cols + 1
+        self.A, self.F = 2 * self.H * self.W, 3 * self.H * self.W
+        self.h = C.c_void_p()
+        rc = self._L.dbaz_deep_create(self.rows, self.cols, self.device, self.max_free, C.byref(self.h))
+        if rc != _lib.OK:
+            self.h = None
+            self._ck(rc)
+        self.max_free = self.max_free or DEEP_FREE
+        self.actions = edge_actions(self.rows, self.cols)
+        self.n_edges = len(self.actions)
+        self.n_free, self.d0, self.solve_ms, self.table_bytes = -1, ILLEGAL, -1.0, 1 << self.max_free
+
+    def _ck(self, rc):
+        if rc != _lib.OK:
+            msg = self._L.dbaz_deep_last_error(self.h)
+            raise _lib.DbazError(rc, msg.decode() if msg else "error %d" % rc)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dbaz_deep_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _info(self):
+        f, b, ms, d0 = C.c_int32(), C.c_int64(), C.c_double(), C.c_int32()
+        self._ck(self._L.dbaz_deep_info(self.h, C.byref(f), C.byref(b), C.byref(ms), C.byref(d0)))
+        self.n_free, self.table_bytes, self.solve_ms, self.d0 = f.value, b.value, ms.value, d0.value
+
+    def solve(self, root_x, low_bits=0):
+        """root_x: ONE feature row int16 [3*H*W] (or [3, H, W]), a numpy array or a tensor anywhere: the geometry is built on the
+        host.  Replaces the previous root's table; returns self when the table is complete, with n_free, d0, solve_ms (HIP-event
+        time of the solve's kernels) and table_bytes set.  More than max_free free edges raises DbazError (EINVAL) and leaves the
+        handle without a table.  low_bits as for Solver.solve."""
+        if hasattr(root_x, "detach"):
+            root_x = root_x.detach().cpu().numpy()
+        row = np.ascontiguousarray(np.asarray(root_x).reshape(-1), dtype=np.int16)
+        if row.size != self.F:
+            raise ValueError("the root is one feature row of %d values, got %d" % (self.F, row.size))
+        rc = self._L.dbaz_deep_solve(self.h, C.c_void_p(row.ctypes.data), int(low_bits))
+        if rc != _lib.OK:
+            self.n_free, self.d0 = -1, ILLEGAL
+            self._ck(rc)
+        self._info()
+        return self
+
+    def table(self, first=0, count=None):
+        """Host copy of T[first : first + count] of the root's 2^n_free entries (default: all of them) as a numpy int8 array."""
+        count = (1 << max(self.n_free, 0)) - first if count is None else count
+        out = np.empty(max(int(count), 0), np.int8)
+        self._ck(self._L.dbaz_deep_table(self.h, C.c_void_p(out.ctypes.data), C.c_int64(first), C.c_int64(count)))
+        return out
+
+    def _rows(self, x):
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        return dev, as_numpy, xt, int(xt.shape[0])
+
+    def score(self, x, pi=None):
+        """Endgame.score's dict from the table, same conventions in and out; solved [n] = the row is served: its free edges are a
+        subset of the root's.  A row that is not served gets value 0, diff -128, q all -128, policy_mass 0; n_free is the row's own
+        count either way.  Before a successful solve(): DbazError (ESTATE)."""
+        import torch
+        dev, as_numpy, xt, n = self._rows(x)
+        pt = None
+        if pi is not None:
+            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
+            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
+            if int(pt.shape[0]) != n:
+                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
+        value = torch.empty(n, dtype=torch.int8, device=dev)
+        diff = torch.empty(n, dtype=torch.int8, device=dev)
+        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        served = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_deep_score(self.h, C.c_int32(n), ptr(xt), ptr(pt), ptr(value), ptr(diff), ptr(q), ptr(mass), ptr(n_free),
+                                             ptr(served), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=served != 0)
+        if as_numpy:
+            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+        return out
+
+    def policy(self, x, seed=0):
+        """Endgame.policy's (p, v, solved) from the table: the same pick among equally good moves for the same seed; solved [n] =
+        the row is served (p = 0, v = 0 where it is not)."""
+        import torch
+        dev, as_numpy, xt, n = self._rows(x)
+        p = torch.empty((n, self.A), dtype=torch.float32, device=dev)
+        v = torch.empty(n, dtype=torch.float32, device=dev)
+        served = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_deep_policy(self.h, C.c_int32(n), ptr(xt), C.c_uint64(int(seed)), ptr(p), ptr(v), ptr(served),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = (p, v, served != 0)
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
+def score_game_tails(samples, rows=None, cols=None, max_free=DEEP_FREE, device=0, deep=None):
+    """score_endgames for game-ordered rows, as Engine.fetch_samples() returns them (x, pi, played, z, game_idx, move_idx): per
+    game the first row, by move_idx, with at most max_free free edges roots ONE solve (DeepEndgame), and that row and every later
+    row of the game are scored from its table; the rows before it are unsolved.  The same keys with the same definitions as
+    score_endgames, by_free of length max_free + 1, plus tables = solves done and solve_ms = the sum of their kernel times.
+    deep: a DeepEndgame of the rows' board size (its max_free holds); without one the board size comes from rows / cols or from
+    x's shape [n, 3, H, W]."""
+    x = np.asarray(samples["x"])
+    if deep is None:
+        if rows is None or cols is None:
+            if x.ndim != 4:
+                raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or deep=DeepEndgame(rows, cols)")
+            rows, cols = x.shape[2] - 1, x.shape[3] - 1
+        deep = DeepEndgame(rows, cols, device, max_free)
+    g, n = deep, len(x)
+    x = np.ascontiguousarray(x.reshape(n, g.F), dtype=np.int16)
+    pi = np.ascontiguousarray(np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
+    game = np.asarray(samples["game_idx"]).astype(np.int64).reshape(n)
+    n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
+    r = dict(value=np.zeros(n, np.int8), q=np.full((n, g.A), ILLEGAL, np.int8), policy_mass=np.zeros(n, np.float32), n_free=n_free,
+             solved=np.zeros(n, bool))
+    order = np.lexsort((np.asarray(samples["move_idx"]).astype(np.int64).reshape(n), game))
+    tables, solve_ms = 0, 0.0
+    by_game = game[order]
+    bounds = [0] + (np.nonzero(by_game[1:] != by_game[:-1])[0] + 1).tolist() + [n]  # where a new game starts
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        idx = order[lo:hi]
+        late = np.nonzero(n_free[idx] <= g.max_free)[0]
+        if not len(late):
+            continue
+        idx = idx[late[0]:]
+        got = g.solve(x[idx[0]]).score(x[idx], pi[idx])
+        tables, solve_ms = tables + 1, solve_ms + g.solve_ms
+        for k in ("value", "q", "policy_mass", "solved"):
+            r[k][idx] = got[k]
+    return dict(_row_report(g, x, samples, r), tables=tables, solve_ms=solve_ms)
+
+
 def random_rows(rows, cols, n, free, seed=0):
     """n feature rows int16 [n, 3*H*W] with free[i] (or free, a number) free edges in row i: all other edges drawn, at random;
     the closed boxes shared out so that the row is a position of an unfinished game wherever one exists with those edges."""
@@ -226,6 +391,79 @@ def random_rows(rows, cols, n, free, seed=0):
             closed += e[:, l * W + c] & e[:, (l + 1) * W + c] & e[:, HW + l * W + c] & e[:, HW + l * W + c + 1]
     x[:, 2 * HW:] = (rows * cols - 2 * (closed // 2))[:, None]
     return x
+
+
+def random_descendants(rows, cols, root, n, seed=0):
+    """n feature rows int16 [n, 3*H*W] that draw further edges of the feature row `root`: row i keeps a random subset of the
+    root's free edges, of a size uniform in 0 .. F; plane 2 as random_rows sets it."""
+    rs = np.random.RandomState(seed)
+    H, W = rows + 1, cols + 1
+    HW, acts = H * W, edge_actions(rows, cols)
+    root = np.asarray(root, np.int16).reshape(3 * HW)
+    free = acts[root[acts] == 0]
+    x = np.repeat(root[None], n, axis=0)
+    keep = rs.randint(0, len(free) + 1, n)
+    x[:, free] = np.argsort(rs.rand(n, len(free)), axis=1) >= keep[:, None]
+    e = x[:, :2 * HW] != 0
+    closed = np.zeros(n, np.int64)
+    for l in range(rows):
+        for c in range(cols):
+            closed += e[:, l * W + c] & e[:, (l + 1) * W + c] & e[:, HW + l * W + c] & e[:, HW + l * W + c + 1]
+    x[:, 2 * HW:] = (rows * cols - 2 * (closed // 2))[:, None]
+    return x
+
+
+def _deep_bench(a):
+    """One root with a.free free edges: HIP-event milliseconds of dbaz_deep_solve (median of 5 after a warm-up), rows/s of one
+    dbaz_deep_score call on a.deep_bench descendants of the root, and rows/s of one dbaz_endgame_score call on those among them
+    with at most 16 free edges -- the two scorers alternating in the same run, outputs preallocated, median of 5 after a warm-up.
+    Stops if the two disagree on a row both answer."""
+    import torch
+    n, free = a.deep_bench, a.free
+    d = DeepEndgame(a.rows, a.cols, a.device, max(free, 1))
+    free = min(free, d.n_edges)
+    g = Endgame(a.rows, a.cols, a.device)
+    dev = torch.device("cuda", d.device)
+    root = random_rows(a.rows, a.cols, 1, free, seed=5)[0]
+    solve_ms = [d.solve(root, a.low_bits).solve_ms for _ in range(6)][1:]
+    x = random_descendants(a.rows, a.cols, root, n, seed=6)
+    left = (x[:, d.actions] == 0).sum(axis=1)
+    xs = {"deep": torch.as_tensor(x).to(dev), "endgame": torch.as_tensor(x[left <= MAX_FREE]).to(dev)}
+    value, diff = torch.empty(n, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int8, device=dev)
+    q = torch.empty((n, d.A), dtype=torch.int8, device=dev)
+    n_free = torch.empty(n, dtype=torch.int16, device=dev)
+    served = torch.empty(n, dtype=torch.uint8, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    ms = dict(deep=[], endgame=[])
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for i in range(6):
+            for which in ("deep", "endgame"):
+                xt = xs[which]
+                m = C.c_int32(int(xt.shape[0]))
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                if which == "deep":
+                    d._ck(d._L.dbaz_deep_score(d.h, m, ptr(xt), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), ptr(served), stream))
+                else:
+                    g._ck(g._L.dbaz_endgame_score(g.h, m, ptr(xt), None, ptr(value), ptr(diff), ptr(q), None, ptr(n_free), stream))
+                t1.record()
+                t1.synchronize()
+                if i:  # the first run warms up
+                    ms[which].append(t0.elapsed_time(t1))
+            if i == 0:
+                assert bool(served.all().item())  # after the deep call of this round
+    n_late = int(xs["endgame"].shape[0])
+    if n_late:  # a table of any size checks itself against the per-row solver on the rows both answer
+        a_, b_ = d.score(xs["endgame"]), g.score(xs["endgame"])
+        assert all(torch.equal(a_[k], b_[k]) for k in ("value", "diff", "q", "n_free")), "the table and the per-row solver disagree"
+    deep_ms, endgame_ms = float(np.median(ms["deep"])), float(np.median(ms["endgame"]))
+    out = dict(rows=a.rows, cols=a.cols, E=d.n_edges, free=int(free), table_bytes=1 << free, d0=d.d0, solve_ms=round(float(np.median(solve_ms)), 4),
+               deep_rows=int(n), deep_score_ms=round(deep_ms, 4), deep_rows_per_s=round(n / (deep_ms * 1e-3)),
+               endgame_rows=n_late, endgame_score_ms=round(endgame_ms, 4), endgame_rows_per_s=round(n_late / (endgame_ms * 1e-3)) if n_late else 0)
+    d.close()
+    g.close()
+    return out
 
 
 def _bench(g, n, free):
@@ -376,7 +614,12 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-free", type=int, default=MAX_FREE)
     ap.add_argument("--bench", type=int, default=4096, metavar="N", help="rows per timed call (median of 5 after a warm-up)")
-    ap.add_argument("--free", type=int, default=MAX_FREE, help="free edges of every row of the first batch")
+    ap.add_argument("--free", type=int, default=None,
+                    help="free edges of every row of the first batch (default 16); --deep-bench: of the root (default 24)")
+    ap.add_argument("--deep-bench", type=int, default=0, metavar="N",
+                    help="solve one root with --free free edges into an HBM table (DeepEndgame), then time dbaz_deep_score on N descendants "
+                         "next to dbaz_endgame_score on those of them with at most 16 free edges")
+    ap.add_argument("--low-bits", type=int, default=0, help="--deep-bench: 0 = default, L = LDS subcube of 2^L masks, -1 = plain kernel")
     ap.add_argument("--selfplay-bench", type=int, default=0, metavar="N",
                     help="play N complete self-play games with a random-init ResNetZero, with and without the endgame tables attached")
     ap.add_argument("--targets-bench", type=int, default=0, metavar="N",
@@ -388,6 +631,11 @@ def main(argv=None):
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5, help="--selfplay-bench: timed runs per configuration (median)")
     a = ap.parse_args(argv)
+    if a.deep_bench > 0:
+        a.free = DEEP_FREE if a.free is None else a.free
+        print(json.dumps(_deep_bench(a)))
+        return
+    a.free = MAX_FREE if a.free is None else a.free
     if a.selfplay_bench > 0:
         a.slots = a.slots or min(a.selfplay_bench, 8192)
         print(json.dumps(_selfplay_bench(a)))

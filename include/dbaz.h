@@ -527,6 +527,48 @@ int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t
  * them; waits for the engine's queued work.  Either pointer may be NULL.  (Not named dbaz_endgame_*, like dbaz_exact_policy.) */
 void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_solved, int64_t *leaves_served);
 
+/* ---- deep endgames: one solved table per position, up to 31 free edges, on any board ---------------------------
+ * The reference has no counterpart.  A position with F free edges is a game over the 2^F subsets of those edges, and every
+ * position that can follow it is an entry of the same table.  The handle solves ONE root position into int8 T[2^F] in HBM with the
+ * small-board solver's kernels (compact edge j = the root's j-th free real edge in ascending action order; bit j of an index =
+ * that edge has been drawn since) and answers feature rows from it.  A row is SERVED when its free real edges are a subset of the
+ * root's: the root, and every position reached from it.  One table per handle; no dbaz_engine. */
+typedef struct dbaz_deep dbaz_deep;
+const char *dbaz_deep_last_error(const dbaz_deep *d); /* d == NULL: why dbaz_deep_create failed */
+/* max_free: 1 .. 31, 0 = 24 (16 MiB).  rows, cols < 1, A > DBAZ_MAX_A or max_free outside 0 .. 31 -> DBAZ_EINVAL before the device
+ * is touched; the table of 2^max_free bytes is allocated by the first solve and reused by every later one */
+int dbaz_deep_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_deep **out);
+void dbaz_deep_destroy(dbaz_deep *d);
+/* Solves the subgame of root_row, a HOST feature row int16 [3*H*W] (planes 0, 1: edges; sentinel slots are never edges), into
+ * the first 2^F bytes of the table; returns when it is complete.  It replaces the previous root's table, after the
+ * dbaz_deep_score / dbaz_deep_policy calls queued so far have read it.  low_bits as for dbaz_solver_solve with E = F (0 = default,
+ * -1 = the plain kernel; F < 4 always takes the plain kernel); every form writes the same bytes.  The work lists of the subcube
+ * kernel depend on (F, low_bits) only and stay on the handle between solves.
+ *   F > max_free, low_bits out of range -> DBAZ_EINVAL;  a table that cannot be allocated -> DBAZ_EDEVICE.  After either the
+ *   handle has no valid table (DBAZ_ESTATE from the calls below) and stays usable: the next solve starts afresh. */
+int dbaz_deep_solve(dbaz_deep *d, const int16_t *root_row_host, int32_t low_bits);
+/* any pointer may be NULL.  n_free: F of the solved root (-1 without a valid table); table_bytes = 2^max_free; solve_ms: HIP-event
+ * time of the last solve's kernels (-1 before); d0 = T[0], the root's score difference for its mover (-128 without a table) */
+int dbaz_deep_info(const dbaz_deep *d, int32_t *n_free, int64_t *table_bytes, double *solve_ms, int32_t *d0);
+/* host copy of T[first .. first + count) of the 2^F entries */
+int dbaz_deep_table(dbaz_deep *d, int8_t *host_dst, int64_t first, int64_t count);
+/* dbaz_endgame_score's outputs from the table: n feature rows (x, pi as for dbaz_solver_score), DEVICE pointers, QUEUED on the
+ * caller's stream, one wavefront per row.
+ *   n_free [n]       the row's own number of free real edges, served or not
+ *   served [n]       1 when the row's free real edges are a subset of the root's, else 0
+ * A served row: diff = T[mask], value = sign(margin + diff), q[a] of every free edge (-128 for drawn edges and sentinel slots),
+ * policy_mass summed in ascending a in float32 -- bit for bit what dbaz_endgame_score writes where it solves the row.  A finished
+ * game (early end included) gets value = get_result, q all -128 and policy_mass 0.  A row that is not served: value 0, diff -128,
+ * q all -128, policy_mass 0.  pi_dev == NULL: mass_dev is not written.  n == 0 is a no-op; DBAZ_ESTATE without a valid table. */
+int dbaz_deep_score(dbaz_deep *d, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev,
+                    int8_t *q_dev /*[n][A]*/, float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream);
+/* dbaz_exact_policy's outputs from the table: p float32 [n][A] ONE-HOT on the k-th optimal move in ascending action order with
+ * dbaz_exact_policy's k (pick_seed and the position's key), v float32 [n] the true result for the mover; the same pick as
+ * dbaz_exact_policy and dbaz_perfect_policy wherever they apply.  A finished game: p = 0, v = get_result, served = 1; a row that
+ * is not served: p = 0, v = 0, served = 0.  DEVICE pointers, QUEUED on the caller's stream; DBAZ_ESTATE without a valid table. */
+int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev /*[n][A]*/, float *v_dev,
+                     uint8_t *served_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
