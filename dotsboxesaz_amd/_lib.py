@@ -38,6 +38,8 @@ SYMBOLS = [
     "dbaz_get_endgame_stats", "dbaz_exact_targets", "dbaz_dataset_exact_targets",
     "dbaz_deep_last_error", "dbaz_deep_create", "dbaz_deep_destroy", "dbaz_deep_solve", "dbaz_deep_info", "dbaz_deep_table",
     "dbaz_deep_score", "dbaz_deep_policy",
+    "dbaz_tables_last_error", "dbaz_tables_create", "dbaz_tables_destroy", "dbaz_tables_solve", "dbaz_tables_info", "dbaz_tables_roots",
+    "dbaz_tables_table", "dbaz_tables_score", "dbaz_tables_targets",
 ]
 
 
@@ -201,11 +203,22 @@ def load():
     L.dbaz_deep_table.argtypes = [vp, vp, i64, i64]
     L.dbaz_deep_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dbaz_deep_policy.argtypes = [vp, i32, vp, C.c_uint64, vp, vp, vp, vp]
+    L.dbaz_tables_last_error.argtypes = [vp]
+    L.dbaz_tables_last_error.restype = C.c_char_p
+    L.dbaz_tables_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.dbaz_tables_destroy.argtypes = [vp]
+    L.dbaz_tables_destroy.restype = None
+    L.dbaz_tables_solve.argtypes = [vp, i32, vp, i32]
+    L.dbaz_tables_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double)]
+    L.dbaz_tables_roots.argtypes = [vp, vp, vp]
+    L.dbaz_tables_table.argtypes = [vp, i32, vp, i64, i64]
+    L.dbaz_tables_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dbaz_tables_targets.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",
                         "dbaz_az_loss_workspace_bytes", "dbaz_solver_last_error", "dbaz_solver_destroy", "dbaz_endgame_last_error", "dbaz_endgame_destroy", "dbaz_get_endgame_stats",
-                        "dbaz_deep_last_error", "dbaz_deep_destroy"):
+                        "dbaz_deep_last_error", "dbaz_deep_destroy", "dbaz_tables_last_error", "dbaz_tables_destroy"):
             fn.restype = C.c_int
     L.dbaz_bn2d_workspace_bytes.restype = C.c_int64
     L.dbaz_az_loss_workspace_bytes.restype = C.c_int64

@@ -17,7 +17,9 @@
 // k_solver_layer: the plain form, one thread per mask and one launch per popcount layer of all E bits (A/B partner).
 //
 // The second half of the file (dbaz_deep_*) runs the same two kernels on the subgame of ONE position of any board, F <= 31 free
-// edges, and answers feature rows from that table (k_deep_score, k_deep_policy).
+// edges, and answers feature rows from that table (k_deep_score, k_deep_policy).  The last part (dbaz_tables_*)
+// is its batched form: a pool of tables, many roots solved side by side (k_solver_subcube_batch, k_solver_layer_batch) and rows of
+// many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -25,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "deep_batch.h"
 #include "position_geo.h"
 #include "solver.h"
 
@@ -62,26 +65,32 @@ static int serr(dbaz_solver *s, int code, const char *fmt, ...)
 // ------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k)
+// The two solving kernels come in two forms that share their bodies: k_solver_layer / k_solver_subcube take ONE geometry in the
+// kernel arguments, k_solver_layer_batch / k_solver_subcube_batch (further below) one geometry per blockIdx.y from an array in
+// HBM.  other = the geometry's box masks, E its edges, D its table.
+typedef uint32_t SolverOther[SOLVER_MAX_E][2];
+
+static __device__ __forceinline__ void solver_layer_body(const SolverOther &other, int E, int8_t *D, int k)
 {
     const uint32_t m = blockIdx.x * 256u + threadIdx.x;
-    if (m >= (1u << g.E) || __popc(m) != k) return;
-    int best = k == g.E ? 0 : -128;
-    for (int e = 0; e < g.E; e++) {
+    if (m >= (1u << E) || __popc(m) != k) return;
+    int best = k == E ? 0 : -128;
+    for (int e = 0; e < E; e++) {
         if ((m >> e) & 1u) continue;
-        best = max(best, solver_move_q(g.other[e][0], g.other[e][1], m, (int)D[m | (1u << e)]));
+        best = max(best, solver_move_q(other[e][0], other[e][1], m, (int)D[m | (1u << e)]));
     }
     D[m] = (int8_t)best;
 }
 
-__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, int8_t *D, int L, const uint32_t *__restrict__ hi_list,
-                                                                   const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
+__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k) { solver_layer_body(g.other, g.E, D, k); }
+
+static __device__ __forceinline__ void solver_subcube_body(const SolverOther &other, int E, int8_t *D, int L, uint32_t hi,
+                                                           const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
 {
     extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [2^L]
     const uint32_t tid = threadIdx.x;
-    const uint32_t hi = hi_list[blockIdx.x];
     const uint32_t base = hi << L, nlow = 1u << L;
-    const int nh = g.E - L;
+    const int nh = E - L;
 
     // A: running maximum over the moves that draw a high edge
     for (uint32_t chunk = tid * 16u; chunk < nlow; chunk += SOLVER_THREADS * 16u) {
@@ -91,7 +100,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
         for (int h = 0; h < nh; h++) {
             if ((hi >> h) & 1u) continue;
             const int e = L + h;
-            const uint32_t o0 = g.other[e][0], o1 = g.other[e][1];
+            const uint32_t o0 = other[e][0], o1 = other[e][1];
             const uint4 v = *reinterpret_cast<const uint4 *>(D + ((size_t)(base | (1u << e)) + chunk));
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -110,7 +119,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
     __syncthreads();
 
     // B: the moves that draw a low edge, by popcount layers of the low bits
-    const uint32_t full = (1u << g.E) - 1u;
+    const uint32_t full = (1u << E) - 1u;
     for (int k = L; k >= 0; k--) {
         for (uint32_t i = low_off[k] + tid; i < low_off[k + 1]; i += SOLVER_THREADS) {
             const uint32_t low = low_perm[i], m = base | low;
@@ -118,7 +127,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
             for (int b = 0; b < L; b++) {
                 const uint32_t bit = 1u << b;
                 if (low & bit) continue;
-                best = max(best, solver_move_q(g.other[b][0], g.other[b][1], m, (int)sd[low | bit]));
+                best = max(best, solver_move_q(other[b][0], other[b][1], m, (int)sd[low | bit]));
             }
             sd[low] = (int8_t)(m == full ? 0 : best);
         }
@@ -128,6 +137,35 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, 
     // C
     for (uint32_t chunk = tid * 16u; chunk < nlow; chunk += SOLVER_THREADS * 16u)
         *reinterpret_cast<uint4 *>(D + ((size_t)base + chunk)) = *reinterpret_cast<const uint4 *>(sd + chunk);
+}
+
+__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, int8_t *D, int L, const uint32_t *__restrict__ hi_list,
+                                                                   const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
+{
+    solver_subcube_body(g.other, g.E, D, L, hi_list[blockIdx.x], low_perm, low_off);
+}
+
+// One root of a batch (dbaz_tables_solve): what the two bodies read of a SolverGeo, and the table slot the root owns.
+struct BatchGeo {
+    int32_t F, slot;
+    SolverOther other;
+};
+
+// The batched forms: blockIdx.y = the root within a group of roots with the same F (deep_batch.h), geo = the group's geometries;
+// the root's table is T + slot * 2^stride_bits.  Every workgroup reads one geometry, so the reads are wave-uniform.
+__global__ void __launch_bounds__(256) k_solver_layer_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int k)
+{
+    const BatchGeo &g = geo[blockIdx.y];
+    solver_layer_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), k);
+}
+
+__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int L,
+                                                                         const uint32_t *__restrict__ hi_list,
+                                                                         const uint16_t *__restrict__ low_perm,
+                                                                         const uint32_t *__restrict__ low_off)
+{
+    const BatchGeo &g = geo[blockIdx.y];
+    solver_subcube_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), L, hi_list[blockIdx.x], low_perm, low_off);
 }
 
 __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
@@ -246,9 +284,6 @@ static void solver_geometry(int rows, int cols, SolverGeo &g)
             for (int j = 0; j < 4; j++) g.other[ed[j]][used[ed[j]]++] = bm & ~(1u << ed[j]);
         }
 }
-
-// 12 of 24 bits (3x3), 14 of 31 (3x4) measured fastest: small subcubes leave more workgroups per launch
-static int default_low_bits(int E) { return std::min(14, std::max(E / 2, std::min(E, 8))); }
 
 extern "C" const char *dbaz_solver_last_error(const dbaz_solver *s) { return s ? s->err.c_str() : g_solver_error.c_str(); }
 
@@ -547,44 +582,53 @@ static __device__ __forceinline__ DeepRow deep_row(const DeepRoot &R, const int8
 // dbaz_endgame_score's outputs of the served rows, plus `served`.  q[a] goes out once per action slot: the lane of slot a finds
 // the slot's compact edge as the rank of a in the root's edge set and fetches that lane's Q.  policy_mass: every lane walks the
 // compact edges in ascending order and adds the members' pi in float32 -- k_endgame_score's additions, hence its bits.
+// deep_score_row: one row of one wavefront, shared by k_deep_score (one root in the kernel arguments) and k_tables_score (the row's
+// root from an array in HBM).
+static __device__ __forceinline__ void deep_score_row(const DeepRoot &R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x,
+                                                      const float *__restrict__ pi, int r, int lane, int8_t *__restrict__ value,
+                                                      int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass,
+                                                      int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
+{
+    const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
+    const int t = d.served ? (int)Tb[d.m] : -128;
+    const int v = !d.served ? 0 : d.open ? sgn(d.f.margin + t) : d.f.res;
+    int8_t *qr = q + (size_t)r * R.A;
+    int before = 0; // root edges in the words below
+#pragma unroll
+    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+        const int a = w * 64 + lane;
+        const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
+        const int qc = __shfl(d.q, c & 63);
+        const bool is_cand = d.served && d.open && ((d.row_free[w] >> lane) & 1ull);
+        if (a < R.A) qr[a] = (int8_t)(is_cand ? qc : -128);
+        before += __popcll(R.free_edges[w]);
+    }
+    float sum = 0.0f;
+    if (mass) {
+        const float p = d.cand ? pi[(size_t)r * R.A + d.a] : 0.0f;
+        const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
+        for (int c = 0; c < R.F; c++) { // ascending action order
+            const float pc = __shfl(p, c);
+            if ((members >> c) & 1u) sum += pc;
+        }
+    }
+    if (lane == 0) {
+        value[r] = (int8_t)v;
+        diff[r] = (int8_t)t;
+        n_free[r] = (int16_t)d.n_free;
+        served[r] = d.served ? 1 : 0;
+        if (mass) mass[r] = sum;
+    }
+}
+
 __global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_score(DeepRoot R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x,
                                                                 const float *__restrict__ pi, int n, int8_t *__restrict__ value,
                                                                 int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass,
                                                                 int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
 {
     const int lane = threadIdx.x & 63;
-    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
-        const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
-        const int t = d.served ? (int)Tb[d.m] : -128;
-        const int v = !d.served ? 0 : d.open ? sgn(d.f.margin + t) : d.f.res;
-        int8_t *qr = q + (size_t)r * R.A;
-        int before = 0; // root edges in the words below
-#pragma unroll
-        for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
-            const int a = w * 64 + lane;
-            const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
-            const int qc = __shfl(d.q, c & 63);
-            const bool is_cand = d.served && d.open && ((d.row_free[w] >> lane) & 1ull);
-            if (a < R.A) qr[a] = (int8_t)(is_cand ? qc : -128);
-            before += __popcll(R.free_edges[w]);
-        }
-        float sum = 0.0f;
-        if (mass) {
-            const float p = d.cand ? pi[(size_t)r * R.A + d.a] : 0.0f;
-            const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
-            for (int c = 0; c < R.F; c++) { // ascending action order
-                const float pc = __shfl(p, c);
-                if ((members >> c) & 1u) sum += pc;
-            }
-        }
-        if (lane == 0) {
-            value[r] = (int8_t)v;
-            diff[r] = (int8_t)t;
-            n_free[r] = (int16_t)d.n_free;
-            served[r] = d.served ? 1 : 0;
-            if (mass) mass[r] = sum;
-        }
-    }
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES)
+        deep_score_row(R, Tb, x, pi, r, lane, value, diff, q, mass, n_free, served);
 }
 
 // The table as a (p, v) evaluator with dbaz_exact_policy's outputs: one-hot on endgame_pick's move, v the true result.  A finished
@@ -806,5 +850,425 @@ extern "C" int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, u
     k_deep_policy<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->root, d->T, x_dev, n, pick_seed, p_dev, v_dev, served_dev);
     DEEP_HIP(d, hipGetLastError());
     DEEP_HIP(d, hipEventRecord(d->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+// ====================================================================================
+// Deep endgames in batches: a pool of tables, many roots solved side by side, rows answered each from its table
+// ====================================================================================
+// dbaz_tables owns n_tables slots of 2^max_free bytes.  dbaz_tables_solve takes n <= n_tables roots: root i is solved into slot i
+// by k_solver_subcube_batch / k_solver_layer_batch, the roots of equal F sharing their launches (deep_batch.h).  Per root the
+// device keeps a BatchGeo (in plan order, for the solve) and a DeepRoot (by root index, for the rows).  k_tables_score and
+// k_tables_targets then answer rows as k_deep_score does, the root of row r being table_of[r]; an index outside [0, n_solved) is
+// "not served", decided before any address is formed from it.
+static_assert(DEEP_BATCH_MAX_FREE == SOLVER_MAX_E && DEEP_BATCH_MIN_LOW == SOLVER_MIN_LOW && DEEP_BATCH_MAX_LOW == SOLVER_MAX_LOW &&
+                  DEEP_BATCH_MAX_HIGH == SOLVER_MAX_HIGH && DEEP_BATCH_LAYER_THREADS == 256,
+              "deep_batch.h restates solver.h");
+static_assert(sizeof(BatchGeo) == 256, "one root's solve geometry");
+
+#define TABLES_DEFAULT 64 // tables of a pool: 1 GiB at the default max_free
+
+struct TablesBoard {
+    int32_t rows, cols, HW, A;
+};
+
+// the popcount-ordered work lists of one (F, L): they depend on nothing else and stay on the handle
+struct TablesLists {
+    int F = 0, L = 0;
+    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
+    uint16_t *low_dev = nullptr;
+    std::vector<uint32_t> hoff;
+};
+
+struct dbaz_tables {
+    TablesBoard board;
+    int dev = 0, max_free = 0, n_tables = 0;
+    int8_t *T = nullptr;                  // [n_tables][2^max_free]; root i's table is the first 2^F_i bytes of slot i
+    BatchGeo *geo_dev = nullptr;          // [n_tables], in the order of the last solve's plan
+    DeepRoot *roots_dev = nullptr;        // [n_tables], by root index
+    int8_t *d0_dev = nullptr;             // [n_tables]
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t used = nullptr;            // behind the last kernel that reads the pool on a caller's stream: the next solve waits for it
+    int n_solved = 0;
+    std::vector<int32_t> n_free, d0;      // of the solved roots
+    std::vector<BatchGeo> geo_host;       // what the last solve uploaded; alive until its copies are done
+    std::vector<DeepRoot> roots_host;
+    std::vector<TablesLists> lists;
+    double solve_ms = -1.0;
+    std::string err;
+};
+
+static thread_local std::string g_tables_error; // message of a failed dbaz_tables_create; per thread
+
+static int terr(dbaz_tables *t, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    (t ? t->err : g_tables_error) = buf;
+    return code;
+}
+
+#define TABLES_HIP(t, call)                                                                                         \
+    do {                                                                                                            \
+        hipError_t _err = (call);                                                                                   \
+        if (_err != hipSuccess) return terr(t, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+    } while (0)
+
+// T[slot i][0], the score difference of root i for its mover
+__global__ void __launch_bounds__(256) k_tables_heads(const int8_t *__restrict__ T, int stride_bits, int n, int8_t *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = T[(size_t)i << stride_bits];
+}
+
+// the free real edges of a row, for the rows no root is read for (deep_row counts them the same way)
+static __device__ __forceinline__ int tables_row_free(const TablesBoard &B, const int16_t *__restrict__ xr, int lane)
+{
+    const int W = B.cols + 1;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+        const int a = w * 64 + lane;
+        bool is_free = false;
+        if (a < B.A) {
+            const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
+            const bool real = p == 0 ? c < B.cols : l < B.rows; // sentinels: board[0,:,W-1] and board[1,H-1,:]
+            is_free = real && xr[a] == 0;
+        }
+        n += __popcll(__ballot(is_free));
+    }
+    return n;
+}
+
+// k_deep_score with the root of row r = roots[table_of[r]] and its table = T + table_of[r] * 2^stride_bits.
+__global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_score(TablesBoard B, const DeepRoot *__restrict__ roots, int n_solved,
+                                                                  const int8_t *__restrict__ T, int stride_bits, const int16_t *__restrict__ x,
+                                                                  const float *__restrict__ pi, const int32_t *__restrict__ table_of, int n,
+                                                                  int8_t *__restrict__ value, int8_t *__restrict__ diff, int8_t *__restrict__ q,
+                                                                  float *__restrict__ mass, int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
+        const int t = table_of[r];
+        if ((unsigned)t >= (unsigned)n_solved) { // not served: no root, no table
+            const int nf = tables_row_free(B, x + (size_t)r * 3 * B.HW, lane);
+            int8_t *qr = q + (size_t)r * B.A;
+            for (int a = lane; a < B.A; a += 64) qr[a] = -128;
+            if (lane == 0) {
+                value[r] = 0;
+                diff[r] = -128;
+                n_free[r] = (int16_t)nf;
+                served[r] = 0;
+                if (mass) mass[r] = 0.0f;
+            }
+            continue;
+        }
+        deep_score_row(roots[t], T + ((size_t)t << stride_bits), x, pi, r, lane, value, diff, q, mass, n_free, served);
+    }
+}
+
+// dbaz_exact_targets' rule (include/dbaz.h) with v and q from the row's table: a row that is not served or of a finished game is
+// left alone; otherwise z <- v and pi by pi_mode over O = the members, S added in ascending action order in float32 as
+// k_endgame_targets adds it, one float32 division per entry -- hence its bits wherever both apply.  The lane of action slot a
+// finds the slot's compact edge as k_deep_score's epilogue does.  pi and z are read and written by the same wavefront only.
+__global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard B, const DeepRoot *__restrict__ roots, int n_solved,
+                                                                    const int8_t *__restrict__ T, int stride_bits, const int16_t *__restrict__ x,
+                                                                    const int32_t *__restrict__ table_of, int n, int pi_mode, int z_mode, float *pi,
+                                                                    float *z, int16_t *__restrict__ n_free, float *__restrict__ mass,
+                                                                    uint8_t *__restrict__ relabelled)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
+        const int16_t *xr = x + (size_t)r * 3 * B.HW;
+        const int t = table_of[r];
+        int nf = 0;
+        bool touched = false;
+        float sum = 0.0f;
+        if ((unsigned)t >= (unsigned)n_solved) nf = tables_row_free(B, xr, lane);
+        else {
+            const DeepRoot &R = roots[t];
+            const int8_t *Tb = T + ((size_t)t << stride_bits);
+            const DeepRow d = deep_row(R, Tb, xr, lane);
+            nf = d.n_free;
+            if (d.served && d.open) {
+                touched = true;
+                const int v = sgn(d.f.margin + (int)Tb[d.m]);
+                float *pr = pi ? pi + (size_t)r * B.A : nullptr;
+                const float p = pr && d.cand ? pr[d.a] : 0.0f;
+                const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
+                for (int c = 0; c < R.F; c++) { // ascending action order
+                    const float pc = __shfl(p, c);
+                    if ((members >> c) & 1u) sum += pc;
+                }
+                if (pi_mode) {
+                    const bool uniform = pi_mode == 1 || !(sum > 0.0f);
+                    const float share = 1.0f / (float)__popc(members);
+                    int before = 0; // root edges in the words below
+#pragma unroll
+                    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+                        const int a = w * 64 + lane;
+                        const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
+                        const bool member = ((d.row_free[w] >> lane) & 1ull) && ((members >> (c & 31)) & 1u);
+                        if (a < B.A) pr[a] = member ? (uniform ? share : pr[a] / sum) : 0.0f;
+                        before += __popcll(R.free_edges[w]);
+                    }
+                }
+                if (lane == 0 && z_mode) z[r] = (float)v;
+            }
+        }
+        if (lane == 0) {
+            if (n_free) n_free[r] = (int16_t)nf;
+            if (mass) mass[r] = sum;
+            if (relabelled) relabelled[r] = touched ? 1 : 0;
+        }
+    }
+}
+
+extern "C" const char *dbaz_tables_last_error(const dbaz_tables *t) { return t ? t->err.c_str() : g_tables_error.c_str(); }
+
+extern "C" void dbaz_tables_destroy(dbaz_tables *t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->dev);
+    for (void *b : {(void *)t->T, (void *)t->geo_dev, (void *)t->roots_dev, (void *)t->d0_dev})
+        if (b) (void)hipFree(b);
+    for (TablesLists &l : t->lists)
+        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
+            if (b) (void)hipFree(b);
+    for (hipEvent_t e : {t->ev0, t->ev1, t->used})
+        if (e) (void)hipEventDestroy(e);
+    if (t->stream) (void)hipStreamDestroy(t->stream);
+    delete t;
+}
+
+extern "C" int dbaz_tables_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, int32_t n_tables, dbaz_tables **out)
+{
+    if (!out) return terr(nullptr, DBAZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (rows < 1 || cols < 1) return terr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    const long long A = 2ll * (rows + 1ll) * (cols + 1ll);
+    if (A > DBAZ_MAX_A) return terr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
+    if (max_free < 0 || max_free > SOLVER_MAX_E)
+        return terr(nullptr, DBAZ_EINVAL, "max_free %d: a position's table holds 2^F bytes, 1 <= max_free <= %d (0 = %d)", max_free, SOLVER_MAX_E,
+                    DEEP_DEFAULT_FREE);
+    if (n_tables < 0 || n_tables > DEEP_BATCH_MAX_TABLES)
+        return terr(nullptr, DBAZ_EINVAL, "n_tables %d: a pool holds 1 <= n_tables <= %d tables (0 = %d)", n_tables, DEEP_BATCH_MAX_TABLES, TABLES_DEFAULT);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return terr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+    dbaz_tables *t = new dbaz_tables();
+    t->board.rows = rows; t->board.cols = cols;
+    t->board.HW = (rows + 1) * (cols + 1); t->board.A = 2 * t->board.HW;
+    t->dev = device;
+    t->max_free = max_free == 0 ? DEEP_DEFAULT_FREE : max_free;
+    t->n_tables = n_tables == 0 ? TABLES_DEFAULT : n_tables;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreate(&t->stream);
+    if (e == hipSuccess) e = hipEventCreate(&t->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&t->ev1);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->used, hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_solver_subcube_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
+    if (e != hipSuccess) {
+        const std::string msg = hipGetErrorString(e);
+        (void)hipGetLastError();
+        dbaz_tables_destroy(t);
+        return terr(nullptr, DBAZ_EDEVICE, "deep tables setup failed: %s", msg.c_str());
+    }
+    *out = t;
+    return DBAZ_OK;
+}
+
+// the work lists of (F, L) on the handle: built and copied the first time the pair is asked for
+static int tables_work_lists(dbaz_tables *t, int F, int L, int *index)
+{
+    for (size_t i = 0; i < t->lists.size(); i++)
+        if (t->lists[i].F == F && t->lists[i].L == L) {
+            *index = (int)i;
+            return DBAZ_OK;
+        }
+    TablesLists l;
+    l.F = F;
+    l.L = L;
+    std::vector<uint32_t> lperm, loff, hperm;
+    popcount_order(L, lperm, loff);
+    popcount_order(F - L, hperm, l.hoff);
+    const std::vector<uint16_t> l16(lperm.begin(), lperm.end());
+    hipError_t e = hipMalloc((void **)&l.hi_dev, hperm.size() * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&l.low_dev, l16.size() * 2);
+    if (e == hipSuccess) e = hipMalloc((void **)&l.off_dev, loff.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(l.hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(l.low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(l.off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
+            if (b) (void)hipFree(b);
+        (void)hipGetLastError();
+        return terr(t, DBAZ_EDEVICE, "work lists of F = %d, L = %d: %s", F, L, hipGetErrorString(e));
+    }
+    t->lists.push_back(std::move(l));
+    *index = (int)t->lists.size() - 1;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host, int32_t low_bits)
+{
+    if (!t) return DBAZ_EINVAL;
+    t->n_solved = 0; // whatever happens below, the old tables are not handed out again
+    t->n_free.clear();
+    t->d0.clear();
+    if (n_roots < 1 || !roots_host) return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %d roots (at least 1, at most the pool's %d)", n_roots, t->n_tables);
+    if (n_roots > t->n_tables) return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %d roots do not fit a pool of %d tables", n_roots, t->n_tables);
+    const TablesBoard &B = t->board;
+    std::vector<PositionGeo> pg((size_t)n_roots);
+    std::vector<int32_t> F((size_t)n_roots);
+    for (int i = 0; i < n_roots; i++) {
+        position_geometry(B.rows, B.cols, roots_host + (size_t)i * 3 * B.HW, pg[i]);
+        F[i] = pg[i].F;
+    }
+    DeepBatchPlan plan;
+    if (deep_batch_plan(F.data(), n_roots, t->max_free, t->n_tables, low_bits, plan) != 0)
+        return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %s", plan.error.c_str());
+    TABLES_HIP(t, hipSetDevice(t->dev));
+    if (!t->T) {
+        const size_t bytes = (size_t)deep_batch_slot_offset(t->n_tables, t->max_free); // 64 bits: 64 x 2^31 is past 32
+        hipError_t e = hipMalloc((void **)&t->T, bytes);
+        if (e == hipSuccess && !t->geo_dev) e = hipMalloc((void **)&t->geo_dev, (size_t)t->n_tables * sizeof(BatchGeo));
+        if (e == hipSuccess && !t->roots_dev) e = hipMalloc((void **)&t->roots_dev, (size_t)t->n_tables * sizeof(DeepRoot));
+        if (e == hipSuccess && !t->d0_dev) e = hipMalloc((void **)&t->d0_dev, (size_t)t->n_tables);
+        if (e != hipSuccess) {
+            if (t->T) (void)hipFree(t->T);
+            t->T = nullptr;
+            (void)hipGetLastError();
+            return terr(t, DBAZ_EDEVICE, "pool of %d tables, %zu bytes: %s", t->n_tables, bytes, hipGetErrorString(e));
+        }
+    }
+    std::vector<int> lists(plan.groups.size(), -1); // per group, its entry of t->lists
+    for (size_t g = 0; g < plan.groups.size(); g++)
+        if (!plan.groups[g].plain) {
+            const int rc = tables_work_lists(t, plan.groups[g].F, plan.groups[g].L, &lists[g]);
+            if (rc != DBAZ_OK) return rc;
+        }
+
+    t->geo_host.assign((size_t)n_roots, BatchGeo());
+    t->roots_host.assign((size_t)n_roots, DeepRoot());
+    for (int at = 0; at < n_roots; at++) {
+        const int i = plan.order[at];
+        BatchGeo &bg = t->geo_host[at];
+        DeepRoot &R = t->roots_host[i];
+        bg.F = F[i];
+        bg.slot = i;
+        R.rows = B.rows; R.cols = B.cols; R.HW = B.HW; R.A = B.A; R.F = F[i];
+        for (int w = 0; w < 4; w++) R.free_edges[w] = pg[i].free_edges[w];
+        for (int j = 0; j < SOLVER_MAX_E; j++) {
+            R.act[j] = pg[i].act[j];
+            for (int k = 0; k < 2; k++) R.other[j][k] = bg.other[j][k] = pg[i].other[j][k];
+        }
+    }
+    hipError_t e = hipStreamWaitEvent(t->stream, t->used, 0); // rows still being answered from the old tables and roots
+    if (e == hipSuccess) e = hipMemcpyAsync(t->geo_dev, t->geo_host.data(), (size_t)n_roots * sizeof(BatchGeo), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->roots_dev, t->roots_host.data(), (size_t)n_roots * sizeof(DeepRoot), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipEventRecord(t->ev0, t->stream);
+    if (e == hipSuccess) {
+        for (const DeepBatchLaunch &l : plan.launches) { // back to back: no host synchronisation between groups
+            const DeepBatchGroup &g = plan.groups[l.group];
+            const dim3 grid(l.grid_x, l.grid_y);
+            if (g.plain) k_solver_layer_batch<<<grid, 256, 0, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, l.k);
+            else {
+                const TablesLists &w = t->lists[(size_t)lists[l.group]];
+                k_solver_subcube_batch<<<grid, SOLVER_THREADS, (size_t)1 << g.L, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, g.L,
+                                                                                             w.hi_dev + w.hoff[l.k], w.low_dev, w.off_dev);
+            }
+        }
+        k_tables_heads<<<(n_roots + 255) / 256, 256, 0, t->stream>>>(t->T, t->max_free, n_roots, t->d0_dev);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(t->ev1, t->stream);
+    std::vector<int8_t> heads((size_t)n_roots);
+    if (e == hipSuccess) e = hipMemcpyAsync(heads.data(), t->d0_dev, (size_t)n_roots, hipMemcpyDeviceToHost, t->stream);
+    const hipError_t done = hipStreamSynchronize(t->stream); // also on a failure above: the host buffers leave scope
+    if (e == hipSuccess) e = done;
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, t->ev0, t->ev1);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return terr(t, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
+    }
+    t->n_free.assign(F.begin(), F.end());
+    t->d0.assign(heads.begin(), heads.end());
+    t->solve_ms = ms;
+    t->n_solved = n_roots;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_info(const dbaz_tables *t, int32_t *n_solved, int64_t *table_bytes, int64_t *pool_bytes, double *solve_ms)
+{
+    if (!t) return DBAZ_EINVAL;
+    if (n_solved) *n_solved = t->n_solved;
+    if (table_bytes) *table_bytes = (int64_t)1 << t->max_free;
+    if (pool_bytes) *pool_bytes = (int64_t)t->n_tables << t->max_free;
+    if (solve_ms) *solve_ms = t->solve_ms;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_roots(const dbaz_tables *t, int32_t *n_free_out, int32_t *d0_out)
+{
+    if (!t) return DBAZ_EINVAL;
+    if (n_free_out) std::copy(t->n_free.begin(), t->n_free.end(), n_free_out);
+    if (d0_out) std::copy(t->d0.begin(), t->d0.end(), d0_out);
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_table(dbaz_tables *t, int32_t i, int8_t *host_dst, int64_t first, int64_t count)
+{
+    if (!t) return DBAZ_EINVAL;
+    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_table before a successful dbaz_tables_solve");
+    if (i < 0 || i >= t->n_solved) return terr(t, DBAZ_EINVAL, "table %d: the last solve filled tables 0 .. %d", i, t->n_solved - 1);
+    const int64_t n = (int64_t)1 << t->n_free[(size_t)i];
+    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
+        return terr(t, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+    if (count == 0) return DBAZ_OK;
+    TABLES_HIP(t, hipSetDevice(t->dev));
+    TABLES_HIP(t, hipMemcpy(host_dst, t->T + deep_batch_slot_offset(i, t->max_free) + first, (size_t)count, hipMemcpyDeviceToHost));
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_score(dbaz_tables *t, int32_t n, const int16_t *x_dev, const float *pi_dev, const int32_t *table_dev, int8_t *value_dev,
+                                 int8_t *diff_dev, int8_t *q_dev, float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
+{
+    if (!t) return DBAZ_EINVAL;
+    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_score before a successful dbaz_tables_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !table_dev || !value_dev || !diff_dev || !q_dev || !n_free_dev || !served_dev)) || (pi_dev && !mass_dev))
+        return terr(t, DBAZ_EINVAL, "dbaz_tables_score: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    TABLES_HIP(t, hipSetDevice(t->dev));
+    k_tables_score<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(t->board, t->roots_dev, t->n_solved, t->T, t->max_free, x_dev, pi_dev,
+                                                                               table_dev, n, value_dev, diff_dev, q_dev, pi_dev ? mass_dev : nullptr,
+                                                                               n_free_dev, served_dev);
+    TABLES_HIP(t, hipGetLastError());
+    TABLES_HIP(t, hipEventRecord(t->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_dev, const int32_t *table_dev, int32_t pi_mode, int32_t z_mode,
+                                   float *pi_dev, float *z_dev, int16_t *n_free_dev, float *mass_dev, uint8_t *relabelled_dev, void *stream)
+{
+    if (!t) return DBAZ_EINVAL;
+    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_targets before a successful dbaz_tables_solve");
+    if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1)
+        return terr(t, DBAZ_EINVAL, "dbaz_tables_targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode,
+                    z_mode);
+    if (n < 0 || (n > 0 && (!x_dev || !table_dev || (pi_mode != 0 && !pi_dev) || (z_mode != 0 && !z_dev))))
+        return terr(t, DBAZ_EINVAL, "dbaz_tables_targets: bad argument (n = %d; a mode other than keep needs its array)", n);
+    if (n == 0) return DBAZ_OK;
+    TABLES_HIP(t, hipSetDevice(t->dev));
+    k_tables_targets<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(t->board, t->roots_dev, t->n_solved, t->T, t->max_free, x_dev, table_dev,
+                                                                                 n, pi_mode, z_mode, pi_dev, z_dev, n_free_dev, mass_dev, relabelled_dev);
+    TABLES_HIP(t, hipGetLastError());
+    TABLES_HIP(t, hipEventRecord(t->used, (hipStream_t)stream));
     return DBAZ_OK;
 }

@@ -4,11 +4,15 @@
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --targets-bench 262144
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --deep-bench 4096 [--free 24]
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --tables-bench 64 --free 20
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --tails-bench 1024 --reads 20 --free 24 [--tables 64]
 
 The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
 over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
 DeepEndgame goes further, up to 31 free edges: one root position solved into a table in HBM by the small-board solver's kernels
 (csrc/solver.hip), and the root and every position after it answered from that table; score_game_tails uses it per game.
+DeepTables is the batched form: a pool of such tables, many roots solved side by side, rows of many games answered in one launch
+(score_game_tails(tables=), game_tail_targets).
 """
 import ctypes as C
 
@@ -337,13 +341,238 @@ class DeepEndgame:
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
 
-def score_game_tails(samples, rows=None, cols=None, max_free=DEEP_FREE, device=0, deep=None):
+DEEP_TABLES = 64  # dbaz_tables_create's default n_tables: a pool of 1 GiB at max_free 24
+
+
+class DeepTables:
+    """A pool of solved tables (dbaz_tables_*): solve(roots_x) solves up to n_tables root positions side by side,
+    root i into table i; score() and targets() then answer rows of many games in one launch, row r from table table_of[r].
+    A > 256, max_free outside 1 .. 31 or n_tables outside 1 .. 65535 raises DbazError before the device is touched."""
+
+    def __init__(self, rows, cols, device=0, max_free=DEEP_FREE, n_tables=DEEP_TABLES):
+        self._L = _lib.load()
+        self.rows, self.cols, self.device, self.max_free, self.n_tables = int(rows), int(cols), int(device), int(max_free), int(n_tables)
+        self.H, self.W = self.rows + 1, self.cols + 1
+        self.A, self.F = 2 * self.H * self.W, 3 * self.H * self.W
+        self.h = C.c_void_p()
+        rc = self._L.dbaz_tables_create(self.rows, self.cols, self.device, self.max_free, self.n_tables, C.byref(self.h))
+        if rc != _lib.OK:
+            self.h = None
+            self._ck(rc)
+        self.max_free, self.n_tables = self.max_free or DEEP_FREE, self.n_tables or DEEP_TABLES
+        self.actions = edge_actions(self.rows, self.cols)
+        self.n_edges = len(self.actions)
+        self.n_solved, self.n_free, self.d0 = 0, np.zeros(0, np.int32), np.zeros(0, np.int32)
+        self.solve_ms, self.table_bytes, self.pool_bytes = -1.0, 1 << self.max_free, self.n_tables << self.max_free
+
+    def _ck(self, rc):
+        if rc != _lib.OK:
+            msg = self._L.dbaz_tables_last_error(self.h)
+            raise _lib.DbazError(rc, msg.decode() if msg else "error %d" % rc)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.dbaz_tables_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _info(self):
+        n, b, p, ms = C.c_int32(), C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._L.dbaz_tables_info(self.h, C.byref(n), C.byref(b), C.byref(p), C.byref(ms)))
+        self.n_solved, self.table_bytes, self.pool_bytes, self.solve_ms = n.value, b.value, p.value, ms.value
+        self.n_free, self.d0 = np.zeros(self.n_solved, np.int32), np.zeros(self.n_solved, np.int32)
+        self._ck(self._L.dbaz_tables_roots(self.h, C.c_void_p(self.n_free.ctypes.data), C.c_void_p(self.d0.ctypes.data)))
+
+    def solve(self, roots_x, low_bits=0):
+        """roots_x: 1 .. n_tables feature rows int16 [m, 3*H*W] (or [m, 3, H, W]), a numpy array or a tensor anywhere: the
+        geometries are built on the host.  Replaces every table of the previous solve; returns self when the tables are complete,
+        with n_solved, n_free[m], d0[m], solve_ms (HIP-event time of the solve's kernels, all roots together) and pool_bytes set.
+        A root with more than max_free free edges, more roots than tables, or a low_bits that does not fit some root raises
+        DbazError (EINVAL) and leaves the handle with n_solved = 0.  low_bits as for DeepEndgame.solve, for every root."""
+        if hasattr(roots_x, "detach"):
+            roots_x = roots_x.detach().cpu().numpy()
+        r = np.ascontiguousarray(np.asarray(roots_x).reshape(-1, self.F), dtype=np.int16)
+        rc = self._L.dbaz_tables_solve(self.h, C.c_int32(len(r)), C.c_void_p(r.ctypes.data), int(low_bits))
+        if rc != _lib.OK:
+            self.n_solved, self.n_free, self.d0 = 0, np.zeros(0, np.int32), np.zeros(0, np.int32)
+            self._ck(rc)
+        self._info()
+        return self
+
+    def table(self, i, first=0, count=None):
+        """Host copy of T_i[first : first + count] of root i's 2^n_free[i] entries (default: all of them) as a numpy int8 array."""
+        if count is None:
+            count = (1 << int(self.n_free[i])) - first if 0 <= i < self.n_solved else 0
+        out = np.empty(max(int(count), 0), np.int8)
+        self._ck(self._L.dbaz_tables_table(self.h, C.c_int32(int(i)), C.c_void_p(out.ctypes.data), C.c_int64(first), C.c_int64(count)))
+        return out
+
+    def _rows(self, x, table_of):
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        tt = torch.as_tensor(np.ascontiguousarray(table_of, dtype=np.int32) if not isinstance(table_of, torch.Tensor) else table_of)
+        tt = tt.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        if int(tt.shape[0]) != int(xt.shape[0]):
+            raise ValueError("table_of has %d entries, x has %d rows" % (tt.shape[0], xt.shape[0]))
+        return dev, as_numpy, xt, tt, int(xt.shape[0])
+
+    def score(self, x, table_of, pi=None):
+        """DeepEndgame.score's dict for rows of many games: table_of int32 [n] names each row's table, the index of its root in
+        the last solve().  solved [n] = the row is served: table_of is in 0 .. n_solved - 1 and the row's free edges are a subset
+        of that root's.  Every other row gets the unsolved outputs; n_free is the row's own count either way.  Before a successful
+        solve(): DbazError (ESTATE)."""
+        import torch
+        dev, as_numpy, xt, tt, n = self._rows(x, table_of)
+        pt = None
+        if pi is not None:
+            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
+            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
+            if int(pt.shape[0]) != n:
+                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
+        value = torch.empty(n, dtype=torch.int8, device=dev)
+        diff = torch.empty(n, dtype=torch.int8, device=dev)
+        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        served = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_tables_score(self.h, C.c_int32(n), ptr(xt), ptr(pt), ptr(tt), ptr(value), ptr(diff), ptr(q), ptr(mass), ptr(n_free),
+                                               ptr(served), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=served != 0)
+        if as_numpy:
+            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+        return out
+
+    def targets(self, x, table_of, pi, z, pi_mode="restrict", z_mode=True):
+        """Endgame.targets from the tables (dbaz_tables_targets), for rows of any depth a table serves: x, pi, z, the modes and
+        the returned (pi', z', info) as there, table_of as for score().  A served row of an unfinished game is relabelled; every
+        other row comes back bit for bit.  The caller's arrays are never modified."""
+        import torch
+        pm, zm = target_modes(pi_mode, z_mode)
+        dev, as_numpy, xt, tt, n = self._rows(x, table_of)
+        z_shape = tuple(z.shape)
+
+        def own(t, cols):  # a contiguous float32 copy on the device that this call may write
+            t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float32) if not isinstance(t, torch.Tensor) else t)
+            return t.to(device=dev, dtype=torch.float32).reshape(-1, cols).clone(memory_format=torch.contiguous_format)
+        pt, zt = own(pi, self.A), own(z, 1).reshape(-1)
+        if int(pt.shape[0]) != n or int(zt.shape[0]) != n:
+            raise ValueError("x has %d rows, pi %d, z %d" % (n, pt.shape[0], zt.shape[0]))
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev)
+        relabelled = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        with torch.cuda.device(dev):
+            self._ck(self._L.dbaz_tables_targets(self.h, C.c_int32(n), ptr(xt), ptr(tt), C.c_int32(pm), C.c_int32(zm), ptr(pt), ptr(zt), ptr(n_free),
+                                                 ptr(mass), ptr(relabelled), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        info = dict(n_free=n_free, mass=mass, relabelled=relabelled != 0)
+        zt = zt.reshape(z_shape)
+        if as_numpy:
+            return pt.cpu().numpy(), zt.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+        return pt, zt, info
+
+
+def _game_roots(game, move, n_free, max_free):
+    """Game-ordered rows in any order -> (root [g]: per game that has one, the index of its first row by move_idx with at most
+    max_free free edges; table_of [n]: per row the position of its game's root in `root` if the row is that root or comes after
+    it, else -1)."""
+    n = len(game)
+    order = np.lexsort((move, game))
+    by_game = game[order]
+    bounds = [0] + (np.nonzero(by_game[1:] != by_game[:-1])[0] + 1).tolist() + [n]  # where a new game starts
+    root, table_of = [], np.full(n, -1, np.int32)
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        idx = order[lo:hi]
+        late = np.nonzero(n_free[idx] <= max_free)[0]
+        if len(late):
+            table_of[idx[late[0]:]] = len(root)
+            root.append(idx[late[0]])
+    return np.asarray(root, np.int64), table_of
+
+
+def _tables_handle(tables, x, rows, cols, max_free, device, what):
+    if isinstance(tables, DeepTables):
+        return tables
+    if rows is None or cols is None:
+        if x.ndim != 4:
+            raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or %s" % what)
+        rows, cols = x.shape[2] - 1, x.shape[3] - 1
+    return DeepTables(rows, cols, device, max_free, int(tables))
+
+
+def _score_game_tails_batched(samples, rows, cols, max_free, device, tables):
+    """score_game_tails' batched path: the games in chunks of n_tables, one solve and one score per chunk"""
+    x = np.asarray(samples["x"])
+    g = _tables_handle(tables, x, rows, cols, max_free, device, "tables=DeepTables(rows, cols)")
+    n = len(x)
+    x = np.ascontiguousarray(x.reshape(n, g.F), dtype=np.int16)
+    pi = np.ascontiguousarray(np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
+    game = np.asarray(samples["game_idx"]).astype(np.int64).reshape(n)
+    move = np.asarray(samples["move_idx"]).astype(np.int64).reshape(n)
+    n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
+    r = dict(value=np.zeros(n, np.int8), q=np.full((n, g.A), ILLEGAL, np.int8), policy_mass=np.zeros(n, np.float32), n_free=n_free,
+             solved=np.zeros(n, bool))
+    root, table_of = _game_roots(game, move, n_free, g.max_free)
+    solve_ms = 0.0
+    for lo in range(0, len(root), g.n_tables):
+        hi = min(lo + g.n_tables, len(root))
+        idx = np.nonzero((table_of >= lo) & (table_of < hi))[0]
+        got = g.solve(x[root[lo:hi]]).score(x[idx], table_of[idx] - lo, pi[idx])
+        solve_ms += g.solve_ms
+        for k in ("value", "q", "policy_mass", "solved"):
+            r[k][idx] = got[k]
+    return dict(_row_report(g, x, samples, r), tables=len(root), solve_ms=solve_ms)
+
+
+def game_tail_targets(samples, rows=None, cols=None, max_free=DEEP_FREE, tables=DEEP_TABLES, pi_mode="restrict", z_mode=True, device=0):
+    """Exact training targets for game-ordered rows, as Engine.fetch_samples() returns them (x, pi, z, game_idx, move_idx), in
+    any order: per game the first row, by move_idx, with at most max_free free edges roots one table, and that row and every
+    later row of an unfinished position of the game are relabelled from it as Endgame.targets relabels the rows it solves
+    (DeepTables.targets); the rows before a game's root come back bit for bit.  The games go through the pool in chunks of its
+    n_tables.  tables: the pool's size, or a DeepTables of the rows' board size (its max_free holds).  Returns (pi', z', info)
+    as numpy arrays in the caller's row order, z' in z's shape; info = dict(n_free int16 [n], mass float32 [n], relabelled bool
+    [n], tables = roots solved)."""
+    x = np.asarray(samples["x"])
+    g = _tables_handle(tables, x, rows, cols, max_free, device, "tables=DeepTables(rows, cols)")
+    n = len(x)
+    x = np.ascontiguousarray(x.reshape(n, g.F), dtype=np.int16)
+    pi = np.array(np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A), copy=True)
+    z_in = np.asarray(samples["z"], dtype=np.float32)
+    z = np.array(z_in.reshape(n), copy=True)
+    game = np.asarray(samples["game_idx"]).astype(np.int64).reshape(n)
+    move = np.asarray(samples["move_idx"]).astype(np.int64).reshape(n)
+    n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
+    info = dict(n_free=n_free, mass=np.zeros(n, np.float32), relabelled=np.zeros(n, bool))
+    root, table_of = _game_roots(game, move, n_free, g.max_free)
+    for lo in range(0, len(root), g.n_tables):
+        hi = min(lo + g.n_tables, len(root))
+        idx = np.nonzero((table_of >= lo) & (table_of < hi))[0]
+        p, zz, got = g.solve(x[root[lo:hi]]).targets(x[idx], table_of[idx] - lo, pi[idx], z[idx], pi_mode, z_mode)
+        pi[idx], z[idx] = p, zz
+        info["mass"][idx], info["relabelled"][idx] = got["mass"], got["relabelled"]
+    return pi, z.reshape(z_in.shape), dict(info, tables=len(root))
+
+
+def score_game_tails(samples, rows=None, cols=None, max_free=DEEP_FREE, device=0, deep=None, tables=None):
     """score_endgames for game-ordered rows, as Engine.fetch_samples() returns them (x, pi, played, z, game_idx, move_idx): per
     game the first row, by move_idx, with at most max_free free edges roots ONE solve (DeepEndgame), and that row and every later
     row of the game are scored from its table; the rows before it are unsolved.  The same keys with the same definitions as
     score_endgames, by_free of length max_free + 1, plus tables = solves done and solve_ms = the sum of their kernel times.
     deep: a DeepEndgame of the rows' board size (its max_free holds); without one the board size comes from rows / cols or from
-    x's shape [n, 3, H, W]."""
+    x's shape [n, 3, H, W].
+    tables: None walks the games one by one as described; a number, or a DeepTables of the rows' board size (its max_free
+    holds), takes the games in chunks of that many through a pool of tables -- one solve and one score per chunk, the same
+    result; tables = the roots solved, solve_ms = the sum over the chunks."""
+    if tables is not None:
+        return _score_game_tails_batched(samples, rows, cols, max_free, device, tables)
     x = np.asarray(samples["x"])
     if deep is None:
         if rows is None or cols is None:
@@ -463,6 +692,91 @@ def _deep_bench(a):
                endgame_rows=n_late, endgame_score_ms=round(endgame_ms, 4), endgame_rows_per_s=round(n_late / (endgame_ms * 1e-3)) if n_late else 0)
     d.close()
     g.close()
+    return out
+
+
+def _tables_bench(a):
+    """a.tables_bench generated roots with a.free free edges each (random_rows, one seed per root), solved two ways that alternate
+    in the same process: one dbaz_deep_solve call per root on a DeepEndgame, and ONE dbaz_tables_solve call for all of them on a
+    DeepTables.  Per way the HIP-event milliseconds of the solves' kernels and the host wall clock around the calls plus a
+    synchronise, each as the median of 5 rounds after a warm-up round, and per root.  Then every batched table is compared with
+    the sequential one."""
+    import time
+    import torch
+    n, free = a.tables_bench, a.free
+    d = DeepEndgame(a.rows, a.cols, a.device, max(free, 1))
+    free = min(free, d.n_edges)
+    t = DeepTables(a.rows, a.cols, a.device, max(free, 1), n)
+    dev = torch.device("cuda", d.device)
+    roots = np.ascontiguousarray(np.concatenate([random_rows(a.rows, a.cols, 1, free, seed=1000 + i) for i in range(n)]))
+    ms_out = C.c_double()
+    ev, wall = dict(sequential=[], batched=[]), dict(sequential=[], batched=[])
+    for i in range(6):
+        for which in ("sequential", "batched"):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            if which == "sequential":
+                ms = 0.0
+                for r in roots:
+                    d._ck(d._L.dbaz_deep_solve(d.h, C.c_void_p(r.ctypes.data), int(a.low_bits)))
+                    d._ck(d._L.dbaz_deep_info(d.h, None, None, C.byref(ms_out), None))
+                    ms += ms_out.value
+            else:
+                t._ck(t._L.dbaz_tables_solve(t.h, C.c_int32(n), C.c_void_p(roots.ctypes.data), int(a.low_bits)))
+                t._ck(t._L.dbaz_tables_info(t.h, None, None, None, C.byref(ms_out)))
+                ms = ms_out.value
+            torch.cuda.synchronize(dev)
+            dt = (time.perf_counter() - t0) * 1e3
+            if i:  # the first round warms up
+                ev[which].append(ms)
+                wall[which].append(dt)
+    t._info()
+    for i in range(n):  # the command checks itself
+        assert np.array_equal(t.table(i), d.solve(roots[i], a.low_bits).table()), "table %d: the batched and the sequential solve disagree" % i
+        assert t.d0[i] == d.d0 and t.n_free[i] == d.n_free
+    out = dict(rows=a.rows, cols=a.cols, roots=int(n), free=int(free), table_bytes=1 << free, pool_bytes=t.pool_bytes, tables_equal=True)
+    for which in ("sequential", "batched"):
+        e_, w_ = float(np.median(ev[which])), float(np.median(wall[which]))
+        out[which] = dict(event_ms=round(e_, 4), wall_ms=round(w_, 4), event_ms_per_root=round(e_ / n, 5), wall_ms_per_root=round(w_ / n, 5))
+    out["event_speedup"] = round(out["sequential"]["event_ms"] / out["batched"]["event_ms"], 3)
+    out["wall_speedup"] = round(out["sequential"]["wall_ms"] / out["batched"]["wall_ms"], 3)
+    d.close()
+    t.close()
+    return out
+
+
+def _tails_bench(a):
+    """a.tails_bench complete self-play games (formula evaluator, a.reads reads per move), their game-ordered rows scored by
+    score_game_tails' game-by-game path and by its batched path (tables=a.tables), alternating: host wall clock of each call,
+    the median of 5 rounds after a warm-up round.  Stops if the two reports differ."""
+    import time
+    from .engine import Engine
+    e = Engine(a.rows, a.cols, min(a.tails_bench, 8192), mcts_num_read=a.reads, evaluator="formula", device=a.device)
+    e.selfplay_start(a.tails_bench, 0)
+    e.run()
+    rows = e.fetch_samples()
+    e.close()
+    max_free = DEEP_FREE if a.free is None else a.free
+    deep = DeepEndgame(a.rows, a.cols, a.device, max_free)
+    pool = DeepTables(a.rows, a.cols, a.device, max_free, a.tables)
+    sec, got = dict(sequential=[], batched=[]), {}
+    for i in range(6):
+        for which in ("sequential", "batched"):
+            t0 = time.perf_counter()
+            kw = dict(deep=deep) if which == "sequential" else dict(tables=pool)
+            got[which] = score_game_tails(rows, **kw)
+            if i:  # the first round warms up
+                sec[which].append(time.perf_counter() - t0)
+    for k in ("value", "policy_mass", "played_optimal", "n_free", "solved"):
+        assert np.array_equal(got["sequential"][k], got["batched"][k]), k
+    assert got["sequential"]["tables"] == got["batched"]["tables"]
+    s, b = float(np.median(sec["sequential"])), float(np.median(sec["batched"]))
+    out = dict(rows=a.rows, cols=a.cols, games=int(a.tails_bench), sample_rows=len(rows["z"]), reads=a.reads, max_free=max_free, pool_tables=a.tables,
+               tables=int(got["batched"]["tables"]), coverage=round(got["batched"]["coverage"], 4), sequential_s=round(s, 4), batched_s=round(b, 4),
+               sequential_solve_ms=round(got["sequential"]["solve_ms"], 3), batched_solve_ms=round(got["batched"]["solve_ms"], 3),
+               speedup=round(s / b, 3))
+    deep.close()
+    pool.close()
     return out
 
 
@@ -619,7 +933,14 @@ def main(argv=None):
     ap.add_argument("--deep-bench", type=int, default=0, metavar="N",
                     help="solve one root with --free free edges into an HBM table (DeepEndgame), then time dbaz_deep_score on N descendants "
                          "next to dbaz_endgame_score on those of them with at most 16 free edges")
-    ap.add_argument("--low-bits", type=int, default=0, help="--deep-bench: 0 = default, L = LDS subcube of 2^L masks, -1 = plain kernel")
+    ap.add_argument("--low-bits", type=int, default=0, help="--deep-bench, --tables-bench: 0 = default, L = LDS subcube of 2^L masks, -1 = plain kernel")
+    ap.add_argument("--tables-bench", type=int, default=0, metavar="N",
+                    help="solve N generated roots with --free free edges (default 20) by N dbaz_deep_solve calls and by one dbaz_tables_solve call, "
+                         "alternating; then compare the tables")
+    ap.add_argument("--tails-bench", type=int, default=0, metavar="N",
+                    help="play N self-play games (formula evaluator, --reads) and time score_game_tails on their rows game by game and with "
+                         "--tables tables, max_free = --free (default 24)")
+    ap.add_argument("--tables", type=int, default=DEEP_TABLES, help="--tails-bench: tables of the pool")
     ap.add_argument("--selfplay-bench", type=int, default=0, metavar="N",
                     help="play N complete self-play games with a random-init ResNetZero, with and without the endgame tables attached")
     ap.add_argument("--targets-bench", type=int, default=0, metavar="N",
@@ -631,6 +952,13 @@ def main(argv=None):
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5, help="--selfplay-bench: timed runs per configuration (median)")
     a = ap.parse_args(argv)
+    if a.tables_bench > 0:
+        a.free = 20 if a.free is None else a.free
+        print(json.dumps(_tables_bench(a)))
+        return
+    if a.tails_bench > 0:
+        print(json.dumps(_tails_bench(a)))
+        return
     if a.deep_bench > 0:
         a.free = DEEP_FREE if a.free is None else a.free
         print(json.dumps(_deep_bench(a)))

@@ -569,6 +569,52 @@ int dbaz_deep_score(dbaz_deep *d, int32_t n, const int16_t *x_dev, const float *
 int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev /*[n][A]*/, float *v_dev,
                      uint8_t *served_dev, void *stream);
 
+/* ---- deep endgames in batches: a pool of tables, many roots solved side by side ----------------------------------
+ * The reference has no counterpart.  dbaz_deep above holds one table; this handle owns a pool of n_tables slots of 2^max_free
+ * bytes each.  One solve takes up to n_tables root positions and solves root i into slot i, the roots of equal F sharing their
+ * launches; rows of many games are then answered in one launch, row r from the table table_dev[r] names -- the root's index in
+ * the last solve.  Tables, served rule and outputs are dbaz_deep's, bit for bit.  No dbaz_engine. */
+typedef struct dbaz_tables dbaz_tables;
+const char *dbaz_tables_last_error(const dbaz_tables *t); /* t == NULL: why dbaz_tables_create failed */
+/* max_free: 1 .. 31, 0 = 24 (16 MiB per table).  n_tables: 1 .. 65535, 0 = 64 (1 GiB at the default max_free).  rows, cols < 1,
+ * A > DBAZ_MAX_A, max_free or n_tables out of range -> DBAZ_EINVAL before the device is touched; the pool of
+ * n_tables * 2^max_free bytes is allocated by the first solve and reused by every later one */
+int dbaz_tables_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, int32_t n_tables, dbaz_tables **out);
+void dbaz_tables_destroy(dbaz_tables *t);
+/* Solves the subgames of n_roots HOST feature rows int16 [n_roots][3*H*W], root i into the first 2^F_i bytes of slot i; returns
+ * when every table is complete.  It replaces all tables of the previous solve, after the dbaz_tables_score / dbaz_tables_targets
+ * calls queued so far have read them.  low_bits as for dbaz_deep_solve, applied to every root (0 = each root's default, -1 = the
+ * plain kernel; F < 4 always takes the plain kernel); every form writes the same bytes.  The work lists of the subcube kernel are
+ * kept per (F, low_bits) on the handle.
+ *   n_roots < 1 or > n_tables, a root with F > max_free, low_bits out of range for a root's F (the message names the root)
+ *                                        -> DBAZ_EINVAL;  a pool that cannot be allocated -> DBAZ_EDEVICE.
+ *   After either the handle has no valid table (n_solved = 0, DBAZ_ESTATE from the calls below) and stays usable. */
+int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host /*int16 [n_roots][3*H*W]*/, int32_t low_bits);
+/* any pointer may be NULL.  n_solved: roots of the last successful solve (0 without one); table_bytes = 2^max_free; pool_bytes =
+ * n_tables * 2^max_free; solve_ms: HIP-event time of the last solve's kernels, all roots together (-1 before) */
+int dbaz_tables_info(const dbaz_tables *t, int32_t *n_solved, int64_t *table_bytes, int64_t *pool_bytes, double *solve_ms);
+/* per solved root i < n_solved, HOST arrays (either may be NULL): its free edges F_i, and d0 = T_i[0], its score difference */
+int dbaz_tables_roots(const dbaz_tables *t, int32_t *n_free_out /*int32 [n_solved]*/, int32_t *d0_out /*int32 [n_solved]*/);
+/* host copy of T_i[first .. first + count) of root i's 2^F_i entries */
+int dbaz_tables_table(dbaz_tables *t, int32_t i, int8_t *host_dst, int64_t first, int64_t count);
+/* dbaz_deep_score for rows of many games: table_dev int32 [n] names the table of each row.  A row is SERVED when table_dev[r] is
+ * in [0, n_solved) and the row's free real edges are a subset of that root's; its outputs are bit for bit those of
+ * dbaz_deep_score with that root's table.  Every other row -- an index outside [0, n_solved) is never used to form an address --
+ * gets value 0, diff -128, q all -128, policy_mass 0, served 0; n_free is the row's own count either way.  DEVICE pointers,
+ * QUEUED on the caller's stream; n == 0 is a no-op; DBAZ_ESTATE without a valid solve. */
+int dbaz_tables_score(dbaz_tables *t, int32_t n, const int16_t *x_dev, const float *pi_dev, const int32_t *table_dev /*int32 [n]*/,
+                      int8_t *value_dev, int8_t *diff_dev, int8_t *q_dev /*[n][A]*/, float *mass_dev, int16_t *n_free_dev,
+                      uint8_t *served_dev, void *stream);
+/* dbaz_exact_targets' rule, in place, with v and q from the row's table instead of a solve from scratch: a row that is not served
+ * (as above) or belongs to a finished game is left untouched, bit for bit; every other row is relabelled as dbaz_exact_targets
+ * relabels a row it solves -- the same O, the same float32 sum S in ascending a, one correctly rounded float32 division per
+ * entry -- so the two agree bit for bit wherever both apply.  Modes, side outputs (each may be NULL; n_free of every row, mass and
+ * relabelled 0 for an untouched row) and argument checks as for dbaz_exact_targets.  DEVICE pointers, QUEUED on the caller's
+ * stream; DBAZ_ESTATE without a valid solve. */
+int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_dev, const int32_t *table_dev /*int32 [n]*/, int32_t pi_mode,
+                        int32_t z_mode, float *pi_dev /*in/out [n][A]*/, float *z_dev /*in/out [n]*/, int16_t *n_free_dev,
+                        float *mass_dev, uint8_t *relabelled_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
