@@ -42,8 +42,9 @@ struct EndgameSlotHdr {
     int64_t game;                            // validity stamp: the slot's game when the table was solved
     int32_t valid, F0;
     int32_t model, pad;
-    uint32_t other[ENDGAME_MAX_FREE][2];     // solver_move_q's box masks over the compact edges
-    uint8_t act[ENDGAME_MAX_FREE];           // compact edge -> action index
+    // sized for the deep attach (dbaz_attach_tables, k_slot_requests in solver.hip): k_endgame_table fills 16 entries at the most
+    uint32_t other[SOLVER_MAX_E][2];         // solver_move_q's box masks over the compact edges
+    uint8_t act[SOLVER_MAX_E];               // compact edge -> action index
 };
 
 // what the search side asks (tree.hip): does the slot's table serve the leaves of a search of game `game`
@@ -61,6 +62,12 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
 void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
                      const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
                      int AS, unsigned long long *stats);
+
+// The same evaluator over slot tables that a dbaz_tables attach solved (dbaz_attach_tables; the producer is solver.hip's
+// slot_tables_pass): k_endgame_eval with the board and max_free given here, slot regions of 2^max_free bytes.
+void endgame_forward_tables(int rows, int cols, int max_free, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
+                            const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
+                            float *V, int AS, unsigned long long *stats);
 
 // ---- exact training targets (dbaz_exact_targets, include/dbaz.h): rows x_stride shorts apart, relabelled in place, queued on
 // `stream`.  stats_host [4 + 17] (may be NULL) as dbaz_dataset_exact_targets documents it: asking for it waits for the stream.

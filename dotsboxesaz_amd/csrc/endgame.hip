@@ -757,6 +757,18 @@ void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlo
                                                                         per_slot, seed0, seed1, P, V, AS, stats);
 }
 
+void endgame_forward_tables(int rows, int cols, int max_free, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
+                            const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
+                            float *V, int AS, unsigned long long *stats)
+{
+    EndgameGeo g = EndgameGeo(); // k_endgame_eval reads the board and max_free only: no per-edge table
+    g.rows = rows; g.cols = cols; g.HW = (rows + 1) * (cols + 1); g.A = 2 * g.HW; g.E = 2 * rows * cols + rows + cols;
+    g.max_free = max_free;
+    const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
+    k_endgame_eval<float><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(g, hdr, tables, (size_t)1 << max_free, feat, list_dev, n_dev, max_n, per_slot,
+                                                                        seed0, seed1, P, V, AS, stats);
+}
+
 // The table path on its own: the yardstick of k_endgame_table / k_endgame_eval against dbaz_exact_policy, the int16 form of the
 // evaluator, and the place where the two kernels are timed.
 extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const int16_t *roots_dev, int32_t per_root, const int16_t *x_dev,

@@ -50,6 +50,10 @@ struct dbaz_engine {
     int8_t *eg_tables = nullptr;
     EndgameSlotHdr *eg_hdr = nullptr;
     unsigned long long *eg_stats = nullptr; // [2] tables solved, leaves served
+    // dbaz_attach_tables: the same with slot tables of up to 31 free edges, solved in HBM (solver.h); a handle's attaches are all
+    // of one kind.  Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own
+    bool eg_deep = false;
+    SlotTables slot_tables = SlotTables();
     // staging (device) for the boundary
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -108,6 +112,8 @@ static int set_error(dbaz_engine *e, int code, const char *fmt, ...)
     } while (0)
 
 static int endgame_drop_tables(dbaz_engine *e);
+static bool endgame_alloc_slots(dbaz_engine *e, size_t stride, void *p[6], hipError_t *err);
+static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6]);
 
 extern "C" const char *dbaz_last_error(const dbaz_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 extern "C" int dbaz_version(void) { return DBAZ_ABI_VERSION; }
@@ -636,6 +642,10 @@ static hipEvent_t next_event(dbaz_engine *e)
 // is one workgroup that returns at once
 static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
 {
+    if (e->eg_deep) { // a fixed launch sequence (slot_tables_plan.h): nothing is read back
+        slot_tables_pass(&e->slot_tables, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats);
+        return;
+    }
     const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
     if (g) endgame_tables(g, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats);
 }
@@ -643,6 +653,11 @@ static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
 // the leaves k_select / k_select_multi put on eg_list, where solver_forward serves its lists
 static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
 {
+    if (e->eg_deep) {
+        endgame_forward_tables(e->g.rows, e->g.cols, e->slot_tables.max_free, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3,
+                               e->n_slots * per_slot, per_slot, e->endgame_seed[0], e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
+        return;
+    }
     const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
     if (g)
         endgame_forward(g, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3, e->n_slots * per_slot, per_slot, e->endgame_seed[0],
@@ -864,6 +879,9 @@ extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *
     if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
         return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
                          e->g.cols, e->cfg.device);
+    if (e->eg_deep)
+        return set_error(e, DBAZ_EINVAL, "this handle's slot tables belong to a dbaz_tables (dbaz_attach_tables, max_free %d): a handle's attaches are "
+                         "all of one kind", e->slot_tables.max_free);
     // the slot regions are sized by the first attach and never resized: any later handle, for either model, must fit them exactly
     if (e->eg_tables && endgame_table_stride(g) != e->eg_stride)
         return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold %zu bytes each (the max_free of its first dbaz_attach_endgame); "
@@ -879,35 +897,122 @@ extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *
     if (!e->eg_tables) {
         // the slot tables: n_slots x 2^max_free bytes, plus headers, requests and the leaf list; nothing is kept when one fails
         const size_t ns = e->n_slots, stride = endgame_table_stride(g);
-        void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        const size_t bytes[6] = {ns * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4,
-                                 ns * (size_t)e->B.kmax * 4, 16};
-        hipError_t err = hipStreamSynchronize(e->stream);
-        for (int i = 0; i < 6 && err == hipSuccess; i++) {
-            err = hipMalloc(&p[i], bytes[i]);
-            if (err != hipSuccess) p[i] = nullptr;
-            else if (i) err = hipMemset(p[i], 0, bytes[i]);
-        }
-        if (err != hipSuccess) {
-            for (void *q : p) if (q) (void)hipFree(q);
-            (void)hipGetLastError();
+        void *p[6];
+        hipError_t err = hipSuccess;
+        if (!endgame_alloc_slots(e, stride, p, &err))
             return set_error(e, DBAZ_EDEVICE, "endgame tables of %zu slots x %zu bytes: %s", ns, stride, hipGetErrorString(err));
-        }
-        for (void *q : p) e->allocs.push_back(q);
-        e->eg_tables = (int8_t *)p[0];
-        e->eg_hdr = (EndgameSlotHdr *)p[1];
-        e->G.hdr = e->eg_hdr;
-        e->eg_start.req = (EndgameReq *)p[2];
-        e->eg_stride = stride;
-        e->G.list = (int32_t *)p[3];
-        e->G.leaf = (int32_t *)p[4];
-        e->eg_stats = (unsigned long long *)p[5];
+        endgame_keep_slots(e, stride, p);
     }
     e->endgame[model] = g;
     e->endgame_seed[model] = pick_seed;
     e->G.model[model] = 1;
     e->read_caps.eg_cap[model] = endgame_reads;
     e->eg_start.max_free[model] = max_free;
+    return DBAZ_OK;
+}
+
+// the slot tables of either kind of attach: n_slots x stride bytes, plus headers, requests, the leaf list and the counters; nothing
+// is kept when one allocation fails (*err)
+static bool endgame_alloc_slots(dbaz_engine *e, size_t stride, void *p[6], hipError_t *err)
+{
+    const size_t ns = e->n_slots;
+    const size_t bytes[6] = {ns * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4, ns * (size_t)e->B.kmax * 4, 16};
+    for (int i = 0; i < 6; i++) p[i] = nullptr;
+    *err = hipStreamSynchronize(e->stream);
+    for (int i = 0; i < 6 && *err == hipSuccess; i++) {
+        *err = hipMalloc(&p[i], bytes[i]);
+        if (*err != hipSuccess) p[i] = nullptr;
+        else if (i) *err = hipMemset(p[i], 0, bytes[i]);
+    }
+    if (*err == hipSuccess) return true;
+    for (int i = 0; i < 6; i++)
+        if (p[i]) (void)hipFree(p[i]);
+    (void)hipGetLastError();
+    return false;
+}
+
+static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
+{
+    for (int i = 0; i < 6; i++) e->allocs.push_back(p[i]);
+    e->eg_tables = (int8_t *)p[0];
+    e->eg_hdr = (EndgameSlotHdr *)p[1];
+    e->G.hdr = e->eg_hdr;
+    e->eg_start.req = (EndgameReq *)p[2];
+    e->eg_stride = stride;
+    e->G.list = (int32_t *)p[3];
+    e->G.leaf = (int32_t *)p[4];
+    e->eg_stats = (unsigned long long *)p[5];
+}
+
+extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
+    if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
+    const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
+    if (ev == DBAZ_EVAL_EXTERNAL || ev == DBAZ_EVAL_SOLVER || (model == 1 && !e->sc.match_play))
+        return set_error(e, DBAZ_EINVAL, "model %d: deep tables attach to a network or formula evaluator the engine runs itself", model);
+    if (endgame_reads < 0) return set_error(e, DBAZ_EINVAL, "endgame_reads must be >= 0");
+    int max_free = 0;
+    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
+                         e->cfg.device);
+    if (e->eg_tables && !e->eg_deep)
+        return set_error(e, DBAZ_EINVAL, "this handle's slot tables belong to a dbaz_endgame (dbaz_attach_endgame): a handle's attaches are all of one "
+                         "kind");
+    if (e->eg_deep && max_free != e->slot_tables.max_free)
+        return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold 2^%d bytes each (the max_free of its first dbaz_attach_tables); "
+                         "every later attach, for either model, needs the same max_free", max_free, e->slot_tables.max_free);
+    if (e->eg_deep) {
+        // a re-attach: as in dbaz_attach_endgame, the tables solved so far do not serve on
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = endgame_drop_tables(e)) return r;
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    } else {
+        const unsigned long long total = (unsigned long long)e->n_slots << max_free; // 64 bits: 8192 slots x 2^20 is past 32
+        SlotTables st;
+        void *lists[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (int rc = slot_tables_setup(t, e->n_slots, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(t));
+        void *p[6];
+        hipError_t err = hipSuccess;
+        if (!endgame_alloc_slots(e, (size_t)1 << max_free, p, &err)) {
+            for (void *q : lists) (void)hipFree(q);
+            return set_error(e, DBAZ_EDEVICE, "slot tables of %d slots x 2^%d bytes = %llu bytes: %s", e->n_slots, max_free, total, hipGetErrorString(err));
+        }
+        endgame_keep_slots(e, (size_t)1 << max_free, p);
+        for (void *q : lists) e->allocs.push_back(q);
+        e->slot_tables = st;
+        e->eg_deep = true;
+    }
+    e->endgame_seed[model] = pick_seed;
+    e->G.model[model] = 1;
+    e->read_caps.eg_cap[model] = endgame_reads;
+    e->eg_start.max_free[model] = max_free;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid, int32_t *n_free, int64_t *game, uint64_t free_edges[4],
+                                   int8_t *host_dst, int64_t first, int64_t count)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!e->eg_tables) return set_error(e, DBAZ_EINVAL, "dbaz_get_slot_table: no endgame solver or deep tables attached to this handle");
+    if (slot < 0 || slot >= e->n_slots) return set_error(e, DBAZ_EINVAL, "slot %d: this handle has slots 0 .. %d", slot, e->n_slots - 1);
+    const int64_t n = (int64_t)e->eg_stride;
+    if (first < 0 || count < 0 || first > n || count > n - first || (count > 0 && !host_dst))
+        return set_error(e, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    EndgameSlotHdr h;
+    HIP_CHECK_RET(e, hipMemcpy(&h, e->eg_hdr + slot, sizeof h, hipMemcpyDeviceToHost));
+    if (valid) *valid = h.valid;
+    if (n_free) *n_free = h.F0;
+    if (game) *game = h.game;
+    if (free_edges)
+        for (int w = 0; w < 4; w++) free_edges[w] = h.free_edges[w];
+    if (count > 0) HIP_CHECK_RET(e, hipMemcpy(host_dst, e->eg_tables + (size_t)slot * e->eg_stride + (size_t)first, (size_t)count, hipMemcpyDeviceToHost));
     return DBAZ_OK;
 }
 

@@ -106,3 +106,30 @@ static inline void popcount_order(int bits, std::vector<uint32_t> &perm, std::ve
 bool solver_serves(const dbaz_solver *s, int rows, int cols, int device, bool *solved);
 void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat, const int32_t *list_dev, const int32_t *n_dev, int max_n,
                     uint64_t pick_seed, float *P, float *V, int AS);
+
+// ---- deep slot tables inside the search (dbaz_attach_tables; kernels k_slot_requests / k_slot_solve in solver.hip, the launch
+// plan in slot_tables_plan.h).  The engine owns the slot regions [n_slots][2^max_free], the headers and the requests (endgame.h);
+// the dbaz_tables supplies the board and max_free and is not needed after the attach: the work lists of every F <= max_free are
+// built into a buffer the engine owns, so a handle may be replaced and destroyed while the engine searches on.  SlotTables is what
+// a pass needs besides: the per-F work-list table, the list of roots the pass solves and its two counters, all on the device.
+struct EndgameReq;     // endgame.h
+struct EndgameSlotHdr; // endgame.h
+#define SLOT_TABLES_GRID 512 // at most this many workgroups per k_slot_solve launch: two per CU; not tuned (DESIGN.md 5 says what was measured)
+struct SlotTables {
+    int32_t rows, cols, max_free;
+    int32_t n_launches;               // S of slot_tables_plan.h
+    uint32_t lds_bytes;
+    uint32_t widest[SOLVER_MAX_E + 1];
+    void *depth_dev;                  // [32] per F: L, top, plain and where its work lists are
+    void *geo_dev;                    // [n_slots] BatchGeo: the roots of the running pass, in the order the atomics gave
+    uint32_t *count_dev;              // [2]: roots listed by the pass of even / odd number
+    uint32_t pass;
+};
+bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *max_free);
+// Uploads what the passes need for every F <= max_free and fills *st; the four device buffers it allocated come back in
+// allocs[4] (the caller frees them).  DBAZ_OK, or an error code with the message in dbaz_tables_last_error(t) and nothing kept.
+int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[4]);
+// One pass on `stream`: every slot with a request keeps, drops or re-solves its table (k_endgame_table's rule); S + 1 launches,
+// nothing read back.  stats [2] as for endgame_tables.
+void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
+                      unsigned long long *stats);

@@ -19,7 +19,9 @@
 // The second half of the file (dbaz_deep_*) runs the same two kernels on the subgame of ONE position of any board, F <= 31 free
 // edges, and answers feature rows from that table (k_deep_score, k_deep_policy).  The last part (dbaz_tables_*)
 // is its batched form: a pool of tables, many roots solved side by side (k_solver_subcube_batch, k_solver_layer_batch) and rows of
-// many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).
+// many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).  At the end, the same bodies
+// inside the search (dbaz_attach_tables): one table per engine slot, solved from requests that exist only on the device
+// (k_slot_requests, k_slot_solve; slot_tables_plan.h).
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -28,7 +30,9 @@
 #include <vector>
 
 #include "deep_batch.h"
+#include "endgame.h"
 #include "position_geo.h"
+#include "slot_tables_plan.h"
 #include "solver.h"
 
 struct dbaz_solver {
@@ -70,9 +74,9 @@ static int serr(dbaz_solver *s, int code, const char *fmt, ...)
 // HBM.  other = the geometry's box masks, E its edges, D its table.
 typedef uint32_t SolverOther[SOLVER_MAX_E][2];
 
-static __device__ __forceinline__ void solver_layer_body(const SolverOther &other, int E, int8_t *D, int k)
+// m: the thread's mask (one thread per mask of the table)
+static __device__ __forceinline__ void solver_layer_body(const SolverOther &other, int E, int8_t *D, int k, uint32_t m)
 {
-    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
     if (m >= (1u << E) || __popc(m) != k) return;
     int best = k == E ? 0 : -128;
     for (int e = 0; e < E; e++) {
@@ -82,7 +86,7 @@ static __device__ __forceinline__ void solver_layer_body(const SolverOther &othe
     D[m] = (int8_t)best;
 }
 
-__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k) { solver_layer_body(g.other, g.E, D, k); }
+__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k) { solver_layer_body(g.other, g.E, D, k, blockIdx.x * 256u + threadIdx.x); }
 
 static __device__ __forceinline__ void solver_subcube_body(const SolverOther &other, int E, int8_t *D, int L, uint32_t hi,
                                                            const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
@@ -156,7 +160,7 @@ struct BatchGeo {
 __global__ void __launch_bounds__(256) k_solver_layer_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int k)
 {
     const BatchGeo &g = geo[blockIdx.y];
-    solver_layer_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), k);
+    solver_layer_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), k, blockIdx.x * 256u + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int L,
@@ -1271,4 +1275,266 @@ extern "C" int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_d
     TABLES_HIP(t, hipGetLastError());
     TABLES_HIP(t, hipEventRecord(t->used, (hipStream_t)stream));
     return DBAZ_OK;
+}
+
+// ====================================================================================
+// Deep tables inside the search (dbaz_attach_tables): one table per engine slot, solved from requests that exist
+// only on the device
+// ====================================================================================
+// A pass is k_slot_requests and then S launches of k_slot_solve on one stream (slot_tables_plan.h); stream order is the only
+// synchronisation between them.  The pass's roots go on a device list with one atomic each, and the counter of the NEXT pass is
+// zeroed by this one (two counters, used in turn), so the host neither resets nor reads anything.
+static_assert(sizeof(SlotTablesPlan().widest) == sizeof(SlotTables().widest), "solver.h restates slot_tables_plan.h");
+
+// what k_slot_solve needs to know about roots of one F
+struct SlotDepthDev {
+    int32_t L, top, plain, pad;
+    const uint32_t *hi;   // the high patterns of F - L bits in ascending popcount order
+    const uint16_t *low;  // the low masks of L bits, likewise
+    const uint32_t *loff; // [L + 2] layers of `low`
+    uint32_t hoff[SOLVER_MAX_HIGH + 2]; // layers of `hi`
+};
+
+static __device__ __forceinline__ uint64_t word_of(const uint64_t (&fe)[4], int w)
+{
+    return w == 0 ? fe[0] : w == 1 ? fe[1] : w == 2 ? fe[2] : fe[3];
+}
+// compact edge of action a: its rank among the free edges
+static __device__ __forceinline__ int slot_rank(const uint64_t (&fe)[4], int a)
+{
+    const int w = a >> 6;
+    int r = __popcll(word_of(fe, w) & ((1ull << (a & 63)) - 1ull));
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        if (i < w) r += __popcll(fe[i]);
+    return r;
+}
+// solver_move_q's mask of box (bl, bc) for its edge `a`: the box's other edges that are free, over the compact edges
+static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, const uint64_t (&fe)[4], int bl, int bc, int a)
+{
+    const int W = B.cols + 1, at = bl * W + bc;
+    const int ed[4] = {at, at + W, B.HW + at, B.HW + at + 1};
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (ed[i] != a && ((word_of(fe, ed[i] >> 6) >> (ed[i] & 63)) & 1ull)) o |= 1u << slot_rank(fe, ed[i]);
+    return o;
+}
+
+// Step 1 of a pass, one wavefront per slot with a request (a slot without one costs one word read), k_endgame_table's rule: the
+// same game with free edges inside the table's keeps the table, F > max_free drops it, anything else gets a new header -- F0, the
+// free-edge set, act and `other` as position_geometry builds them, the real edges and box neighbours from the board alone -- and
+// its BatchGeo goes on the pass's list.  Lane l looks at action slots l, 64 + l, ...; a free one writes its compact edge's entries.
+#define SLOT_REQ_WAVES 4
+__global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
+                                                                       EndgameSlotHdr *__restrict__ hdr, int n_slots, BatchGeo *__restrict__ geo,
+                                                                       uint32_t *__restrict__ count, uint32_t *__restrict__ count_next,
+                                                                       unsigned long long *__restrict__ stats)
+{
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count_next = 0u; // nobody reads it before the next pass
+    const int W = B.cols + 1;
+    for (int slot = blockIdx.x * SLOT_REQ_WAVES + (threadIdx.x >> 6); slot < n_slots; slot += gridDim.x * SLOT_REQ_WAVES) {
+        EndgameReq *rq = req + slot;
+        EndgameSlotHdr *h = hdr + slot;
+        if (!*(volatile const int32_t *)&rq->want) continue; // the same answer in every lane: nobody has written yet
+        uint64_t fe[4];
+        bool subset = true;
+        int F = 0;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int a = w * 64 + lane;
+            const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
+            const bool real = a < B.A && (p == 0 ? c < B.cols : l < B.rows); // sentinels: board[0,:,W-1] and board[1,H-1,:]
+            fe[w] = rq->free_edges[w] & __ballot(real);
+            subset = subset && (fe[w] & ~h->free_edges[w]) == 0ull;
+            F += __popcll(fe[w]);
+        }
+        const int64_t game = rq->game;
+        const int model = rq->model;
+        const bool keep = h->valid != 0 && h->game == game && subset;
+        const bool solve = !keep && F <= max_free;
+        if (lane == 0) {
+            rq->want = 0;
+            h->model = model;
+            if (!keep && !solve) h->valid = 0;
+        }
+        if (!solve) continue;
+
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(count, 1u);
+        at = (uint32_t)__shfl((int)at, 0);
+        if (at >= (uint32_t)n_slots) continue; // one request per slot: cannot happen
+        BatchGeo *bg = geo + at;
+        if (lane >= F && lane < SOLVER_MAX_E) { // the entries no edge owns, as position_geometry leaves them
+            bg->other[lane][0] = bg->other[lane][1] = SOLVER_NO_BOX;
+            h->other[lane][0] = h->other[lane][1] = SOLVER_NO_BOX;
+            h->act[lane] = 0;
+        }
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int a = w * 64 + lane;
+            if (!((fe[w] >> lane) & 1ull)) continue;
+            const int j = slot_rank(fe, a);
+            uint32_t o[2] = {SOLVER_NO_BOX, SOLVER_NO_BOX};
+            int used = 0;
+            if (a < B.HW) { // a horizontal edge: the boxes above and below, in the order of the board's box scan
+                const int l = a / W, c = a % W;
+                if (l >= 1) o[used++] = slot_box_other(B, fe, l - 1, c, a);
+                if (l < B.rows) o[used++] = slot_box_other(B, fe, l, c, a);
+            } else { // a vertical edge: the boxes to its left and right
+                const int l = (a - B.HW) / W, c = (a - B.HW) % W;
+                if (c >= 1) o[used++] = slot_box_other(B, fe, l, c - 1, a);
+                if (c < B.cols) o[used++] = slot_box_other(B, fe, l, c, a);
+            }
+            bg->other[j][0] = h->other[j][0] = o[0];
+            bg->other[j][1] = h->other[j][1] = o[1];
+            h->act[j] = (uint8_t)a;
+        }
+        if (lane == 0) {
+            bg->F = F;
+            bg->slot = slot;
+            for (int w = 0; w < 4; w++) h->free_edges[w] = fe[w];
+            h->game = game;
+            h->F0 = F;
+            h->valid = 1; // the table is complete before anything later on this stream reads it
+            atomicAdd(stats, 1ull);
+        }
+    }
+}
+
+// Launch s of a pass: for every listed root its own layer k = top(F) - s (k < 0: the root is finished).  The fixed grid strides
+// over (root, work item) pairs, `width` items per root -- the widest layer any F <= max_free has in this launch; an item the
+// root's layer does not have is skipped.  Every condition in the loop is the same for the whole workgroup.
+__global__ void __launch_bounds__(SOLVER_THREADS) k_slot_solve(const BatchGeo *__restrict__ geo, const uint32_t *__restrict__ count, int n_slots,
+                                                               int8_t *T, int stride_bits, const SlotDepthDev *__restrict__ depth, int max_free,
+                                                               int s, uint32_t width)
+{
+    const uint32_t n = min(*count, (uint32_t)n_slots);
+    const uint64_t total = (uint64_t)n * width;
+    for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BatchGeo &g = geo[w / width];
+        const uint32_t item = (uint32_t)(w % width);
+        if ((unsigned)g.F > (unsigned)max_free || (unsigned)g.slot >= (unsigned)n_slots) continue; // never outside the slot regions
+        const SlotDepthDev &d = depth[g.F];
+        const int k = d.top - s;
+        if (k < 0) continue;
+        int8_t *D = T + ((size_t)g.slot << stride_bits);
+        if (d.plain) { // 2^F <= 8 masks: one work item, no LDS
+            if (item == 0) solver_layer_body(g.other, g.F, D, k, threadIdx.x);
+            continue;
+        }
+        const uint32_t first = d.hoff[k];
+        if (item >= d.hoff[k + 1] - first) continue;
+        solver_subcube_body(g.other, g.F, D, d.L, d.hi[first + item], d.low, d.loff);
+        __syncthreads(); // the next item of this workgroup reuses the LDS subcube
+    }
+}
+
+bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *max_free)
+{
+    *max_free = t->max_free;
+    return t->board.rows == rows && t->board.cols == cols && t->dev == device;
+}
+
+int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[4])
+{
+    SlotTablesPlan plan;
+    if (slot_tables_plan(t->max_free, plan) != 0) return terr(t, DBAZ_EINVAL, "slot tables: max_free %d is outside 0 .. %d", t->max_free, SOLVER_MAX_E);
+    TABLES_HIP(t, hipSetDevice(t->dev));
+    // The work lists of every (F, L) with F <= max_free in ONE buffer that the caller owns -- not the lists cached on t, which go
+    // away with t while the engine may search on under another handle: all 32-bit lists (the high patterns per F, the layer
+    // offsets of the low masks per L) first, then the 16-bit low masks per L.
+    std::vector<uint32_t> words;
+    std::vector<uint16_t> halves;
+    size_t hi_at[SOLVER_MAX_E + 1] = {0}, loff_at[SOLVER_MAX_LOW + 1] = {0}, low_at[SOLVER_MAX_LOW + 1] = {0};
+    bool have_low[SOLVER_MAX_LOW + 1] = {false};
+    SlotDepthDev depth[SOLVER_MAX_E + 1];
+    for (int F = 0; F <= SOLVER_MAX_E; F++) {
+        SlotDepthDev &d = depth[F];
+        d = SlotDepthDev();
+        d.plain = 1;
+        if (F > t->max_free) continue;
+        d.L = plan.depth[F].L;
+        d.top = plan.depth[F].top;
+        d.plain = plan.depth[F].plain ? 1 : 0;
+        if (d.plain) continue;
+        std::vector<uint32_t> hperm, hoff;
+        popcount_order(F - d.L, hperm, hoff);
+        std::copy(hoff.begin(), hoff.end(), d.hoff);
+        hi_at[F] = words.size();
+        words.insert(words.end(), hperm.begin(), hperm.end());
+        if (!have_low[d.L]) {
+            std::vector<uint32_t> lperm, loff;
+            popcount_order(d.L, lperm, loff);
+            have_low[d.L] = true;
+            loff_at[d.L] = words.size();
+            words.insert(words.end(), loff.begin(), loff.end());
+            low_at[d.L] = halves.size();
+            halves.insert(halves.end(), lperm.begin(), lperm.end());
+        }
+    }
+    const size_t word_bytes = (words.size() * 4 + 15) / 16 * 16;
+    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+    const char *what[4] = {"the per-depth table", "the root list", "the counters", "the work lists"};
+    const size_t bytes[4] = {sizeof depth, std::max<size_t>(1, (size_t)n_slots) * sizeof(BatchGeo), 2 * sizeof(uint32_t),
+                             std::max<size_t>(16, word_bytes + halves.size() * 2)};
+    hipError_t e = hipSuccess;
+    int failed = 0;
+    for (int i = 0; i < 4 && e == hipSuccess; i++) {
+        failed = i;
+        e = hipMalloc(&p[i], bytes[i]);
+        if (e != hipSuccess) p[i] = nullptr;
+        else if (i == 1 || i == 2) e = hipMemset(p[i], 0, bytes[i]);
+    }
+    if (e == hipSuccess) {
+        failed = 3;
+        if (!words.empty()) e = hipMemcpy(p[3], words.data(), words.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !halves.empty()) e = hipMemcpy((char *)p[3] + word_bytes, halves.data(), halves.size() * 2, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) {
+        for (int F = 0; F <= t->max_free; F++) {
+            SlotDepthDev &d = depth[F];
+            if (d.plain) continue;
+            d.hi = (const uint32_t *)p[3] + hi_at[F];
+            d.loff = (const uint32_t *)p[3] + loff_at[d.L];
+            d.low = (const uint16_t *)((const char *)p[3] + word_bytes) + low_at[d.L];
+        }
+        failed = 0;
+        e = hipMemcpy(p[0], depth, sizeof depth, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { // (the dynamic LDS of k_slot_solve is 2^14 bytes at the most: default_low_bits never goes higher)
+        for (void *q : p)
+            if (q) (void)hipFree(q);
+        (void)hipGetLastError();
+        return terr(t, DBAZ_EDEVICE, "slot tables of %d slots: %s (%zu bytes): %s", n_slots, what[failed], bytes[failed], hipGetErrorString(e));
+    }
+    *st = SlotTables();
+    st->rows = t->board.rows; st->cols = t->board.cols; st->max_free = t->max_free;
+    st->n_launches = plan.n_launches;
+    st->lds_bytes = plan.lds_bytes;
+    std::copy(plan.widest, plan.widest + SOLVER_MAX_E + 1, st->widest);
+    st->depth_dev = p[0];
+    st->geo_dev = p[1];
+    st->count_dev = (uint32_t *)p[2];
+    st->pass = 0;
+    for (int i = 0; i < 4; i++) allocs[i] = p[i];
+    return DBAZ_OK;
+}
+
+void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
+                      unsigned long long *stats)
+{
+    TablesBoard B;
+    B.rows = st->rows; B.cols = st->cols; B.HW = (st->rows + 1) * (st->cols + 1); B.A = 2 * B.HW;
+    uint32_t *count = st->count_dev + (st->pass & 1u), *count_next = st->count_dev + ((st->pass + 1u) & 1u);
+    st->pass++;
+    const int blocks = std::min((n_slots + SLOT_REQ_WAVES - 1) / SLOT_REQ_WAVES, 1024);
+    k_slot_requests<<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next, stats);
+    for (int s = 0; s < st->n_launches; s++) {
+        // never more workgroups than (root, item) pairs the launch can have
+        const unsigned grid = (unsigned)std::min<uint64_t>(SLOT_TABLES_GRID, (uint64_t)std::max(n_slots, 1) * st->widest[s]);
+        k_slot_solve<<<grid, SOLVER_THREADS, st->lds_bytes, stream>>>((const BatchGeo *)st->geo_dev, count, n_slots, tables, st->max_free,
+                                                                  (const SlotDepthDev *)st->depth_dev, st->max_free, s, st->widest[s]);
+    }
 }

@@ -1,7 +1,7 @@
 """Exact endgame solver for any board (A <= 256): true values of positions with at most 16 free edges.
 
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --bench 4096 [--free 16]
-    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0]
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --selfplay-bench 8192 [--slots 8192] [--reads 800] [--endgame-reads 0] [--max-free 20]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --targets-bench 262144
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --deep-bench 4096 [--free 24]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --tables-bench 64 --free 20
@@ -12,7 +12,8 @@ over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip)
 DeepEndgame goes further, up to 31 free edges: one root position solved into a table in HBM by the small-board solver's kernels
 (csrc/solver.hip), and the root and every position after it answered from that table; score_game_tails uses it per game.
 DeepTables is the batched form: a pool of such tables, many roots solved side by side, rows of many games answered in one launch
-(score_game_tails(tables=), game_tail_targets).
+(score_game_tails(tables=), game_tail_targets).  Engine(endgame=DeepTables(rows, cols, max_free=M)) puts such tables inside the
+search, one per engine slot (Engine.attach_endgame, dbaz_attach_tables).
 """
 import ctypes as C
 
@@ -37,6 +38,8 @@ def target_modes(pi_mode, z_mode):
 class Endgame:
     """Endgame scorer of one board size on one GPU.  A > 256 or max_free outside 1 .. 16 raises DbazError before the device is
     touched."""
+
+    ATTACH = "dbaz_attach_endgame"  # the entry Engine.attach_endgame calls with this handle
 
     def __init__(self, rows, cols, device=0, max_free=MAX_FREE):
         self._L = _lib.load()
@@ -348,6 +351,8 @@ class DeepTables:
     """A pool of solved tables (dbaz_tables_*): solve(roots_x) solves up to n_tables root positions side by side,
     root i into table i; score() and targets() then answer rows of many games in one launch, row r from table table_of[r].
     A > 256, max_free outside 1 .. 31 or n_tables outside 1 .. 65535 raises DbazError before the device is touched."""
+
+    ATTACH = "dbaz_attach_tables"  # the entry Engine.attach_endgame calls with this handle
 
     def __init__(self, rows, cols, device=0, max_free=DEEP_FREE, n_tables=DEEP_TABLES):
         self._L = _lib.load()
@@ -882,7 +887,9 @@ def _targets_bench(g, n):
 def _selfplay_bench(a):
     """n complete self-play games with a random-init ResNetZero (noise, tree reuse: bench.py --full-games' engine), once without
     and once with the endgame tables attached: games/s, network evaluations per game, tables solved.  Each figure is the median
-    of a.repeats runs after one warm-up run."""
+    of a.repeats runs after one warm-up run.  --max-free M > 16: three engines -- plain, Endgame(16) and DeepTables(max_free=M)
+    attached -- each with the table_bytes of its slot tables."""
+    import sys
     import time
     import torch
     from . import nn as dnn
@@ -904,6 +911,7 @@ def _selfplay_bench(a):
             n_rows = len(eng.fetch_samples()["z"])
             dt = time.perf_counter() - t0
             c = eng.counters()
+            print("selfplay-bench: %s run %d of %d, %.1f s" % (type(g).__name__, i, a.repeats, dt), file=sys.stderr, flush=True)
             if i:  # the first run warms up
                 runs.append(dict(games_per_s=c["games_finished"] / dt, nn_evals_per_game=c["nn_evals"] / max(1, c["games_finished"]),
                                  rows_per_game=n_rows / max(1, c["games_finished"]), tables_solved=eng.endgame_stats()[0] - solved0,
@@ -911,6 +919,20 @@ def _selfplay_bench(a):
         eng.close()
         return {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
 
+    if a.max_free > MAX_FREE:
+        # past 16 free edges the slot tables are a DeepTables' (dbaz_attach_tables): plain, Endgame(16) and deep side by side
+        g, d = Endgame(a.rows, a.cols, a.device, MAX_FREE), DeepTables(a.rows, a.cols, a.device, max_free=a.max_free)
+        out = dict(rows=a.rows, cols=a.cols, games=a.selfplay_bench, slots=a.slots, reads=a.reads, max_free=d.max_free, endgame_reads=a.endgame_reads,
+                   plain=dict(play(None), table_bytes=0), endgame16=dict(play(g), table_bytes=a.slots << MAX_FREE),
+                   deep=dict(play(d), table_bytes=a.slots << d.max_free))
+        out["speedup"] = out["deep"]["games_per_s"] / out["plain"]["games_per_s"]
+        out["speedup_over_16"] = out["deep"]["games_per_s"] / out["endgame16"]["games_per_s"]
+        # the one relation that must hold on the same games: the deeper tables take more leaves away from the network
+        out["deep_saves_nn_evals"] = out["deep"]["nn_evals_per_game"] < out["endgame16"]["nn_evals_per_game"]
+        assert out["deep_saves_nn_evals"], out
+        g.close()
+        d.close()
+        return out
     g = Endgame(a.rows, a.cols, a.device, a.max_free)
     out = dict(rows=a.rows, cols=a.cols, games=a.selfplay_bench, slots=a.slots, reads=a.reads, max_free=g.max_free,
                endgame_reads=a.endgame_reads, table_bytes=a.slots * max(16, 1 << g.max_free), plain=play(None), endgame=play(g))

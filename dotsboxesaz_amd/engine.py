@@ -43,6 +43,8 @@ class Engine:
     evaluates them, answer every leaf under a search root with at most max_free free edges from that root's exact table, solved
     once per game (attach_endgame); endgame_seed picks among equally good moves, endgame_reads > 0 caps the driver rule's reads of
     the searches the tables serve.  The Engine keeps a reference to the handle.
+    endgame=DeepTables(rows, cols, max_free=M) means the same for any M <= 31 that fits in memory (n_slots x 2^M bytes): the slot
+    tables are solved in HBM by the deep solver's kernels (dbaz_attach_tables).  A handle's attaches are all of one kind.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -139,8 +141,12 @@ class Engine:
         at most endgame.max_free free edges from that root's exact table, which the engine solves once per game and keeps per slot
         (n_slots x 2^max_free bytes of device memory).  The Endgame is borrowed and kept alive with the Engine.  seed: which of
         several optimal moves gets the prior (0 = the lowest action index); reads > 0: searches the tables serve run
-        min(driver rule, reads) reads."""
-        self._ck(self._L.dbaz_attach_endgame(self.h, int(model), endgame.h, C.c_uint64(int(seed)), int(reads)))
+        min(driver rule, reads) reads.
+        endgame: an endgame.Endgame (max_free <= 16, solved in LDS) or an endgame.DeepTables (dbaz_attach_tables: max_free <= 31,
+        solved in HBM; its own pool is not used); every attach of one Engine is of the same kind and max_free."""
+        # the handle's class names its entry (Endgame.ATTACH, DeepTables.ATTACH): the C side cannot tell the two handle types apart
+        attach = getattr(self._L, endgame.ATTACH)
+        self._ck(attach(self.h, int(model), endgame.h, C.c_uint64(int(seed)), int(reads)))
         self._endgames[int(model)] = endgame
 
     def endgame_stats(self):
@@ -148,6 +154,18 @@ class Engine:
         t, n = C.c_int64(), C.c_int64()
         self._L.dbaz_get_endgame_stats(self.h, C.byref(t), C.byref(n))
         return int(t.value), int(n.value)
+
+    def slot_table(self, slot):
+        """dbaz_get_slot_table: dict(valid, n_free, game, free_edges, table) of a slot's endgame table after the queued work is
+        done -- free_edges uint64 [4] by action index, table int8 [2^n_free] (empty without a valid table).  DbazError (EINVAL)
+        without an attach or for a slot outside 0 .. n_slots - 1."""
+        valid, n_free, game = C.c_int32(), C.c_int32(), C.c_int64()
+        fe = np.zeros(4, np.uint64)
+        self._ck(self._L.dbaz_get_slot_table(self.h, int(slot), C.byref(valid), C.byref(n_free), C.byref(game), _p(fe), None, 0, 0))
+        table = np.empty((1 << n_free.value) if valid.value else 0, np.int8)
+        if len(table):
+            self._ck(self._L.dbaz_get_slot_table(self.h, int(slot), None, None, None, None, _p(table), 0, len(table)))
+        return dict(valid=bool(valid.value), n_free=int(n_free.value), game=int(game.value), free_edges=fe, table=table)
 
     # ---------------------------------------------------------------- rules (G1-G6)
     def rules_init(self, n):

@@ -174,7 +174,7 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     start_states: a book of start positions (move sequences from the empty board, or mirror BoxesStates): game g starts from
     start_states[start_index(g, len(start_states), games_per_start)], g being the absolute game index, so a game's rows stay
     a function of (seed, game index) however the games are sharded over ranks.  None: the empty board.
-    endgame: an endgame.Endgame of the board and device: from a game's first search root with at most endgame.max_free free edges
+    endgame: an endgame.Endgame (max_free <= 16) or endgame.DeepTables (max_free <= 31) of the board and device: from a game's first search root with at most endgame.max_free free edges
     on, every leaf is answered from that root's exact table instead of the network (Engine.attach_endgame)."""
     from .engine import Engine
     game = _get(params, "game")
@@ -373,7 +373,7 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     openings: a book of start positions (move sequences or mirror BoxesStates) instead of n_games games from the empty board:
     games 2k and 2k+1 start from opening k % len(openings), so with the seat swap of odd games every opening is played once per
     seating.
-    endgame, endgame_models: an endgame.Endgame that answers the late leaves of the listed models (Engine.attach_endgame); the
+    endgame, endgame_models: an endgame.Endgame or endgame.DeepTables that answers the late leaves of the listed models (Engine.attach_endgame); the
     same network with and without it -- params twice, endgame_models=(0,) -- is then one call.
     Returns (elo0, elo1, n1 / number of decided games)."""
     from .engine import Engine

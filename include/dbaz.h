@@ -520,6 +520,7 @@ int dbaz_dataset_exact_targets(dbaz_engine *e, dbaz_endgame *g, int32_t pi_mode,
  *   the model's evaluator DBAZ_EVAL_EXTERNAL or DBAZ_EVAL_SOLVER, model not 0 / 1 (1 without match play), g of another board size
  *   or device, endgame_reads < 0                                  -> DBAZ_EINVAL
  *   a max_free other than that of the handle's FIRST attach (either model; the slot regions are sized once) -> DBAZ_EINVAL
+ *   a handle whose slot tables belong to a dbaz_tables (dbaz_attach_tables below: one kind of attach per handle) -> DBAZ_EINVAL
  * A later attach with the same max_free replaces the model's solver, seed and endgame_reads and drops every slot's table.
  *   the slot tables cannot be allocated                           -> DBAZ_EDEVICE; the engine stays usable without the attach */
 int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t pick_seed, int32_t endgame_reads);
@@ -614,6 +615,32 @@ int dbaz_tables_score(dbaz_tables *t, int32_t n, const int16_t *x_dev, const flo
 int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_dev, const int32_t *table_dev /*int32 [n]*/, int32_t pi_mode,
                         int32_t z_mode, float *pi_dev /*in/out [n][A]*/, float *z_dev /*in/out [n]*/, int16_t *n_free_dev,
                         float *mass_dev, uint8_t *relabelled_dev, void *stream);
+
+/* ---- deep tables inside the search: dbaz_attach_endgame's meaning for up to 31 free edges ------------------------
+ * The counterpart of dbaz_attach_endgame with a dbaz_tables: once a search root of a slot has F0 <= max_free free edges, the
+ * engine solves that root's subgame once per game into the slot's region in HBM and answers every later leaf and root of the game
+ * from it, exactly as described there -- the same (p, v), bit for bit, the same routing, counters and endgame_reads.  t supplies
+ * the board and max_free; its own pool is not touched and need not be allocated, and the engine keeps nothing of t's on the device
+ * (the work lists of every F <= max_free are built into the engine's own memory at the first attach), so a handle that a later
+ * attach has replaced may be destroyed.  The
+ * engine allocates n_slots << max_free bytes of slot tables (64-bit sizes: 8 192 slots x 1 MiB = 8 GiB at max_free = 20), a region
+ * of 2^max_free bytes per slot whatever a root's F, plus headers, requests and the list of roots of a pass.  The tables are solved
+ * on the device from requests that exist only there: every pass over the slots is one fixed launch sequence, a function of
+ * max_free alone, and no request waits for a later pass, however many arrive at once.  The engine BORROWS t.
+ *   the refusals of dbaz_attach_endgame (evaluator, model, board or device, endgame_reads < 0)          -> DBAZ_EINVAL
+ *   a handle's attaches are all of ONE kind and one max_free: a dbaz_tables after a dbaz_endgame, a dbaz_endgame after a
+ *   dbaz_tables, or another max_free than the first dbaz_attach_tables   -> DBAZ_EINVAL, nothing changes
+ *   the slot tables cannot be allocated   -> DBAZ_EDEVICE, the byte count in the message; the handle stays as it was
+ * A later attach with the same max_free replaces the model's handle, seed and endgame_reads and drops every slot's table.
+ * dbaz_get_endgame_stats counts these tables and leaves too. */
+int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads);
+/* A slot's table as the search sees it, after waiting for the engine's queued work; for either kind of attach.  valid: the slot
+ * has a table (of game `game`, n_free = F0 free edges at its root, free_edges [4] = those edges by action index; compact edge j is
+ * the j-th of them, bit j of a table index = that edge has been drawn since).  host_dst (may be NULL with count = 0) receives
+ * bytes [first, first + count) of the slot's region, whose first 2^F0 bytes are the table.  Any output pointer may be NULL.
+ *   no attach on this handle, slot outside 0 .. n_slots - 1, a range outside the slot's region -> DBAZ_EINVAL */
+int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid, int32_t *n_free, int64_t *game, uint64_t free_edges[4],
+                        int8_t *host_dst, int64_t first, int64_t count);
 
 #ifdef __cplusplus
 }
