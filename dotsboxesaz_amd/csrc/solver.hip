@@ -16,14 +16,17 @@
 // One launch per popcount layer of the high bits (E - L + 1 launches).
 // k_solver_layer: the plain form, one thread per mask and one launch per popcount layer of all E bits (A/B partner).
 //
-// The second half of the file (dbaz_deep_*) runs the same two kernels on the subgame of ONE position of any board, F <= 31 free
-// edges, and answers feature rows from that table (k_deep_score, k_deep_policy).  The last part (dbaz_tables_*)
-// is its batched form: a pool of tables, many roots solved side by side (k_solver_subcube_batch, k_solver_layer_batch) and rows of
-// many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).  At the end, the same bodies
-// inside the search (dbaz_attach_tables): one table per engine slot, solved from requests that exist only on the device
-// (k_slot_requests, k_slot_solve; slot_tables_plan.h).
+// Both kernels read their geometry from an array in HBM, one BatchGeo per blockIdx.y: the whole board is an array of one.
+//
+// The second half of the file runs the same two kernels on the subgames of positions of any board, F <= 31 free
+// edges each: a pool of tables (dbaz_tables_*), many roots solved side by side with grid.y = the roots of equal F, and rows of
+// many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).  dbaz_deep_* is a pool of one
+// table on the same path, plus the table as an evaluator (k_deep_policy).  At the end, the same bodies inside the search
+// (dbaz_attach_tables): one table per engine slot, solved from requests that exist only on the device (k_slot_requests,
+// k_slot_solve; slot_tables_plan.h).
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -35,45 +38,61 @@
 #include "slot_tables_plan.h"
 #include "solver.h"
 
+// One root's solve geometry as the two solving kernels read it from HBM: what the bodies need of a SolverGeo, and the table slot
+// the root owns.  A whole board (dbaz_solver) is one entry with F = E and slot 0.
+typedef uint32_t SolverOther[SOLVER_MAX_E][2];
+struct BatchGeo {
+    int32_t F, slot;
+    SolverOther other;
+};
+static_assert(sizeof(BatchGeo) == 256, "one root's solve geometry");
+
+// the popcount-ordered work lists of one (F, L) on the device: they depend on nothing else and stay on the handle that asked
+struct WorkLists {
+    int F = 0, L = 0;
+    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
+    uint16_t *low_dev = nullptr;
+    std::vector<uint32_t> hoff;
+};
+
 struct dbaz_solver {
     SolverGeo g;
     int dev = 0;
     int8_t *D = nullptr;     // [2^E]
+    BatchGeo *geo_dev = nullptr; // [1]: g as the solving kernels read it
     hipStream_t stream = nullptr;
     bool solved = false;
     int low_bits = 0;        // of the last solve (-1: plain kernel)
     double solve_ms = -1.0;
     int d0 = -128;
+    std::vector<WorkLists> lists;
     std::string err;
 };
 
-static thread_local std::string g_solver_error; // message of a failed dbaz_solver_create (no handle to keep it in); per thread
+// Where a failure's message goes: the handle's `err`, or the family's slot for a failed create (no handle to keep it in); per thread.
+static thread_local std::string g_solver_error, g_deep_error, g_tables_error;
 
-static int serr(dbaz_solver *s, int code, const char *fmt, ...)
+static int fail(std::string &err, int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    (s ? s->err : g_solver_error) = buf;
+    err = buf;
     return code;
 }
 
-#define SOLVER_HIP(s, call)                                                                                         \
+#define CHECK_HIP(err, call)                                                                                        \
     do {                                                                                                            \
         hipError_t _err = (call);                                                                                   \
-        if (_err != hipSuccess) return serr(s, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+        if (_err != hipSuccess) return fail(err, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
     } while (0)
 
 // ------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------
-// The two solving kernels come in two forms that share their bodies: k_solver_layer / k_solver_subcube take ONE geometry in the
-// kernel arguments, k_solver_layer_batch / k_solver_subcube_batch (further below) one geometry per blockIdx.y from an array in
-// HBM.  other = the geometry's box masks, E its edges, D its table.
-typedef uint32_t SolverOther[SOLVER_MAX_E][2];
-
+// The bodies of the two solving kernels, shared with k_slot_solve: other = the geometry's box masks, E its edges, D its table.
 // m: the thread's mask (one thread per mask of the table)
 static __device__ __forceinline__ void solver_layer_body(const SolverOther &other, int E, int8_t *D, int k, uint32_t m)
 {
@@ -85,8 +104,6 @@ static __device__ __forceinline__ void solver_layer_body(const SolverOther &othe
     }
     D[m] = (int8_t)best;
 }
-
-__global__ void __launch_bounds__(256) k_solver_layer(SolverGeo g, int8_t *D, int k) { solver_layer_body(g.other, g.E, D, k, blockIdx.x * 256u + threadIdx.x); }
 
 static __device__ __forceinline__ void solver_subcube_body(const SolverOther &other, int E, int8_t *D, int L, uint32_t hi,
                                                            const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
@@ -143,30 +160,18 @@ static __device__ __forceinline__ void solver_subcube_body(const SolverOther &ot
         *reinterpret_cast<uint4 *>(D + ((size_t)base + chunk)) = *reinterpret_cast<const uint4 *>(sd + chunk);
 }
 
-__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(SolverGeo g, int8_t *D, int L, const uint32_t *__restrict__ hi_list,
-                                                                   const uint16_t *__restrict__ low_perm, const uint32_t *__restrict__ low_off)
-{
-    solver_subcube_body(g.other, g.E, D, L, hi_list[blockIdx.x], low_perm, low_off);
-}
-
-// One root of a batch (dbaz_tables_solve): what the two bodies read of a SolverGeo, and the table slot the root owns.
-struct BatchGeo {
-    int32_t F, slot;
-    SolverOther other;
-};
-
-// The batched forms: blockIdx.y = the root within a group of roots with the same F (deep_batch.h), geo = the group's geometries;
-// the root's table is T + slot * 2^stride_bits.  Every workgroup reads one geometry, so the reads are wave-uniform.
-__global__ void __launch_bounds__(256) k_solver_layer_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int k)
+// The two solving kernels: blockIdx.y = the root within a group of roots with the same F (deep_batch.h; a whole board or a single
+// position is a group of one), geo = the group's geometries; the root's table is T + slot * 2^stride_bits.  Every workgroup reads
+// one geometry, so the reads are wave-uniform.
+__global__ void __launch_bounds__(256) k_solver_layer(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int k)
 {
     const BatchGeo &g = geo[blockIdx.y];
     solver_layer_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), k, blockIdx.x * 256u + threadIdx.x);
 }
 
-__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube_batch(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int L,
-                                                                         const uint32_t *__restrict__ hi_list,
-                                                                         const uint16_t *__restrict__ low_perm,
-                                                                         const uint32_t *__restrict__ low_off)
+__global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(const BatchGeo *__restrict__ geo, int8_t *T, int stride_bits, int L,
+                                                                   const uint32_t *__restrict__ hi_list, const uint16_t *__restrict__ low_perm,
+                                                                   const uint32_t *__restrict__ low_off)
 {
     const BatchGeo &g = geo[blockIdx.y];
     solver_subcube_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), L, hi_list[blockIdx.x], low_perm, low_off);
@@ -291,36 +296,81 @@ static void solver_geometry(int rows, int cols, SolverGeo &g)
 
 extern "C" const char *dbaz_solver_last_error(const dbaz_solver *s) { return s ? s->err.c_str() : g_solver_error.c_str(); }
 
+// The work lists of (F, L) in a handle's cache, built and copied the first time the pair is asked for: its index, or -1 with *e set.
+static int work_lists(std::vector<WorkLists> &cache, int F, int L, hipError_t *e)
+{
+    for (size_t i = 0; i < cache.size(); i++)
+        if (cache[i].F == F && cache[i].L == L) return (int)i;
+    WorkLists l;
+    l.F = F;
+    l.L = L;
+    std::vector<uint32_t> lperm, loff, hperm;
+    popcount_order(L, lperm, loff);
+    popcount_order(F - L, hperm, l.hoff);
+    const std::vector<uint16_t> l16(lperm.begin(), lperm.end());
+    *e = hipMalloc((void **)&l.hi_dev, hperm.size() * 4);
+    if (*e == hipSuccess) *e = hipMalloc((void **)&l.low_dev, l16.size() * 2);
+    if (*e == hipSuccess) *e = hipMalloc((void **)&l.off_dev, loff.size() * 4);
+    if (*e == hipSuccess) *e = hipMemcpy(l.hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice);
+    if (*e == hipSuccess) *e = hipMemcpy(l.low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice);
+    if (*e == hipSuccess) *e = hipMemcpy(l.off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice);
+    if (*e != hipSuccess) {
+        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
+            if (b) (void)hipFree(b);
+        (void)hipGetLastError();
+        return -1;
+    }
+    cache.push_back(std::move(l));
+    return (int)cache.size() - 1;
+}
+
+static void free_work_lists(std::vector<WorkLists> &cache)
+{
+    for (WorkLists &l : cache)
+        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
+            if (b) (void)hipFree(b);
+    cache.clear();
+}
+
 extern "C" void dbaz_solver_destroy(dbaz_solver *s)
 {
     if (!s) return;
     (void)hipSetDevice(s->dev);
     if (s->D) (void)hipFree(s->D);
+    if (s->geo_dev) (void)hipFree(s->geo_dev);
+    free_work_lists(s->lists);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 
 extern "C" int dbaz_solver_create(int32_t rows, int32_t cols, int32_t device, dbaz_solver **out)
 {
-    if (!out) return serr(nullptr, DBAZ_EINVAL, "null argument");
+    if (!out) return fail(g_solver_error, DBAZ_EINVAL, "null argument");
     *out = nullptr;
-    if (rows < 1 || cols < 1) return serr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    if (rows < 1 || cols < 1) return fail(g_solver_error, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
     const long long E = 2ll * rows * cols + rows + cols;
     if (E > SOLVER_MAX_E)
-        return serr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld edges: the solver's table holds 2^E bytes, E <= %d", rows, cols, E, SOLVER_MAX_E);
+        return fail(g_solver_error, DBAZ_EINVAL, "board %dx%d has %lld edges: the solver's table holds 2^E bytes, E <= %d", rows, cols, E, SOLVER_MAX_E);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return serr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+        return fail(g_solver_error, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
     dbaz_solver *s = new dbaz_solver();
     s->dev = device;
     solver_geometry(rows, cols, s->g);
+    BatchGeo bg; // the board as a group of one root: it never changes, so it goes up once
+    bg.F = s->g.E;
+    bg.slot = 0;
+    memcpy(bg.other, s->g.other, sizeof bg.other);
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreate(&s->stream);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_solver_subcube, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->geo_dev, sizeof bg);
+    if (e == hipSuccess) e = hipMemcpy(s->geo_dev, &bg, sizeof bg, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         const std::string msg = hipGetErrorString(e);
+        (void)hipGetLastError();
         dbaz_solver_destroy(s);
-        return serr(nullptr, DBAZ_EDEVICE, "solver setup failed: %s", msg.c_str());
+        return fail(g_solver_error, DBAZ_EDEVICE, "solver setup failed: %s", msg.c_str());
     }
     *out = s;
     return DBAZ_OK;
@@ -333,50 +383,35 @@ extern "C" int dbaz_solver_solve(dbaz_solver *s, int32_t low_bits)
     const bool plain = low_bits == -1;
     const int L = low_bits == 0 ? default_low_bits(E) : low_bits;
     if (!plain && (L < SOLVER_MIN_LOW || L > SOLVER_MAX_LOW || L > E || E - L > SOLVER_MAX_HIGH))
-        return serr(s, DBAZ_EINVAL, "low_bits %d: E = %d needs max(%d, E - %d) <= low_bits <= min(E, %d) (0 = default, -1 = plain kernel)",
+        return fail(s->err, DBAZ_EINVAL, "low_bits %d: E = %d needs max(%d, E - %d) <= low_bits <= min(E, %d) (0 = default, -1 = plain kernel)",
                     low_bits, E, SOLVER_MIN_LOW, SOLVER_MAX_HIGH, SOLVER_MAX_LOW);
-    SOLVER_HIP(s, hipSetDevice(s->dev));
+    CHECK_HIP(s->err, hipSetDevice(s->dev));
     const size_t bytes = (size_t)1 << E;
     if (!s->D) {
         const hipError_t e = hipMalloc((void **)&s->D, bytes);
         if (e != hipSuccess) {
             s->D = nullptr;
             (void)hipGetLastError();
-            return serr(s, DBAZ_EDEVICE, "table of %zu bytes: %s", bytes, hipGetErrorString(e));
+            return fail(s->err, DBAZ_EDEVICE, "table of %zu bytes: %s", bytes, hipGetErrorString(e));
         }
     }
     s->solved = false;
-    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
-    uint16_t *low_dev = nullptr;
-    std::vector<uint32_t> hperm, hoff;
-    if (!plain) {
-        std::vector<uint32_t> lperm, loff;
-        popcount_order(L, lperm, loff);
-        popcount_order(E - L, hperm, hoff);
-        std::vector<uint16_t> l16(lperm.begin(), lperm.end());
-        hipError_t e = hipMalloc((void **)&hi_dev, hperm.size() * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&low_dev, l16.size() * 2);
-        if (e == hipSuccess) e = hipMalloc((void **)&off_dev, loff.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(hi_dev); (void)hipFree(low_dev); (void)hipFree(off_dev);
-            (void)hipGetLastError();
-            return serr(s, DBAZ_EDEVICE, "solver work lists: %s", hipGetErrorString(e));
-        }
-    }
+    hipError_t e = hipSuccess;
+    const int li = plain ? -1 : work_lists(s->lists, E, L, &e);
+    if (e != hipSuccess) return fail(s->err, DBAZ_EDEVICE, "solver work lists: %s", hipGetErrorString(e));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipError_t e = hipEventCreate(&ev0);
+    e = hipEventCreate(&ev0);
     if (e == hipSuccess) e = hipEventCreate(&ev1);
     if (e == hipSuccess) e = hipEventRecord(ev0, s->stream);
     if (e == hipSuccess) {
         if (plain) {
             const unsigned grid = (unsigned)((bytes + 255) / 256);
-            for (int k = E; k >= 0; k--) k_solver_layer<<<grid, 256, 0, s->stream>>>(s->g, s->D, k);
+            for (int k = E; k >= 0; k--) k_solver_layer<<<grid, 256, 0, s->stream>>>(s->geo_dev, s->D, 0, k);
         } else {
+            const WorkLists &w = s->lists[(size_t)li];
             for (int k = E - L; k >= 0; k--)
-                k_solver_subcube<<<hoff[k + 1] - hoff[k], SOLVER_THREADS, (size_t)1 << L, s->stream>>>(s->g, s->D, L, hi_dev + hoff[k], low_dev, off_dev);
+                k_solver_subcube<<<w.hoff[k + 1] - w.hoff[k], SOLVER_THREADS, (size_t)1 << L, s->stream>>>(s->geo_dev, s->D, 0, L, w.hi_dev + w.hoff[k],
+                                                                                                          w.low_dev, w.off_dev);
         }
         e = hipGetLastError();
     }
@@ -388,8 +423,7 @@ extern "C" int dbaz_solver_solve(dbaz_solver *s, int32_t low_bits)
     if (e == hipSuccess) e = hipMemcpy(&d0, s->D, 1, hipMemcpyDeviceToHost);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(hi_dev); (void)hipFree(low_dev); (void)hipFree(off_dev);
-    if (e != hipSuccess) return serr(s, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(s->err, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
     s->solved = true;
     s->low_bits = plain ? -1 : L;
     s->solve_ms = ms;
@@ -410,13 +444,13 @@ extern "C" int dbaz_solver_info(const dbaz_solver *s, int32_t *n_edges, int64_t 
 extern "C" int dbaz_solver_table(dbaz_solver *s, int8_t *host_dst, int64_t first, int64_t count)
 {
     if (!s) return DBAZ_EINVAL;
-    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_solver_table before dbaz_solver_solve");
+    if (!s->solved) return fail(s->err, DBAZ_ESTATE, "dbaz_solver_table before dbaz_solver_solve");
     const int64_t n = (int64_t)1 << s->g.E;
     if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
-        return serr(s, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+        return fail(s->err, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
     if (count == 0) return DBAZ_OK;
-    SOLVER_HIP(s, hipSetDevice(s->dev));
-    SOLVER_HIP(s, hipMemcpy(host_dst, s->D + first, (size_t)count, hipMemcpyDeviceToHost));
+    CHECK_HIP(s->err, hipSetDevice(s->dev));
+    CHECK_HIP(s->err, hipMemcpy(host_dst, s->D + first, (size_t)count, hipMemcpyDeviceToHost));
     return DBAZ_OK;
 }
 
@@ -424,14 +458,14 @@ extern "C" int dbaz_solver_score(dbaz_solver *s, int32_t n, const int16_t *x_dev
                                  int8_t *q_dev, float *policy_mass_dev, void *stream)
 {
     if (!s) return DBAZ_EINVAL;
-    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_solver_score before dbaz_solver_solve");
+    if (!s->solved) return fail(s->err, DBAZ_ESTATE, "dbaz_solver_score before dbaz_solver_solve");
     if (n < 0 || (n > 0 && (!x_dev || !value_dev || !diff_dev || !q_dev)) || (pi_dev && !policy_mass_dev))
-        return serr(s, DBAZ_EINVAL, "dbaz_solver_score: bad argument (n = %d)", n);
+        return fail(s->err, DBAZ_EINVAL, "dbaz_solver_score: bad argument (n = %d)", n);
     if (n == 0) return DBAZ_OK;
-    SOLVER_HIP(s, hipSetDevice(s->dev));
+    CHECK_HIP(s->err, hipSetDevice(s->dev));
     k_solver_score<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(s->g, s->D, x_dev, pi_dev, n, value_dev, diff_dev, q_dev,
                                                                      pi_dev ? policy_mass_dev : nullptr);
-    SOLVER_HIP(s, hipGetLastError());
+    CHECK_HIP(s->err, hipGetLastError());
     return DBAZ_OK;
 }
 
@@ -446,12 +480,12 @@ static void launch_eval(const dbaz_solver *s, hipStream_t stream, const T *x, co
 extern "C" int dbaz_perfect_policy(dbaz_solver *s, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev, void *stream)
 {
     if (!s) return DBAZ_EINVAL;
-    if (!s->solved) return serr(s, DBAZ_ESTATE, "dbaz_perfect_policy before dbaz_solver_solve");
-    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev))) return serr(s, DBAZ_EINVAL, "dbaz_perfect_policy: bad argument (n = %d)", n);
+    if (!s->solved) return fail(s->err, DBAZ_ESTATE, "dbaz_perfect_policy before dbaz_solver_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev))) return fail(s->err, DBAZ_EINVAL, "dbaz_perfect_policy: bad argument (n = %d)", n);
     if (n == 0) return DBAZ_OK;
-    SOLVER_HIP(s, hipSetDevice(s->dev));
+    CHECK_HIP(s->err, hipSetDevice(s->dev));
     launch_eval<int16_t>(s, (hipStream_t)stream, x_dev, nullptr, nullptr, n, pick_seed, p_dev, v_dev, s->g.A);
-    SOLVER_HIP(s, hipGetLastError());
+    CHECK_HIP(s->err, hipGetLastError());
     return DBAZ_OK;
 }
 
@@ -469,67 +503,90 @@ void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat,
 }
 
 // ====================================================================================
-// Deep endgames: ONE position with F <= 31 free edges on any board (A <= DBAZ_MAX_A), solved by the kernels above
+// Deep endgames: positions with F <= 31 free edges on any board (A <= DBAZ_MAX_A), solved by the kernels above into
+// a pool of tables, and feature rows answered each from its table
 // ====================================================================================
-// D depends only on which edges are free, so the position is a game over the 2^F subsets of its free edges, and every position
-// that can follow it is an entry of the same table.  position_geometry (position_geo.h) turns the root row into a SolverGeo --
-// E = F, `other` over the compact edges -- and k_solver_subcube / k_solver_layer solve it into int8 T[2^F] in HBM as they solve a
-// whole board; they read g.E and g.other only.  k_deep_score / k_deep_policy then answer feature rows from the table.
+// D depends only on which edges are free, so a position is a game over the 2^F subsets of its free edges, and every position that
+// can follow it is an entry of the same table.  position_geometry (position_geo.h) turns a root row into the solve geometry -- F
+// edges, `other` over the compact edges -- and k_solver_subcube / k_solver_layer solve it into int8 T[2^F] in HBM as they solve a
+// whole board.
 //
-// A row is SERVED when its free real edges are a subset of the root's.  One wavefront per row, lane j = compact edge j of the
+// dbaz_tables owns n_tables slots of 2^max_free bytes.  A solve takes n <= n_tables roots: root i is solved into slot i, the roots
+// of equal F sharing their launches (deep_batch.h).  Per root the device keeps a BatchGeo (in plan order, for the solve) and a
+// DeepRoot (by root index, for the rows).  k_tables_score and k_tables_targets then answer rows, the root of row r being
+// table_of[r]; an index outside [0, n_solved) is "not served", decided before any address is formed from it.  dbaz_deep is a pool
+// of ONE table: the same functions with n = 1, every row answered from table 0 (table_of == nullptr), plus k_deep_policy.
+//
+// A row is SERVED when its free real edges are a subset of its root's.  One wavefront per row, lane j = compact edge j of the
 // root (F0 <= 31 < 64): the drawn ones ballot into `mask`, a free lane reads T[mask | 1 << j] and forms Q with solver_move_q;
 // margin and the finished-game test are solver_facts on the boxes counted from planes 0 / 1, as in endgame.hip.
 static_assert(POSITION_NO_BOX == SOLVER_NO_BOX && POSITION_MAX_FREE == SOLVER_MAX_E, "position_geo.h restates solver.h");
+static_assert(DEEP_BATCH_MAX_FREE == SOLVER_MAX_E && DEEP_BATCH_MIN_LOW == SOLVER_MIN_LOW && DEEP_BATCH_MAX_LOW == SOLVER_MAX_LOW &&
+                  DEEP_BATCH_MAX_HIGH == SOLVER_MAX_HIGH && DEEP_BATCH_LAYER_THREADS == 256,
+              "deep_batch.h restates solver.h");
 
 #define DEEP_DEFAULT_FREE 24 // 16 MiB, the size of the solved 3x3 board
 #define DEEP_WAVES 4
+#define TABLES_DEFAULT 64    // tables of a pool: 1 GiB at the default max_free
 
-// the table's root, by value in the kernel arguments
+struct TablesBoard {
+    int32_t rows, cols, HW, A;
+};
+
+// A table's root, read from HBM by the wavefronts that answer its rows.  The board is not restated here: every kernel that reads
+// a root has the pool's TablesBoard in its arguments, so a row's loads do not wait for the root's.
 struct DeepRoot {
-    int32_t rows, cols, HW, A, F;
+    int32_t F;
     uint64_t free_edges[4];               // the root's free real edges by action index
     uint32_t other[SOLVER_MAX_E][2];      // solver_move_q's box masks over the compact edges
     uint8_t act[SOLVER_MAX_E + 1];        // compact edge -> action index
 };
 
-struct dbaz_deep {
-    int rows = 0, cols = 0, dev = 0, max_free = 0;
-    SolverGeo g;                          // of the last root: E = F and `other`
-    DeepRoot root;
-    int8_t *T = nullptr;                  // [2^max_free]; the last root's table is its first 2^F bytes
+struct dbaz_tables {
+    TablesBoard board;
+    int dev = 0, max_free = 0, n_tables = 0;
+    const char *api = "dbaz_tables";      // the family a message names
+    int8_t *T = nullptr;                  // [n_tables][2^max_free]; root i's table is the first 2^F_i bytes of slot i
+    BatchGeo *geo_dev = nullptr;          // [n_tables], in the order of the last solve's plan
+    DeepRoot *roots_dev = nullptr;        // [n_tables], by root index
+    int8_t *d0_dev = nullptr;             // [n_tables]
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t used = nullptr;            // behind the last kernel that reads T on a caller's stream: the next solve waits for it
-    bool solved = false;
-    // the popcount-ordered work lists of the last (F, L) that used k_solver_subcube: they depend on nothing else
-    int list_F = -1, list_L = -1;
-    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
-    uint16_t *low_dev = nullptr;
-    size_t hi_cap = 0, low_cap = 0;       // entries
-    std::vector<uint32_t> hoff;
+    hipEvent_t used = nullptr;            // behind the last kernel that reads the pool on a caller's stream: the next solve waits for it
+    int n_solved = 0;
+    std::vector<int32_t> n_free, d0;      // of the solved roots
+    std::vector<BatchGeo> geo_host;       // what the last solve uploaded; alive until its copies are done
+    std::vector<DeepRoot> roots_host;
+    std::vector<WorkLists> lists;
     double solve_ms = -1.0;
-    int d0 = -128;
     std::string err;
 };
 
-static thread_local std::string g_deep_error; // message of a failed dbaz_deep_create; per thread
+// A pool of one table.  Everything dbaz_deep_info reports is the pool's: no root solved means no table.
+struct dbaz_deep : dbaz_tables {};
 
-static int derr(dbaz_deep *d, int code, const char *fmt, ...)
+// action slot a is a real edge of the board (the sentinels are board[0,:,W-1] and board[1,H-1,:])
+static __device__ __forceinline__ bool board_real_edge(const TablesBoard &B, int a)
 {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    (d ? d->err : g_deep_error) = buf;
-    return code;
+    const int W = B.cols + 1;
+    const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
+    return a < B.A && (p == 0 ? c < B.cols : l < B.rows);
 }
 
-#define DEEP_HIP(d, call)                                                                                           \
-    do {                                                                                                            \
-        hipError_t _err = (call);                                                                                   \
-        if (_err != hipSuccess) return derr(d, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
+// The free real edges of a row by action index, one ballot per 64 action slots (lane l looks at slots l, 64 + l, ...); returns
+// their number.
+template <typename T>
+static __device__ __forceinline__ int row_free_edges(const TablesBoard &B, const T *__restrict__ xr, int lane, uint64_t (&free_edges)[4])
+{
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
+        const int a = w * 64 + lane;
+        free_edges[w] = __ballot(board_real_edge(B, a) && xr[a] == (T)0);
+        n += __popcll(free_edges[w]);
+    }
+    return n;
+}
 
 // What one wavefront finds out about its row, the same in every lane unless noted.
 struct DeepRow {
@@ -543,25 +600,15 @@ struct DeepRow {
 };
 
 template <typename T>
-static __device__ __forceinline__ DeepRow deep_row(const DeepRoot &R, const int8_t *__restrict__ Tb, const T *__restrict__ xr, int lane)
+static __device__ __forceinline__ DeepRow deep_row(const TablesBoard &board, const DeepRoot &R, const int8_t *__restrict__ Tb,
+                                                   const T *__restrict__ xr, int lane)
 {
     DeepRow d;
-    const int W = R.cols + 1, B = R.rows * R.cols;
-    d.n_free = 0;
+    const int cols = board.cols, HW = board.HW, W = cols + 1, B = board.rows * cols;
+    d.n_free = row_free_edges(board, xr, lane, d.row_free);
     d.served = true;
 #pragma unroll
-    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
-        const int a = w * 64 + lane;
-        bool is_free = false;
-        if (a < R.A) {
-            const int p = a / R.HW, l = (a % R.HW) / W, c = a % W;
-            const bool real = p == 0 ? c < R.cols : l < R.rows; // sentinels: board[0,:,W-1] and board[1,H-1,:]
-            is_free = real && xr[a] == (T)0;
-        }
-        d.row_free[w] = __ballot(is_free);
-        d.n_free += __popcll(d.row_free[w]);
-        d.served = d.served && (d.row_free[w] & ~R.free_edges[w]) == 0ull;
-    }
+    for (int w = 0; w < DBAZ_MAX_A / 64; w++) d.served = d.served && (d.row_free[w] & ~R.free_edges[w]) == 0ull;
     const bool edge = lane < R.F;
     d.a = edge ? (int)R.act[lane] : 0;
     const bool drawn = edge && xr[d.a] != (T)0;
@@ -571,12 +618,12 @@ static __device__ __forceinline__ DeepRow deep_row(const DeepRoot &R, const int8
         const int b = b0 + lane;
         bool c = false;
         if (b < B) {
-            const int at = (b / R.cols) * W + b % R.cols;
-            c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[R.HW + at] != (T)0 && xr[R.HW + at + 1] != (T)0;
+            const int at = (b / cols) * W + b % cols;
+            c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[HW + at] != (T)0 && xr[HW + at + 1] != (T)0;
         }
         closed += __popcll(__ballot(c));
     }
-    d.f = solver_facts(B, closed, (int)xr[2 * R.HW]);
+    d.f = solver_facts(B, closed, (int)xr[2 * HW]);
     d.open = d.f.res == DBAZ_RESULT_NONE;
     d.cand = d.served && d.open && edge && !drawn;
     d.q = d.cand ? solver_move_q(R.other[lane][0], R.other[lane][1], d.m, (int)Tb[d.m | (1u << lane)]) : 0;
@@ -586,17 +633,17 @@ static __device__ __forceinline__ DeepRow deep_row(const DeepRoot &R, const int8
 // dbaz_endgame_score's outputs of the served rows, plus `served`.  q[a] goes out once per action slot: the lane of slot a finds
 // the slot's compact edge as the rank of a in the root's edge set and fetches that lane's Q.  policy_mass: every lane walks the
 // compact edges in ascending order and adds the members' pi in float32 -- k_endgame_score's additions, hence its bits.
-// deep_score_row: one row of one wavefront, shared by k_deep_score (one root in the kernel arguments) and k_tables_score (the row's
-// root from an array in HBM).
-static __device__ __forceinline__ void deep_score_row(const DeepRoot &R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x,
-                                                      const float *__restrict__ pi, int r, int lane, int8_t *__restrict__ value,
-                                                      int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass,
-                                                      int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
+// deep_score_row: one row of one wavefront.
+static __device__ __forceinline__ void deep_score_row(const TablesBoard &B, const DeepRoot &R, const int8_t *__restrict__ Tb,
+                                                      const int16_t *__restrict__ x, const float *__restrict__ pi, int r, int lane,
+                                                      int8_t *__restrict__ value, int8_t *__restrict__ diff, int8_t *__restrict__ q,
+                                                      float *__restrict__ mass, int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
 {
-    const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
+    const int A = B.A;
+    const DeepRow d = deep_row(B, R, Tb, x + (size_t)r * 3 * B.HW, lane);
     const int t = d.served ? (int)Tb[d.m] : -128;
     const int v = !d.served ? 0 : d.open ? sgn(d.f.margin + t) : d.f.res;
-    int8_t *qr = q + (size_t)r * R.A;
+    int8_t *qr = q + (size_t)r * A;
     int before = 0; // root edges in the words below
 #pragma unroll
     for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
@@ -604,12 +651,12 @@ static __device__ __forceinline__ void deep_score_row(const DeepRoot &R, const i
         const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
         const int qc = __shfl(d.q, c & 63);
         const bool is_cand = d.served && d.open && ((d.row_free[w] >> lane) & 1ull);
-        if (a < R.A) qr[a] = (int8_t)(is_cand ? qc : -128);
+        if (a < A) qr[a] = (int8_t)(is_cand ? qc : -128);
         before += __popcll(R.free_edges[w]);
     }
     float sum = 0.0f;
     if (mass) {
-        const float p = d.cand ? pi[(size_t)r * R.A + d.a] : 0.0f;
+        const float p = d.cand ? pi[(size_t)r * A + d.a] : 0.0f;
         const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
         for (int c = 0; c < R.F; c++) { // ascending action order
             const float pc = __shfl(p, c);
@@ -625,303 +672,6 @@ static __device__ __forceinline__ void deep_score_row(const DeepRoot &R, const i
     }
 }
 
-__global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_score(DeepRoot R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x,
-                                                                const float *__restrict__ pi, int n, int8_t *__restrict__ value,
-                                                                int8_t *__restrict__ diff, int8_t *__restrict__ q, float *__restrict__ mass,
-                                                                int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
-{
-    const int lane = threadIdx.x & 63;
-    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES)
-        deep_score_row(R, Tb, x, pi, r, lane, value, diff, q, mass, n_free, served);
-}
-
-// The table as a (p, v) evaluator with dbaz_exact_policy's outputs: one-hot on endgame_pick's move, v the true result.  A finished
-// game: p = 0, v = get_result; a row that is not served: p = 0, v = 0.
-__global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_policy(DeepRoot R, const int8_t *__restrict__ Tb, const int16_t *__restrict__ x, int n,
-                                                                 uint64_t pick_seed, float *__restrict__ P, float *__restrict__ V,
-                                                                 uint8_t *__restrict__ served)
-{
-    const int lane = threadIdx.x & 63;
-    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
-        const DeepRow d = deep_row(R, Tb, x + (size_t)r * 3 * R.HW, lane);
-        const int pick = endgame_pick(d.cand, d.q, d.a, pick_seed);
-        float *pr = P + (size_t)r * R.A;
-        for (int a = lane; a < R.A; a += 64) pr[a] = a == pick ? 1.0f : 0.0f;
-        if (lane == 0) {
-            V[r] = !d.served ? 0.0f : (float)(d.open ? sgn(d.f.margin + (int)Tb[d.m]) : d.f.res);
-            served[r] = d.served ? 1 : 0;
-        }
-    }
-}
-
-extern "C" const char *dbaz_deep_last_error(const dbaz_deep *d) { return d ? d->err.c_str() : g_deep_error.c_str(); }
-
-extern "C" void dbaz_deep_destroy(dbaz_deep *d)
-{
-    if (!d) return;
-    (void)hipSetDevice(d->dev);
-    for (void *b : {(void *)d->T, (void *)d->hi_dev, (void *)d->low_dev, (void *)d->off_dev})
-        if (b) (void)hipFree(b);
-    for (hipEvent_t e : {d->ev0, d->ev1, d->used})
-        if (e) (void)hipEventDestroy(e);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-}
-
-extern "C" int dbaz_deep_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_deep **out)
-{
-    if (!out) return derr(nullptr, DBAZ_EINVAL, "null argument");
-    *out = nullptr;
-    if (rows < 1 || cols < 1) return derr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
-    const long long A = 2ll * (rows + 1ll) * (cols + 1ll);
-    if (A > DBAZ_MAX_A) return derr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
-    if (max_free < 0 || max_free > SOLVER_MAX_E)
-        return derr(nullptr, DBAZ_EINVAL, "max_free %d: a position's table holds 2^F bytes, 1 <= max_free <= %d (0 = %d)", max_free, SOLVER_MAX_E,
-                    DEEP_DEFAULT_FREE);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return derr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
-    dbaz_deep *d = new dbaz_deep();
-    d->rows = rows; d->cols = cols; d->dev = device;
-    d->max_free = max_free == 0 ? DEEP_DEFAULT_FREE : max_free;
-    d->g = SolverGeo();
-    d->root = DeepRoot();
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreate(&d->stream);
-    if (e == hipSuccess) e = hipEventCreate(&d->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&d->ev1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->used, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_solver_subcube, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
-    if (e != hipSuccess) {
-        const std::string msg = hipGetErrorString(e);
-        (void)hipGetLastError();
-        dbaz_deep_destroy(d);
-        return derr(nullptr, DBAZ_EDEVICE, "deep endgame setup failed: %s", msg.c_str());
-    }
-    *out = d;
-    return DBAZ_OK;
-}
-
-// the work lists of (F, L) on the handle: built and copied only when the pair differs from the last solve's
-static int deep_work_lists(dbaz_deep *d, int F, int L)
-{
-    if (d->list_F == F && d->list_L == L) return DBAZ_OK;
-    d->list_F = d->list_L = -1;
-    std::vector<uint32_t> lperm, loff, hperm;
-    popcount_order(L, lperm, loff);
-    popcount_order(F - L, hperm, d->hoff);
-    const std::vector<uint16_t> l16(lperm.begin(), lperm.end());
-    if (hperm.size() > d->hi_cap) {
-        if (d->hi_dev) (void)hipFree(d->hi_dev);
-        d->hi_dev = nullptr;
-        d->hi_cap = 0;
-        DEEP_HIP(d, hipMalloc((void **)&d->hi_dev, hperm.size() * 4));
-        d->hi_cap = hperm.size();
-    }
-    if (l16.size() > d->low_cap) {
-        if (d->low_dev) (void)hipFree(d->low_dev);
-        d->low_dev = nullptr;
-        d->low_cap = 0;
-        DEEP_HIP(d, hipMalloc((void **)&d->low_dev, l16.size() * 2));
-        d->low_cap = l16.size();
-    }
-    if (!d->off_dev) DEEP_HIP(d, hipMalloc((void **)&d->off_dev, (SOLVER_MAX_LOW + 2) * 4));
-    DEEP_HIP(d, hipMemcpy(d->hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice));
-    DEEP_HIP(d, hipMemcpy(d->low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice));
-    DEEP_HIP(d, hipMemcpy(d->off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice));
-    d->list_F = F;
-    d->list_L = L;
-    return DBAZ_OK;
-}
-
-extern "C" int dbaz_deep_solve(dbaz_deep *d, const int16_t *root_row_host, int32_t low_bits)
-{
-    if (!d) return DBAZ_EINVAL;
-    if (!root_row_host) return derr(d, DBAZ_EINVAL, "dbaz_deep_solve: null root row");
-    d->solved = false; // whatever happens below, the old table is not handed out again
-    PositionGeo pg;
-    position_geometry(d->rows, d->cols, root_row_host, pg);
-    const int F = pg.F;
-    if (F > d->max_free)
-        return derr(d, DBAZ_EINVAL, "the root has %d free edges: this handle's table holds 2^%d bytes (max_free <= %d)", F, d->max_free, SOLVER_MAX_E);
-    const bool plain = low_bits == -1 || F < SOLVER_MIN_LOW;
-    const int L = low_bits == 0 ? default_low_bits(F) : low_bits;
-    if (!plain && (L < SOLVER_MIN_LOW || L > SOLVER_MAX_LOW || L > F || F - L > SOLVER_MAX_HIGH))
-        return derr(d, DBAZ_EINVAL, "low_bits %d: F = %d needs max(%d, F - %d) <= low_bits <= min(F, %d) (0 = default, -1 = plain kernel)",
-                    low_bits, F, SOLVER_MIN_LOW, SOLVER_MAX_HIGH, SOLVER_MAX_LOW);
-    DEEP_HIP(d, hipSetDevice(d->dev));
-    if (!d->T) {
-        const size_t bytes = (size_t)1 << d->max_free;
-        const hipError_t e = hipMalloc((void **)&d->T, bytes);
-        if (e != hipSuccess) {
-            d->T = nullptr;
-            (void)hipGetLastError();
-            return derr(d, DBAZ_EDEVICE, "table of %zu bytes: %s", bytes, hipGetErrorString(e));
-        }
-    }
-    if (!plain) {
-        const int rc = deep_work_lists(d, F, L);
-        if (rc != DBAZ_OK) {
-            (void)hipGetLastError();
-            return rc;
-        }
-    }
-    d->root = DeepRoot();
-    d->root.rows = d->rows; d->root.cols = d->cols;
-    d->root.HW = (d->rows + 1) * (d->cols + 1); d->root.A = 2 * d->root.HW; d->root.F = F;
-    d->g = SolverGeo();
-    d->g.rows = d->rows; d->g.cols = d->cols; d->g.HW = d->root.HW; d->g.A = d->root.A; d->g.E = F;
-    for (int w = 0; w < 4; w++) d->root.free_edges[w] = pg.free_edges[w];
-    for (int j = 0; j < SOLVER_MAX_E; j++) {
-        d->root.act[j] = pg.act[j];
-        for (int k = 0; k < 2; k++) d->root.other[j][k] = d->g.other[j][k] = pg.other[j][k];
-    }
-    hipError_t e = hipStreamWaitEvent(d->stream, d->used, 0); // rows still being answered from the old table
-    if (e == hipSuccess) e = hipEventRecord(d->ev0, d->stream);
-    if (e == hipSuccess) {
-        if (plain) {
-            const unsigned grid = (unsigned)((((size_t)1 << F) + 255) / 256);
-            for (int k = F; k >= 0; k--) k_solver_layer<<<grid, 256, 0, d->stream>>>(d->g, d->T, k);
-        } else {
-            for (int k = F - L; k >= 0; k--)
-                k_solver_subcube<<<d->hoff[k + 1] - d->hoff[k], SOLVER_THREADS, (size_t)1 << L, d->stream>>>(d->g, d->T, L, d->hi_dev + d->hoff[k],
-                                                                                                            d->low_dev, d->off_dev);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(d->ev1, d->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(d->ev1);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, d->ev0, d->ev1);
-    int8_t d0 = 0;
-    if (e == hipSuccess) e = hipMemcpy(&d0, d->T, 1, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return derr(d, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
-    d->solved = true;
-    d->solve_ms = ms;
-    d->d0 = d0;
-    return DBAZ_OK;
-}
-
-extern "C" int dbaz_deep_info(const dbaz_deep *d, int32_t *n_free, int64_t *table_bytes, double *solve_ms, int32_t *d0)
-{
-    if (!d) return DBAZ_EINVAL;
-    if (n_free) *n_free = d->solved ? d->root.F : -1;
-    if (table_bytes) *table_bytes = (int64_t)1 << d->max_free;
-    if (solve_ms) *solve_ms = d->solve_ms;
-    if (d0) *d0 = d->solved ? d->d0 : -128;
-    return DBAZ_OK;
-}
-
-extern "C" int dbaz_deep_table(dbaz_deep *d, int8_t *host_dst, int64_t first, int64_t count)
-{
-    if (!d) return DBAZ_EINVAL;
-    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_table before a successful dbaz_deep_solve");
-    const int64_t n = (int64_t)1 << d->root.F;
-    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
-        return derr(d, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
-    if (count == 0) return DBAZ_OK;
-    DEEP_HIP(d, hipSetDevice(d->dev));
-    DEEP_HIP(d, hipMemcpy(host_dst, d->T + first, (size_t)count, hipMemcpyDeviceToHost));
-    return DBAZ_OK;
-}
-
-static unsigned deep_blocks(int n) { return (unsigned)std::min((n + DEEP_WAVES - 1) / DEEP_WAVES, 16384); }
-
-extern "C" int dbaz_deep_score(dbaz_deep *d, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev, int8_t *q_dev,
-                               float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
-{
-    if (!d) return DBAZ_EINVAL;
-    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_score before a successful dbaz_deep_solve");
-    if (n < 0 || (n > 0 && (!x_dev || !value_dev || !diff_dev || !q_dev || !n_free_dev || !served_dev)) || (pi_dev && !mass_dev))
-        return derr(d, DBAZ_EINVAL, "dbaz_deep_score: bad argument (n = %d)", n);
-    if (n == 0) return DBAZ_OK;
-    DEEP_HIP(d, hipSetDevice(d->dev));
-    k_deep_score<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->root, d->T, x_dev, pi_dev, n, value_dev, diff_dev, q_dev,
-                                                                             pi_dev ? mass_dev : nullptr, n_free_dev, served_dev);
-    DEEP_HIP(d, hipGetLastError());
-    DEEP_HIP(d, hipEventRecord(d->used, (hipStream_t)stream));
-    return DBAZ_OK;
-}
-
-extern "C" int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev, uint8_t *served_dev,
-                                void *stream)
-{
-    if (!d) return DBAZ_EINVAL;
-    if (!d->solved) return derr(d, DBAZ_ESTATE, "dbaz_deep_policy before a successful dbaz_deep_solve");
-    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !served_dev))) return derr(d, DBAZ_EINVAL, "dbaz_deep_policy: bad argument (n = %d)", n);
-    if (n == 0) return DBAZ_OK;
-    DEEP_HIP(d, hipSetDevice(d->dev));
-    k_deep_policy<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->root, d->T, x_dev, n, pick_seed, p_dev, v_dev, served_dev);
-    DEEP_HIP(d, hipGetLastError());
-    DEEP_HIP(d, hipEventRecord(d->used, (hipStream_t)stream));
-    return DBAZ_OK;
-}
-
-// ====================================================================================
-// Deep endgames in batches: a pool of tables, many roots solved side by side, rows answered each from its table
-// ====================================================================================
-// dbaz_tables owns n_tables slots of 2^max_free bytes.  dbaz_tables_solve takes n <= n_tables roots: root i is solved into slot i
-// by k_solver_subcube_batch / k_solver_layer_batch, the roots of equal F sharing their launches (deep_batch.h).  Per root the
-// device keeps a BatchGeo (in plan order, for the solve) and a DeepRoot (by root index, for the rows).  k_tables_score and
-// k_tables_targets then answer rows as k_deep_score does, the root of row r being table_of[r]; an index outside [0, n_solved) is
-// "not served", decided before any address is formed from it.
-static_assert(DEEP_BATCH_MAX_FREE == SOLVER_MAX_E && DEEP_BATCH_MIN_LOW == SOLVER_MIN_LOW && DEEP_BATCH_MAX_LOW == SOLVER_MAX_LOW &&
-                  DEEP_BATCH_MAX_HIGH == SOLVER_MAX_HIGH && DEEP_BATCH_LAYER_THREADS == 256,
-              "deep_batch.h restates solver.h");
-static_assert(sizeof(BatchGeo) == 256, "one root's solve geometry");
-
-#define TABLES_DEFAULT 64 // tables of a pool: 1 GiB at the default max_free
-
-struct TablesBoard {
-    int32_t rows, cols, HW, A;
-};
-
-// the popcount-ordered work lists of one (F, L): they depend on nothing else and stay on the handle
-struct TablesLists {
-    int F = 0, L = 0;
-    uint32_t *hi_dev = nullptr, *off_dev = nullptr;
-    uint16_t *low_dev = nullptr;
-    std::vector<uint32_t> hoff;
-};
-
-struct dbaz_tables {
-    TablesBoard board;
-    int dev = 0, max_free = 0, n_tables = 0;
-    int8_t *T = nullptr;                  // [n_tables][2^max_free]; root i's table is the first 2^F_i bytes of slot i
-    BatchGeo *geo_dev = nullptr;          // [n_tables], in the order of the last solve's plan
-    DeepRoot *roots_dev = nullptr;        // [n_tables], by root index
-    int8_t *d0_dev = nullptr;             // [n_tables]
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t used = nullptr;            // behind the last kernel that reads the pool on a caller's stream: the next solve waits for it
-    int n_solved = 0;
-    std::vector<int32_t> n_free, d0;      // of the solved roots
-    std::vector<BatchGeo> geo_host;       // what the last solve uploaded; alive until its copies are done
-    std::vector<DeepRoot> roots_host;
-    std::vector<TablesLists> lists;
-    double solve_ms = -1.0;
-    std::string err;
-};
-
-static thread_local std::string g_tables_error; // message of a failed dbaz_tables_create; per thread
-
-static int terr(dbaz_tables *t, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    (t ? t->err : g_tables_error) = buf;
-    return code;
-}
-
-#define TABLES_HIP(t, call)                                                                                         \
-    do {                                                                                                            \
-        hipError_t _err = (call);                                                                                   \
-        if (_err != hipSuccess) return terr(t, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
-
 // T[slot i][0], the score difference of root i for its mover
 __global__ void __launch_bounds__(256) k_tables_heads(const int8_t *__restrict__ T, int stride_bits, int n, int8_t *__restrict__ out)
 {
@@ -929,26 +679,8 @@ __global__ void __launch_bounds__(256) k_tables_heads(const int8_t *__restrict__
     if (i < n) out[i] = T[(size_t)i << stride_bits];
 }
 
-// the free real edges of a row, for the rows no root is read for (deep_row counts them the same way)
-static __device__ __forceinline__ int tables_row_free(const TablesBoard &B, const int16_t *__restrict__ xr, int lane)
-{
-    const int W = B.cols + 1;
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
-        const int a = w * 64 + lane;
-        bool is_free = false;
-        if (a < B.A) {
-            const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
-            const bool real = p == 0 ? c < B.cols : l < B.rows; // sentinels: board[0,:,W-1] and board[1,H-1,:]
-            is_free = real && xr[a] == 0;
-        }
-        n += __popcll(__ballot(is_free));
-    }
-    return n;
-}
-
-// k_deep_score with the root of row r = roots[table_of[r]] and its table = T + table_of[r] * 2^stride_bits.
+// One wavefront per row: the root of row r = roots[table_of[r]] and its table = T + table_of[r] * 2^stride_bits; table_of == nullptr
+// means table 0 for every row (the pool of one).
 __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_score(TablesBoard B, const DeepRoot *__restrict__ roots, int n_solved,
                                                                   const int8_t *__restrict__ T, int stride_bits, const int16_t *__restrict__ x,
                                                                   const float *__restrict__ pi, const int32_t *__restrict__ table_of, int n,
@@ -957,9 +689,10 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_score(TablesBoard B,
 {
     const int lane = threadIdx.x & 63;
     for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
-        const int t = table_of[r];
+        const int t = table_of ? __builtin_amdgcn_readfirstlane(table_of[r]) : 0; // one row per wavefront: a scalar, so are the root's reads
         if ((unsigned)t >= (unsigned)n_solved) { // not served: no root, no table
-            const int nf = tables_row_free(B, x + (size_t)r * 3 * B.HW, lane);
+            uint64_t row_free[4];
+            const int nf = row_free_edges(B, x + (size_t)r * 3 * B.HW, lane, row_free);
             int8_t *qr = q + (size_t)r * B.A;
             for (int a = lane; a < B.A; a += 64) qr[a] = -128;
             if (lane == 0) {
@@ -971,14 +704,14 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_score(TablesBoard B,
             }
             continue;
         }
-        deep_score_row(roots[t], T + ((size_t)t << stride_bits), x, pi, r, lane, value, diff, q, mass, n_free, served);
+        deep_score_row(B, roots[t], T + ((size_t)t << stride_bits), x, pi, r, lane, value, diff, q, mass, n_free, served);
     }
 }
 
 // dbaz_exact_targets' rule (include/dbaz.h) with v and q from the row's table: a row that is not served or of a finished game is
 // left alone; otherwise z <- v and pi by pi_mode over O = the members, S added in ascending action order in float32 as
 // k_endgame_targets adds it, one float32 division per entry -- hence its bits wherever both apply.  The lane of action slot a
-// finds the slot's compact edge as k_deep_score's epilogue does.  pi and z are read and written by the same wavefront only.
+// finds the slot's compact edge as deep_score_row does.  pi and z are read and written by the same wavefront only.
 __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard B, const DeepRoot *__restrict__ roots, int n_solved,
                                                                     const int8_t *__restrict__ T, int stride_bits, const int16_t *__restrict__ x,
                                                                     const int32_t *__restrict__ table_of, int n, int pi_mode, int z_mode, float *pi,
@@ -988,15 +721,17 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard 
     const int lane = threadIdx.x & 63;
     for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
         const int16_t *xr = x + (size_t)r * 3 * B.HW;
-        const int t = table_of[r];
+        const int t = __builtin_amdgcn_readfirstlane(table_of[r]); // one row per wavefront: a scalar, so are the root's reads
         int nf = 0;
         bool touched = false;
         float sum = 0.0f;
-        if ((unsigned)t >= (unsigned)n_solved) nf = tables_row_free(B, xr, lane);
-        else {
+        if ((unsigned)t >= (unsigned)n_solved) {
+            uint64_t row_free[4];
+            nf = row_free_edges(B, xr, lane, row_free);
+        } else {
             const DeepRoot &R = roots[t];
             const int8_t *Tb = T + ((size_t)t << stride_bits);
-            const DeepRow d = deep_row(R, Tb, xr, lane);
+            const DeepRow d = deep_row(B, R, Tb, xr, lane);
             nf = d.n_free;
             if (d.served && d.open) {
                 touched = true;
@@ -1032,39 +767,54 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard 
     }
 }
 
-extern "C" const char *dbaz_tables_last_error(const dbaz_tables *t) { return t ? t->err.c_str() : g_tables_error.c_str(); }
-
-extern "C" void dbaz_tables_destroy(dbaz_tables *t)
+// The table as a (p, v) evaluator with dbaz_exact_policy's outputs: one-hot on endgame_pick's move, v the true result.  A finished
+// game: p = 0, v = get_result; a row that is not served: p = 0, v = 0.  One root, one table (dbaz_deep_policy).
+__global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_policy(TablesBoard B, const DeepRoot *__restrict__ root, const int8_t *__restrict__ Tb,
+                                                                 const int16_t *__restrict__ x, int n, uint64_t pick_seed, float *__restrict__ P,
+                                                                 float *__restrict__ V, uint8_t *__restrict__ served)
 {
-    if (!t) return;
+    const DeepRoot &R = *root;
+    const int lane = threadIdx.x & 63, A = B.A;
+    for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
+        const DeepRow d = deep_row(B, R, Tb, x + (size_t)r * 3 * B.HW, lane);
+        const int pick = endgame_pick(d.cand, d.q, d.a, pick_seed);
+        float *pr = P + (size_t)r * A;
+        for (int a = lane; a < A; a += 64) pr[a] = a == pick ? 1.0f : 0.0f;
+        if (lane == 0) {
+            V[r] = !d.served ? 0.0f : (float)(d.open ? sgn(d.f.margin + (int)Tb[d.m]) : d.f.res);
+            served[r] = d.served ? 1 : 0;
+        }
+    }
+}
+
+// ---- host: the static functions take the pool; dbaz_tables_* and dbaz_deep_* are the two families of entries over them
+static void tables_release(dbaz_tables *t)
+{
     (void)hipSetDevice(t->dev);
     for (void *b : {(void *)t->T, (void *)t->geo_dev, (void *)t->roots_dev, (void *)t->d0_dev})
         if (b) (void)hipFree(b);
-    for (TablesLists &l : t->lists)
-        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
-            if (b) (void)hipFree(b);
+    free_work_lists(t->lists);
     for (hipEvent_t e : {t->ev0, t->ev1, t->used})
         if (e) (void)hipEventDestroy(e);
     if (t->stream) (void)hipStreamDestroy(t->stream);
-    delete t;
 }
 
-extern "C" int dbaz_tables_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, int32_t n_tables, dbaz_tables **out)
+// Checks the arguments, then makes the stream and the events; no table memory before the first solve.  err: the family's slot
+// for a failed create.  On a failure nothing is left on the device.
+static int tables_init(dbaz_tables *t, std::string &err, const char *api, int rows, int cols, int device, int max_free, int n_tables)
 {
-    if (!out) return terr(nullptr, DBAZ_EINVAL, "null argument");
-    *out = nullptr;
-    if (rows < 1 || cols < 1) return terr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    if (rows < 1 || cols < 1) return fail(err, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
     const long long A = 2ll * (rows + 1ll) * (cols + 1ll);
-    if (A > DBAZ_MAX_A) return terr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
+    if (A > DBAZ_MAX_A) return fail(err, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
     if (max_free < 0 || max_free > SOLVER_MAX_E)
-        return terr(nullptr, DBAZ_EINVAL, "max_free %d: a position's table holds 2^F bytes, 1 <= max_free <= %d (0 = %d)", max_free, SOLVER_MAX_E,
+        return fail(err, DBAZ_EINVAL, "max_free %d: a position's table holds 2^F bytes, 1 <= max_free <= %d (0 = %d)", max_free, SOLVER_MAX_E,
                     DEEP_DEFAULT_FREE);
     if (n_tables < 0 || n_tables > DEEP_BATCH_MAX_TABLES)
-        return terr(nullptr, DBAZ_EINVAL, "n_tables %d: a pool holds 1 <= n_tables <= %d tables (0 = %d)", n_tables, DEEP_BATCH_MAX_TABLES, TABLES_DEFAULT);
+        return fail(err, DBAZ_EINVAL, "n_tables %d: a pool holds 1 <= n_tables <= %d tables (0 = %d)", n_tables, DEEP_BATCH_MAX_TABLES, TABLES_DEFAULT);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return terr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
-    dbaz_tables *t = new dbaz_tables();
+        return fail(err, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+    t->api = api;
     t->board.rows = rows; t->board.cols = cols;
     t->board.HW = (rows + 1) * (cols + 1); t->board.A = 2 * t->board.HW;
     t->dev = device;
@@ -1075,58 +825,36 @@ extern "C" int dbaz_tables_create(int32_t rows, int32_t cols, int32_t device, in
     if (e == hipSuccess) e = hipEventCreate(&t->ev0);
     if (e == hipSuccess) e = hipEventCreate(&t->ev1);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->used, hipEventDisableTiming);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_solver_subcube_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_solver_subcube, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << SOLVER_MAX_LOW);
     if (e != hipSuccess) {
         const std::string msg = hipGetErrorString(e);
         (void)hipGetLastError();
-        dbaz_tables_destroy(t);
-        return terr(nullptr, DBAZ_EDEVICE, "deep tables setup failed: %s", msg.c_str());
+        tables_release(t);
+        return fail(err, DBAZ_EDEVICE, "%s_create: setup failed: %s", api, msg.c_str());
     }
-    *out = t;
     return DBAZ_OK;
 }
 
-// the work lists of (F, L) on the handle: built and copied the first time the pair is asked for
-static int tables_work_lists(dbaz_tables *t, int F, int L, int *index)
+template <typename H>
+static int tables_create(H **out, std::string &err, const char *api, int rows, int cols, int device, int max_free, int n_tables)
 {
-    for (size_t i = 0; i < t->lists.size(); i++)
-        if (t->lists[i].F == F && t->lists[i].L == L) {
-            *index = (int)i;
-            return DBAZ_OK;
-        }
-    TablesLists l;
-    l.F = F;
-    l.L = L;
-    std::vector<uint32_t> lperm, loff, hperm;
-    popcount_order(L, lperm, loff);
-    popcount_order(F - L, hperm, l.hoff);
-    const std::vector<uint16_t> l16(lperm.begin(), lperm.end());
-    hipError_t e = hipMalloc((void **)&l.hi_dev, hperm.size() * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&l.low_dev, l16.size() * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&l.off_dev, loff.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(l.hi_dev, hperm.data(), hperm.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(l.low_dev, l16.data(), l16.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(l.off_dev, loff.data(), loff.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        for (void *b : {(void *)l.hi_dev, (void *)l.low_dev, (void *)l.off_dev})
-            if (b) (void)hipFree(b);
-        (void)hipGetLastError();
-        return terr(t, DBAZ_EDEVICE, "work lists of F = %d, L = %d: %s", F, L, hipGetErrorString(e));
-    }
-    t->lists.push_back(std::move(l));
-    *index = (int)t->lists.size() - 1;
-    return DBAZ_OK;
+    if (!out) return fail(err, DBAZ_EINVAL, "null argument");
+    *out = nullptr;
+    H *h = new H();
+    const int rc = tables_init(h, err, api, rows, cols, device, max_free, n_tables);
+    if (rc == DBAZ_OK) *out = h;
+    else delete h;
+    return rc;
 }
 
-extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host, int32_t low_bits)
+static int tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host, int32_t low_bits)
 {
-    if (!t) return DBAZ_EINVAL;
     t->n_solved = 0; // whatever happens below, the old tables are not handed out again
     t->n_free.clear();
     t->d0.clear();
-    if (n_roots < 1 || !roots_host) return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %d roots (at least 1, at most the pool's %d)", n_roots, t->n_tables);
-    if (n_roots > t->n_tables) return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %d roots do not fit a pool of %d tables", n_roots, t->n_tables);
+    if (!roots_host) return fail(t->err, DBAZ_EINVAL, "%s_solve: null root rows", t->api);
+    if (n_roots < 1) return fail(t->err, DBAZ_EINVAL, "%s_solve: %d roots (at least 1, at most the pool's %d)", t->api, n_roots, t->n_tables);
+    if (n_roots > t->n_tables) return fail(t->err, DBAZ_EINVAL, "%s_solve: %d roots do not fit a pool of %d tables", t->api, n_roots, t->n_tables);
     const TablesBoard &B = t->board;
     std::vector<PositionGeo> pg((size_t)n_roots);
     std::vector<int32_t> F((size_t)n_roots);
@@ -1136,8 +864,8 @@ extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t 
     }
     DeepBatchPlan plan;
     if (deep_batch_plan(F.data(), n_roots, t->max_free, t->n_tables, low_bits, plan) != 0)
-        return terr(t, DBAZ_EINVAL, "dbaz_tables_solve: %s", plan.error.c_str());
-    TABLES_HIP(t, hipSetDevice(t->dev));
+        return fail(t->err, DBAZ_EINVAL, "%s_solve: %s", t->api, plan.error.c_str());
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
     if (!t->T) {
         const size_t bytes = (size_t)deep_batch_slot_offset(t->n_tables, t->max_free); // 64 bits: 64 x 2^31 is past 32
         hipError_t e = hipMalloc((void **)&t->T, bytes);
@@ -1148,14 +876,16 @@ extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t 
             if (t->T) (void)hipFree(t->T);
             t->T = nullptr;
             (void)hipGetLastError();
-            return terr(t, DBAZ_EDEVICE, "pool of %d tables, %zu bytes: %s", t->n_tables, bytes, hipGetErrorString(e));
+            return fail(t->err, DBAZ_EDEVICE, "pool of %d tables, %zu bytes: %s", t->n_tables, bytes, hipGetErrorString(e));
         }
     }
     std::vector<int> lists(plan.groups.size(), -1); // per group, its entry of t->lists
     for (size_t g = 0; g < plan.groups.size(); g++)
         if (!plan.groups[g].plain) {
-            const int rc = tables_work_lists(t, plan.groups[g].F, plan.groups[g].L, &lists[g]);
-            if (rc != DBAZ_OK) return rc;
+            hipError_t e = hipSuccess;
+            lists[g] = work_lists(t->lists, plan.groups[g].F, plan.groups[g].L, &e);
+            if (e != hipSuccess)
+                return fail(t->err, DBAZ_EDEVICE, "work lists of F = %d, L = %d: %s", plan.groups[g].F, plan.groups[g].L, hipGetErrorString(e));
         }
 
     t->geo_host.assign((size_t)n_roots, BatchGeo());
@@ -1164,9 +894,8 @@ extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t 
         const int i = plan.order[at];
         BatchGeo &bg = t->geo_host[at];
         DeepRoot &R = t->roots_host[i];
-        bg.F = F[i];
+        bg.F = R.F = F[i];
         bg.slot = i;
-        R.rows = B.rows; R.cols = B.cols; R.HW = B.HW; R.A = B.A; R.F = F[i];
         for (int w = 0; w < 4; w++) R.free_edges[w] = pg[i].free_edges[w];
         for (int j = 0; j < SOLVER_MAX_E; j++) {
             R.act[j] = pg[i].act[j];
@@ -1181,11 +910,11 @@ extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t 
         for (const DeepBatchLaunch &l : plan.launches) { // back to back: no host synchronisation between groups
             const DeepBatchGroup &g = plan.groups[l.group];
             const dim3 grid(l.grid_x, l.grid_y);
-            if (g.plain) k_solver_layer_batch<<<grid, 256, 0, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, l.k);
+            if (g.plain) k_solver_layer<<<grid, 256, 0, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, l.k);
             else {
-                const TablesLists &w = t->lists[(size_t)lists[l.group]];
-                k_solver_subcube_batch<<<grid, SOLVER_THREADS, (size_t)1 << g.L, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, g.L,
-                                                                                             w.hi_dev + w.hoff[l.k], w.low_dev, w.off_dev);
+                const WorkLists &w = t->lists[(size_t)lists[l.group]];
+                k_solver_subcube<<<grid, SOLVER_THREADS, (size_t)1 << g.L, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, g.L,
+                                                                                       w.hi_dev + w.hoff[l.k], w.low_dev, w.off_dev);
             }
         }
         k_tables_heads<<<(n_roots + 255) / 256, 256, 0, t->stream>>>(t->T, t->max_free, n_roots, t->d0_dev);
@@ -1200,13 +929,65 @@ extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t 
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, t->ev0, t->ev1);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return terr(t, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
+        return fail(t->err, DBAZ_EDEVICE, "solve failed: %s", hipGetErrorString(e));
     }
     t->n_free.assign(F.begin(), F.end());
     t->d0.assign(heads.begin(), heads.end());
     t->solve_ms = ms;
     t->n_solved = n_roots;
     return DBAZ_OK;
+}
+
+static int tables_table(dbaz_tables *t, int32_t i, int8_t *host_dst, int64_t first, int64_t count)
+{
+    if (t->n_solved == 0) return fail(t->err, DBAZ_ESTATE, "%s_table before a successful %s_solve", t->api, t->api);
+    if (i < 0 || i >= t->n_solved) return fail(t->err, DBAZ_EINVAL, "table %d: the last solve filled tables 0 .. %d", i, t->n_solved - 1);
+    const int64_t n = (int64_t)1 << t->n_free[(size_t)i];
+    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
+        return fail(t->err, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
+    if (count == 0) return DBAZ_OK;
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
+    CHECK_HIP(t->err, hipMemcpy(host_dst, t->T + deep_batch_slot_offset(i, t->max_free) + first, (size_t)count, hipMemcpyDeviceToHost));
+    return DBAZ_OK;
+}
+
+static unsigned deep_blocks(int n) { return (unsigned)std::min((n + DEEP_WAVES - 1) / DEEP_WAVES, 16384); }
+
+// one_table: every row is answered from table 0 and there is no table_dev (the pool of one)
+static int tables_score(dbaz_tables *t, bool one_table, int32_t n, const int16_t *x_dev, const float *pi_dev, const int32_t *table_dev,
+                        int8_t *value_dev, int8_t *diff_dev, int8_t *q_dev, float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
+{
+    if (t->n_solved == 0) return fail(t->err, DBAZ_ESTATE, "%s_score before a successful %s_solve", t->api, t->api);
+    if (n < 0 || (n > 0 && (!x_dev || (!one_table && !table_dev) || !value_dev || !diff_dev || !q_dev || !n_free_dev || !served_dev)) ||
+        (pi_dev && !mass_dev))
+        return fail(t->err, DBAZ_EINVAL, "%s_score: bad argument (n = %d)", t->api, n);
+    if (n == 0) return DBAZ_OK;
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
+    k_tables_score<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(t->board, t->roots_dev, t->n_solved, t->T, t->max_free, x_dev, pi_dev,
+                                                                               table_dev, n, value_dev, diff_dev, q_dev, pi_dev ? mass_dev : nullptr,
+                                                                               n_free_dev, served_dev);
+    CHECK_HIP(t->err, hipGetLastError());
+    CHECK_HIP(t->err, hipEventRecord(t->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+extern "C" const char *dbaz_tables_last_error(const dbaz_tables *t) { return t ? t->err.c_str() : g_tables_error.c_str(); }
+
+extern "C" void dbaz_tables_destroy(dbaz_tables *t)
+{
+    if (!t) return;
+    tables_release(t);
+    delete t;
+}
+
+extern "C" int dbaz_tables_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, int32_t n_tables, dbaz_tables **out)
+{
+    return tables_create(out, g_tables_error, "dbaz_tables", rows, cols, device, max_free, n_tables);
+}
+
+extern "C" int dbaz_tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host, int32_t low_bits)
+{
+    return t ? tables_solve(t, n_roots, roots_host, low_bits) : DBAZ_EINVAL;
 }
 
 extern "C" int dbaz_tables_info(const dbaz_tables *t, int32_t *n_solved, int64_t *table_bytes, int64_t *pool_bytes, double *solve_ms)
@@ -1229,51 +1010,86 @@ extern "C" int dbaz_tables_roots(const dbaz_tables *t, int32_t *n_free_out, int3
 
 extern "C" int dbaz_tables_table(dbaz_tables *t, int32_t i, int8_t *host_dst, int64_t first, int64_t count)
 {
-    if (!t) return DBAZ_EINVAL;
-    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_table before a successful dbaz_tables_solve");
-    if (i < 0 || i >= t->n_solved) return terr(t, DBAZ_EINVAL, "table %d: the last solve filled tables 0 .. %d", i, t->n_solved - 1);
-    const int64_t n = (int64_t)1 << t->n_free[(size_t)i];
-    if (!host_dst || first < 0 || count < 0 || first > n || count > n - first)
-        return terr(t, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
-    if (count == 0) return DBAZ_OK;
-    TABLES_HIP(t, hipSetDevice(t->dev));
-    TABLES_HIP(t, hipMemcpy(host_dst, t->T + deep_batch_slot_offset(i, t->max_free) + first, (size_t)count, hipMemcpyDeviceToHost));
-    return DBAZ_OK;
+    return t ? tables_table(t, i, host_dst, first, count) : DBAZ_EINVAL;
 }
 
 extern "C" int dbaz_tables_score(dbaz_tables *t, int32_t n, const int16_t *x_dev, const float *pi_dev, const int32_t *table_dev, int8_t *value_dev,
                                  int8_t *diff_dev, int8_t *q_dev, float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
 {
-    if (!t) return DBAZ_EINVAL;
-    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_score before a successful dbaz_tables_solve");
-    if (n < 0 || (n > 0 && (!x_dev || !table_dev || !value_dev || !diff_dev || !q_dev || !n_free_dev || !served_dev)) || (pi_dev && !mass_dev))
-        return terr(t, DBAZ_EINVAL, "dbaz_tables_score: bad argument (n = %d)", n);
-    if (n == 0) return DBAZ_OK;
-    TABLES_HIP(t, hipSetDevice(t->dev));
-    k_tables_score<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(t->board, t->roots_dev, t->n_solved, t->T, t->max_free, x_dev, pi_dev,
-                                                                               table_dev, n, value_dev, diff_dev, q_dev, pi_dev ? mass_dev : nullptr,
-                                                                               n_free_dev, served_dev);
-    TABLES_HIP(t, hipGetLastError());
-    TABLES_HIP(t, hipEventRecord(t->used, (hipStream_t)stream));
-    return DBAZ_OK;
+    return !t ? DBAZ_EINVAL : tables_score(t, false, n, x_dev, pi_dev, table_dev, value_dev, diff_dev, q_dev, mass_dev, n_free_dev, served_dev, stream);
 }
 
 extern "C" int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_dev, const int32_t *table_dev, int32_t pi_mode, int32_t z_mode,
                                    float *pi_dev, float *z_dev, int16_t *n_free_dev, float *mass_dev, uint8_t *relabelled_dev, void *stream)
 {
     if (!t) return DBAZ_EINVAL;
-    if (t->n_solved == 0) return terr(t, DBAZ_ESTATE, "dbaz_tables_targets before a successful dbaz_tables_solve");
+    if (t->n_solved == 0) return fail(t->err, DBAZ_ESTATE, "dbaz_tables_targets before a successful dbaz_tables_solve");
     if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1)
-        return terr(t, DBAZ_EINVAL, "dbaz_tables_targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode,
+        return fail(t->err, DBAZ_EINVAL, "dbaz_tables_targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode,
                     z_mode);
     if (n < 0 || (n > 0 && (!x_dev || !table_dev || (pi_mode != 0 && !pi_dev) || (z_mode != 0 && !z_dev))))
-        return terr(t, DBAZ_EINVAL, "dbaz_tables_targets: bad argument (n = %d; a mode other than keep needs its array)", n);
+        return fail(t->err, DBAZ_EINVAL, "dbaz_tables_targets: bad argument (n = %d; a mode other than keep needs its array)", n);
     if (n == 0) return DBAZ_OK;
-    TABLES_HIP(t, hipSetDevice(t->dev));
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
     k_tables_targets<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(t->board, t->roots_dev, t->n_solved, t->T, t->max_free, x_dev, table_dev,
                                                                                  n, pi_mode, z_mode, pi_dev, z_dev, n_free_dev, mass_dev, relabelled_dev);
-    TABLES_HIP(t, hipGetLastError());
-    TABLES_HIP(t, hipEventRecord(t->used, (hipStream_t)stream));
+    CHECK_HIP(t->err, hipGetLastError());
+    CHECK_HIP(t->err, hipEventRecord(t->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+// ---- dbaz_deep_*: the pool of one
+extern "C" const char *dbaz_deep_last_error(const dbaz_deep *d) { return d ? d->err.c_str() : g_deep_error.c_str(); }
+
+extern "C" void dbaz_deep_destroy(dbaz_deep *d)
+{
+    if (!d) return;
+    tables_release(d);
+    delete d;
+}
+
+extern "C" int dbaz_deep_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_deep **out)
+{
+    return tables_create(out, g_deep_error, "dbaz_deep", rows, cols, device, max_free, 1);
+}
+
+extern "C" int dbaz_deep_solve(dbaz_deep *d, const int16_t *root_row_host, int32_t low_bits)
+{
+    return d ? tables_solve(d, 1, root_row_host, low_bits) : DBAZ_EINVAL;
+}
+
+extern "C" int dbaz_deep_info(const dbaz_deep *d, int32_t *n_free, int64_t *table_bytes, double *solve_ms, int32_t *d0)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (n_free) *n_free = d->n_solved ? d->n_free[0] : -1;
+    if (table_bytes) *table_bytes = (int64_t)1 << d->max_free;
+    if (solve_ms) *solve_ms = d->solve_ms;
+    if (d0) *d0 = d->n_solved ? d->d0[0] : -128;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_deep_table(dbaz_deep *d, int8_t *host_dst, int64_t first, int64_t count)
+{
+    return d ? tables_table(d, 0, host_dst, first, count) : DBAZ_EINVAL;
+}
+
+extern "C" int dbaz_deep_score(dbaz_deep *d, int32_t n, const int16_t *x_dev, const float *pi_dev, int8_t *value_dev, int8_t *diff_dev, int8_t *q_dev,
+                               float *mass_dev, int16_t *n_free_dev, uint8_t *served_dev, void *stream)
+{
+    return d ? tables_score(d, true, n, x_dev, pi_dev, nullptr, value_dev, diff_dev, q_dev, mass_dev, n_free_dev, served_dev, stream) : DBAZ_EINVAL;
+}
+
+extern "C" int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, uint64_t pick_seed, float *p_dev, float *v_dev, uint8_t *served_dev,
+                                void *stream)
+{
+    if (!d) return DBAZ_EINVAL;
+    if (d->n_solved == 0) return fail(d->err, DBAZ_ESTATE, "dbaz_deep_policy before a successful dbaz_deep_solve");
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !served_dev))) return fail(d->err, DBAZ_EINVAL, "dbaz_deep_policy: bad argument (n = %d)", n);
+    if (n == 0) return DBAZ_OK;
+    CHECK_HIP(d->err, hipSetDevice(d->dev));
+    k_deep_policy<<<deep_blocks(n), 64 * DEEP_WAVES, 0, (hipStream_t)stream>>>(d->board, d->roots_dev, d->T, x_dev, n, pick_seed, p_dev, v_dev, served_dev);
+    CHECK_HIP(d->err, hipGetLastError());
+    CHECK_HIP(d->err, hipEventRecord(d->used, (hipStream_t)stream));
     return DBAZ_OK;
 }
 
@@ -1343,10 +1159,7 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
         int F = 0;
 #pragma unroll
         for (int w = 0; w < 4; w++) {
-            const int a = w * 64 + lane;
-            const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
-            const bool real = a < B.A && (p == 0 ? c < B.cols : l < B.rows); // sentinels: board[0,:,W-1] and board[1,H-1,:]
-            fe[w] = rq->free_edges[w] & __ballot(real);
+            fe[w] = rq->free_edges[w] & __ballot(board_real_edge(B, w * 64 + lane));
             subset = subset && (fe[w] & ~h->free_edges[w]) == 0ull;
             F += __popcll(fe[w]);
         }
@@ -1440,8 +1253,8 @@ bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *ma
 int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[4])
 {
     SlotTablesPlan plan;
-    if (slot_tables_plan(t->max_free, plan) != 0) return terr(t, DBAZ_EINVAL, "slot tables: max_free %d is outside 0 .. %d", t->max_free, SOLVER_MAX_E);
-    TABLES_HIP(t, hipSetDevice(t->dev));
+    if (slot_tables_plan(t->max_free, plan) != 0) return fail(t->err, DBAZ_EINVAL, "slot tables: max_free %d is outside 0 .. %d", t->max_free, SOLVER_MAX_E);
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
     // The work lists of every (F, L) with F <= max_free in ONE buffer that the caller owns -- not the lists cached on t, which go
     // away with t while the engine may search on under another handle: all 32-bit lists (the high patterns per F, the layer
     // offsets of the low masks per L) first, then the 16-bit low masks per L.
@@ -1507,7 +1320,7 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[
         for (void *q : p)
             if (q) (void)hipFree(q);
         (void)hipGetLastError();
-        return terr(t, DBAZ_EDEVICE, "slot tables of %d slots: %s (%zu bytes): %s", n_slots, what[failed], bytes[failed], hipGetErrorString(e));
+        return fail(t->err, DBAZ_EDEVICE, "slot tables of %d slots: %s (%zu bytes): %s", n_slots, what[failed], bytes[failed], hipGetErrorString(e));
     }
     *st = SlotTables();
     st->rows = t->board.rows; st->cols = t->board.cols; st->max_free = t->max_free;

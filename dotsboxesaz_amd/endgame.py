@@ -229,34 +229,37 @@ def score_endgames(samples, rows=None, cols=None, endgame=None, max_free=MAX_FRE
 DEEP_FREE = 24  # dbaz_deep_create's default max_free: a table of 16 MiB
 
 
-class DeepEndgame:
-    """One solved table per position (dbaz_deep_*, DESIGN.md 4.7): solve(root_x) solves the subgame of a root position with at
-    most max_free <= 31 free edges into a table of 2^F bytes in HBM; score() and policy() then answer the root and every position
-    that follows it from that table.  A > 256 or max_free outside 1 .. 31 raises DbazError before the device is touched."""
+class _TableHandle:
+    """What DeepEndgame and DeepTables share: a handle of one family of C entries (_API + "_create", "_score", ...) on one board
+    and device, its error check, its end, and the rows in / outputs out of score()."""
 
-    def __init__(self, rows, cols, device=0, max_free=DEEP_FREE):
+    _API = None  # "dbaz_deep" or "dbaz_tables"
+
+    def _open(self, rows, cols, device, max_free, *more):
         self._L = _lib.load()
         self.rows, self.cols, self.device, self.max_free = int(rows), int(cols), int(device), int(max_free)
         self.H, self.W = self.rows + 1, self.cols + 1
         self.A, self.F = 2 * self.H * self.W, 3 * self.H * self.W
         self.h = C.c_void_p()
-        rc = self._L.dbaz_deep_create(self.rows, self.cols, self.device, self.max_free, C.byref(self.h))
+        rc = self._fn("create")(self.rows, self.cols, self.device, self.max_free, *more, C.byref(self.h))
         if rc != _lib.OK:
             self.h = None
             self._ck(rc)
         self.max_free = self.max_free or DEEP_FREE
         self.actions = edge_actions(self.rows, self.cols)
         self.n_edges = len(self.actions)
-        self.n_free, self.d0, self.solve_ms, self.table_bytes = -1, ILLEGAL, -1.0, 1 << self.max_free
+
+    def _fn(self, name):
+        return getattr(self._L, "%s_%s" % (self._API, name))
 
     def _ck(self, rc):
         if rc != _lib.OK:
-            msg = self._L.dbaz_deep_last_error(self.h)
+            msg = self._fn("last_error")(self.h)
             raise _lib.DbazError(rc, msg.decode() if msg else "error %d" % rc)
 
     def close(self):
         if getattr(self, "h", None):
-            self._L.dbaz_deep_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -264,6 +267,57 @@ class DeepEndgame:
             self.close()
         except Exception:
             pass
+
+    def _rows(self, x, table_of=None):
+        """(device, x is numpy, x int16 [n, 3*H*W] on the device, table_of int32 [n] there or None, n)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(x, torch.Tensor)
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
+        tt = None
+        if table_of is not None:
+            tt = torch.as_tensor(np.ascontiguousarray(table_of, dtype=np.int32) if not isinstance(table_of, torch.Tensor) else table_of)
+            tt = tt.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            if int(tt.shape[0]) != int(xt.shape[0]):
+                raise ValueError("table_of has %d entries, x has %d rows" % (tt.shape[0], xt.shape[0]))
+        return dev, as_numpy, xt, tt, int(xt.shape[0])
+
+    def _score(self, x, pi, table_of=None):
+        """score() of either class: the family's _score entry takes table_of after pi where there is one"""
+        import torch
+        dev, as_numpy, xt, tt, n = self._rows(x, table_of)
+        pt = None
+        if pi is not None:
+            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
+            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
+            if int(pt.shape[0]) != n:
+                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
+        value = torch.empty(n, dtype=torch.int8, device=dev)
+        diff = torch.empty(n, dtype=torch.int8, device=dev)
+        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
+        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
+        n_free = torch.empty(n, dtype=torch.int16, device=dev)
+        served = torch.empty(n, dtype=torch.uint8, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        args = [xt, pt] + ([tt] if table_of is not None else []) + [value, diff, q, mass, n_free, served]
+        with torch.cuda.device(dev):
+            self._ck(self._fn("score")(self.h, C.c_int32(n), *[ptr(t) for t in args], C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=served != 0)
+        if as_numpy:
+            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+        return out
+
+
+class DeepEndgame(_TableHandle):
+    """One solved table per position (dbaz_deep_*, DESIGN.md 4.7): solve(root_x) solves the subgame of a root position with at
+    most max_free <= 31 free edges into a table of 2^F bytes in HBM; score() and policy() then answer the root and every position
+    that follows it from that table.  A > 256 or max_free outside 1 .. 31 raises DbazError before the device is touched."""
+
+    _API = "dbaz_deep"
+
+    def __init__(self, rows, cols, device=0, max_free=DEEP_FREE):
+        self._open(rows, cols, device, max_free)
+        self.n_free, self.d0, self.solve_ms, self.table_bytes = -1, ILLEGAL, -1.0, 1 << self.max_free
 
     def _info(self):
         f, b, ms, d0 = C.c_int32(), C.c_int64(), C.c_double(), C.c_int32()
@@ -294,45 +348,17 @@ class DeepEndgame:
         self._ck(self._L.dbaz_deep_table(self.h, C.c_void_p(out.ctypes.data), C.c_int64(first), C.c_int64(count)))
         return out
 
-    def _rows(self, x):
-        import torch
-        dev = torch.device("cuda", self.device)
-        as_numpy = not isinstance(x, torch.Tensor)
-        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
-        return dev, as_numpy, xt, int(xt.shape[0])
-
     def score(self, x, pi=None):
         """Endgame.score's dict from the table, same conventions in and out; solved [n] = the row is served: its free edges are a
         subset of the root's.  A row that is not served gets value 0, diff -128, q all -128, policy_mass 0; n_free is the row's own
         count either way.  Before a successful solve(): DbazError (ESTATE)."""
-        import torch
-        dev, as_numpy, xt, n = self._rows(x)
-        pt = None
-        if pi is not None:
-            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
-            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
-            if int(pt.shape[0]) != n:
-                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
-        value = torch.empty(n, dtype=torch.int8, device=dev)
-        diff = torch.empty(n, dtype=torch.int8, device=dev)
-        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
-        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
-        n_free = torch.empty(n, dtype=torch.int16, device=dev)
-        served = torch.empty(n, dtype=torch.uint8, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
-        with torch.cuda.device(dev):
-            self._ck(self._L.dbaz_deep_score(self.h, C.c_int32(n), ptr(xt), ptr(pt), ptr(value), ptr(diff), ptr(q), ptr(mass), ptr(n_free),
-                                             ptr(served), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=served != 0)
-        if as_numpy:
-            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
-        return out
+        return self._score(x, pi)
 
     def policy(self, x, seed=0):
         """Endgame.policy's (p, v, solved) from the table: the same pick among equally good moves for the same seed; solved [n] =
         the row is served (p = 0, v = 0 where it is not)."""
         import torch
-        dev, as_numpy, xt, n = self._rows(x)
+        dev, as_numpy, xt, _, n = self._rows(x)
         p = torch.empty((n, self.A), dtype=torch.float32, device=dev)
         v = torch.empty(n, dtype=torch.float32, device=dev)
         served = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -347,44 +373,20 @@ class DeepEndgame:
 DEEP_TABLES = 64  # dbaz_tables_create's default n_tables: a pool of 1 GiB at max_free 24
 
 
-class DeepTables:
+class DeepTables(_TableHandle):
     """A pool of solved tables (dbaz_tables_*): solve(roots_x) solves up to n_tables root positions side by side,
     root i into table i; score() and targets() then answer rows of many games in one launch, row r from table table_of[r].
     A > 256, max_free outside 1 .. 31 or n_tables outside 1 .. 65535 raises DbazError before the device is touched."""
 
+    _API = "dbaz_tables"
     ATTACH = "dbaz_attach_tables"  # the entry Engine.attach_endgame calls with this handle
 
     def __init__(self, rows, cols, device=0, max_free=DEEP_FREE, n_tables=DEEP_TABLES):
-        self._L = _lib.load()
-        self.rows, self.cols, self.device, self.max_free, self.n_tables = int(rows), int(cols), int(device), int(max_free), int(n_tables)
-        self.H, self.W = self.rows + 1, self.cols + 1
-        self.A, self.F = 2 * self.H * self.W, 3 * self.H * self.W
-        self.h = C.c_void_p()
-        rc = self._L.dbaz_tables_create(self.rows, self.cols, self.device, self.max_free, self.n_tables, C.byref(self.h))
-        if rc != _lib.OK:
-            self.h = None
-            self._ck(rc)
-        self.max_free, self.n_tables = self.max_free or DEEP_FREE, self.n_tables or DEEP_TABLES
-        self.actions = edge_actions(self.rows, self.cols)
-        self.n_edges = len(self.actions)
+        self.n_tables = int(n_tables)
+        self._open(rows, cols, device, max_free, self.n_tables)
+        self.n_tables = self.n_tables or DEEP_TABLES
         self.n_solved, self.n_free, self.d0 = 0, np.zeros(0, np.int32), np.zeros(0, np.int32)
         self.solve_ms, self.table_bytes, self.pool_bytes = -1.0, 1 << self.max_free, self.n_tables << self.max_free
-
-    def _ck(self, rc):
-        if rc != _lib.OK:
-            msg = self._L.dbaz_tables_last_error(self.h)
-            raise _lib.DbazError(rc, msg.decode() if msg else "error %d" % rc)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.dbaz_tables_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _info(self):
         n, b, p, ms = C.c_int32(), C.c_int64(), C.c_int64(), C.c_double()
@@ -417,44 +419,12 @@ class DeepTables:
         self._ck(self._L.dbaz_tables_table(self.h, C.c_int32(int(i)), C.c_void_p(out.ctypes.data), C.c_int64(first), C.c_int64(count)))
         return out
 
-    def _rows(self, x, table_of):
-        import torch
-        dev = torch.device("cuda", self.device)
-        as_numpy = not isinstance(x, torch.Tensor)
-        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.int16) if as_numpy else x).to(device=dev, dtype=torch.int16).reshape(-1, self.F).contiguous()
-        tt = torch.as_tensor(np.ascontiguousarray(table_of, dtype=np.int32) if not isinstance(table_of, torch.Tensor) else table_of)
-        tt = tt.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        if int(tt.shape[0]) != int(xt.shape[0]):
-            raise ValueError("table_of has %d entries, x has %d rows" % (tt.shape[0], xt.shape[0]))
-        return dev, as_numpy, xt, tt, int(xt.shape[0])
-
     def score(self, x, table_of, pi=None):
         """DeepEndgame.score's dict for rows of many games: table_of int32 [n] names each row's table, the index of its root in
         the last solve().  solved [n] = the row is served: table_of is in 0 .. n_solved - 1 and the row's free edges are a subset
         of that root's.  Every other row gets the unsolved outputs; n_free is the row's own count either way.  Before a successful
         solve(): DbazError (ESTATE)."""
-        import torch
-        dev, as_numpy, xt, tt, n = self._rows(x, table_of)
-        pt = None
-        if pi is not None:
-            pt = torch.as_tensor(np.ascontiguousarray(pi, dtype=np.float32) if not isinstance(pi, torch.Tensor) else pi)
-            pt = pt.to(device=dev, dtype=torch.float32).reshape(-1, self.A).contiguous()
-            if int(pt.shape[0]) != n:
-                raise ValueError("pi has %d rows, x has %d" % (pt.shape[0], n))
-        value = torch.empty(n, dtype=torch.int8, device=dev)
-        diff = torch.empty(n, dtype=torch.int8, device=dev)
-        q = torch.empty((n, self.A), dtype=torch.int8, device=dev)
-        mass = torch.empty(n, dtype=torch.float32, device=dev) if pt is not None else None
-        n_free = torch.empty(n, dtype=torch.int16, device=dev)
-        served = torch.empty(n, dtype=torch.uint8, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
-        with torch.cuda.device(dev):
-            self._ck(self._L.dbaz_tables_score(self.h, C.c_int32(n), ptr(xt), ptr(pt), ptr(tt), ptr(value), ptr(diff), ptr(q), ptr(mass), ptr(n_free),
-                                               ptr(served), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        out = dict(value=value, diff=diff, q=q, policy_mass=mass, n_free=n_free, solved=served != 0)
-        if as_numpy:
-            out = {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
-        return out
+        return self._score(x, pi, table_of)
 
     def targets(self, x, table_of, pi, z, pi_mode="restrict", z_mode=True):
         """Endgame.targets from the tables (dbaz_tables_targets), for rows of any depth a table serves: x, pi, z, the modes and
@@ -488,19 +458,20 @@ class DeepTables:
 def _game_roots(game, move, n_free, max_free):
     """Game-ordered rows in any order -> (root [g]: per game that has one, the index of its first row by move_idx with at most
     max_free free edges; table_of [n]: per row the position of its game's root in `root` if the row is that root or comes after
-    it, else -1)."""
+    it, else -1; tails: per root the indices of those rows, the root first)."""
     n = len(game)
     order = np.lexsort((move, game))
     by_game = game[order]
     bounds = [0] + (np.nonzero(by_game[1:] != by_game[:-1])[0] + 1).tolist() + [n]  # where a new game starts
-    root, table_of = [], np.full(n, -1, np.int32)
+    root, table_of, tails = [], np.full(n, -1, np.int32), []
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         idx = order[lo:hi]
         late = np.nonzero(n_free[idx] <= max_free)[0]
         if len(late):
-            table_of[idx[late[0]:]] = len(root)
-            root.append(idx[late[0]])
-    return np.asarray(root, np.int64), table_of
+            tails.append(idx[late[0]:])
+            table_of[tails[-1]] = len(root)
+            root.append(tails[-1][0])
+    return np.asarray(root, np.int64), table_of, tails
 
 
 def _tables_handle(tables, x, rows, cols, max_free, device, what):
@@ -513,10 +484,10 @@ def _tables_handle(tables, x, rows, cols, max_free, device, what):
     return DeepTables(rows, cols, device, max_free, int(tables))
 
 
-def _score_game_tails_batched(samples, rows, cols, max_free, device, tables):
-    """score_game_tails' batched path: the games in chunks of n_tables, one solve and one score per chunk"""
+def _tail_rows(g, samples):
+    """score_game_tails' rows for the handle g: (x int16 [n, 3*H*W], pi float32 [n, A], r: the report's per-row arrays with every
+    row unsolved, then root, table_of and tails as _game_roots gives them)"""
     x = np.asarray(samples["x"])
-    g = _tables_handle(tables, x, rows, cols, max_free, device, "tables=DeepTables(rows, cols)")
     n = len(x)
     x = np.ascontiguousarray(x.reshape(n, g.F), dtype=np.int16)
     pi = np.ascontiguousarray(np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
@@ -525,7 +496,13 @@ def _score_game_tails_batched(samples, rows, cols, max_free, device, tables):
     n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
     r = dict(value=np.zeros(n, np.int8), q=np.full((n, g.A), ILLEGAL, np.int8), policy_mass=np.zeros(n, np.float32), n_free=n_free,
              solved=np.zeros(n, bool))
-    root, table_of = _game_roots(game, move, n_free, g.max_free)
+    return (x, pi, r) + _game_roots(game, move, n_free, g.max_free)
+
+
+def _score_game_tails_batched(samples, rows, cols, max_free, device, tables):
+    """score_game_tails' batched path: the games in chunks of n_tables, one solve and one score per chunk"""
+    g = _tables_handle(tables, np.asarray(samples["x"]), rows, cols, max_free, device, "tables=DeepTables(rows, cols)")
+    x, pi, r, root, table_of, _ = _tail_rows(g, samples)
     solve_ms = 0.0
     for lo in range(0, len(root), g.n_tables):
         hi = min(lo + g.n_tables, len(root))
@@ -556,7 +533,7 @@ def game_tail_targets(samples, rows=None, cols=None, max_free=DEEP_FREE, tables=
     move = np.asarray(samples["move_idx"]).astype(np.int64).reshape(n)
     n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
     info = dict(n_free=n_free, mass=np.zeros(n, np.float32), relabelled=np.zeros(n, bool))
-    root, table_of = _game_roots(game, move, n_free, g.max_free)
+    root, table_of, _ = _game_roots(game, move, n_free, g.max_free)
     for lo in range(0, len(root), g.n_tables):
         hi = min(lo + g.n_tables, len(root))
         idx = np.nonzero((table_of >= lo) & (table_of < hi))[0]
@@ -585,28 +562,15 @@ def score_game_tails(samples, rows=None, cols=None, max_free=DEEP_FREE, device=0
                 raise ValueError("flat feature rows do not tell the board size: pass rows= and cols=, or deep=DeepEndgame(rows, cols)")
             rows, cols = x.shape[2] - 1, x.shape[3] - 1
         deep = DeepEndgame(rows, cols, device, max_free)
-    g, n = deep, len(x)
-    x = np.ascontiguousarray(x.reshape(n, g.F), dtype=np.int16)
-    pi = np.ascontiguousarray(np.asarray(samples["pi"], dtype=np.float32).reshape(n, g.A))
-    game = np.asarray(samples["game_idx"]).astype(np.int64).reshape(n)
-    n_free = (x[:, g.actions] == 0).sum(axis=1).astype(np.int16)
-    r = dict(value=np.zeros(n, np.int8), q=np.full((n, g.A), ILLEGAL, np.int8), policy_mass=np.zeros(n, np.float32), n_free=n_free,
-             solved=np.zeros(n, bool))
-    order = np.lexsort((np.asarray(samples["move_idx"]).astype(np.int64).reshape(n), game))
-    tables, solve_ms = 0, 0.0
-    by_game = game[order]
-    bounds = [0] + (np.nonzero(by_game[1:] != by_game[:-1])[0] + 1).tolist() + [n]  # where a new game starts
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
-        idx = order[lo:hi]
-        late = np.nonzero(n_free[idx] <= g.max_free)[0]
-        if not len(late):
-            continue
-        idx = idx[late[0]:]
+    g = deep
+    x, pi, r, _, _, tails = _tail_rows(g, samples)
+    solve_ms = 0.0
+    for idx in tails:
         got = g.solve(x[idx[0]]).score(x[idx], pi[idx])
-        tables, solve_ms = tables + 1, solve_ms + g.solve_ms
+        solve_ms += g.solve_ms
         for k in ("value", "q", "policy_mass", "solved"):
             r[k][idx] = got[k]
-    return dict(_row_report(g, x, samples, r), tables=tables, solve_ms=solve_ms)
+    return dict(_row_report(g, x, samples, r), tables=len(tails), solve_ms=solve_ms)
 
 
 def random_rows(rows, cols, n, free, seed=0):

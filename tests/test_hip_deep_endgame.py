@@ -289,6 +289,29 @@ def test_served_rule():
     d.close()
 
 
+def test_a_reused_handle_keeps_nothing_of_the_table_before():
+    """One handle, three roots of three games: F = 12, then F = 3 (8 bytes at the head of the same 4 096-byte region), then F = 12
+    again.  After each solve the table is the new root's, byte for byte, d0 is its first entry, and of the three roots exactly
+    those whose free edges are a subset of the current root's are served."""
+    R, C = 6, 6
+    acts, _ = ER.board(R, C)
+    roots = np.stack([root_of(R, C, 0, 12), root_of(R, C, 1, 3), root_of(R, C, 2, 12)])
+    free = roots[:, acts] == 0
+    d = DeepEndgame(R, C, max_free=12)
+    for i, root in enumerate(roots):
+        want = ref_table(R, C, root)
+        got = d.solve(root).table()
+        assert got.shape == (1 << int(free[i].sum()),) and np.array_equal(got, want), i
+        assert d.n_free == free[i].sum() and d.d0 == int(want[0]) and d.table_bytes == 4096
+        inside = ~(free & ~free[i]).any(axis=1)  # per root: no free edge that the current root has drawn
+        assert inside[i] and not inside.all()
+        scored = d.score(roots)
+        assert scored["solved"].tolist() == inside.tolist(), i
+        check_unsolved(scored, np.nonzero(~inside)[0])
+        assert scored["diff"][i] == want[0]
+    d.close()
+
+
 def test_a_row_laid_out_for_another_board_is_not_served():
     """The same position on the wrong handle size: 2x7 and 3x5 rows both have 72 values.  A 2x7 position with 20 free edges, read
     as a 3x5 row, still has more free real edges than the 3x5 root has at all: not served, next to a served 3x5 row."""

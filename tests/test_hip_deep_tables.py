@@ -1,6 +1,6 @@
 """Deep endgames in batches on the GPU (dbaz_tables_* in csrc/solver.hip, DeepTables / score_game_tails(tables=) /
-game_tail_targets in dotsboxesaz_amd/endgame.py): every table of a batch against the single-table handle byte for byte, every
-work split against the numpy recurrence, rows of many games in one launch against DeepEndgame.score bit for bit, the served rule
+game_tail_targets in dotsboxesaz_amd/endgame.py): every table of a batch against the single-table handle and both against the
+numpy recurrence byte for byte, every work split against the numpy recurrence, rows of many games in one launch against DeepEndgame.score bit for bit, the served rule
 by table index, the targets against Endgame.targets (F <= 16) and targets_ref.py (F = 17 .. 20), and the two game-level
 functions against the game-by-game path.  Pools of at most 16 tables of 1 MiB."""
 import numpy as np
@@ -35,9 +35,8 @@ def test_tables_equal_the_single_table_handle(R, C):
     d = DeepEndgame(R, C, max_free=ROOT_FREE)
     want = [(d.solve(r).table(), d.n_free, d.d0) for r in roots]
     assert [w[1] for w in want] == DEPTHS
-    for i, f in enumerate(DEPTHS):
-        if f <= 16:
-            assert np.array_equal(want[i][0], ref_table(R, C, roots[i])), f
+    for i, f in enumerate(DEPTHS):  # both handle kinds run the same code: every table against the numpy recurrence
+        assert np.array_equal(want[i][0], ref_table(R, C, roots[i])), f
     t = DeepTables(R, C, max_free=ROOT_FREE, n_tables=len(DEPTHS))
     assert t.pool_bytes == len(DEPTHS) << 20 and t.n_solved == 0
     for order in (np.arange(len(DEPTHS)), np.random.RandomState(R + C).permutation(len(DEPTHS))):
