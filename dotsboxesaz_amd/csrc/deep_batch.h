@@ -5,9 +5,9 @@
 // offset i << max_free), so the table index a caller passes later is its root index.  Roots of equal F share their launches:
 // a GROUP is the roots of one F in ascending root index, the groups are ordered deepest first, and a launch of a group has
 // grid.y = the group's size.  Per group
-//   plain   F < DEEP_BATCH_MIN_LOW or low_bits == -1: k_solver_layer_batch, F + 1 launches (popcount layers F .. 0 of all bits),
+//   plain   F < DEEP_BATCH_MIN_LOW or low_bits == -1: k_solver_layer, F + 1 launches (popcount layers F .. 0 of all bits),
 //           grid.x = ceil(2^F / DEEP_BATCH_LAYER_THREADS)
-//   else    k_solver_subcube_batch with L = default_low_bits(F) or the given low_bits: one launch per popcount layer
+//   else    k_solver_subcube with L = default_low_bits(F) or the given low_bits: one launch per popcount layer
 //           k = F - L .. 0 of the high bits, grid.x = C(F - L, k), the high patterns of that layer
 // low_bits has dbaz_deep_solve's meaning and applies to every root.
 #pragma once

@@ -50,6 +50,28 @@ struct EndgameSlotHdr {
 // what the search side asks (tree.hip): does the slot's table serve the leaves of a search of game `game`
 __host__ __device__ __forceinline__ bool endgame_hdr_serves(const EndgameSlotHdr &h, int64_t game) { return h.valid != 0 && h.game == game; }
 
+// What a pass does with a slot's request (k_endgame_table, k_slot_requests): a position the slot's table still serves -- the same
+// game, free edges a subset of the table's -- keeps the table; F > max_free drops it; anything else is solved.  free_edges: the
+// request's, masked with the board's real edges.
+struct SlotDecision {
+    int F;
+    bool keep, solve;
+};
+__host__ __device__ __forceinline__ SlotDecision slot_request_rule(const uint64_t (&free_edges)[4], int hdr_valid, int64_t hdr_game,
+                                                                   const uint64_t (&hdr_free)[4], int64_t game, int max_free)
+{
+    SlotDecision d;
+    d.F = 0;
+    bool subset = true;
+    for (int w = 0; w < 4; w++) {
+        subset = subset && (free_edges[w] & ~hdr_free[w]) == 0ull;
+        d.F += __builtin_popcountll(free_edges[w]);
+    }
+    d.keep = hdr_valid != 0 && hdr_game == game && subset;
+    d.solve = !d.keep && d.F <= max_free;
+    return d;
+}
+
 struct dbaz_endgame;
 // the engine's side, like solver_serves / solver_forward (solver.h)
 bool endgame_serves(const dbaz_endgame *g, int rows, int cols, int device, int *max_free);
@@ -57,17 +79,14 @@ size_t endgame_table_stride(const dbaz_endgame *g); // bytes of one slot's table
 // stats [2]: tables solved, leaves served (cumulative, device)
 void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
                     unsigned long long *stats);
-// nn_forward's contract on float feature planes: rows feat[list[j]], j < *n_dev <= max_n, of slot list[j] / per_slot, to
-// P[list[j] * AS + a] and V[list[j]]; seeds [2]: the pick seed of each model
-void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
-                     const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
-                     int AS, unsigned long long *stats);
-
-// The same evaluator over slot tables that a dbaz_tables attach solved (dbaz_attach_tables; the producer is solver.hip's
-// slot_tables_pass): k_endgame_eval with the board and max_free given here, slot regions of 2^max_free bytes.
-void endgame_forward_tables(int rows, int cols, int max_free, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
-                            const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
-                            float *V, int AS, unsigned long long *stats);
+// The slot tables as an evaluator, whoever solved them (k_endgame_table, or solver.hip's slot_tables_pass): k_endgame_eval with
+// nn_forward's contract on rows of T = float (TreeBufs.feat planes) or int16 -- rows x[list[j]], j < *n_dev <= max_n, of slot
+// list[j] / per_slot, to P[list[j] * AS + a] and V[list[j]]; seeds: the pick seed of each model.  No header claims more than
+// max_free compact edges; a slot's region is tab_stride >= 2^max_free bytes.
+template <typename T>
+void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables,
+                     const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
+                     float *V, int AS, unsigned long long *stats);
 
 // ---- exact training targets (dbaz_exact_targets, include/dbaz.h): rows x_stride shorts apart, relabelled in place, queued on
 // `stream`.  stats_host [4 + 17] (may be NULL) as dbaz_dataset_exact_targets documents it: asking for it waits for the stream.

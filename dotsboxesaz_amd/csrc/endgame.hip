@@ -14,14 +14,12 @@
 // k_endgame_table / k_endgame_eval: a search root's table kept per slot in HBM, and the leaves of that game answered from it.
 // k_endgame_candidates / k_endgame_list / k_endgame_targets: exact training targets (dbaz_exact_targets): the rows with
 //   F <= max_free listed deepest first, then steps 1 and 2 per listed row and the solved z and pi written in place.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "endgame.h"
+#include "table_row.h"
 
 // counters of one dbaz_exact_targets call (device): rows per F <= max_free, the append cursors of k_endgame_list, and the
 // statistics of the dataset form -- [0] finished rows left alone, [1] rows whose z differed from v, [2 + F] rows relabelled
@@ -45,28 +43,9 @@ struct dbaz_endgame {
 
 static thread_local std::string g_endgame_error; // message of a failed dbaz_endgame_create; per thread
 
-static int gerr(dbaz_endgame *g, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    (g ? g->err : g_endgame_error) = buf;
-    return code;
-}
-
-#define ENDGAME_HIP(g, call)                                                                                        \
-    do {                                                                                                            \
-        hipError_t _err = (call);                                                                                   \
-        if (_err != hipSuccess) return gerr(g, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
-
 // ------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------
-static __device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
-
 #define ENDGAME_TABLE_GRID 1024 // workgroups of k_endgame_table: four rounds of the chip at two per CU
 
 // static LDS of one workgroup, next to the dynamic int8 table [2^max_free]
@@ -268,9 +247,9 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_policy(EndgameGeo g
 
 // One game's table for the search (endgame.h): one workgroup per slot that needs a table.  The grid is at most
 // ENDGAME_TABLE_GRID workgroups, each looking at the slots blockIdx.x, + gridDim.x, ...: a slot without a request costs one word
-// read (a workgroup holds 64 KB of LDS, so one workgroup per idle slot would go through the chip in many rounds).  A request whose position the slot's table still serves -- same game, free edges a subset of
-// the table's -- keeps the table; one with F > max_free drops it; any other is solved, k_endgame_score's setup and solve, and goes
-// from LDS to the slot's region in 16-byte stores together with the header.
+// read (a workgroup holds 64 KB of LDS, so one workgroup per idle slot would go through the chip in many rounds).  A request is
+// kept, dropped or solved by slot_request_rule (endgame.h); a solved one is k_endgame_score's setup and solve, and goes from LDS
+// to the slot's region in 16-byte stores together with the header.
 __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_table(EndgameGeo g, EndgameReq *__restrict__ req, EndgameSlotHdr *__restrict__ hdr,
                                                                    int8_t *__restrict__ tables, size_t stride, int n_slots,
                                                                    unsigned long long *__restrict__ stats)
@@ -284,23 +263,18 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_table(EndgameGeo g,
     EndgameSlotHdr *h = hdr + slot;
     if (!*(volatile const int32_t *)&rq->want) continue; // the same answer in every thread: nobody has written yet
     MaskEdges me;
-    bool subset = true;
-    int F = 0;
-    for (int w = 0; w < 4; w++) {
-        me.free_edges[w] = rq->free_edges[w];
-        subset = subset && (me.free_edges[w] & ~h->free_edges[w]) == 0ull;
-        F += __popcll(me.free_edges[w]);
-    }
+    for (int w = 0; w < 4; w++) me.free_edges[w] = rq->free_edges[w];
     const int64_t game = rq->game;
     const int model = rq->model;
-    const bool keep = h->valid != 0 && h->game == game && subset;
+    const SlotDecision d = slot_request_rule(me.free_edges, h->valid, h->game, h->free_edges, game, g.max_free);
+    const int F = d.F;
     __syncthreads(); // every thread has read the request and the header
     if (tid == 0) {
         rq->want = 0;
         h->model = model;
-        if (!keep && F > g.max_free) h->valid = 0;
+        if (!d.keep && !d.solve) h->valid = 0;
     }
-    if (keep || F > g.max_free) continue;
+    if (!d.solve) continue;
 
     endgame_setup(g, me, L);
     endgame_solve(g, F, L, sd);
@@ -344,12 +318,13 @@ __global__ void k_endgame_requests(EndgameGeo g, const int16_t *__restrict__ x, 
 }
 
 // A slot's table as a (p, v) evaluator with k_solver_eval's contract: rows x[list[j]], j < min(*n_dev, max_n), of slot
-// list[j] / per_slot; T = float (TreeBufs.feat planes) or int16.  One wavefront per row, lane j = compact edge j of the slot's
-// table: the drawn ones ballot into the subgame mask, every free lane reads T[mask | 1 << j], endgame_pick names the move;
-// v = sign(margin + T[mask]).  A finished position gets p = 0 and v = get_result; a row of a slot without a valid table p = 0, v = 0.
+// list[j] / per_slot; T = float (TreeBufs.feat planes) or int16.  One wavefront per row, table_row (table_row.h) against the
+// slot's header and table, without the served check: the caller lists only rows the header serves.  endgame_pick names the
+// move; v = sign(margin + T[mask]).  A finished position gets p = 0 and v = get_result; a row of a slot without a valid table
+// p = 0, v = 0.
 #define ENDGAME_EVAL_WAVES 4
 template <typename T>
-__global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(EndgameGeo g, const EndgameSlotHdr *__restrict__ hdr,
+__global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(TablesBoard B, int max_free, const EndgameSlotHdr *__restrict__ hdr,
                                                                           const int8_t *__restrict__ tables, size_t tab_stride,
                                                                           const T *__restrict__ x, const int32_t *__restrict__ list,
                                                                           const int32_t *__restrict__ n_dev, int max_n, int per_slot,
@@ -359,42 +334,22 @@ __global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(Endgam
     const int lane = threadIdx.x & 63;
     const int n = n_dev ? min(*n_dev, max_n) : max_n;
     if (stats && blockIdx.x == 0 && threadIdx.x == 0 && n > 0) atomicAdd(stats + 1, (unsigned long long)n);
-    const int W = g.cols + 1, B = g.rows * g.cols;
     for (int j = blockIdx.x * ENDGAME_EVAL_WAVES + (threadIdx.x >> 6); j < n; j += gridDim.x * ENDGAME_EVAL_WAVES) {
         const int r = list ? list[j] : j;
         if ((unsigned)r >= (unsigned)max_n) continue; // never outside the caller's buffers
         const size_t slot = (size_t)(r / per_slot);
         const EndgameSlotHdr *h = hdr + slot;
-        const int F0 = min(h->F0, g.max_free);
-        const T *xr = x + (size_t)r * 3 * g.HW;
         float *pr = P + (size_t)r * stride;
         if (!h->valid) { // no table (the engine never lists such a leaf; dbaz_exact_policy_from: a root with F > max_free)
             for (int i = lane; i < stride; i += 64) pr[i] = 0.0f;
             if (lane == 0) V[r] = 0.0f;
             continue;
         }
-        const bool edge = lane < F0;
-        const int a = edge ? (int)h->act[lane] : 0;
-        const bool drawn = edge && xr[a] != (T)0;
-        const uint32_t m = (uint32_t)__ballot(drawn);
-        int closed = 0;
-        for (int b0 = 0; b0 < B; b0 += 64) {
-            const int b = b0 + lane;
-            bool c = false;
-            if (b < B) {
-                const int at = (b / g.cols) * W + b % g.cols;
-                c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[g.HW + at] != (T)0 && xr[g.HW + at + 1] != (T)0;
-            }
-            closed += __popcll(__ballot(c));
-        }
-        const RowFacts f = solver_facts(B, closed, (int)xr[2 * g.HW]);
-        const bool open = f.res == DBAZ_RESULT_NONE;
         const int8_t *Tb = tables + slot * tab_stride;
-        const bool cand = open && edge && !drawn;
-        const int q = cand ? solver_move_q(h->other[lane][0], h->other[lane][1], m, (int)Tb[m | (1u << lane)]) : 0;
-        const int pick = endgame_pick(cand, q, a, h->model ? seed1 : seed0);
+        const TableRow d = table_row<false>(B, *h, min(h->F0, max_free), Tb, x + (size_t)r * 3 * B.HW, lane);
+        const int pick = endgame_pick(d.cand, d.q, d.a, h->model ? seed1 : seed0);
         for (int i = lane; i < stride; i += 64) pr[i] = i == pick ? 1.0f : 0.0f;
-        if (lane == 0) V[r] = (float)(open ? sgn(f.margin + (int)Tb[m]) : f.res);
+        if (lane == 0) V[r] = (float)(d.open ? sgn(d.f.margin + (int)Tb[d.m]) : d.f.res);
     }
 }
 
@@ -455,8 +410,8 @@ __global__ void __launch_bounds__(256) k_endgame_list(int max_free, int n, const
 // One workgroup per listed row of the class f_lo .. g.max_free (the host passes the class's upper end as the geometry's max_free:
 // the dynamic table sd holds 2^max_free bytes): k_endgame_score's setup and solve, then the rule of include/dbaz.h in place.
 // The grid is fixed (the host does not know the counts); workgroup b takes the class's rows b, b + gridDim.x, ... of the
-// deepest-first list, so every workgroup gets the same mix of depths.  Wave 0, lane c = compact edge c: the result-preserving set as a ballot, and S in ascending action order
-// -- the float32 additions of k_endgame_score's policy_mass, in every lane.  The statistics are kept per workgroup in LDS.
+// deepest-first list, so every workgroup gets the same mix of depths.  Wave 0, lane c = compact edge c, finds the members and
+// S (row_members, table_row.h); the workgroup writes the row's pi (relabel_entry).  The statistics are kept per workgroup in LDS.
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) k_endgame_targets(EndgameGeo g, int f_lo, TargetCounters *__restrict__ cnt, const int32_t *__restrict__ list,
                                                              int n, const int16_t *__restrict__ x, int x_stride, int pi_mode, int z_mode,
@@ -465,8 +420,7 @@ __global__ void __launch_bounds__(THREADS) k_endgame_targets(EndgameGeo g, int f
 {
     extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [max(16, 2^g.max_free)]
     __shared__ EndgameLds L;
-    __shared__ uint32_t s_members;
-    __shared__ float s_sum;
+    __shared__ RowMembers s_members;
     __shared__ uint32_t s_stats[ENDGAME_MAX_FREE + 3];
 
     const int tid = threadIdx.x;
@@ -497,35 +451,21 @@ __global__ void __launch_bounds__(THREADS) k_endgame_targets(EndgameGeo g, int f
             if (tid < 64) {
                 const bool edge = tid < F;
                 const int qq = edge ? solver_move_q(L.other[tid][0], L.other[tid][1], 0u, (int)sd[1u << tid]) : 0;
-                const uint32_t members = (uint32_t)__ballot(edge && sgn(f.margin + qq) == v);
-                const float p = pr && edge ? pr[L.act[tid]] : 0.0f;
-                float sum = 0.0f;
-                for (int c = 0; c < F; c++) {
-                    const float pc = __shfl(p, c);
-                    if ((members >> c) & 1u) sum += pc;
-                }
-                if (tid == 0) {
-                    s_members = members;
-                    s_sum = sum;
-                }
+                const RowMembers M = row_members(edge, f.margin, qq, v, pr && edge ? pr[L.act[tid]] : 0.0f, F);
+                if (tid == 0) s_members = M;
             }
             __syncthreads();
-            const uint32_t members = s_members;
-            const float sum = s_sum;
-            if (pi_mode) {
-                const bool uniform = pi_mode == 1 || !(sum > 0.0f);
-                const float share = 1.0f / (float)__popc(members);
+            const RowMembers M = s_members;
+            if (pi_mode)
                 for (int a = tid; a < g.A; a += THREADS) {
                     const int c = L.cidx[a];
-                    const bool member = c >= 0 && ((members >> c) & 1u);
-                    pr[a] = member ? (uniform ? share : pr[a] / sum) : 0.0f;
+                    pr[a] = relabel_entry(M, pi_mode, c >= 0 && ((M.set >> c) & 1u), pr[a]);
                 }
-            }
             if (tid == 0) {
                 if (z && z[r] != (float)v) s_stats[1]++;
                 s_stats[2 + F]++;
                 if (z_mode) z[r] = (float)v;
-                if (mass) mass[r] = sum;
+                if (mass) mass[r] = M.sum;
                 if (relabelled) relabelled[r] = 1;
             }
         } else if (tid == 0) s_stats[0]++;
@@ -552,17 +492,17 @@ extern "C" void dbaz_endgame_destroy(dbaz_endgame *g)
 
 extern "C" int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, int32_t max_free, dbaz_endgame **out)
 {
-    if (!out) return gerr(nullptr, DBAZ_EINVAL, "null argument");
+    if (!out) return fail(g_endgame_error, DBAZ_EINVAL, "null argument");
     *out = nullptr;
-    if (rows < 1 || cols < 1) return gerr(nullptr, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
+    if (rows < 1 || cols < 1) return fail(g_endgame_error, DBAZ_EINVAL, "board %dx%d: rows and cols must be >= 1", rows, cols);
     const long long A = 2ll * (rows + 1ll) * (cols + 1ll);
-    if (A > DBAZ_MAX_A) return gerr(nullptr, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
+    if (A > DBAZ_MAX_A) return fail(g_endgame_error, DBAZ_EINVAL, "board %dx%d has %lld action slots: at most %d are supported", rows, cols, A, DBAZ_MAX_A);
     if (max_free < 0 || max_free > ENDGAME_MAX_FREE)
-        return gerr(nullptr, DBAZ_EINVAL, "max_free %d: a position's 2^F subgame table lives in LDS, 1 <= max_free <= %d (0 = %d)", max_free,
+        return fail(g_endgame_error, DBAZ_EINVAL, "max_free %d: a position's 2^F subgame table lives in LDS, 1 <= max_free <= %d (0 = %d)", max_free,
                     ENDGAME_MAX_FREE, ENDGAME_MAX_FREE);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return gerr(nullptr, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
+        return fail(g_endgame_error, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
 
     const int H = rows + 1, W = cols + 1, HW = H * W;
     std::vector<uint8_t> action;
@@ -618,7 +558,7 @@ extern "C" int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, i
         const std::string msg = hipGetErrorString(e);
         (void)hipGetLastError();
         dbaz_endgame_destroy(g);
-        return gerr(nullptr, DBAZ_EDEVICE, "endgame setup failed: %s", msg.c_str());
+        return fail(g_endgame_error, DBAZ_EDEVICE, "endgame setup failed: %s", msg.c_str());
     }
     g->g.rows = rows; g->g.cols = cols; g->g.HW = HW; g->g.A = 2 * HW; g->g.E = E;
     g->g.max_free = max_free == 0 ? ENDGAME_MAX_FREE : max_free;
@@ -635,12 +575,12 @@ extern "C" int dbaz_endgame_score(dbaz_endgame *g, int32_t n, const int16_t *x_d
 {
     if (!g) return DBAZ_EINVAL;
     if (n < 0 || (n > 0 && (!x_dev || !value_dev || !diff_dev || !q_dev || !n_free_dev)) || (pi_dev && !mass_dev))
-        return gerr(g, DBAZ_EINVAL, "dbaz_endgame_score: bad argument (n = %d)", n);
+        return fail(g->err, DBAZ_EINVAL, "dbaz_endgame_score: bad argument (n = %d)", n);
     if (n == 0) return DBAZ_OK;
-    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    CHECK_HIP(g->err, hipSetDevice(g->dev));
     k_endgame_score<<<(unsigned)n, ENDGAME_THREADS, (size_t)1 << g->g.max_free, (hipStream_t)stream>>>(g->g, x_dev, pi_dev, value_dev, diff_dev, q_dev,
                                                                                                       pi_dev ? mass_dev : nullptr, n_free_dev);
-    ENDGAME_HIP(g, hipGetLastError());
+    CHECK_HIP(g->err, hipGetLastError());
     return DBAZ_OK;
 }
 
@@ -648,12 +588,12 @@ extern "C" int dbaz_exact_policy(dbaz_endgame *g, int32_t n, const int16_t *x_de
                                  uint8_t *solved_dev, void *stream)
 {
     if (!g) return DBAZ_EINVAL;
-    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !solved_dev))) return gerr(g, DBAZ_EINVAL, "dbaz_exact_policy: bad argument (n = %d)", n);
+    if (n < 0 || (n > 0 && (!x_dev || !p_dev || !v_dev || !solved_dev))) return fail(g->err, DBAZ_EINVAL, "dbaz_exact_policy: bad argument (n = %d)", n);
     if (n == 0) return DBAZ_OK;
-    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    CHECK_HIP(g->err, hipSetDevice(g->dev));
     k_endgame_policy<<<(unsigned)n, ENDGAME_THREADS, (size_t)1 << g->g.max_free, (hipStream_t)stream>>>(g->g, x_dev, pick_seed, p_dev, v_dev,
                                                                                                        solved_dev);
-    ENDGAME_HIP(g, hipGetLastError());
+    CHECK_HIP(g->err, hipGetLastError());
     return DBAZ_OK;
 }
 
@@ -672,13 +612,13 @@ int endgame_targets(dbaz_endgame *g, hipStream_t s, int32_t n, const int16_t *x,
                     int16_t *n_free, float *mass, uint8_t *relabelled, int64_t *stats_host)
 {
     if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1)
-        return gerr(g, DBAZ_EINVAL, "exact targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode, z_mode);
+        return fail(g->err, DBAZ_EINVAL, "exact targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)", pi_mode, z_mode);
     if (n < 0 || (n > 0 && (!x || (pi_mode != 0 && !pi) || (z_mode != 0 && !z))))
-        return gerr(g, DBAZ_EINVAL, "exact targets: bad argument (n = %d; a mode other than keep needs its array)", n);
+        return fail(g->err, DBAZ_EINVAL, "exact targets: bad argument (n = %d; a mode other than keep needs its array)", n);
     if (stats_host) std::fill(stats_host, stats_host + 4 + ENDGAME_MAX_FREE + 1, (int64_t)0);
     if (n == 0) return DBAZ_OK;
-    ENDGAME_HIP(g, hipSetDevice(g->dev));
-    if (!g->tg_cnt) ENDGAME_HIP(g, hipMalloc((void **)&g->tg_cnt, sizeof(TargetCounters)));
+    CHECK_HIP(g->err, hipSetDevice(g->dev));
+    if (!g->tg_cnt) CHECK_HIP(g->err, hipMalloc((void **)&g->tg_cnt, sizeof(TargetCounters)));
     if ((size_t)n > g->tg_cap) { // hipFree waits for the kernels that still use the old scratch
         if (g->tg_list) (void)hipFree(g->tg_list);
         if (g->tg_nfree) (void)hipFree(g->tg_nfree);
@@ -686,12 +626,12 @@ int endgame_targets(dbaz_endgame *g, hipStream_t s, int32_t n, const int16_t *x,
         g->tg_nfree = nullptr;
         g->tg_cap = 0;
         const size_t cap = (size_t)n + (size_t)n / 2;
-        ENDGAME_HIP(g, hipMalloc((void **)&g->tg_list, cap * sizeof(int32_t)));
-        ENDGAME_HIP(g, hipMalloc((void **)&g->tg_nfree, cap * sizeof(int16_t)));
+        CHECK_HIP(g->err, hipMalloc((void **)&g->tg_list, cap * sizeof(int32_t)));
+        CHECK_HIP(g->err, hipMalloc((void **)&g->tg_nfree, cap * sizeof(int16_t)));
         g->tg_cap = cap;
     }
     int16_t *nf = n_free ? n_free : g->tg_nfree;
-    ENDGAME_HIP(g, hipMemsetAsync(g->tg_cnt, 0, sizeof(TargetCounters), s));
+    CHECK_HIP(g->err, hipMemsetAsync(g->tg_cnt, 0, sizeof(TargetCounters), s));
     const int cand_blocks = std::min((n + ENDGAME_CAND_WAVES - 1) / ENDGAME_CAND_WAVES, 16384);
     k_endgame_candidates<<<cand_blocks, 64 * ENDGAME_CAND_WAVES, 0, s>>>(g->g, x, x_stride, n, nf, mass, relabelled, g->tg_cnt);
     k_endgame_list<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->g.max_free, n, nf, g->tg_cnt, g->tg_list);
@@ -708,11 +648,11 @@ int endgame_targets(dbaz_endgame *g, hipStream_t s, int32_t n, const int16_t *x,
             k_endgame_targets<ENDGAME_THREADS><<<grid, ENDGAME_THREADS, lds, s>>>(gc, c.f_lo, g->tg_cnt, g->tg_list, n, x, x_stride, pi_mode, z_mode, pi,
                                                                                   z, mass, relabelled, stats_host != nullptr);
     }
-    ENDGAME_HIP(g, hipGetLastError());
+    CHECK_HIP(g->err, hipGetLastError());
     if (stats_host) {
         unsigned long long st[ENDGAME_MAX_FREE + 3];
-        ENDGAME_HIP(g, hipMemcpyAsync(st, g->tg_cnt->stats, sizeof st, hipMemcpyDeviceToHost, s));
-        ENDGAME_HIP(g, hipStreamSynchronize(s));
+        CHECK_HIP(g->err, hipMemcpyAsync(st, g->tg_cnt->stats, sizeof st, hipMemcpyDeviceToHost, s));
+        CHECK_HIP(g->err, hipStreamSynchronize(s));
         stats_host[0] = n;
         stats_host[2] = (int64_t)st[0];
         stats_host[3] = (int64_t)st[1];
@@ -748,26 +688,17 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
                                                                                                     stats);
 }
 
-void endgame_forward(const dbaz_endgame *g, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
-                     const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P, float *V,
-                     int AS, unsigned long long *stats)
+template <typename T>
+void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables,
+                     const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
+                     float *V, int AS, unsigned long long *stats)
 {
     const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
-    k_endgame_eval<float><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(g->g, hdr, tables, endgame_table_stride(g), feat, list_dev, n_dev, max_n,
-                                                                        per_slot, seed0, seed1, P, V, AS, stats);
+    k_endgame_eval<T><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(tables_board(rows, cols), max_free, hdr, tables, tab_stride, x, list_dev, n_dev,
+                                                                    max_n, per_slot, seed0, seed1, P, V, AS, stats);
 }
-
-void endgame_forward_tables(int rows, int cols, int max_free, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables, const float *feat,
-                            const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
-                            float *V, int AS, unsigned long long *stats)
-{
-    EndgameGeo g = EndgameGeo(); // k_endgame_eval reads the board and max_free only: no per-edge table
-    g.rows = rows; g.cols = cols; g.HW = (rows + 1) * (cols + 1); g.A = 2 * g.HW; g.E = 2 * rows * cols + rows + cols;
-    g.max_free = max_free;
-    const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
-    k_endgame_eval<float><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(g, hdr, tables, (size_t)1 << max_free, feat, list_dev, n_dev, max_n, per_slot,
-                                                                        seed0, seed1, P, V, AS, stats);
-}
+template void endgame_forward<float>(int, int, int, size_t, hipStream_t, const EndgameSlotHdr *, const int8_t *, const float *, const int32_t *,
+                                     const int32_t *, int, int, uint64_t, uint64_t, float *, float *, int, unsigned long long *); // the engine's
 
 // The table path on its own: the yardstick of k_endgame_table / k_endgame_eval against dbaz_exact_policy, the int16 form of the
 // evaluator, and the place where the two kernels are timed.
@@ -776,10 +707,10 @@ extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const in
 {
     if (!g) return DBAZ_EINVAL;
     if (n_roots < 0 || per_root < 1 || (long long)n_roots * per_root > 0x7fffffffll || (n_roots > 0 && (!roots_dev || !x_dev || !p_dev || !v_dev)))
-        return gerr(g, DBAZ_EINVAL, "dbaz_exact_policy_from: bad argument (n_roots = %d, per_root = %d)", n_roots, per_root);
+        return fail(g->err, DBAZ_EINVAL, "dbaz_exact_policy_from: bad argument (n_roots = %d, per_root = %d)", n_roots, per_root);
     if (ms_out) ms_out[0] = ms_out[1] = 0.0f;
     if (n_roots == 0) return DBAZ_OK;
-    ENDGAME_HIP(g, hipSetDevice(g->dev));
+    CHECK_HIP(g->err, hipSetDevice(g->dev));
     hipStream_t s = (hipStream_t)stream;
     const size_t stride = endgame_table_stride(g), n = (size_t)n_roots;
     void *buf[4] = {nullptr, nullptr, nullptr, nullptr}; // tables, headers, requests, stats
@@ -801,11 +732,8 @@ extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const in
         e = hipEventRecord(ev[1], s);
     }
     if (e == hipSuccess) {
-        const int max_n = n_roots * per_root;
-        const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
-        k_endgame_eval<int16_t><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, s>>>(g->g, (const EndgameSlotHdr *)buf[1], (const int8_t *)buf[0], stride, x_dev,
-                                                                         nullptr, nullptr, max_n, per_root, pick_seed, pick_seed, p_dev, v_dev,
-                                                                         g->g.A, nullptr);
+        endgame_forward<int16_t>(g->g.rows, g->g.cols, g->g.max_free, stride, s, (const EndgameSlotHdr *)buf[1], (const int8_t *)buf[0], x_dev, nullptr,
+                                 nullptr, n_roots * per_root, per_root, pick_seed, pick_seed, p_dev, v_dev, g->g.A, nullptr);
         e = hipEventRecord(ev[2], s);
     }
     if (e == hipSuccess) e = hipGetLastError();
@@ -820,7 +748,7 @@ extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const in
         if (b) (void)hipFree(b);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return gerr(g, DBAZ_EDEVICE, "dbaz_exact_policy_from (%d roots x %zu bytes): %s", n_roots, stride, hipGetErrorString(e));
+        return fail(g->err, DBAZ_EDEVICE, "dbaz_exact_policy_from (%d roots x %zu bytes): %s", n_roots, stride, hipGetErrorString(e));
     }
     return DBAZ_OK;
 }

@@ -43,6 +43,7 @@ struct dbaz_engine {
     ReadCaps read_caps = {{0, 0}, {0, 0}};
     EndgameStart eg_start = {nullptr, {0, 0}};
     size_t eg_stride = 0; // bytes per slot of eg_tables as allocated: every attached handle must have this stride
+    int eg_max_free = 0;  // the largest max_free attached so far: no header claims more compact edges, and 2^eg_max_free <= eg_stride
     EndgameBufs G = {nullptr, nullptr, nullptr, {0, 0}};
     // dbaz_attach_endgame: the borrowed endgame solver of each model, its pick seed; one table region and header per slot
     const dbaz_endgame *endgame[2] = {nullptr, nullptr};
@@ -112,8 +113,6 @@ static int set_error(dbaz_engine *e, int code, const char *fmt, ...)
     } while (0)
 
 static int endgame_drop_tables(dbaz_engine *e);
-static bool endgame_alloc_slots(dbaz_engine *e, size_t stride, void *p[6], hipError_t *err);
-static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6]);
 
 extern "C" const char *dbaz_last_error(const dbaz_engine *e) { return e ? e->err.c_str() : g_create_error.c_str(); }
 extern "C" int dbaz_version(void) { return DBAZ_ABI_VERSION; }
@@ -653,15 +652,9 @@ static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
 // the leaves k_select / k_select_multi put on eg_list, where solver_forward serves its lists
 static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
 {
-    if (e->eg_deep) {
-        endgame_forward_tables(e->g.rows, e->g.cols, e->slot_tables.max_free, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3,
+    if (e->eg_tables)
+        endgame_forward<float>(e->g.rows, e->g.cols, e->eg_max_free, e->eg_stride, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3,
                                e->n_slots * per_slot, per_slot, e->endgame_seed[0], e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
-        return;
-    }
-    const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
-    if (g)
-        endgame_forward(g, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3, e->n_slots * per_slot, per_slot, e->endgame_seed[0],
-                        e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
 }
 
 // new positions or a new run: no table of an earlier game may serve them
@@ -865,52 +858,6 @@ extern "C" int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s,
     return DBAZ_OK;
 }
 
-extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t pick_seed, int32_t endgame_reads)
-{
-    if (!e) return DBAZ_EINVAL;
-    USE_DEVICE(e);
-    if (!g) return set_error(e, DBAZ_EINVAL, "null endgame solver");
-    if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
-    const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
-    if (ev == DBAZ_EVAL_EXTERNAL || ev == DBAZ_EVAL_SOLVER || (model == 1 && !e->sc.match_play))
-        return set_error(e, DBAZ_EINVAL, "model %d: an endgame solver attaches to a network or formula evaluator the engine runs itself", model);
-    if (endgame_reads < 0) return set_error(e, DBAZ_EINVAL, "endgame_reads must be >= 0");
-    int max_free = 0;
-    if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
-        return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
-                         e->g.cols, e->cfg.device);
-    if (e->eg_deep)
-        return set_error(e, DBAZ_EINVAL, "this handle's slot tables belong to a dbaz_tables (dbaz_attach_tables, max_free %d): a handle's attaches are "
-                         "all of one kind", e->slot_tables.max_free);
-    // the slot regions are sized by the first attach and never resized: any later handle, for either model, must fit them exactly
-    if (e->eg_tables && endgame_table_stride(g) != e->eg_stride)
-        return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold %zu bytes each (the max_free of its first dbaz_attach_endgame); "
-                         "every later attach, for either model, needs the same max_free", max_free, e->eg_stride);
-    if (e->eg_tables) {
-        // a re-attach: tables solved under the handle it replaces do not serve on (headers and requests are dropped); a search
-        // that is running goes on with its model's evaluator until its next root
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
-        if (int r = endgame_drop_tables(e)) return r;
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-    }
-    if (!e->eg_tables) {
-        // the slot tables: n_slots x 2^max_free bytes, plus headers, requests and the leaf list; nothing is kept when one fails
-        const size_t ns = e->n_slots, stride = endgame_table_stride(g);
-        void *p[6];
-        hipError_t err = hipSuccess;
-        if (!endgame_alloc_slots(e, stride, p, &err))
-            return set_error(e, DBAZ_EDEVICE, "endgame tables of %zu slots x %zu bytes: %s", ns, stride, hipGetErrorString(err));
-        endgame_keep_slots(e, stride, p);
-    }
-    e->endgame[model] = g;
-    e->endgame_seed[model] = pick_seed;
-    e->G.model[model] = 1;
-    e->read_caps.eg_cap[model] = endgame_reads;
-    e->eg_start.max_free[model] = max_free;
-    return DBAZ_OK;
-}
-
 // the slot tables of either kind of attach: n_slots x stride bytes, plus headers, requests, the leaf list and the counters; nothing
 // is kept when one allocation fails (*err)
 static bool endgame_alloc_slots(dbaz_engine *e, size_t stride, void *p[6], hipError_t *err)
@@ -944,53 +891,83 @@ static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
     e->eg_stats = (unsigned long long *)p[5];
 }
 
-extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads)
+// What both attach entries do once their handle is resolved: `kind` names the handle's type and entry in messages, stride is the
+// bytes of a slot's region (at least 2^max_free), deep the dbaz_tables whose passes solve the slots (nullptr: a dbaz_endgame's
+// k_endgame_table does).  A handle's attaches are all of one kind and one stride: the slot regions are sized by the first attach
+// and never resized.  A refused attach changes nothing.
+static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, dbaz_tables *deep, int max_free, size_t stride, uint64_t pick_seed,
+                              int32_t endgame_reads)
 {
-    if (!e) return DBAZ_EINVAL;
-    USE_DEVICE(e);
-    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
     if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
     const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
     if (ev == DBAZ_EVAL_EXTERNAL || ev == DBAZ_EVAL_SOLVER || (model == 1 && !e->sc.match_play))
-        return set_error(e, DBAZ_EINVAL, "model %d: deep tables attach to a network or formula evaluator the engine runs itself", model);
+        return set_error(e, DBAZ_EINVAL, "model %d: a %s attaches to a network or formula evaluator the engine runs itself", model, kind);
     if (endgame_reads < 0) return set_error(e, DBAZ_EINVAL, "endgame_reads must be >= 0");
-    int max_free = 0;
-    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
-        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
-                         e->cfg.device);
-    if (e->eg_tables && !e->eg_deep)
-        return set_error(e, DBAZ_EINVAL, "this handle's slot tables belong to a dbaz_endgame (dbaz_attach_endgame): a handle's attaches are all of one "
-                         "kind");
-    if (e->eg_deep && max_free != e->slot_tables.max_free)
-        return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold 2^%d bytes each (the max_free of its first dbaz_attach_tables); "
-                         "every later attach, for either model, needs the same max_free", max_free, e->slot_tables.max_free);
-    if (e->eg_deep) {
-        // a re-attach: as in dbaz_attach_endgame, the tables solved so far do not serve on
+    if (e->eg_tables && (deep != nullptr) != e->eg_deep)
+        return set_error(e, DBAZ_EINVAL, "a %s: this handle's slot tables belong to a %s (max_free %d): a handle's attaches are all of one kind", kind,
+                         e->eg_deep ? "dbaz_tables" : "dbaz_endgame", e->eg_max_free);
+    if (e->eg_tables && stride != e->eg_stride)
+        return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold %zu bytes each (the max_free of its first attach); every later "
+                         "attach, for either model, needs the same max_free", max_free, e->eg_stride);
+    if (e->eg_tables) {
+        // a re-attach: tables solved under the handle it replaces do not serve on (headers and requests are dropped); a search
+        // that is running goes on with its model's evaluator until its next root
         HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
         if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
         if (int r = endgame_drop_tables(e)) return r;
         HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
     } else {
-        const unsigned long long total = (unsigned long long)e->n_slots << max_free; // 64 bits: 8192 slots x 2^20 is past 32
-        SlotTables st;
+        SlotTables st = SlotTables();
         void *lists[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (int rc = slot_tables_setup(t, e->n_slots, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(t));
+        if (deep)
+            if (int rc = slot_tables_setup(deep, e->n_slots, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
         void *p[6];
         hipError_t err = hipSuccess;
-        if (!endgame_alloc_slots(e, (size_t)1 << max_free, p, &err)) {
-            for (void *q : lists) (void)hipFree(q);
-            return set_error(e, DBAZ_EDEVICE, "slot tables of %d slots x 2^%d bytes = %llu bytes: %s", e->n_slots, max_free, total, hipGetErrorString(err));
+        if (!endgame_alloc_slots(e, stride, p, &err)) {
+            for (void *q : lists)
+                if (q) (void)hipFree(q);
+            return set_error(e, DBAZ_EDEVICE, "slot tables of %d slots x %zu bytes = %llu bytes: %s", e->n_slots, stride,
+                             (unsigned long long)e->n_slots * stride, hipGetErrorString(err)); // 64 bits: 8192 slots x 2^20 is past 32
         }
-        endgame_keep_slots(e, (size_t)1 << max_free, p);
-        for (void *q : lists) e->allocs.push_back(q);
+        endgame_keep_slots(e, stride, p);
+        for (void *q : lists)
+            if (q) e->allocs.push_back(q);
         e->slot_tables = st;
-        e->eg_deep = true;
+        e->eg_deep = deep != nullptr;
     }
+    e->eg_max_free = std::max(e->eg_max_free, max_free);
     e->endgame_seed[model] = pick_seed;
     e->G.model[model] = 1;
     e->read_caps.eg_cap[model] = endgame_reads;
     e->eg_start.max_free[model] = max_free;
     return DBAZ_OK;
+}
+
+extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *g, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!g) return set_error(e, DBAZ_EINVAL, "null endgame solver");
+    int max_free = 0;
+    if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
+                         e->g.cols, e->cfg.device);
+    if (int r = attach_slot_tables(e, model, "dbaz_endgame", nullptr, max_free, endgame_table_stride(g), pick_seed, endgame_reads)) return r;
+    e->endgame[model] = g;
+    return DBAZ_OK;
+}
+
+// Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own (slot_tables_setup).
+extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
+    int max_free = 0;
+    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
+                         e->cfg.device);
+    return attach_slot_tables(e, model, "dbaz_tables", t, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
 }
 
 extern "C" int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid, int32_t *n_free, int64_t *game, uint64_t free_edges[4],

@@ -3,8 +3,11 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdint.h>
+#include <stdio.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/dbaz.h"
@@ -88,6 +91,25 @@ static __device__ __forceinline__ int endgame_pick(bool cand, int q, int action,
     return __shfl(action, __ffsll((long long)opt) - 1);
 }
 
+// How solver.hip and endgame.hip report a failure: the message goes to `err` -- the handle's, or the family's per-thread slot for
+// a failed create (no handle to keep it in) -- and the code comes back.
+static inline int fail(std::string &err, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    err = buf;
+    return code;
+}
+
+#define CHECK_HIP(err, call)                                                                                        \
+    do {                                                                                                            \
+        hipError_t _err = (call);                                                                                   \
+        if (_err != hipSuccess) return fail(err, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
+    } while (0)
+
 // masks of `bits` bits in ascending popcount order; off[k] .. off[k + 1] holds popcount k
 static inline void popcount_order(int bits, std::vector<uint32_t> &perm, std::vector<uint32_t> &off)
 {
@@ -129,7 +151,7 @@ bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *ma
 // Uploads what the passes need for every F <= max_free and fills *st; the four device buffers it allocated come back in
 // allocs[4] (the caller frees them).  DBAZ_OK, or an error code with the message in dbaz_tables_last_error(t) and nothing kept.
 int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[4]);
-// One pass on `stream`: every slot with a request keeps, drops or re-solves its table (k_endgame_table's rule); S + 1 launches,
+// One pass on `stream`: every slot with a request keeps, drops or re-solves its table (slot_request_rule, endgame.h); S + 1 launches,
 // nothing read back.  stats [2] as for endgame_tables.
 void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
                       unsigned long long *stats);

@@ -24,8 +24,6 @@
 // table on the same path, plus the table as an evaluator (k_deep_policy).  At the end, the same bodies inside the search
 // (dbaz_attach_tables): one table per engine slot, solved from requests that exist only on the device (k_slot_requests,
 // k_slot_solve; slot_tables_plan.h).
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -37,6 +35,7 @@
 #include "position_geo.h"
 #include "slot_tables_plan.h"
 #include "solver.h"
+#include "table_row.h"
 
 // One root's solve geometry as the two solving kernels read it from HBM: what the bodies need of a SolverGeo, and the table slot
 // the root owns.  A whole board (dbaz_solver) is one entry with F = E and slot 0.
@@ -69,25 +68,8 @@ struct dbaz_solver {
     std::string err;
 };
 
-// Where a failure's message goes: the handle's `err`, or the family's slot for a failed create (no handle to keep it in); per thread.
+// the message of a failed create, per family and thread (fail, solver.h)
 static thread_local std::string g_solver_error, g_deep_error, g_tables_error;
-
-static int fail(std::string &err, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
-
-#define CHECK_HIP(err, call)                                                                                        \
-    do {                                                                                                            \
-        hipError_t _err = (call);                                                                                   \
-        if (_err != hipSuccess) return fail(err, DBAZ_EDEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
 
 // ------------------------------------------------------------------------------------
 // kernels
@@ -176,8 +158,6 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_solver_subcube(const BatchGe
     const BatchGeo &g = geo[blockIdx.y];
     solver_subcube_body(g.other, g.F, T + ((size_t)g.slot << stride_bits), L, hi_list[blockIdx.x], low_perm, low_off);
 }
-
-__device__ __forceinline__ int sgn(int v) { return (v > 0) - (v < 0); }
 
 // solver_facts (solver.h) of a position given as a mask: the closed boxes come from the box masks.  Shared by k_solver_score and
 // k_solver_eval.
@@ -517,9 +497,8 @@ void solver_forward(const dbaz_solver *s, hipStream_t stream, const float *feat,
 // table_of[r]; an index outside [0, n_solved) is "not served", decided before any address is formed from it.  dbaz_deep is a pool
 // of ONE table: the same functions with n = 1, every row answered from table 0 (table_of == nullptr), plus k_deep_policy.
 //
-// A row is SERVED when its free real edges are a subset of its root's.  One wavefront per row, lane j = compact edge j of the
-// root (F0 <= 31 < 64): the drawn ones ballot into `mask`, a free lane reads T[mask | 1 << j] and forms Q with solver_move_q;
-// margin and the finished-game test are solver_facts on the boxes counted from planes 0 / 1, as in endgame.hip.
+// A row is SERVED when its free real edges are a subset of its root's.  One wavefront per row reads it against the root and
+// the table: table_row (table_row.h), with the served check.
 static_assert(POSITION_NO_BOX == SOLVER_NO_BOX && POSITION_MAX_FREE == SOLVER_MAX_E, "position_geo.h restates solver.h");
 static_assert(DEEP_BATCH_MAX_FREE == SOLVER_MAX_E && DEEP_BATCH_MIN_LOW == SOLVER_MIN_LOW && DEEP_BATCH_MAX_LOW == SOLVER_MAX_LOW &&
                   DEEP_BATCH_MAX_HIGH == SOLVER_MAX_HIGH && DEEP_BATCH_LAYER_THREADS == 256,
@@ -529,12 +508,8 @@ static_assert(DEEP_BATCH_MAX_FREE == SOLVER_MAX_E && DEEP_BATCH_MIN_LOW == SOLVE
 #define DEEP_WAVES 4
 #define TABLES_DEFAULT 64    // tables of a pool: 1 GiB at the default max_free
 
-struct TablesBoard {
-    int32_t rows, cols, HW, A;
-};
-
-// A table's root, read from HBM by the wavefronts that answer its rows.  The board is not restated here: every kernel that reads
-// a root has the pool's TablesBoard in its arguments, so a row's loads do not wait for the root's.
+// A table's root, read from HBM by the wavefronts that answer its rows (table_row.h).  The board is not restated here: every
+// kernel that reads a root has the pool's TablesBoard in its arguments.
 struct DeepRoot {
     int32_t F;
     uint64_t free_edges[4];               // the root's free real edges by action index
@@ -565,104 +540,27 @@ struct dbaz_tables {
 // A pool of one table.  Everything dbaz_deep_info reports is the pool's: no root solved means no table.
 struct dbaz_deep : dbaz_tables {};
 
-// action slot a is a real edge of the board (the sentinels are board[0,:,W-1] and board[1,H-1,:])
-static __device__ __forceinline__ bool board_real_edge(const TablesBoard &B, int a)
-{
-    const int W = B.cols + 1;
-    const int p = a / B.HW, l = (a % B.HW) / W, c = a % W;
-    return a < B.A && (p == 0 ? c < B.cols : l < B.rows);
-}
-
-// The free real edges of a row by action index, one ballot per 64 action slots (lane l looks at slots l, 64 + l, ...); returns
-// their number.
-template <typename T>
-static __device__ __forceinline__ int row_free_edges(const TablesBoard &B, const T *__restrict__ xr, int lane, uint64_t (&free_edges)[4])
-{
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
-        const int a = w * 64 + lane;
-        free_edges[w] = __ballot(board_real_edge(B, a) && xr[a] == (T)0);
-        n += __popcll(free_edges[w]);
-    }
-    return n;
-}
-
-// What one wavefront finds out about its row, the same in every lane unless noted.
-struct DeepRow {
-    uint64_t row_free[4]; // the row's free real edges by action index
-    int n_free;
-    bool served, open;
-    uint32_t m;           // the drawn compact edges of the root
-    RowFacts f;
-    bool cand;            // per lane: compact edge `lane` is free and the game is open
-    int a, q;             // per lane: the edge's action index; its worth (cand only)
-};
-
-template <typename T>
-static __device__ __forceinline__ DeepRow deep_row(const TablesBoard &board, const DeepRoot &R, const int8_t *__restrict__ Tb,
-                                                   const T *__restrict__ xr, int lane)
-{
-    DeepRow d;
-    const int cols = board.cols, HW = board.HW, W = cols + 1, B = board.rows * cols;
-    d.n_free = row_free_edges(board, xr, lane, d.row_free);
-    d.served = true;
-#pragma unroll
-    for (int w = 0; w < DBAZ_MAX_A / 64; w++) d.served = d.served && (d.row_free[w] & ~R.free_edges[w]) == 0ull;
-    const bool edge = lane < R.F;
-    d.a = edge ? (int)R.act[lane] : 0;
-    const bool drawn = edge && xr[d.a] != (T)0;
-    d.m = (uint32_t)__ballot(drawn);
-    int closed = 0;
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int b = b0 + lane;
-        bool c = false;
-        if (b < B) {
-            const int at = (b / cols) * W + b % cols;
-            c = xr[at] != (T)0 && xr[at + W] != (T)0 && xr[HW + at] != (T)0 && xr[HW + at + 1] != (T)0;
-        }
-        closed += __popcll(__ballot(c));
-    }
-    d.f = solver_facts(B, closed, (int)xr[2 * HW]);
-    d.open = d.f.res == DBAZ_RESULT_NONE;
-    d.cand = d.served && d.open && edge && !drawn;
-    d.q = d.cand ? solver_move_q(R.other[lane][0], R.other[lane][1], d.m, (int)Tb[d.m | (1u << lane)]) : 0;
-    return d;
-}
-
-// dbaz_endgame_score's outputs of the served rows, plus `served`.  q[a] goes out once per action slot: the lane of slot a finds
-// the slot's compact edge as the rank of a in the root's edge set and fetches that lane's Q.  policy_mass: every lane walks the
-// compact edges in ascending order and adds the members' pi in float32 -- k_endgame_score's additions, hence its bits.
-// deep_score_row: one row of one wavefront.
+// dbaz_endgame_score's outputs of the served rows, plus `served`, for one row of one wavefront.  q[a] goes out once per action
+// slot: the lane of slot a fetches the Q of the slot's compact edge (edge_rank).  policy_mass is row_members' S.
 static __device__ __forceinline__ void deep_score_row(const TablesBoard &B, const DeepRoot &R, const int8_t *__restrict__ Tb,
                                                       const int16_t *__restrict__ x, const float *__restrict__ pi, int r, int lane,
                                                       int8_t *__restrict__ value, int8_t *__restrict__ diff, int8_t *__restrict__ q,
                                                       float *__restrict__ mass, int16_t *__restrict__ n_free, uint8_t *__restrict__ served)
 {
     const int A = B.A;
-    const DeepRow d = deep_row(B, R, Tb, x + (size_t)r * 3 * B.HW, lane);
+    const TableRow d = table_row<true>(B, R, R.F, Tb, x + (size_t)r * 3 * B.HW, lane);
     const int t = d.served ? (int)Tb[d.m] : -128;
     const int v = !d.served ? 0 : d.open ? sgn(d.f.margin + t) : d.f.res;
     int8_t *qr = q + (size_t)r * A;
-    int before = 0; // root edges in the words below
 #pragma unroll
     for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
         const int a = w * 64 + lane;
-        const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
-        const int qc = __shfl(d.q, c & 63);
+        const int qc = __shfl(d.q, edge_rank(R.free_edges, a) & 63);
         const bool is_cand = d.served && d.open && ((d.row_free[w] >> lane) & 1ull);
         if (a < A) qr[a] = (int8_t)(is_cand ? qc : -128);
-        before += __popcll(R.free_edges[w]);
     }
     float sum = 0.0f;
-    if (mass) {
-        const float p = d.cand ? pi[(size_t)r * A + d.a] : 0.0f;
-        const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
-        for (int c = 0; c < R.F; c++) { // ascending action order
-            const float pc = __shfl(p, c);
-            if ((members >> c) & 1u) sum += pc;
-        }
-    }
+    if (mass) sum = row_members(d.cand, d.f.margin, d.q, v, d.cand ? pi[(size_t)r * A + d.a] : 0.0f, R.F).sum;
     if (lane == 0) {
         value[r] = (int8_t)v;
         diff[r] = (int8_t)t;
@@ -709,9 +607,8 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_score(TablesBoard B,
 }
 
 // dbaz_exact_targets' rule (include/dbaz.h) with v and q from the row's table: a row that is not served or of a finished game is
-// left alone; otherwise z <- v and pi by pi_mode over O = the members, S added in ascending action order in float32 as
-// k_endgame_targets adds it, one float32 division per entry -- hence its bits wherever both apply.  The lane of action slot a
-// finds the slot's compact edge as deep_score_row does.  pi and z are read and written by the same wavefront only.
+// left alone; otherwise z <- v and pi by pi_mode over the members (row_members, relabel_entry: table_row.h).  pi and z are read
+// and written by the same wavefront only.
 __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard B, const DeepRoot *__restrict__ roots, int n_solved,
                                                                     const int8_t *__restrict__ T, int stride_bits, const int16_t *__restrict__ x,
                                                                     const int32_t *__restrict__ table_of, int n, int pi_mode, int z_mode, float *pi,
@@ -731,29 +628,20 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard 
         } else {
             const DeepRoot &R = roots[t];
             const int8_t *Tb = T + ((size_t)t << stride_bits);
-            const DeepRow d = deep_row(B, R, Tb, xr, lane);
+            const TableRow d = table_row<true>(B, R, R.F, Tb, xr, lane);
             nf = d.n_free;
             if (d.served && d.open) {
                 touched = true;
                 const int v = sgn(d.f.margin + (int)Tb[d.m]);
                 float *pr = pi ? pi + (size_t)r * B.A : nullptr;
-                const float p = pr && d.cand ? pr[d.a] : 0.0f;
-                const uint32_t members = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
-                for (int c = 0; c < R.F; c++) { // ascending action order
-                    const float pc = __shfl(p, c);
-                    if ((members >> c) & 1u) sum += pc;
-                }
+                const RowMembers M = row_members(d.cand, d.f.margin, d.q, v, pr && d.cand ? pr[d.a] : 0.0f, R.F);
+                sum = M.sum;
                 if (pi_mode) {
-                    const bool uniform = pi_mode == 1 || !(sum > 0.0f);
-                    const float share = 1.0f / (float)__popc(members);
-                    int before = 0; // root edges in the words below
 #pragma unroll
                     for (int w = 0; w < DBAZ_MAX_A / 64; w++) {
                         const int a = w * 64 + lane;
-                        const int c = before + __popcll(R.free_edges[w] & ((1ull << lane) - 1ull));
-                        const bool member = ((d.row_free[w] >> lane) & 1ull) && ((members >> (c & 31)) & 1u);
-                        if (a < B.A) pr[a] = member ? (uniform ? share : pr[a] / sum) : 0.0f;
-                        before += __popcll(R.free_edges[w]);
+                        const bool member = ((d.row_free[w] >> lane) & 1ull) && ((M.set >> (edge_rank(R.free_edges, a) & 31)) & 1u);
+                        if (a < B.A) pr[a] = relabel_entry(M, pi_mode, member, pr[a]);
                     }
                 }
                 if (lane == 0 && z_mode) z[r] = (float)v;
@@ -776,7 +664,7 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_policy(TablesBoard B, 
     const DeepRoot &R = *root;
     const int lane = threadIdx.x & 63, A = B.A;
     for (int r = blockIdx.x * DEEP_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * DEEP_WAVES) {
-        const DeepRow d = deep_row(B, R, Tb, x + (size_t)r * 3 * B.HW, lane);
+        const TableRow d = table_row<true>(B, R, R.F, Tb, x + (size_t)r * 3 * B.HW, lane);
         const int pick = endgame_pick(d.cand, d.q, d.a, pick_seed);
         float *pr = P + (size_t)r * A;
         for (int a = lane; a < A; a += 64) pr[a] = a == pick ? 1.0f : 0.0f;
@@ -815,8 +703,7 @@ static int tables_init(dbaz_tables *t, std::string &err, const char *api, int ro
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return fail(err, DBAZ_EDEVICE, "no HIP device %d (there is no CPU fallback)", device);
     t->api = api;
-    t->board.rows = rows; t->board.cols = cols;
-    t->board.HW = (rows + 1) * (cols + 1); t->board.A = 2 * t->board.HW;
+    t->board = tables_board(rows, cols);
     t->dev = device;
     t->max_free = max_free == 0 ? DEEP_DEFAULT_FREE : max_free;
     t->n_tables = n_tables == 0 ? TABLES_DEFAULT : n_tables;
@@ -1111,20 +998,6 @@ struct SlotDepthDev {
     uint32_t hoff[SOLVER_MAX_HIGH + 2]; // layers of `hi`
 };
 
-static __device__ __forceinline__ uint64_t word_of(const uint64_t (&fe)[4], int w)
-{
-    return w == 0 ? fe[0] : w == 1 ? fe[1] : w == 2 ? fe[2] : fe[3];
-}
-// compact edge of action a: its rank among the free edges
-static __device__ __forceinline__ int slot_rank(const uint64_t (&fe)[4], int a)
-{
-    const int w = a >> 6;
-    int r = __popcll(word_of(fe, w) & ((1ull << (a & 63)) - 1ull));
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        if (i < w) r += __popcll(fe[i]);
-    return r;
-}
 // solver_move_q's mask of box (bl, bc) for its edge `a`: the box's other edges that are free, over the compact edges
 static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, const uint64_t (&fe)[4], int bl, int bc, int a)
 {
@@ -1133,14 +1006,13 @@ static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, 
     uint32_t o = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++)
-        if (ed[i] != a && ((word_of(fe, ed[i] >> 6) >> (ed[i] & 63)) & 1ull)) o |= 1u << slot_rank(fe, ed[i]);
+        if (ed[i] != a && ((word_of(fe, ed[i] >> 6) >> (ed[i] & 63)) & 1ull)) o |= 1u << edge_rank(fe, ed[i]);
     return o;
 }
 
-// Step 1 of a pass, one wavefront per slot with a request (a slot without one costs one word read), k_endgame_table's rule: the
-// same game with free edges inside the table's keeps the table, F > max_free drops it, anything else gets a new header -- F0, the
-// free-edge set, act and `other` as position_geometry builds them, the real edges and box neighbours from the board alone -- and
-// its BatchGeo goes on the pass's list.  Lane l looks at action slots l, 64 + l, ...; a free one writes its compact edge's entries.
+// Step 1 of a pass, one wavefront per slot with a request (a slot without one costs one word read): slot_request_rule
+// (endgame.h) keeps or drops the table, or the slot gets a new header -- F0, the free-edge set, act and `other` as
+// position_geometry builds them, the real edges and box neighbours from the board alone -- and its BatchGeo goes on the pass's list.  Lane l looks at action slots l, 64 + l, ...; a free one writes its compact edge's entries.
 #define SLOT_REQ_WAVES 4
 __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
                                                                        EndgameSlotHdr *__restrict__ hdr, int n_slots, BatchGeo *__restrict__ geo,
@@ -1155,24 +1027,18 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
         EndgameSlotHdr *h = hdr + slot;
         if (!*(volatile const int32_t *)&rq->want) continue; // the same answer in every lane: nobody has written yet
         uint64_t fe[4];
-        bool subset = true;
-        int F = 0;
 #pragma unroll
-        for (int w = 0; w < 4; w++) {
-            fe[w] = rq->free_edges[w] & __ballot(board_real_edge(B, w * 64 + lane));
-            subset = subset && (fe[w] & ~h->free_edges[w]) == 0ull;
-            F += __popcll(fe[w]);
-        }
+        for (int w = 0; w < 4; w++) fe[w] = rq->free_edges[w] & __ballot(board_real_edge(B, w * 64 + lane));
         const int64_t game = rq->game;
         const int model = rq->model;
-        const bool keep = h->valid != 0 && h->game == game && subset;
-        const bool solve = !keep && F <= max_free;
+        const SlotDecision d = slot_request_rule(fe, h->valid, h->game, h->free_edges, game, max_free);
+        const int F = d.F;
         if (lane == 0) {
             rq->want = 0;
             h->model = model;
-            if (!keep && !solve) h->valid = 0;
+            if (!d.keep && !d.solve) h->valid = 0;
         }
-        if (!solve) continue;
+        if (!d.solve) continue;
 
         uint32_t at = 0;
         if (lane == 0) at = atomicAdd(count, 1u);
@@ -1188,7 +1054,7 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
         for (int w = 0; w < 4; w++) {
             const int a = w * 64 + lane;
             if (!((fe[w] >> lane) & 1ull)) continue;
-            const int j = slot_rank(fe, a);
+            const int j = edge_rank(fe, a);
             uint32_t o[2] = {SOLVER_NO_BOX, SOLVER_NO_BOX};
             int used = 0;
             if (a < B.HW) { // a horizontal edge: the boxes above and below, in the order of the board's box scan
@@ -1338,8 +1204,7 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[
 void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
                       unsigned long long *stats)
 {
-    TablesBoard B;
-    B.rows = st->rows; B.cols = st->cols; B.HW = (st->rows + 1) * (st->cols + 1); B.A = 2 * B.HW;
+    const TablesBoard B = tables_board(st->rows, st->cols);
     uint32_t *count = st->count_dev + (st->pass & 1u), *count_next = st->count_dev + ((st->pass + 1u) & 1u);
     st->pass++;
     const int blocks = std::min((n_slots + SLOT_REQ_WAVES - 1) / SLOT_REQ_WAVES, 1024);
