@@ -39,7 +39,7 @@ SYMBOLS = [
     "dbaz_deep_last_error", "dbaz_deep_create", "dbaz_deep_destroy", "dbaz_deep_solve", "dbaz_deep_info", "dbaz_deep_table",
     "dbaz_deep_score", "dbaz_deep_policy",
     "dbaz_tables_last_error", "dbaz_tables_create", "dbaz_tables_destroy", "dbaz_tables_solve", "dbaz_tables_info", "dbaz_tables_roots",
-    "dbaz_tables_table", "dbaz_tables_score", "dbaz_tables_targets",
+    "dbaz_tables_table", "dbaz_tables_score", "dbaz_tables_targets", "dbaz_replay_exact_targets",
     "dbaz_attach_tables", "dbaz_get_slot_table",
 ]
 
@@ -215,6 +215,7 @@ def load():
     L.dbaz_tables_table.argtypes = [vp, i32, vp, i64, i64]
     L.dbaz_tables_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dbaz_tables_targets.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.dbaz_replay_exact_targets.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp]
     L.dbaz_attach_tables.argtypes = [vp, i32, vp, C.c_uint64, i32]
     L.dbaz_get_slot_table.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, i64, i64]
     for name in SYMBOLS:

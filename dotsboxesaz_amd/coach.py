@@ -44,7 +44,10 @@ class Coach:
     def __init__(self, params, rows, cols, device=0, n_slots=None, dist=None, nn_precision=1, exact_targets=None, exact_pi="restrict",
                  exact_z=True):
         """exact_targets: an endgame.Endgame of the board, or True for one with max_free = 16 -- the train and the validation
-        dataset of every generation get the solved z (exact_z) and pi (exact_pi) on their late rows (train_data.ReplayDataset)."""
+        dataset of every generation get the solved z (exact_z) and pi (exact_pi) on their late rows (train_data.ReplayDataset).
+        An endgame.DeepTables of the board (max_free <= 31) instead relabels the packed replay rows themselves, right after
+        self-play and before the ranks exchange them (DeepTables.replay_targets: one table per game, every rank its own games);
+        the datasets are then built from the relabelled generation without a relabel of their own."""
         self.params, self.rows, self.cols = params, int(rows), int(cols)
         self.exact_targets, self.exact_pi, self.exact_z = exact_targets, exact_pi, exact_z
         self.exact_stats = None
@@ -78,12 +81,25 @@ class Coach:
         first, count = sp.shard_games(n_games, world, rank)
         tick = time.time()
         rows = sp.collect_rows_device(e, count, first)  # backpressure drains stay on the device
+        exact = None
+        if self._relabels_rows():  # this rank's games only: a game's rows are all here before the exchange
+            exact = self.exact_targets.replay_targets(rows, self.exact_pi, self.exact_z)
+            exact["by_free"] = exact["by_free"].tolist()
+            self.exact_stats = exact
         if self.dist is not None and world > 1:
             rows, _ = sp.all_gather_rows(rows, self.dist)
         self.store.add_generation(generation, rows, train_split=float(_get(_get(_get(self.params, "nn"), "train_params"), "train_split", 0.9)))
         c = e.counters()  # this rank's games: network evaluations, those the exact-f32 safety net redid, tree-reuse fallbacks
-        return dict(rows=int(rows.shape[0]), seconds=time.time() - tick, games=n_games, nn_evals=int(c["nn_evals"]),
-                    f32_fallback_evals=int(c["f32_fallback_evals"]), pool_resets=int(c["pool_resets"]), moves_played=int(c["moves_played"]))
+        out = dict(rows=int(rows.shape[0]), seconds=time.time() - tick, games=n_games, nn_evals=int(c["nn_evals"]),
+                   f32_fallback_evals=int(c["f32_fallback_evals"]), pool_resets=int(c["pool_resets"]), moves_played=int(c["moves_played"]))
+        if exact is not None:
+            out["exact_targets"] = exact
+        return out
+
+    def _relabels_rows(self):
+        """exact_targets is a pool of deep tables: the packed rows are relabelled in selfplay(), not the datasets in train_nn()"""
+        from .endgame import DeepTables
+        return isinstance(self.exact_targets, DeepTables)
 
     def train_nn(self, generation, writer=None):
         """coach.train_nn (coach.py:35-96) on the device-resident window."""
@@ -104,11 +120,13 @@ class Coach:
         if self.exact_targets is True:
             from .endgame import Endgame
             self.exact_targets = Endgame(self.rows, self.cols, self.device)
-        exact = dict(exact=self.exact_targets, exact_pi=self.exact_pi, exact_z=self.exact_z) if self.exact_targets is not None else {}
+        by_dataset = self.exact_targets is not None and not self._relabels_rows()
+        exact = dict(exact=self.exact_targets, exact_pi=self.exact_pi, exact_z=self.exact_z) if by_dataset else {}
         # both datasets: the train and the validation loss are measured against the same targets
         train_ds = self.store.dataset(train=True, min_generation=gmin, n_samples=int(n_samples * split), pos_average=avg, **exact)
         val_ds = self.store.dataset(train=False, min_generation=gmin, n_samples=int(n_samples * (1 - split)), pos_average=avg, **exact)
-        self.exact_stats = train_ds.exact_stats
+        if by_dataset:
+            self.exact_stats = train_ds.exact_stats
         self.store.drop_before(gmin)  # (the window's lower edge only moves forward: older rows would stay in HBM for nothing)
         return wrapper.train(train_ds, val_ds if len(val_ds) else None, writer, generation)
 

@@ -29,9 +29,9 @@
 #include <vector>
 
 #include "replay.h"
+#include "replay_row.h"
 
-#define ROW_X_OFF 28 // sizeof(RowMeta)
-#define ROW_Z_OFF 25
+static_assert(sizeof(RowMeta) == ROW_X_OFF && offsetof(RowMeta, z) == ROW_Z_OFF, "replay_row.h restates RowMeta");
 
 struct DevBuf {
     void *p = nullptr;

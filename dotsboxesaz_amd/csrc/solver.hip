@@ -21,9 +21,12 @@
 // The second half of the file runs the same two kernels on the subgames of positions of any board, F <= 31 free
 // edges each: a pool of tables (dbaz_tables_*), many roots solved side by side with grid.y = the roots of equal F, and rows of
 // many games answered in one launch, each from its game's table (k_tables_score, k_tables_targets).  dbaz_deep_* is a pool of one
-// table on the same path, plus the table as an evaluator (k_deep_policy).  At the end, the same bodies inside the search
+// table on the same path, plus the table as an evaluator (k_deep_policy).  dbaz_replay_exact_targets takes packed replay rows
+// instead of feature rows: games, roots and geometries are found on the device (k_replay_*), the rows relabelled where they lie.
+// At the end, the same bodies inside the search
 // (dbaz_attach_tables): one table per engine slot, solved from requests that exist only on the device (k_slot_requests,
 // k_slot_solve; slot_tables_plan.h).
+#include <hipcub/hipcub.hpp>
 #include <string.h>
 
 #include <algorithm>
@@ -33,6 +36,8 @@
 #include "deep_batch.h"
 #include "endgame.h"
 #include "position_geo.h"
+#include "replay_chunks.h"
+#include "replay_row.h"
 #include "slot_tables_plan.h"
 #include "solver.h"
 #include "table_row.h"
@@ -517,6 +522,31 @@ struct DeepRoot {
     uint8_t act[SOLVER_MAX_E + 1];        // compact edge -> action index
 };
 
+// device scratch that grows on demand and keeps nothing across a growth
+struct DevScratch {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t need(size_t bytes)
+    {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = bytes + bytes / 2 + 256;
+        const hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        else p = nullptr;
+        return e;
+    }
+};
+
+// what one dbaz_replay_exact_targets call needs besides the pool; one call at a time per handle
+struct ReplayScratch {
+    DevScratch keys, keys2, idx, idx2; // (game_idx, move_idx) and the row index beside it, before and after the sort
+    DevScratch n_free, flag, gid, gstart, games, first, cum, tmp, small;
+    std::vector<hipEvent_t> marks;     // the call's timeline
+};
+
 struct dbaz_tables {
     TablesBoard board;
     int dev = 0, max_free = 0, n_tables = 0;
@@ -528,6 +558,8 @@ struct dbaz_tables {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t used = nullptr;            // behind the last kernel that reads the pool on a caller's stream: the next solve waits for it
+    hipEvent_t caller = nullptr;          // dbaz_replay_exact_targets: where the caller's stream stood when the call began
+    ReplayScratch replay;
     int n_solved = 0;
     std::vector<int32_t> n_free, d0;      // of the solved roots
     std::vector<BatchGeo> geo_host;       // what the last solve uploaded; alive until its copies are done
@@ -655,6 +687,220 @@ __global__ void __launch_bounds__(64 * DEEP_WAVES) k_tables_targets(TablesBoard 
     }
 }
 
+// ---- exact targets on packed replay rows (dbaz_replay_exact_targets, include/dbaz.h) ---------------------------
+// The rows of one call lie in HBM as the engine packed them (replay_row.h), in any order.  k_replay_scan keys every row by
+// (game_idx, move_idx) and counts its free edges; a radix sort of the keys puts each game's rows together in move order;
+// k_replay_flags / an inclusive scan / k_replay_gstart cut the sorted rows into games (and flag a key that occurs twice);
+// k_replay_games finds each game's root.  Per chunk of roots (replay_chunks.h) k_replay_roots builds the geometries where the root
+// rows lie, the solving kernels fill the chunk's tables, and k_replay_relabel rewrites the candidate rows in place.
+static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, const uint64_t (&fe)[4], int bl, int bc, int a); // below, with k_slot_requests
+
+#define REPLAY_WAVES 4
+#define REPLAY_COUNTERS (4 + SOLVER_MAX_E + 1) // relabelled, finished, unserved, z_changed, by_free[32]
+
+static __device__ __forceinline__ unsigned long long replay_key(int32_t game, int16_t move)
+{
+    return ((unsigned long long)((uint32_t)game ^ 0x80000000u) << 16) | (unsigned long long)(uint16_t)((uint16_t)move ^ 0x8000u);
+}
+
+// One wavefront per packed row: the sort key, the row's own index beside it, and F from the edge planes.
+__global__ void __launch_bounds__(64 * REPLAY_WAVES) k_replay_scan(TablesBoard B, const unsigned char *__restrict__ rows, int row_bytes, int n,
+                                                                   unsigned long long *__restrict__ keys, int32_t *__restrict__ idx,
+                                                                   int32_t *__restrict__ n_free)
+{
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.x * REPLAY_WAVES + (threadIdx.x >> 6); r < n; r += gridDim.x * REPLAY_WAVES) {
+        const unsigned char *row = rows + (size_t)r * row_bytes;
+        uint64_t fe[4];
+        const int F = row_free_edges(B, reinterpret_cast<const int16_t *>(row + ROW_X_OFF), lane, fe);
+        if (lane == 0) {
+            keys[r] = replay_key(*reinterpret_cast<const int32_t *>(row + ROW_GAME_OFF), *reinterpret_cast<const int16_t *>(row + ROW_MOVE_OFF));
+            idx[r] = r;
+            n_free[r] = F;
+        }
+    }
+}
+
+// One thread per sorted position: a new game starts here; a key equal to its predecessor's sets hdr[0].
+__global__ void __launch_bounds__(256) k_replay_flags(const unsigned long long *__restrict__ keys, int n, int32_t *__restrict__ flag,
+                                                      int32_t *__restrict__ hdr)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const bool first = i == 0 || (keys[i] >> 16) != (keys[i - 1] >> 16);
+    if (i > 0 && keys[i] == keys[i - 1]) atomicOr(hdr, 1);
+    flag[i] = first ? 1 : 0;
+}
+
+// gid: the inclusive sum of flag.  gstart[g] = where game g begins among the sorted rows, gstart[games] = n; hdr[1] = games.
+__global__ void __launch_bounds__(256) k_replay_gstart(const int32_t *__restrict__ flag, const int32_t *__restrict__ gid, int n,
+                                                       int32_t *__restrict__ gstart, int32_t *__restrict__ hdr)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (flag[i]) gstart[gid[i] - 1] = i;
+    if (i == n - 1) {
+        gstart[gid[i]] = n;
+        hdr[1] = gid[i];
+    }
+}
+
+// One lane per game: its root is its first row in move order with F <= max_free.  root_of (may be null): per row the row index of
+// its game's root if the row is that root or comes after it, else -1.  Nothing is written once a duplicate key was flagged.
+__global__ void __launch_bounds__(256) k_replay_games(const unsigned long long *__restrict__ keys, const int32_t *__restrict__ idx,
+                                                      const int32_t *__restrict__ n_free, const int32_t *__restrict__ gstart,
+                                                      const int32_t *__restrict__ hdr, int n, int max_free, ReplayGame *__restrict__ games,
+                                                      int32_t *__restrict__ root_of)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (hdr[0] != 0 || g >= min(hdr[1], n)) return;
+    const int lo = gstart[g], hi = min(gstart[g + 1], n);
+    int first = -1, root_row = -1, F = -1;
+    for (int i = lo; i < hi; i++) {
+        const int r = idx[i];
+        if ((unsigned)r >= (unsigned)n) continue; // never outside the caller's rows
+        if (first < 0 && n_free[r] <= max_free) {
+            first = i;
+            root_row = r;
+            F = n_free[r];
+        }
+        if (root_of) root_of[r] = root_row;
+    }
+    ReplayGame out;
+    out.game_idx = (int32_t)((uint32_t)(keys[lo] >> 16) ^ 0x80000000u);
+    out.F = F;
+    out.first = first < 0 ? hi : first;
+    out.end = hi;
+    games[g] = out;
+}
+
+// The device form of position_geometry, one wavefront per root of the chunk: root k = the row at sorted position first[k], into
+// geo[k] (slot k) for the solve and roots[k] for the rows.  Lane l looks at action slots l, 64 + l, ...; a free one writes its
+// compact edge's entries, the box neighbours in the order of the board's box scan; lanes F .. 31 write the entries no edge owns.
+// A row with more than max_free free edges (the scan has seen to it that there is none) gets an empty root, which serves nothing.
+__global__ void __launch_bounds__(64 * REPLAY_WAVES) k_replay_roots(TablesBoard B, int max_free, const unsigned char *__restrict__ rows, int row_bytes,
+                                                                    int n, const int32_t *__restrict__ idx, const int32_t *__restrict__ first,
+                                                                    int n_roots, BatchGeo *__restrict__ geo, DeepRoot *__restrict__ roots)
+{
+    const int lane = threadIdx.x & 63, W = B.cols + 1;
+    for (int k = blockIdx.x * REPLAY_WAVES + (threadIdx.x >> 6); k < n_roots; k += gridDim.x * REPLAY_WAVES) {
+        const int pos = first[k];
+        const int r = (unsigned)pos < (unsigned)n ? idx[pos] : -1;
+        uint64_t fe[4] = {0ull, 0ull, 0ull, 0ull};
+        int F = 0;
+        if ((unsigned)r < (unsigned)n) F = row_free_edges(B, reinterpret_cast<const int16_t *>(rows + (size_t)r * row_bytes + ROW_X_OFF), lane, fe);
+        if (F > max_free) {
+            F = 0;
+            fe[0] = fe[1] = fe[2] = fe[3] = 0ull;
+        }
+        BatchGeo *bg = geo + k;
+        DeepRoot *R = roots + k;
+        if (lane >= F && lane <= SOLVER_MAX_E) {
+            R->act[lane] = 0;
+            if (lane < SOLVER_MAX_E) bg->other[lane][0] = bg->other[lane][1] = R->other[lane][0] = R->other[lane][1] = SOLVER_NO_BOX;
+        }
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const int a = w * 64 + lane;
+            if (!((fe[w] >> lane) & 1ull)) continue;
+            const int j = edge_rank(fe, a);
+            uint32_t o[2] = {SOLVER_NO_BOX, SOLVER_NO_BOX};
+            int used = 0;
+            if (a < B.HW) { // a horizontal edge: the boxes above and below
+                const int l = a / W, c = a % W;
+                if (l >= 1) o[used++] = slot_box_other(B, fe, l - 1, c, a);
+                if (l < B.rows) o[used++] = slot_box_other(B, fe, l, c, a);
+            } else { // a vertical edge: the boxes to its left and right
+                const int l = (a - B.HW) / W, c = (a - B.HW) % W;
+                if (c >= 1) o[used++] = slot_box_other(B, fe, l, c - 1, a);
+                if (c < B.cols) o[used++] = slot_box_other(B, fe, l, c, a);
+            }
+            bg->other[j][0] = R->other[j][0] = o[0];
+            bg->other[j][1] = R->other[j][1] = o[1];
+            R->act[j] = (uint8_t)a;
+        }
+        if (lane == 0) {
+            bg->F = R->F = F;
+            bg->slot = k;
+            for (int w = 0; w < 4; w++) R->free_edges[w] = fe[w];
+        }
+    }
+}
+
+// One wavefront per candidate row of the chunk.  The candidates of the chunk's root k are the sorted positions
+// first[k] .. first[k] + (cum[k + 1] - cum[k]) - 1, candidate number c - cum[0] of the chunk belongs to the root with
+// cum[k] <= c < cum[k + 1].  The rule of include/dbaz.h in visit space: a row that its root does not serve or whose game is over
+// is only counted; otherwise O comes from the table as in k_tables_targets, the visits on O are summed in int32, and the
+// row's visits and z are rewritten by the wavefront that read them.  The visits are 2-byte aligned (replay_row.h): they are read and
+// written as halves.  Counters: per workgroup in LDS, added once.
+__global__ void __launch_bounds__(64 * REPLAY_WAVES) k_replay_relabel(TablesBoard B, const DeepRoot *__restrict__ roots, int n_roots,
+                                                                      const int8_t *__restrict__ T, int stride_bits, unsigned char *rows,
+                                                                      int row_bytes, int n, const int32_t *__restrict__ idx,
+                                                                      const int32_t *__restrict__ first, const int32_t *__restrict__ cum,
+                                                                      int pi_mode, int z_mode, unsigned long long *__restrict__ counters)
+{
+    __shared__ unsigned int cnt[REPLAY_COUNTERS];
+    for (int i = threadIdx.x; i < REPLAY_COUNTERS; i += blockDim.x) cnt[i] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int c0 = cum[0], total = cum[n_roots] - c0;
+    for (int w = blockIdx.x * REPLAY_WAVES + (threadIdx.x >> 6); w < total; w += gridDim.x * REPLAY_WAVES) {
+        const int c = c0 + w;
+        int lo = 0, hi = n_roots; // the last k with cum[k] <= c: the same search in every lane
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (cum[mid] <= c) lo = mid;
+            else hi = mid;
+        }
+        const int k = lo, pos = first[k] + (c - cum[k]);
+        const int r = (unsigned)pos < (unsigned)n ? idx[pos] : -1;
+        if ((unsigned)r >= (unsigned)n) continue; // never outside the caller's rows
+        unsigned char *row = rows + (size_t)r * row_bytes;
+        const DeepRoot &R = roots[k];
+        const int8_t *Tb = T + ((size_t)k << stride_bits);
+        const TableRow d = table_row<true>(B, R, R.F, Tb, reinterpret_cast<const int16_t *>(row + ROW_X_OFF), lane);
+        if (!d.served || !d.open) {
+            if (lane == 0) atomicAdd(&cnt[d.served ? 1 : 2], 1u);
+            continue;
+        }
+        const int v = sgn(d.f.margin + (int)Tb[d.m]);
+        const uint32_t set = (uint32_t)__ballot(d.cand && sgn(d.f.margin + d.q) == v);
+        uint16_t *vis = reinterpret_cast<uint16_t *>(row + ROW_X_OFF + (size_t)3 * B.HW * 2);
+        int32_t mine[DBAZ_MAX_A / 64];
+        bool member[DBAZ_MAX_A / 64];
+        int32_t sum = 0;
+#pragma unroll
+        for (int q = 0; q < DBAZ_MAX_A / 64; q++) {
+            const int a = q * 64 + lane;
+            member[q] = ((d.row_free[q] >> lane) & 1ull) && ((set >> (edge_rank(R.free_edges, a) & 31)) & 1u);
+            mine[q] = a < B.A ? (int32_t)((uint32_t)vis[2 * a] | ((uint32_t)vis[2 * a + 1] << 16)) : 0;
+            if (member[q]) sum += mine[q];
+        }
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        if (pi_mode) {
+#pragma unroll
+            for (int q = 0; q < DBAZ_MAX_A / 64; q++) {
+                const int a = q * 64 + lane;
+                const int32_t out = !member[q] ? 0 : (pi_mode == 1 || sum == 0) ? 1 : mine[q];
+                if (a < B.A) {
+                    vis[2 * a] = (uint16_t)((uint32_t)out & 0xFFFFu);
+                    vis[2 * a + 1] = (uint16_t)((uint32_t)out >> 16);
+                }
+            }
+        }
+        if (lane == 0) {
+            int8_t *z = reinterpret_cast<int8_t *>(row + ROW_Z_OFF);
+            if ((int)*z != v) atomicAdd(&cnt[3], 1u);
+            if (z_mode) *z = (int8_t)v;
+            atomicAdd(&cnt[0], 1u);
+            atomicAdd(&cnt[4 + min(d.n_free, SOLVER_MAX_E)], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < REPLAY_COUNTERS; i += blockDim.x)
+        if (cnt[i]) atomicAdd(&counters[i], (unsigned long long)cnt[i]);
+}
+
 // The table as a (p, v) evaluator with dbaz_exact_policy's outputs: one-hot on endgame_pick's move, v the true result.  A finished
 // game: p = 0, v = get_result; a row that is not served: p = 0, v = 0.  One root, one table (dbaz_deep_policy).
 __global__ void __launch_bounds__(64 * DEEP_WAVES) k_deep_policy(TablesBoard B, const DeepRoot *__restrict__ root, const int8_t *__restrict__ Tb,
@@ -682,7 +928,11 @@ static void tables_release(dbaz_tables *t)
     for (void *b : {(void *)t->T, (void *)t->geo_dev, (void *)t->roots_dev, (void *)t->d0_dev})
         if (b) (void)hipFree(b);
     free_work_lists(t->lists);
-    for (hipEvent_t e : {t->ev0, t->ev1, t->used})
+    ReplayScratch &rs = t->replay;
+    for (DevScratch *b : {&rs.keys, &rs.keys2, &rs.idx, &rs.idx2, &rs.n_free, &rs.flag, &rs.gid, &rs.gstart, &rs.games, &rs.first, &rs.cum, &rs.tmp, &rs.small})
+        if (b->p) (void)hipFree(b->p);
+    for (hipEvent_t e : rs.marks) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {t->ev0, t->ev1, t->used, t->caller})
         if (e) (void)hipEventDestroy(e);
     if (t->stream) (void)hipStreamDestroy(t->stream);
 }
@@ -734,6 +984,56 @@ static int tables_create(H **out, std::string &err, const char *api, int rows, i
     return rc;
 }
 
+// The pool and the per-root arrays, allocated by the first solve and kept.
+static int tables_pool(dbaz_tables *t)
+{
+    CHECK_HIP(t->err, hipSetDevice(t->dev));
+    if (t->T) return DBAZ_OK;
+    const size_t bytes = (size_t)deep_batch_slot_offset(t->n_tables, t->max_free); // 64 bits: 64 x 2^31 is past 32
+    hipError_t e = hipMalloc((void **)&t->T, bytes);
+    if (e == hipSuccess && !t->geo_dev) e = hipMalloc((void **)&t->geo_dev, (size_t)t->n_tables * sizeof(BatchGeo));
+    if (e == hipSuccess && !t->roots_dev) e = hipMalloc((void **)&t->roots_dev, (size_t)t->n_tables * sizeof(DeepRoot));
+    if (e == hipSuccess && !t->d0_dev) e = hipMalloc((void **)&t->d0_dev, (size_t)t->n_tables);
+    if (e != hipSuccess) {
+        if (t->T) (void)hipFree(t->T);
+        t->T = nullptr;
+        (void)hipGetLastError();
+        return fail(t->err, DBAZ_EDEVICE, "pool of %d tables, %zu bytes: %s", t->n_tables, bytes, hipGetErrorString(e));
+    }
+    return DBAZ_OK;
+}
+
+// lists[g]: the entry of t->lists that group g of the plan solves with (-1 for a plain group)
+static int tables_plan_lists(dbaz_tables *t, const DeepBatchPlan &plan, std::vector<int> &lists)
+{
+    lists.assign(plan.groups.size(), -1);
+    for (size_t g = 0; g < plan.groups.size(); g++)
+        if (!plan.groups[g].plain) {
+            hipError_t e = hipSuccess;
+            lists[g] = work_lists(t->lists, plan.groups[g].F, plan.groups[g].L, &e);
+            if (e != hipSuccess)
+                return fail(t->err, DBAZ_EDEVICE, "work lists of F = %d, L = %d: %s", plan.groups[g].F, plan.groups[g].L, hipGetErrorString(e));
+        }
+    return DBAZ_OK;
+}
+
+// The plan's launches on the handle's stream, back to back -- no host synchronisation between groups -- over the geometries
+// t->geo_dev holds in plan order, and then every root's T[0]
+static void tables_launch_plan(dbaz_tables *t, const DeepBatchPlan &plan, const std::vector<int> &lists, int n_roots)
+{
+    for (const DeepBatchLaunch &l : plan.launches) {
+        const DeepBatchGroup &g = plan.groups[l.group];
+        const dim3 grid(l.grid_x, l.grid_y);
+        if (g.plain) k_solver_layer<<<grid, 256, 0, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, l.k);
+        else {
+            const WorkLists &w = t->lists[(size_t)lists[l.group]];
+            k_solver_subcube<<<grid, SOLVER_THREADS, (size_t)1 << g.L, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, g.L,
+                                                                                   w.hi_dev + w.hoff[l.k], w.low_dev, w.off_dev);
+        }
+    }
+    k_tables_heads<<<(n_roots + 255) / 256, 256, 0, t->stream>>>(t->T, t->max_free, n_roots, t->d0_dev);
+}
+
 static int tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_host, int32_t low_bits)
 {
     t->n_solved = 0; // whatever happens below, the old tables are not handed out again
@@ -752,28 +1052,10 @@ static int tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_ho
     DeepBatchPlan plan;
     if (deep_batch_plan(F.data(), n_roots, t->max_free, t->n_tables, low_bits, plan) != 0)
         return fail(t->err, DBAZ_EINVAL, "%s_solve: %s", t->api, plan.error.c_str());
-    CHECK_HIP(t->err, hipSetDevice(t->dev));
-    if (!t->T) {
-        const size_t bytes = (size_t)deep_batch_slot_offset(t->n_tables, t->max_free); // 64 bits: 64 x 2^31 is past 32
-        hipError_t e = hipMalloc((void **)&t->T, bytes);
-        if (e == hipSuccess && !t->geo_dev) e = hipMalloc((void **)&t->geo_dev, (size_t)t->n_tables * sizeof(BatchGeo));
-        if (e == hipSuccess && !t->roots_dev) e = hipMalloc((void **)&t->roots_dev, (size_t)t->n_tables * sizeof(DeepRoot));
-        if (e == hipSuccess && !t->d0_dev) e = hipMalloc((void **)&t->d0_dev, (size_t)t->n_tables);
-        if (e != hipSuccess) {
-            if (t->T) (void)hipFree(t->T);
-            t->T = nullptr;
-            (void)hipGetLastError();
-            return fail(t->err, DBAZ_EDEVICE, "pool of %d tables, %zu bytes: %s", t->n_tables, bytes, hipGetErrorString(e));
-        }
-    }
-    std::vector<int> lists(plan.groups.size(), -1); // per group, its entry of t->lists
-    for (size_t g = 0; g < plan.groups.size(); g++)
-        if (!plan.groups[g].plain) {
-            hipError_t e = hipSuccess;
-            lists[g] = work_lists(t->lists, plan.groups[g].F, plan.groups[g].L, &e);
-            if (e != hipSuccess)
-                return fail(t->err, DBAZ_EDEVICE, "work lists of F = %d, L = %d: %s", plan.groups[g].F, plan.groups[g].L, hipGetErrorString(e));
-        }
+    std::vector<int> lists;
+    int rc = tables_pool(t);
+    if (rc == DBAZ_OK) rc = tables_plan_lists(t, plan, lists);
+    if (rc != DBAZ_OK) return rc;
 
     t->geo_host.assign((size_t)n_roots, BatchGeo());
     t->roots_host.assign((size_t)n_roots, DeepRoot());
@@ -794,17 +1076,7 @@ static int tables_solve(dbaz_tables *t, int32_t n_roots, const int16_t *roots_ho
     if (e == hipSuccess) e = hipMemcpyAsync(t->roots_dev, t->roots_host.data(), (size_t)n_roots * sizeof(DeepRoot), hipMemcpyHostToDevice, t->stream);
     if (e == hipSuccess) e = hipEventRecord(t->ev0, t->stream);
     if (e == hipSuccess) {
-        for (const DeepBatchLaunch &l : plan.launches) { // back to back: no host synchronisation between groups
-            const DeepBatchGroup &g = plan.groups[l.group];
-            const dim3 grid(l.grid_x, l.grid_y);
-            if (g.plain) k_solver_layer<<<grid, 256, 0, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, l.k);
-            else {
-                const WorkLists &w = t->lists[(size_t)lists[l.group]];
-                k_solver_subcube<<<grid, SOLVER_THREADS, (size_t)1 << g.L, t->stream>>>(t->geo_dev + g.first, t->T, t->max_free, g.L,
-                                                                                       w.hi_dev + w.hoff[l.k], w.low_dev, w.off_dev);
-            }
-        }
-        k_tables_heads<<<(n_roots + 255) / 256, 256, 0, t->stream>>>(t->T, t->max_free, n_roots, t->d0_dev);
+        tables_launch_plan(t, plan, lists, n_roots);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(t->ev1, t->stream);
@@ -922,6 +1194,193 @@ extern "C" int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_d
                                                                                  n, pi_mode, z_mode, pi_dev, z_dev, n_free_dev, mass_dev, relabelled_dev);
     CHECK_HIP(t->err, hipGetLastError());
     CHECK_HIP(t->err, hipEventRecord(t->used, (hipStream_t)stream));
+    return DBAZ_OK;
+}
+
+// ---- dbaz_replay_exact_targets: packed replay rows in, packed replay rows out (kernels: k_replay_* above)
+static_assert(sizeof(ReplayGame) == 16, "one game's record as the host reads it back");
+#define REPLAY_STATS 8          // rows, games, roots, chunks, relabelled, finished, unserved, z_changed
+#define REPLAY_PHASES 5         // scan, group, geometry, solve, relabel
+
+static hipError_t replay_sort(ReplayScratch &rs, int n, hipStream_t s, bool run)
+{
+    size_t bytes = run ? rs.tmp.cap : 0;
+    return hipcub::DeviceRadixSort::SortPairs(run ? rs.tmp.p : nullptr, bytes, (unsigned long long *)rs.keys.p, (unsigned long long *)rs.keys2.p,
+                                              (int32_t *)rs.idx.p, (int32_t *)rs.idx2.p, n, 0, 48, s) == hipSuccess
+               ? (run ? hipSuccess : rs.tmp.need(bytes))
+               : hipErrorUnknown;
+}
+
+static hipError_t replay_scan_sum(ReplayScratch &rs, int n, hipStream_t s, bool run)
+{
+    size_t bytes = run ? rs.tmp.cap : 0;
+    return hipcub::DeviceScan::InclusiveSum(run ? rs.tmp.p : nullptr, bytes, (int32_t *)rs.flag.p, (int32_t *)rs.gid.p, n, s) == hipSuccess
+               ? (run ? hipSuccess : rs.tmp.need(bytes))
+               : hipErrorUnknown;
+}
+
+// event `at` of the call's timeline, created the first time a call gets that far
+static hipError_t replay_mark(dbaz_tables *t, size_t at)
+{
+    ReplayScratch &rs = t->replay;
+    while (rs.marks.size() <= at) {
+        hipEvent_t ev = nullptr;
+        const hipError_t e = hipEventCreate(&ev);
+        if (e != hipSuccess) return e;
+        rs.marks.push_back(ev);
+    }
+    return hipEventRecord(rs.marks[at], t->stream);
+}
+
+extern "C" int dbaz_replay_exact_targets(dbaz_tables *t, void *rows_dev, int64_t n_rows, int32_t row_bytes, int32_t pi_mode, int32_t z_mode,
+                                         int32_t *root_of_dev, int64_t *stats_host, void *stream)
+{
+    if (!t) return DBAZ_EINVAL;
+    const TablesBoard &B = t->board;
+    if (pi_mode < 0 || pi_mode > 2 || z_mode < 0 || z_mode > 1)
+        return fail(t->err, DBAZ_EINVAL, "dbaz_replay_exact_targets: pi_mode %d / z_mode %d (pi_mode 0 keep, 1 uniform, 2 restrict; z_mode 0 keep, 1 solved)",
+                    pi_mode, z_mode);
+    if (row_bytes != replay_row_bytes(B.HW))
+        return fail(t->err, DBAZ_EINVAL, "dbaz_replay_exact_targets: row_bytes %d, a packed replay row of a %dx%d board has %d", row_bytes, B.rows, B.cols,
+                    replay_row_bytes(B.HW));
+    if (n_rows < 0 || n_rows > 0x7FFFFFF0ll || (n_rows > 0 && !rows_dev) || ((uintptr_t)rows_dev & 7) != 0)
+        return fail(t->err, DBAZ_EINVAL, "dbaz_replay_exact_targets: bad rows (n_rows = %lld; the rows are 8-byte aligned and at most 2^31 - 16)",
+                    (long long)n_rows);
+    if (stats_host) std::fill(stats_host, stats_host + REPLAY_STATS + SOLVER_MAX_E + 1 + REPLAY_PHASES, (int64_t)0);
+    if (n_rows == 0) return DBAZ_OK;
+
+    t->n_solved = 0; // the pool is about to be overwritten: the old tables are not handed out again
+    t->n_free.clear();
+    t->d0.clear();
+    const int n = (int)n_rows;
+    ReplayScratch &rs = t->replay;
+    unsigned char *rows = (unsigned char *)rows_dev;
+    int rc = tables_pool(t);
+    if (rc != DBAZ_OK) return rc;
+    hipError_t e = hipSuccess;
+    if (!t->caller) e = hipEventCreateWithFlags(&t->caller, hipEventDisableTiming);
+    for (DevScratch *b : {&rs.keys, &rs.keys2})
+        if (e == hipSuccess) e = b->need((size_t)n * 8);
+    for (DevScratch *b : {&rs.idx, &rs.idx2, &rs.n_free, &rs.flag, &rs.gid})
+        if (e == hipSuccess) e = b->need((size_t)n * 4);
+    if (e == hipSuccess) e = rs.gstart.need(((size_t)n + 1) * 4);
+    if (e == hipSuccess) e = rs.games.need((size_t)n * sizeof(ReplayGame));
+    if (e == hipSuccess) e = rs.first.need((size_t)n * 4);
+    if (e == hipSuccess) e = rs.cum.need(((size_t)n + 1) * 4);
+    if (e == hipSuccess) e = rs.small.need(64 + REPLAY_COUNTERS * 8);
+    if (e == hipSuccess) e = replay_sort(rs, n, t->stream, false);
+    if (e == hipSuccess) e = replay_scan_sum(rs, n, t->stream, false);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: scratch for %d rows: %s", n, hipGetErrorString(e));
+    }
+    int32_t *hdr = (int32_t *)rs.small.p;                                           // [0]: a key occurs twice; [1]: games
+    unsigned long long *counters = (unsigned long long *)((char *)rs.small.p + 64); // [REPLAY_COUNTERS]
+    const unsigned row_blocks = deep_blocks(n), lane_blocks = (unsigned)((n + 255) / 256);
+
+    // the rows as the caller's stream leaves them, and the pool after its last readers
+    CHECK_HIP(t->err, hipEventRecord(t->caller, (hipStream_t)stream));
+    CHECK_HIP(t->err, hipStreamWaitEvent(t->stream, t->caller, 0));
+    CHECK_HIP(t->err, hipStreamWaitEvent(t->stream, t->used, 0));
+    CHECK_HIP(t->err, hipMemsetAsync(rs.small.p, 0, 64 + REPLAY_COUNTERS * 8, t->stream));
+    size_t mark = 0;
+    CHECK_HIP(t->err, replay_mark(t, mark++)); // 0
+    k_replay_scan<<<row_blocks, 64 * REPLAY_WAVES, 0, t->stream>>>(B, rows, row_bytes, n, (unsigned long long *)rs.keys.p, (int32_t *)rs.idx.p,
+                                                                   (int32_t *)rs.n_free.p);
+    CHECK_HIP(t->err, replay_mark(t, mark++)); // 1
+    CHECK_HIP(t->err, replay_sort(rs, n, t->stream, true));
+    const unsigned long long *keys = (const unsigned long long *)rs.keys2.p;
+    const int32_t *idx = (const int32_t *)rs.idx2.p;
+    k_replay_flags<<<lane_blocks, 256, 0, t->stream>>>(keys, n, (int32_t *)rs.flag.p, hdr);
+    CHECK_HIP(t->err, replay_scan_sum(rs, n, t->stream, true));
+    k_replay_gstart<<<lane_blocks, 256, 0, t->stream>>>((const int32_t *)rs.flag.p, (const int32_t *)rs.gid.p, n, (int32_t *)rs.gstart.p, hdr);
+    k_replay_games<<<lane_blocks, 256, 0, t->stream>>>(keys, idx, (const int32_t *)rs.n_free.p, (const int32_t *)rs.gstart.p, hdr, n, t->max_free,
+                                                       (ReplayGame *)rs.games.p, root_of_dev);
+    CHECK_HIP(t->err, hipGetLastError());
+    CHECK_HIP(t->err, replay_mark(t, mark++)); // 2
+    int32_t head[2] = {0, 0};
+    CHECK_HIP(t->err, hipMemcpyAsync(head, hdr, sizeof head, hipMemcpyDeviceToHost, t->stream));
+    CHECK_HIP(t->err, hipStreamSynchronize(t->stream));
+    if (head[0] != 0) return fail(t->err, DBAZ_EINVAL, "dbaz_replay_exact_targets: two rows of one call have the same (game_idx, move_idx)");
+    const int n_games = head[1];
+    if (n_games < 1 || n_games > n) return fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: %d games in %d rows", n_games, n);
+    std::vector<ReplayGame> games((size_t)n_games);
+    CHECK_HIP(t->err, hipMemcpy(games.data(), rs.games.p, (size_t)n_games * sizeof(ReplayGame), hipMemcpyDeviceToHost));
+    ReplayChunks ch;
+    if (replay_chunks_plan(games.data(), n_games, n, t->max_free, t->n_tables, ch) != 0)
+        return fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: the games' records do not tile the %d sorted rows", n);
+    const int n_roots = (int)ch.order.size(), n_chunks = (int)ch.chunk_first.size() - 1;
+
+    // per chunk: geometry, solve, relabel -- back to back; the next chunk's solve overwrites the tables behind this chunk's rows
+    std::vector<int8_t> heads;
+    int last = 0;
+    if (n_roots > 0) {
+        CHECK_HIP(t->err, hipMemcpyAsync(rs.first.p, ch.first.data(), (size_t)n_roots * 4, hipMemcpyHostToDevice, t->stream));
+        CHECK_HIP(t->err, hipMemcpyAsync(rs.cum.p, ch.cum.data(), ((size_t)n_roots + 1) * 4, hipMemcpyHostToDevice, t->stream));
+    }
+    for (int c = 0; c < n_chunks; c++) {
+        const int lo = ch.chunk_first[c], m = ch.chunk_first[c + 1] - lo;
+        DeepBatchPlan plan;
+        if (deep_batch_plan(ch.n_free.data() + lo, m, t->max_free, t->n_tables, 0, plan) != 0)
+            rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: chunk %d: %s", c, plan.error.c_str());
+        for (int at = 0; rc == DBAZ_OK && at < m; at++)
+            if (plan.order[at] != at) rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: chunk %d is not in plan order", c);
+        std::vector<int> lists;
+        if (rc == DBAZ_OK) rc = tables_plan_lists(t, plan, lists);
+        if (rc != DBAZ_OK) break;
+        const int32_t *first = (const int32_t *)rs.first.p + lo, *cum = (const int32_t *)rs.cum.p + lo;
+        const int cand = ch.cum[lo + m] - ch.cum[lo];
+        e = replay_mark(t, mark++); // 3 + 3 c
+        k_replay_roots<<<deep_blocks(m), 64 * REPLAY_WAVES, 0, t->stream>>>(B, t->max_free, rows, row_bytes, n, idx, first, m, t->geo_dev, t->roots_dev);
+        if (e == hipSuccess) e = replay_mark(t, mark++);
+        tables_launch_plan(t, plan, lists, m);
+        if (e == hipSuccess) e = replay_mark(t, mark++);
+        k_replay_relabel<<<deep_blocks(cand), 64 * REPLAY_WAVES, 0, t->stream>>>(B, t->roots_dev, m, t->T, t->max_free, rows, row_bytes, n, idx, first, cum,
+                                                                                pi_mode, z_mode, counters);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) {
+            rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: chunk %d: %s", c, hipGetErrorString(e));
+            break;
+        }
+        last = m;
+    }
+    if (rc == DBAZ_OK && (e = replay_mark(t, mark++)) != hipSuccess) rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: %s", hipGetErrorString(e));
+    unsigned long long got[REPLAY_COUNTERS] = {0};
+    heads.assign((size_t)last, 0);
+    if (rc == DBAZ_OK) {
+        e = hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, t->stream);
+        if (e == hipSuccess && last > 0) e = hipMemcpyAsync(heads.data(), t->d0_dev, (size_t)last, hipMemcpyDeviceToHost, t->stream);
+        if (e != hipSuccess) rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets: %s", hipGetErrorString(e));
+    }
+    e = hipStreamSynchronize(t->stream); // also on a failure above: the rows are final, or the call says why not
+    if (rc == DBAZ_OK && e != hipSuccess) rc = fail(t->err, DBAZ_EDEVICE, "dbaz_replay_exact_targets failed: %s", hipGetErrorString(e));
+    if (rc != DBAZ_OK) {
+        (void)hipGetLastError();
+        return rc;
+    }
+    // the call's timeline: marks 0 1 2 bound scan and group, the host plans the chunks between marks 2 and 3, then three intervals per chunk
+    float ms[REPLAY_PHASES] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (size_t i = 0; i + 1 < mark; i++) {
+        float d = 0.0f;
+        if (i == 2 || hipEventElapsedTime(&d, rs.marks[i], rs.marks[i + 1]) != hipSuccess) continue;
+        ms[i < 2 ? i : 2 + (i - 3) % 3] += d;
+    }
+    (void)hipGetLastError();
+    if (last > 0) { // the last chunk's tables: a solved pool like any other
+        t->n_free.assign(ch.n_free.begin() + ch.chunk_first[n_chunks - 1], ch.n_free.end());
+        t->d0.assign(heads.begin(), heads.end());
+        t->solve_ms = ms[3];
+        t->n_solved = last;
+    }
+    if (stats_host) {
+        stats_host[0] = n;
+        stats_host[1] = n_games;
+        stats_host[2] = n_roots;
+        stats_host[3] = n_chunks;
+        for (int i = 0; i < 4; i++) stats_host[4 + i] = (int64_t)got[i];
+        for (int f = 0; f <= SOLVER_MAX_E; f++) stats_host[REPLAY_STATS + f] = (int64_t)got[4 + f];
+        for (int i = 0; i < REPLAY_PHASES; i++) stats_host[REPLAY_STATS + SOLVER_MAX_E + 1 + i] = (int64_t)((double)ms[i] * 1e6);
+    }
     return DBAZ_OK;
 }
 

@@ -6,13 +6,15 @@
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --deep-bench 4096 [--free 24]
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --tables-bench 64 --free 20
     python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --tails-bench 1024 --reads 20 --free 24 [--tables 64]
+    python -m dotsboxesaz_amd.endgame --rows 6 --cols 6 --replay-bench 1024 --reads 20 --free 20 --tables 64
 
 The solver's D (solver.py) depends only on which edges are still free, so a position with F free edges is a game
 over 2^F masks; one workgroup solves it in LDS (csrc/endgame.hip).  No table, no solve step.
 DeepEndgame goes further, up to 31 free edges: one root position solved into a table in HBM by the small-board solver's kernels
 (csrc/solver.hip), and the root and every position after it answered from that table; score_game_tails uses it per game.
 DeepTables is the batched form: a pool of such tables, many roots solved side by side, rows of many games answered in one launch
-(score_game_tails(tables=), game_tail_targets).  Engine(endgame=DeepTables(rows, cols, max_free=M)) puts such tables inside the
+(score_game_tails(tables=), game_tail_targets; DeepTables.replay_targets does it on packed replay rows without leaving the device:
+Coach(exact_targets=DeepTables(...))).  Engine(endgame=DeepTables(rows, cols, max_free=M)) puts such tables inside the
 search, one per engine slot (Engine.attach_endgame, dbaz_attach_tables).
 """
 import ctypes as C
@@ -376,6 +378,7 @@ DEEP_TABLES = 64  # dbaz_tables_create's default n_tables: a pool of 1 GiB at ma
 class DeepTables(_TableHandle):
     """A pool of solved tables (dbaz_tables_*): solve(roots_x) solves up to n_tables root positions side by side,
     root i into table i; score() and targets() then answer rows of many games in one launch, row r from table table_of[r].
+    replay_targets() takes packed replay rows on the device instead: roots found, solved and rows relabelled without a host copy.
     A > 256, max_free outside 1 .. 31 or n_tables outside 1 .. 65535 raises DbazError before the device is touched."""
 
     _API = "dbaz_tables"
@@ -453,6 +456,57 @@ class DeepTables(_TableHandle):
         if as_numpy:
             return pt.cpu().numpy(), zt.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
         return pt, zt, info
+
+
+    REPLAY_STATS = ("rows", "games", "roots", "chunks", "relabelled", "finished", "unserved", "z_changed")
+    REPLAY_PHASES = ("scan", "group", "geometry", "solve", "relabel")
+
+    def replay_targets(self, rows, pi_mode="restrict", z_mode=True, return_roots=False):
+        """Exact targets on packed replay rows (dbaz_replay_exact_targets): rows is a contiguous uint8 CUDA tensor [n, row_bytes]
+        on the handle's device, as self_play.collect_rows_device returns it, in any order -- anything else raises ValueError
+        before the C call.  It is relabelled IN PLACE: a caller who wants the played targets too clones first.  Per game the
+        first row by move_idx with at most max_free free edges roots one table (built and solved on the device, the games going
+        through the pool n_tables at a time); that row and every later row of an unfinished position get z = the true result
+        (z_mode) and their visits restricted to the moves that keep it ("restrict": 0 elsewhere, 1 on those moves if none was
+        visited; "uniform": 1 on them, 0 elsewhere; "keep": untouched).  Every other byte comes back as it was.
+        Returns dict(rows, games, roots, chunks, relabelled, finished, unserved, z_changed, by_free int64 [max_free + 1]:
+        relabelled rows by free edges, kernel_ms: HIP-event milliseconds of scan, group, geometry, solve, relabel); with
+        return_roots also root_of, an int32 CUDA tensor [n]: per row the index of its game's root row if the row is that root or
+        comes after it, else -1.  Afterwards the handle holds the last chunk's tables (n_solved, n_free, d0, table(), score())."""
+        import torch
+        pm, zm = target_modes(pi_mode, z_mode)
+        if pm not in (0, 1, 2) or zm not in (0, 1):
+            raise ValueError("pi_mode %r / z_mode %r" % (pi_mode, z_mode))
+        from .self_play import row_bytes
+        rb = row_bytes(self.F, self.A)
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() != 2:
+            raise ValueError("rows must be a uint8 tensor [n, row_bytes]")
+        if not rows.is_cuda or rows.device.index != self.device:
+            raise ValueError("rows must live on the handle's device cuda:%d, got %s" % (self.device, rows.device))
+        if int(rows.shape[1]) != rb:
+            raise ValueError("row_bytes %d: a packed replay row of a %dx%d board has %d" % (rows.shape[1], self.rows, self.cols, rb))
+        if not rows.is_contiguous():
+            raise ValueError("rows must be contiguous: they are relabelled in place")
+        n = int(rows.shape[0])
+        dev = rows.device
+        root_of = torch.full((n,), -1, dtype=torch.int32, device=dev) if return_roots else None
+        st = np.zeros(len(self.REPLAY_STATS) + 32 + len(self.REPLAY_PHASES), np.int64)
+        with torch.cuda.device(dev):
+            rc = self._L.dbaz_replay_exact_targets(self.h, C.c_void_p(rows.data_ptr() if n else None), C.c_int64(n), C.c_int32(rb), C.c_int32(pm),
+                                                   C.c_int32(zm), C.c_void_p(root_of.data_ptr() if return_roots and n else None),
+                                                   C.c_void_p(st.ctypes.data), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != _lib.OK:
+            self.n_solved, self.n_free, self.d0 = 0, np.zeros(0, np.int32), np.zeros(0, np.int32)
+            self._ck(rc)
+        if n:
+            self._info()
+        k = len(self.REPLAY_STATS)
+        out = {name: int(st[i]) for i, name in enumerate(self.REPLAY_STATS)}
+        out["by_free"] = st[k:k + self.max_free + 1].copy()
+        out["kernel_ms"] = {name: float(st[k + 32 + i]) * 1e-6 for i, name in enumerate(self.REPLAY_PHASES)}
+        if return_roots:
+            out["root_of"] = root_of
+        return out
 
 
 def _game_roots(game, move, n_free, max_free):
@@ -749,6 +803,60 @@ def _tails_bench(a):
     return out
 
 
+def _replay_bench(a):
+    """a.replay_bench complete self-play games (formula evaluator, a.reads reads per move), their packed rows left on the device
+    (self_play.collect_rows_device): DeepTables.replay_targets on them next to game_tail_targets(tables=) on the same rows
+    unpacked on the host, alternating in one process, a.repeats (at least 5) timed rounds after a warm-up round, the packed rows
+    restored before every round.  Per route the host wall clock around the call (median, min, max); for the device route also
+    the HIP-event time of its kernels, phase by phase.  Stops if the two routes relabel different rows or disagree on a z."""
+    import time
+    import torch
+    from . import self_play as sp
+    from .engine import Engine
+    e = Engine(a.rows, a.cols, min(a.replay_bench, 8192), mcts_num_read=a.reads, evaluator="formula", device=a.device)
+    packed0 = sp.collect_rows_device(e, a.replay_bench, 0)
+    F, A = e.F, e.A
+    e.close()
+    host0 = packed0.cpu().numpy()
+    samples = sp.unpack_rows(host0, F, A)
+    max_free = DEEP_FREE if a.free is None else a.free
+    pool = DeepTables(a.rows, a.cols, a.device, max_free, a.tables)
+    dev = packed0.device
+    packed = packed0.clone()
+    wall, phases, stats, got = dict(device=[], host=[]), [], None, None
+    for i in range(max(a.repeats, 5) + 1):
+        packed.copy_(packed0)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        stats = pool.replay_targets(packed)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        got = game_tail_targets(samples, tables=pool)
+        t2 = time.perf_counter()
+        if i:  # the first round warms up
+            wall["device"].append(t1 - t0)
+            wall["host"].append(t2 - t1)
+            phases.append(stats["kernel_ms"])
+    after = sp.unpack_rows(packed.cpu().numpy(), F, A)
+    before = sp.unpack_rows(host0, F, A)
+    changed = (after["z"] != before["z"]) | (after["visits"] != before["visits"]).any(axis=1)
+    assert stats["relabelled"] == int(got[2]["relabelled"].sum()) and not (changed & ~got[2]["relabelled"]).any(), "the two routes relabel different rows"
+    assert np.array_equal(after["z"][got[2]["relabelled"]].astype(np.float32), np.asarray(got[1]).reshape(-1)[got[2]["relabelled"]]), "z differs"
+    out = dict(rows=a.rows, cols=a.cols, games=int(a.replay_bench), reads=a.reads, max_free=pool.max_free, pool_tables=pool.n_tables, runs=len(wall["device"]),
+               sample_rows=stats["rows"], **{k: stats[k] for k in DeepTables.REPLAY_STATS[2:]})
+    for which in ("device", "host"):
+        w = np.asarray(wall[which]) * 1e3
+        out[which] = dict(wall_ms=round(float(np.median(w)), 3), wall_ms_min=round(float(w.min()), 3), wall_ms_max=round(float(w.max()), 3),
+                          rows_per_s=round(stats["rows"] / (float(np.median(w)) * 1e-3)))
+    out["device"]["kernel_ms"] = {k: round(float(np.median([p[k] for p in phases])), 4) for k in DeepTables.REPLAY_PHASES}
+    out["device"]["kernel_ms_total"] = round(float(np.median([sum(p.values()) for p in phases])), 4)
+    spread = max(out[w]["wall_ms_max"] - out[w]["wall_ms_min"] for w in ("device", "host"))
+    out["speedup"] = round(out["host"]["wall_ms"] / out["device"]["wall_ms"], 3)
+    out["device_faster"] = bool(out["host"]["wall_ms"] - out["device"]["wall_ms"] > spread)  # by more than the larger spread
+    pool.close()
+    return out
+
+
 def _bench(g, n, free):
     """HIP-event milliseconds of one dbaz_endgame_score call on n rows that all have `free` free edges, and on n rows with n_free
     uniform in 0 .. 16: outputs preallocated, median of 5 after a warm-up"""
@@ -926,7 +1034,10 @@ def main(argv=None):
     ap.add_argument("--tails-bench", type=int, default=0, metavar="N",
                     help="play N self-play games (formula evaluator, --reads) and time score_game_tails on their rows game by game and with "
                          "--tables tables, max_free = --free (default 24)")
-    ap.add_argument("--tables", type=int, default=DEEP_TABLES, help="--tails-bench: tables of the pool")
+    ap.add_argument("--tables", type=int, default=DEEP_TABLES, help="--tails-bench, --replay-bench: tables of the pool")
+    ap.add_argument("--replay-bench", type=int, default=0, metavar="N",
+                    help="play N self-play games (formula evaluator, --reads) and time DeepTables.replay_targets on their packed rows on the "
+                         "device next to game_tail_targets on the same rows on the host, max_free = --free (default 24), --tables tables")
     ap.add_argument("--selfplay-bench", type=int, default=0, metavar="N",
                     help="play N complete self-play games with a random-init ResNetZero, with and without the endgame tables attached")
     ap.add_argument("--targets-bench", type=int, default=0, metavar="N",
@@ -944,6 +1055,9 @@ def main(argv=None):
         return
     if a.tails_bench > 0:
         print(json.dumps(_tails_bench(a)))
+        return
+    if a.replay_bench > 0:
+        print(json.dumps(_replay_bench(a)))
         return
     if a.deep_bench > 0:
         a.free = DEEP_FREE if a.free is None else a.free

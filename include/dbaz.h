@@ -616,6 +616,32 @@ int dbaz_tables_targets(dbaz_tables *t, int32_t n, const int16_t *x_dev, const i
                         int32_t z_mode, float *pi_dev /*in/out [n][A]*/, float *z_dev /*in/out [n]*/, int16_t *n_free_dev,
                         float *mass_dev, uint8_t *relabelled_dev, void *stream);
 
+/* ---- deep exact targets on packed replay rows: one table per game, rows relabelled where they lie -----------------
+ * The reference has no counterpart.  rows_dev: n_rows packed replay rows (RowMeta | x int16[3*H*W] | visits int32[A], row_bytes
+ * apart and 8-byte aligned: what dbaz_replay_rows_dev hands out) on t's DEVICE, in any order.  A GAME is the rows of one game_idx;
+ * its ROOT is its first row by move_idx with at most max_free free real edges (none: the game's rows come back byte for byte).
+ * The root and every later row of the game are CANDIDATES.  The roots are solved through t's pool n_tables at a time, in the
+ * order (F descending, game_idx ascending), the geometries built on the device from the root rows; per candidate, in place:
+ *   its free real edges are no subset of its root's (dbaz_tables_score's served rule)  -> untouched, counted `unserved`
+ *   its game is over (early end included)                                             -> untouched, counted `finished`
+ *   otherwise RELABELLED: v = sign(margin + T[mask]), O = the free edges a with sign(margin + q[a]) == v, dbaz_tables_targets' set;
+ *     z_mode 1: RowMeta.z <- v;  pi_mode 2 (restrict): visits[a] <- 0 for every a outside O, sentinel slots included, and 1 on O
+ *     if the visits on O sum to 0;  pi_mode 1 (uniform): 1 on O, 0 elsewhere;  pi_mode 0: visits as they are.  Integers only.
+ * No other byte of any row changes.  The handle's stream waits for `stream`; the call returns when the rows are final.
+ * root_of_dev (may be NULL): int32 [n_rows] on the device, per row the row index of its game's root if the row is a candidate, else -1.
+ * stats_host (may be NULL): int64 [8 + 32 + 5] = rows, games, roots (tables solved), chunks, relabelled, finished, unserved,
+ *   z_changed (relabelled rows whose z was not v, whatever z_mode says); by_free[32]: relabelled rows by their own free edges;
+ *   nanoseconds of HIP-event time of the call's kernels: scan, sort + segment pass, geometry, solve, relabel.
+ * Afterwards t holds the LAST chunk's tables as after a dbaz_tables_solve of those roots (n_solved = 0 if no game has a root,
+ * and after any failure past the argument checks); solve_ms of dbaz_tables_info is then the solve time of all chunks together.
+ * One call at a time per handle; its scratch stays on the handle.
+ *   pi_mode / z_mode out of range, row_bytes not the board's, rows_dev NULL with n_rows > 0, misaligned rows, n_rows < 0
+ *                                      -> DBAZ_EINVAL before the device is touched;  n_rows == 0: DBAZ_OK, zero stats
+ *   two rows with the same (game_idx, move_idx) -> DBAZ_EINVAL, found on the device before any row is written
+ *   (Not named dbaz_tables_*: that family is the pool's own.) */
+int dbaz_replay_exact_targets(dbaz_tables *t, void *rows_dev, int64_t n_rows, int32_t row_bytes, int32_t pi_mode, int32_t z_mode,
+                              int32_t *root_of_dev /*int32 [n_rows]*/, int64_t *stats_host /*int64 [45]*/, void *stream);
+
 /* ---- deep tables inside the search: dbaz_attach_endgame's meaning for up to 31 free edges ------------------------
  * The counterpart of dbaz_attach_endgame with a dbaz_tables: once a search root of a slot has F0 <= max_free free edges, the
  * engine solves that root's subgame once per game into the slot's region in HBM and answers every later leaf and root of the game
