@@ -31,7 +31,7 @@ struct EndgameGeo {
 struct EndgameReq {
     uint64_t free_edges[4]; // the root's free real edges by action index
     int64_t game;           // Slot::game_idx
-    int32_t want;           // 1: a search has started; cleared by k_endgame_table
+    int32_t want;           // 1: a search has started; 2 (pooled deep attach only): the game is over, its region goes back; cleared by the pass
     int32_t model;          // the model that searches (its pick seed serves the leaves)
 };
 
@@ -41,7 +41,9 @@ struct EndgameSlotHdr {
     uint64_t free_edges[4];
     int64_t game;                            // validity stamp: the slot's game when the table was solved
     int32_t valid, F0;
-    int32_t model, pad;
+    int32_t model;
+    int32_t table;                           // the region of `tables` that holds it: the slot's own (k_endgame_table, dbaz_attach_tables),
+                                             // or one of the engine's pool (dbaz_attach_tables_pool; -1 there: the slot holds none)
     // sized for the deep attach (dbaz_attach_tables, k_slot_requests in solver.hip): k_endgame_table fills 16 entries at the most
     uint32_t other[SOLVER_MAX_E][2];         // solver_move_q's box masks over the compact edges
     uint8_t act[SOLVER_MAX_E];               // compact edge -> action index
@@ -82,9 +84,9 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
 // The slot tables as an evaluator, whoever solved them (k_endgame_table, or solver.hip's slot_tables_pass): k_endgame_eval with
 // nn_forward's contract on rows of T = float (TreeBufs.feat planes) or int16 -- rows x[list[j]], j < *n_dev <= max_n, of slot
 // list[j] / per_slot, to P[list[j] * AS + a] and V[list[j]]; seeds: the pick seed of each model.  No header claims more than
-// max_free compact edges; a slot's region is tab_stride >= 2^max_free bytes.
+// max_free compact edges; a header's table is region EndgameSlotHdr::table of the n_tables regions of tab_stride >= 2^max_free bytes.
 template <typename T>
-void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables,
+void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, int n_tables, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables,
                      const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
                      float *V, int AS, unsigned long long *stats);
 

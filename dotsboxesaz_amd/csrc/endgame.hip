@@ -292,6 +292,7 @@ __global__ void __launch_bounds__(ENDGAME_THREADS) k_endgame_table(EndgameGeo g,
         for (int w = 0; w < 4; w++) h->free_edges[w] = me.free_edges[w];
         h->game = game;
         h->F0 = F;
+        h->table = (int32_t)slot;
         h->valid = 1;
         atomicAdd(stats, 1ull);
     }
@@ -325,7 +326,7 @@ __global__ void k_endgame_requests(EndgameGeo g, const int16_t *__restrict__ x, 
 #define ENDGAME_EVAL_WAVES 4
 template <typename T>
 __global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(TablesBoard B, int max_free, const EndgameSlotHdr *__restrict__ hdr,
-                                                                          const int8_t *__restrict__ tables, size_t tab_stride,
+                                                                          const int8_t *__restrict__ tables, size_t tab_stride, int n_tables,
                                                                           const T *__restrict__ x, const int32_t *__restrict__ list,
                                                                           const int32_t *__restrict__ n_dev, int max_n, int per_slot,
                                                                           uint64_t seed0, uint64_t seed1, float *__restrict__ P,
@@ -340,12 +341,14 @@ __global__ void __launch_bounds__(64 * ENDGAME_EVAL_WAVES) k_endgame_eval(Tables
         const size_t slot = (size_t)(r / per_slot);
         const EndgameSlotHdr *h = hdr + slot;
         float *pr = P + (size_t)r * stride;
-        if (!h->valid) { // no table (the engine never lists such a leaf; dbaz_exact_policy_from: a root with F > max_free)
+        const int table = h->table;
+        // no table (the engine never lists such a leaf; dbaz_exact_policy_from: a root with F > max_free), and never outside the regions
+        if (!h->valid || (unsigned)table >= (unsigned)n_tables) {
             for (int i = lane; i < stride; i += 64) pr[i] = 0.0f;
             if (lane == 0) V[r] = 0.0f;
             continue;
         }
-        const int8_t *Tb = tables + slot * tab_stride;
+        const int8_t *Tb = tables + (size_t)table * tab_stride;
         const TableRow d = table_row<false>(B, *h, min(h->F0, max_free), Tb, x + (size_t)r * 3 * B.HW, lane);
         const int pick = endgame_pick(d.cand, d.q, d.a, h->model ? seed1 : seed0);
         for (int i = lane; i < stride; i += 64) pr[i] = i == pick ? 1.0f : 0.0f;
@@ -689,15 +692,15 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
 }
 
 template <typename T>
-void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, hipStream_t stream, const EndgameSlotHdr *hdr, const int8_t *tables,
-                     const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
+void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, int n_tables, hipStream_t stream, const EndgameSlotHdr *hdr,
+                     const int8_t *tables, const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
                      float *V, int AS, unsigned long long *stats)
 {
     const int blocks = std::min((max_n + ENDGAME_EVAL_WAVES - 1) / ENDGAME_EVAL_WAVES, 4096);
-    k_endgame_eval<T><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(tables_board(rows, cols), max_free, hdr, tables, tab_stride, x, list_dev, n_dev,
-                                                                    max_n, per_slot, seed0, seed1, P, V, AS, stats);
+    k_endgame_eval<T><<<blocks, 64 * ENDGAME_EVAL_WAVES, 0, stream>>>(tables_board(rows, cols), max_free, hdr, tables, tab_stride, n_tables, x, list_dev,
+                                                                    n_dev, max_n, per_slot, seed0, seed1, P, V, AS, stats);
 }
-template void endgame_forward<float>(int, int, int, size_t, hipStream_t, const EndgameSlotHdr *, const int8_t *, const float *, const int32_t *,
+template void endgame_forward<float>(int, int, int, size_t, int, hipStream_t, const EndgameSlotHdr *, const int8_t *, const float *, const int32_t *,
                                      const int32_t *, int, int, uint64_t, uint64_t, float *, float *, int, unsigned long long *); // the engine's
 
 // The table path on its own: the yardstick of k_endgame_table / k_endgame_eval against dbaz_exact_policy, the int16 form of the
@@ -732,7 +735,7 @@ extern "C" int dbaz_exact_policy_from(dbaz_endgame *g, int32_t n_roots, const in
         e = hipEventRecord(ev[1], s);
     }
     if (e == hipSuccess) {
-        endgame_forward<int16_t>(g->g.rows, g->g.cols, g->g.max_free, stride, s, (const EndgameSlotHdr *)buf[1], (const int8_t *)buf[0], x_dev, nullptr,
+        endgame_forward<int16_t>(g->g.rows, g->g.cols, g->g.max_free, stride, n_roots, s, (const EndgameSlotHdr *)buf[1], (const int8_t *)buf[0], x_dev, nullptr,
                                  nullptr, n_roots * per_root, per_root, pick_seed, pick_seed, p_dev, v_dev, g->g.A, nullptr);
         e = hipEventRecord(ev[2], s);
     }

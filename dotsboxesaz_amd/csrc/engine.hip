@@ -55,6 +55,8 @@ struct dbaz_engine {
     // of one kind.  Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own
     bool eg_deep = false;
     SlotTables slot_tables = SlotTables();
+    // dbaz_attach_tables_pool: eg_tables is eg_n_tables regions that the slots share (0: one region per slot, region == slot)
+    int eg_n_tables = 0;
     // staging (device) for the boundary
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -653,7 +655,7 @@ static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
 static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
 {
     if (e->eg_tables)
-        endgame_forward<float>(e->g.rows, e->g.cols, e->eg_max_free, e->eg_stride, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3,
+        endgame_forward<float>(e->g.rows, e->g.cols, e->eg_max_free, e->eg_stride, e->eg_n_tables ? e->eg_n_tables : e->n_slots, s, e->eg_hdr, e->eg_tables, feat, e->G.list, e->B.n_eval + 3,
                                e->n_slots * per_slot, per_slot, e->endgame_seed[0], e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
 }
 
@@ -663,6 +665,10 @@ static int endgame_drop_tables(dbaz_engine *e)
     if (e->eg_hdr) {
         HIP_CHECK_RET(e, hipMemsetAsync(e->eg_hdr, 0, sizeof(EndgameSlotHdr) * (size_t)e->n_slots, e->stream));
         HIP_CHECK_RET(e, hipMemsetAsync(e->eg_start.req, 0, sizeof(EndgameReq) * (size_t)e->n_slots, e->stream));
+        if (e->eg_n_tables) { // and every region goes back to the pool
+            slot_tables_pool_reset(&e->slot_tables, e->stream, e->eg_hdr, e->n_slots);
+            HIP_CHECK_RET(e, hipGetLastError());
+        }
     }
     return DBAZ_OK;
 }
@@ -858,12 +864,12 @@ extern "C" int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s,
     return DBAZ_OK;
 }
 
-// the slot tables of either kind of attach: n_slots x stride bytes, plus headers, requests, the leaf list and the counters; nothing
+// the slot tables of either kind of attach: n_regions x stride bytes, plus headers, requests, the leaf list and the counters; nothing
 // is kept when one allocation fails (*err)
-static bool endgame_alloc_slots(dbaz_engine *e, size_t stride, void *p[6], hipError_t *err)
+static bool endgame_alloc_slots(dbaz_engine *e, size_t n_regions, size_t stride, void *p[6], hipError_t *err)
 {
     const size_t ns = e->n_slots;
-    const size_t bytes[6] = {ns * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4, ns * (size_t)e->B.kmax * 4, 16};
+    const size_t bytes[6] = {n_regions * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4, ns * (size_t)e->B.kmax * 4, 16};
     for (int i = 0; i < 6; i++) p[i] = nullptr;
     *err = hipStreamSynchronize(e->stream);
     for (int i = 0; i < 6 && *err == hipSuccess; i++) {
@@ -894,9 +900,10 @@ static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
 // What both attach entries do once their handle is resolved: `kind` names the handle's type and entry in messages, stride is the
 // bytes of a slot's region (at least 2^max_free), deep the dbaz_tables whose passes solve the slots (nullptr: a dbaz_endgame's
 // k_endgame_table does).  A handle's attaches are all of one kind and one stride: the slot regions are sized by the first attach
-// and never resized.  A refused attach changes nothing.
-static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, dbaz_tables *deep, int max_free, size_t stride, uint64_t pick_seed,
-                              int32_t endgame_reads)
+// and never resized.  n_tables > 0: the pooled form of the deep attach, that many regions shared by the slots -- a kind of its
+// own, with one n_tables per handle.  A refused attach changes nothing.
+static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, dbaz_tables *deep, int n_tables, int max_free, size_t stride,
+                              uint64_t pick_seed, int32_t endgame_reads)
 {
     if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
     const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
@@ -906,6 +913,16 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
     if (e->eg_tables && (deep != nullptr) != e->eg_deep)
         return set_error(e, DBAZ_EINVAL, "a %s: this handle's slot tables belong to a %s (max_free %d): a handle's attaches are all of one kind", kind,
                          e->eg_deep ? "dbaz_tables" : "dbaz_endgame", e->eg_max_free);
+    if (e->eg_tables && (n_tables > 0) != (e->eg_n_tables > 0))
+        return set_error(e, DBAZ_EINVAL, "a %s: this handle's slot tables are %s: a handle's attaches are all of one kind", kind,
+                         e->eg_n_tables ? "a pool shared by the slots (dbaz_attach_tables_pool)" : "one region per slot (dbaz_attach_tables)");
+    if (e->eg_tables && n_tables != e->eg_n_tables)
+        return set_error(e, DBAZ_EINVAL, "n_tables %d: this handle's pool has %d regions (the n_tables of its first attach)", n_tables, e->eg_n_tables);
+    // begin_search caps the reads before the pass knows whether the slot gets a region: a denied search would run on the model's
+    // evaluator with a handful of reads
+    if (n_tables > 0 && endgame_reads > 0)
+        return set_error(e, DBAZ_EINVAL, "endgame_reads %d: the pooled attach takes no read cap (a slot that is denied a table searches with its "
+                         "model's evaluator)", endgame_reads);
     if (e->eg_tables && stride != e->eg_stride)
         return set_error(e, DBAZ_EINVAL, "max_free %d: this handle's slot tables hold %zu bytes each (the max_free of its first attach); every later "
                          "attach, for either model, needs the same max_free", max_free, e->eg_stride);
@@ -918,22 +935,30 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
         HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
     } else {
         SlotTables st = SlotTables();
-        void *lists[4] = {nullptr, nullptr, nullptr, nullptr};
+        void *lists[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (deep)
-            if (int rc = slot_tables_setup(deep, e->n_slots, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
+            if (int rc = slot_tables_setup(deep, e->n_slots, n_tables, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
         void *p[6];
         hipError_t err = hipSuccess;
-        if (!endgame_alloc_slots(e, stride, p, &err)) {
+        const int n_regions = n_tables > 0 ? n_tables : e->n_slots;
+        if (!endgame_alloc_slots(e, (size_t)n_regions, stride, p, &err)) {
             for (void *q : lists)
                 if (q) (void)hipFree(q);
-            return set_error(e, DBAZ_EDEVICE, "slot tables of %d slots x %zu bytes = %llu bytes: %s", e->n_slots, stride,
-                             (unsigned long long)e->n_slots * stride, hipGetErrorString(err)); // 64 bits: 8192 slots x 2^20 is past 32
+            return set_error(e, DBAZ_EDEVICE, "slot tables of %d %s x %zu bytes = %llu bytes: %s", n_regions, n_tables > 0 ? "pooled regions" : "slots",
+                             stride, (unsigned long long)n_regions * stride, hipGetErrorString(err)); // 64 bits: 8192 slots x 2^20 is past 32
         }
         endgame_keep_slots(e, stride, p);
         for (void *q : lists)
             if (q) e->allocs.push_back(q);
         e->slot_tables = st;
         e->eg_deep = deep != nullptr;
+        e->eg_n_tables = n_tables;
+        e->eg_start.release = n_tables > 0 ? 1 : 0;
+        if (n_tables > 0) { // no header names a region yet
+            slot_tables_pool_reset(&e->slot_tables, e->stream, e->eg_hdr, e->n_slots);
+            HIP_CHECK_RET(e, hipGetLastError());
+            HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        }
     }
     e->eg_max_free = std::max(e->eg_max_free, max_free);
     e->endgame_seed[model] = pick_seed;
@@ -952,7 +977,7 @@ extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *
     if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
         return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
                          e->g.cols, e->cfg.device);
-    if (int r = attach_slot_tables(e, model, "dbaz_endgame", nullptr, max_free, endgame_table_stride(g), pick_seed, endgame_reads)) return r;
+    if (int r = attach_slot_tables(e, model, "dbaz_endgame", nullptr, 0, max_free, endgame_table_stride(g), pick_seed, endgame_reads)) return r;
     e->endgame[model] = g;
     return DBAZ_OK;
 }
@@ -967,7 +992,63 @@ extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t,
     if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
         return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
                          e->cfg.device);
-    return attach_slot_tables(e, model, "dbaz_tables", t, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
+    return attach_slot_tables(e, model, "dbaz_tables", t, 0, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
+}
+
+// The same with n_tables regions that the slots share (table_pool.h, slot_tables_pass): both models of a match draw on one pool.
+extern "C" int dbaz_attach_tables_pool(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
+    if (n_tables < 1 || n_tables > e->n_slots)
+        return set_error(e, DBAZ_EINVAL, "n_tables %d: a pool has 1 .. n_slots = %d regions", n_tables, e->n_slots);
+    int max_free = 0;
+    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
+                         e->cfg.device);
+    return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
+}
+
+extern "C" int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *in_use, int32_t *high_water, int64_t *denied)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    int32_t use = 0, high = 0;
+    int64_t den = 0;
+    if (e->eg_n_tables) {
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        HIP_CHECK_RET(e, slot_tables_pool_read(&e->slot_tables, &use, &high, &den));
+    }
+    if (n_tables) *n_tables = e->eg_n_tables;
+    if (in_use) *in_use = use;
+    if (high_water) *high_water = high;
+    if (denied) *denied = den;
+    return DBAZ_OK;
+}
+
+// the header of a slot after the queued work; *table: the region it names (-1: a pooled slot that holds none)
+static int read_slot_hdr(dbaz_engine *e, int32_t slot, EndgameSlotHdr *h, int32_t *table)
+{
+    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    HIP_CHECK_RET(e, hipMemcpy(h, e->eg_hdr + slot, sizeof *h, hipMemcpyDeviceToHost));
+    *table = e->eg_n_tables ? (h->table >= 0 && h->table < e->eg_n_tables ? h->table : -1) : slot;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_slot_table_index(dbaz_engine *e, int32_t slot, int32_t *table)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!e->eg_tables) return set_error(e, DBAZ_EINVAL, "dbaz_get_slot_table_index: no endgame solver or deep tables attached to this handle");
+    if (slot < 0 || slot >= e->n_slots) return set_error(e, DBAZ_EINVAL, "slot %d: this handle has slots 0 .. %d", slot, e->n_slots - 1);
+    EndgameSlotHdr h;
+    int32_t at = -1;
+    if (int r = read_slot_hdr(e, slot, &h, &at)) return r;
+    if (table) *table = at;
+    return DBAZ_OK;
 }
 
 extern "C" int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid, int32_t *n_free, int64_t *game, uint64_t free_edges[4],
@@ -980,16 +1061,16 @@ extern "C" int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid,
     const int64_t n = (int64_t)e->eg_stride;
     if (first < 0 || count < 0 || first > n || count > n - first || (count > 0 && !host_dst))
         return set_error(e, DBAZ_EINVAL, "table slice [%lld, +%lld) outside [0, %lld)", (long long)first, (long long)count, (long long)n);
-    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
     EndgameSlotHdr h;
-    HIP_CHECK_RET(e, hipMemcpy(&h, e->eg_hdr + slot, sizeof h, hipMemcpyDeviceToHost));
+    int32_t table = -1;
+    if (int r = read_slot_hdr(e, slot, &h, &table)) return r;
+    if (count > 0 && table < 0) return set_error(e, DBAZ_EINVAL, "slot %d holds no region of the pool: it has no table to read", slot);
     if (valid) *valid = h.valid;
     if (n_free) *n_free = h.F0;
     if (game) *game = h.game;
     if (free_edges)
         for (int w = 0; w < 4; w++) free_edges[w] = h.free_edges[w];
-    if (count > 0) HIP_CHECK_RET(e, hipMemcpy(host_dst, e->eg_tables + (size_t)slot * e->eg_stride + (size_t)first, (size_t)count, hipMemcpyDeviceToHost));
+    if (count > 0) HIP_CHECK_RET(e, hipMemcpy(host_dst, e->eg_tables + (size_t)table * e->eg_stride + (size_t)first, (size_t)count, hipMemcpyDeviceToHost));
     return DBAZ_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "replay_row.h"
 #include "slot_tables_plan.h"
 #include "solver.h"
+#include "table_pool.h"
 #include "table_row.h"
 
 // One root's solve geometry as the two solving kernels read it from HBM: what the bodies need of a SolverGeo, and the table slot
@@ -1446,6 +1447,8 @@ extern "C" int dbaz_deep_policy(dbaz_deep *d, int32_t n, const int16_t *x_dev, u
 // A pass is k_slot_requests and then S launches of k_slot_solve on one stream (slot_tables_plan.h); stream order is the only
 // synchronisation between them.  The pass's roots go on a device list with one atomic each, and the counter of the NEXT pass is
 // zeroed by this one (two counters, used in turn), so the host neither resets nor reads anything.
+// The pooled form (dbaz_attach_tables_pool, table_pool.h) puts k_pool_decide and k_pool_grant in front: the slots share n_tables
+// regions, given back and granted on the device; the per-slot form launches neither.
 static_assert(sizeof(SlotTablesPlan().widest) == sizeof(SlotTables().widest), "solver.h restates slot_tables_plan.h");
 
 // what k_slot_solve needs to know about roots of one F
@@ -1472,7 +1475,10 @@ static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, 
 // Step 1 of a pass, one wavefront per slot with a request (a slot without one costs one word read): slot_request_rule
 // (endgame.h) keeps or drops the table, or the slot gets a new header -- F0, the free-edge set, act and `other` as
 // position_geometry builds them, the real edges and box neighbours from the board alone -- and its BatchGeo goes on the pass's list.  Lane l looks at action slots l, 64 + l, ...; a free one writes its compact edge's entries.
+// POOLED (dbaz_attach_tables_pool): k_pool_decide and k_pool_grant have run, so every request still standing is a solve, into the
+// region the header names; a slot whose header names none was denied, and its header stays invalid.
 #define SLOT_REQ_WAVES 4
+template <bool POOLED>
 __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
                                                                        EndgameSlotHdr *__restrict__ hdr, int n_slots, BatchGeo *__restrict__ geo,
                                                                        uint32_t *__restrict__ count, uint32_t *__restrict__ count_next,
@@ -1498,6 +1504,8 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
             if (!d.keep && !d.solve) h->valid = 0;
         }
         if (!d.solve) continue;
+        const int table = POOLED ? h->table : slot;
+        if (POOLED && table < 0) continue; // denied: the leaves of this search go to the model's own evaluator
 
         uint32_t at = 0;
         if (lane == 0) at = atomicAdd(count, 1u);
@@ -1531,21 +1539,112 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
         }
         if (lane == 0) {
             bg->F = F;
-            bg->slot = slot;
+            bg->slot = table;
             for (int w = 0; w < 4; w++) h->free_edges[w] = fe[w];
             h->game = game;
             h->F0 = F;
+            if (!POOLED) h->table = table;
             h->valid = 1; // the table is complete before anything later on this stream reads it
             atomicAdd(stats, 1ull);
         }
     }
 }
 
+// ---- the pooled form (table_pool.h): two light kernels in front of k_slot_requests ----
+// k_pool_decide, one wavefront per slot with a request: slot_request_rule as above.  A keep is finished here; a drop and a release
+// request (EndgameReq::want == 2, left by the driver when the slot's game ended) invalidate the header and push the slot's region
+// back on the free stack -- the position comes from one atomic, so the stack's order is not reproducible, which changes no
+// result; a solve stays standing for k_slot_requests, and ask[slot] says whether the slot needs a region for it.
+__global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_pool_decide(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
+                                                                     EndgameSlotHdr *__restrict__ hdr, int n_slots, TablePoolState *__restrict__ pool,
+                                                                     int32_t *__restrict__ stack, uint8_t *__restrict__ ask)
+{
+    const int lane = threadIdx.x & 63;
+    const int n_tables = pool->n_tables; // never written after the attach
+    for (int slot = blockIdx.x * SLOT_REQ_WAVES + (threadIdx.x >> 6); slot < n_slots; slot += gridDim.x * SLOT_REQ_WAVES) {
+        EndgameReq *rq = req + slot;
+        EndgameSlotHdr *h = hdr + slot;
+        const int want = *(volatile const int32_t *)&rq->want; // the same answer in every lane: nobody has written yet
+        if (!want) {
+            if (lane == 0) ask[slot] = 0;
+            continue;
+        }
+        uint64_t fe[4];
+#pragma unroll
+        for (int w = 0; w < 4; w++) fe[w] = rq->free_edges[w] & __ballot(board_real_edge(B, w * 64 + lane));
+        const int held = h->table;
+        SlotDecision d = slot_request_rule(fe, h->valid, h->game, h->free_edges, rq->game, max_free);
+        if (want == 2) d.keep = d.solve = false; // the game is over, whichever it was: no later search of this slot is served by it
+        const int model = rq->model;
+        if (lane == 0) {
+            ask[slot] = d.solve && held < 0 ? 1 : 0;
+            if (!d.solve) rq->want = 0;
+            if (d.keep) h->model = model;
+            if (!d.keep && !d.solve) {
+                h->valid = 0;
+                h->table = -1;
+                if ((unsigned)held < (unsigned)n_tables) {
+                    const int at = atomicAdd(&pool->top, 1);
+                    if ((unsigned)at < (unsigned)n_tables) stack[at] = held; // every region is held or on the stack, never both
+                }
+            }
+        }
+    }
+}
+
+// k_pool_grant, ONE workgroup: the asking slots in ascending slot order, TABLE_POOL_GROUP of them per round, take the free regions
+// from the top of the stack (table_pool_grant) as long as they last; then the pool's figures are settled.
+__global__ void __launch_bounds__(TABLE_POOL_GROUP) k_pool_grant(EndgameSlotHdr *__restrict__ hdr, int n_slots, TablePoolState *__restrict__ pool,
+                                                                 const int32_t *__restrict__ stack, const uint8_t *__restrict__ ask)
+{
+    __shared__ int s_wave[TABLE_POOL_GROUP / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n_tables = pool->n_tables;
+    const int n_free = min(max(pool->top, 0), n_tables);
+    long long base = 0; // asking slots of the rounds before
+    for (int g0 = 0; g0 < n_slots; g0 += TABLE_POOL_GROUP) {
+        const int slot = g0 + t;
+        const bool asks = slot < n_slots && ask[slot] != 0;
+        const unsigned long long b = __ballot(asks);
+        if (lane == 0) s_wave[wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < TABLE_POOL_GROUP / 64; w++) {
+            const int c = s_wave[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (asks) {
+            const int pos = table_pool_grant(n_free, base + before + __popcll(b & ((1ull << lane) - 1ull)));
+            if (pos >= 0) hdr[slot].table = stack[pos];
+        }
+        base += total;
+        __syncthreads(); // s_wave is written again
+    }
+    if (t == 0) {
+        TablePoolState s = *pool;
+        s.top = n_free;
+        table_pool_settle(s, base);
+        *pool = s;
+    }
+}
+
+// a clear-all point: every region free, no header names one (the headers have just been zeroed on this stream)
+__global__ void __launch_bounds__(256) k_pool_reset(EndgameSlotHdr *__restrict__ hdr, int n_slots, TablePoolState *__restrict__ pool,
+                                                    int32_t *__restrict__ stack, int n_tables)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_slots) hdr[i].table = -1;
+    if (i < n_tables) stack[i] = table_pool_initial(n_tables, i);
+    if (i == 0) pool->top = n_tables;
+}
+
 // Launch s of a pass: for every listed root its own layer k = top(F) - s (k < 0: the root is finished).  The fixed grid strides
 // over (root, work item) pairs, `width` items per root -- the widest layer any F <= max_free has in this launch; an item the
 // root's layer does not have is skipped.  Every condition in the loop is the same for the whole workgroup.
 __global__ void __launch_bounds__(SOLVER_THREADS) k_slot_solve(const BatchGeo *__restrict__ geo, const uint32_t *__restrict__ count, int n_slots,
-                                                               int8_t *T, int stride_bits, const SlotDepthDev *__restrict__ depth, int max_free,
+                                                               int n_tables, int8_t *T, int stride_bits, const SlotDepthDev *__restrict__ depth, int max_free,
                                                                int s, uint32_t width)
 {
     const uint32_t n = min(*count, (uint32_t)n_slots);
@@ -1553,7 +1652,7 @@ __global__ void __launch_bounds__(SOLVER_THREADS) k_slot_solve(const BatchGeo *_
     for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
         const BatchGeo &g = geo[w / width];
         const uint32_t item = (uint32_t)(w % width);
-        if ((unsigned)g.F > (unsigned)max_free || (unsigned)g.slot >= (unsigned)n_slots) continue; // never outside the slot regions
+        if ((unsigned)g.F > (unsigned)max_free || (unsigned)g.slot >= (unsigned)n_tables) continue; // never outside the regions
         const SlotDepthDev &d = depth[g.F];
         const int k = d.top - s;
         if (k < 0) continue;
@@ -1575,7 +1674,7 @@ bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *ma
     return t->board.rows == rows && t->board.cols == cols && t->dev == device;
 }
 
-int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[4])
+int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st, void *allocs[6])
 {
     SlotTablesPlan plan;
     if (slot_tables_plan(t->max_free, plan) != 0) return fail(t->err, DBAZ_EINVAL, "slot tables: max_free %d is outside 0 .. %d", t->max_free, SOLVER_MAX_E);
@@ -1613,17 +1712,29 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[
         }
     }
     const size_t word_bytes = (words.size() * 4 + 15) / 16 * 16;
-    void *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    const char *what[4] = {"the per-depth table", "the root list", "the counters", "the work lists"};
-    const size_t bytes[4] = {sizeof depth, std::max<size_t>(1, (size_t)n_slots) * sizeof(BatchGeo), 2 * sizeof(uint32_t),
-                             std::max<size_t>(16, word_bytes + halves.size() * 2)};
+    // the pooled form besides: the pool's figures with the free stack behind them, and the asking flags of a pass
+    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const char *what[6] = {"the per-depth table", "the root list", "the counters", "the work lists", "the pool's free stack", "the asking flags"};
+    const size_t bytes[6] = {sizeof depth, std::max<size_t>(1, (size_t)n_slots) * sizeof(BatchGeo), 2 * sizeof(uint32_t),
+                             std::max<size_t>(16, word_bytes + halves.size() * 2), sizeof(TablePoolState) + (size_t)n_tables * sizeof(int32_t),
+                             std::max<size_t>(16, (size_t)n_slots)};
+    const int n_bufs = n_tables > 0 ? 6 : 4;
     hipError_t e = hipSuccess;
     int failed = 0;
-    for (int i = 0; i < 4 && e == hipSuccess; i++) {
+    for (int i = 0; i < n_bufs && e == hipSuccess; i++) {
         failed = i;
         e = hipMalloc(&p[i], bytes[i]);
         if (e != hipSuccess) p[i] = nullptr;
-        else if (i == 1 || i == 2) e = hipMemset(p[i], 0, bytes[i]);
+        else if (i == 1 || i == 2 || i >= 4) e = hipMemset(p[i], 0, bytes[i]);
+    }
+    if (e == hipSuccess && n_tables > 0) { // all free; the headers get their -1 from slot_tables_pool_reset
+        failed = 4;
+        TablePoolState ps = TablePoolState();
+        ps.n_tables = ps.top = n_tables;
+        std::vector<int32_t> stack((size_t)n_tables);
+        for (int i = 0; i < n_tables; i++) stack[(size_t)i] = table_pool_initial(n_tables, i);
+        e = hipMemcpy(p[4], &ps, sizeof ps, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy((char *)p[4] + sizeof ps, stack.data(), stack.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess) {
         failed = 3;
@@ -1656,7 +1767,10 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, SlotTables *st, void *allocs[
     st->geo_dev = p[1];
     st->count_dev = (uint32_t *)p[2];
     st->pass = 0;
-    for (int i = 0; i < 4; i++) allocs[i] = p[i];
+    st->n_tables = n_tables;
+    st->pool_dev = p[4];
+    st->ask_dev = (uint8_t *)p[5];
+    for (int i = 0; i < 6; i++) allocs[i] = p[i];
     return DBAZ_OK;
 }
 
@@ -1667,11 +1781,39 @@ void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, Endga
     uint32_t *count = st->count_dev + (st->pass & 1u), *count_next = st->count_dev + ((st->pass + 1u) & 1u);
     st->pass++;
     const int blocks = std::min((n_slots + SLOT_REQ_WAVES - 1) / SLOT_REQ_WAVES, 1024);
-    k_slot_requests<<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next, stats);
+    const int n_regions = st->n_tables > 0 ? st->n_tables : n_slots;
+    if (st->n_tables > 0) { // releases, then grants in slot order, then the headers of the slots that hold a region
+        TablePoolState *pool = (TablePoolState *)st->pool_dev;
+        int32_t *stack = (int32_t *)(pool + 1);
+        k_pool_decide<<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, pool, stack, st->ask_dev);
+        k_pool_grant<<<1, TABLE_POOL_GROUP, 0, stream>>>(hdr, n_slots, pool, stack, st->ask_dev);
+        k_slot_requests<true><<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next,
+                                                                          stats);
+    } else {
+        k_slot_requests<false><<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next,
+                                                                           stats);
+    }
     for (int s = 0; s < st->n_launches; s++) {
         // never more workgroups than (root, item) pairs the launch can have
-        const unsigned grid = (unsigned)std::min<uint64_t>(SLOT_TABLES_GRID, (uint64_t)std::max(n_slots, 1) * st->widest[s]);
-        k_slot_solve<<<grid, SOLVER_THREADS, st->lds_bytes, stream>>>((const BatchGeo *)st->geo_dev, count, n_slots, tables, st->max_free,
+        const unsigned grid = (unsigned)std::min<uint64_t>(SLOT_TABLES_GRID, (uint64_t)std::max(std::min(n_slots, n_regions), 1) * st->widest[s]);
+        k_slot_solve<<<grid, SOLVER_THREADS, st->lds_bytes, stream>>>((const BatchGeo *)st->geo_dev, count, n_slots, n_regions, tables, st->max_free,
                                                                   (const SlotDepthDev *)st->depth_dev, st->max_free, s, st->widest[s]);
     }
+}
+
+void slot_tables_pool_reset(SlotTables *st, hipStream_t stream, EndgameSlotHdr *hdr, int n_slots)
+{
+    if (st->n_tables <= 0) return;
+    TablePoolState *pool = (TablePoolState *)st->pool_dev;
+    k_pool_reset<<<(std::max(n_slots, st->n_tables) + 255) / 256, 256, 0, stream>>>(hdr, n_slots, pool, (int32_t *)(pool + 1), st->n_tables);
+}
+
+hipError_t slot_tables_pool_read(const SlotTables *st, int32_t *in_use, int32_t *high_water, int64_t *denied)
+{
+    TablePoolState ps = TablePoolState();
+    hipError_t e = st->n_tables > 0 ? hipMemcpy(&ps, st->pool_dev, sizeof ps, hipMemcpyDeviceToHost) : hipSuccess;
+    *in_use = ps.n_tables - ps.top;
+    *high_water = ps.high_water;
+    *denied = ps.denied;
+    return e;
 }

@@ -30,6 +30,7 @@ struct ReadCaps {
 struct EndgameStart {
     EndgameReq *req; // [n_slots]
     int32_t max_free[2];
+    int32_t release; // 1 (dbaz_attach_tables_pool): a game that ends leaves a release request (EndgameReq::want = 2) for its slot's region
 };
 
 // the arguments of the kernels that start searches (k_search_begin, k_selfplay_start, k_advance_auto), next to the configuration

@@ -450,12 +450,23 @@ __device__ __forceinline__ int rule_num_reads(const Geo &g, const SearchCfg &cfg
     return f < (double)cfg.mcts_num_read ? (int)f : cfg.mcts_num_read;
 }
 
+// The slot's game is over.  With a pool of tables shared by the slots (EndgameStart::release) the region it holds goes back in
+// the pass that follows on this stream, whether or not the slot starts another game.
+__device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, const Slot *S, int lane)
+{
+    if (sa.eg.release && lane == 0) {
+        sa.eg.req[slot].game = S->game_idx;
+        sa.eg.req[slot].want = 2;
+    }
+}
+
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
 __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                              uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
     if (rm.flags & NF_TERMINAL) { // play_game never searches a terminal root
+        endgame_release(sa, slot, S, lane);
         S->sims_left = 0;
         set_phase_stamped(S, PH_IDLE, cfg.step);
         return;
@@ -1699,7 +1710,8 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
     S->move_idx = ply + 1;
     if (lane == 0) atomicAdd((unsigned long long *)B.moves_played, 1ull);
     NodeMeta nm = load_meta(pool, g, S->root);
-    if (nm.flags & NF_TERMINAL) {
+    if (nm.flags & NF_TERMINAL) { // (the self-play driver never reaches begin_search's terminal branch: the game ends here)
+        endgame_release(sa, slot, S, lane);
         const bool emitted = try_emit(g, B, slot, S, pool, lane);
         if (lane == 0)
             S->phase = emitted ? PH_NEWGAME : PH_EMIT;

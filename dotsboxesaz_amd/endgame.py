@@ -960,16 +960,18 @@ def _selfplay_bench(a):
     """n complete self-play games with a random-init ResNetZero (noise, tree reuse: bench.py --full-games' engine), once without
     and once with the endgame tables attached: games/s, network evaluations per game, tables solved.  Each figure is the median
     of a.repeats runs after one warm-up run.  --max-free M > 16: three engines -- plain, Endgame(16) and DeepTables(max_free=M)
-    attached -- each with the table_bytes of its slot tables."""
+    attached -- each with the table_bytes of its slot tables.  --pool N adds a fourth, DeepTables(max_free=M) with a pool of N tables
+    shared by the slots (Engine(endgame_tables=N)): its high_water, denied and the pool's table_bytes.  deep=0 with --pool leaves
+    the per-slot deep engine out (its n_slots << M bytes may not fit where the pool does)."""
     import sys
     import time
     import torch
     from . import nn as dnn
     from .engine import Engine
 
-    def play(g):
+    def play(g, pool=None):
         eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=a.reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
-                     device=a.device, endgame=g, endgame_reads=a.endgame_reads)
+                     device=a.device, endgame=g, endgame_reads=a.endgame_reads, endgame_tables=pool)
         torch.manual_seed(0)
         model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
         eng.load_state_dict(model.state_dict(), "resnet", **model.shape)
@@ -983,25 +985,37 @@ def _selfplay_bench(a):
             n_rows = len(eng.fetch_samples()["z"])
             dt = time.perf_counter() - t0
             c = eng.counters()
-            print("selfplay-bench: %s run %d of %d, %.1f s" % (type(g).__name__, i, a.repeats, dt), file=sys.stderr, flush=True)
+            print("selfplay-bench: %s%s run %d of %d, %.1f s" % (type(g).__name__, " pool %d" % pool if pool else "", i, a.repeats, dt),
+                  file=sys.stderr, flush=True)
             if i:  # the first run warms up
                 runs.append(dict(games_per_s=c["games_finished"] / dt, nn_evals_per_game=c["nn_evals"] / max(1, c["games_finished"]),
                                  rows_per_game=n_rows / max(1, c["games_finished"]), tables_solved=eng.endgame_stats()[0] - solved0,
                                  seconds=dt))
+        tp = eng.table_pool()
         eng.close()
-        return {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+        out = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+        if pool:  # counted over the warm-up and the timed runs together
+            out.update(high_water=tp["high_water"], denied=tp["denied"], in_use_at_end=tp["in_use"])
+        return out
 
     if a.max_free > MAX_FREE:
         # past 16 free edges the slot tables are a DeepTables' (dbaz_attach_tables): plain, Endgame(16) and deep side by side
         g, d = Endgame(a.rows, a.cols, a.device, MAX_FREE), DeepTables(a.rows, a.cols, a.device, max_free=a.max_free)
         out = dict(rows=a.rows, cols=a.cols, games=a.selfplay_bench, slots=a.slots, reads=a.reads, max_free=d.max_free, endgame_reads=a.endgame_reads,
-                   plain=dict(play(None), table_bytes=0), endgame16=dict(play(g), table_bytes=a.slots << MAX_FREE),
-                   deep=dict(play(d), table_bytes=a.slots << d.max_free))
-        out["speedup"] = out["deep"]["games_per_s"] / out["plain"]["games_per_s"]
-        out["speedup_over_16"] = out["deep"]["games_per_s"] / out["endgame16"]["games_per_s"]
-        # the one relation that must hold on the same games: the deeper tables take more leaves away from the network
-        out["deep_saves_nn_evals"] = out["deep"]["nn_evals_per_game"] < out["endgame16"]["nn_evals_per_game"]
-        assert out["deep_saves_nn_evals"], out
+                   plain=dict(play(None), table_bytes=0), endgame16=dict(play(g), table_bytes=a.slots << MAX_FREE))
+        if a.pool > 0:
+            out["pooled"] = dict(play(d, a.pool), n_tables=a.pool, table_bytes=a.pool << d.max_free)
+        if a.pool <= 0 or a.per_slot_deep:
+            out["deep"] = dict(play(d), table_bytes=a.slots << d.max_free)
+        best = out["deep"] if "deep" in out else out["pooled"]
+        out["speedup"] = best["games_per_s"] / out["plain"]["games_per_s"]
+        out["speedup_over_16"] = best["games_per_s"] / out["endgame16"]["games_per_s"]
+        if "deep" in out and "pooled" in out:  # with denied == 0 the same games: the difference is the cost of the pool's two launches
+            out["pooled_over_deep"] = out["pooled"]["games_per_s"] / out["deep"]["games_per_s"]
+        # the one relation that must hold on the same games: the deeper tables take more leaves away from the network.  A pool
+        # that ran dry does not play the same games (its denied searches go to the network), so nothing is asserted of it
+        out["deep_saves_nn_evals"] = best["nn_evals_per_game"] < out["endgame16"]["nn_evals_per_game"]
+        assert out["deep_saves_nn_evals"] or ("deep" not in out and out["pooled"]["denied"] > 0), out
         g.close()
         d.close()
         return out
@@ -1043,6 +1057,10 @@ def main(argv=None):
     ap.add_argument("--targets-bench", type=int, default=0, metavar="N",
                     help="time dbaz_exact_targets next to dbaz_endgame_score on N generated rows: n_free uniform in 0 .. 16, and a self-play-like mix")
     ap.add_argument("--slots", type=int, default=0, help="--selfplay-bench: engine slots (default min(N, 8192))")
+    ap.add_argument("--pool", type=int, default=0, metavar="N",
+                    help="--selfplay-bench with --max-free > 16: a fourth engine whose slots share a pool of N deep tables")
+    ap.add_argument("--per-slot-deep", type=int, default=1,
+                    help="--selfplay-bench with --pool: 0 leaves out the engine with one deep table per slot (slots << max_free bytes)")
     ap.add_argument("--reads", type=int, default=800, help="--selfplay-bench: mcts_num_read")
     ap.add_argument("--endgame-reads", type=int, default=0, help="--selfplay-bench: read cap of the searches the tables serve (0: none)")
     ap.add_argument("--channels", type=int, default=64)

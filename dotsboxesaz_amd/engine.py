@@ -45,6 +45,9 @@ class Engine:
     the searches the tables serve.  The Engine keeps a reference to the handle.
     endgame=DeepTables(rows, cols, max_free=M) means the same for any M <= 31 that fits in memory (n_slots x 2^M bytes): the slot
     tables are solved in HBM by the deep solver's kernels (dbaz_attach_tables).  A handle's attaches are all of one kind.
+    endgame_tables=N with a DeepTables (dbaz_attach_tables_pool): N regions of 2^M bytes that the slots share, 1 <= N <= n_slots,
+    handed out on the device in ascending slot order and taken back when a game ends.  A slot that finds the pool dry searches
+    that move with its model's own evaluator (table_pool()["denied"]; run() warns).  None: one region per slot.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -55,7 +58,7 @@ class Engine:
                  temperature=None, reuse_tree=True, evaluator="formula", nodes_per_slot=0, seed=0, device=0,
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
-                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0):
+                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -110,7 +113,10 @@ class Engine:
         if endgame is not None:
             try:
                 for model in endgame_models:
-                    self.attach_endgame(endgame, model, endgame_seed, endgame_reads)
+                    if endgame_tables is None:
+                        self.attach_endgame(endgame, model, endgame_seed, endgame_reads)
+                    else:
+                        self.attach_endgame_pool(endgame, endgame_tables, model, endgame_seed, endgame_reads)
             except Exception:
                 self.close()
                 raise
@@ -149,6 +155,25 @@ class Engine:
         self._ck(attach(self.h, int(model), endgame.h, C.c_uint64(int(seed)), int(reads)))
         self._endgames[int(model)] = endgame
 
+    def attach_endgame_pool(self, endgame, tables, model=0, seed=0, reads=0):
+        """dbaz_attach_tables_pool: attach_endgame with a DeepTables whose slot tables are `tables` regions of 2^max_free bytes that
+        the slots share (1 .. n_slots; tables << max_free bytes of device memory).  A region is handed to a slot when its search
+        root first has at most max_free free edges -- in ascending slot order when several ask in one pass -- and goes back when
+        the slot's game ends; a slot that finds the pool dry searches that move with its model's own evaluator and is counted
+        (table_pool()).  reads must be 0.  Every attach of one Engine is pooled or not, with one max_free and one `tables`:
+        DbazError (EINVAL) otherwise, also for an Endgame, and nothing changes."""
+        if endgame.ATTACH != "dbaz_attach_tables":  # the C side cannot tell the two handle types apart
+            raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
+        self._ck(self._L.dbaz_attach_tables_pool(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
+        self._endgames[int(model)] = endgame
+
+    def table_pool(self):
+        """dbaz_get_table_pool: dict(n_tables, in_use, high_water, denied) of the pool of tables after the queued work is done;
+        n_tables 0 (and zeros) without a pooled attach.  high_water and denied count since the first attach."""
+        n, use, high, den = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._ck(self._L.dbaz_get_table_pool(self.h, C.byref(n), C.byref(use), C.byref(high), C.byref(den)))
+        return dict(n_tables=int(n.value), in_use=int(use.value), high_water=int(high.value), denied=int(den.value))
+
     def endgame_stats(self):
         """(tables_solved, leaves_served) since the first attach_endgame; (0, 0) without one"""
         t, n = C.c_int64(), C.c_int64()
@@ -156,16 +181,19 @@ class Engine:
         return int(t.value), int(n.value)
 
     def slot_table(self, slot):
-        """dbaz_get_slot_table: dict(valid, n_free, game, free_edges, table) of a slot's endgame table after the queued work is
-        done -- free_edges uint64 [4] by action index, table int8 [2^n_free] (empty without a valid table).  DbazError (EINVAL)
-        without an attach or for a slot outside 0 .. n_slots - 1."""
+        """dbaz_get_slot_table: dict(valid, n_free, game, free_edges, table, table_index) of a slot's endgame table after the
+        queued work is done -- free_edges uint64 [4] by action index, table int8 [2^n_free] (empty without a valid table),
+        table_index the region that holds it (dbaz_get_slot_table_index: the slot's own index, or with a pool of tables one of
+        its regions, -1 for none).  DbazError (EINVAL) without an attach or for a slot outside 0 .. n_slots - 1."""
         valid, n_free, game = C.c_int32(), C.c_int32(), C.c_int64()
         fe = np.zeros(4, np.uint64)
         self._ck(self._L.dbaz_get_slot_table(self.h, int(slot), C.byref(valid), C.byref(n_free), C.byref(game), _p(fe), None, 0, 0))
         table = np.empty((1 << n_free.value) if valid.value else 0, np.int8)
         if len(table):
             self._ck(self._L.dbaz_get_slot_table(self.h, int(slot), None, None, None, None, _p(table), 0, len(table)))
-        return dict(valid=bool(valid.value), n_free=int(n_free.value), game=int(game.value), free_edges=fe, table=table)
+        at = C.c_int32()
+        self._ck(self._L.dbaz_get_slot_table_index(self.h, int(slot), C.byref(at)))
+        return dict(valid=bool(valid.value), n_free=int(n_free.value), game=int(game.value), free_edges=fe, table=table, table_index=int(at.value))
 
     # ---------------------------------------------------------------- rules (G1-G6)
     def rules_init(self, n):
@@ -389,6 +417,7 @@ class Engine:
             c = self.counters()
             if max_steps or c["active_slots"] == 0 or c["blocked_slots"] < c["active_slots"]:
                 self._warn_pool_resets(c)
+                self._warn_tables_denied()
                 return
             self._drained.append(self._fetch_once())
 
@@ -402,6 +431,18 @@ class Engine:
             warnings.warn("%d of %d moves were searched from a fresh root because the reused subtree did not leave mcts_num_read + 2 "
                           "nodes of the slot's pool free: raise nodes_per_slot (now %d) to keep the reference's tree reuse on every move"
                           % (n, int(c.get("moves_played", 0)), self.nodes_per_slot))
+
+    def _warn_tables_denied(self):
+        """A pool of tables that runs dry changes results as pool_resets do: the slot searches that move without its exact table
+        (table_pool()["denied"]).  Said once per handle."""
+        if not getattr(self, "_endgames", None) or getattr(self, "_warned_denied", False):
+            return
+        p = self.table_pool()
+        if p["denied"]:
+            import warnings
+            self._warned_denied = True
+            warnings.warn("%d searches with at most max_free free edges found the pool of %d tables dry and ran on the model's own evaluator: "
+                          "raise endgame_tables (most held at once: %d) for exact endgames in every game" % (p["denied"], p["n_tables"], p["high_water"]))
 
     def sync(self):
         self._ck(self._L.dbaz_sync(self.h))

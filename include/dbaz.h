@@ -668,6 +668,35 @@ int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t p
 int dbaz_get_slot_table(dbaz_engine *e, int32_t slot, int32_t *valid, int32_t *n_free, int64_t *game, uint64_t free_edges[4],
                         int8_t *host_dst, int64_t first, int64_t count);
 
+/* ---- deep tables from a pool that the slots share ----------------------------------------------------------------
+ * dbaz_attach_tables with n_tables regions of 2^max_free bytes instead of one per slot: n_tables << max_free bytes (64-bit sizes),
+ * 1 <= n_tables <= n_slots.  A slot needs a table only while its game is in its last max_free moves; a region is handed to the slot
+ * on the device when its search root first has F0 <= max_free free edges and goes back to the pool when the slot's game ends,
+ * whether or not the slot starts another.  Every pass runs where dbaz_attach_tables' passes run, and still no request waits for a
+ * later pass:
+ *   - all regions given back in a pass (a game that ended, a root past max_free) are free before any is granted in that pass;
+ *   - the slots that ask are granted in ASCENDING SLOT ORDER as long as free regions last; which region a slot receives is
+ *     unspecified and changes no result;
+ *   - a slot that asks and gets nothing is DENIED: it has no table, the leaves of THIS search go to the model's own evaluator, and
+ *     the slot asks again when its next search starts.  Denials are counted (dbaz_get_table_pool) and change results, as
+ *     dbaz_counters.pool_resets do: two runs of one configuration give the same rows and counters, but runs with different slot
+ *     counts may differ once something is denied.  With no denial the rows are those of dbaz_attach_tables, bit for bit.
+ * dbaz_set_positions, dbaz_selfplay_start and a later attach free every region.  Both models of a match draw on the one pool.
+ *   every refusal of dbaz_attach_tables; n_tables outside 1 .. n_slots; endgame_reads > 0 (the reads of a search are capped before
+ *   the pass knows whether the slot gets a region); a pooled attach on a handle with one region per slot or the reverse; another
+ *   n_tables than the first pooled attach                                  -> DBAZ_EINVAL, nothing changes
+ *   the regions cannot be allocated   -> DBAZ_EDEVICE, the byte count in the message; the handle stays as it was */
+int dbaz_attach_tables_pool(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads);
+/* The pool's figures after waiting for the engine's queued work: its regions (0: no pooled attach on this handle, and the other
+ * figures are 0), the regions held now, the most held at once and the denials, the last two counted since the first attach.  Any
+ * output pointer may be NULL. */
+int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *in_use, int32_t *high_water, int64_t *denied);
+/* The region that a slot's header names, after waiting for the queued work: the slot's own index for dbaz_attach_endgame and
+ * dbaz_attach_tables, a region of the pool or -1 (the slot holds none) for dbaz_attach_tables_pool.  dbaz_get_slot_table reads the
+ * bytes of that region; with count > 0 for a slot that holds none it is DBAZ_EINVAL.
+ *   no attach on this handle, slot outside 0 .. n_slots - 1 -> DBAZ_EINVAL */
+int dbaz_get_slot_table_index(dbaz_engine *e, int32_t slot, int32_t *table);
+
 #ifdef __cplusplus
 }
 #endif
