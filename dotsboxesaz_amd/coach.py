@@ -90,7 +90,9 @@ class Coach:
             rows, _ = sp.all_gather_rows(rows, self.dist)
         self.store.add_generation(generation, rows, train_split=float(_get(_get(_get(self.params, "nn"), "train_params"), "train_split", 0.9)))
         c = e.counters()  # this rank's games: network evaluations, those the exact-f32 safety net redid, tree-reuse fallbacks
-        out = dict(rows=int(rows.shape[0]), seconds=time.time() - tick, games=n_games, nn_evals=int(c["nn_evals"]),
+        n_fast = int(self.store.chunks[-1]["n_fast"])  # playout cap (params.self_play.playout_cap): rows that only moved a game on
+        out = dict(rows=int(rows.shape[0]), full_rows=int(rows.shape[0]) - n_fast, fast_rows=n_fast, seconds=time.time() - tick, games=n_games,
+                   nn_evals=int(c["nn_evals"]),
                    f32_fallback_evals=int(c["f32_fallback_evals"]), pool_resets=int(c["pool_resets"]), moves_played=int(c["moves_played"]))
         if exact is not None:
             out["exact_targets"] = exact

@@ -59,6 +59,8 @@ struct Slot {
     int32_t leaf, path_len, leaf_terminal, leaf_result, leaf_to_play;
     int32_t move_idx;        // ply within the current game
     int32_t n_rows;          // sample rows recorded for the current game
+    int32_t fast_search;     // 1 = the current search is a fast one of the playout cap (playout_cap.h): capped reads, no root noise,
+                             // its row marked; written by every begin_search (in what was padding in front of game_idx)
     int64_t game_idx;        // -1: no game
     double temperature;
     int32_t error;
@@ -109,7 +111,7 @@ struct RowMeta {
     int32_t tree_size, terminal_count;
     float q_value;
     int8_t player, z;
-    int16_t pad;
+    int16_t flags;           // replay_row.h: ROW_FLAG_FAST; 0 on every row made without a playout cap ("pad" in the numpy dtypes)
 };
 
 // ---- search parameters ---------------------------------------------------------------
@@ -187,7 +189,7 @@ struct TreeBufs {
     long long last_game;  // exclusive
     long long first_game;
     long long *games_finished; // [1]
-    long long *moves_played;   // [1]
+    long long *moves_played;   // [3]: moves played; full and fast searches the self-play driver started (playout_cap.h)
     // teacher-forcing scripts (tests)
     const int16_t *script_moves; // [n_script][E+1], -1 = sample
     const double *script_noise;  // [n_script][E+1][A] or null

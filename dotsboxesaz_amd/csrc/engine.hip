@@ -41,6 +41,8 @@ struct dbaz_engine {
     const dbaz_solver *solver[2] = {nullptr, nullptr};
     uint64_t solver_seed[2] = {0, 0};
     ReadCaps read_caps = {{0, 0}, {0, 0}};
+    PlayoutCap playout = {4294967296ull, 0, 0}; // dbaz_selfplay_set_playout_cap (off)
+    double playout_prob = 1.0;                  // full_prob as the caller gave it
     EndgameStart eg_start = {nullptr, {0, 0}};
     size_t eg_stride = 0; // bytes per slot of eg_tables as allocated: every attached handle must have this stride
     int eg_max_free = 0;  // the largest max_free attached so far: no header claims more compact edges, and 2^eg_max_free <= eg_stride
@@ -338,7 +340,7 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     CREATE_CHECK(dmalloc(e, &B.out_count, 4));
     CREATE_CHECK(dmalloc(e, &B.next_game, 2));
     CREATE_CHECK(dmalloc(e, &B.games_finished, 2));
-    CREATE_CHECK(dmalloc(e, &B.moves_played, 2));
+    CREATE_CHECK(dmalloc(e, &B.moves_played, 4));
     CREATE_CHECK(dmalloc(e, &e->d_small, 16));
     CREATE_CHECK(dmalloc(e, &e->d_sum, 1));
     // log / sqrt tables evaluated with the HOST libm (what python's math.log/math.sqrt call),
@@ -687,7 +689,7 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
     if (with_driver) {
-        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
         endgame_solve_tables(e, s);
     }
     tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
@@ -724,7 +726,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
         HIP_CHECK_RET(e, hipEventRecord(e->ev_fork, s));
         HIP_CHECK_RET(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
         // the searches this pass starts do not select in this step; the join below orders their tables before the next k_select
         endgame_solve_tables(e, e->stream2);
         HIP_CHECK_RET(e, hipEventRecord(e->ev_join, e->stream2));
@@ -811,7 +813,7 @@ extern "C" int dbaz_search_begin(dbaz_engine *e, const int32_t *num_reads, const
     int r = upload_search_inputs(e, num_reads, noise, &d_reads);
     if (r) return r;
     e->sc.step = 0;
-    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads, StartArgs{e->read_caps, e->eg_start});
+    tree_launch_search_begin(e->stream, e->g, e->sc, e->B, e->n_slots, d_reads, StartArgs{e->read_caps, e->eg_start, PlayoutCap{0, 0, 0}});
     endgame_solve_tables(e, e->stream); // every slot is looked at again: the positions may have changed
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
@@ -1358,6 +1360,50 @@ extern "C" int dbaz_selfplay_quickplay(dbaz_engine *e, const int32_t *plies, int
     return DBAZ_OK;
 }
 
+// ---- playout cap randomization (playout_cap.h; the rule is stated in full in include/dbaz.h)
+static bool playout_prob_ok(double p) { return p == p && p >= 0.0 && p <= 1.0; }
+
+extern "C" int dbaz_selfplay_set_playout_cap(dbaz_engine *e, double full_prob, int32_t fast_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!playout_prob_ok(full_prob)) return set_error(e, DBAZ_EINVAL, "full_prob = %g is outside [0, 1]", full_prob);
+    if (full_prob < 1.0 && fast_reads < 1) return set_error(e, DBAZ_EINVAL, "fast_reads = %d must be >= 1", fast_reads);
+    if (e->sc.match_play) return set_error(e, DBAZ_EINVAL, "the playout cap belongs to self-play: this handle plays matches (match_play)");
+    if (e->selfplay) {
+        // the driver's launches read the setting at every step: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    e->playout = playout_cap_make(full_prob, fast_reads);
+    e->playout_prob = e->playout.on ? full_prob : 1.0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_playout_cap(dbaz_engine *e, double *full_prob, int32_t *fast_reads, int64_t *full_searches, int64_t *fast_searches)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (full_prob) *full_prob = e->playout_prob;
+    if (fast_reads) *fast_reads = e->playout.fast_reads;
+    if (full_searches || fast_searches) {
+        long long c[3] = {0, 0, 0}; // moves played, full searches, fast searches
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        HIP_CHECK_RET(e, hipMemcpy(c, e->B.moves_played, sizeof(c), hipMemcpyDeviceToHost));
+        if (full_searches) *full_searches = c[1];
+        if (fast_searches) *fast_searches = c[2];
+    }
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_playout_cap_is_full(uint64_t seed, int64_t game_idx, int32_t ply, double full_prob)
+{
+    if (!playout_prob_ok(full_prob)) return -1;
+    return playout_is_full(playout_cap_make(full_prob, 1), seed, game_idx, (uint32_t)ply) ? 1 : 0;
+}
+
 extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t first_game_idx)
 {
     if (!e || n_games < 0) return e ? set_error(e, DBAZ_EINVAL, "bad argument") : DBAZ_EINVAL;
@@ -1394,7 +1440,7 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
     long long next = first_game_idx + std::min<int64_t>(n_games, e->n_slots);
     HIP_CHECK_RET(e, hipMemcpy(B.next_game, &next, 8, hipMemcpyHostToDevice));
     HIP_CHECK_RET(e, hipMemset(B.games_finished, 0, 8));
-    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 8));
+    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 24)); // with the full and fast searches
     HIP_CHECK_RET(e, hipMemset(B.out_count, 0, 4));
     HIP_CHECK_RET(e, hipMemset(B.noise_valid, 0, (size_t)e->n_slots * 4));
     // scripts
@@ -1429,7 +1475,7 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
     }
     e->sc.step = 0; // searches started here carry stamp 0, which no step ever has
     if (int r = endgame_drop_tables(e)) return r;
-    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots, StartArgs{e->read_caps, e->eg_start});
+    tree_launch_selfplay_start(s, e->g, e->sc, B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
     endgame_solve_tables(e, s);
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(s));

@@ -31,7 +31,7 @@
 #include "replay.h"
 #include "replay_row.h"
 
-static_assert(sizeof(RowMeta) == ROW_X_OFF && offsetof(RowMeta, z) == ROW_Z_OFF, "replay_row.h restates RowMeta");
+static_assert(sizeof(RowMeta) == ROW_X_OFF && offsetof(RowMeta, z) == ROW_Z_OFF && offsetof(RowMeta, flags) == ROW_FLAGS_OFF, "replay_row.h restates RowMeta");
 
 struct DevBuf {
     void *p = nullptr;

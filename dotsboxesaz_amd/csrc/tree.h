@@ -1,6 +1,7 @@
 // tree.h -- host launchers of the tree / rules kernels (tree.hip)
 #pragma once
 #include "common.h"
+#include "playout_cap.h"
 
 struct EndgameReq;     // endgame.h
 struct EndgameSlotHdr; // endgame.h
@@ -37,6 +38,7 @@ struct EndgameStart {
 struct StartArgs {
     ReadCaps caps;
     EndgameStart eg;
+    PlayoutCap pc; // dbaz_selfplay_set_playout_cap: the self-play driver's launches only (all zero = off for k_search_begin)
 };
 
 // One game's endgame table per slot as an evaluator inside the search (endgame.h; all zero until dbaz_attach_endgame): a leaf of a

@@ -13,6 +13,7 @@
 // float32 prior sums with numpy's pairwise summation.  This TU is compiled with
 // -ffp-contract=off: a fused multiply-add would change the roundings.
 #include "endgame.h"
+#include "replay_row.h"
 #include "rules.h"
 #include "tree.h"
 
@@ -394,8 +395,13 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
             ldsd[i] = (cpsum != 0.0) ? ldsd[i] / cpsum : 0.0;
     }
     __syncthreads();
-    const double onemc = 1.0 - cfg.coeff;
-    if (cfg.alpha > 0) {
+    // a fast search of the playout cap is UCT_search(..., dirichlet=(0.0, 0.0)): no noise, coeff = 0; a vector waiting in noise_in
+    // (scripted for this ply, or left by the host) is dropped, not kept for a later search
+    const bool fast = S->fast_search != 0;
+    const double coeff = fast ? 0.0 : cfg.coeff;
+    const double onemc = 1.0 - coeff;
+    if (fast && lane == 0) B.noise_valid[slot] = 0;
+    if (cfg.alpha > 0 && !fast) {
         const bool ext = B.noise_valid[slot] != 0;
         const double *nin = B.noise_in + (size_t)slot * g.AS;
         double gsum = 0.0;
@@ -415,12 +421,12 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
             double nz = ext ? nin[i] : gam[k] / gsum;
             nz = nz * (gs_valid(g, rm.st, i) ? 1.0 : 0.0);
             double a = probs_f64 ? onemc * ldsd[i] : (double)((float)onemc * ldsf[i]);
-            rp[i] = a + cfg.coeff * nz;
+            rp[i] = a + coeff * nz;
         }
         S->root_prior_f64 = 1;
         if (lane == 0) B.noise_valid[slot] = 0;
     } else {
-        const double cn = cfg.coeff * 0.0;
+        const double cn = coeff * 0.0;
         for (int i = lane; i < A; i += WAVE)
             rp[i] = probs_f64 ? onemc * ldsd[i] + cn : (double)((float)onemc * ldsf[i] + (float)cn);
         S->root_prior_f64 = probs_f64 ? 1 : 0;
@@ -461,10 +467,12 @@ __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, c
 }
 
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
+// fast: a fast search of the playout cap (start_move_search decides; explicit searches are never fast)
 __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                             uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
+                             uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane, bool fast = false)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
+    S->fast_search = fast ? 1 : 0; // root_prep (here or after the root's expansion) and the row of this search read it
     if (rm.flags & NF_TERMINAL) { // play_game never searches a terminal root
         endgame_release(sa, slot, S, lane);
         S->sims_left = 0;
@@ -473,6 +481,7 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     }
     if (num_reads < 0) {
         num_reads = rule_num_reads(g, cfg, rm.st);
+        if (fast) num_reads = min(num_reads, sa.pc.fast_reads);
         // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads); the model of a
         // move's search is chosen as select_one chooses it
         const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
@@ -1560,7 +1569,10 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
         if (cfg.temp_idx[k] == i) S->temperature = cfg.temp_val[k];
     // teacher-forced Dirichlet vector for this (game, ply), if scripted
     long long gi = S->game_idx - B.first_game;
-    if (cfg.alpha > 0 && B.script_noise && gi >= 0 && gi < B.n_script && B.script_has_noise[gi] && i <= g.E) {
+    // playout cap: full or fast is a function of (seed, game, ply) alone
+    const bool fast = !playout_is_full(sa.pc, cfg.seed, S->game_idx, (uint32_t)i);
+    if (lane == 0) atomicAdd((unsigned long long *)B.moves_played + (fast ? 2 : 1), 1ull);
+    if (cfg.alpha > 0 && !fast && B.script_noise && gi >= 0 && gi < B.n_script && B.script_has_noise[gi] && i <= g.E) {
         const double *src = B.script_noise + ((size_t)gi * (g.E + 1) + i) * g.A;
         double *dst = B.noise_in + (size_t)slot * g.AS;
         for (int k = lane; k < g.A; k += WAVE) dst[k] = src[k];
@@ -1568,7 +1580,7 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
         __syncthreads();
         __threadfence_block();
     }
-    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane);
+    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, fast);
 }
 
 
@@ -1695,7 +1707,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             mm.q_value = S->root_W / (float)(1 + S->root_N); // TreeRoot.get_tree_stats, mcts.py:33-36
             mm.player = (int8_t)rm.st.to_play;
             mm.z = 0;
-            mm.pad = 0;
+            mm.flags = S->fast_search ? ROW_FLAG_FAST : 0;
             B.row_meta[(size_t)slot * rcap + r] = mm;
         }
         S->n_rows = r + 1;

@@ -48,6 +48,7 @@ class Engine:
     endgame_tables=N with a DeepTables (dbaz_attach_tables_pool): N regions of 2^M bytes that the slots share, 1 <= N <= n_slots,
     handed out on the device in ascending slot order and taken back when a game ends.  A slot that finds the pool dry searches
     that move with its model's own evaluator (table_pool()["denied"]; run() warns).  None: one region per slot.
+    playout_cap=(full_prob, fast_reads): playout cap randomization (selfplay_set_playout_cap); None: off.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -58,7 +59,7 @@ class Engine:
                  temperature=None, reuse_tree=True, evaluator="formula", nodes_per_slot=0, seed=0, device=0,
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
-                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None):
+                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -117,6 +118,12 @@ class Engine:
                         self.attach_endgame(endgame, model, endgame_seed, endgame_reads)
                     else:
                         self.attach_endgame_pool(endgame, endgame_tables, model, endgame_seed, endgame_reads)
+            except Exception:
+                self.close()
+                raise
+        if playout_cap is not None:
+            try:
+                self.selfplay_set_playout_cap(*playout_cap)
             except Exception:
                 self.close()
                 raise
@@ -403,6 +410,22 @@ class Engine:
                                                    [np.zeros(1, np.int16)]), np.int16)
         self._ck(self._L.dbaz_selfplay_set_start(self.h, _p(flat), _p(off), len(move_lists), int(games_per_start)))
 
+    def selfplay_set_playout_cap(self, full_prob, fast_reads=0):
+        """dbaz_selfplay_set_playout_cap: playout cap randomization for every later selfplay_start.  A search the self-play
+        driver starts is a full one -- today's search, its row a training target -- with probability full_prob, decided by
+        playout_cap.is_full(seed, game_idx, ply, full_prob); every other one runs min(driver rule, fast_reads) reads without
+        root noise and marks its row (bit 0 of "pad"; fetch_samples()["full"] is False).  full_prob >= 1.0: off (the default);
+        0: every search fast.  DbazError: EINVAL for full_prob outside [0, 1], fast_reads < 1 with full_prob < 1 or a
+        match_play handle, ESTATE while games are being played; a failed call changes nothing."""
+        self._ck(self._L.dbaz_selfplay_set_playout_cap(self.h, C.c_double(float(full_prob)), int(fast_reads)))
+
+    def playout_cap(self):
+        """dbaz_get_playout_cap: dict(full_prob, fast_reads, full_searches, fast_searches) -- the setting (1.0, 0 when off) and
+        the searches the driver started since the last selfplay_start, after the queued work is done."""
+        p, n, a, b = C.c_double(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self._L.dbaz_get_playout_cap(self.h, C.byref(p), C.byref(n), C.byref(a), C.byref(b)))
+        return dict(full_prob=float(p.value), fast_reads=int(n.value), full_searches=int(a.value), fast_searches=int(b.value))
+
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
 
@@ -465,7 +488,14 @@ class Engine:
         self._drained = []
         out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
         order = np.lexsort((out["move_idx"], out["game_idx"]))
-        return {k: v[order] for k, v in out.items()}
+        out = {k: v[order] for k, v in out.items()}
+        prob = C.c_double()
+        self._ck(self._L.dbaz_get_playout_cap(self.h, C.byref(prob), None, None, None))  # the setting alone: no device work
+        if prob.value < 1.0:
+            # dbaz_fetch_samples keeps its 13 arrays: the column is the rule restated on the host from (seed, game, ply)
+            from . import playout_cap as PC
+            out["full"] = PC.is_full(self.cfg.seed, out["game_idx"], out["move_idx"], prob.value)
+        return out
 
     def _fetch_once(self):
         n = C.c_int32()

@@ -72,7 +72,10 @@ def engine_kwargs_from_params(params, async_searches=False):
     game (max_pending_evals = 1: the semantics of every parity path).  async_searches=True honours the knob instead: every search
     of every game runs in waves of self_play.mcts.max_async_searches simulations with the reference's bookkeeping
     (dbaz_config.selfplay_pending; equal to the reference's own UCT_search(..., max_pending_evals=K) under an evaluator that
-    suspends once per call, tests/test_hip_pending.py)."""
+    suspends once per call, tests/test_hip_pending.py).
+
+    params.self_play.playout_cap = {"full_prob": p, "fast_reads": n} (not a knob of the reference; absent = off) becomes
+    Engine(playout_cap=(p, n)): playout cap randomization, Engine.selfplay_set_playout_cap."""
     sp = _get(params, "self_play")
     m = _get(sp, "mcts")
     noise = _get(sp, "noise", [0.0, 0.0])
@@ -82,6 +85,9 @@ def engine_kwargs_from_params(params, async_searches=False):
     k = int(_get(m, "max_async_searches", 1) or 1)
     if async_searches and k > 1:
         kw.update(max_pending_evals=k, selfplay_pending=True, transposition_cache=False)
+    cap = _get(sp, "playout_cap")
+    if cap is not None:
+        kw["playout_cap"] = (float(_get(cap, "full_prob")), int(_get(cap, "fast_reads")))
     return kw
 
 
@@ -158,7 +164,7 @@ def write_dataset(file_name, key, df):
 
 def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_workers=None, games_per_workers=10,
                    rows=None, cols=None, n_slots=None, device=0, dist=None, nn_precision=None, async_searches=False,
-                   start_states=None, games_per_start=1, endgame=None, endgame_models=(0,), endgame_tables=None):
+                   start_states=None, games_per_start=1, endgame=None, endgame_models=(0,), endgame_tables=None, fast_rows="drop"):
     """Reference: self_play.generate_games (self_play.py:291-306) called from coach.selfplay
     (coach.py:27-29).  Plays n_games with generation-1's weights (random init for generation 0,
     self_play.py:187-190) and appends the samples (+ `training` = 0) to key "fresh".
@@ -176,8 +182,13 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     a function of (seed, game index) however the games are sharded over ranks.  None: the empty board.
     endgame: an endgame.Endgame (max_free <= 16) or endgame.DeepTables (max_free <= 31) of the board and device: from a game's first search root with at most endgame.max_free free edges
     on, every leaf is answered from that root's exact table instead of the network (Engine.attach_endgame).
-    endgame_tables: with a DeepTables, the slots share a pool of that many tables (Engine(endgame_tables=N)); None: one per slot."""
+    endgame_tables: with a DeepTables, the slots share a pool of that many tables (Engine(endgame_tables=N)); None: one per slot.
+    fast_rows: with params.self_play.playout_cap set, "drop" leaves the rows of the fast searches (bit 0 of "pad") out of the
+    DataFrame -- they moved the games on and are no training targets -- and "keep" writes every row.  Without a cap no row is
+    marked and the two are the same."""
     from .engine import Engine
+    if fast_rows not in ("drop", "keep"):
+        raise ValueError("fast_rows must be 'drop' or 'keep', not %r" % (fast_rows,))
     game = _get(params, "game")
     if rows is None:
         dims = _get(game, "dims") or getattr(_get(game, "clazz"), "BOARD_DIM", (3, 3))
@@ -203,6 +214,8 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
         samples = unpack_rows(packed.cpu().numpy(), eng.F, eng.A)
     finally:
         eng.close()
+    if fast_rows == "drop":
+        samples = full_rows_only(samples)
     df = samples_to_dataframe(samples, generation, rows, cols, True)
     df["training"] = np.zeros(len(df.index), dtype=np.int8)
     if hdf_file_name is not None and rank == 0:
@@ -226,6 +239,15 @@ ROW_META = np.dtype([("game_idx", "<i4"), ("move_idx", "<i2"), ("move", "<i2"), 
 assert ROW_META.itemsize == 28
 
 
+ROW_FLAGS_OFF, ROW_FLAG_FAST = 26, 1  # csrc/replay_row.h: the int16 "pad"; bit 0 = the row of a fast search of the playout cap
+
+
+def full_rows_only(samples):
+    """The rows of a sample dict of unpack_rows whose search was a full one ("pad" bit 0 clear); the dict itself when none is marked."""
+    keep = (samples["pad"] & ROW_FLAG_FAST) == 0
+    return samples if keep.all() else {k: v[keep] for k, v in samples.items()}
+
+
 def row_bytes(F, A):
     return (ROW_META.itemsize + 2 * F + 4 * A + 7) // 8 * 8
 
@@ -233,7 +255,7 @@ def row_bytes(F, A):
 def unpack_rows(packed, F, A):
     """Packed replay rows (uint8 [n, row_bytes], any rank order) -> the sample dict of
     Engine.fetch_samples(), sorted by (game_idx, move_idx); pi = visits / (sum or 1.0) in float64
-    (self_play.py:114-115)."""
+    (self_play.py:114-115), plus "pad", the rows' flag word (bit 0: the row of a fast search of the playout cap; 0 without one)."""
     packed = np.ascontiguousarray(packed, dtype=np.uint8)
     n = packed.shape[0]
     if n and packed.shape[1] != row_bytes(F, A):
@@ -249,7 +271,7 @@ def unpack_rows(packed, F, A):
                visits=vis.astype(np.int32), pi=pi, z=meta["z"].astype(np.int8),
                max_deepness=meta["max_deepness"].astype(np.int16), tree_size=meta["tree_size"].astype(np.int32),
                terminal_count=meta["terminal_count"].astype(np.int32), q_value=meta["q_value"].astype(np.float32),
-               played=meta["played"].astype(np.int16))
+               played=meta["played"].astype(np.int16), pad=meta["pad"].astype(np.int16))
     order = np.lexsort((out["move_idx"], out["game_idx"]))
     return {k: v[order] for k, v in out.items()}
 
@@ -383,6 +405,7 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     p0, p1 = params
     over = _get(elo_params, "self_play_override", {}) or {}
     kw = engine_kwargs_from_params(p0)
+    kw.pop("playout_cap", None)  # the cap belongs to self-play: a match searches every move in full
     if "reuse_mcts_tree" in over:
         kw["reuse_tree"] = bool(_get(over, "reuse_mcts_tree"))
     if "noise" in over:
@@ -444,6 +467,7 @@ def solver_match(params, generation, n_games, rows, cols, openings=None, solver=
     # the shipped match configuration (configuration.py:107-113): every move from a fresh root -- a reused subtree would carry the
     # other model's priors, and the table's one-hot prior only binds the search from a root whose expansion was counted -- no noise
     kw.update(reuse_tree=False, noise=(0.0, 0.0))
+    kw.pop("playout_cap", None)  # the cap belongs to self-play
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=model.kind, evaluator2="solver", match_play=True,
                  device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads, **kw)
     try:

@@ -22,6 +22,8 @@ import random
 
 import numpy as np
 
+from .self_play import ROW_FLAG_FAST, ROW_FLAGS_OFF
+
 
 def _sample_locs(n, size):
     """DataFrame.sample(n=size) without replacement: pandas draws np.random.choice(n, size, replace=False)."""
@@ -35,17 +37,40 @@ class ReplayStore:
         self.engine = engine
         self.chunks = []  # dicts: generation, rows (device), n, train_locs, val_locs
 
-    def add_generation(self, generation, rows, train_split=0.9):
+    def add_generation(self, generation, rows, train_split=0.9, fast_rows="drop"):
         """rows: torch uint8 CUDA tensor [n, row_bytes] (kept alive here) or the tuple of
         engine.replay_rows_dev() (only valid until the engine's next call of it).
-        coach.py:59-63: train = sample(frac), val = the rest in original order."""
+        coach.py:59-63: train = sample(frac), val = the rest in original order.
+        fast_rows="drop": the rows of the playout cap's fast searches (bit 0 of the rows' flag word, 2 n bytes read to the host)
+        enter neither split, and train_split is a share of the rows that train; "keep": every row is split, as without a cap.
+        A generation without a marked row -- every generation made without a cap -- is split as ever, with the same random draws."""
+        if fast_rows not in ("drop", "keep"):
+            raise ValueError("fast_rows must be 'drop' or 'keep', not %r" % (fast_rows,))
         n = rows[1] if isinstance(rows, tuple) else int(rows.shape[0])
-        size = int(round(train_split * n))
-        train_locs = _sample_locs(n, size) if n else np.zeros(0, dtype=np.int64)
-        mask = np.ones(n, dtype=bool)
+        full = None
+        if fast_rows == "drop" and n and (rows[2] if isinstance(rows, tuple) else int(rows.shape[1])) >= ROW_FLAGS_OFF + 2:
+            fast = (self._row_flags(rows, n) & ROW_FLAG_FAST) != 0
+            if fast.any():
+                full = np.nonzero(~fast)[0]
+        m = n if full is None else len(full)
+        size = int(round(train_split * m))
+        train_locs = _sample_locs(m, size) if m else np.zeros(0, dtype=np.int64)
+        mask = np.ones(m, dtype=bool)
         mask[train_locs] = False
-        self.chunks.append(dict(generation=int(generation), rows=rows, n=n, train_locs=train_locs.astype(np.int32),
-                                val_locs=np.nonzero(mask)[0].astype(np.int32)))
+        val_locs = np.nonzero(mask)[0]
+        if full is not None:
+            train_locs, val_locs = full[train_locs], full[val_locs]
+        self.chunks.append(dict(generation=int(generation), rows=rows, n=n, n_fast=n - m, train_locs=train_locs.astype(np.int32),
+                                val_locs=val_locs.astype(np.int32)))
+
+    def _row_flags(self, rows, n):
+        """int16 [n]: the flag word of every packed row (csrc/replay_row.h), the only bytes of the rows that visit the host"""
+        import torch
+        if isinstance(rows, tuple):
+            from .self_play import _DevBuf
+            ptr, _, rb = rows
+            rows = torch.as_tensor(_DevBuf(ptr, n * rb), device=torch.device("cuda", self.engine.cfg.device)).view(n, rb)
+        return np.ascontiguousarray(rows[:, ROW_FLAGS_OFF:ROW_FLAGS_OFF + 2].cpu().numpy()).view("<i2").reshape(n)
 
     def dataset(self, train=True, min_generation=0, n_samples=int(1e12), pos_average=False, slot=None, exact=None, exact_pi="restrict",
                 exact_z=True):

@@ -248,6 +248,37 @@ int dbaz_selfplay_stagger(dbaz_engine *e, const int32_t *first_reads);
  * the slots reach mid-game positions of the kind search-based play produces (uniformly random plies, the fastforward knob,
  * give positions with more terminal leaves and transpositions than games do).  Applies to the next dbaz_selfplay_start. */
 int dbaz_selfplay_quickplay(dbaz_engine *e, const int32_t *plies, int32_t reads);
+/* Playout cap randomization (Wu 2019, section 3.1): a random share full_prob of the searches that the self-play driver starts
+ * are full searches -- today's search to the bit: the driver rule's reads, root noise, a row that trains -- and every other
+ * one is a fast search: min(driver rule, fast_reads) reads (solver_reads, endgame_reads, the stagger and quickplay budgets
+ * apply on top, as for any search), the root prepared as UCT_search(..., dirichlet=(0.0, 0.0)) prepares it (a scripted noise
+ * vector for that ply is ignored), and bit 0 of its replay row's flag word set (the int16 at byte 26 of the packed row, "pad"
+ * in the numpy dtypes; 0 on every row otherwise).  Temperature schedule, move draw, tree reuse, the pool guard
+ * (mcts_num_read + 2), transpositions, full rounds and endgame tables are untouched; explicit searches (dbaz_search*) never
+ * see the cap.
+ * The rule, in full: the search of game g (absolute index) at ply i (counted from the game's start position, like move_idx)
+ * under seed s (dbaz_config.seed) is full iff  x < floor(full_prob * 2^32),  x being output word 0 of Philox4x32-10 with
+ *   counter (lo32(g), hi32(g), i, 0x33333333)   and   key (lo32(s), hi32(s)),
+ * g taken as its 64-bit two's complement pattern.  Philox4x32-10: ten times
+ *   (c0, c1, c2, c3) <- (hi(0xCD9E8D57 * c2) ^ c1 ^ k0,  lo(0xCD9E8D57 * c2),  hi(0xD2511F53 * c0) ^ c3 ^ k1,  lo(0xD2511F53 * c0)),
+ *   (k0, k1) <- (k0 + 0x9E3779B9, k1 + 0xBB67AE85)   (mod 2^32; hi / lo: the halves of the 64-bit product);
+ * word 0 is c0 after the tenth round.  Check value: counter (1, 2, 3, 0x33333333), key (7, 0) gives 1157962352.
+ * A function of (seed, game, ply) alone: never of slot, step, rank or schedule.
+ *
+ * dbaz_selfplay_set_playout_cap is a setting of the handle: it holds for every later dbaz_selfplay_start (not consumed).
+ * full_prob >= 1.0 switches the cap off (the state after dbaz_create; fast_reads is then ignored); full_prob = 0 makes every
+ * search fast.
+ *   full_prob NaN or outside [0, 1], fast_reads < 1 while full_prob < 1, a match_play handle   -> DBAZ_EINVAL
+ *   games of an earlier dbaz_selfplay_start still being played                                 -> DBAZ_ESTATE
+ * A failed call changes nothing.
+ * dbaz_get_playout_cap: the setting (full_prob as given; 1.0 and 0 when off) and the full and fast searches the driver has
+ * started since the last dbaz_selfplay_start, which zeroes them (with the cap off every search counts as full).  Any output
+ * pointer may be NULL.
+ * dbaz_playout_cap_is_full: the rule above on the host -- no handle, no device: 1 = full, 0 = fast, -1 = full_prob NaN or
+ * outside [0, 1].  full_prob >= 1.0 answers 1. */
+int dbaz_selfplay_set_playout_cap(dbaz_engine *e, double full_prob, int32_t fast_reads);
+int dbaz_get_playout_cap(dbaz_engine *e, double *full_prob, int32_t *fast_reads, int64_t *full_searches, int64_t *fast_searches);
+int dbaz_playout_cap_is_full(uint64_t seed, int64_t game_idx, int32_t ply, double full_prob);
 int dbaz_step(dbaz_engine *e, int32_t k);             /* k simulation steps, asynchronous */
 /* until all games are finished, max_steps (if > 0) are done, or every remaining slot is
  * blocked on a full output buffer (counters.blocked_slots == active_slots: fetch and call again) */
