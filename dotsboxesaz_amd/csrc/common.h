@@ -59,8 +59,10 @@ struct Slot {
     int32_t leaf, path_len, leaf_terminal, leaf_result, leaf_to_play;
     int32_t move_idx;        // ply within the current game
     int32_t n_rows;          // sample rows recorded for the current game
-    int32_t fast_search;     // 1 = the current search is a fast one of the playout cap (playout_cap.h): capped reads, no root noise,
-                             // its row marked; written by every begin_search (in what was padding in front of game_idx)
+    int32_t fast_search;     // the kind of the current search, written by every begin_search (in what was padding in front of game_idx):
+                             // bit 0 (SEARCH_FAST) = a fast one of the playout cap (playout_cap.h): capped reads, no root noise, its row
+                             // marked; bits 1, 2 (SEARCH_FORCED, SEARCH_PRUNE; forced_playouts.h) = a full search of the self-play driver
+                             // with forced playouts at its root, and its row records the pruned visits
     int64_t game_idx;        // -1: no game
     double temperature;
     int32_t error;
@@ -111,7 +113,8 @@ struct RowMeta {
     int32_t tree_size, terminal_count;
     float q_value;
     int8_t player, z;
-    int16_t flags;           // replay_row.h: ROW_FLAG_FAST; 0 on every row made without a playout cap ("pad" in the numpy dtypes)
+    int16_t flags;           // replay_row.h: ROW_FLAG_FAST, ROW_FLAG_PRUNED; 0 on every row made without a playout cap or pruning
+                             // ("pad" in the numpy dtypes)
 };
 
 // ---- search parameters ---------------------------------------------------------------
@@ -135,6 +138,9 @@ struct SearchCfg {
     int eval_round, eval_defer_max; // 0: every leaf is evaluated in the step that selected it
     int gc_lazy;             // node collector: > 0 = recycle dropped nodes only while fewer than this many indices are available
                              // (dropped nodes then live on as transposition twins until their memory is needed); 0 = two per simulation
+    double forced_k;         // forced playouts (forced_playouts.h, dbaz_selfplay_set_forced_playouts): k, 0 = off.  Only searches whose
+                             // Slot::fast_search carries SEARCH_FORCED see it
+    int forced_prune;        // ... 1 = the rows of those searches record the pruned visits
 };
 
 // the two families of built-in evaluators (DBAZ_EVAL_EXTERNAL is neither)
@@ -189,7 +195,8 @@ struct TreeBufs {
     long long last_game;  // exclusive
     long long first_game;
     long long *games_finished; // [1]
-    long long *moves_played;   // [3]: moves played; full and fast searches the self-play driver started (playout_cap.h)
+    long long *moves_played;   // [5]: moves played; full and fast searches the self-play driver started (playout_cap.h); rows pruned and
+                               // visits taken out of them (forced_playouts.h)
     // teacher-forcing scripts (tests)
     const int16_t *script_moves; // [n_script][E+1], -1 = sample
     const double *script_noise;  // [n_script][E+1][A] or null

@@ -340,7 +340,7 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     CREATE_CHECK(dmalloc(e, &B.out_count, 4));
     CREATE_CHECK(dmalloc(e, &B.next_game, 2));
     CREATE_CHECK(dmalloc(e, &B.games_finished, 2));
-    CREATE_CHECK(dmalloc(e, &B.moves_played, 4));
+    CREATE_CHECK(dmalloc(e, &B.moves_played, 6));
     CREATE_CHECK(dmalloc(e, &e->d_small, 16));
     CREATE_CHECK(dmalloc(e, &e->d_sum, 1));
     // log / sqrt tables evaluated with the HOST libm (what python's math.log/math.sqrt call),
@@ -1404,6 +1404,53 @@ extern "C" int dbaz_playout_cap_is_full(uint64_t seed, int64_t game_idx, int32_t
     return playout_is_full(playout_cap_make(full_prob, 1), seed, game_idx, (uint32_t)ply) ? 1 : 0;
 }
 
+// ---- forced playouts and policy target pruning (forced_playouts.h; the rule is stated in full in include/dbaz.h)
+extern "C" int dbaz_selfplay_set_forced_playouts(dbaz_engine *e, double k, int32_t prune)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!(k >= 0.0 && k <= FORCED_K_MAX)) return set_error(e, DBAZ_EINVAL, "k = %g is outside [0, %g]", k, FORCED_K_MAX);
+    if (prune != 0 && prune != 1) return set_error(e, DBAZ_EINVAL, "prune = %d must be 0 or 1", prune);
+    if (e->sc.match_play) return set_error(e, DBAZ_EINVAL, "forced playouts belong to self-play: this handle plays matches (match_play)");
+    if (e->cfg.selfplay_pending)
+        return set_error(e, DBAZ_EINVAL, "forced playouts are not defined for self-play in waves (selfplay_pending): no reference pins forced children among in-flight visits");
+    if (e->selfplay) {
+        // the driver's launches read the setting at every step: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    e->sc.forced_k = k > 0.0 ? k : 0.0;
+    e->sc.forced_prune = k > 0.0 ? prune : 0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_forced_playouts(dbaz_engine *e, double *k, int32_t *prune, int64_t *rows_pruned, int64_t *visits_pruned)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (k) *k = e->sc.forced_k;
+    if (prune) *prune = e->sc.forced_prune;
+    if (rows_pruned || visits_pruned) {
+        long long c[5] = {0, 0, 0, 0, 0}; // moves played, full searches, fast searches, rows pruned, visits pruned
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        HIP_CHECK_RET(e, hipMemcpy(c, e->B.moves_played, sizeof(c), hipMemcpyDeviceToHost));
+        if (rows_pruned) *rows_pruned = c[3];
+        if (visits_pruned) *visits_pruned = c[4];
+    }
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double sq, int64_t root_N, const double *P, const float *W,
+                                 const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out)
+{
+    if (n_actions < 1 || n_actions > DBAZ_MAX_A || !(k >= 0.0 && k <= FORCED_K_MAX) || root_N < 0 || !P || !W || !n_and_sign || !valid || !out)
+        return DBAZ_EINVAL;
+    forced_prune_row(n_actions, k, pbc, sq, root_N, P, W, n_and_sign, valid, out);
+    return DBAZ_OK;
+}
+
 extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t first_game_idx)
 {
     if (!e || n_games < 0) return e ? set_error(e, DBAZ_EINVAL, "bad argument") : DBAZ_EINVAL;
@@ -1440,7 +1487,7 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
     long long next = first_game_idx + std::min<int64_t>(n_games, e->n_slots);
     HIP_CHECK_RET(e, hipMemcpy(B.next_game, &next, 8, hipMemcpyHostToDevice));
     HIP_CHECK_RET(e, hipMemset(B.games_finished, 0, 8));
-    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 24)); // with the full and fast searches
+    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 40)); // with the full and fast searches, the rows pruned and the visits cut
     HIP_CHECK_RET(e, hipMemset(B.out_count, 0, 4));
     HIP_CHECK_RET(e, hipMemset(B.noise_valid, 0, (size_t)e->n_slots * 4));
     // scripts
@@ -1674,6 +1721,32 @@ extern "C" int dbaz_debug_read_stamps(dbaz_engine *e, unsigned long long *out, i
     return nn_read_stamps(e->nn, out, n_wg) == 0 ? DBAZ_OK : DBAZ_ESTATE;
 }
 #endif
+
+// the flag words of the rows dbaz_fetch_samples would hand out now, in its order; drains nothing
+extern "C" int dbaz_fetch_row_flags(dbaz_engine *e, int32_t max_rows, int32_t *n_rows, int16_t *flags)
+{
+    if (!e || !n_rows) return e ? set_error(e, DBAZ_EINVAL, "null argument") : DBAZ_EINVAL;
+    USE_DEVICE(e);
+    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    int32_t n = 0;
+    HIP_CHECK_RET(e, hipMemcpy(&n, e->B.out_count, 4, hipMemcpyDeviceToHost));
+    *n_rows = n;
+    if (max_rows < n) {
+        if (max_rows == 0) return DBAZ_OK; // size query
+        return set_error(e, DBAZ_EINVAL, "%d rows ready but max_rows = %d", n, max_rows);
+    }
+    if (n == 0 || !flags) return DBAZ_OK;
+    std::vector<RowMeta> meta(n);
+    HIP_CHECK_RET(e, hipMemcpy(meta.data(), e->B.out_meta, sizeof(RowMeta) * n, hipMemcpyDeviceToHost));
+    std::vector<int> order(n);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        if (meta[a].game_idx != meta[b].game_idx) return meta[a].game_idx < meta[b].game_idx;
+        return meta[a].move_idx < meta[b].move_idx;
+    });
+    for (int r = 0; r < n; r++) flags[r] = meta[order[r]].flags;
+    return DBAZ_OK;
+}
 
 extern "C" int dbaz_replay_rows_dev(dbaz_engine *e, void **rows_dev, int32_t *n_rows, int32_t *row_bytes)
 {

@@ -1,6 +1,7 @@
 // tree.h -- host launchers of the tree / rules kernels (tree.hip)
 #pragma once
 #include "common.h"
+#include "forced_playouts.h"
 #include "playout_cap.h"
 
 struct EndgameReq;     // endgame.h

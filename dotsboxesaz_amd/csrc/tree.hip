@@ -17,6 +17,8 @@
 #include "rules.h"
 #include "tree.h"
 
+static_assert(FORCED_VISITS_MASK == NS_MASK && FORCED_SAME_BIT == NS_SAME, "forced_playouts.h restates a child's visits | same-player word");
+
 // ------------------------------------------------------------------------------------
 // node access
 // ------------------------------------------------------------------------------------
@@ -397,7 +399,7 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
     __syncthreads();
     // a fast search of the playout cap is UCT_search(..., dirichlet=(0.0, 0.0)): no noise, coeff = 0; a vector waiting in noise_in
     // (scripted for this ply, or left by the host) is dropped, not kept for a later search
-    const bool fast = S->fast_search != 0;
+    const bool fast = (S->fast_search & SEARCH_FAST) != 0;
     const double coeff = fast ? 0.0 : cfg.coeff;
     const double onemc = 1.0 - coeff;
     if (fast && lane == 0) B.noise_valid[slot] = 0;
@@ -467,12 +469,14 @@ __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, c
 }
 
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
-// fast: a fast search of the playout cap (start_move_search decides; explicit searches are never fast)
+// kind: SEARCH_FAST = a fast search of the playout cap, SEARCH_FORCED / SEARCH_PRUNE = forced playouts at the root and a pruned
+// row (start_move_search decides; explicit searches are of kind 0)
 __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
-                             uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane, bool fast = false)
+                             uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane, int kind = 0)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
-    S->fast_search = fast ? 1 : 0; // root_prep (here or after the root's expansion) and the row of this search read it
+    const bool fast = (kind & SEARCH_FAST) != 0;
+    S->fast_search = kind; // root_prep (here or after the root's expansion), the descents and the row of this search read it
     if (rm.flags & NF_TERMINAL) { // play_game never searches a terminal root
         endgame_release(sa, slot, S, lane);
         S->sims_left = 0;
@@ -637,6 +641,7 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     const int root = S->root;
     int cur = root, depth = 0, err = 0;
     const int root_N = S->root_N;
+    const int kind = S->fast_search; // requested beside root_N, looked at once the root's rows are on their way
     NodeMeta m = load_meta(pool, g, root);
     NodeRows<NPL> R;
     load_rows<NPL>(R, pool, g, root, lane);
@@ -648,6 +653,27 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     for (int j = 0; j < NPL; j++) rp[j] = (lane + WAVE * j < A) ? rprior[lane + WAVE * j] : 0.0;
     int in_move = m.move;
     const int root_to_play = m.st.to_play;
+    // forced playouts (forced_playouts.h): on for a full search of the self-play driver, and at the root level only
+    const bool forced = (__builtin_amdgcn_readfirstlane(kind) & SEARCH_FORCED) != 0;
+    if (forced && is_inner(m.flags)) {
+        // Root-only pre-pass: a forced child scores FORCED_SCORE, above every other score, and the argmax takes the first maximum,
+        // so the root level's choice is the lowest forced index.  That child is found here, from rows the root level reads anyway,
+        // and handed to the loop below in the one place that is the root level's alone: its entry of rp becomes FORCED_PRIOR, under
+        // which its score (pb_c > 0: a forced child has n > 0, so N > 0) is beyond every other one.  The loop itself is untouched:
+        // no register and no instruction more at any level, and nothing at all with the rule off.
+        const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < NPL; j++) {
+            const int i = lane + WAVE * j;
+            const bool valid = i < A && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
+            const unsigned long long mk = __ballot(valid && forced_child(cfg.forced_k, rp[j], (int)(R.NS[j] & NS_MASK), root_N));
+            if (!found && mk != 0ull) {
+                if (lane == __ffsll((long long)mk) - 1) rp[j] = FORCED_PRIOR;
+                found = true;
+            }
+        }
+    }
     if (lane == 0) {
         if (vv) S->root_N = root_N + 1;
         if (is_inner(m.flags)) S->root_W = S->root_W - 1.0f; // current.total_value -= VIRTUAL_LOSS (root slot)
@@ -1580,7 +1606,9 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
         __syncthreads();
         __threadfence_block();
     }
-    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, fast);
+    // forced playouts belong to the driver's full searches (with the cap off every search is one)
+    const int kind = fast ? SEARCH_FAST : (cfg.forced_k > 0.0 ? SEARCH_FORCED | (cfg.forced_prune ? SEARCH_PRUNE : 0) : 0);
+    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, kind);
 }
 
 
@@ -1690,11 +1718,53 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
     }
     // ---- row of get_datasets for this root (self_play.py:107-117) ----
     const int r = S->n_rows;
+    const int kind = S->fast_search;
+    const bool prune = (kind & SEARCH_PRUNE) != 0;
     if (r < rcap) {
         int16_t *rx = B.row_x + ((size_t)slot * rcap + r) * F;
         for (int i = lane; i < F; i += WAVE) rx[i] = (int16_t)gs_feature(g, rm.st, i);
         int32_t *rv = B.row_vis + ((size_t)slot * rcap + r) * A;
-        for (int i = lane; i < A; i += WAVE) rv[i] = (int32_t)(NS0[i] & NS_MASK);
+        if (prune) {
+            // policy target pruning (forced_playouts.h; the rule is in include/dbaz.h): the move above came from the raw visits, the
+            // tree keeps them, the row gets n'.  c* = the first valid child with the most visits
+            int bn = -1, bi = 0x7fffffff;
+            for (int i = lane; i < A; i += WAVE) {
+                const int vc = (int)(NS0[i] & NS_MASK);
+                if (gs_valid(g, rm.st, i) && vc > bn) { bn = vc; bi = i; }
+            }
+            for (int o = 32; o > 0; o >>= 1) {
+                const int on = __shfl_xor(bn, o), oi = __shfl_xor(bi, o);
+                if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+            }
+            const int cs = __builtin_amdgcn_readfirstlane(bi);
+            const int root_N = S->root_N;
+            double pbc, sq; // what the next simulation of this root would read
+            select_tab(cfg, B, root_N, pbc, sq);
+            select_tab_fix(cfg, root_N, pbc, sq);
+            const double *rprior = B.root_prior + (size_t)slot * g.AS;
+            const float *W0 = reinterpret_cast<const float *>(node_ptr(pool, g, root) + META_DW + g.AS);
+            long long cut = 0;
+            if (bn >= 0) { // (a root without a valid child is terminal and never gets here)
+                const double ustar = forced_ustar(pbc, sq, rprior[cs], W0[cs], NS0[cs]); // one address for the wave
+                for (int i = lane; i < A; i += WAVE) {
+                    const uint32_t ns = NS0[i];
+                    const int vc = (int)(ns & NS_MASK);
+                    int np = vc;
+                    if (i != cs && vc > 0 && gs_valid(g, rm.st, i)) np = forced_pruned(cfg.forced_k, pbc, sq, root_N, rprior[i], W0[i], ns, ustar);
+                    rv[i] = np;
+                    cut += vc - np;
+                }
+            } else {
+                for (int i = lane; i < A; i += WAVE) rv[i] = (int32_t)(NS0[i] & NS_MASK);
+            }
+            for (int o = 32; o > 0; o >>= 1) cut += __shfl_xor(cut, o);
+            if (lane == 0) {
+                atomicAdd((unsigned long long *)B.moves_played + 3, 1ull);
+                atomicAdd((unsigned long long *)B.moves_played + 4, (unsigned long long)cut);
+            }
+        } else {
+            for (int i = lane; i < A; i += WAVE) rv[i] = (int32_t)(NS0[i] & NS_MASK);
+        }
         if (lane == 0) {
             RowMeta mm;
             mm.game_idx = (int32_t)S->game_idx;
@@ -1707,7 +1777,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             mm.q_value = S->root_W / (float)(1 + S->root_N); // TreeRoot.get_tree_stats, mcts.py:33-36
             mm.player = (int8_t)rm.st.to_play;
             mm.z = 0;
-            mm.flags = S->fast_search ? ROW_FLAG_FAST : 0;
+            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0);
             B.row_meta[(size_t)slot * rcap + r] = mm;
         }
         S->n_rows = r + 1;

@@ -49,6 +49,8 @@ class Engine:
     handed out on the device in ascending slot order and taken back when a game ends.  A slot that finds the pool dry searches
     that move with its model's own evaluator (table_pool()["denied"]; run() warns).  None: one region per slot.
     playout_cap=(full_prob, fast_reads): playout cap randomization (selfplay_set_playout_cap); None: off.
+    forced_playouts=(k, prune): forced playouts and policy target pruning at the root of the self-play driver's full searches
+    (selfplay_set_forced_playouts); None: off.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -59,7 +61,8 @@ class Engine:
                  temperature=None, reuse_tree=True, evaluator="formula", nodes_per_slot=0, seed=0, device=0,
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
-                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None):
+                 solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None,
+                 forced_playouts=None):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -124,6 +127,12 @@ class Engine:
         if playout_cap is not None:
             try:
                 self.selfplay_set_playout_cap(*playout_cap)
+            except Exception:
+                self.close()
+                raise
+        if forced_playouts is not None:
+            try:
+                self.selfplay_set_forced_playouts(*forced_playouts)
             except Exception:
                 self.close()
                 raise
@@ -426,6 +435,23 @@ class Engine:
         self._ck(self._L.dbaz_get_playout_cap(self.h, C.byref(p), C.byref(n), C.byref(a), C.byref(b)))
         return dict(full_prob=float(p.value), fast_reads=int(n.value), full_searches=int(a.value), fast_searches=int(b.value))
 
+    def selfplay_set_forced_playouts(self, k, prune=True):
+        """dbaz_selfplay_set_forced_playouts: forced playouts and policy target pruning (Wu 2019, section 3.2) for every later
+        selfplay_start.  In a full search of the self-play driver every visited root child gets at least sqrt(k P N) playouts;
+        with prune those are taken out of the recorded visits again wherever PUCT alone would not have spent them (the row's
+        bit 1 of "pad"; fetch_samples()["pruned"] is True).  The game, the tree, q_value and TreeStats are untouched by the
+        pruning.  k = 0: off (the default).  The rule is stated in full in include/dbaz.h; forced_playouts.prune_visits is its
+        second half on the host.  DbazError: EINVAL for k outside [0, 16], prune not a bool, a match_play handle or
+        selfplay_pending; ESTATE while games are being played; a failed call changes nothing."""
+        self._ck(self._L.dbaz_selfplay_set_forced_playouts(self.h, C.c_double(float(k)), int(prune)))
+
+    def forced_playouts(self):
+        """dbaz_get_forced_playouts: dict(k, prune, rows_pruned, visits_pruned) -- the setting (0.0, False when off) and the rows
+        pruning ran on and the visits it took out of them since the last selfplay_start, after the queued work is done."""
+        k, p, a, b = C.c_double(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self._L.dbaz_get_forced_playouts(self.h, C.byref(k), C.byref(p), C.byref(a), C.byref(b)))
+        return dict(k=float(k.value), prune=bool(p.value), rows_pruned=int(a.value), visits_pruned=int(b.value))
+
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
 
@@ -495,12 +521,20 @@ class Engine:
             # dbaz_fetch_samples keeps its 13 arrays: the column is the rule restated on the host from (seed, game, ply)
             from . import playout_cap as PC
             out["full"] = PC.is_full(self.cfg.seed, out["game_idx"], out["move_idx"], prob.value)
+        flags = out.pop("_flags")
+        prune = C.c_int32()
+        self._ck(self._L.dbaz_get_forced_playouts(self.h, None, C.byref(prune), None, None))  # the setting alone: no device work
+        if prune.value or (flags & 2).any():
+            out["pruned"] = (flags & 2) != 0  # ROW_FLAG_PRUNED, read from the rows themselves
         return out
 
     def _fetch_once(self):
         n = C.c_int32()
         self._ck(self._L.dbaz_fetch_samples(self.h, 0, C.byref(n), *([None] * 13)))
         m = n.value
+        flags = np.zeros(m, np.int16)  # the rows' flag words, in the order of the rows below (taken first: it drains nothing)
+        if m:
+            self._ck(self._L.dbaz_fetch_row_flags(self.h, m, C.byref(n), _p(flags)))
         out = dict(game_idx=np.zeros(m, np.int32), move_idx=np.zeros(m, np.int16), move=np.zeros(m, np.int16),
                    player=np.zeros(m, np.int8), x=np.zeros((m, self.F), np.int16), visits=np.zeros((m, self.A), np.int32),
                    pi=np.zeros((m, self.A), np.float64), z=np.zeros(m, np.int8), max_deepness=np.zeros(m, np.int16),
@@ -511,6 +545,7 @@ class Engine:
                 self.h, m, C.byref(n), _p(out["game_idx"]), _p(out["move_idx"]), _p(out["move"]), _p(out["player"]),
                 _p(out["x"]), _p(out["visits"]), _p(out["pi"]), _p(out["z"]), _p(out["max_deepness"]),
                 _p(out["tree_size"]), _p(out["terminal_count"]), _p(out["q_value"]), _p(out["played"])))
+        out["_flags"] = flags
         return out
 
     def replay_rows_dev(self):

@@ -75,7 +75,10 @@ def engine_kwargs_from_params(params, async_searches=False):
     suspends once per call, tests/test_hip_pending.py).
 
     params.self_play.playout_cap = {"full_prob": p, "fast_reads": n} (not a knob of the reference; absent = off) becomes
-    Engine(playout_cap=(p, n)): playout cap randomization, Engine.selfplay_set_playout_cap."""
+    Engine(playout_cap=(p, n)): playout cap randomization, Engine.selfplay_set_playout_cap.
+    params.self_play.forced_playouts = {"k": 2.0, "prune": True} (the same; absent = off) becomes Engine(forced_playouts=(k, prune)):
+    forced playouts and policy target pruning, Engine.selfplay_set_forced_playouts.  It is refused together with
+    async_searches=True and max_async_searches > 1 (self-play in waves)."""
     sp = _get(params, "self_play")
     m = _get(sp, "mcts")
     noise = _get(sp, "noise", [0.0, 0.0])
@@ -88,6 +91,9 @@ def engine_kwargs_from_params(params, async_searches=False):
     cap = _get(sp, "playout_cap")
     if cap is not None:
         kw["playout_cap"] = (float(_get(cap, "full_prob")), int(_get(cap, "fast_reads")))
+    forced = _get(sp, "forced_playouts")
+    if forced is not None:
+        kw["forced_playouts"] = (float(_get(forced, "k")), bool(_get(forced, "prune", True)))
     return kw
 
 
@@ -127,6 +133,9 @@ class SelfPlay:
         self.params = params
         self.engine = getattr(nn, "engine", nn)
         self.samples = None
+        forced = _get(_get(params, "self_play"), "forced_playouts")
+        if forced is not None:  # the engine was made elsewhere: the setting of the handle follows the parameters
+            self.engine.selfplay_set_forced_playouts(float(_get(forced, "k")), bool(_get(forced, "prune", True)))
 
     def play_games_sync(self, games_idxs, game_state=None):
         """game_state: the position every game starts from (self_play.py:51-55; None = the empty board); move_idx and the
@@ -240,6 +249,7 @@ assert ROW_META.itemsize == 28
 
 
 ROW_FLAGS_OFF, ROW_FLAG_FAST = 26, 1  # csrc/replay_row.h: the int16 "pad"; bit 0 = the row of a fast search of the playout cap
+ROW_FLAG_PRUNED = 2  # bit 1 = policy target pruning ran on the row: its visits (and pi) are the pruned ones
 
 
 def full_rows_only(samples):
@@ -406,6 +416,7 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     over = _get(elo_params, "self_play_override", {}) or {}
     kw = engine_kwargs_from_params(p0)
     kw.pop("playout_cap", None)  # the cap belongs to self-play: a match searches every move in full
+    kw.pop("forced_playouts", None)  # and so do forced playouts
     if "reuse_mcts_tree" in over:
         kw["reuse_tree"] = bool(_get(over, "reuse_mcts_tree"))
     if "noise" in over:
@@ -468,6 +479,7 @@ def solver_match(params, generation, n_games, rows, cols, openings=None, solver=
     # other model's priors, and the table's one-hot prior only binds the search from a root whose expansion was counted -- no noise
     kw.update(reuse_tree=False, noise=(0.0, 0.0))
     kw.pop("playout_cap", None)  # the cap belongs to self-play
+    kw.pop("forced_playouts", None)
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=model.kind, evaluator2="solver", match_play=True,
                  device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads, **kw)
     try:

@@ -279,6 +279,53 @@ int dbaz_selfplay_quickplay(dbaz_engine *e, const int32_t *plies, int32_t reads)
 int dbaz_selfplay_set_playout_cap(dbaz_engine *e, double full_prob, int32_t fast_reads);
 int dbaz_get_playout_cap(dbaz_engine *e, double *full_prob, int32_t *fast_reads, int64_t *full_searches, int64_t *fast_searches);
 int dbaz_playout_cap_is_full(uint64_t seed, int64_t game_idx, int32_t ply, double full_prob);
+/* Forced playouts and policy target pruning (Wu 2019, section 3.2) at the root of the self-play driver's full searches.
+ * Scope: the rule is active in a search iff k > 0 and the search is a full search of the driver (with the playout cap off every
+ * search of the driver is full).  Fast searches, explicit searches (dbaz_search*, dbaz_select) and match play never see it.
+ * All arithmetic below is float64, every operation rounded on its own (no fused multiply-add), in the order written.
+ *
+ * Forced playouts -- in the descent of a simulation, at the root level only, for a valid child c: with
+ *   n = the child's visit count as the UCB of this simulation reads it,
+ *   N = the root's own visit count as this simulation reads it (the N of its sqrt(N) and log terms; it restarts at 0 with
+ *       every move, tree reuse or not),
+ *   P = the child's float64 root prior (noise mixed in),
+ * the child is forced iff   n > 0   and   (double)n * (double)n < (k * P) * (double)N.
+ * A forced child's score is the constant 1e20 in place of prior_score + value_score; the argmax is the usual first maximum,
+ * so the lowest forced index is taken.  Unvisited children are never forced (the first visits go by PUCT), and below the root
+ * nothing changes.
+ *
+ * Pruning (prune = 1) -- when the driver records the row of such a search, after the move has been chosen from the raw visits:
+ * the row's visits become n' below; the move, the tree (whose kept subtree carries the raw counts on), q_value, TreeStats
+ * and z are what they would have been.  With N the root's visit count after the search, pbc = log((N + base + 1) / base) +
+ * cpuct and sq = sqrt(N) (the values the next simulation would read), W, n, sgn the root's child_total_value (float32),
+ * child_number_visits and +1 / -1 for a child whose player to move is / is not the root's:
+ *   value(c)   = ((double)W / (double)(1 + n)) * sgn
+ *   expl(c, m) = (pbc * (sq / (double)(m + 1))) * P
+ *   1. c* = the first valid child with the maximum visit count; it keeps its visits n*.
+ *   2. U* = expl(c*, n*) + value(c*).
+ *   3. every other valid child with n > 0:  f = the smallest integer >= 0 with (double)f * (double)f >= (k * P) * (double)N,
+ *      lo = max(0, n - f),  n' = the smallest integer m in [lo, n] with  expl(c, m) + value(c) < U*,  n' = n if there is none;
+ *      then, if n' < n and n' == 1, n' = 0.
+ *   4. every other child keeps its count (an unvisited or invalid one has 0).
+ * The predicate of step 3 is monotone in m.  The row's flag word gets bit 1 (ROW_FLAG_PRUNED, value 2) whenever pruning ran on
+ * it, also when nothing was cut.  With prune = 0 the search is forced, the raw visits are recorded and the bit stays clear.
+ *
+ * dbaz_selfplay_set_forced_playouts is a setting of the handle: it holds for every later dbaz_selfplay_start (not consumed).
+ * k = 0 switches the rule off (the state after dbaz_create; prune is then ignored and reads back 0).
+ *   k NaN, negative or above 16; prune outside {0, 1}; a match_play handle; a handle created with selfplay_pending   -> DBAZ_EINVAL
+ *     (self-play in waves would inherit the rule through the shared descent, and nothing pins forced children among in-flight
+ *     visits: the combination is refused)
+ *   games of an earlier dbaz_selfplay_start still being played                                                     -> DBAZ_ESTATE
+ * A failed call changes nothing.
+ * dbaz_get_forced_playouts: the setting, and the rows pruning ran on and the visits it took out of them (the sum of n - n')
+ * since the last dbaz_selfplay_start, which zeroes both.  Any output pointer may be NULL.
+ * dbaz_prune_visits: steps 1-4 on the host -- no handle, no device -- from the very code the driver runs.  n_and_sign[i] =
+ * n | (sgn > 0 ? 0x40000000 : 0); valid[i] != 0 for a valid child; out[i] = n'.  k = 0 copies the counts.  n_actions outside
+ * 1 .. DBAZ_MAX_A, k outside [0, 16], root_N < 0 or a NULL pointer -> DBAZ_EINVAL. */
+int dbaz_selfplay_set_forced_playouts(dbaz_engine *e, double k, int32_t prune);
+int dbaz_get_forced_playouts(dbaz_engine *e, double *k, int32_t *prune, int64_t *rows_pruned, int64_t *visits_pruned);
+int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double sq, int64_t root_N, const double *P, const float *W,
+                      const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
 int dbaz_step(dbaz_engine *e, int32_t k);             /* k simulation steps, asynchronous */
 /* until all games are finished, max_steps (if > 0) are done, or every remaining slot is
  * blocked on a full output buffer (counters.blocked_slots == active_slots: fetch and call again) */
@@ -293,6 +340,9 @@ int dbaz_fetch_samples(dbaz_engine *e, int32_t max_rows, int32_t *n_rows,
                        int16_t *x /*[rows*3HW]*/, int32_t *visits /*[rows*A]*/, double *pi /*[rows*A]*/,
                        int8_t *z, int16_t *max_deepness, int32_t *tree_size, int32_t *terminal_count,
                        float *q_value, int16_t *played);
+/* The flag words (the int16 at byte 26 of a packed row: bit 0 = row of a fast search, bit 1 = pruned visits) of the rows
+ * dbaz_fetch_samples would hand out now, in its order.  Drains nothing: call it first.  max_rows = 0: the count alone. */
+int dbaz_fetch_row_flags(dbaz_engine *e, int32_t max_rows, int32_t *n_rows, int16_t *flags);
 /* device-resident replay rows for the RCCL all-gather (multi-GPU iteration end):
  * fixed-stride packed rows, see DESIGN.md "replay row".  Returns a DEVICE pointer. */
 int dbaz_replay_rows_dev(dbaz_engine *e, void **rows_dev, int32_t *n_rows, int32_t *row_bytes);
