@@ -43,7 +43,7 @@ SYMBOLS = [
     "dbaz_tables_last_error", "dbaz_tables_create", "dbaz_tables_destroy", "dbaz_tables_solve", "dbaz_tables_info", "dbaz_tables_roots",
     "dbaz_tables_table", "dbaz_tables_score", "dbaz_tables_targets", "dbaz_replay_exact_targets",
     "dbaz_attach_tables", "dbaz_get_slot_table",
-    "dbaz_attach_tables_pool", "dbaz_get_table_pool", "dbaz_get_slot_table_index",
+    "dbaz_attach_tables_pool", "dbaz_get_table_pool", "dbaz_get_slot_table_index", "dbaz_attach_tables_pool_wait", "dbaz_get_table_pool_waits",
 ]
 
 
@@ -230,6 +230,8 @@ def load():
     L.dbaz_get_slot_table.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), vp, vp, i64, i64]
     L.dbaz_attach_tables_pool.argtypes = [vp, i32, vp, i32, C.c_uint64, i32]
     L.dbaz_get_table_pool.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    L.dbaz_attach_tables_pool_wait.argtypes = [vp, i32, vp, i32, C.c_uint64, i32]
+    L.dbaz_get_table_pool_waits.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.dbaz_get_slot_table_index.argtypes = [vp, i32, C.POINTER(i32)]
     for name in SYMBOLS:
         fn = getattr(L, name)

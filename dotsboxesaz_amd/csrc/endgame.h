@@ -44,10 +44,17 @@ struct EndgameSlotHdr {
     int32_t model;
     int32_t table;                           // the region of `tables` that holds it: the slot's own (k_endgame_table, dbaz_attach_tables),
                                              // or one of the engine's pool (dbaz_attach_tables_pool; -1 there: the slot holds none)
+    // dbaz_attach_tables_pool_wait only (0 otherwise).  ENDGAME_WAITING: the slot's solve request found the pool dry and stands;
+    // k_select / k_select_multi leave the slot alone.  > 0: the engine step of the pass that granted it a region and solved its
+    // table -- that pass runs next to k_select of the same step, which leaves the slot alone once more (tree.hip, set_phase_stamped)
+    int32_t wait;
+    int32_t pad;
     // sized for the deep attach (dbaz_attach_tables, k_slot_requests in solver.hip): k_endgame_table fills 16 entries at the most
     uint32_t other[SOLVER_MAX_E][2];         // solver_move_q's box masks over the compact edges
     uint8_t act[SOLVER_MAX_E];               // compact edge -> action index
 };
+
+#define ENDGAME_WAITING (-1) // EndgameSlotHdr::wait
 
 // what the search side asks (tree.hip): does the slot's table serve the leaves of a search of game `game`
 __host__ __device__ __forceinline__ bool endgame_hdr_serves(const EndgameSlotHdr &h, int64_t game) { return h.valid != 0 && h.game == game; }

@@ -59,6 +59,8 @@ struct dbaz_engine {
     SlotTables slot_tables = SlotTables();
     // dbaz_attach_tables_pool: eg_tables is eg_n_tables regions that the slots share (0: one region per slot, region == slot)
     int eg_n_tables = 0;
+    // dbaz_attach_tables_pool_wait: a slot that finds the pool dry waits for a region (a handle's pooled attaches are all of one mode)
+    bool eg_wait = false;
     // staging (device) for the boundary
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -646,7 +648,7 @@ static hipEvent_t next_event(dbaz_engine *e)
 static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
 {
     if (e->eg_deep) { // a fixed launch sequence (slot_tables_plan.h): nothing is read back
-        slot_tables_pass(&e->slot_tables, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats);
+        slot_tables_pass(&e->slot_tables, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats, e->sc.step);
         return;
     }
     const dbaz_endgame *g = e->endgame[0] ? e->endgame[0] : e->endgame[1];
@@ -795,6 +797,15 @@ static int upload_search_inputs(dbaz_engine *e, const int32_t *num_reads, const 
     return DBAZ_OK;
 }
 
+// Wait mode of the pool of tables: only the self-play driver gives regions back (a game that ends), so a slot of an explicit
+// search that found the pool dry would wait for ever.
+static int refuse_waiting_pool(dbaz_engine *e, const char *entry)
+{
+    if (!e->eg_wait) return DBAZ_OK;
+    return set_error(e, DBAZ_ESTATE, "%s: this handle's pool of tables is in wait mode (dbaz_attach_tables_pool_wait), which serves the self-play "
+                     "driver only (dbaz_run, dbaz_step): nothing gives a region back during an explicit search", entry);
+}
+
 static int count_phases(dbaz_engine *e, int32_t out[4])
 {
     HIP_CHECK_RET(e, hipMemsetAsync(e->d_small, 0, 16, e->stream));
@@ -808,6 +819,7 @@ extern "C" int dbaz_search_begin(dbaz_engine *e, const int32_t *num_reads, const
 {
     if (!e) return DBAZ_EINVAL;
     USE_DEVICE(e);
+    if (int r = refuse_waiting_pool(e, "dbaz_search_begin")) return r;
     if (e->selfplay) return set_error(e, DBAZ_ESTATE, "self-play in progress; call dbaz_set_positions first");
     const int32_t *d_reads;
     int r = upload_search_inputs(e, num_reads, noise, &d_reads);
@@ -903,9 +915,9 @@ static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
 // bytes of a slot's region (at least 2^max_free), deep the dbaz_tables whose passes solve the slots (nullptr: a dbaz_endgame's
 // k_endgame_table does).  A handle's attaches are all of one kind and one stride: the slot regions are sized by the first attach
 // and never resized.  n_tables > 0: the pooled form of the deep attach, that many regions shared by the slots -- a kind of its
-// own, with one n_tables per handle.  A refused attach changes nothing.
+// own, with one n_tables per handle and one mode: wait (dbaz_attach_tables_pool_wait) or deny.  A refused attach changes nothing.
 static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, dbaz_tables *deep, int n_tables, int max_free, size_t stride,
-                              uint64_t pick_seed, int32_t endgame_reads)
+                              uint64_t pick_seed, int32_t endgame_reads, bool wait = false)
 {
     if (model < 0 || model > 1) return set_error(e, DBAZ_EINVAL, "model must be 0 or 1");
     const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
@@ -920,9 +932,12 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
                          e->eg_n_tables ? "a pool shared by the slots (dbaz_attach_tables_pool)" : "one region per slot (dbaz_attach_tables)");
     if (e->eg_tables && n_tables != e->eg_n_tables)
         return set_error(e, DBAZ_EINVAL, "n_tables %d: this handle's pool has %d regions (the n_tables of its first attach)", n_tables, e->eg_n_tables);
+    if (e->eg_tables && wait != e->eg_wait)
+        return set_error(e, DBAZ_EINVAL, "a %s: this handle's pool of tables %s: a handle's pooled attaches are all of one mode", kind,
+                         e->eg_wait ? "lets a slot wait for a region (dbaz_attach_tables_pool_wait)" : "denies a slot that finds it dry (dbaz_attach_tables_pool)");
     // begin_search caps the reads before the pass knows whether the slot gets a region: a denied search would run on the model's
-    // evaluator with a handful of reads
-    if (n_tables > 0 && endgame_reads > 0)
+    // evaluator with a handful of reads.  In wait mode no search is denied, and the cap is right again.
+    if (n_tables > 0 && endgame_reads > 0 && !wait)
         return set_error(e, DBAZ_EINVAL, "endgame_reads %d: the pooled attach takes no read cap (a slot that is denied a table searches with its "
                          "model's evaluator)", endgame_reads);
     if (e->eg_tables && stride != e->eg_stride)
@@ -939,7 +954,7 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
         SlotTables st = SlotTables();
         void *lists[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (deep)
-            if (int rc = slot_tables_setup(deep, e->n_slots, n_tables, &st, lists)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
+            if (int rc = slot_tables_setup(deep, e->n_slots, n_tables, &st, lists, wait)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
         void *p[6];
         hipError_t err = hipSuccess;
         const int n_regions = n_tables > 0 ? n_tables : e->n_slots;
@@ -955,6 +970,8 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
         e->slot_tables = st;
         e->eg_deep = deep != nullptr;
         e->eg_n_tables = n_tables;
+        e->eg_wait = wait;
+        e->G.wait = wait ? 1 : 0;
         e->eg_start.release = n_tables > 0 ? 1 : 0;
         if (n_tables > 0) { // no header names a region yet
             slot_tables_pool_reset(&e->slot_tables, e->stream, e->eg_hdr, e->n_slots);
@@ -1010,6 +1027,38 @@ extern "C" int dbaz_attach_tables_pool(dbaz_engine *e, int32_t model, dbaz_table
         return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
                          e->cfg.device);
     return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
+}
+
+// The pool in wait mode (the rule is stated in full in include/dbaz.h): a slot that finds it dry waits for a region.
+extern "C" int dbaz_attach_tables_pool_wait(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
+    if (n_tables < 1 || n_tables > e->n_slots)
+        return set_error(e, DBAZ_EINVAL, "n_tables %d: a pool has 1 .. n_slots = %d regions", n_tables, e->n_slots);
+    int max_free = 0;
+    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
+                         e->cfg.device);
+    return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads, true);
+}
+
+extern "C" int dbaz_get_table_pool_waits(dbaz_engine *e, int32_t *wait_mode, int32_t *waiting, int64_t *waited)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    int32_t use = 0, high = 0, now = 0;
+    int64_t den = 0, total = 0;
+    if (e->eg_n_tables) {
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        HIP_CHECK_RET(e, slot_tables_pool_read(&e->slot_tables, &use, &high, &den, &now, &total));
+    }
+    if (wait_mode) *wait_mode = e->eg_n_tables && e->eg_wait ? 1 : 0;
+    if (waiting) *waiting = now;
+    if (waited) *waited = total;
+    return DBAZ_OK;
 }
 
 extern "C" int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *in_use, int32_t *high_water, int64_t *denied)
@@ -1092,6 +1141,7 @@ extern "C" void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_sol
 extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const double *noise, double time_limit_s)
 {
     if (!e) return DBAZ_EINVAL;
+    if (int r = refuse_waiting_pool(e, "dbaz_search_timed")) return r;
     if (int r = search_preconditions(e, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup")) return r;
     // end_time = time.time() + (time_limit or 120), mcts.py:201-203
     const auto t_end = std::chrono::steady_clock::now() + std::chrono::duration<double>(time_limit_s > 0 ? time_limit_s : 120.0);
@@ -1125,6 +1175,7 @@ extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const
 extern "C" int dbaz_search(dbaz_engine *e, const int32_t *num_reads, const double *noise)
 {
     if (!e) return DBAZ_EINVAL;
+    if (int r = refuse_waiting_pool(e, "dbaz_search")) return r;
     if (int r = search_preconditions(e, "external evaluator: use dbaz_search_begin/dbaz_select/dbaz_expand_backup")) return r;
     int r = dbaz_search_begin(e, num_reads, noise);
     if (r) return r;
@@ -1148,6 +1199,7 @@ extern "C" int dbaz_select(dbaz_engine *e, int32_t *n_active, int16_t *leaf_x, u
 {
     if (!e || !n_active || !leaf_x || !need_eval) return e ? set_error(e, DBAZ_EINVAL, "null argument") : DBAZ_EINVAL;
     USE_DEVICE(e);
+    if (int r = refuse_waiting_pool(e, "dbaz_select")) return r;
     if (!e->search_open) return set_error(e, DBAZ_ESTATE, "dbaz_search_begin not called");
     const Geo &g = e->g;
     const size_t F = 3 * g.HW, ns = e->n_slots;

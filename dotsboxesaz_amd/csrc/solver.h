@@ -151,19 +151,23 @@ struct SlotTables {
     int32_t n_tables;
     void *pool_dev;                   // TablePoolState, the free stack int32 [n_tables] behind it
     uint8_t *ask_dev;                 // [n_slots] of the running pass: the slot needs a region for its solve
+    int32_t wait_mode;                // 1 (dbaz_attach_tables_pool_wait): a slot that finds the pool dry waits for a region
 };
 bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *max_free);
 // Uploads what the passes need for every F <= max_free and fills *st; n_tables > 0: the pooled form with that many regions, all
 // free.  The device buffers it allocated come back in allocs[6] (four, and two more for the pool; the rest nullptr; the caller
-// frees them).  DBAZ_OK, or an error code with the message in dbaz_tables_last_error(t) and nothing kept.
-int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st, void *allocs[6]);
+// frees them).  wait: the pool's wait mode (table_pool.h).  DBAZ_OK, or an error code with the message in
+// dbaz_tables_last_error(t) and nothing kept.
+int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st, void *allocs[6], bool wait = false);
 // One pass on `stream`: every slot with a request keeps, drops or re-solves its table (slot_request_rule, endgame.h); S + 1 launches,
 // nothing read back.  stats [2] as for endgame_tables.  The pooled form: S + 3 launches -- regions given back (a drop, or a game
 // that ended) are free before any is granted, grants go to the asking slots in ascending slot order, a slot left without one is
-// denied and counted, and its header stays invalid.
+// denied and counted, and its header stays invalid.  In wait mode it is not denied: its request stands, its header says
+// ENDGAME_WAITING, and the pass that grants it a region leaves `step` there (the engine step the pass belongs to; endgame.h).
 void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
-                      unsigned long long *stats);
+                      unsigned long long *stats, int step = 0);
 // the pooled form at a clear-all point, after the headers were zeroed on `stream`: every region free, every header's table -1
 void slot_tables_pool_reset(SlotTables *st, hipStream_t stream, EndgameSlotHdr *hdr, int n_slots);
 // the pool's figures as they are on the device now (the caller has waited for the queued work); all 0 for the per-slot form
-hipError_t slot_tables_pool_read(const SlotTables *st, int32_t *in_use, int32_t *high_water, int64_t *denied);
+hipError_t slot_tables_pool_read(const SlotTables *st, int32_t *in_use, int32_t *high_water, int64_t *denied, int32_t *waiting = nullptr,
+                                 int64_t *waited = nullptr);

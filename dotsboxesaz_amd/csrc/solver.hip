@@ -1476,13 +1476,15 @@ static __device__ __forceinline__ uint32_t slot_box_other(const TablesBoard &B, 
 // (endgame.h) keeps or drops the table, or the slot gets a new header -- F0, the free-edge set, act and `other` as
 // position_geometry builds them, the real edges and box neighbours from the board alone -- and its BatchGeo goes on the pass's list.  Lane l looks at action slots l, 64 + l, ...; a free one writes its compact edge's entries.
 // POOLED (dbaz_attach_tables_pool): k_pool_decide and k_pool_grant have run, so every request still standing is a solve, into the
-// region the header names; a slot whose header names none was denied, and its header stays invalid.
+// region the header names; a slot whose header names none was denied, and its header stays invalid.  wait_mode
+// (dbaz_attach_tables_pool_wait): such a slot waits instead -- its request stays standing for the next pass and its header says
+// ENDGAME_WAITING, so that the search leaves it alone; the pass that solves a slot's table leaves its step there (endgame.h).
 #define SLOT_REQ_WAVES 4
 template <bool POOLED>
 __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
                                                                        EndgameSlotHdr *__restrict__ hdr, int n_slots, BatchGeo *__restrict__ geo,
                                                                        uint32_t *__restrict__ count, uint32_t *__restrict__ count_next,
-                                                                       unsigned long long *__restrict__ stats)
+                                                                       unsigned long long *__restrict__ stats, int wait_mode, int step)
 {
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) *count_next = 0u; // nobody reads it before the next pass
@@ -1498,14 +1500,16 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
         const int model = rq->model;
         const SlotDecision d = slot_request_rule(fe, h->valid, h->game, h->free_edges, game, max_free);
         const int F = d.F;
+        const int table = POOLED ? h->table : slot;
+        const bool waits = POOLED && wait_mode && d.solve && table < 0; // the pool is dry: the request stands
         if (lane == 0) {
-            rq->want = 0;
+            if (!waits) rq->want = 0;
             h->model = model;
             if (!d.keep && !d.solve) h->valid = 0;
+            if (waits) h->wait = ENDGAME_WAITING;
         }
         if (!d.solve) continue;
-        const int table = POOLED ? h->table : slot;
-        if (POOLED && table < 0) continue; // denied: the leaves of this search go to the model's own evaluator
+        if (POOLED && table < 0) continue; // denied: the leaves of this search go to the model's own evaluator (or the slot waits)
 
         uint32_t at = 0;
         if (lane == 0) at = atomicAdd(count, 1u);
@@ -1544,6 +1548,7 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
             h->game = game;
             h->F0 = F;
             if (!POOLED) h->table = table;
+            if (POOLED && wait_mode) h->wait = step; // k_select of this very step leaves the slot alone (0: no step runs next to this pass)
             h->valid = 1; // the table is complete before anything later on this stream reads it
             atomicAdd(stats, 1ull);
         }
@@ -1554,7 +1559,8 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_slot_requests(TablesBoa
 // k_pool_decide, one wavefront per slot with a request: slot_request_rule as above.  A keep is finished here; a drop and a release
 // request (EndgameReq::want == 2, left by the driver when the slot's game ended) invalidate the header and push the slot's region
 // back on the free stack -- the position comes from one atomic, so the stack's order is not reproducible, which changes no
-// result; a solve stays standing for k_slot_requests, and ask[slot] says whether the slot needs a region for it.
+// result; a solve stays standing for k_slot_requests, and ask[slot] says whether the slot needs a region for it.  In wait mode the
+// request of a waiting slot is still standing and is decided again like a new one; a release or a drop ends its wait.
 __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_pool_decide(TablesBoard B, int max_free, EndgameReq *__restrict__ req,
                                                                      EndgameSlotHdr *__restrict__ hdr, int n_slots, TablePoolState *__restrict__ pool,
                                                                      int32_t *__restrict__ stack, uint8_t *__restrict__ ask)
@@ -1583,6 +1589,7 @@ __global__ void __launch_bounds__(64 * SLOT_REQ_WAVES) k_pool_decide(TablesBoard
             if (!d.keep && !d.solve) {
                 h->valid = 0;
                 h->table = -1;
+                if (pool->wait_mode) h->wait = 0;
                 if ((unsigned)held < (unsigned)n_tables) {
                     const int at = atomicAdd(&pool->top, 1);
                     if ((unsigned)at < (unsigned)n_tables) stack[at] = held; // every region is held or on the stack, never both
@@ -1637,7 +1644,10 @@ __global__ void __launch_bounds__(256) k_pool_reset(EndgameSlotHdr *__restrict__
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_slots) hdr[i].table = -1;
     if (i < n_tables) stack[i] = table_pool_initial(n_tables, i);
-    if (i == 0) pool->top = n_tables;
+    if (i == 0) {
+        pool->top = n_tables;
+        pool->waiting = 0; // the zeroed headers and requests: nobody waits
+    }
 }
 
 // Launch s of a pass: for every listed root its own layer k = top(F) - s (k < 0: the root is finished).  The fixed grid strides
@@ -1674,7 +1684,7 @@ bool tables_serves(const dbaz_tables *t, int rows, int cols, int device, int *ma
     return t->board.rows == rows && t->board.cols == cols && t->dev == device;
 }
 
-int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st, void *allocs[6])
+int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st, void *allocs[6], bool wait)
 {
     SlotTablesPlan plan;
     if (slot_tables_plan(t->max_free, plan) != 0) return fail(t->err, DBAZ_EINVAL, "slot tables: max_free %d is outside 0 .. %d", t->max_free, SOLVER_MAX_E);
@@ -1731,6 +1741,7 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st,
         failed = 4;
         TablePoolState ps = TablePoolState();
         ps.n_tables = ps.top = n_tables;
+        ps.wait_mode = wait ? 1 : 0;
         std::vector<int32_t> stack((size_t)n_tables);
         for (int i = 0; i < n_tables; i++) stack[(size_t)i] = table_pool_initial(n_tables, i);
         e = hipMemcpy(p[4], &ps, sizeof ps, hipMemcpyHostToDevice);
@@ -1770,12 +1781,13 @@ int slot_tables_setup(dbaz_tables *t, int n_slots, int n_tables, SlotTables *st,
     st->n_tables = n_tables;
     st->pool_dev = p[4];
     st->ask_dev = (uint8_t *)p[5];
+    st->wait_mode = n_tables > 0 && wait ? 1 : 0;
     for (int i = 0; i < 6; i++) allocs[i] = p[i];
     return DBAZ_OK;
 }
 
 void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, EndgameSlotHdr *hdr, int8_t *tables, int n_slots,
-                      unsigned long long *stats)
+                      unsigned long long *stats, int step)
 {
     const TablesBoard B = tables_board(st->rows, st->cols);
     uint32_t *count = st->count_dev + (st->pass & 1u), *count_next = st->count_dev + ((st->pass + 1u) & 1u);
@@ -1788,10 +1800,10 @@ void slot_tables_pass(SlotTables *st, hipStream_t stream, EndgameReq *req, Endga
         k_pool_decide<<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, pool, stack, st->ask_dev);
         k_pool_grant<<<1, TABLE_POOL_GROUP, 0, stream>>>(hdr, n_slots, pool, stack, st->ask_dev);
         k_slot_requests<true><<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next,
-                                                                          stats);
+                                                                          stats, st->wait_mode, step);
     } else {
         k_slot_requests<false><<<blocks, 64 * SLOT_REQ_WAVES, 0, stream>>>(B, st->max_free, req, hdr, n_slots, (BatchGeo *)st->geo_dev, count, count_next,
-                                                                           stats);
+                                                                           stats, 0, 0);
     }
     for (int s = 0; s < st->n_launches; s++) {
         // never more workgroups than (root, item) pairs the launch can have
@@ -1808,12 +1820,14 @@ void slot_tables_pool_reset(SlotTables *st, hipStream_t stream, EndgameSlotHdr *
     k_pool_reset<<<(std::max(n_slots, st->n_tables) + 255) / 256, 256, 0, stream>>>(hdr, n_slots, pool, (int32_t *)(pool + 1), st->n_tables);
 }
 
-hipError_t slot_tables_pool_read(const SlotTables *st, int32_t *in_use, int32_t *high_water, int64_t *denied)
+hipError_t slot_tables_pool_read(const SlotTables *st, int32_t *in_use, int32_t *high_water, int64_t *denied, int32_t *waiting, int64_t *waited)
 {
     TablePoolState ps = TablePoolState();
     hipError_t e = st->n_tables > 0 ? hipMemcpy(&ps, st->pool_dev, sizeof ps, hipMemcpyDeviceToHost) : hipSuccess;
     *in_use = ps.n_tables - ps.top;
     *high_water = ps.high_water;
     *denied = ps.denied;
+    if (waiting) *waiting = ps.waiting;
+    if (waited) *waited = ps.waited;
     return e;
 }

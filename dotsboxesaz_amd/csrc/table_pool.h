@@ -6,6 +6,11 @@
 // (in any order: which region a slot receives changes no result), then grants: the asking slots are ranked in ascending slot
 // order, and the slot of rank r takes the r-th region from the top of the stack as long as regions last.  A slot that asks and
 // gets nothing is denied and counted; nothing waits for a later pass.
+//
+// Wait mode (dbaz_attach_tables_pool_wait, TablePoolState::wait_mode): such a slot is not denied.  Its request stays standing, so
+// every later pass ranks it with that pass's askers under the same rule -- the caller keeps its flag in `ask` raised -- until a
+// region is free for it.  The grants are the same function of (free regions, asking flags); only the count of the unserved goes
+// into `waited` (slot-passes spent waiting, cumulative) and `waiting` (the unserved of the last pass) instead of `denied`.
 #pragma once
 
 #include <stdint.h>
@@ -23,8 +28,11 @@ struct TablePoolState {
     int32_t n_tables;
     int32_t top;        // free regions
     int32_t high_water; // the most regions held at once
+    int32_t wait_mode;  // 1: an asking slot that gets nothing waits (its request stands); 0: it is denied
+    int64_t denied;     // asking slots that got nothing (wait_mode 0)
+    int64_t waited;     // wait_mode 1: what `denied` would have counted -- slot-passes spent waiting
+    int32_t waiting;    // wait_mode 1: the slots left waiting by the last pass
     int32_t pad;
-    int64_t denied;     // asking slots that got nothing
 };
 
 // the stack after a clear-all: every region free, region 0 on top
@@ -39,7 +47,12 @@ TABLE_POOL_HD void table_pool_settle(TablePoolState &s, int64_t n_asking)
 {
     const int32_t granted = n_asking < (int64_t)s.top ? (int32_t)n_asking : s.top;
     s.top -= granted;
-    s.denied += n_asking - granted;
+    if (s.wait_mode) {
+        s.waited += n_asking - granted;
+        s.waiting = (int32_t)(n_asking - granted);
+    } else {
+        s.denied += n_asking - granted;
+    }
     const int32_t in_use = s.n_tables - s.top;
     if (in_use > s.high_water) s.high_water = in_use;
 }

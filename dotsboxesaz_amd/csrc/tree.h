@@ -50,6 +50,7 @@ struct EndgameBufs {
     int32_t *list;             // [n_slots * kmax] slots, or slot * kmax + k in a wave
     int32_t *leaf;             // [n_slots * kmax] 1 = the leaf (of simulation k) is answered from the table
     int32_t model[2];          // 1 = the model has an endgame solver attached
+    int32_t wait;              // 1 (dbaz_attach_tables_pool_wait) = a slot may be waiting for a region of the pool: see endgame_slot_waits
 };
 
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,

@@ -807,6 +807,17 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
 #define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
 #define SEL_ENDGAME 3          // select_one: the leaf is answered from the slot's endgame table (eg_list)
 
+// The pool of tables in wait mode (dbaz_attach_tables_pool_wait): a slot whose search found the pool dry selects nothing until a
+// pass grants it a region (EndgameSlotHdr::wait == ENDGAME_WAITING) -- its reads and its tree stay as begin_search left them.  The
+// pass that wakes it leaves its step there, like set_phase_stamped: where it runs next to this step's selection, the slot -- whose
+// table that pass is still solving -- takes its first selection in the next step, behind the join.
+__device__ __forceinline__ bool endgame_slot_waits(const SearchCfg &cfg, const EndgameBufs &G, int slot)
+{
+    if (!G.hdr || !G.wait) return false;
+    const int w = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile const int32_t *>(&G.hdr[slot].wait));
+    return w == ENDGAME_WAITING || (w == cfg.step && cfg.driver_concurrent);
+}
+
 // returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, SEL_ENDGAME, or -1
 template <int NPL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
@@ -818,6 +829,8 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
         return -1;
     if (stamp == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
+        return -1;
+    if (endgame_slot_waits(cfg, G, slot))
         return -1;
     if (cfg.eval_round > 0 && S->pending) {
         // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
@@ -1078,6 +1091,7 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
+    if (endgame_slot_waits(cfg, G, slot)) return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
     const int A = g.A, K = B.kmax;
     int width = min(max(cfg.pending, 1), K);

@@ -962,16 +962,19 @@ def _selfplay_bench(a):
     of a.repeats runs after one warm-up run.  --max-free M > 16: three engines -- plain, Endgame(16) and DeepTables(max_free=M)
     attached -- each with the table_bytes of its slot tables.  --pool N adds a fourth, DeepTables(max_free=M) with a pool of N tables
     shared by the slots (Engine(endgame_tables=N)): its high_water, denied and the pool's table_bytes.  deep=0 with --pool leaves
-    the per-slot deep engine out (its n_slots << M bytes may not fit where the pool does)."""
+    the per-slot deep engine out (its n_slots << M bytes may not fit where the pool does).  --wait adds the pool in wait mode
+    (Engine(endgame_wait=True)), with --endgame-reads if given -- the deny-mode pool takes no read cap and runs without one: its
+    waited slot-passes, the peak of the slots waiting at once (looked at every 256 steps), evaluations per game and games/s."""
     import sys
     import time
     import torch
     from . import nn as dnn
     from .engine import Engine
 
-    def play(g, pool=None):
+    def play(g, pool=None, wait=False):
+        peak_waiting = 0
         eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=a.reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
-                     device=a.device, endgame=g, endgame_reads=a.endgame_reads, endgame_tables=pool)
+                     device=a.device, endgame=g, endgame_reads=0 if pool and not wait else a.endgame_reads, endgame_tables=pool, endgame_wait=wait)
         torch.manual_seed(0)
         model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
         eng.load_state_dict(model.state_dict(), "resnet", **model.shape)
@@ -981,21 +984,30 @@ def _selfplay_bench(a):
             eng.sync()
             t0 = time.perf_counter()
             eng.selfplay_start(a.selfplay_bench, 0)
-            eng.run()
+            if wait:  # in pieces, to see how many slots wait at once
+                while eng.counters()["active_slots"]:
+                    eng.run(max_steps=256)
+                    if eng.counters()["blocked_slots"]:
+                        eng._drained.append(eng._fetch_once())
+                    peak_waiting = max(peak_waiting, eng.table_pool_waits()["waiting"])
+            else:
+                eng.run()
             n_rows = len(eng.fetch_samples()["z"])
             dt = time.perf_counter() - t0
             c = eng.counters()
-            print("selfplay-bench: %s%s run %d of %d, %.1f s" % (type(g).__name__, " pool %d" % pool if pool else "", i, a.repeats, dt),
+            print("selfplay-bench: %s%s%s run %d of %d, %.1f s" % (type(g).__name__, " pool %d" % pool if pool else "", " wait" if wait else "", i, a.repeats, dt),
                   file=sys.stderr, flush=True)
             if i:  # the first run warms up
                 runs.append(dict(games_per_s=c["games_finished"] / dt, nn_evals_per_game=c["nn_evals"] / max(1, c["games_finished"]),
                                  rows_per_game=n_rows / max(1, c["games_finished"]), tables_solved=eng.endgame_stats()[0] - solved0,
                                  seconds=dt))
-        tp = eng.table_pool()
+        tp, tw = eng.table_pool(), eng.table_pool_waits()
         eng.close()
         out = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
         if pool:  # counted over the warm-up and the timed runs together
             out.update(high_water=tp["high_water"], denied=tp["denied"], in_use_at_end=tp["in_use"])
+        if wait:
+            out.update(waited=tw["waited"], peak_waiting=peak_waiting, waiting_at_end=tw["waiting"], endgame_reads=a.endgame_reads)
         return out
 
     if a.max_free > MAX_FREE:
@@ -1005,6 +1017,8 @@ def _selfplay_bench(a):
                    plain=dict(play(None), table_bytes=0), endgame16=dict(play(g), table_bytes=a.slots << MAX_FREE))
         if a.pool > 0:
             out["pooled"] = dict(play(d, a.pool), n_tables=a.pool, table_bytes=a.pool << d.max_free)
+            if a.wait:  # no search is denied: the games of the per-slot deep engine, at the price of idle slot-passes
+                out["pooled_wait"] = dict(play(d, a.pool, True), n_tables=a.pool, table_bytes=a.pool << d.max_free)
         if a.pool <= 0 or a.per_slot_deep:
             out["deep"] = dict(play(d), table_bytes=a.slots << d.max_free)
         best = out["deep"] if "deep" in out else out["pooled"]
@@ -1059,6 +1073,8 @@ def main(argv=None):
     ap.add_argument("--slots", type=int, default=0, help="--selfplay-bench: engine slots (default min(N, 8192))")
     ap.add_argument("--pool", type=int, default=0, metavar="N",
                     help="--selfplay-bench with --max-free > 16: a fourth engine whose slots share a pool of N deep tables")
+    ap.add_argument("--wait", action="store_true",
+                    help="--selfplay-bench with --pool: a further engine whose pool is in wait mode (a slot that finds it dry waits for a table)")
     ap.add_argument("--per-slot-deep", type=int, default=1,
                     help="--selfplay-bench with --pool: 0 leaves out the engine with one deep table per slot (slots << max_free bytes)")
     ap.add_argument("--reads", type=int, default=800, help="--selfplay-bench: mcts_num_read")

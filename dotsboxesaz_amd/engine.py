@@ -48,6 +48,10 @@ class Engine:
     endgame_tables=N with a DeepTables (dbaz_attach_tables_pool): N regions of 2^M bytes that the slots share, 1 <= N <= n_slots,
     handed out on the device in ascending slot order and taken back when a game ends.  A slot that finds the pool dry searches
     that move with its model's own evaluator (table_pool()["denied"]; run() warns).  None: one region per slot.
+    endgame_wait=True with endgame_tables=N (dbaz_attach_tables_pool_wait): a slot that finds the pool dry waits for a region
+    instead -- it selects nothing until a game that ends gives one back -- so no search is denied, the rows are those of
+    endgame_tables=None for every N >= 1, and endgame_reads may be given.  The idle slot-passes are table_pool_waits()["waited"].
+    Self-play and match play only: search() and search_timed() are refused (ESTATE) on such an Engine.
     playout_cap=(full_prob, fast_reads): playout cap randomization (selfplay_set_playout_cap); None: off.
     forced_playouts=(k, prune): forced playouts and policy target pruning at the root of the self-play driver's full searches
     (selfplay_set_forced_playouts); None: off.
@@ -62,7 +66,7 @@ class Engine:
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
                  solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None,
-                 forced_playouts=None):
+                 forced_playouts=None, endgame_wait=False):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -114,11 +118,16 @@ class Engine:
                 self.close()
                 raise
         self._endgames = {}
+        if endgame_wait and (endgame is None or endgame_tables is None):
+            self.close()
+            raise _lib.DbazError(_lib.EINVAL, "endgame_wait=True is the wait mode of a pool of tables: it needs endgame=DeepTables(...) and endgame_tables=N")
         if endgame is not None:
             try:
                 for model in endgame_models:
                     if endgame_tables is None:
                         self.attach_endgame(endgame, model, endgame_seed, endgame_reads)
+                    elif endgame_wait:
+                        self.attach_endgame_pool_wait(endgame, endgame_tables, model, endgame_seed, endgame_reads)
                     else:
                         self.attach_endgame_pool(endgame, endgame_tables, model, endgame_seed, endgame_reads)
             except Exception:
@@ -182,6 +191,27 @@ class Engine:
             raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
         self._ck(self._L.dbaz_attach_tables_pool(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
         self._endgames[int(model)] = endgame
+
+    def attach_endgame_pool_wait(self, endgame, tables, model=0, seed=0, reads=0):
+        """dbaz_attach_tables_pool_wait: attach_endgame_pool in wait mode.  A slot that finds the pool dry is not denied: its request
+        stands, it selects nothing and spends none of its reads until a pass grants it a region (waiting slots and new askers
+        together, in ascending slot order), and then searches as if its search had started in that pass.  The rows are those of
+        attach_endgame for every `tables` >= 1; reads means what it means for attach_endgame.  table_pool()["denied"] stays 0 and
+        table_pool_waits() counts the waiting.  The self-play driver only: search() and search_timed() raise DbazError (ESTATE)
+        afterwards.  An Engine's pooled attaches are all of one mode: DbazError (EINVAL) otherwise, and nothing changes.
+        (A method of its own: attach_endgame_pool keeps its parameters.)"""
+        if endgame.ATTACH != "dbaz_attach_tables":  # the C side cannot tell the two handle types apart
+            raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
+        self._ck(self._L.dbaz_attach_tables_pool_wait(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
+        self._endgames[int(model)] = endgame
+
+    def table_pool_waits(self):
+        """dbaz_get_table_pool_waits: dict(wait_mode, waiting, waited) after the queued work is done -- whether the pool is in wait
+        mode, the slots waiting for a region now, and the slot-passes spent waiting since the first attach (what table_pool()'s
+        `denied` would have counted).  Zeros without a pooled attach."""
+        mode, now, total = C.c_int32(), C.c_int32(), C.c_int64()
+        self._ck(self._L.dbaz_get_table_pool_waits(self.h, C.byref(mode), C.byref(now), C.byref(total)))
+        return dict(wait_mode=int(mode.value), waiting=int(now.value), waited=int(total.value))
 
     def table_pool(self):
         """dbaz_get_table_pool: dict(n_tables, in_use, high_water, denied) of the pool of tables after the queued work is done;

@@ -778,6 +778,37 @@ int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *in_use, int3
  *   no attach on this handle, slot outside 0 .. n_slots - 1 -> DBAZ_EINVAL */
 int dbaz_get_slot_table_index(dbaz_engine *e, int32_t slot, int32_t *table);
 
+/* ---- the pool in WAIT MODE: a slot that finds the pool dry waits for a region --------------------------------------
+ * dbaz_attach_tables_pool, except that no search is ever denied, so that the rows no longer depend on the slot count, the pool
+ * size or the schedule: for every n_tables >= 1 they are the rows of dbaz_attach_tables, bit for bit.  endgame_reads means what
+ * it means for dbaz_attach_tables (every search under a root with F <= max_free free edges has a table, so the cap is right).
+ * The rule:
+ *   - the requests of a pass are handled as in dbaz_attach_tables_pool: all regions given back in the pass are free first, then
+ *     the slots that ask take the free regions in ASCENDING SLOT ORDER as long as they last;
+ *   - a slot that asks and gets nothing keeps its request standing and is WAITING: it selects no leaf and evaluates nothing, it
+ *     consumes none of its reads, and its tree stays as the start of its search left it;
+ *   - every later pass ranks the waiting slots together with that pass's new askers, by slot index, under the same rule.  (Any
+ *     work-conserving order gives the same rows and the same number of regions held at every pass -- a slot's rows are a function
+ *     of (seed, game, ply) alone, and a free region never stays free while a slot asks; ascending slot order is the order the
+ *     deny mode already has.  It is no FIFO: a low slot that asks late overtakes a high slot that has waited.)
+ *   - the pass that grants a waiting slot a region solves its table in that pass, and the slot's search proceeds as if it had
+ *     started then; in the one-simulation step, where the pass runs next to the step's selection, the slot takes its first
+ *     selection in the following step;
+ *   - `denied` (dbaz_get_table_pool) stays 0; the slot-passes spent waiting are counted instead (dbaz_get_table_pool_waits).
+ * A wait ends: regions come back whenever a holder's game ends, and a holder never waits.  A waiting slot is an active slot
+ * (dbaz_counters.active_slots), never a blocked one.  dbaz_set_positions, dbaz_selfplay_start and a later attach clear every
+ * wait along with the regions.
+ * Scope: the self-play driver only (dbaz_run, dbaz_step; one simulation per step and selfplay_pending waves alike, match play
+ * included).  Nothing gives a region back during an explicit search, so on a handle in wait mode dbaz_search, dbaz_search_timed,
+ * dbaz_search_begin and dbaz_select return DBAZ_ESTATE.
+ *   every refusal of dbaz_attach_tables_pool except endgame_reads > 0 (endgame_reads < 0 is refused); a handle's pooled attaches
+ *   are all of ONE mode: a wait attach on a handle whose pool denies, or the reverse   -> DBAZ_EINVAL, nothing changes */
+int dbaz_attach_tables_pool_wait(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads);
+/* After waiting for the engine's queued work: wait_mode (1: the handle's pool is in wait mode), the slots waiting now, and the
+ * slot-passes spent waiting -- what `denied` would have counted -- cumulative since the first attach.  All 0 without a pooled
+ * attach.  Any output pointer may be NULL. */
+int dbaz_get_table_pool_waits(dbaz_engine *e, int32_t *wait_mode, int32_t *waiting, int64_t *waited);
+
 #ifdef __cplusplus
 }
 #endif
