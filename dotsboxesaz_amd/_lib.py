@@ -44,6 +44,7 @@ SYMBOLS = [
     "dbaz_tables_table", "dbaz_tables_score", "dbaz_tables_targets", "dbaz_replay_exact_targets",
     "dbaz_attach_tables", "dbaz_get_slot_table",
     "dbaz_attach_tables_pool", "dbaz_get_table_pool", "dbaz_get_slot_table_index", "dbaz_attach_tables_pool_wait", "dbaz_get_table_pool_waits",
+    "dbaz_attach_leaf_solver", "dbaz_get_leaf_solves",
 ]
 
 
@@ -233,6 +234,8 @@ def load():
     L.dbaz_attach_tables_pool_wait.argtypes = [vp, i32, vp, i32, C.c_uint64, i32]
     L.dbaz_get_table_pool_waits.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.dbaz_get_slot_table_index.argtypes = [vp, i32, C.POINTER(i32)]
+    L.dbaz_attach_leaf_solver.argtypes = [vp, i32, vp, i32, C.c_uint64]
+    L.dbaz_get_leaf_solves.argtypes = [vp, C.POINTER(i64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("dbaz_last_error", "dbaz_build_info", "dbaz_destroy", "dbaz_trainer_last_error", "dbaz_trainer_destroy", "dbaz_bn2d_workspace_bytes",

@@ -42,15 +42,19 @@ class NullWriter:
 
 class Coach:
     def __init__(self, params, rows, cols, device=0, n_slots=None, dist=None, nn_precision=1, exact_targets=None, exact_pi="restrict",
-                 exact_z=True):
+                 exact_z=True, leaf_endgame=None, leaf_free=None, leaf_seed=0):
         """exact_targets: an endgame.Endgame of the board, or True for one with max_free = 16 -- the train and the validation
         dataset of every generation get the solved z (exact_z) and pi (exact_pi) on their late rows (train_data.ReplayDataset).
         An endgame.DeepTables of the board (max_free <= 31) instead relabels the packed replay rows themselves, right after
         self-play and before the ranks exchange them (DeepTables.replay_targets: one table per game, every rank its own games);
-        the datasets are then built from the relabelled generation without a relabel of their own."""
+        the datasets are then built from the relabelled generation without a relabel of their own.
+        leaf_endgame, leaf_free, leaf_seed: an endgame.Endgame whose solver answers the self-play leaves with at most leaf_free
+        free edges (Engine(leaf_endgame=...), Engine.attach_leaf_solver; self-play has one model), leaf_seed picking among equally
+        good moves (Engine(endgame_seed=)); the matches of compute_elo run without it."""
         self.params, self.rows, self.cols = params, int(rows), int(cols)
         self.exact_targets, self.exact_pi, self.exact_z = exact_targets, exact_pi, exact_z
         self.exact_stats = None
+        self.leaf_endgame, self.leaf_free, self.leaf_seed = leaf_endgame, leaf_free, int(leaf_seed)
         self.device, self.dist, self.n_slots, self.nn_precision = device, dist, n_slots, nn_precision
         self.model_class = _get(_get(params, "nn"), "model_class")
         self.engine = None
@@ -65,6 +69,7 @@ class Coach:
             slots = self.n_slots or max(1, min(-(-n_games // world), 8192))
             self.engine = Engine(self.rows, self.cols, slots, evaluator=kind, device=self.device,
                                  nn_precision=self.nn_precision if kind == "resnet" else 0,
+                                 leaf_endgame=self.leaf_endgame, leaf_free=self.leaf_free, endgame_seed=self.leaf_seed,
                                  **sp.engine_kwargs_from_params(self.params))
             self.store = TD.ReplayStore(self.engine)
         return self.engine

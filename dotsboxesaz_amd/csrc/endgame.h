@@ -97,6 +97,20 @@ void endgame_forward(int rows, int cols, int max_free, size_t tab_stride, int n_
                      const T *x, const int32_t *list_dev, const int32_t *n_dev, int max_n, int per_slot, uint64_t seed0, uint64_t seed1, float *P,
                      float *V, int AS, unsigned long long *stats);
 
+// ---- leaves solved from scratch inside the search (dbaz_attach_leaf_solver; kernel: k_endgame_leaves) ---------------------------
+// A leaf with F <= the model's threshold that no table serves is listed by k_select / k_select_multi in the class of its F -- the
+// classes of k_endgame_targets, deepest first: a class's workgroups hold 2^f_hi bytes of LDS -- and one fixed-grid launch per class
+// the threshold reaches solves the listed leaves between select and expand.  An entry is the leaf's row (the slot, or
+// slot * K + k in a wave) with the searching model in bit LEAF_SOLVE_MODEL_SHIFT.
+#define LEAF_SOLVE_CLASSES 4
+#define LEAF_SOLVE_MODEL_SHIFT 30
+__host__ __device__ __forceinline__ int leaf_solve_class(int F) { return F >= 16 ? 0 : (F >= 14 ? 1 : (F >= 11 ? 2 : 3)); }
+// list_dev [LEAF_SOLVE_CLASSES][cap] and cnt_dev [LEAF_SOLVE_CLASSES] are the caller's (the engine's); rows of x = TreeBufs.feat
+// planes; rows outside [0, max_n) are skipped.  leaf_free: the largest threshold attached (classes above it are not launched);
+// stats [17] (cumulative, device): leaves solved per F.  Nothing of g is written.
+void endgame_solve_leaves(const dbaz_endgame *g, hipStream_t stream, int leaf_free, const int32_t *list_dev, const int32_t *cnt_dev, int cap,
+                          const float *x, int max_n, uint64_t seed0, uint64_t seed1, float *P, float *V, int AS, unsigned long long *stats);
+
 // ---- exact training targets (dbaz_exact_targets, include/dbaz.h): rows x_stride shorts apart, relabelled in place, queued on
 // `stream`.  stats_host [4 + 17] (may be NULL) as dbaz_dataset_exact_targets documents it: asking for it waits for the stream.
 // The message of a failure is dbaz_endgame_last_error(g)'s.

@@ -64,6 +64,11 @@ struct RowEdges {
     const int16_t *xr;
     __device__ __forceinline__ bool operator()(int a) const { return xr[a] != 0; }
 };
+template <typename T>
+struct PlaneEdges { // T = float: the search's feature planes (TreeBufs.feat)
+    const T *xr;
+    __device__ __forceinline__ bool operator()(int a) const { return xr[a] != (T)0; }
+};
 struct MaskEdges {
     uint64_t free_edges[4];
     __device__ __forceinline__ bool operator()(int a) const { return !((free_edges[a >> 6] >> (a & 63)) & 1ull); }
@@ -477,6 +482,62 @@ __global__ void __launch_bounds__(THREADS) k_endgame_targets(EndgameGeo g, int f
     if (want_stats && tid < ENDGAME_MAX_FREE + 3 && s_stats[tid]) atomicAdd(&cnt->stats[tid], (unsigned long long)s_stats[tid]);
 }
 
+// Leaves of the search solved from scratch (endgame.h, dbaz_attach_leaf_solver): k_endgame_targets' shape on the search's feature
+// planes.  One launch per class of F with the class's upper end as the geometry's max_free (sd holds 2^max_free bytes) and a
+// fixed grid; workgroup b takes entries b, b + gridDim.x, ... of the class's list, whose length is read here.  Per entry
+// k_endgame_policy's steps and answer: setup and solve, wave 0 picks, the workgroup writes the one-hot row of `stride` floats and
+// v.  An entry whose row lies outside the caller's buffers is skipped; one with F above the class (select lists none) gets
+// k_endgame_policy's p = 0, v = 0.  The leaves solved per F are counted per workgroup in LDS and added once at the end.
+template <int THREADS, typename T>
+__global__ void __launch_bounds__(THREADS) k_endgame_leaves(EndgameGeo g, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
+                                                            const T *__restrict__ x, int max_n, uint64_t seed0, uint64_t seed1, float *__restrict__ P,
+                                                            float *__restrict__ V, int stride, unsigned long long *__restrict__ stats)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t sd[]; // [max(16, 2^g.max_free)]
+    __shared__ EndgameLds L;
+    __shared__ int s_pick;
+    __shared__ uint32_t s_stats[ENDGAME_MAX_FREE + 1];
+
+    const int tid = threadIdx.x;
+    const int count = min(max(*cnt, 0), cap);
+    if ((int)blockIdx.x >= count) return; // the same answer in every thread
+    if (tid <= ENDGAME_MAX_FREE) s_stats[tid] = 0;
+    __syncthreads();
+    for (int i = blockIdx.x; i < count; i += gridDim.x) {
+        const int entry = list[i];
+        const int r = entry & ((1 << LEAF_SOLVE_MODEL_SHIFT) - 1);
+        if (entry < 0 || r >= max_n) continue; // never outside the caller's buffers (the same answer in every thread)
+        const T *xr = x + (size_t)r * 3 * g.HW;
+        float *pr = P + (size_t)r * stride;
+        const int F = endgame_setup<PlaneEdges<T>, THREADS>(g, PlaneEdges<T>{xr}, L);
+        if (F > g.max_free) {
+            for (int a = tid; a < stride; a += THREADS) pr[a] = 0.0f;
+            if (tid == 0) V[r] = 0.0f;
+            __syncthreads();
+            continue;
+        }
+        endgame_solve<THREADS>(g, F, L, sd);
+
+        const RowFacts f = solver_facts(g.rows * g.cols, L.closed, (int)xr[2 * g.HW]);
+        const bool open = f.res == DBAZ_RESULT_NONE; // a finished position is never listed: p = 0, v = get_result all the same
+        if (tid < 64) {
+            const bool cand = open && tid < F;
+            const int qq = cand ? solver_move_q(L.other[tid][0], L.other[tid][1], 0u, (int)sd[1u << tid]) : 0;
+            const int pick = endgame_pick(cand, qq, cand ? (int)L.act[tid] : 0, (entry >> LEAF_SOLVE_MODEL_SHIFT) & 1 ? seed1 : seed0);
+            if (tid == 0) s_pick = pick;
+        }
+        __syncthreads();
+        const int pick = s_pick;
+        for (int a = tid; a < stride; a += THREADS) pr[a] = a == pick ? 1.0f : 0.0f;
+        if (tid == 0) {
+            V[r] = (float)(open ? sgn(f.margin + (int)sd[0]) : f.res);
+            s_stats[F]++;
+        }
+        __syncthreads(); // the next entry of this workgroup reuses L, sd and s_pick
+    }
+    if (tid <= ENDGAME_MAX_FREE && s_stats[tid]) atomicAdd(&stats[tid], (unsigned long long)s_stats[tid]);
+}
+
 // ------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------
@@ -557,6 +618,8 @@ extern "C" int dbaz_endgame_create(int32_t rows, int32_t cols, int32_t device, i
         e = hipFuncSetAttribute((const void *)k_endgame_table, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_endgame_targets<ENDGAME_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_endgame_leaves<ENDGAME_THREADS, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << ENDGAME_MAX_FREE);
     if (e != hipSuccess) {
         const std::string msg = hipGetErrorString(e);
         (void)hipGetLastError();
@@ -689,6 +752,31 @@ void endgame_tables(const dbaz_endgame *g, hipStream_t stream, EndgameReq *req, 
     const size_t stride = endgame_table_stride(g);
     k_endgame_table<<<(unsigned)std::min(n_slots, ENDGAME_TABLE_GRID), ENDGAME_THREADS, stride, stream>>>(g->g, req, hdr, tables, stride, n_slots,
                                                                                                     stats);
+}
+
+// The leaf solver's launches of one step: the classes of kTargetClasses that leaf_free reaches, deepest first, each with the grid
+// the chip holds at once (256 CUs x the workgroups per CU that the class's LDS and 32 wave slots admit) -- a step lists hundreds
+// of leaves, not a dataset, and a class without entries costs one word read per workgroup.
+static const int kLeafGrids[LEAF_SOLVE_CLASSES] = {512, 1024, 1024, 2048};
+
+void endgame_solve_leaves(const dbaz_endgame *g, hipStream_t stream, int leaf_free, const int32_t *list_dev, const int32_t *cnt_dev, int cap,
+                          const float *x, int max_n, uint64_t seed0, uint64_t seed1, float *P, float *V, int AS, unsigned long long *stats)
+{
+    static_assert(sizeof kTargetClasses / sizeof kTargetClasses[0] == LEAF_SOLVE_CLASSES, "leaf_solve_class (endgame.h) names these classes");
+    for (int c = 0; c < LEAF_SOLVE_CLASSES; c++) {
+        const TargetClass &tc = kTargetClasses[c];
+        if (tc.f_lo > leaf_free) continue;
+        EndgameGeo gc = g->g;
+        gc.max_free = std::min(tc.f_hi, std::min(leaf_free, g->g.max_free));
+        const size_t lds = std::max<size_t>(16, (size_t)1 << gc.max_free);
+        const unsigned grid = (unsigned)std::max(1, std::min(cap, kLeafGrids[c]));
+        const int32_t *list = list_dev + (size_t)c * cap;
+        if (tc.threads == 256)
+            k_endgame_leaves<256, float><<<grid, 256, lds, stream>>>(gc, list, cnt_dev + c, cap, x, max_n, seed0, seed1, P, V, AS, stats);
+        else
+            k_endgame_leaves<ENDGAME_THREADS, float><<<grid, ENDGAME_THREADS, lds, stream>>>(gc, list, cnt_dev + c, cap, x, max_n, seed0, seed1, P, V, AS,
+                                                                                            stats);
+    }
 }
 
 template <typename T>

@@ -53,6 +53,11 @@ struct dbaz_engine {
     int8_t *eg_tables = nullptr;
     EndgameSlotHdr *eg_hdr = nullptr;
     unsigned long long *eg_stats = nullptr; // [2] tables solved, leaves served
+    // dbaz_attach_leaf_solver: the borrowed endgame solver of each model and its pick seed (thresholds: G.ls_free); the lists, their
+    // counters and the statistics are the engine's own, so the handle may serve as endgame= or for targets meanwhile
+    const dbaz_endgame *leaf_solver[2] = {nullptr, nullptr};
+    uint64_t leaf_seed[2] = {0, 0};
+    unsigned long long *ls_stats = nullptr; // [17] leaves solved per F
     // dbaz_attach_tables: the same with slot tables of up to 31 free edges, solved in HBM (solver.h); a handle's attaches are all
     // of one kind.  Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own
     bool eg_deep = false;
@@ -663,6 +668,17 @@ static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat
                                e->n_slots * per_slot, per_slot, e->endgame_seed[0], e->endgame_seed[1], P, V, e->g.AS, e->eg_stats);
 }
 
+// the leaves k_select / k_select_multi put on the leaf solver's lists (dbaz_attach_leaf_solver): one launch per class of F that
+// the largest threshold reaches, fixed by the attach -- the counts stay on the device
+static void leaf_solver_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
+{
+    const int L = std::max(e->G.ls_free[0], e->G.ls_free[1]);
+    if (L <= 0) return;
+    const dbaz_endgame *g = e->G.ls_free[0] >= e->G.ls_free[1] ? e->leaf_solver[0] : e->leaf_solver[1]; // its max_free covers L
+    endgame_solve_leaves(g, s, L, e->G.ls_list, e->G.ls_cnt, e->G.ls_cap, feat, e->n_slots * per_slot, e->leaf_seed[0], e->leaf_seed[1], P, V, e->g.AS,
+                         e->ls_stats);
+}
+
 // new positions or a new run: no table of an earlier game may serve them
 static int endgame_drop_tables(dbaz_engine *e)
 {
@@ -703,6 +719,7 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
         solver_forward(e->solver[0], s, e->B.feat_m, e->B.list_m, e->B.n_eval, e->n_slots * e->B.kmax, e->solver_seed[0], e->B.evalP_m,
                        e->B.evalV_m, e->g.AS);
     endgame_eval_leaves(e, s, e->B.feat_m, e->B.kmax, e->B.evalP_m, e->B.evalV_m);
+    leaf_solver_eval_leaves(e, s, e->B.feat_m, e->B.kmax, e->B.evalP_m, e->B.evalV_m);
     tree_launch_expand_backup_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
@@ -761,6 +778,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         solver_forward(e->solver[1], s, e->B.feat, e->B.eval_list2, e->B.n_eval + 1, e->n_slots, e->solver_seed[1], e->B.evalP, e->B.evalV,
                        e->g.AS);
     endgame_eval_leaves(e, s, e->B.feat, 1, e->B.evalP, e->B.evalV);
+    leaf_solver_eval_leaves(e, s, e->B.feat, 1, e->B.evalP, e->B.evalV);
     // the driver pass may run on under the network: nothing there reads what it writes (leaf lists and features come from
     // k_select, which skipped the slots the pass starts); k_expand_backup does (it clears the pass's slot list).
     // 3x3: 11.9 -> 13.2 M expansions/s, 6x6: +1.5 %, 9x9: +2.8 % against joining in front of the network
@@ -1136,6 +1154,87 @@ extern "C" void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_sol
     }
     if (tables_solved) *tables_solved = (int64_t)st[0];
     if (leaves_served) *leaves_served = (int64_t)st[1];
+}
+
+// ---- leaves solved from scratch (include/dbaz.h: the rule; endgame.h, tree.h) ----
+extern "C" int dbaz_attach_leaf_solver(dbaz_engine *e, int32_t model, dbaz_endgame *g, int32_t leaf_free, uint64_t pick_seed)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (model < 0 || model > 1 || (model == 1 && !e->sc.match_play))
+        return set_error(e, DBAZ_EINVAL, "model %d: 0, or 1 in match play", model);
+    const int ev = model ? e->sc.evaluator2 : e->sc.evaluator;
+    if (ev == DBAZ_EVAL_EXTERNAL || ev == DBAZ_EVAL_SOLVER)
+        return set_error(e, DBAZ_EINVAL, "model %d: a leaf solver attaches to a network or formula evaluator the engine runs itself", model);
+    int max_free = 0;
+    if (g) {
+        if (!endgame_serves(g, e->g.rows, e->g.cols, e->cfg.device, &max_free))
+            return set_error(e, DBAZ_EINVAL, "the endgame solver is of another board size or device than this %dx%d handle on device %d", e->g.rows,
+                             e->g.cols, e->cfg.device);
+        if (leaf_free < 0 || leaf_free > max_free)
+            return set_error(e, DBAZ_EINVAL, "leaf_free %d: 1 .. the solver's max_free = %d (0 = %d)", leaf_free, max_free, max_free);
+    }
+    // the rule is a property of a whole search: it changes between searches only
+    if (e->search_open) return set_error(e, DBAZ_ESTATE, "dbaz_attach_leaf_solver: a search is open (dbaz_search_begin)");
+    if (e->selfplay) {
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    if (!g) { // detach: the model's leaves go to its evaluator again; the counters stay
+        e->G.ls_free[model] = 0;
+        e->leaf_solver[model] = nullptr;
+        return DBAZ_OK;
+    }
+    if (!e->G.ls_list) {
+        const size_t cap = (size_t)e->n_slots * (size_t)e->B.kmax;
+        if (cap >= ((size_t)1 << LEAF_SOLVE_MODEL_SHIFT))
+            return set_error(e, DBAZ_EINVAL, "leaf solver: %zu leaves per step do not fit a list entry", cap);
+        void *p[4] = {nullptr, nullptr, nullptr, nullptr}; // lists, counters, statistics, the leaf flags (unless a table attach made them)
+        const size_t bytes[4] = {LEAF_SOLVE_CLASSES * cap * 4, LEAF_SOLVE_CLASSES * 4, (ENDGAME_MAX_FREE + 1) * sizeof(unsigned long long),
+                                 e->G.leaf ? 0 : cap * 4};
+        hipError_t err = hipSuccess;
+        for (int i = 0; i < 4 && err == hipSuccess; i++) {
+            if (!bytes[i]) continue;
+            err = hipMalloc(&p[i], bytes[i]);
+            if (err != hipSuccess) p[i] = nullptr;
+            else err = hipMemset(p[i], 0, bytes[i]);
+        }
+        if (err != hipSuccess) {
+            for (void *q : p)
+                if (q) (void)hipFree(q);
+            (void)hipGetLastError();
+            return set_error(e, DBAZ_EDEVICE, "leaf solver lists of %zu entries: %s", cap, hipGetErrorString(err));
+        }
+        for (void *q : p)
+            if (q) e->allocs.push_back(q);
+        e->G.ls_list = (int32_t *)p[0];
+        e->G.ls_cnt = (int32_t *)p[1];
+        e->ls_stats = (unsigned long long *)p[2];
+        if (p[3]) e->G.leaf = (int32_t *)p[3];
+        e->G.ls_cap = (int32_t)cap;
+    }
+    e->leaf_solver[model] = g;
+    e->leaf_seed[model] = pick_seed;
+    e->G.ls_free[model] = leaf_free == 0 ? max_free : leaf_free;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_leaf_solves(dbaz_engine *e, int64_t *by_free)
+{
+    if (!e || !by_free) return e ? set_error(e, DBAZ_EINVAL, "null argument") : DBAZ_EINVAL;
+    USE_DEVICE(e);
+    unsigned long long st[ENDGAME_MAX_FREE + 1] = {};
+    if (e->ls_stats) {
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        HIP_CHECK_RET(e, hipMemcpy(st, e->ls_stats, sizeof st, hipMemcpyDeviceToHost));
+    }
+    for (int f = 0; f <= ENDGAME_MAX_FREE; f++) by_free[f] = (int64_t)st[f];
+    return DBAZ_OK;
 }
 
 extern "C" int dbaz_search_timed(dbaz_engine *e, const int32_t *num_reads, const double *noise, double time_limit_s)

@@ -48,9 +48,16 @@ struct StartArgs {
 struct EndgameBufs {
     const EndgameSlotHdr *hdr; // [n_slots]
     int32_t *list;             // [n_slots * kmax] slots, or slot * kmax + k in a wave
-    int32_t *leaf;             // [n_slots * kmax] 1 = the leaf (of simulation k) is answered from the table
+    int32_t *leaf;             // [n_slots * kmax] 1 = the leaf (of simulation k) is answered from the table, 2 + c = by the leaf solver
     int32_t model[2];          // 1 = the model has an endgame solver attached
     int32_t wait;              // 1 (dbaz_attach_tables_pool_wait) = a slot may be waiting for a region of the pool: see endgame_slot_waits
+    // dbaz_attach_leaf_solver (all zero until then; independent of the table state above, but for `leaf`, which either attach
+    // allocates): a non-terminal leaf with at most ls_free[model] free real edges that no table serves goes on the list of its
+    // class of F (endgame.h) and is solved from scratch between select and expand; expand reads it like a table's leaf.
+    int32_t ls_free[2];        // the model's threshold, 0 = no leaf solver attached to it
+    int32_t *ls_list;          // [LEAF_SOLVE_CLASSES][ls_cap] entries
+    int32_t *ls_cnt;           // [LEAF_SOLVE_CLASSES] the lists' lengths, zeroed by expand like n_eval
+    int32_t ls_cap;            // n_slots * kmax
 };
 
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,

@@ -806,6 +806,19 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
 #define EV_CLASS_NEW (-3)      // a leaf selected in this step
 #define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
 #define SEL_ENDGAME 3          // select_one: the leaf is answered from the slot's endgame table (eg_list)
+#define SEL_LEAF_SOLVE 4       // select_one: + c = the leaf is solved from scratch, class c of leaf_solve_class (EndgameBufs::ls_list)
+
+// The leaf solver's rule (include/dbaz.h, dbaz_attach_leaf_solver) for a non-terminal leaf that no table serves: a leaf with
+// at most ls_free[model] free real edges is solved from scratch.  Returns its class, or -1.  Scalar popcounts: wave-uniform.
+__device__ __forceinline__ int leaf_solve_rule(const Geo &g, const EndgameBufs &G, int model, const GState &st)
+{
+    const int L = G.ls_free[model];
+    if (L <= 0) return -1;
+    const int F = gs_count_valid(g, st);
+    return F <= L ? leaf_solve_class(F) : -1;
+}
+// G.leaf: 0 = the model's evaluator, 1 = the slot's table, 2 + c = solved from scratch in class c
+__device__ __forceinline__ void leaf_solve_append(const EndgameBufs &G, int c, int at, int entry) { G.ls_list[(size_t)c * G.ls_cap + at] = entry; }
 
 // The pool of tables in wait mode (dbaz_attach_tables_pool_wait): a slot whose search found the pool dry selects nothing until a
 // pass grants it a region (EndgameSlotHdr::wait == ENDGAME_WAITING) -- its reads and its tree stay as begin_search left them.  The
@@ -818,7 +831,7 @@ __device__ __forceinline__ bool endgame_slot_waits(const SearchCfg &cfg, const E
     return w == ENDGAME_WAITING || (w == cfg.step && cfg.driver_concurrent);
 }
 
-// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, SEL_ENDGAME, or -1
+// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, SEL_ENDGAME, SEL_LEAF_SOLVE + class, or -1
 template <int NPL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
@@ -870,12 +883,16 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     int need_eval = -1;
     // a leaf under a valid table of this game is answered from it, whatever the evaluator: not on the evaluation lists (so never
     // counted in or deferred by the full-rounds cut), no transposition probe
-    const bool eg = !(m.flags & NF_TERMINAL) && G.hdr && G.model[model] && endgame_hdr_serves(G.hdr[slot], S->game_idx);
-    if (G.hdr && lane == 0) G.leaf[slot] = eg ? 1 : 0;
+    const bool tab = !(m.flags & NF_TERMINAL) && G.hdr && G.model[model] && endgame_hdr_serves(G.hdr[slot], S->game_idx);
+    // the same holds for a leaf that the model's leaf solver answers; the table wins: it is a lookup
+    const int lsc = (m.flags & NF_TERMINAL) || tab ? -1 : leaf_solve_rule(g, G, model, m.st);
+    const bool eg = tab || lsc >= 0;
+    if (G.leaf && lane == 0) G.leaf[slot] = tab ? 1 : (lsc >= 0 ? 2 + lsc : 0);
     if (!(m.flags & NF_TERMINAL)) {
         write_features(g, m.st, B.feat + (size_t)slot * 3 * g.HW, lane);
         const int ev = model ? cfg.evaluator2 : cfg.evaluator;
-        if (eg) need_eval = SEL_ENDGAME;
+        if (tab) need_eval = SEL_ENDGAME;
+        else if (lsc >= 0) need_eval = SEL_LEAF_SOLVE + lsc;
         else if (eval_uses_list(ev)) need_eval = model;
         int hit = -1;
         // (the table exists for network evaluators, and for the formula evaluators when forced on -- transposition_cache
@@ -922,7 +939,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 // ONE (full rounds only, cfg.eval_round > 0): one game per workgroup.  There this kernel appends to no network list -- it leaves
 // ev_class[slot] for k_order_evals -- so nothing is left to share between the games of a workgroup: no LDS counters, no barrier,
 // and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare endgame
-// leaf goes onto eg_list with the wave's own atomic.
+// leaf goes onto eg_list, and a leaf of the leaf solver onto its class's list, with the wave's own atomic.
 template <int NPL, bool ONE>
 __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
@@ -933,23 +950,29 @@ __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo
         if (lane == 0) {
             B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
             if (model == SEL_ENDGAME) G.list[atomicAdd(B.n_eval + 3, 1)] = slot;
+            if (model >= SEL_LEAF_SOLVE) // (full rounds: one model)
+                leaf_solve_append(G, model - SEL_LEAF_SOLVE, atomicAdd(G.ls_cnt + (model - SEL_LEAF_SOLVE), 1), slot);
         }
         return;
     }
-    __shared__ int s_cnt[3], s_base[3]; // the two models' lists and eg_list
+    constexpr int NL = 3 + LEAF_SOLVE_CLASSES;
+    __shared__ int s_cnt[NL], s_base[NL]; // the two models' lists, eg_list and the leaf solver's classes
     const int slot = blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (WAVE - 1);
-    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < NL) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     int model = -1;
     if (slot < n_slots) model = select_one<NPL>(g, cfg, B, G, slot, lane);
-    int cls = model == SEL_ENDGAME ? 2 : ((model == 0 || model == 1) ? model : -1);
+    int cls = model >= SEL_LEAF_SOLVE ? 3 + (model - SEL_LEAF_SOLVE) : (model == SEL_ENDGAME ? 2 : ((model == 0 || model == 1) ? model : -1));
     int my = -1;
     if (cls >= 0 && lane == 0) my = atomicAdd(&s_cnt[cls], 1);
     __syncthreads();
     if (threadIdx.x < 3 && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(B.n_eval + (threadIdx.x == 2 ? 3 : threadIdx.x), s_cnt[threadIdx.x]);
+    if (threadIdx.x >= 3 && threadIdx.x < NL && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(G.ls_cnt + (threadIdx.x - 3), s_cnt[threadIdx.x]);
     __syncthreads();
     if (my >= 0) {
-        if (cls == 2) {
+        if (cls >= 3) {
+            leaf_solve_append(G, cls - 3, s_base[cls] + my, slot | (B.slots[slot].model << LEAF_SOLVE_MODEL_SHIFT)); // the model's seed picks
+        } else if (cls == 2) {
             G.list[s_base[2] + my] = slot;
         } else {
             (cls ? B.eval_list2 : B.eval_list)[s_base[cls] + my] = slot;
@@ -1116,7 +1139,13 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
             SimRec sr;
             sr.leaf = lf.cur; sr.path_len = lf.depth + 1; sr.terminal = term ? 1 : 0; sr.result = m.result; sr.to_play = m.st.to_play;
             sr.dup = dup ? 1 : 0;
-            if (G.hdr) G.leaf[(size_t)slot * K + k] = (eg && !term && !dup) ? 1 : 0;
+            if (G.leaf) {
+                // model 0's threshold, and entries without a model bit (so model 0's seed), as for `eg` above: the waves run one
+                // model (sim_wave evaluates cfg.evaluator only).  Waves in match play would have to pass S->model here and
+                // set the entry's bit LEAF_SOLVE_MODEL_SHIFT in k_select_multi.
+                const int lsc = eg || term || dup ? -1 : leaf_solve_rule(g, G, 0, m.st);
+                G.leaf[(size_t)slot * K + k] = (term || dup) ? 0 : (eg ? 1 : (lsc >= 0 ? 2 + lsc : 0));
+            }
             B.simrec[(size_t)slot * K + k] = sr;
             if (!term && !dup)
                 node_ptr(pool, g, lf.cur)[11] = pack_dw11(m.flags | NF_INFLIGHT, m.result, m.deepness);
@@ -1149,14 +1178,17 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     if (S->phase == PH_ERROR) return;
     const int K = B.kmax, n = S->wave_sims;
     const bool lists = eval_uses_list(cfg.evaluator);
-    if ((!lists && !G.hdr) || S->sel_step != cfg.step) return;
+    if ((!lists && !G.leaf) || S->sel_step != cfg.step) return;
     for (int k0 = 0; k0 < n; k0 += WAVE) {
         const int k = k0 + lane;
         bool need = false, eg = false;
+        int lsc = -1; // the leaf solver's class of the leaf
         if (k < n) {
             const SimRec sr = B.simrec[(size_t)slot * K + k];
-            eg = G.hdr && G.leaf[(size_t)slot * K + k] != 0; // never set for a terminal or duplicate leaf
-            need = lists && !sr.terminal && !sr.dup && !eg;
+            const int how = G.leaf ? G.leaf[(size_t)slot * K + k] : 0; // never set for a terminal or duplicate leaf
+            eg = how == 1;
+            lsc = how >= 2 ? how - 2 : -1;
+            need = lists && !sr.terminal && !sr.dup && how == 0;
         }
         const unsigned long long mk = __ballot(need), me = __ballot(eg);
         int base = 0, ebase = 0;
@@ -1166,6 +1198,14 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
         ebase = __shfl(ebase, 0);
         if (need) B.list_m[base + (int)__popcll(mk & ((1ull << lane) - 1ull))] = slot * K + k;
         if (eg) G.list[ebase + (int)__popcll(me & ((1ull << lane) - 1ull))] = slot * K + k;
+        for (int c = 0; G.ls_list && c < LEAF_SOLVE_CLASSES; c++) {
+            const unsigned long long ml = __ballot(lsc == c);
+            if (!ml) continue;
+            int lbase = 0;
+            if (lane == 0) lbase = atomicAdd(G.ls_cnt + c, (int)__popcll(ml));
+            lbase = __shfl(lbase, 0);
+            if (lsc == c) leaf_solve_append(G, c, lbase + (int)__popcll(ml & ((1ull << lane) - 1ull)), slot * K + k);
+        }
     }
 }
 
@@ -1247,6 +1287,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
     __shared__ double ldsd[DBAZ_MAX_A];
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; } // (drv_count: self-play in waves)
+    if (G.ls_cnt && slot == 0 && lane < LEAF_SOLVE_CLASSES) G.ls_cnt[lane] = 0;
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
@@ -1255,7 +1296,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
     const int K = B.kmax, n = S->wave_sims;
     for (int k = 0; k < n; k++) {
         const SimRec sr = B.simrec[(size_t)slot * K + k];
-        const bool eg = G.hdr && !sr.terminal && !sr.dup && G.leaf[(size_t)slot * K + k] != 0;
+        const bool eg = G.leaf && !sr.terminal && !sr.dup && G.leaf[(size_t)slot * K + k] != 0;
         const PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
         NodeMeta lm = load_meta(pool, g, sr.leaf);
         uint32_t *nd = node_ptr(pool, g, sr.leaf);
@@ -1297,6 +1338,7 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
     // the step's last kernel resets the per-step counters for the next one (the evaluation lists were consumed by the network
     // launches before it, the driver list by the pass joined before them): no memset launches between the kernels
     if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; }
+    if (G.ls_cnt && slot == 0 && lane < LEAF_SOLVE_CLASSES) G.ls_cnt[lane] = 0;
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
@@ -1313,7 +1355,7 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
     uint32_t *nd = node_ptr(pool, g, leaf);
     float v;
     int hit = -1;
-    const bool eg = !(lm.flags & NF_TERMINAL) && G.hdr && G.leaf[slot] != 0; // (p, v) came from the slot's endgame table, whatever the evaluator
+    const bool eg = !(lm.flags & NF_TERMINAL) && G.leaf && G.leaf[slot] != 0; // (p, v) came from the slot's endgame table or the leaf solver, whatever the evaluator
     if (!(lm.flags & NF_TERMINAL)) {
         float *Prow = reinterpret_cast<float *>(nd + META_DW);
         const int ev = (cfg.match_play && S->model) ? cfg.evaluator2 : cfg.evaluator;

@@ -964,23 +964,29 @@ def _selfplay_bench(a):
     shared by the slots (Engine(endgame_tables=N)): its high_water, denied and the pool's table_bytes.  deep=0 with --pool leaves
     the per-slot deep engine out (its n_slots << M bytes may not fit where the pool does).  --wait adds the pool in wait mode
     (Engine(endgame_wait=True)), with --endgame-reads if given -- the deny-mode pool takes no read cap and runs without one: its
-    waited slot-passes, the peak of the slots waiting at once (looked at every 256 steps), evaluations per game and games/s."""
+    waited slot-passes, the peak of the slots waiting at once (looked at every 256 steps), evaluations per game and games/s.
+    --leaf-free L[,L...] adds, per L, an engine with the leaf solver alone (Engine(leaf_endgame=Endgame(16), leaf_free=L)) and one
+    with the leaf solver next to the table attach asked for (the pool if --pool, else the per-slot tables): leaves solved per game
+    by F next to the other figures.  And "leaf_idle": the per-step time of the attach where no leaf qualifies -- the first steps of
+    fresh games, the same engine with and without the attach, alternating."""
     import sys
     import time
     import torch
     from . import nn as dnn
     from .engine import Engine
 
-    def play(g, pool=None, wait=False):
+    def play(g, pool=None, wait=False, leaf=None):
         peak_waiting = 0
         eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=a.reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
-                     device=a.device, endgame=g, endgame_reads=0 if pool and not wait else a.endgame_reads, endgame_tables=pool, endgame_wait=wait)
+                     device=a.device, endgame=g, endgame_reads=0 if pool and not wait else a.endgame_reads, endgame_tables=pool, endgame_wait=wait,
+                     leaf_endgame=leaf_g if leaf else None, leaf_free=leaf, endgame_seed=0)
         torch.manual_seed(0)
         model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
         eng.load_state_dict(model.state_dict(), "resnet", **model.shape)
         runs = []
         for i in range(a.repeats + 1):
             solved0 = eng.endgame_stats()[0]
+            leaves0 = eng.leaf_solves()["by_free"]
             eng.sync()
             t0 = time.perf_counter()
             eng.selfplay_start(a.selfplay_bench, 0)
@@ -995,20 +1001,65 @@ def _selfplay_bench(a):
             n_rows = len(eng.fetch_samples()["z"])
             dt = time.perf_counter() - t0
             c = eng.counters()
-            print("selfplay-bench: %s%s%s run %d of %d, %.1f s" % (type(g).__name__, " pool %d" % pool if pool else "", " wait" if wait else "", i, a.repeats, dt),
+            print("selfplay-bench: %s%s%s%s run %d of %d, %.1f s" % (type(g).__name__, " pool %d" % pool if pool else "", " wait" if wait else "",
+                                                                   " leaf %d" % leaf if leaf else "", i, a.repeats, dt),
                   file=sys.stderr, flush=True)
             if i:  # the first run warms up
                 runs.append(dict(games_per_s=c["games_finished"] / dt, nn_evals_per_game=c["nn_evals"] / max(1, c["games_finished"]),
                                  rows_per_game=n_rows / max(1, c["games_finished"]), tables_solved=eng.endgame_stats()[0] - solved0,
                                  seconds=dt))
+                if leaf:
+                    games = max(1, c["games_finished"])
+                    by = [(n1 - n0) / games for n0, n1 in zip(leaves0, eng.leaf_solves()["by_free"])]
+                    runs[-1].update(leaves_solved_per_game=sum(by), **{"leaves_F%d" % f: by[f] for f in range(1, leaf + 1)})
         tp, tw = eng.table_pool(), eng.table_pool_waits()
         eng.close()
         out = {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+        if leaf:
+            out["leaves_solved_per_game_by_free"] = {f: out.pop("leaves_F%d" % f) for f in range(1, leaf + 1)}
         if pool:  # counted over the warm-up and the timed runs together
             out.update(high_water=tp["high_water"], denied=tp["denied"], in_use_at_end=tp["in_use"])
         if wait:
             out.update(waited=tw["waited"], peak_waiting=peak_waiting, waiting_at_end=tw["waiting"], endgame_reads=a.endgame_reads)
         return out
+
+    def idle_cost(leaf, steps=200, rounds=5):
+        """ms per step over the first `steps` steps of fresh games (no leaf anywhere near `leaf` free edges), plain and attached in turn"""
+        engs = {}
+        for name, lf in (("plain", None), ("attached", leaf)):
+            engs[name] = Engine(a.rows, a.cols, a.slots, mcts_num_read=a.reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
+                                device=a.device, leaf_endgame=leaf_g if lf else None, leaf_free=lf)
+            torch.manual_seed(0)
+            model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
+            engs[name].load_state_dict(model.state_dict(), "resnet", **model.shape)
+        ms = {k: [] for k in engs}
+        for i in range(rounds + 1):
+            for name, eng in engs.items():
+                eng.selfplay_start(a.slots, 0)
+                eng.step(8)
+                eng.sync()
+                t0 = time.perf_counter()
+                eng.step(steps)
+                eng.sync()
+                if i:  # the first round warms up
+                    ms[name].append(1e3 * (time.perf_counter() - t0) / steps)
+        solved = engs["attached"].leaf_solves()["total"]
+        for eng in engs.values():
+            eng.close()
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        return dict(leaf_free=leaf, steps=steps, rounds=rounds, ms_per_step=med, ms_per_step_all={k: [round(x, 4) for x in v] for k, v in ms.items()},
+                    attach_cost_ms=med["attached"] - med["plain"], spread_ms=max(max(v) - min(v) for v in ms.values()), leaves_solved=solved)
+
+    leaves = [int(x) for x in str(a.leaf_free).split(",") if x] if a.leaf_free else []
+    leaf_g = Endgame(a.rows, a.cols, a.device, MAX_FREE) if leaves else None
+
+    def leaf_runs(out, g, pool):
+        for lf in leaves:
+            out["leaf%d" % lf] = play(None, leaf=lf)
+            out["leaf%d_with_tables" % lf] = play(g, pool or None, leaf=lf)
+        if leaves:
+            out["leaf_idle"] = idle_cost(max(leaves))
+            leaf_g.close()
 
     if a.max_free > MAX_FREE:
         # past 16 free edges the slot tables are a DeepTables' (dbaz_attach_tables): plain, Endgame(16) and deep side by side
@@ -1030,6 +1081,7 @@ def _selfplay_bench(a):
         # that ran dry does not play the same games (its denied searches go to the network), so nothing is asserted of it
         out["deep_saves_nn_evals"] = best["nn_evals_per_game"] < out["endgame16"]["nn_evals_per_game"]
         assert out["deep_saves_nn_evals"] or ("deep" not in out and out["pooled"]["denied"] > 0), out
+        leaf_runs(out, d, a.pool if a.pool > 0 else 0)
         g.close()
         d.close()
         return out
@@ -1037,6 +1089,7 @@ def _selfplay_bench(a):
     out = dict(rows=a.rows, cols=a.cols, games=a.selfplay_bench, slots=a.slots, reads=a.reads, max_free=g.max_free,
                endgame_reads=a.endgame_reads, table_bytes=a.slots * max(16, 1 << g.max_free), plain=play(None), endgame=play(g))
     out["speedup"] = out["endgame"]["games_per_s"] / out["plain"]["games_per_s"]
+    leaf_runs(out, g, 0)
     g.close()
     return out
 
@@ -1077,6 +1130,9 @@ def main(argv=None):
                     help="--selfplay-bench with --pool: a further engine whose pool is in wait mode (a slot that finds it dry waits for a table)")
     ap.add_argument("--per-slot-deep", type=int, default=1,
                     help="--selfplay-bench with --pool: 0 leaves out the engine with one deep table per slot (slots << max_free bytes)")
+    ap.add_argument("--leaf-free", default="", metavar="L[,L...]",
+                    help="--selfplay-bench: per L two further engines, the leaf solver (leaves with at most L free edges solved from scratch) alone "
+                         "and next to the table attach asked for; and the per-step cost of the attach where no leaf qualifies")
     ap.add_argument("--reads", type=int, default=800, help="--selfplay-bench: mcts_num_read")
     ap.add_argument("--endgame-reads", type=int, default=0, help="--selfplay-bench: read cap of the searches the tables serve (0: none)")
     ap.add_argument("--channels", type=int, default=64)

@@ -52,6 +52,9 @@ class Engine:
     instead -- it selects nothing until a game that ends gives one back -- so no search is denied, the rows are those of
     endgame_tables=None for every N >= 1, and endgame_reads may be given.  The idle slot-passes are table_pool_waits()["waited"].
     Self-play and match play only: search() and search_timed() are refused (ESTATE) on such an Engine.
+    leaf_endgame=Endgame(rows, cols, max_free=M) (dbaz_attach_leaf_solver): the models in leaf_models solve every leaf with at
+    most leaf_free (None: M) free edges that no table serves from scratch, whatever the root (attach_leaf_solver); the seed is
+    endgame_seed.  It works alone or next to any endgame= above; leaf_solves() counts the solved leaves.
     playout_cap=(full_prob, fast_reads): playout cap randomization (selfplay_set_playout_cap); None: off.
     forced_playouts=(k, prune): forced playouts and policy target pruning at the root of the self-play driver's full searches
     (selfplay_set_forced_playouts); None: off.
@@ -66,7 +69,7 @@ class Engine:
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
                  solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None,
-                 forced_playouts=None, endgame_wait=False):
+                 forced_playouts=None, endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -130,6 +133,14 @@ class Engine:
                         self.attach_endgame_pool_wait(endgame, endgame_tables, model, endgame_seed, endgame_reads)
                     else:
                         self.attach_endgame_pool(endgame, endgame_tables, model, endgame_seed, endgame_reads)
+            except Exception:
+                self.close()
+                raise
+        self._leaf_solvers = {}
+        if leaf_endgame is not None:
+            try:
+                for model in leaf_models:
+                    self.attach_leaf_solver(leaf_endgame, leaf_free, model, endgame_seed)
             except Exception:
                 self.close()
                 raise
@@ -204,6 +215,29 @@ class Engine:
             raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
         self._ck(self._L.dbaz_attach_tables_pool_wait(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
         self._endgames[int(model)] = endgame
+
+    def attach_leaf_solver(self, endgame, leaf_free=None, model=0, seed=0):
+        """dbaz_attach_leaf_solver: model 0 / 1 (any evaluator but "external" and "solver") solves every non-terminal leaf with at
+        most leaf_free free edges (None: endgame.max_free) that no slot table serves from scratch -- Endgame.policy's (p, v) for
+        `seed`, bit for bit -- instead of evaluating it; the rule looks at the leaf alone, not at the root.  endgame: an
+        endgame.Endgame, borrowed and kept alive with the Engine; it may be attached as endgame= as well.  endgame=None detaches
+        the model.  DbazError (EINVAL) for a leaf_free outside 1 .. endgame.max_free, (ESTATE) while a search is open or games
+        are being played; nothing changes then."""
+        if endgame is not None and getattr(endgame, "ATTACH", None) != "dbaz_attach_endgame":  # the C side cannot tell the handle types apart
+            raise _lib.DbazError(_lib.EINVAL, "a leaf solver needs an Endgame, not a %s" % type(endgame).__name__)
+        if leaf_free is not None and int(leaf_free) < 1:
+            raise _lib.DbazError(_lib.EINVAL, "leaf_free %r: 1 .. the Endgame's max_free, or None" % (leaf_free,))
+        self._ck(self._L.dbaz_attach_leaf_solver(self.h, int(model), endgame.h if endgame is not None else None,
+                                                 0 if leaf_free is None else int(leaf_free), C.c_uint64(int(seed))))
+        self._leaf_solvers[int(model)] = endgame
+
+    def leaf_solves(self):
+        """dbaz_get_leaf_solves: dict(total, by_free) -- the leaves solved from scratch since the first attach_leaf_solver, by_free
+        a list of 17 counts for F = 0 .. 16; zeros without an attach.  Waits for the queued work."""
+        by = (C.c_int64 * 17)()
+        self._ck(self._L.dbaz_get_leaf_solves(self.h, by))
+        by = [int(v) for v in by]
+        return dict(total=sum(by), by_free=by)
 
     def table_pool_waits(self):
         """dbaz_get_table_pool_waits: dict(wait_mode, waiting, waited) after the queued work is done -- whether the pool is in wait

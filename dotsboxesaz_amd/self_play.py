@@ -127,12 +127,17 @@ def samples_to_dataframe(s, generation, rows, cols, with_features=True):
 
 class SelfPlay:
     """Reference: self_play.py:19-156.  `nn` is a dotsboxesaz_amd.nn.NeuralNetWrapper (its engine
-    plays the games) or an Engine whose evaluator is already configured."""
+    plays the games) or an Engine whose evaluator is already configured.  leaf_endgame, leaf_free, leaf_models, leaf_seed: an
+    endgame.Endgame that is attached to that engine as the leaf solver of the listed models (Engine.attach_leaf_solver) before
+    the first game; leaf_seed picks among equally good moves, as Engine(endgame_seed=) does."""
 
-    def __init__(self, nn, params):
+    def __init__(self, nn, params, leaf_endgame=None, leaf_free=None, leaf_models=(0,), leaf_seed=0):
         self.params = params
         self.engine = getattr(nn, "engine", nn)
         self.samples = None
+        if leaf_endgame is not None:
+            for model in leaf_models:
+                self.engine.attach_leaf_solver(leaf_endgame, leaf_free, model, leaf_seed)
         forced = _get(_get(params, "self_play"), "forced_playouts")
         if forced is not None:  # the engine was made elsewhere: the setting of the handle follows the parameters
             self.engine.selfplay_set_forced_playouts(float(_get(forced, "k")), bool(_get(forced, "prune", True)))
@@ -174,7 +179,7 @@ def write_dataset(file_name, key, df):
 def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_workers=None, games_per_workers=10,
                    rows=None, cols=None, n_slots=None, device=0, dist=None, nn_precision=None, async_searches=False,
                    start_states=None, games_per_start=1, endgame=None, endgame_models=(0,), endgame_tables=None, fast_rows="drop",
-                   endgame_wait=False):
+                   endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
     """Reference: self_play.generate_games (self_play.py:291-306) called from coach.selfplay
     (coach.py:27-29).  Plays n_games with generation-1's weights (random init for generation 0,
     self_play.py:187-190) and appends the samples (+ `training` = 0) to key "fresh".
@@ -195,6 +200,8 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     endgame_tables: with a DeepTables, the slots share a pool of that many tables (Engine(endgame_tables=N)); None: one per slot.
     endgame_wait: with endgame_tables, a slot that finds the pool dry waits for a table instead of searching that move without one
     (Engine(endgame_wait=True)): the rows are those of endgame_tables=None whatever the pool's size.
+    leaf_endgame, leaf_free, leaf_models: an endgame.Endgame whose solver answers every leaf with at most leaf_free free edges that no
+    table serves, whatever the root (Engine(leaf_endgame=...), Engine.attach_leaf_solver); alone or next to endgame=.
     fast_rows: with params.self_play.playout_cap set, "drop" leaves the rows of the fast searches (bit 0 of "pad") out of the
     DataFrame -- they moved the games on and are no training targets -- and "keep" writes every row.  Without a cap no row is
     marked and the two are the same."""
@@ -214,7 +221,8 @@ def generate_games(hdf_file_name, generation, nn_class, n_games, params, n_worke
     # Philox streams are keyed by (seed, game, ply): sharding does not change a game
     eng = Engine(rows, cols, n_slots, evaluator=model.kind, device=device, seed=generation * 1000003,
                  nn_precision=nn_precision, endgame=endgame, endgame_models=endgame_models, endgame_tables=endgame_tables,
-                 endgame_wait=endgame_wait, **engine_kwargs_from_params(params, async_searches))
+                 endgame_wait=endgame_wait, leaf_endgame=leaf_endgame, leaf_free=leaf_free, leaf_models=leaf_models,
+                 **engine_kwargs_from_params(params, async_searches))
     try:
         if model.kind in ("resnet", "simplenn"):
             eng.load_state_dict(model.state_dict(), model.kind, **model.shape)
@@ -400,7 +408,8 @@ def match_winners(samples, generations):
 
 
 def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=None, cols=None, n_slots=None, device=0,
-                nn_precision=None, openings=None, endgame=None, endgame_models=(0,), endgame_tables=None, endgame_wait=False):
+                nn_precision=None, openings=None, endgame=None, endgame_models=(0,), endgame_tables=None, endgame_wait=False,
+                leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
     """Reference: self_play.compute_elo(elo_params, [params0, params1], [gen0, gen1], (elo0, elo1)).
     The two models play elo_params.n_games games against each other on the GPU: the model of the
     player to move at the root runs that move's whole search (self_play.py:59,237-239), seats are
@@ -414,6 +423,8 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     same network with and without it -- params twice, endgame_models=(0,) -- is then one call.  endgame_tables: with a DeepTables, a pool
     of that many tables shared by the slots and by both models (Engine(endgame_tables=N)); endgame_wait: a slot that finds that pool dry
     waits for a table (Engine(endgame_wait=True)), so that the match does not depend on the pool's size.
+    leaf_endgame, leaf_free, leaf_models: an endgame.Endgame that solves the leaves with at most leaf_free free edges of the listed
+    models from scratch, whatever the root (Engine.attach_leaf_solver).
     Returns (elo0, elo1, n1 / number of decided games)."""
     from .engine import Engine
     p0, p1 = params
@@ -441,7 +452,8 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
             mdl.load_parameters(gen)  # compare_models: generation g itself (self_play.py:190)
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=models[0].kind, evaluator2=models[1].kind,
                  match_play=True, device=device, nn_precision=nn_precision, endgame=endgame, endgame_models=endgame_models,
-                 endgame_tables=endgame_tables, endgame_wait=endgame_wait, **kw)
+                 endgame_tables=endgame_tables, endgame_wait=endgame_wait, leaf_endgame=leaf_endgame, leaf_free=leaf_free,
+                 leaf_models=leaf_models, **kw)
     try:
         for i, mdl in enumerate(models):
             eng.load_state_dict(mdl.state_dict(), mdl.kind, model=i, **mdl.shape)

@@ -592,7 +592,7 @@ int dbaz_dataset_exact_targets(dbaz_engine *e, dbaz_endgame *g, int32_t pi_mode,
  * (p, v), bit for bit.  Such a leaf never reaches the model's own evaluator, network or formula: it is not on the evaluation lists,
  * not counted in or deferred by the full-rounds cut, skips the transposition probe and is not counted in dbaz_counters.nn_evals.
  * Every other leaf is handled as without the attach; in particular a leaf with F <= max_free under a root with F > max_free still
- * goes to the model's evaluator (the table is rooted at search roots only).  A table is valid for the slot's current game only.
+ * goes to the model's evaluator (the table is rooted at search roots only; dbaz_attach_leaf_solver below solves such leaves).  A table is valid for the slot's current game only.
  * model: 0, or 1 = the second model in match play.  The engine BORROWS g: it must outlive the engine's use of it.
  * endgame_reads > 0: a search under the driver's rule (num_reads == NULL, self-play) whose root has F <= max_free runs
  * min(rule, endgame_reads) reads; 0 = the rule; explicit num_reads are never touched.
@@ -808,6 +808,35 @@ int dbaz_attach_tables_pool_wait(dbaz_engine *e, int32_t model, dbaz_tables *t, 
  * slot-passes spent waiting -- what `denied` would have counted -- cumulative since the first attach.  All 0 without a pooled
  * attach.  Any output pointer may be NULL. */
 int dbaz_get_table_pool_waits(dbaz_engine *e, int32_t *wait_mode, int32_t *waiting, int64_t *waited);
+
+/* ---- exact endgames at the LEAVES: a leaf with few free edges is solved from scratch ------------------------------
+ * The attaches above answer leaves from a table rooted at a search root; this one needs no root and no HBM.  With a leaf solver
+ * attached to the searching model with threshold L (1 <= L <= g's max_free <= 16), a non-terminal leaf -- the root expansion of a
+ * search counts as a leaf -- is treated as follows:
+ *   - the slot's table serves the game (any attach above): the leaf is answered from the table, as without this attach -- the
+ *     table wins because it is a lookup;
+ *   - otherwise, the leaf's own number of free real edges is F <= L: the leaf is SOLVED from scratch.  Its (p, v) is
+ *     dbaz_exact_policy's for that position and this attach's pick_seed, bit for bit.  Such a leaf is not on the evaluation lists,
+ *     is not counted in or deferred by the full-rounds cut, skips the transposition probe and insert, is not counted in
+ *     dbaz_counters.nn_evals, and is counted by dbaz_get_leaf_solves;
+ *   - otherwise the leaf goes to the model's evaluator, as without this attach.
+ * The rule depends on the leaf's position and the model only: not on the root, the slot, the step or the batch.  It applies to
+ * dbaz_search / dbaz_search_timed, self-play, match play and selfplay_pending waves (there a terminal or duplicate leaf of a wave
+ * is not solved, as it is not evaluated), alone or next to dbaz_attach_endgame, dbaz_attach_tables and the pool in either mode: a
+ * slot that a dry pool denied, or whose table is not valid yet, gets exact leaves a few moves earlier.  endgame_reads stays a
+ * property of table-served searches.  The solves run between selection and expansion in one launch per class of F that L reaches
+ * (16 / 14-15 / 11-13 / 0-10; 2^F bytes of LDS per leaf), a sequence fixed by the attach: nothing is read back inside a step.
+ * The engine BORROWS g and writes nothing to it: the same handle may be attached as dbaz_attach_endgame's or used for
+ * dbaz_exact_targets meanwhile.  model: 0, or 1 = the second model in match play.  leaf_free: L, 0 = g's max_free.
+ * g == NULL detaches the model (its leaves go to its evaluator again; the counters stay).
+ *   the model's evaluator DBAZ_EVAL_EXTERNAL or DBAZ_EVAL_SOLVER, model not 0 / 1 (1 without match play), g of another board size
+ *   or device, leaf_free < 0 or > g's max_free                                          -> DBAZ_EINVAL
+ *   between dbaz_search_begin and the end of that search, or while games of a dbaz_selfplay_start are being played -> DBAZ_ESTATE
+ * A refused call changes nothing.  (Not named dbaz_endgame_*, like dbaz_exact_policy.) */
+int dbaz_attach_leaf_solver(dbaz_engine *e, int32_t model, dbaz_endgame *g, int32_t leaf_free, uint64_t pick_seed);
+/* by_free int64 [17]: the leaves solved per F = 0 .. 16 (F = 0 never occurs: such a position is finished), cumulative since the
+ * first attach, both models together; waits for the engine's queued work.  All 0 without an attach. */
+int dbaz_get_leaf_solves(dbaz_engine *e, int64_t *by_free /*[17]*/);
 
 #ifdef __cplusplus
 }
