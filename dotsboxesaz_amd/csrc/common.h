@@ -163,7 +163,8 @@ struct TreeBufs {
     int32_t *eval_list;// [n_slots] compacted slots needing an NN evaluation (model 0)
     int32_t *ev_class;  // [n_slots] full rounds only: k_select's class of each slot's leaf, for k_order_evals
     int32_t *eval_list2;// [n_slots] same for model 1 (match play)
-    int32_t *n_eval;   // [4] list lengths of the two models; [2] leaves model 0's network took this step (k_tower, full rounds only)
+    int32_t *n_eval;   // [4] [0], [1] lengths of eval_list (list_m in a wave) and eval_list2; [2] leaves model 0's network took this
+                       // step (k_tower, full rounds only); [3] length of the list of ROUTE_TABLE (tree.h)
     int32_t *pend;     // [n_slots][cap] ring: dropped nodes waiting for the collector (their child rows are still needed)
     int32_t *freel;    // [n_slots][cap] stack: node indices ready for reuse
     // search with K > 1 pending evaluations per tree (buffers exist when dbaz_config.max_pending_evals > 1)

@@ -146,6 +146,32 @@ static int dmalloc(dbaz_engine *e, T **p, size_t count, bool zero = true)
     return 0;
 }
 
+// everything queued on either stream is done: what a host read of state that the driver pass (stream2) writes waits for
+static int sync_streams(dbaz_engine *e)
+{
+    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    return DBAZ_OK;
+}
+
+// All or nothing: n device blocks of bytes[i] (0: none, p[i] null), bit i of `zero` = zeroed; a failure frees all and clears HIP's error
+static hipError_t alloc_all(dbaz_engine *e, int n, const size_t *bytes, unsigned zero, void **p)
+{
+    hipError_t err = hipSuccess;
+    for (int i = 0; i < n; i++) p[i] = nullptr;
+    for (int i = 0; i < n && err == hipSuccess; i++) {
+        if (!bytes[i]) continue;
+        err = hipMalloc(&p[i], bytes[i]);
+        if (err != hipSuccess) p[i] = nullptr;
+        else if ((zero >> i) & 1u) err = hipMemset(p[i], 0, bytes[i]);
+    }
+    for (int i = 0; i < n; i++)
+        if (p[i] && err == hipSuccess) e->allocs.push_back(p[i]);
+        else if (p[i]) (void)hipFree(p[i]);
+    if (err != hipSuccess) (void)hipGetLastError();
+    return err;
+}
+
 static int ensure_stage(dbaz_engine *e, size_t bytes)
 {
     if (bytes <= e->stage_bytes) return 0;
@@ -660,7 +686,7 @@ static void endgame_solve_tables(dbaz_engine *e, hipStream_t s)
     if (g) endgame_tables(g, s, e->eg_start.req, e->eg_hdr, e->eg_tables, e->n_slots, e->eg_stats);
 }
 
-// the leaves k_select / k_select_multi put on eg_list, where solver_forward serves its lists
+// the leaves k_select / k_select_multi put on the list of ROUTE_TABLE, where solver_forward serves its lists
 static void endgame_eval_leaves(dbaz_engine *e, hipStream_t s, const float *feat, int per_slot, float *P, float *V)
 {
     if (e->eg_tables)
@@ -896,29 +922,17 @@ extern "C" int dbaz_attach_solver(dbaz_engine *e, int32_t model, dbaz_solver *s,
     return DBAZ_OK;
 }
 
-// the slot tables of either kind of attach: n_regions x stride bytes, plus headers, requests, the leaf list and the counters; nothing
-// is kept when one allocation fails (*err)
-static bool endgame_alloc_slots(dbaz_engine *e, size_t n_regions, size_t stride, void *p[6], hipError_t *err)
+// the slot tables of either kind of attach: n_regions x stride bytes (not zeroed), plus headers, requests, the leaf list, the leaf
+// flags and the counters; nothing is kept when one allocation fails
+static hipError_t endgame_alloc_slots(dbaz_engine *e, size_t n_regions, size_t stride)
 {
     const size_t ns = e->n_slots;
     const size_t bytes[6] = {n_regions * stride, ns * sizeof(EndgameSlotHdr), ns * sizeof(EndgameReq), ns * (size_t)e->B.kmax * 4, ns * (size_t)e->B.kmax * 4, 16};
-    for (int i = 0; i < 6; i++) p[i] = nullptr;
-    *err = hipStreamSynchronize(e->stream);
-    for (int i = 0; i < 6 && *err == hipSuccess; i++) {
-        *err = hipMalloc(&p[i], bytes[i]);
-        if (*err != hipSuccess) p[i] = nullptr;
-        else if (i) *err = hipMemset(p[i], 0, bytes[i]);
-    }
-    if (*err == hipSuccess) return true;
-    for (int i = 0; i < 6; i++)
-        if (p[i]) (void)hipFree(p[i]);
-    (void)hipGetLastError();
-    return false;
-}
-
-static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
-{
-    for (int i = 0; i < 6; i++) e->allocs.push_back(p[i]);
+    void *p[6];
+    hipError_t err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess) err = alloc_all(e, 6, bytes, 0x3eu, p);
+    else (void)hipGetLastError();
+    if (err != hipSuccess) return err;
     e->eg_tables = (int8_t *)p[0];
     e->eg_hdr = (EndgameSlotHdr *)p[1];
     e->G.hdr = e->eg_hdr;
@@ -927,6 +941,7 @@ static void endgame_keep_slots(dbaz_engine *e, size_t stride, void *p[6])
     e->G.list = (int32_t *)p[3];
     e->G.leaf = (int32_t *)p[4];
     e->eg_stats = (unsigned long long *)p[5];
+    return hipSuccess;
 }
 
 // What both attach entries do once their handle is resolved: `kind` names the handle's type and entry in messages, stride is the
@@ -964,8 +979,7 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
     if (e->eg_tables) {
         // a re-attach: tables solved under the handle it replaces do not serve on (headers and requests are dropped); a search
         // that is running goes on with its model's evaluator until its next root
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = sync_streams(e)) return r;
         if (int r = endgame_drop_tables(e)) return r;
         HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
     } else {
@@ -973,16 +987,13 @@ static int attach_slot_tables(dbaz_engine *e, int32_t model, const char *kind, d
         void *lists[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (deep)
             if (int rc = slot_tables_setup(deep, e->n_slots, n_tables, &st, lists, wait)) return set_error(e, rc, "%s", dbaz_tables_last_error(deep));
-        void *p[6];
-        hipError_t err = hipSuccess;
         const int n_regions = n_tables > 0 ? n_tables : e->n_slots;
-        if (!endgame_alloc_slots(e, (size_t)n_regions, stride, p, &err)) {
+        if (const hipError_t err = endgame_alloc_slots(e, (size_t)n_regions, stride)) {
             for (void *q : lists)
                 if (q) (void)hipFree(q);
             return set_error(e, DBAZ_EDEVICE, "slot tables of %d %s x %zu bytes = %llu bytes: %s", n_regions, n_tables > 0 ? "pooled regions" : "slots",
                              stride, (unsigned long long)n_regions * stride, hipGetErrorString(err)); // 64 bits: 8192 slots x 2^20 is past 32
         }
-        endgame_keep_slots(e, stride, p);
         for (void *q : lists)
             if (q) e->allocs.push_back(q);
         e->slot_tables = st;
@@ -1019,47 +1030,35 @@ extern "C" int dbaz_attach_endgame(dbaz_engine *e, int32_t model, dbaz_endgame *
     return DBAZ_OK;
 }
 
-// Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own (slot_tables_setup).
-extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads)
+// What the three deep attach entries share.  pooled: n_tables regions that the slots share (table_pool.h; both models of a match draw
+// on one pool), else 0.  Nothing of the dbaz_tables is kept: board and max_free are copied, the work lists are the engine's own.
+static int attach_deep_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, bool pooled, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads,
+                              bool wait)
 {
     if (!e) return DBAZ_EINVAL;
     USE_DEVICE(e);
     if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
-    int max_free = 0;
-    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
-        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
-                         e->cfg.device);
-    return attach_slot_tables(e, model, "dbaz_tables", t, 0, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
-}
-
-// The same with n_tables regions that the slots share (table_pool.h, slot_tables_pass): both models of a match draw on one pool.
-extern "C" int dbaz_attach_tables_pool(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads)
-{
-    if (!e) return DBAZ_EINVAL;
-    USE_DEVICE(e);
-    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
-    if (n_tables < 1 || n_tables > e->n_slots)
+    if (pooled && (n_tables < 1 || n_tables > e->n_slots))
         return set_error(e, DBAZ_EINVAL, "n_tables %d: a pool has 1 .. n_slots = %d regions", n_tables, e->n_slots);
     int max_free = 0;
     if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
         return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
                          e->cfg.device);
-    return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads);
+    return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads, wait);
 }
 
+extern "C" int dbaz_attach_tables(dbaz_engine *e, int32_t model, dbaz_tables *t, uint64_t pick_seed, int32_t endgame_reads)
+{
+    return attach_deep_tables(e, model, t, false, 0, pick_seed, endgame_reads, false);
+}
+extern "C" int dbaz_attach_tables_pool(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads)
+{
+    return attach_deep_tables(e, model, t, true, n_tables, pick_seed, endgame_reads, false);
+}
 // The pool in wait mode (the rule is stated in full in include/dbaz.h): a slot that finds it dry waits for a region.
 extern "C" int dbaz_attach_tables_pool_wait(dbaz_engine *e, int32_t model, dbaz_tables *t, int32_t n_tables, uint64_t pick_seed, int32_t endgame_reads)
 {
-    if (!e) return DBAZ_EINVAL;
-    USE_DEVICE(e);
-    if (!t) return set_error(e, DBAZ_EINVAL, "null deep tables");
-    if (n_tables < 1 || n_tables > e->n_slots)
-        return set_error(e, DBAZ_EINVAL, "n_tables %d: a pool has 1 .. n_slots = %d regions", n_tables, e->n_slots);
-    int max_free = 0;
-    if (!tables_serves(t, e->g.rows, e->g.cols, e->cfg.device, &max_free))
-        return set_error(e, DBAZ_EINVAL, "the deep tables are of another board size or device than this %dx%d handle on device %d", e->g.rows, e->g.cols,
-                         e->cfg.device);
-    return attach_slot_tables(e, model, "dbaz_tables", t, n_tables, max_free, (size_t)1 << max_free, pick_seed, endgame_reads, true);
+    return attach_deep_tables(e, model, t, true, n_tables, pick_seed, endgame_reads, true);
 }
 
 extern "C" int dbaz_get_table_pool_waits(dbaz_engine *e, int32_t *wait_mode, int32_t *waiting, int64_t *waited)
@@ -1069,8 +1068,7 @@ extern "C" int dbaz_get_table_pool_waits(dbaz_engine *e, int32_t *wait_mode, int
     int32_t use = 0, high = 0, now = 0;
     int64_t den = 0, total = 0;
     if (e->eg_n_tables) {
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = sync_streams(e)) return r;
         HIP_CHECK_RET(e, slot_tables_pool_read(&e->slot_tables, &use, &high, &den, &now, &total));
     }
     if (wait_mode) *wait_mode = e->eg_n_tables && e->eg_wait ? 1 : 0;
@@ -1086,8 +1084,7 @@ extern "C" int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *i
     int32_t use = 0, high = 0;
     int64_t den = 0;
     if (e->eg_n_tables) {
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = sync_streams(e)) return r;
         HIP_CHECK_RET(e, slot_tables_pool_read(&e->slot_tables, &use, &high, &den));
     }
     if (n_tables) *n_tables = e->eg_n_tables;
@@ -1100,8 +1097,7 @@ extern "C" int dbaz_get_table_pool(dbaz_engine *e, int32_t *n_tables, int32_t *i
 // the header of a slot after the queued work; *table: the region it names (-1: a pooled slot that holds none)
 static int read_slot_hdr(dbaz_engine *e, int32_t slot, EndgameSlotHdr *h, int32_t *table)
 {
-    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    if (int r = sync_streams(e)) return r;
     HIP_CHECK_RET(e, hipMemcpy(h, e->eg_hdr + slot, sizeof *h, hipMemcpyDeviceToHost));
     *table = e->eg_n_tables ? (h->table >= 0 && h->table < e->eg_n_tables ? h->table : -1) : slot;
     return DBAZ_OK;
@@ -1148,7 +1144,7 @@ extern "C" void dbaz_get_endgame_stats(const dbaz_engine *e, int64_t *tables_sol
     unsigned long long st[2] = {0, 0};
     if (e && e->eg_stats) {
         (void)hipSetDevice(e->cfg.device);
-        (void)hipStreamSynchronize(e->stream);
+        (void)hipStreamSynchronize(e->stream); // (a const handle and no error to report: not sync_streams)
         if (e->stream2) (void)hipStreamSynchronize(e->stream2);
         (void)hipMemcpy(st, e->eg_stats, sizeof st, hipMemcpyDeviceToHost);
     }
@@ -1182,8 +1178,7 @@ extern "C" int dbaz_attach_leaf_solver(dbaz_engine *e, int32_t model, dbaz_endga
         if (r) return r;
         if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
     }
-    HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-    if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+    if (int r = sync_streams(e)) return r;
     if (!g) { // detach: the model's leaves go to its evaluator again; the counters stay
         e->G.ls_free[model] = 0;
         e->leaf_solver[model] = nullptr;
@@ -1193,24 +1188,11 @@ extern "C" int dbaz_attach_leaf_solver(dbaz_engine *e, int32_t model, dbaz_endga
         const size_t cap = (size_t)e->n_slots * (size_t)e->B.kmax;
         if (cap >= ((size_t)1 << LEAF_SOLVE_MODEL_SHIFT))
             return set_error(e, DBAZ_EINVAL, "leaf solver: %zu leaves per step do not fit a list entry", cap);
-        void *p[4] = {nullptr, nullptr, nullptr, nullptr}; // lists, counters, statistics, the leaf flags (unless a table attach made them)
+        void *p[4]; // lists, counters, statistics, the leaf flags (unless a table attach made them)
         const size_t bytes[4] = {LEAF_SOLVE_CLASSES * cap * 4, LEAF_SOLVE_CLASSES * 4, (ENDGAME_MAX_FREE + 1) * sizeof(unsigned long long),
                                  e->G.leaf ? 0 : cap * 4};
-        hipError_t err = hipSuccess;
-        for (int i = 0; i < 4 && err == hipSuccess; i++) {
-            if (!bytes[i]) continue;
-            err = hipMalloc(&p[i], bytes[i]);
-            if (err != hipSuccess) p[i] = nullptr;
-            else err = hipMemset(p[i], 0, bytes[i]);
-        }
-        if (err != hipSuccess) {
-            for (void *q : p)
-                if (q) (void)hipFree(q);
-            (void)hipGetLastError();
+        if (const hipError_t err = alloc_all(e, 4, bytes, 0xfu, p))
             return set_error(e, DBAZ_EDEVICE, "leaf solver lists of %zu entries: %s", cap, hipGetErrorString(err));
-        }
-        for (void *q : p)
-            if (q) e->allocs.push_back(q);
         e->G.ls_list = (int32_t *)p[0];
         e->G.ls_cnt = (int32_t *)p[1];
         e->ls_stats = (unsigned long long *)p[2];
@@ -1229,8 +1211,7 @@ extern "C" int dbaz_get_leaf_solves(dbaz_engine *e, int64_t *by_free)
     USE_DEVICE(e);
     unsigned long long st[ENDGAME_MAX_FREE + 1] = {};
     if (e->ls_stats) {
-        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
-        if (e->stream2) HIP_CHECK_RET(e, hipStreamSynchronize(e->stream2));
+        if (int r = sync_streams(e)) return r;
         HIP_CHECK_RET(e, hipMemcpy(st, e->ls_stats, sizeof st, hipMemcpyDeviceToHost));
     }
     for (int f = 0; f <= ENDGAME_MAX_FREE; f++) by_free[f] = (int64_t)st[f];

@@ -1,11 +1,9 @@
 // tree.h -- host launchers of the tree / rules kernels (tree.hip)
 #pragma once
 #include "common.h"
+#include "endgame.h"
 #include "forced_playouts.h"
 #include "playout_cap.h"
-
-struct EndgameReq;     // endgame.h
-struct EndgameSlotHdr; // endgame.h
 
 // Evaluators that answer through the evaluation list: k_select / k_select_multi append their leaves to eval_list / eval_list2 /
 // list_m, a launch between select and expand fills evalP / evalV, and expand reads (p, v) from there -- the networks and the
@@ -42,13 +40,18 @@ struct StartArgs {
     PlayoutCap pc; // dbaz_selfplay_set_playout_cap: the self-play driver's launches only (all zero = off for k_search_begin)
 };
 
+// Who answers a leaf, and so which list k_select / k_select_multi put it on.  ROUTE_NONE: nobody has to (terminal, duplicate, formula
+// evaluator, transposition hit).  ROUTE_MODEL0 / 1: that model's evaluator, through eval_list / eval_list2 / list_m.  ROUTE_TABLE: the
+// slot's endgame table.  ROUTE_SOLVE + c: the leaf solver, class c.  tree.hip: leaf_route decides, route_counter / route_put hold the lists.
+enum { ROUTE_NONE = -1, ROUTE_MODEL0 = 0, ROUTE_MODEL1 = 1, ROUTE_TABLE = 2, ROUTE_SOLVE = 3, N_ROUTES = ROUTE_SOLVE + LEAF_SOLVE_CLASSES };
+
 // One game's endgame table per slot as an evaluator inside the search (endgame.h; all zero until dbaz_attach_endgame): a leaf of a
-// slot whose searching model has one attached and whose table serves the slot's game goes on `list` -- not on eval_list /
-// eval_list2 / list_m -- and expand reads its (p, v) from evalP / evalV whatever the evaluator.  The list's length is n_eval[3].
+// slot whose searching model has one attached and whose table serves the slot's game takes ROUTE_TABLE: it goes on `list` (length
+// n_eval[3]), not on eval_list / eval_list2 / list_m, and expand reads its (p, v) from evalP / evalV whatever the evaluator.
 struct EndgameBufs {
     const EndgameSlotHdr *hdr; // [n_slots]
     int32_t *list;             // [n_slots * kmax] slots, or slot * kmax + k in a wave
-    int32_t *leaf;             // [n_slots * kmax] 1 = the leaf (of simulation k) is answered from the table, 2 + c = by the leaf solver
+    int32_t *leaf;             // [n_slots * kmax] the route of the leaf (of simulation k) where it is >= ROUTE_TABLE, else 0
     int32_t model[2];          // 1 = the model has an endgame solver attached
     int32_t wait;              // 1 (dbaz_attach_tables_pool_wait) = a slot may be waiting for a region of the pool: see endgame_slot_waits
     // dbaz_attach_leaf_solver (all zero until then; independent of the table state above, but for `leaf`, which either attach

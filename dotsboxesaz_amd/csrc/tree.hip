@@ -458,6 +458,10 @@ __device__ __forceinline__ int rule_num_reads(const Geo &g, const SearchCfg &cfg
     return f < (double)cfg.mcts_num_read ? (int)f : cfg.mcts_num_read;
 }
 
+// Match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the whole search of this move; odd
+// games swap the seats (the reference shuffles them by worker pid)
+__device__ __forceinline__ int search_model(const SearchCfg &cfg, int to_play, int64_t game_idx) { return cfg.match_play ? ((to_play ^ (int)(game_idx & 1)) & 1) : 0; }
+
 // The slot's game is over.  With a pool of tables shared by the slots (EndgameStart::release) the region it holds goes back in
 // the pass that follows on this stream, whether or not the slot starts another game.
 __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, const Slot *S, int lane)
@@ -486,9 +490,8 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     if (num_reads < 0) {
         num_reads = rule_num_reads(g, cfg, rm.st);
         if (fast) num_reads = min(num_reads, sa.pc.fast_reads);
-        // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads); the model of a
-        // move's search is chosen as select_one chooses it
-        const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
+        // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads)
+        const int model = search_model(cfg, rm.st.to_play, S->game_idx);
         if ((model ? cfg.evaluator2 : cfg.evaluator) == DBAZ_EVAL_SOLVER && sa.caps.cap[model] > 0) num_reads = min(num_reads, sa.caps.cap[model]);
         // the same for a search whose leaves the slot's endgame table will answer (dbaz_attach_endgame's endgame_reads)
         if (sa.caps.eg_cap[model] > 0 && gs_count_valid(g, rm.st) <= sa.eg.max_free[model]) num_reads = min(num_reads, sa.caps.eg_cap[model]);
@@ -509,7 +512,7 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     }
     if (sa.eg.req) {
         // a search starts: k_endgame_table (next on this stream) solves or re-checks the slot's table before the first selection
-        const int model = cfg.match_play ? ((rm.st.to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
+        const int model = search_model(cfg, rm.st.to_play, S->game_idx);
         if (sa.eg.max_free[model] > 0 && lane == 0) {
             EndgameReq rq;
             rq.free_edges[0] = ~(rm.st.e0 | g.sentinel[0]) & g.amask[0];
@@ -804,9 +807,7 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
 // full rounds only: k_select's class of each slot's leaf (TreeBufs::ev_class), read by k_order_evals
 #define EV_CLASS_DEFERRED (-2) // the leaf of an earlier step whose evaluation was put off: head of the list
 #define EV_CLASS_NEW (-3)      // a leaf selected in this step
-#define SEL_DEFERRED 2         // select_one: the slot's put-off leaf asks again (full rounds only)
-#define SEL_ENDGAME 3          // select_one: the leaf is answered from the slot's endgame table (eg_list)
-#define SEL_LEAF_SOLVE 4       // select_one: + c = the leaf is solved from scratch, class c of leaf_solve_class (EndgameBufs::ls_list)
+#define SEL_DEFERRED (-2)      // select_one, beside the routes: the slot's put-off leaf asks again (full rounds only)
 
 // The leaf solver's rule (include/dbaz.h, dbaz_attach_leaf_solver) for a non-terminal leaf that no table serves: a leaf with
 // at most ls_free[model] free real edges is solved from scratch.  Returns its class, or -1.  Scalar popcounts: wave-uniform.
@@ -817,8 +818,37 @@ __device__ __forceinline__ int leaf_solve_rule(const Geo &g, const EndgameBufs &
     const int F = gs_count_valid(g, st);
     return F <= L ? leaf_solve_class(F) : -1;
 }
-// G.leaf: 0 = the model's evaluator, 1 = the slot's table, 2 + c = solved from scratch in class c
-__device__ __forceinline__ void leaf_solve_append(const EndgameBufs &G, int c, int at, int entry) { G.ls_list[(size_t)c * G.ls_cap + at] = entry; }
+// does the slot's table serve the leaves of this game's search by `model` (one header read)
+__device__ __forceinline__ bool table_serves(const EndgameBufs &G, int slot, int64_t game, int model) { return G.hdr && G.model[model] && endgame_hdr_serves(G.hdr[slot], game); }
+// The route (tree.h) of a non-terminal, non-duplicate leaf of a search by `model`; tab = table_serves.  A leaf under a valid table
+// of its game is answered from it, whatever the evaluator: it is a lookup, so it wins over the leaf solver.  Either keeps the leaf
+// off the evaluation lists (so it is never counted in or deferred by the full-rounds cut) and away from the transposition probe.
+__device__ __forceinline__ int leaf_route(const Geo &g, const SearchCfg &cfg, const EndgameBufs &G, int model, const GState &st, bool tab)
+{
+    if (tab) return ROUTE_TABLE;
+    const int c = leaf_solve_rule(g, G, model, st);
+    return c >= 0 ? ROUTE_SOLVE + c : (eval_uses_list(model ? cfg.evaluator2 : cfg.evaluator) ? model : ROUTE_NONE);
+}
+// EndgameBufs::leaf, select to expand: the leaf's route where a table or the leaf solver answers it (its (p, v) are in evalP /
+// evalV whatever the evaluator), else 0.  leaf_answered is its only reader.
+__device__ __forceinline__ void leaf_note(const EndgameBufs &G, size_t row, int route) { if (G.leaf) G.leaf[row] = route >= ROUTE_TABLE ? route : 0; }
+__device__ __forceinline__ int leaf_answered(const EndgameBufs &G, size_t row) { return G.leaf ? G.leaf[row] : 0; }
+// The lists of the routes.  route_counter: the length word of route r's list.  route_put: entry (the slot, or slot * K + k in a wave)
+// goes to place `at` of it; a wave's leaves for the model are on list_m, a single leaf also leaves its place in Slot::eval_pos.
+__device__ __forceinline__ int32_t *route_counter(const TreeBufs &B, const EndgameBufs &G, int r)
+{
+    return r >= ROUTE_SOLVE ? G.ls_cnt + (r - ROUTE_SOLVE) : B.n_eval + (r == ROUTE_TABLE ? 3 : r); // (n_eval[2] is k_tower's)
+}
+__device__ __forceinline__ void route_put(const TreeBufs &B, const EndgameBufs &G, int r, int at, int entry, bool wave)
+{
+    if (r >= ROUTE_SOLVE) G.ls_list[(size_t)(r - ROUTE_SOLVE) * G.ls_cap + at] = entry;
+    else if (r == ROUTE_TABLE) G.list[at] = entry;
+    else if (wave) B.list_m[at] = entry;
+    else {
+        (r ? B.eval_list2 : B.eval_list)[at] = entry;
+        B.slots[entry].eval_pos = at;
+    }
+}
 
 // The pool of tables in wait mode (dbaz_attach_tables_pool_wait): a slot whose search found the pool dry selects nothing until a
 // pass grants it a region (EndgameSlotHdr::wait == ENDGAME_WAITING) -- its reads and its tree stay as begin_search left them.  The
@@ -831,7 +861,7 @@ __device__ __forceinline__ bool endgame_slot_waits(const SearchCfg &cfg, const E
     return w == ENDGAME_WAITING || (w == cfg.step && cfg.driver_concurrent);
 }
 
-// returns the model (0 / 1) whose network must evaluate this game's leaf, SEL_DEFERRED, SEL_ENDGAME, SEL_LEAF_SOLVE + class, or -1
+// returns the route of this game's leaf (ROUTE_NONE: of no leaf, or of one that goes on no list), or SEL_DEFERRED
 template <int NPL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
@@ -840,11 +870,11 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     // (one address for the whole wave: say so, and the branches on it are scalar)
     const int phase = __builtin_amdgcn_readfirstlane((int)(unsigned)pw), stamp = __builtin_amdgcn_readfirstlane((int)(unsigned)(pw >> 32));
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
-        return -1;
+        return ROUTE_NONE;
     if (stamp == cfg.step && cfg.driver_concurrent) // search started by this step's driver pass (see set_phase_stamped)
-        return -1;
+        return ROUTE_NONE;
     if (endgame_slot_waits(cfg, G, slot))
-        return -1;
+        return ROUTE_NONE;
     if (cfg.eval_round > 0 && S->pending) {
         // the leaf of an earlier step whose evaluation was put off (full rounds only): path, leaf and features are still in place.
         // k_order_evals puts it at the head of the list.
@@ -860,13 +890,11 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, 0u, lane);
     if (lf.err) {
         if (lane == 0) { S->error = lf.err; S->phase = PH_ERROR; }
-        return -1;
+        return ROUTE_NONE;
     }
     const NodeMeta &m = lf.m;
     const int cur = lf.cur;
-    // match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the
-    // whole search of this move; odd games swap the seats (the reference shuffles them by worker pid)
-    const int model = cfg.match_play ? ((lf.root_to_play ^ (int)(S->game_idx & 1)) & 1) : 0;
+    const int model = search_model(cfg, lf.root_to_play, S->game_idx);
     gc_finish(gcb, g, B, slot, q, lane);
     path_put(path, lf.depth, cur, lf.in_move, m, lane);
     if (lane == 0) {
@@ -880,24 +908,15 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
         S->model = model;
         if (q.n_nodes > S->pool_high) S->pool_high = q.n_nodes;
     }
-    int need_eval = -1;
-    // a leaf under a valid table of this game is answered from it, whatever the evaluator: not on the evaluation lists (so never
-    // counted in or deferred by the full-rounds cut), no transposition probe
-    const bool tab = !(m.flags & NF_TERMINAL) && G.hdr && G.model[model] && endgame_hdr_serves(G.hdr[slot], S->game_idx);
-    // the same holds for a leaf that the model's leaf solver answers; the table wins: it is a lookup
-    const int lsc = (m.flags & NF_TERMINAL) || tab ? -1 : leaf_solve_rule(g, G, model, m.st);
-    const bool eg = tab || lsc >= 0;
-    if (G.leaf && lane == 0) G.leaf[slot] = tab ? 1 : (lsc >= 0 ? 2 + lsc : 0);
+    int route = (m.flags & NF_TERMINAL) ? ROUTE_NONE : leaf_route(g, cfg, G, model, m.st, table_serves(G, slot, S->game_idx, model));
+    if (lane == 0) leaf_note(G, slot, route);
     if (!(m.flags & NF_TERMINAL)) {
         write_features(g, m.st, B.feat + (size_t)slot * 3 * g.HW, lane);
         const int ev = model ? cfg.evaluator2 : cfg.evaluator;
-        if (tab) need_eval = SEL_ENDGAME;
-        else if (lsc >= 0) need_eval = SEL_LEAF_SOLVE + lsc;
-        else if (eval_uses_list(ev)) need_eval = model;
         int hit = -1;
         // (the table exists for network evaluators, and for the formula evaluators when forced on -- transposition_cache
         // = 2 -- so that the hit path can be compared with the oracle bit for bit)
-        if (B.tt && leaf_uses_transpositions(ev, eg)) {
+        if (B.tt && leaf_uses_transpositions(ev, route >= ROUTE_TABLE)) {
             // lanes 0..TT_PROBES-1 read the probe window; a candidate is verified against the live tree
             const uint64_t h = formula_hash(m.st);
             const unsigned long long *tt = B.tt + (size_t)slot * ((size_t)B.tt_mask + 1);
@@ -921,11 +940,11 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
                     }
                 }
             }
-            if (hit >= 0) need_eval = -1;
+            if (hit >= 0) route = ROUTE_NONE;
         }
         if (lane == 0) S->leaf_hit = hit;
     }
-    return need_eval;
+    return route;
 }
 
 // One wave per game.  Two forms; tree_launch_select picks by cfg.eval_round, and neither form serves the other's path.
@@ -934,51 +953,44 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 // match play, two networks, the manual search calls).  The leaves that need a network evaluation are
 // appended to the per-model lists with ONE global atomic per workgroup and model (positions inside
 // the workgroup come from an LDS counter): a per-wave atomicAdd on the single list counter serialises
-// 8192 same-address atomics per step and was most of this kernel's duration.
+// 8192 same-address atomics per step and was most of this kernel's duration.  The other routes' lists are written the same way.
+// A value that a wave without a slot carries around the descent costs a register for its whole length: `route` is the only one.
 //
 // ONE (full rounds only, cfg.eval_round > 0): one game per workgroup.  There this kernel appends to no network list -- it leaves
 // ev_class[slot] for k_order_evals -- so nothing is left to share between the games of a workgroup: no LDS counters, no barrier,
-// and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare endgame
-// leaf goes onto eg_list, and a leaf of the leaf solver onto its class's list, with the wave's own atomic.
+// and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare leaf of
+// ROUTE_TABLE or the leaf solver goes onto its list with the wave's own atomic.
 template <int NPL, bool ONE>
 __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
     if (ONE) {
         const int slot = blockIdx.x, lane = threadIdx.x;
         if (slot >= n_slots) return;
-        const int model = select_one<NPL>(g, cfg, B, G, slot, lane);
+        const int route = select_one<NPL>(g, cfg, B, G, slot, lane);
         if (lane == 0) {
-            B.ev_class[slot] = model == SEL_DEFERRED ? EV_CLASS_DEFERRED : (model == 0 ? EV_CLASS_NEW : -1);
-            if (model == SEL_ENDGAME) G.list[atomicAdd(B.n_eval + 3, 1)] = slot;
-            if (model >= SEL_LEAF_SOLVE) // (full rounds: one model)
-                leaf_solve_append(G, model - SEL_LEAF_SOLVE, atomicAdd(G.ls_cnt + (model - SEL_LEAF_SOLVE), 1), slot);
+            B.ev_class[slot] = route == SEL_DEFERRED ? EV_CLASS_DEFERRED : (route == ROUTE_MODEL0 ? EV_CLASS_NEW : -1);
+            // (full rounds: one model, so no model bit on a solver entry)
+            if (route >= ROUTE_TABLE) route_put(B, G, route, atomicAdd(route_counter(B, G, route), 1), slot, false);
         }
         return;
     }
-    constexpr int NL = 3 + LEAF_SOLVE_CLASSES;
-    __shared__ int s_cnt[NL], s_base[NL]; // the two models' lists, eg_list and the leaf solver's classes
+    __shared__ int s_cnt[N_ROUTES], s_base[N_ROUTES];
     const int slot = blockIdx.x * SELECT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & (WAVE - 1);
-    if (threadIdx.x < NL) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < N_ROUTES) s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    int model = -1;
-    if (slot < n_slots) model = select_one<NPL>(g, cfg, B, G, slot, lane);
-    int cls = model >= SEL_LEAF_SOLVE ? 3 + (model - SEL_LEAF_SOLVE) : (model == SEL_ENDGAME ? 2 : ((model == 0 || model == 1) ? model : -1));
-    int my = -1;
-    if (cls >= 0 && lane == 0) my = atomicAdd(&s_cnt[cls], 1);
+    int route = ROUTE_NONE; // (no put-off leaves here: they are of the full rounds)
+    if (slot < n_slots) route = select_one<NPL>(g, cfg, B, G, slot, lane);
+    const bool put = route >= 0 && lane == 0;
+    int my = 0;
+    if (put) my = atomicAdd(&s_cnt[route], 1);
     __syncthreads();
-    if (threadIdx.x < 3 && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(B.n_eval + (threadIdx.x == 2 ? 3 : threadIdx.x), s_cnt[threadIdx.x]);
-    if (threadIdx.x >= 3 && threadIdx.x < NL && s_cnt[threadIdx.x] > 0) s_base[threadIdx.x] = atomicAdd(G.ls_cnt + (threadIdx.x - 3), s_cnt[threadIdx.x]);
+    // (two statements: one for all routes holds both counters' addresses in scalar registers across the descent, 16 bytes of scratch)
+    const int t = threadIdx.x;
+    if (t < ROUTE_SOLVE && s_cnt[t] > 0) s_base[t] = atomicAdd(route_counter(B, G, t), s_cnt[t]);
+    if (t >= ROUTE_SOLVE && t < N_ROUTES && s_cnt[t] > 0) s_base[t] = atomicAdd(route_counter(B, G, t), s_cnt[t]);
     __syncthreads();
-    if (my >= 0) {
-        if (cls >= 3) {
-            leaf_solve_append(G, cls - 3, s_base[cls] + my, slot | (B.slots[slot].model << LEAF_SOLVE_MODEL_SHIFT)); // the model's seed picks
-        } else if (cls == 2) {
-            G.list[s_base[2] + my] = slot;
-        } else {
-            (cls ? B.eval_list2 : B.eval_list)[s_base[cls] + my] = slot;
-            B.slots[slot].eval_pos = s_base[cls] + my;
-        }
-    }
+    if (put) // a solver entry carries the model: the model's seed picks
+        route_put(B, G, route, s_base[route] + my, route >= ROUTE_SOLVE ? slot | (B.slots[slot].model << LEAF_SOLVE_MODEL_SHIFT) : slot, false);
 }
 
 // Full rounds only (SearchCfg.eval_round > 0, one model): which leaves land behind the network's cut depends on their order in
@@ -1122,7 +1134,9 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
     int n_sims = phase == PH_EXPAND_ROOT ? 1 : min(width, S->sims_left);
     PoolState q = pool_load(S);
     const unsigned vv = cfg.virtual_visits ? 1u : 0u; // the visit is counted at selection (backup then adds the value only)
-    const bool eg = G.hdr && G.model[0] && endgame_hdr_serves(G.hdr[slot], S->game_idx); // the slot's leaves come from its table
+    // Model 0 here and below: the waves never run match play (dbaz_create refuses the combination), so k_select_multi's solver
+    // entries carry no model bit either.  One header read per slot, not per simulation.
+    const bool tab = table_serves(G, slot, S->game_idx, 0);
     int err = 0, done = 0;
     for (int k = 0; k < n_sims && !err; k++) {
         PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
@@ -1140,11 +1154,10 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
             sr.leaf = lf.cur; sr.path_len = lf.depth + 1; sr.terminal = term ? 1 : 0; sr.result = m.result; sr.to_play = m.st.to_play;
             sr.dup = dup ? 1 : 0;
             if (G.leaf) {
-                // model 0's threshold, and entries without a model bit (so model 0's seed), as for `eg` above: the waves run one
-                // model (sim_wave evaluates cfg.evaluator only).  Waves in match play would have to pass S->model here and
-                // set the entry's bit LEAF_SOLVE_MODEL_SHIFT in k_select_multi.
-                const int lsc = eg || term || dup ? -1 : leaf_solve_rule(g, G, 0, m.st);
-                G.leaf[(size_t)slot * K + k] = (term || dup) ? 0 : (eg ? 1 : (lsc >= 0 ? 2 + lsc : 0));
+                // leaf_route's first half written out, and only with something attached: the K-loop's descents run in sequence and
+                // pay for every register it holds -- calling leaf_route here cost the single tree 1.5 to 3 % (EXPERIMENTS 2)
+                const int lsc = tab || term || dup ? -1 : leaf_solve_rule(g, G, 0, m.st);
+                G.leaf[(size_t)slot * K + k] = (term || dup) ? 0 : (tab ? ROUTE_TABLE : (lsc >= 0 ? ROUTE_SOLVE + lsc : 0));
             }
             B.simrec[(size_t)slot * K + k] = sr;
             if (!term && !dup)
@@ -1173,7 +1186,7 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     if (slot >= n_slots) return;
     select_multi_one<NPL>(g, cfg, B, G, slot, lane);
     __syncthreads();
-    // evaluation list: the wave's simulations that need the network, in simulation order
+    // the lists: the wave's simulations of each route, in simulation order (one loop over all routes is the slower code: EXPERIMENTS 2)
     const Slot *S = B.slots + slot;
     if (S->phase == PH_ERROR) return;
     const int K = B.kmax, n = S->wave_sims;
@@ -1181,30 +1194,28 @@ __global__ void __launch_bounds__(WAVE) k_select_multi(Geo g, SearchCfg cfg, Tre
     if ((!lists && !G.leaf) || S->sel_step != cfg.step) return;
     for (int k0 = 0; k0 < n; k0 += WAVE) {
         const int k = k0 + lane;
-        bool need = false, eg = false;
-        int lsc = -1; // the leaf solver's class of the leaf
+        int route = ROUTE_NONE;
         if (k < n) {
             const SimRec sr = B.simrec[(size_t)slot * K + k];
-            const int how = G.leaf ? G.leaf[(size_t)slot * K + k] : 0; // never set for a terminal or duplicate leaf
-            eg = how == 1;
-            lsc = how >= 2 ? how - 2 : -1;
-            need = lists && !sr.terminal && !sr.dup && how == 0;
+            route = leaf_answered(G, (size_t)slot * K + k); // (0 for a terminal or duplicate leaf)
+            if (route == 0) route = lists && !sr.terminal && !sr.dup ? ROUTE_MODEL0 : ROUTE_NONE;
         }
+        const bool need = route == ROUTE_MODEL0, eg = route == ROUTE_TABLE;
+        const int lsc = route >= ROUTE_SOLVE ? route - ROUTE_SOLVE : -1;
         const unsigned long long mk = __ballot(need), me = __ballot(eg);
         int base = 0, ebase = 0;
-        if (lane == 0 && mk) base = atomicAdd(B.n_eval, (int)__popcll(mk));
-        if (lane == 0 && me) ebase = atomicAdd(B.n_eval + 3, (int)__popcll(me));
-        base = __shfl(base, 0);
-        ebase = __shfl(ebase, 0);
-        if (need) B.list_m[base + (int)__popcll(mk & ((1ull << lane) - 1ull))] = slot * K + k;
-        if (eg) G.list[ebase + (int)__popcll(me & ((1ull << lane) - 1ull))] = slot * K + k;
+        if (lane == 0 && mk) base = atomicAdd(route_counter(B, G, ROUTE_MODEL0), (int)__popcll(mk));
+        if (lane == 0 && me) ebase = atomicAdd(route_counter(B, G, ROUTE_TABLE), (int)__popcll(me));
+        base = __shfl(base, 0), ebase = __shfl(ebase, 0);
+        if (need) route_put(B, G, ROUTE_MODEL0, base + (int)__popcll(mk & ((1ull << lane) - 1ull)), slot * K + k, true);
+        if (eg) route_put(B, G, ROUTE_TABLE, ebase + (int)__popcll(me & ((1ull << lane) - 1ull)), slot * K + k, true);
         for (int c = 0; G.ls_list && c < LEAF_SOLVE_CLASSES; c++) {
             const unsigned long long ml = __ballot(lsc == c);
             if (!ml) continue;
             int lbase = 0;
-            if (lane == 0) lbase = atomicAdd(G.ls_cnt + c, (int)__popcll(ml));
+            if (lane == 0) lbase = atomicAdd(route_counter(B, G, ROUTE_SOLVE + c), (int)__popcll(ml));
             lbase = __shfl(lbase, 0);
-            if (lsc == c) leaf_solve_append(G, c, lbase + (int)__popcll(ml & ((1ull << lane) - 1ull)), slot * K + k);
+            if (lsc == c) route_put(B, G, ROUTE_SOLVE + c, lbase + (int)__popcll(ml & ((1ull << lane) - 1ull)), slot * K + k, true);
         }
     }
 }
@@ -1281,13 +1292,19 @@ __device__ __forceinline__ void end_step(const Geo &g, const SearchCfg &cfg, con
     }
 }
 
+// The step's last kernel resets the per-step counters (the routes' lists and the driver list are consumed by then): no memset launches.
+__device__ __forceinline__ void reset_step_counters(const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
+{
+    if (slot == 0 && lane < N_ROUTES && (lane < ROUTE_SOLVE || G.ls_cnt)) *route_counter(B, G, lane) = 0;
+    if (slot == 0 && lane == 0) B.drv_count[0] = 0;
+}
+
 __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int slot = blockIdx.x, lane = threadIdx.x;
-    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; } // (drv_count: self-play in waves)
-    if (G.ls_cnt && slot == 0 && lane < LEAF_SOLVE_CLASSES) G.ls_cnt[lane] = 0;
+    reset_step_counters(B, G, slot, lane);
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS) return;
@@ -1296,7 +1313,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
     const int K = B.kmax, n = S->wave_sims;
     for (int k = 0; k < n; k++) {
         const SimRec sr = B.simrec[(size_t)slot * K + k];
-        const bool eg = G.leaf && !sr.terminal && !sr.dup && G.leaf[(size_t)slot * K + k] != 0;
+        const bool eg = !sr.terminal && !sr.dup && leaf_answered(G, (size_t)slot * K + k) != 0;
         const PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
         NodeMeta lm = load_meta(pool, g, sr.leaf);
         uint32_t *nd = node_ptr(pool, g, sr.leaf);
@@ -1335,10 +1352,7 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
     __shared__ float ldsf[DBAZ_MAX_A];
     __shared__ double ldsd[DBAZ_MAX_A];
     const int slot = blockIdx.x, lane = threadIdx.x;
-    // the step's last kernel resets the per-step counters for the next one (the evaluation lists were consumed by the network
-    // launches before it, the driver list by the pass joined before them): no memset launches between the kernels
-    if (slot == 0 && lane == 0) { B.n_eval[0] = 0; B.n_eval[1] = 0; B.n_eval[3] = 0; B.drv_count[0] = 0; }
-    if (G.ls_cnt && slot == 0 && lane < LEAF_SOLVE_CLASSES) G.ls_cnt[lane] = 0;
+    reset_step_counters(B, G, slot, lane);
     Slot *S = B.slots + slot;
     const int phase = S->phase;
     if (phase != PH_EXPAND_ROOT && phase != PH_SIMS)
@@ -1355,7 +1369,7 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
     uint32_t *nd = node_ptr(pool, g, leaf);
     float v;
     int hit = -1;
-    const bool eg = !(lm.flags & NF_TERMINAL) && G.leaf && G.leaf[slot] != 0; // (p, v) came from the slot's endgame table or the leaf solver, whatever the evaluator
+    const bool eg = !(lm.flags & NF_TERMINAL) && leaf_answered(G, slot) != 0; // (p, v) came from the slot's endgame table or the leaf solver
     if (!(lm.flags & NF_TERMINAL)) {
         float *Prow = reinterpret_cast<float *>(nd + META_DW);
         const int ev = (cfg.match_play && S->model) ? cfg.evaluator2 : cfg.evaluator;

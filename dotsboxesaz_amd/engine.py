@@ -198,10 +198,7 @@ class Engine:
         the slot's game ends; a slot that finds the pool dry searches that move with its model's own evaluator and is counted
         (table_pool()).  reads must be 0.  Every attach of one Engine is pooled or not, with one max_free and one `tables`:
         DbazError (EINVAL) otherwise, also for an Endgame, and nothing changes."""
-        if endgame.ATTACH != "dbaz_attach_tables":  # the C side cannot tell the two handle types apart
-            raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
-        self._ck(self._L.dbaz_attach_tables_pool(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
-        self._endgames[int(model)] = endgame
+        self._attach_pool("dbaz_attach_tables_pool", endgame, tables, model, seed, reads)
 
     def attach_endgame_pool_wait(self, endgame, tables, model=0, seed=0, reads=0):
         """dbaz_attach_tables_pool_wait: attach_endgame_pool in wait mode.  A slot that finds the pool dry is not denied: its request
@@ -211,9 +208,12 @@ class Engine:
         table_pool_waits() counts the waiting.  The self-play driver only: search() and search_timed() raise DbazError (ESTATE)
         afterwards.  An Engine's pooled attaches are all of one mode: DbazError (EINVAL) otherwise, and nothing changes.
         (A method of its own: attach_endgame_pool keeps its parameters.)"""
+        self._attach_pool("dbaz_attach_tables_pool_wait", endgame, tables, model, seed, reads)
+
+    def _attach_pool(self, entry, endgame, tables, model, seed, reads):
         if endgame.ATTACH != "dbaz_attach_tables":  # the C side cannot tell the two handle types apart
             raise _lib.DbazError(_lib.EINVAL, "a pool of tables needs a DeepTables, not a %s" % type(endgame).__name__)
-        self._ck(self._L.dbaz_attach_tables_pool_wait(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
+        self._ck(getattr(self._L, entry)(self.h, int(model), endgame.h, int(tables), C.c_uint64(int(seed)), int(reads)))
         self._endgames[int(model)] = endgame
 
     def attach_leaf_solver(self, endgame, leaf_free=None, model=0, seed=0):
