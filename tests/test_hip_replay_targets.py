@@ -2,7 +2,8 @@
 Coach(exact_targets=DeepTables(...))): the relabelled rows byte for byte against the numpy restatement (replay_targets_ref.py) in
 every mode, in any row order, the roots against endgame._game_roots, the device-built geometries through the tables they solve,
 the merged host route game_tail_targets, the rows through the dataset kernels, the refusals, and the generation loop.
-The 4x4 formula fixture of the deep tests, pools of 1 MiB tables."""
+The 4x4 formula fixture of the deep tests, pools of 1 MiB tables.  Boards with other row layouts (more ballot words, 2-byte aligned
+visits, A = 256, 1x1) are in test_hip_replay_targets_boards.py, against a numpy-only reference."""
 import numpy as np
 import pytest
 
