@@ -62,7 +62,8 @@ struct Slot {
     int32_t fast_search;     // the kind of the current search, written by every begin_search (in what was padding in front of game_idx):
                              // bit 0 (SEARCH_FAST) = a fast one of the playout cap (playout_cap.h): capped reads, no root noise, its row
                              // marked; bits 1, 2 (SEARCH_FORCED, SEARCH_PRUNE; forced_playouts.h) = a full search of the self-play driver
-                             // with forced playouts at its root, and its row records the pruned visits
+                             // with forced playouts at its root, and its row records the pruned visits; bit 3 (SEARCH_GUMBEL; gumbel.h)
+                             // = a search of the self-play driver with the Gumbel rule at its root
     int64_t game_idx;        // -1: no game
     double temperature;
     int32_t error;
@@ -113,7 +114,7 @@ struct RowMeta {
     int32_t tree_size, terminal_count;
     float q_value;
     int8_t player, z;
-    int16_t flags;           // replay_row.h: ROW_FLAG_FAST, ROW_FLAG_PRUNED; 0 on every row made without a playout cap or pruning
+    int16_t flags;           // replay_row.h: ROW_FLAG_FAST, ROW_FLAG_PRUNED, ROW_FLAG_GUMBEL; 0 on every row made without a playout cap, pruning or Gumbel
                              // ("pad" in the numpy dtypes)
 };
 
@@ -141,6 +142,9 @@ struct SearchCfg {
     double forced_k;         // forced playouts (forced_playouts.h, dbaz_selfplay_set_forced_playouts): k, 0 = off.  Only searches whose
                              // Slot::fast_search carries SEARCH_FORCED see it
     int forced_prune;        // ... 1 = the rows of those searches record the pruned visits
+    int gumbel_m;            // Gumbel root search (gumbel.h, dbaz_selfplay_set_gumbel): m, 0 = off.  Only searches whose Slot::fast_search
+                             // carries SEARCH_GUMBEL see it
+    double gumbel_c_visit, gumbel_c_scale; // ... the two constants of sigma
 };
 
 // the two families of built-in evaluators (DBAZ_EVAL_EXTERNAL is neither)
@@ -157,6 +161,10 @@ struct TreeBufs {
     double *root_prior;// [n_slots][AS]
     double *noise_in;  // [n_slots][AS] externally supplied Dirichlet vectors
     int32_t *noise_valid; // [n_slots] 1 = noise_in holds a vector for the next prep
+    // Gumbel root search (gumbel.h); allocated when the rule is first switched on, null before
+    double *gumbel_gl;    // [n_slots][AS] g + logit of the current search's candidates, -inf for every other child
+    int32_t *gumbel_n0;   // [n_slots][AS] the children's visits when the search was prepared
+    int32_t *gumbel_hdr;  // [n_slots][2] R = the reads the search was started with, m' = min(m, candidates)
     float *feat;       // [n_slots][3*HW] leaf features (float32 planes, predict_sync layout)
     float *evalP;      // [n_slots][AS]
     float *evalV;      // [n_slots]
@@ -196,8 +204,8 @@ struct TreeBufs {
     long long last_game;  // exclusive
     long long first_game;
     long long *games_finished; // [1]
-    long long *moves_played;   // [5]: moves played; full and fast searches the self-play driver started (playout_cap.h); rows pruned and
-                               // visits taken out of them (forced_playouts.h)
+    long long *moves_played;   // [7]: moves played; full and fast searches the self-play driver started (playout_cap.h); rows pruned and
+                               // visits taken out of them (forced_playouts.h); Gumbel searches started and Gumbel rows written (gumbel.h)
     // teacher-forcing scripts (tests)
     const int16_t *script_moves; // [n_script][E+1], -1 = sample
     const double *script_noise;  // [n_script][E+1][A] or null

@@ -373,7 +373,7 @@ extern "C" int dbaz_create(const dbaz_config *cfg, dbaz_engine **out)
     CREATE_CHECK(dmalloc(e, &B.out_count, 4));
     CREATE_CHECK(dmalloc(e, &B.next_game, 2));
     CREATE_CHECK(dmalloc(e, &B.games_finished, 2));
-    CREATE_CHECK(dmalloc(e, &B.moves_played, 6));
+    CREATE_CHECK(dmalloc(e, &B.moves_played, 8));
     CREATE_CHECK(dmalloc(e, &e->d_small, 16));
     CREATE_CHECK(dmalloc(e, &e->d_sum, 1));
     // log / sqrt tables evaluated with the HOST libm (what python's math.log/math.sqrt call),
@@ -1553,6 +1553,8 @@ extern "C" int dbaz_selfplay_set_forced_playouts(dbaz_engine *e, double k, int32
         if (r) return r;
         if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
     }
+    if (k > 0.0 && e->sc.gumbel_m > 0)
+        return set_error(e, DBAZ_EINVAL, "forced playouts and the Gumbel root search (dbaz_selfplay_set_gumbel) both own the root's pick: switch one off first");
     e->sc.forced_k = k > 0.0 ? k : 0.0;
     e->sc.forced_prune = k > 0.0 ? prune : 0;
     return DBAZ_OK;
@@ -1580,6 +1582,77 @@ extern "C" int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double
     if (n_actions < 1 || n_actions > DBAZ_MAX_A || !(k >= 0.0 && k <= FORCED_K_MAX) || root_N < 0 || !P || !W || !n_and_sign || !valid || !out)
         return DBAZ_EINVAL;
     forced_prune_row(n_actions, k, pbc, sq, root_N, P, W, n_and_sign, valid, out);
+    return DBAZ_OK;
+}
+
+// ---- Gumbel root search (gumbel.h; the rule is stated in full in include/dbaz.h)
+static_assert(GUMBEL_M_MAX == DBAZ_MAX_A, "gumbel.h sizes its host arrays by the most children a root has");
+extern "C" int dbaz_selfplay_set_gumbel(dbaz_engine *e, int32_t m, double c_visit, double c_scale)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (m < 0 || m > DBAZ_MAX_A) return set_error(e, DBAZ_EINVAL, "m = %d is outside [0, %d]", m, DBAZ_MAX_A);
+    if (m > 0 && !(c_visit >= 0.0 && c_visit <= GUMBEL_C_VISIT_MAX)) return set_error(e, DBAZ_EINVAL, "c_visit = %g is outside [0, %g]", c_visit, GUMBEL_C_VISIT_MAX);
+    if (m > 0 && !(c_scale > 0.0 && c_scale <= GUMBEL_C_SCALE_MAX)) return set_error(e, DBAZ_EINVAL, "c_scale = %g is outside (0, %g]", c_scale, GUMBEL_C_SCALE_MAX);
+    if (e->sc.match_play) return set_error(e, DBAZ_EINVAL, "the Gumbel root search belongs to self-play: this handle plays matches (match_play)");
+    if (e->cfg.selfplay_pending)
+        return set_error(e, DBAZ_EINVAL, "the Gumbel root search is not defined for self-play in waves (selfplay_pending): sequential halving counts finished visits");
+    if (m > 0 && e->sc.forced_k > 0.0)
+        return set_error(e, DBAZ_EINVAL, "the Gumbel root search and forced playouts (dbaz_selfplay_set_forced_playouts) both own the root's pick: switch one off first");
+    if (e->selfplay) {
+        // the driver's launches read the setting at every step: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    if (m > 0 && !e->B.gumbel_gl) {
+        // the per-slot state of a Gumbel search exists from the first time the rule is switched on
+        const size_t ns = e->n_slots;
+        const size_t bytes[3] = {ns * e->g.AS * sizeof(double), ns * e->g.AS * sizeof(int32_t), ns * 2 * sizeof(int32_t)};
+        void *p[3] = {nullptr, nullptr, nullptr};
+        if (alloc_all(e, 3, bytes, 7u, p) != hipSuccess) return set_error(e, DBAZ_EDEVICE, "no device memory for the Gumbel search state");
+        e->B.gumbel_gl = (double *)p[0];
+        e->B.gumbel_n0 = (int32_t *)p[1];
+        e->B.gumbel_hdr = (int32_t *)p[2];
+    }
+    e->sc.gumbel_m = m;
+    e->sc.gumbel_c_visit = m > 0 ? c_visit : 0.0;
+    e->sc.gumbel_c_scale = m > 0 ? c_scale : 0.0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_gumbel(dbaz_engine *e, int32_t *m, double *c_visit, double *c_scale, int64_t *searches, int64_t *rows)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (m) *m = e->sc.gumbel_m;
+    if (c_visit) *c_visit = e->sc.gumbel_c_visit;
+    if (c_scale) *c_scale = e->sc.gumbel_c_scale;
+    if (searches || rows) {
+        long long c[7] = {0, 0, 0, 0, 0, 0, 0}; // ..., Gumbel searches started, Gumbel rows written
+        HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
+        HIP_CHECK_RET(e, hipMemcpy(c, e->B.moves_played, sizeof(c), hipMemcpyDeviceToHost));
+        if (searches) *searches = c[5];
+        if (rows) *rows = c[6];
+    }
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_gumbel_considered(int32_t m_eff, int32_t R, int32_t *out)
+{
+    if (m_eff < 0 || m_eff > DBAZ_MAX_A || R < 0 || (R > 0 && !out)) return DBAZ_EINVAL;
+    for (int t = 0; t < R; t++) out[t] = gumbel_considered(m_eff, R, t);
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_gumbel_target(int32_t n_actions, double c_visit, double c_scale, const double *P, const float *W,
+                                  const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out)
+{
+    if (n_actions < 1 || n_actions > DBAZ_MAX_A || !(c_visit >= 0.0 && c_visit <= GUMBEL_C_VISIT_MAX) ||
+        !(c_scale > 0.0 && c_scale <= GUMBEL_C_SCALE_MAX) || !P || !W || !n_and_sign || !valid || !out)
+        return DBAZ_EINVAL;
+    gumbel_target_row(n_actions, c_visit, c_scale, P, W, n_and_sign, valid, out);
     return DBAZ_OK;
 }
 
@@ -1619,7 +1692,7 @@ extern "C" int dbaz_selfplay_start(dbaz_engine *e, int64_t n_games, int64_t firs
     long long next = first_game_idx + std::min<int64_t>(n_games, e->n_slots);
     HIP_CHECK_RET(e, hipMemcpy(B.next_game, &next, 8, hipMemcpyHostToDevice));
     HIP_CHECK_RET(e, hipMemset(B.games_finished, 0, 8));
-    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 40)); // with the full and fast searches, the rows pruned and the visits cut
+    HIP_CHECK_RET(e, hipMemset(B.moves_played, 0, 56)); // with the full and fast searches, the rows pruned and the visits cut, the Gumbel searches and rows
     HIP_CHECK_RET(e, hipMemset(B.out_count, 0, 4));
     HIP_CHECK_RET(e, hipMemset(B.noise_valid, 0, (size_t)e->n_slots * 4));
     // scripts

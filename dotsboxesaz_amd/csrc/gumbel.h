@@ -1,0 +1,116 @@
+// gumbel.h -- Gumbel root search (Danihelka et al., ICLR 2022, "Policy improvement by planning with Gumbel"): candidates by
+// Gumbel-top-m, the read budget spent by sequential halving, and softmax(logits + sigma(completed Q)) as the policy target, at the
+// root of the self-play driver's searches.  The rule is stated in full in include/dbaz.h next to dbaz_selfplay_set_gumbel; this
+// file is that statement as code, once, for the preparation (tree.hip: gumbel_prep), the descent (tree.hip: descend), the driver's
+// move and row (tree.hip: advance_one) and the host (dbaz_gumbel_considered, dbaz_gumbel_target).
+//
+// Every expression is float64 in the order written there.  Nothing here may be contracted into a fused multiply-add: tree.hip is
+// built with -ffp-contract=off, and the host side targets baseline x86-64, which has none.
+// Plain C++ for g++ and hipcc alike.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "forced_playouts.h" // FORCED_HD, forced_value (the descent's value_score), FORCED_PRIOR, the SEARCH_* bits below 8
+
+#define SEARCH_GUMBEL 8 // Slot::fast_search: a search of the self-play driver with the Gumbel rule at its root (beside SEARCH_FAST)
+
+#define GUMBEL_M_MAX 256         // DBAZ_MAX_A (engine.hip asserts it): the most children a root has
+#define GUMBEL_C_VISIT_MAX 1e6
+#define GUMBEL_C_SCALE_MAX 1e3
+#define GUMBEL_LOGIT_MIN (-1e30) // logit of a candidate whose prior is 0 (only when no valid child has a positive prior)
+#define GUMBEL_TAG 0x44444444u   // word 3 of the Philox counter of g(a); 0x11111111, 0x22222222, 0x33333333, 0x40000000 and the two
+                                 // families 0x80000000 + i, 0xC0000000 + i are the other streams'
+#define GUMBEL_PI_ONE 16777216.0 // 2^24: the row's visits are floor(pi' * 2^24 + 0.5)
+
+// u in [2^-53, 1 - 2^-53] -> g = -log(-log(u))
+FORCED_HD inline double gumbel_clamp_u(double u)
+{
+    const double lo = 1.0 / 9007199254740992.0;
+    if (u < lo) u = lo;
+    if (u > 1.0 - lo) u = 1.0 - lo;
+    return u;
+}
+FORCED_HD inline double gumbel_from_u(double u) { return -log(-log(gumbel_clamp_u(u))); }
+
+FORCED_HD inline double gumbel_logit(double P) { return P > 0.0 ? log(P) : GUMBEL_LOGIT_MIN; }
+
+// mctx's sequence of considered visits at position t, in closed form per phase (integers only)
+FORCED_HD inline int gumbel_considered(int m_eff, int R, int t)
+{
+    if (m_eff <= 1) return t;
+    int L = 0;
+    while ((1 << L) < m_eff) L++; // ceil(log2(m'))
+    int nc = m_eff, base = 0, pos = 0;
+    for (;;) {
+        int extra = R / (L * nc);
+        if (extra < 1) extra = 1;
+        const int len = extra * nc;
+        if (t < pos + len) return base + (t - pos) / nc;
+        pos += len;
+        base += extra;
+        nc = nc / 2 < 2 ? 2 : nc / 2;
+    }
+}
+
+// sigma of a completed Q
+FORCED_HD inline double gumbel_sigma(double c_visit, double c_scale, int n_max, double cq)
+{
+    return ((c_visit + (double)n_max) * c_scale) * cq;
+}
+
+FORCED_HD inline double gumbel_vmix(double num, double den) { return den != 0.0 ? num / den : 0.0; }
+
+// the row's count of a target probability
+FORCED_HD inline int32_t gumbel_count(double pi) { return (int32_t)floor(pi * GUMBEL_PI_ONE + 0.5); }
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// the sum order of the rule: lane i of 64 adds its entries i, i + 64, i + 128, i + 192 (absent ones +0.0), then six butterfly
+// stages s = s + s[lane ^ o], o = 32 .. 1.  Every lane ends with the same bits; lane 0's are returned.
+inline double gumbel_sum(const double *x, int n)
+{
+    double s[64], t[64];
+    for (int l = 0; l < 64; l++) {
+        double a = 0.0;
+        for (int i = l; i < 256; i += 64) a = a + (i < n ? x[i] : 0.0);
+        s[l] = a;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int l = 0; l < 64; l++) t[l] = s[l] + s[l ^ o];
+        for (int l = 0; l < 64; l++) s[l] = t[l];
+    }
+    return s[0];
+}
+
+// the whole target on one root (the host's dbaz_gumbel_target): out[i] = the row's visits of child i
+inline void gumbel_target_row(int n_actions, double c_visit, double c_scale, const double *P, const float *W, const uint32_t *ns,
+                              const uint8_t *valid, int32_t *out)
+{
+    double a[GUMBEL_M_MAX], b[GUMBEL_M_MAX], x[GUMBEL_M_MAX];
+    bool cand[GUMBEL_M_MAX];
+    bool any = false;
+    int n_max = 0;
+    for (int i = 0; i < n_actions; i++) {
+        const int n = (int)(ns[i] & FORCED_VISITS_MASK);
+        a[i] = b[i] = 0.0;
+        if (n > 0) {
+            a[i] = P[i] * forced_value(W[i], n, (ns[i] & FORCED_SAME_BIT) != 0);
+            b[i] = P[i];
+        }
+        if (valid[i] && n > n_max) n_max = n;
+        if (valid[i] && P[i] > 0.0) any = true;
+    }
+    const double vmix = gumbel_vmix(gumbel_sum(a, n_actions), gumbel_sum(b, n_actions));
+    double M = -INFINITY;
+    for (int i = 0; i < n_actions; i++) {
+        const int n = (int)(ns[i] & FORCED_VISITS_MASK);
+        cand[i] = valid[i] && (P[i] > 0.0 || !any);
+        if (!cand[i]) continue;
+        const double cq = n > 0 ? forced_value(W[i], n, (ns[i] & FORCED_SAME_BIT) != 0) : vmix;
+        x[i] = gumbel_logit(P[i]) + gumbel_sigma(c_visit, c_scale, n_max, cq);
+        if (x[i] > M) M = x[i];
+    }
+    for (int i = 0; i < n_actions; i++) a[i] = cand[i] ? exp(x[i] - M) : 0.0;
+    const double se = gumbel_sum(a, n_actions);
+    for (int i = 0; i < n_actions; i++) out[i] = cand[i] ? gumbel_count(a[i] / se) : 0;
+}

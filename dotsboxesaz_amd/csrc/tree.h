@@ -3,6 +3,7 @@
 #include "common.h"
 #include "endgame.h"
 #include "forced_playouts.h"
+#include "gumbel.h"
 #include "playout_cap.h"
 
 // Evaluators that answer through the evaluation list: k_select / k_select_multi append their leaves to eval_list / eval_list2 /

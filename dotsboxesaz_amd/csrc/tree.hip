@@ -333,7 +333,7 @@ __device__ __forceinline__ double u01(uint32_t a, uint32_t b)
     return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
 }
 // stream: (game, ply, element, purpose)
-__device__ double rng_gamma(uint64_t seed, uint64_t game, uint32_t ply, uint32_t elem, double a)
+__device__ __forceinline__ double rng_gamma(uint64_t seed, uint64_t game, uint32_t ply, uint32_t elem, double a)
 {
     uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
     double boost = 1.0;
@@ -363,9 +363,60 @@ __device__ double rng_gamma(uint64_t seed, uint64_t game, uint32_t ply, uint32_t
 }
 
 // ------------------------------------------------------------------------------------
+// Gumbel root search (gumbel.h; the rule is in include/dbaz.h): what a search keeps from its preparation.  Runs at the end of
+// root_prep, on the float64 root prior it has just written: the candidates, gl = g + logit (-inf for every other child), the
+// children's visits of this moment and m'.  ext: noise_in holds a scripted g for this (game, ply).
+// ------------------------------------------------------------------------------------
+__device__ void gumbel_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool, const NodeMeta &rm,
+                            bool ext, int lane)
+{
+    const int A = g.A;
+    const double *rp = B.root_prior + (size_t)slot * g.AS;
+    const double *nin = B.noise_in + (size_t)slot * g.AS;
+    const uint32_t *NS0 = node_ptr(pool, g, S->root) + META_DW + 2 * g.AS;
+    double *gl = B.gumbel_gl + (size_t)slot * g.AS;
+    int32_t *n0 = B.gumbel_n0 + (size_t)slot * g.AS;
+    int npos = 0, nval = 0;
+    for (int i = lane; i < A; i += WAVE) {
+        const bool v = gs_valid(g, rm.st, i);
+        nval += v ? 1 : 0;
+        npos += (v && rp[i] > 0.0) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        nval += __shfl_xor(nval, o);
+        npos += __shfl_xor(npos, o);
+    }
+    const bool any = npos > 0; // no valid child with a positive prior: every valid child is a candidate
+    const uint2 key = make_uint2((uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
+    const uint64_t game = (uint64_t)S->game_idx;
+    const uint32_t ply = (uint32_t)S->move_idx;
+    for (int i = lane; i < A; i += WAVE) {
+        const double P = rp[i];
+        const bool cand = gs_valid(g, rm.st, i) && (P > 0.0 || !any);
+        double x = -INFINITY;
+        if (cand) {
+            double gv;
+            if (ext) {
+                gv = nin[i];
+            } else {
+                const uint4 r = philox(make_uint4((uint32_t)game, (uint32_t)(game >> 32), ply + 65536u * (uint32_t)i, GUMBEL_TAG), key);
+                gv = gumbel_from_u(u01(r.x, r.y));
+            }
+            x = gv + gumbel_logit(P);
+        }
+        gl[i] = x;
+        n0[i] = (int32_t)(NS0[i] & NS_MASK);
+    }
+    if (lane == 0) B.gumbel_hdr[2 * slot + 1] = min(cfg.gumbel_m, any ? npos : nval);
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------
 // root prior renormalisation + Dirichlet mix, mcts.py:211-226 (wave-cooperative)
 // ------------------------------------------------------------------------------------
-__device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
+// GUMBEL: the instantiation a handle with the Gumbel rule on launches (gumbel.h); false compiles every trace of the rule out
+template <bool GUMBEL>
+__device__ __forceinline__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                           uint32_t *pool, float *ldsf, double *ldsd, int lane)
 {
     const int root = S->root;
@@ -399,7 +450,11 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
     __syncthreads();
     // a fast search of the playout cap is UCT_search(..., dirichlet=(0.0, 0.0)): no noise, coeff = 0; a vector waiting in noise_in
     // (scripted for this ply, or left by the host) is dropped, not kept for a later search
-    const bool fast = (S->fast_search & SEARCH_FAST) != 0;
+    // a Gumbel search (gumbel.h) is prepared the same way; a vector waiting for it is its g, read before it is dropped here
+    const bool gumbel = GUMBEL && (S->fast_search & SEARCH_GUMBEL) != 0;
+    const bool g_ext = gumbel && B.noise_valid[slot] != 0;
+    if (GUMBEL) __syncthreads();
+    const bool fast = (S->fast_search & SEARCH_FAST) != 0 || gumbel;
     const double coeff = fast ? 0.0 : cfg.coeff;
     const double onemc = 1.0 - coeff;
     if (fast && lane == 0) B.noise_valid[slot] = 0;
@@ -435,6 +490,7 @@ __device__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B,
     }
     S->root_prepped = 1;
     __syncthreads();
+    if (GUMBEL && gumbel) gumbel_prep(g, cfg, B, slot, S, pool, rm, g_ext, lane);
 }
 
 // phase and a step stamp leave in ONE 8-byte store.  The driver pass (move choice, re-root, next search) of step t
@@ -475,7 +531,8 @@ __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, c
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
 // kind: SEARCH_FAST = a fast search of the playout cap, SEARCH_FORCED / SEARCH_PRUNE = forced playouts at the root and a pruned
 // row (start_move_search decides; explicit searches are of kind 0)
-__device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
+template <bool GUMBEL>
+__device__ __forceinline__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                              uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane, int kind = 0)
 {
     NodeMeta rm = load_meta(pool, g, S->root);
@@ -525,11 +582,12 @@ __device__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs 
             sa.eg.req[slot] = rq;
         }
     }
+    if (GUMBEL && (kind & SEARCH_GUMBEL) && lane == 0) B.gumbel_hdr[2 * slot] = num_reads; // R of sequential halving (gumbel.h)
     S->sims_left = num_reads;
     S->first_wave = 1;
     S->wave_sims = 0;
     if (rm.flags & NF_EXPANDED) {
-        root_prep(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        root_prep<GUMBEL>(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
         set_phase_stamped(S, num_reads > 0 ? PH_SIMS : PH_READY, cfg.step);
     } else {
         set_phase_stamped(S, PH_EXPAND_ROOT, cfg.step);
@@ -545,7 +603,7 @@ __global__ void __launch_bounds__(WAVE) k_search_begin(Geo g, SearchCfg cfg, Tre
     if (S->phase == PH_ERROR || S->game_idx < 0)
         return;
     uint32_t *pool = B.nodes + (size_t)slot * g.cap * g.node_dw;
-    begin_search(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, sa, ldsf, ldsd, lane);
+    begin_search<false>(g, cfg, B, slot, S, pool, num_reads ? num_reads[slot] : -1, sa, ldsf, ldsd, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -629,13 +687,88 @@ __device__ __forceinline__ void write_features(const Geo &g, const GState &st, f
 // node left, and the one-round-trip prefetch of the next level.  vv = 1 (K-pending search with virtual_visits) counts
 // the visit of every edge taken, the root's included, NOW instead of at backup; vv = 0 folds away at the call site.
 // The leaf's own path entry, path[depth], is the caller's.
+// The root level of a Gumbel search (gumbel.h; the rule is in include/dbaz.h): the child this simulation takes.  R: the root's
+// rows as the descent holds them, rp: its float64 priors.  Four butterfly reductions (t, n_max and the two sums of v_mix) and the
+// argmax; the sums run in the rule's order -- this lane's children in index order, then o = 32 .. 1.  The child found gets
+// FORCED_PRIOR in rp, and the root level's pb_c terms become 1, under which that child's score is beyond every other one.
+template <int NPL>
+__device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const NodeMeta &m,
+                                                 const NodeRows<NPL> &R, double (&rp)[NPL], double &pbc_cur, double &sq_cur, int lane)
+{
+    const int A = g.A;
+    const double *glrow = B.gumbel_gl + (size_t)slot * g.AS;
+    const int32_t *n0row = B.gumbel_n0 + (size_t)slot * g.AS;
+    const int reads = B.gumbel_hdr[2 * slot], m_eff = B.gumbel_hdr[2 * slot + 1];
+    const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
+    double gl[NPL];
+    int nsr[NPL]; // n_s, the visits of this search
+    int t = 0, n_max = 0;
+    double num = 0.0, den = 0.0;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const int i = lane + WAVE * j;
+        const bool in = i < A;
+        const bool valid = in && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
+        const int n = (int)(R.NS[j] & NS_MASK);
+        gl[j] = in ? glrow[i] : -INFINITY;
+        nsr[j] = in ? n - n0row[i] : 0;
+        t += nsr[j];
+        n_max = (valid && n > n_max) ? n : n_max;
+        num = num + (n > 0 ? rp[j] * forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : 0.0);
+        den = den + (n > 0 ? rp[j] : 0.0);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        t += __shfl_xor(t, o);
+        n_max = max(n_max, __shfl_xor(n_max, o));
+        num = num + __shfl_xor(num, o);
+        den = den + __shfl_xor(den, o);
+    }
+    t = __builtin_amdgcn_readfirstlane(t);
+    n_max = __builtin_amdgcn_readfirstlane(n_max);
+    const double vmix = gumbel_vmix(num, den);
+    int cv = gumbel_considered(m_eff, reads, t);
+    // gl + sigma of the candidates at cv visits of this search, -inf for every other child
+    double sc[NPL], mx;
+    for (int pass = 0;; pass++) {
+        mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NPL; j++) {
+            const int n = (int)(R.NS[j] & NS_MASK);
+            const double cq = n > 0 ? forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : vmix;
+            sc[j] = (gl[j] > -INFINITY && nsr[j] == cv) ? gl[j] + gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, cq) : -INFINITY;
+            mx = fmax(mx, sc[j]);
+        }
+        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+        if (mx > -INFINITY || pass) break;
+        // no candidate at cv visits (never while t < R): the candidates with the fewest visits compete
+        int mn = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < NPL; j++) mn = (gl[j] > -INFINITY && nsr[j] < mn) ? nsr[j] : mn;
+        for (int o = 32; o > 0; o >>= 1) mn = min(mn, __shfl_xor(mn, o));
+        cv = __builtin_amdgcn_readfirstlane(mn);
+    }
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const unsigned long long mk = __ballot(sc[j] == mx && sc[j] > -INFINITY);
+        if (!found && mk != 0ull) {
+            if (lane == __ffsll((long long)mk) - 1) rp[j] = FORCED_PRIOR;
+            found = true;
+        }
+    }
+    pbc_cur = 1.0;
+    sq_cur = 1.0;
+}
+
 struct Leaf {
     int cur, depth, in_move, err;
     int root_to_play;
     NodeMeta m;
 };
 
-template <int NPL>
+// GUMBEL = false (a handle with the Gumbel rule off, and the K-pending search, which the rule never reaches) compiles the Gumbel
+// pre-pass out: the descent is then the parent's, instruction for instruction.
+template <int NPL, bool GUMBEL>
 __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool,
                                         PoolState &q, PathEnt *path, const unsigned vv, int lane)
 {
@@ -656,8 +789,14 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     for (int j = 0; j < NPL; j++) rp[j] = (lane + WAVE * j < A) ? rprior[lane + WAVE * j] : 0.0;
     int in_move = m.move;
     const int root_to_play = m.st.to_play;
+    // Gumbel root search (gumbel.h): on for the searches of the self-play driver, and at the root level only, in the instantiations a
+    // handle with the rule on launches.  The pre-pass picks the root's child by sequential halving and hands it to the loop the way
+    // the forced pre-pass below does, through rp; it also makes the root level's pb_c a plain 1 / (n + 1) > 0, since a re-used root
+    // starts its search at N = 0, where sqrt(N) would wipe FORCED_PRIOR out.  (Such a handle has no forced playouts.)
+    if (GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) && is_inner(m.flags))
+        gumbel_root_pick<NPL>(g, cfg, B, slot, m, R, rp, pbc_cur, sq_cur, lane);
     // forced playouts (forced_playouts.h): on for a full search of the self-play driver, and at the root level only
-    const bool forced = (__builtin_amdgcn_readfirstlane(kind) & SEARCH_FORCED) != 0;
+    const bool forced = !GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_FORCED) != 0;
     if (forced && is_inner(m.flags)) {
         // Root-only pre-pass: a forced child scores FORCED_SCORE, above every other score, and the argmax takes the first maximum,
         // so the root level's choice is the lowest forced index.  That child is found here, from rows the root level reads anyway,
@@ -862,7 +1001,7 @@ __device__ __forceinline__ bool endgame_slot_waits(const SearchCfg &cfg, const E
 }
 
 // returns the route of this game's leaf (ROUTE_NONE: of no leaf, or of one that goes on no list), or SEL_DEFERRED
-template <int NPL>
+template <int NPL, bool GUMBEL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
     Slot *S = B.slots + slot;
@@ -887,7 +1026,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
     GcBatch<GC_PER_STEP, NPL> gcb; // the collector's share of this simulation: rows requested now, consumed after the descent
     gcb.k = 0;
     if (cfg.gc_lazy <= 0 || q.n_free + (g.cap - q.n_nodes) < cfg.gc_lazy) gc_issue(gcb, g, B, slot, pool, q, lane);
-    const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, 0u, lane);
+    const Leaf lf = descend<NPL, GUMBEL>(g, cfg, B, slot, S, pool, q, path, 0u, lane);
     if (lf.err) {
         if (lane == 0) { S->error = lf.err; S->phase = PH_ERROR; }
         return ROUTE_NONE;
@@ -960,13 +1099,13 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 // ev_class[slot] for k_order_evals -- so nothing is left to share between the games of a workgroup: no LDS counters, no barrier,
 // and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare leaf of
 // ROUTE_TABLE or the leaf solver goes onto its list with the wave's own atomic.
-template <int NPL, bool ONE>
+template <int NPL, bool ONE, bool GUMBEL>
 __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
     if (ONE) {
         const int slot = blockIdx.x, lane = threadIdx.x;
         if (slot >= n_slots) return;
-        const int route = select_one<NPL>(g, cfg, B, G, slot, lane);
+        const int route = select_one<NPL, GUMBEL>(g, cfg, B, G, slot, lane);
         if (lane == 0) {
             B.ev_class[slot] = route == SEL_DEFERRED ? EV_CLASS_DEFERRED : (route == ROUTE_MODEL0 ? EV_CLASS_NEW : -1);
             // (full rounds: one model, so no model bit on a solver entry)
@@ -979,7 +1118,7 @@ __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo
     if (threadIdx.x < N_ROUTES) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     int route = ROUTE_NONE; // (no put-off leaves here: they are of the full rounds)
-    if (slot < n_slots) route = select_one<NPL>(g, cfg, B, G, slot, lane);
+    if (slot < n_slots) route = select_one<NPL, GUMBEL>(g, cfg, B, G, slot, lane);
     const bool put = route >= 0 && lane == 0;
     int my = 0;
     if (put) my = atomicAdd(&s_cnt[route], 1);
@@ -1141,7 +1280,7 @@ __device__ __forceinline__ void select_multi_one(const Geo &g, const SearchCfg &
     for (int k = 0; k < n_sims && !err; k++) {
         PathEnt *path = B.path_m + ((size_t)slot * K + k) * g.dmax;
         pool_collect<GC_PER_STEP>(g, B, slot, pool, q, lane);
-        const Leaf lf = descend<NPL>(g, cfg, B, slot, S, pool, q, path, vv, lane);
+        const Leaf lf = descend<NPL, false>(g, cfg, B, slot, S, pool, q, path, vv, lane);
         err = lf.err;
         if (err) break;
         // leaf bookkeeping of simulation k
@@ -1279,11 +1418,12 @@ __device__ __forceinline__ void count_sim(Slot *S, int term, bool served, bool e
 }
 
 // a slot's step ends: the root expansion (uncounted, mcts.py:207-208) hands over to the simulations, `sims` of which are done otherwise
+template <bool GUMBEL>
 __device__ __forceinline__ void end_step(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool, int phase,
                                          int sims, float *ldsf, double *ldsd, int lane)
 {
     if (phase == PH_EXPAND_ROOT) {
-        root_prep(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
+        root_prep<GUMBEL>(g, cfg, B, slot, S, pool, ldsf, ldsd, lane);
         if (lane == 0) set_phase_stamped(S, S->sims_left > 0 ? PH_SIMS : PH_READY, cfg.step);
     } else if (lane == 0) {
         int left = S->sims_left - sims;
@@ -1337,7 +1477,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    end_step(g, cfg, B, slot, S, pool, phase, n, ldsf, ldsd, lane);
+    end_step<false>(g, cfg, B, slot, S, pool, phase, n, ldsf, ldsd, lane);
     if (lane == 0) S->wave_sims = 0;
 }
 
@@ -1347,6 +1487,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
 // Four waves per SIMD (second launch bound: at most 128 registers), so that 8 192 slots are two rounds of one-wave workgroups
 // instead of 2.67.  What does not fit is the float64 pow / log / cos of the Dirichlet sampler inlined through end_step ->
 // root_prep -> rng_gamma: the allocator spills there, once per move, and nowhere on the path of an ordinary simulation.
+template <bool GUMBEL>
 __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1412,7 +1553,7 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
     backup_path(g, pool, S, path, plen, lm.st.to_play, v, true, lane);
     __syncthreads();
     if (lane == 0) count_sim(S, (lm.flags & NF_TERMINAL) ? 1 : 0, hit >= 0, eg, plen, lm.deepness);
-    end_step(g, cfg, B, slot, S, pool, phase, 1, ldsf, ldsd, lane);
+    end_step<GUMBEL>(g, cfg, B, slot, S, pool, phase, 1, ldsf, ldsd, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1656,7 +1797,8 @@ __device__ bool try_emit(const Geo &g, const TreeBufs &B, int slot, Slot *S, uin
     return true;
 }
 
-__device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
+template <bool GUMBEL>
+__device__ __forceinline__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                                   uint32_t *pool, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
 {
     // play_game loop head (self_play.py:57-66): temperature schedule, sims budget, search
@@ -1668,20 +1810,27 @@ __device__ void start_move_search(const Geo &g, const SearchCfg &cfg, const Tree
     // playout cap: full or fast is a function of (seed, game, ply) alone
     const bool fast = !playout_is_full(sa.pc, cfg.seed, S->game_idx, (uint32_t)i);
     if (lane == 0) atomicAdd((unsigned long long *)B.moves_played + (fast ? 2 : 1), 1ull);
-    if (cfg.alpha > 0 && !fast && B.script_noise && gi >= 0 && gi < B.n_script && B.script_has_noise[gi] && i <= g.E) {
+    // (with the Gumbel rule on, a scripted vector is the search's g, whatever the noise setting, and for fast searches too)
+    const bool gumbel = GUMBEL && cfg.gumbel_m > 0;
+    if ((gumbel || (cfg.alpha > 0 && !fast)) && B.script_noise && gi >= 0 && gi < B.n_script && B.script_has_noise[gi] && i <= g.E) {
         const double *src = B.script_noise + ((size_t)gi * (g.E + 1) + i) * g.A;
         double *dst = B.noise_in + (size_t)slot * g.AS;
         for (int k = lane; k < g.A; k += WAVE) dst[k] = src[k];
         if (lane == 0) B.noise_valid[slot] = 1;
         __syncthreads();
         __threadfence_block();
+    } else if (GUMBEL && gumbel && lane == 0) {
+        B.noise_valid[slot] = 0; // only a scripted vector is a search's g: one that the host left in noise_in is dropped
     }
+    if (GUMBEL && gumbel && lane == 0) atomicAdd((unsigned long long *)B.moves_played + 5, 1ull); // Gumbel searches started
     // forced playouts belong to the driver's full searches (with the cap off every search is one)
-    const int kind = fast ? SEARCH_FAST : (cfg.forced_k > 0.0 ? SEARCH_FORCED | (cfg.forced_prune ? SEARCH_PRUNE : 0) : 0);
-    begin_search(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, kind);
+    // (the Gumbel rule belongs to every search of the driver, full or fast; a handle has it or forced playouts, never both)
+    const int kind = (fast ? SEARCH_FAST : (cfg.forced_k > 0.0 ? SEARCH_FORCED | (cfg.forced_prune ? SEARCH_PRUNE : 0) : 0)) | (gumbel ? SEARCH_GUMBEL : 0);
+    begin_search<GUMBEL>(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, kind);
 }
 
 
+template <bool GUMBEL>
 __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1704,7 +1853,74 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
         return;
     }
     fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-    start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
+    start_move_search<GUMBEL>(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
+}
+
+// The end of a Gumbel search (gumbel.h; the rule is in include/dbaz.h), everything read after the search: the move -- the first
+// maximum of gl + sigma over the candidates with the most visits of this search -- is returned, and rv (if not null) gets the
+// row's visits, softmax(logit + sigma) over the candidates in units of 2^-24.  One wave; the sums run in the rule's order.
+__device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, uint32_t *pool, int root, const NodeMeta &rm,
+                             int32_t *rv, double *ldsd, int lane)
+{
+    const int A = g.A;
+    const uint32_t *NS0 = node_ptr(pool, g, root) + META_DW + 2 * g.AS;
+    const float *W0 = reinterpret_cast<const float *>(node_ptr(pool, g, root) + META_DW + g.AS);
+    const double *rprior = B.root_prior + (size_t)slot * g.AS;
+    const double *gl = B.gumbel_gl + (size_t)slot * g.AS;
+    const int32_t *n0 = B.gumbel_n0 + (size_t)slot * g.AS;
+    int n_max = 0, ns_max = -1;
+    double num = 0.0, den = 0.0;
+    for (int i = lane; i < A; i += WAVE) {
+        const uint32_t ns = NS0[i];
+        const int n = (int)(ns & NS_MASK);
+        if (gs_valid(g, rm.st, i) && n > n_max) n_max = n;
+        if (gl[i] > -INFINITY && n - n0[i] > ns_max) ns_max = n - n0[i];
+        num = num + (n > 0 ? rprior[i] * forced_value(W0[i], n, (ns & NS_SAME) != 0) : 0.0);
+        den = den + (n > 0 ? rprior[i] : 0.0);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        n_max = max(n_max, __shfl_xor(n_max, o));
+        ns_max = max(ns_max, __shfl_xor(ns_max, o));
+        num = num + __shfl_xor(num, o);
+        den = den + __shfl_xor(den, o);
+    }
+    const double vmix = gumbel_vmix(num, den);
+    // the move, and x = logit + sigma with its maximum
+    double bs = -INFINITY, M = -INFINITY;
+    int bi = 0x7fffffff;
+    __syncthreads();
+    for (int i = lane; i < A; i += WAVE) {
+        const bool cand = gl[i] > -INFINITY;
+        double x = -INFINITY;
+        if (cand) {
+            const uint32_t ns = NS0[i];
+            const int n = (int)(ns & NS_MASK);
+            const double sg = gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, n > 0 ? forced_value(W0[i], n, (ns & NS_SAME) != 0) : vmix);
+            const double s = gl[i] + sg;
+            if (n - n0[i] == ns_max && s > bs) { bs = s; bi = i; }
+            x = gumbel_logit(rprior[i]) + sg;
+            if (x > M) M = x;
+        }
+        ldsd[i] = x;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double os = __shfl_xor(bs, o);
+        const int oi = __shfl_xor(bi, o);
+        if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
+        M = fmax(M, __shfl_xor(M, o));
+    }
+    if (rv) {
+        double se = 0.0;
+        for (int i = lane; i < A; i += WAVE) {
+            const double e = ldsd[i] > -INFINITY ? exp(ldsd[i] - M) : 0.0;
+            ldsd[i] = e;
+            se = se + e;
+        }
+        for (int o = 32; o > 0; o >>= 1) se = se + __shfl_xor(se, o);
+        for (int i = lane; i < A; i += WAVE) rv[i] = gl[i] > -INFINITY ? gumbel_count(ldsd[i] / se) : 0;
+    }
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(bi);
 }
 
 // One pass of the driver for every slot whose reads are done (PH_READY), whose finished game still waits for output space
@@ -1712,7 +1928,8 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
 // here leaves the slot in PH_NEWGAME until the next pass.
 // (the slots come from k_driver_scan's list: a step in which no slot needs the driver costs two tiny launches instead
 // of one workgroup per game squeezing in between the network's workgroups)
-__device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const StartArgs &sa, float *ldsf,
+template <bool GUMBEL>
+__device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const StartArgs &sa, float *ldsf,
                             double *ldsd, int lane)
 {
     Slot *S = B.slots + slot;
@@ -1726,7 +1943,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
         const long long gidx = S->game_idx;
         S->quick_until = 0; // only a slot's first game has quick plies
         fresh_game(g, cfg, B, slot, S, pool, gidx, lane);
-        start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
+        start_move_search<GUMBEL>(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
         return;
     }
     if (phase == PH_EMIT) {
@@ -1755,6 +1972,15 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
     long long gi = S->game_idx - B.first_game;
     if (B.script_moves && gi >= 0 && gi < B.n_script && ply <= g.E)
         mv = B.script_moves[(size_t)gi * (g.E + 1) + ply];
+    const int r = S->n_rows;
+    const int kind = S->fast_search;
+    const bool gumbel = GUMBEL && (kind & SEARCH_GUMBEL) != 0;
+    if (GUMBEL && gumbel) {
+        // Gumbel root search (gumbel.h): the move by the rule -- no temperature, the move-draw stream is not consumed -- unless a
+        // scripted one wins, and the row's visits, which are the target pi'
+        const int gmv = gumbel_finish(g, cfg, B, slot, pool, root, rm, r < rcap ? B.row_vis + ((size_t)slot * rcap + r) * A : nullptr, ldsd, lane);
+        if (mv < 0) mv = gmv;
+    }
     if (mv < 0) {
         // probs = (vc/vc.max())**(1/T); probs /= probs.sum(); np.random.choice(A, p=probs)
         const double invT = 1.0 / S->temperature;
@@ -1787,8 +2013,6 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
         __syncthreads();
     }
     // ---- row of get_datasets for this root (self_play.py:107-117) ----
-    const int r = S->n_rows;
-    const int kind = S->fast_search;
     const bool prune = (kind & SEARCH_PRUNE) != 0;
     if (r < rcap) {
         int16_t *rx = B.row_x + ((size_t)slot * rcap + r) * F;
@@ -1832,6 +2056,8 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
                 atomicAdd((unsigned long long *)B.moves_played + 3, 1ull);
                 atomicAdd((unsigned long long *)B.moves_played + 4, (unsigned long long)cut);
             }
+        } else if (gumbel) {
+            if (lane == 0) atomicAdd((unsigned long long *)B.moves_played + 6, 1ull); // (gumbel_finish wrote the visits)
         } else {
             for (int i = lane; i < A; i += WAVE) rv[i] = (int32_t)(NS0[i] & NS_MASK);
         }
@@ -1847,7 +2073,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             mm.q_value = S->root_W / (float)(1 + S->root_N); // TreeRoot.get_tree_stats, mcts.py:33-36
             mm.player = (int8_t)rm.st.to_play;
             mm.z = 0;
-            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0);
+            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0) | (gumbel ? ROW_FLAG_GUMBEL : 0);
             B.row_meta[(size_t)slot * rcap + r] = mm;
         }
         S->n_rows = r + 1;
@@ -1869,7 +2095,7 @@ __device__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &
             S->phase = emitted ? PH_NEWGAME : PH_EMIT;
         return;
     }
-    start_move_search(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
+    start_move_search<GUMBEL>(g, cfg, B, slot, S, pool, sa, ldsf, ldsd, lane);
 }
 
 // which slots need the driver: finished reads, a blocked emit or a finished game (the pass runs after the previous step's
@@ -1940,6 +2166,7 @@ __global__ void __launch_bounds__(SCAN_T) k_driver_scan(SearchCfg cfg, TreeBufs 
     }
 }
 
+template <bool GUMBEL>
 __global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1947,7 +2174,7 @@ __global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, Tre
     const int lane = threadIdx.x;
     const int n = *B.drv_count;
     for (int li = blockIdx.x; li < n; li += gridDim.x) {
-        advance_one(g, cfg, B, B.drv_list[li], sa, ldsf, ldsd, lane);
+        advance_one<GUMBEL>(g, cfg, B, B.drv_list[li], sa, ldsf, ldsd, lane);
         __syncthreads();
     }
 }
@@ -2133,25 +2360,32 @@ void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, c
 {
     hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev, sa);
 }
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
+template <bool GUMBEL>
+static void launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     const int npl = (g.A + WAVE - 1) / WAVE;
     if (c.eval_round > 0) { // k_order_evals writes the network's list: one game per workgroup
         switch (npl) {
-        case 1: hipLaunchKernelGGL((k_select<1, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
-        case 2: hipLaunchKernelGGL((k_select<2, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
-        case 3: hipLaunchKernelGGL((k_select<3, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
-        default: hipLaunchKernelGGL((k_select<4, true>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        case 1: hipLaunchKernelGGL((k_select<1, true, GUMBEL>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        case 2: hipLaunchKernelGGL((k_select<2, true, GUMBEL>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        case 3: hipLaunchKernelGGL((k_select<3, true, GUMBEL>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
+        default: hipLaunchKernelGGL((k_select<4, true, GUMBEL>), dim3(n_slots), dim3(WAVE), 0, s, g, c, B, n_slots, G); break;
         }
         return;
     }
     const dim3 grid((n_slots + SELECT_WAVES - 1) / SELECT_WAVES), block(WAVE * SELECT_WAVES);
     switch (npl) {
-    case 1: hipLaunchKernelGGL((k_select<1, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
-    case 2: hipLaunchKernelGGL((k_select<2, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
-    case 3: hipLaunchKernelGGL((k_select<3, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
-    default: hipLaunchKernelGGL((k_select<4, false>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    case 1: hipLaunchKernelGGL((k_select<1, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    case 2: hipLaunchKernelGGL((k_select<2, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    case 3: hipLaunchKernelGGL((k_select<3, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
+    default: hipLaunchKernelGGL((k_select<4, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
     }
+}
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
+{
+    // a handle with the Gumbel rule on launches the instantiations that hold its root pre-pass; every other handle the ones without
+    if (c.gumbel_m > 0) launch_select<true>(s, g, c, B, n_slots, G);
+    else launch_select<false>(s, g, c, B, n_slots, G);
 }
 void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
@@ -2168,7 +2402,9 @@ void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCf
 }
 void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
-    hipLaunchKernelGGL(k_expand_backup, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    // (a handle with the Gumbel rule on launches the instantiations that hold it; every other handle the ones without a trace of it)
+    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_expand_backup<true>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    else hipLaunchKernelGGL(k_expand_backup<false>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                const int16_t *moves_dev, const int32_t *offsets_dev)
@@ -2182,7 +2418,8 @@ void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c,
 }
 void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
-    hipLaunchKernelGGL(k_selfplay_start, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
+    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_selfplay_start<true>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
+    else hipLaunchKernelGGL(k_selfplay_start<false>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
 {
@@ -2195,7 +2432,8 @@ void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, c
     hipLaunchKernelGGL(k_driver_flags, dim3((n_slots + WAVE - 1) / WAVE), dim3(WAVE), 0, s, B, n_slots);
     if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_driver_scan<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
     else hipLaunchKernelGGL(k_driver_scan<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
-    hipLaunchKernelGGL(k_advance_auto, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_advance_auto<true>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    else hipLaunchKernelGGL(k_advance_auto<false>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,

@@ -58,6 +58,8 @@ class Engine:
     playout_cap=(full_prob, fast_reads): playout cap randomization (selfplay_set_playout_cap); None: off.
     forced_playouts=(k, prune): forced playouts and policy target pruning at the root of the self-play driver's full searches
     (selfplay_set_forced_playouts); None: off.
+    gumbel=(m, c_visit, c_scale): Gumbel root search in every search of the self-play driver (selfplay_set_gumbel; the usual setting
+    is (16, 50.0, 1.0)); None: off.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -69,7 +71,7 @@ class Engine:
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
                  solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None,
-                 forced_playouts=None, endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
+                 forced_playouts=None, gumbel=None, endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -153,6 +155,12 @@ class Engine:
         if forced_playouts is not None:
             try:
                 self.selfplay_set_forced_playouts(*forced_playouts)
+            except Exception:
+                self.close()
+                raise
+        if gumbel is not None:
+            try:
+                self.selfplay_set_gumbel(*gumbel)
             except Exception:
                 self.close()
                 raise
@@ -516,6 +524,24 @@ class Engine:
         self._ck(self._L.dbaz_get_forced_playouts(self.h, C.byref(k), C.byref(p), C.byref(a), C.byref(b)))
         return dict(k=float(k.value), prune=bool(p.value), rows_pruned=int(a.value), visits_pruned=int(b.value))
 
+    def selfplay_set_gumbel(self, m=16, c_visit=50.0, c_scale=1.0):
+        """dbaz_selfplay_set_gumbel: the Gumbel root search (Danihelka et al., ICLR 2022) for every later selfplay_start.  Every
+        search of the self-play driver, full or fast, samples its candidates by Gumbel-top-m, spends its reads by sequential
+        halving and records softmax(logits + sigma(completed Q)) as the row's target: visits = round(pi' * 2^24), bit 2 of "pad"
+        (fetch_samples()["gumbel"] is True).  The move is the rule's own (no temperature).  A vector scripted through
+        selfplay_script is the search's g.  m = 0: off (the default).  The rule is stated in full in include/dbaz.h;
+        gumbel.considered_visits and gumbel.target are its host mirrors.  DbazError: EINVAL for m outside [0, 256], c_visit outside
+        [0, 1e6], c_scale outside (0, 1e3], a match_play handle, selfplay_pending or forced playouts on; ESTATE while games are
+        being played; a failed call changes nothing."""
+        self._ck(self._L.dbaz_selfplay_set_gumbel(self.h, int(m), C.c_double(float(c_visit)), C.c_double(float(c_scale))))
+
+    def gumbel(self):
+        """dbaz_get_gumbel: dict(m, c_visit, c_scale, searches, rows) -- the setting (0, 0.0, 0.0 when off) and the Gumbel searches
+        started and rows written since the last selfplay_start, after the queued work is done."""
+        m, cv, cs, a, b = C.c_int32(), C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(m), C.byref(cv), C.byref(cs), C.byref(a), C.byref(b)))
+        return dict(m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value), searches=int(a.value), rows=int(b.value))
+
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
 
@@ -590,6 +616,10 @@ class Engine:
         self._ck(self._L.dbaz_get_forced_playouts(self.h, None, C.byref(prune), None, None))  # the setting alone: no device work
         if prune.value or (flags & 2).any():
             out["pruned"] = (flags & 2) != 0  # ROW_FLAG_PRUNED, read from the rows themselves
+        gm = C.c_int32()
+        self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(gm), None, None, None, None))  # the setting alone: no device work
+        if gm.value or (flags & 4).any():
+            out["gumbel"] = (flags & 4) != 0  # ROW_FLAG_GUMBEL: visits are the target pi' in units of 2^-24
         return out
 
     def _fetch_once(self):

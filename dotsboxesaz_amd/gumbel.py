@@ -1,0 +1,138 @@
+"""Gumbel root search (Danihelka et al., ICLR 2022, "Policy improvement by planning with Gumbel") at the root of the self-play
+driver's searches.
+
+With Engine(gumbel=(m, c_visit, c_scale)) -- params.self_play.gumbel = {"m": 16, "c_visit": 50, "c_scale": 1.0} -- every search
+the driver starts samples its candidates by the Gumbel-top-m trick, spends its reads by sequential halving, plays the rule's own
+move and records softmax(logits + sigma(completed Q)) as the row's target (visits = round(pi' * 2^24), bit 2 of a row's "pad";
+fetch_samples()["gumbel"]).  That target is a policy improvement at any budget, which is what the searches of 16 to 100 reads
+need.  The rule is stated in full in include/dbaz.h; its host mirrors (no device):
+
+    considered_visits(m_eff, R)                       the sequence of considered visits (dbaz_gumbel_considered)
+    target(c_visit, c_scale, P, W, n, same, valid)    the row's visits of a root (dbaz_gumbel_target)
+
+What the rule does to playing strength per GPU-hour has not been measured here.
+
+    python -m dotsboxesaz_amd.gumbel --rows 6 --cols 6 --bench 8192 --slots 8192 --reads 32,64,100 [--full-prob 0.25 --fast-reads 100]
+
+plays the same game indices with a random-init ResNetZero with PUCT at --puct-reads and with the Gumbel root at each read count,
+in one process, and prints one JSON line: per mode games/s, recorded rows/s, network evaluations per game and the mean entropy
+(nats) of the recorded pi.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+DEFAULT = (16, 50.0, 1.0)  # m, c_visit, c_scale
+
+
+def considered_visits(m_eff, R):
+    """int32 [R]: considered(m_eff, R, t) for t = 0 .. R - 1.  ValueError for what dbaz_gumbel_considered refuses."""
+    L = _lib.load()
+    out = np.zeros(max(int(R), 0), dtype=np.int32)
+    if L.dbaz_gumbel_considered(int(m_eff), int(R), out.ctypes.data) != 0:
+        raise ValueError("dbaz_gumbel_considered refused its arguments (m_eff = %r, R = %r)" % (m_eff, R))
+    return out
+
+
+def target(c_visit, c_scale, P, W, n, same, valid):
+    """int32 [A]: the visits a Gumbel row records for a root with float64 priors P, float32 child_total_value W, visit counts n,
+    same[i] = child i's player to move is the root's (sgn = +1), valid[i] = child i is a legal move: floor(pi' * 2^24 + 0.5) with
+    pi' = softmax(logit + sigma(completed Q)) over the candidates.  ValueError for what dbaz_gumbel_target refuses."""
+    L = _lib.load()
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.int64)
+    A = P.shape[0]
+    if not (P.shape == W.shape == n.shape == (A,) == np.shape(same) == np.shape(valid)) or (n < 0).any() or (n > 0x3FFFFFFF).any():
+        raise ValueError("P, W, n, same and valid are [A] arrays, n in 0 .. 2^30 - 1")
+    ns = (n.astype(np.uint32) | np.where(np.asarray(same, dtype=bool), np.uint32(0x40000000), np.uint32(0))).astype(np.uint32)
+    v = np.ascontiguousarray(np.asarray(valid, dtype=bool), dtype=np.uint8)
+    out = np.zeros(A, dtype=np.int32)
+    rc = L.dbaz_gumbel_target(A, C.c_double(float(c_visit)), C.c_double(float(c_scale)), P.ctypes.data, W.ctypes.data, ns.ctypes.data,
+                              v.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("dbaz_gumbel_target refused its arguments (A = %d, c_visit = %r, c_scale = %r)" % (A, c_visit, c_scale))
+    return out
+
+
+def _entropy(pi):
+    """mean over the rows of -sum pi log pi (nats)"""
+    p = np.asarray(pi, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(p > 0, p * np.log(p), 0.0)
+    return float(-t.sum(axis=1).mean()) if len(p) else 0.0
+
+
+def _bench(a):
+    import sys
+    import time
+    import torch
+    from . import nn as dnn
+    from .engine import Engine
+
+    cap = (a.full_prob, a.fast_reads) if a.full_prob < 1.0 else None
+
+    def play(name, reads, gumbel):
+        eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=reads, noise=(0.8, 0.25), reuse_tree=True, evaluator="resnet", seed=1000,
+                     device=a.device, playout_cap=cap, gumbel=gumbel)
+        torch.manual_seed(0)
+        model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
+        eng.load_state_dict(model.state_dict(), "resnet", **model.shape)
+        runs = []
+        for i in range(a.repeats + 1):
+            n_games = a.bench if i else min(a.bench, a.warmup_games)  # the first run warms up, on few games
+            eng.sync()
+            t0 = time.perf_counter()
+            eng.selfplay_start(n_games, 0)
+            eng.run()
+            dt = time.perf_counter() - t0  # the games; the rows are fetched outside (a generation keeps them on the device)
+            got = eng.fetch_samples()
+            c, gm = eng.counters(), eng.gumbel()
+            full = got["full"] if "full" in got else np.ones(len(got["z"]), bool)
+            print("gumbel bench: %s run %d of %d, %d games, %.1f s" % (name, i, a.repeats, n_games, dt), file=sys.stderr, flush=True)
+            if i:
+                games = max(1, c["games_finished"])
+                runs.append(dict(games_per_s=c["games_finished"] / dt, recorded_rows_per_s=int(full.sum()) / dt,
+                                 nn_evals_per_game=c["nn_evals"] / games, gumbel_rows=gm["rows"], steps=c["steps"],
+                                 pi_entropy=_entropy(got["pi"][full]), pool_resets=c["pool_resets"], seconds=dt))
+        eng.close()
+        return {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
+
+    out = dict(rows=a.rows, cols=a.cols, games=a.bench, slots=a.slots, m=a.m, c_visit=a.c_visit, c_scale=a.c_scale, full_prob=a.full_prob,
+               fast_reads=a.fast_reads, puct_reads=a.puct_reads)
+    if a.puct_reads > 0:
+        out["puct"] = play("puct %d" % a.puct_reads, a.puct_reads, None)
+    for r in a.reads:
+        out["gumbel_%d" % r] = play("gumbel %d" % r, r, (a.m, a.c_visit, a.c_scale))
+    return out
+
+
+def main(argv=None):
+    import argparse
+    import json
+    ap = argparse.ArgumentParser(description="self-play with PUCT and with the Gumbel root search at several read counts; prints one JSON line")
+    ap.add_argument("--rows", type=int, default=6)
+    ap.add_argument("--cols", type=int, default=6)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--bench", type=int, default=8192, metavar="N", help="games per timed run (game indices 0 .. N-1, in every mode)")
+    ap.add_argument("--slots", type=int, default=0, help="engine slots (default min(N, 8192))")
+    ap.add_argument("--reads", type=lambda s: [int(x) for x in s.split(",") if x], default=[32, 64, 100], help="mcts_num_read of the Gumbel runs")
+    ap.add_argument("--puct-reads", type=int, default=800, help="mcts_num_read of the PUCT run (0: none)")
+    ap.add_argument("--m", type=int, default=DEFAULT[0], help="candidates sampled without replacement")
+    ap.add_argument("--c-visit", type=float, default=DEFAULT[1])
+    ap.add_argument("--c-scale", type=float, default=DEFAULT[2])
+    ap.add_argument("--full-prob", type=float, default=1.0, help="playout cap: share of full searches (1 = no cap)")
+    ap.add_argument("--fast-reads", type=int, default=100)
+    ap.add_argument("--channels", type=int, default=64)
+    ap.add_argument("--blocks", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=1, help="timed runs per mode (median)")
+    ap.add_argument("--warmup-games", type=int, default=64, help="games of the one untimed run in front of them")
+    a = ap.parse_args(argv)
+    a.slots = a.slots or max(1, min(a.bench, 8192))
+    print(json.dumps(_bench(a)))
+
+
+if __name__ == "__main__":
+    main()

@@ -63,6 +63,11 @@ def start_moves(game_state, rows, cols):
     return [int(m) for m in game_state]  # a plain move sequence
 
 
+def _gumbel_args(gum):
+    """params.self_play.gumbel -> (m, c_visit, c_scale) with the defaults of Engine.selfplay_set_gumbel"""
+    return (int(_get(gum, "m", 16)), float(_get(gum, "c_visit", 50.0)), float(_get(gum, "c_scale", 1.0)))
+
+
 def engine_kwargs_from_params(params, async_searches=False):
     """Pull the hot-path knobs out of a reference-style params dict (configuration.py:82-100).
 
@@ -78,7 +83,10 @@ def engine_kwargs_from_params(params, async_searches=False):
     Engine(playout_cap=(p, n)): playout cap randomization, Engine.selfplay_set_playout_cap.
     params.self_play.forced_playouts = {"k": 2.0, "prune": True} (the same; absent = off) becomes Engine(forced_playouts=(k, prune)):
     forced playouts and policy target pruning, Engine.selfplay_set_forced_playouts.  It is refused together with
-    async_searches=True and max_async_searches > 1 (self-play in waves)."""
+    async_searches=True and max_async_searches > 1 (self-play in waves).
+    params.self_play.gumbel = {"m": 16, "c_visit": 50, "c_scale": 1.0} (the same; absent = off) becomes Engine(gumbel=(m, c_visit,
+    c_scale)): the Gumbel root search, Engine.selfplay_set_gumbel.  It is refused together with forced_playouts and with self-play
+    in waves."""
     sp = _get(params, "self_play")
     m = _get(sp, "mcts")
     noise = _get(sp, "noise", [0.0, 0.0])
@@ -94,6 +102,9 @@ def engine_kwargs_from_params(params, async_searches=False):
     forced = _get(sp, "forced_playouts")
     if forced is not None:
         kw["forced_playouts"] = (float(_get(forced, "k")), bool(_get(forced, "prune", True)))
+    gum = _get(sp, "gumbel")
+    if gum is not None:
+        kw["gumbel"] = _gumbel_args(gum)
     return kw
 
 
@@ -141,6 +152,9 @@ class SelfPlay:
         forced = _get(_get(params, "self_play"), "forced_playouts")
         if forced is not None:  # the engine was made elsewhere: the setting of the handle follows the parameters
             self.engine.selfplay_set_forced_playouts(float(_get(forced, "k")), bool(_get(forced, "prune", True)))
+        gum = _get(_get(params, "self_play"), "gumbel")
+        if gum is not None:
+            self.engine.selfplay_set_gumbel(*_gumbel_args(gum))
 
     def play_games_sync(self, games_idxs, game_state=None):
         """game_state: the position every game starts from (self_play.py:51-55; None = the empty board); move_idx and the
@@ -261,6 +275,7 @@ assert ROW_META.itemsize == 28
 
 ROW_FLAGS_OFF, ROW_FLAG_FAST = 26, 1  # csrc/replay_row.h: the int16 "pad"; bit 0 = the row of a fast search of the playout cap
 ROW_FLAG_PRUNED = 2  # bit 1 = policy target pruning ran on the row: its visits (and pi) are the pruned ones
+ROW_FLAG_GUMBEL = 4  # bit 2 = the row of a Gumbel search: its visits are the target pi' in units of 2^-24 (pi = visits / visits.sum())
 
 
 def full_rows_only(samples):
@@ -432,6 +447,7 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     kw = engine_kwargs_from_params(p0)
     kw.pop("playout_cap", None)  # the cap belongs to self-play: a match searches every move in full
     kw.pop("forced_playouts", None)  # and so do forced playouts
+    kw.pop("gumbel", None)  # and the Gumbel root search
     if "reuse_mcts_tree" in over:
         kw["reuse_tree"] = bool(_get(over, "reuse_mcts_tree"))
     if "noise" in over:
@@ -496,6 +512,7 @@ def solver_match(params, generation, n_games, rows, cols, openings=None, solver=
     kw.update(reuse_tree=False, noise=(0.0, 0.0))
     kw.pop("playout_cap", None)  # the cap belongs to self-play
     kw.pop("forced_playouts", None)
+    kw.pop("gumbel", None)
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=model.kind, evaluator2="solver", match_play=True,
                  device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads, **kw)
     try:

@@ -326,6 +326,78 @@ int dbaz_selfplay_set_forced_playouts(dbaz_engine *e, double k, int32_t prune);
 int dbaz_get_forced_playouts(dbaz_engine *e, double *k, int32_t *prune, int64_t *rows_pruned, int64_t *visits_pruned);
 int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double sq, int64_t root_N, const double *P, const float *W,
                       const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
+/* Gumbel root search (Danihelka et al., ICLR 2022, "Policy improvement by planning with Gumbel") at the root of the self-play
+ * driver's searches: candidates sampled without replacement by the Gumbel-top-m trick, the read budget spent by sequential
+ * halving, and softmax(logits + sigma(completed Q)) as the policy target in place of the visit counts.
+ * dbaz_selfplay_set_gumbel(e, m, c_visit, c_scale) is a setting of the handle: it holds for every later dbaz_selfplay_start.
+ * m = 0 switches the rule off (the state after dbaz_create; the other two arguments are then ignored and read back 0).  With the
+ * rule off every row is what it was.
+ * Scope: with m > 0 every search that the self-play driver starts is a Gumbel search, full and fast searches of the playout cap
+ * alike (a fast search still has capped reads and its row still carries bit 0).  Explicit searches (dbaz_search*, dbaz_select)
+ * and match play never see the rule.  Below the root nothing changes.
+ * All arithmetic below is float64, every operation rounded on its own (no fused multiply-add), in the order written.
+ *
+ * Root preparation -- where the root's priors are prepared for such a search (at its start, or after the root's expansion):
+ *   The root is prepared as UCT_search(..., dirichlet=(0.0, 0.0)) prepares it, like a fast search: no Dirichlet noise.
+ *   P(a) = the float64 root prior that results.
+ *   C = the valid children with P(a) > 0; if there are none, all valid children.  m' = min(m, |C|).
+ *   logit(a) = log(P(a)) for P(a) > 0, else -1e30.
+ *   g(a) = -log(-log(u)), u = u01(words 0, 1) of Philox4x32-10 with counter (lo32(game), hi32(game), ply + 65536 a, 0x44444444)
+ *     and the key (lo32(seed), hi32(seed)), u clamped to [2^-53, 1 - 2^-53]; u01(a, b) = ((a >> 5) 2^26 + (b >> 6)) 2^-53.
+ *     A vector scripted for this (game, ply) through dbaz_selfplay_script is taken as g as is, whatever noise_alpha is and for
+ *     fast searches too.  (On a handle with m = 0 scripts mean what they mean without the rule.)  Only a scripted vector is
+ *     taken: one that the host left for the slot by other means is dropped when such a search starts.
+ *   Kept per slot:  gl(a) = g(a) + logit(a);  n0(a) = the child's visit count as the tree holds it at this moment (non-zero
+ *     under tree reuse);  R = the reads this search was started with (after the driver rule, fast_reads, solver_reads,
+ *     endgame_reads, stagger and quickplay).
+ *
+ * Selection at the root level of every simulation -- with n(a), W(a), sgn(a) as this simulation reads them:
+ *   n_s(a) = n(a) - n0(a),  t = sum_a n_s(a).
+ *   q(a) = ((double)W / (double)(1 + n)) * sgn  for n(a) > 0  (the descent's own value_score).
+ *   v_mix = sum_{n>0} P(a) q(a) / sum_{n>0} P(a), or 0 if the denominator is 0.  (The paper's mixed value without the raw
+ *     network value of the root: once tree reuse has made a child the root, that value is not kept anywhere.)
+ *   cq(a) = q(a) for n(a) > 0, else v_mix.
+ *   n_max = the maximum of n over the valid children.
+ *   sigma(a) = ((c_visit + (double)n_max) * c_scale) * cq(a).
+ *   cv = considered(m', R, t), below.
+ *   The simulation takes the first maximum of gl(a) + sigma(a) over the candidates with n_s(a) == cv.  If no candidate has
+ *   n_s == cv, the candidates with the smallest n_s compete (this cannot happen while t < R; it makes the rule total).
+ * Sum order: each sum over the A children is taken in two stages.  Lane i of 64 adds its entries i, i + 64, i + 128, i + 192 in
+ * that order, absent ones (and the terms of children with n = 0) as +0.0; then six butterfly stages s = s + s[lane ^ o] for
+ * o = 32, 16, ..., 1.
+ *
+ * considered(m', R, t) -- mctx's sequence of considered visits in closed form per phase.  For m' <= 1 it is t.  Otherwise
+ *   L = ceil(log2(m'));  nc = m'; base = 0; pos = 0
+ *   loop:  extra = max(1, R / (L * nc))   (integer division);  len = extra * nc
+ *          if t < pos + len: return base + (t - pos) / nc
+ *          pos += len; base += extra; nc = max(2, nc / 2)
+ * The halving is implicit: a child that is picked leaves the set n_s == cv, so each phase visits the best nc children by
+ * gl + sigma `extra` times each.
+ *
+ * The move: a scripted move wins.  Otherwise the first maximum of gl(a) + sigma(a) over the candidates with the maximum n_s, all
+ * quantities read after the search.  Temperature is not used and the move-draw stream is not consumed.
+ *
+ * The row: x(a) = logit(a) + sigma(a) over the candidates (without g), M = max x, e(a) = exp(x(a) - M), pi'(a) = e(a) / sum e
+ * (in the sum order above).  The row's visits[a] = (int32) floor(pi'(a) * 2^24 + 0.5); every non-candidate gets 0.  The row's
+ * flag word gets bit 2 (ROW_FLAG_GUMBEL, value 4).  q_value, the tree statistics and z are what they were.  Every reader of the
+ * row turns visits into pi by visits / visits.sum().
+ *
+ *   m < 0 or m > DBAZ_MAX_A; c_visit NaN, negative or above 1e6; c_scale NaN, <= 0 or above 1e3 (both only looked at for
+ *   m > 0); a match_play handle; a handle created with selfplay_pending; a handle with forced playouts on      -> DBAZ_EINVAL
+ *     (dbaz_selfplay_set_forced_playouts(k > 0) refuses a handle with the Gumbel rule on in turn: both own the root's pick)
+ *   games of an earlier dbaz_selfplay_start still being played                                                  -> DBAZ_ESTATE
+ * A failed call changes nothing.
+ * dbaz_get_gumbel: the setting, and the Gumbel searches the driver has started and the Gumbel rows written since the last
+ * dbaz_selfplay_start, which zeroes both.  Any output pointer may be NULL.
+ * dbaz_gumbel_considered, dbaz_gumbel_target: the rule on the host -- no handle, no device -- from the very code the kernels
+ * run.  out[t] = considered(m_eff, R, t) for t < R.  dbaz_gumbel_target: the row's visits of a root given its P, W,
+ * n_and_sign[i] = n | (sgn > 0 ? 0x40000000 : 0) and valid[i] != 0 for a valid child.  Arguments out of the ranges above,
+ * n_actions outside 1 .. DBAZ_MAX_A or a NULL pointer -> DBAZ_EINVAL. */
+int dbaz_selfplay_set_gumbel(dbaz_engine *e, int32_t m, double c_visit, double c_scale);
+int dbaz_get_gumbel(dbaz_engine *e, int32_t *m, double *c_visit, double *c_scale, int64_t *searches, int64_t *rows);
+int dbaz_gumbel_considered(int32_t m_eff, int32_t R, int32_t *out /*[R]*/);
+int dbaz_gumbel_target(int32_t n_actions, double c_visit, double c_scale, const double *P, const float *W,
+                       const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
 int dbaz_step(dbaz_engine *e, int32_t k);             /* k simulation steps, asynchronous */
 /* until all games are finished, max_steps (if > 0) are done, or every remaining slot is
  * blocked on a full output buffer (counters.blocked_slots == active_slots: fetch and call again) */
@@ -340,7 +412,7 @@ int dbaz_fetch_samples(dbaz_engine *e, int32_t max_rows, int32_t *n_rows,
                        int16_t *x /*[rows*3HW]*/, int32_t *visits /*[rows*A]*/, double *pi /*[rows*A]*/,
                        int8_t *z, int16_t *max_deepness, int32_t *tree_size, int32_t *terminal_count,
                        float *q_value, int16_t *played);
-/* The flag words (the int16 at byte 26 of a packed row: bit 0 = row of a fast search, bit 1 = pruned visits) of the rows
+/* The flag words (the int16 at byte 26 of a packed row: bit 0 = row of a fast search, bit 1 = pruned visits, bit 2 = row of a Gumbel search) of the rows
  * dbaz_fetch_samples would hand out now, in its order.  Drains nothing: call it first.  max_rows = 0: the count alone. */
 int dbaz_fetch_row_flags(dbaz_engine *e, int32_t max_rows, int32_t *n_rows, int16_t *flags);
 /* device-resident replay rows for the RCCL all-gather (multi-GPU iteration end):
