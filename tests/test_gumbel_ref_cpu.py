@@ -9,7 +9,15 @@
   exp and log are not correctly rounded);
 * the gap condition: over every decision of every case of CASES -- the table test_hip_gumbel.py plays -- the best score is more
   than 1e-9 above the second, so a last-bit difference between device and host log changes no decision.  The seeds were picked
-  here so that this holds."""
+  here so that this holds;
+* the game loop's new arguments (table=, endgame_reads=, served_from=, a LeafSolver as the evaluator) at their defaults change no
+  byte of the existing cases;
+* the cases of FEATURES -- the table test_hip_gumbel_features.py plays -- keep the gap condition and reach what they are there for
+  (a served root with m' > 1, R < m', solved leaves under high roots and right below a Gumbel root, first rows at ply 0 of a
+  start position), the six mistakes still show on them, and so do the mistakes only they can show: R not capped by endgame_reads,
+  an ignored cap, no table, a zero-prior candidate, the ply counted from the empty board;
+* zero priors: the three kinds of root with a formula evaluator whose priors are zeroed on half of the actions, and with the torch
+  forward pass of test_hip_gumbel_net.py's network, which also tells which network seeds leave the gap condition room."""
 import math
 import os
 import subprocess
@@ -83,7 +91,7 @@ def phase_budgets(m_eff, R):
 
 @pytest.mark.parametrize("name", SMALL)
 def test_phase_budgets_and_the_first_round(name):
-    _, R, C, sims, m, reuse, cap, g_mode, ev, _ = next(c for c in GR.CASES if c[0] == name)
+    _, R, C, sims, m, reuse, cap, g_mode, ev, _, c_visit, c_scale = GR.case(name)
     d = O.dims(R, C)
     seen = []
 
@@ -102,7 +110,7 @@ def test_phase_budgets_and_the_first_round(name):
         seen.append((info["m_eff"], reuse and bool(info["n0"].any())))
 
     for gi in range(4):
-        GR.play_game(d, g_mode=g_mode, game_idx=gi, seed=GR.SEED, sims=sims, reuse=reuse, gumbel=(m, GR.C_VISIT, GR.C_SCALE), cap=cap,
+        GR.play_game(d, g_mode=g_mode, game_idx=gi, seed=GR.SEED, sims=sims, reuse=reuse, gumbel=(m, c_visit, c_scale), cap=cap,
                      base_ev=GR.KIND[ev], on_root=on_root)
     assert len(seen) > 60 and any(me < m for me, _ in seen)  # m > |C| late in a game
     assert not reuse or any(r for _, r in seen)  # n0 is non-zero under tree reuse: n and n_s part
@@ -130,19 +138,189 @@ def test_gap_condition(name):
         assert np.array_equal(g["flags"], np.where(g["full"], 4, 5))
 
 
+# ---------------------------------------------------------------- tables, a leaf solver, start positions, zero priors
+ROW_KEYS = ("x", "player", "visits", "pi", "q_value", "max_deepness", "tree_size", "terminal_count", "played", "reads", "full", "served", "flags", "z",
+            "vectors")
+
+
+def same_game(a, b, keys=("visits", "played", "q_value", "tree_size", "z")):
+    return a["n_rows"] == b["n_rows"] and all(np.array_equal(a[k], b[k]) for k in keys)
+
+
+@pytest.mark.parametrize("name", ["3x3-script-m4", "3x3-philox-m2-cap"])
+def test_the_new_arguments_at_their_defaults_change_nothing(name):
+    """table=None, endgame_reads=0, served_from=None: the game loop as it was, written out here without the new arguments"""
+    _, R, C, sims, m, reuse, cap, g_mode, ev, _, c_visit, c_scale = GR.case(name)
+    d = O.dims(R, C)
+    for gi, want in enumerate(GR.case_games(name, None, 4)):
+        gv = GR.gumbel_vectors(np.random.RandomState(1000 + gi)) if g_mode == "script" else None
+        t = GR.Tree(d, O.new_state(d))
+        gaps, i = [], 0
+        while not t.is_terminal:
+            valid = t.first.valid
+            reads = GR.ESR._fact_reads(int(valid.sum()), sims)
+            full = cap is None or GR.PCR.is_full(GR.SEED, gi, i, cap[0])
+            reads = reads if full else min(reads, cap[1])
+            g = np.asarray(gv(i, valid)) if gv else np.array([GR.philox_g(GR.SEED, gi, i, a) for a in range(d.A)])
+            move, vis, _ = t.gsearch(reads, FR.formula(GR.KIND[ev]), m, c_visit, c_scale, g, gaps)
+            q = t.stats()[3]
+            assert move == want["played"][i] and vis.tobytes() == want["visits"][i].tobytes() and reads == want["reads"][i]
+            assert np.float32(q).tobytes() == np.float32(want["q_value"][i]).tobytes() and not want["served"][i]
+            t.advance(move, reuse)
+            i += 1
+        assert i == want["n_rows"] and min(gaps) == want["min_gap"] and want["n_tied_roots"] == 0
+        again = GR.play_game(d, g_mode=g_mode, game_idx=gi, seed=GR.SEED, sims=sims, reuse=reuse, gumbel=(m, c_visit, c_scale), cap=cap,
+                             base_ev=GR.KIND[ev], table=None, endgame_reads=0, served_from=None)
+        for key in ROW_KEYS:
+            assert again[key].dtype == want[key].dtype and again[key].tobytes() == want[key].tobytes(), (gi, key)
+
+
+@pytest.mark.parametrize("name", GR.FEATURE_IDS)
+def test_feature_cases_gap_and_reach(name):
+    """the gap condition of every case test_hip_gumbel_features.py plays, and that the case reaches what it is there for"""
+    f = GR.FEATURES[name]
+    games, w = GR.feature_games(name)
+    gap = min(g["min_gap"] for g in games.values())
+    print(name, "minimum gap", gap)
+    assert gap >= 1e-9 and sum(g["n_tied_roots"] for g in games.values()) == 0
+    d = O.dims(f["R"], f["C"])
+    if "table" in f:
+        rows = {k: np.concatenate([g[k] for g in games.values()]) for k in ("served", "m_eff", "R", "n_free", "n0_any", "reads")}
+        assert np.array_equal(rows["served"], rows["n_free"] <= f["table"])
+        # a served root that another evaluator's leaf expanded earlier keeps that prior under tree reuse: m' > 1
+        assert (rows["served"] & (rows["m_eff"] > 1) & rows["n0_any"]).any()
+        assert all(g["served"].any() and not g["served"].all() for g in games.values())  # served and unserved rows in one game
+        assert sum(g["table_calls"] for g in games.values()) > 0 and sum(g["base_calls"] for g in games.values()) > 0
+        short = rows["served"] & (rows["R"] < rows["m_eff"])  # considered() with extra clamped to 1 from the first phase on
+        assert short.any() == (0 < f["endgame_reads"] < 8)
+        if f["endgame_reads"]:
+            assert (rows["reads"][rows["served"]] <= f["endgame_reads"]).all() and (rows["reads"][~rows["served"]] > f["endgame_reads"]).all()
+    if "leaf" in f:
+        assert sum(w.solved_under_high_roots()) > 0 and w.calls["base"] > 0
+        # a solved leaf as a direct child of a Gumbel root: a visited, unfinished child with F <= L under a root with F = L + 1
+        direct = []
+
+        def on_root(t, info, reads, full):
+            r = t.first
+            if int(r.valid.sum()) == f["leaf"] + 1:
+                direct.extend(a for a, c in r.children.items() if c.expanded and not c.terminal and info["ns"][a] > 0)
+
+        w2 = GR.LSR.LeafSolver(f["R"], f["C"], f["leaf"], GR.TABLE_SEED, 0)
+        for gi in range(2):
+            g = GR.play_game(d, g_mode=f["g"], game_idx=gi, seed=GR.SEED, sims=f["sims"], reuse=f["reuse"], gumbel=(f["m"], GR.C_VISIT, GR.C_SCALE),
+                             base_ev=w2, on_root=on_root)
+            assert same_game(g, games[gi])
+        assert len(direct) > 0
+    if "starts" in f:
+        # the engine's convention (test_hip_selfplay_start.py, Engine.selfplay_set_start): move_idx, scripts and every per-ply stream
+        # count plies from the START POSITION -- the first row of a game has move_idx 0 (and move -1) whatever its opening's length
+        book = GR.feature_book(name)
+        assert sorted(len(b) for b in book) == sorted(f["starts"]) and len({tuple(b) for b in book}) == 3
+        used = set()
+        for gi, g in games.items():
+            si = GR.start_of(gi, 3, 2)
+            used.add(si)
+            assert np.array_equal(g["x"][0], O.features(d, O.state_from_moves(d, book[si])).ravel())
+            if f["g"] == "philox":  # row 0's g is the stream's ply 0
+                assert g["vectors"][0][5] == GR.philox_g(GR.SEED, gi, 0, 5) != GR.philox_g(GR.SEED, gi, len(book[si]), 5)
+        assert used == {0, 1, 2}
+
+
+def changed_games(name, **kw):
+    right, _ = GR.feature_games(name)
+    wrong, _ = GR.feature_games(name, **kw)
+    return sum(0 if same_game(right[gi], wrong[gi]) else 1 for gi in wrong)
+
+
+@pytest.mark.parametrize("mistake", GR.MISTAKES)
+def test_every_mistake_changes_a_row_of_a_feature_case(mistake):
+    assert sum(changed_games(name, mistake=mistake, n_games=4) for name in ("3x3-table-reads3", "3x3-leaf", "3x3-start-philox")) >= 1, mistake
+
+
+def test_table_case_needs_the_table_and_the_cap():
+    """a reference that ignores endgame_reads, one that treats every root as unserved, and one that keeps the uncapped reads as the
+    R of the halving (what begin_search would store before the cap) each differ from the right one"""
+    assert changed_games("3x3-table-reads3", endgame_reads=0) >= 1
+    assert changed_games("3x3-table-reads3", table=False) >= 1 and changed_games("3x3-table", table=False) >= 1
+    # considered(m', R, t) does not depend on R while t < 3, so the cap of 3 cannot show which R is kept; the cap of 12 does
+    assert changed_games("3x3-table-reads3", mistake="R_uncapped") == 0 and changed_games("3x3-table-reads12", mistake="R_uncapped") >= 1
+    assert changed_games("3x3-table", mistake="R_uncapped") == 0  # without a cap there is nothing to get wrong
+    late = changed_games("3x3-table", served_from=((0, 1 << 30), (1, 1 << 30)))  # a game that a dry pool never serves
+    assert late == 2
+
+
+def test_start_case_needs_the_ply_from_the_start_position():
+    assert changed_games("3x3-start-philox", mistake="ply_from_empty_board") >= 1
+    assert changed_games("6x6-start-script", mistake="ply_from_empty_board") == 0  # scripted g: the stream is not read
+
+
+# ---- zero priors: a formula evaluator with the priors of a fixed half of the actions set to 0 (a network's softmax can do that)
+ZERO = tuple(range(0, 32, 2))
+
+
+def zeroed(d, st):
+    p, v = O.eval_formula(d, st, 0)
+    p = np.array(p, np.float32)
+    p[list(ZERO)] = 0.0
+    return p, v
+
+
+def zero_prior_games(mistake=None, n_games=4, ev=zeroed, game_idxs=None):
+    d = O.dims(3, 3)
+    return [GR.play_recording_roots(d, g_mode="philox", game_idx=gi, seed=GR.SEED, sims=32, reuse=True, gumbel=(16, GR.C_VISIT, GR.C_SCALE),
+                                    base_ev=ev, mistake=mistake) for gi in (game_idxs or range(n_games))]
+
+
+def test_zero_priors_three_kinds_of_root():
+    """roots with both kinds of valid child, roots without a positive prior, and the change from one to the other inside a game"""
+    played = zero_prior_games()
+    kinds = [GR.zero_prior_roots(g, roots, ZERO) for g, roots in played]
+    assert sum(k[0] for k in kinds) > 0 and sum(k[1] for k in kinds) > 0 and any(k[2] for k in kinds)
+    assert min(g["min_gap"] for g, _ in played) >= 1e-9
+    wrong = zero_prior_games("zero_prior_candidate")
+    assert sum(0 if same_game(a[0], b[0]) else 1 for a, b in zip(played, wrong)) >= 1
+
+
+# ---- the network cases of test_hip_gumbel_net.py, with the torch model in the engine's place: which seeds have room
+@pytest.mark.parametrize("R,C", sorted(GR.NET))
+def test_network_seeds_have_room(R, C):
+    """the GPU test's own assertion is the one that counts: the engine's network differs from torch's in the last bits, so its games
+    may part from these.  Here the same games with the torch forward pass as the evaluator keep every decision 1e-9 off a tie."""
+    ev = GR.torch_evaluator(GR.network(R, C), R, C)
+    n = GR.NET[(R, C)]
+    d = O.dims(R, C)
+    games = [GR.play_game(d, g_mode="philox", game_idx=gi, seed=GR.SEED, sims=n["sims"], reuse=True, gumbel=(16, GR.C_VISIT, GR.C_SCALE), base_ev=ev)
+             for gi in n["replay"][:1 if R > 3 else 4]]
+    gap = min(g["min_gap"] for g in games)
+    print("%dx%d network, torch evaluator: minimum gap %g" % (R, C, gap))
+    assert gap >= 1e-9
+
+
+def test_zero_prior_network_reaches_the_three_kinds_of_root():
+    ev = GR.torch_evaluator(GR.network(3, 3, zero=True), 3, 3)
+    d = O.dims(3, 3)
+    p, _ = ev(d, O.new_state(d))
+    assert (p[list(GR.NET_ZERO)] == 0).all() and (np.delete(p, list(GR.NET_ZERO)) > 0).all()
+    played = zero_prior_games(ev=ev, game_idxs=GR.NET_ZERO_REPLAY)
+    kinds = [GR.zero_prior_roots(g, roots, GR.NET_ZERO) for g, roots in played]
+    print("zero-prior network, torch evaluator: (mixed, tied, change) per game", kinds, "minimum gap", min(g["min_gap"] for g, _ in played))
+    assert sum(k[0] for k in kinds) > 0 and sum(k[1] for k in kinds) > 0 and any(k[2] for k in kinds)
+    assert min(g["min_gap"] for g, _ in played) >= 1e-9
+
+
 def roots_of(name, n_games):
     """(c_visit, c_scale, P, W, n, same, valid, the reference's visits) of every root of a case's first games"""
-    _, R, C, sims, m, reuse, cap, g_mode, ev, _ = next(c for c in GR.CASES if c[0] == name)
+    _, R, C, sims, m, reuse, cap, g_mode, ev, _, c_visit, c_scale = GR.case(name)
     d = O.dims(R, C)
     roots = []
 
     def on_root(t, info, reads, full):
         P, W, n, sgn = t.root_arrays()
         valid = t.first.valid.copy()
-        roots.append((GR.C_VISIT, GR.C_SCALE, P, W, n, sgn > 0, valid, GR.target(GR.C_VISIT, GR.C_SCALE, P, W, n, sgn, valid)))
+        roots.append((c_visit, c_scale, P, W, n, sgn > 0, valid, GR.target(c_visit, c_scale, P, W, n, sgn, valid)))
 
     for gi in range(n_games):
-        GR.play_game(d, g_mode=g_mode, game_idx=gi, seed=GR.SEED, sims=sims, reuse=reuse, gumbel=(m, GR.C_VISIT, GR.C_SCALE), cap=cap,
+        GR.play_game(d, g_mode=g_mode, game_idx=gi, seed=GR.SEED, sims=sims, reuse=reuse, gumbel=(m, c_visit, c_scale), cap=cap,
                      base_ev=GR.KIND[ev], on_root=on_root)
     return roots
 

@@ -6,7 +6,9 @@ flags, and within +-1 count per entry in visits (device and host exp / log are n
 no decision of these games is within 1e-9 of a tie).
 
 Formula evaluators, 8 slots, 2 to 16 games, 16 and 32 reads; one board per lanes-per-child class: 3x3 (A = 32), 6x6 (A = 98),
-8x8 (A = 162), 10x10 (A = 242)."""
+8x8 (A = 162), 10x10 (A = 242); 1x1 with m = 256, 2x7 with m = 3, and the constants (0, 0.1) and (1e6, 1) next to (50, 1).
+The network evaluator is test_hip_gumbel_net.py's, tables, the leaf solver, start positions and more slots
+test_hip_gumbel_features.py's."""
 import numpy as np
 import pytest
 
@@ -61,9 +63,9 @@ def sorted_payload(e, packed):
 @pytest.mark.parametrize("name", GR.CASE_IDS)
 def test_rows_against_the_reference(name):
     """fails on a library without the feature: Engine(gumbel=) finds no dbaz_selfplay_set_gumbel"""
-    _, R, C, sims, m, reuse, cap, g_mode, ev, n_games = next(c for c in GR.CASES if c[0] == name)
+    _, R, C, sims, m, reuse, cap, g_mode, ev, n_games, c_visit, c_scale = GR.case(name)
     games = GR.case_games(name)
-    e = make(R, C, 8, (m, GR.C_VISIT, GR.C_SCALE), sims=sims, evaluator=ev, reuse_tree=reuse, playout_cap=cap)
+    e = make(R, C, 8, (m, c_visit, c_scale), sims=sims, evaluator=ev, reuse_tree=reuse, playout_cap=cap)
     if g_mode == "script":
         for gi, g in enumerate(games):
             e.selfplay_script(gi, np.full(g["n_rows"], -1, np.int16), g["vectors"])  # no move is forced: the rule picks
@@ -93,7 +95,7 @@ def test_rows_against_the_reference(name):
     print(name, "largest difference in counts", worst)
     n_rows = sum(g["n_rows"] for g in games)
     assert c["expansions"] == sum(g["n_search"] for g in games)  # the reads are the reference's, capped ones included
-    assert (gm["m"], gm["c_visit"], gm["c_scale"], gm["searches"], gm["rows"]) == (m, GR.C_VISIT, GR.C_SCALE, n_rows, n_rows)
+    assert (gm["m"], gm["c_visit"], gm["c_scale"], gm["searches"], gm["rows"]) == (m, c_visit, c_scale, n_rows, n_rows)
 
 
 # ---------------------------------------------------------------- the playout cap: flags and reads
