@@ -27,7 +27,9 @@ SYMBOLS = [
     "dbaz_selfplay_start", "dbaz_selfplay_set_start", "dbaz_selfplay_script", "dbaz_selfplay_fastforward", "dbaz_selfplay_stagger", "dbaz_selfplay_quickplay",
     "dbaz_selfplay_set_playout_cap", "dbaz_get_playout_cap", "dbaz_playout_cap_is_full",
     "dbaz_selfplay_set_forced_playouts", "dbaz_get_forced_playouts", "dbaz_prune_visits", "dbaz_fetch_row_flags",
-    "dbaz_selfplay_set_gumbel", "dbaz_get_gumbel", "dbaz_gumbel_considered", "dbaz_gumbel_target", "dbaz_step", "dbaz_run",
+    "dbaz_selfplay_set_gumbel", "dbaz_get_gumbel", "dbaz_gumbel_considered", "dbaz_gumbel_target",
+    "dbaz_selfplay_set_gumbel_mode", "dbaz_get_gumbel_mode", "dbaz_gumbel_improved_policy", "dbaz_gumbel_nonroot_pick", "dbaz_gumbel_target_full",
+    "dbaz_step", "dbaz_run",
     "dbaz_get_counters", "dbaz_timing_begin", "dbaz_timing_end", "dbaz_fetch_samples", "dbaz_replay_rows_dev",
     "dbaz_replay_rows_clear", "dbaz_dataset_select", "dbaz_dataset_begin", "dbaz_dataset_add_rows", "dbaz_dataset_finish", "dbaz_dataset_fetch", "dbaz_dataset_batch", "dbaz_dataset_batch_on",
     "dbaz_symmetry_apply", "dbaz_symmetry_table",
@@ -164,6 +166,10 @@ def load():
     L.dbaz_get_gumbel.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64)]
     L.dbaz_gumbel_considered.argtypes = [i32, i32, vp]
     L.dbaz_gumbel_target.argtypes = [i32, C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    L.dbaz_selfplay_set_gumbel_mode.argtypes = [vp, i32]
+    L.dbaz_get_gumbel_mode.argtypes = [vp, C.POINTER(i32)]
+    for f in (L.dbaz_gumbel_improved_policy, L.dbaz_gumbel_nonroot_pick, L.dbaz_gumbel_target_full):
+        f.argtypes = [i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.dbaz_step.argtypes = [vp, i32]
     L.dbaz_run.argtypes = [vp, i64]
     L.dbaz_get_counters.argtypes = [vp, C.POINTER(Counters)]

@@ -43,6 +43,8 @@ struct dbaz_engine {
     ReadCaps read_caps = {{0, 0}, {0, 0}};
     PlayoutCap playout = {4294967296ull, 0, 0}; // dbaz_selfplay_set_playout_cap (off)
     double playout_prob = 1.0;                  // full_prob as the caller gave it
+    int gumbel_full = 0; // dbaz_selfplay_set_gumbel_mode: 1 = the rule below the root and the full v_mix too; looked at while sc.gumbel_m > 0.
+                         // The launchers pick the kernels' instantiation by it; the kernels' arguments do not change
     EndgameStart eg_start = {nullptr, {0, 0}};
     size_t eg_stride = 0; // bytes per slot of eg_tables as allocated: every attached handle must have this stride
     int eg_max_free = 0;  // the largest max_free attached so far: no header claims more compact edges, and 2^eg_max_free <= eg_stride
@@ -733,7 +735,7 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
     if (with_driver) {
-        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
+        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout}, e->gumbel_full);
         endgame_solve_tables(e, s);
     }
     tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
@@ -771,7 +773,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
         HIP_CHECK_RET(e, hipEventRecord(e->ev_fork, s));
         HIP_CHECK_RET(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
+        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout}, e->gumbel_full);
         // the searches this pass starts do not select in this step; the join below orders their tables before the next k_select
         endgame_solve_tables(e, e->stream2);
         HIP_CHECK_RET(e, hipEventRecord(e->ev_join, e->stream2));
@@ -782,7 +784,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         e->sc.eval_round = e->eval_round;
         e->sc.eval_defer_max = e->eval_defer_max;
     }
-    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots, e->G); // (the lists' counters were zeroed by the previous k_expand_backup)
+    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots, e->G, e->gumbel_full); // (the lists' counters were zeroed by the previous k_expand_backup)
     if (e->sc.eval_round > 0) tree_launch_order_evals(s, e->B, e->n_slots, e->sc.step); // the list in slot order (deterministic cut)
     const bool late_join = with_driver && e->late_join;
     if (with_driver && !late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
@@ -809,7 +811,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
     // k_select, which skipped the slots the pass starts); k_expand_backup does (it clears the pass's slot list).
     // 3x3: 11.9 -> 13.2 M expansions/s, 6x6: +1.5 %, 9x9: +2.8 % against joining in front of the network
     if (late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
-    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots, e->G);
+    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots, e->G, e->gumbel_full);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     return DBAZ_OK;
@@ -1291,7 +1293,7 @@ extern "C" int dbaz_select(dbaz_engine *e, int32_t *n_active, int16_t *leaf_x, u
     int32_t *d_na = cv.take<int32_t>(4);
     e->sc.step = (e->sc.step & 0x3FFFFFFF) + 1;
     e->sc.driver_concurrent = 0;
-    tree_launch_select(e->stream, g, e->sc, e->B, e->n_slots);
+    tree_launch_select(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs(), e->gumbel_full);
     HIP_CHECK_RET(e, hipMemsetAsync(d_na, 0, 16, e->stream));
     tree_launch_get_leaves(e->stream, g, e->B, e->n_slots, d_x, d_ne, d_na);
     HIP_CHECK_RET(e, hipGetLastError());
@@ -1317,7 +1319,7 @@ extern "C" int dbaz_expand_backup(dbaz_engine *e, const float *p, const float *v
         memcpy(padded.data() + (size_t)i * g.AS, p + (size_t)i * g.A, (size_t)g.A * 4);
     HIP_CHECK_RET(e, hipMemcpyAsync(e->B.evalP, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, e->stream));
     HIP_CHECK_RET(e, hipMemcpyAsync(e->B.evalV, v, (size_t)e->n_slots * 4, hipMemcpyHostToDevice, e->stream));
-    tree_launch_expand_backup(e->stream, g, e->sc, e->B, e->n_slots);
+    tree_launch_expand_backup(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs(), e->gumbel_full);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
@@ -1639,6 +1641,29 @@ extern "C" int dbaz_get_gumbel(dbaz_engine *e, int32_t *m, double *c_visit, doub
     return DBAZ_OK;
 }
 
+extern "C" int dbaz_selfplay_set_gumbel_mode(dbaz_engine *e, int32_t mode)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (mode != 0 && mode != 1) return set_error(e, DBAZ_EINVAL, "mode = %d is neither 0 (the rule at the root) nor 1 (full)", mode);
+    if (e->selfplay) {
+        // the launchers read the setting at every step: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
+    }
+    e->gumbel_full = mode;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_get_gumbel_mode(dbaz_engine *e, int32_t *mode)
+{
+    if (!e) return DBAZ_EINVAL;
+    if (mode) *mode = e->gumbel_full;
+    return DBAZ_OK;
+}
+
 extern "C" int dbaz_gumbel_considered(int32_t m_eff, int32_t R, int32_t *out)
 {
     if (m_eff < 0 || m_eff > DBAZ_MAX_A || R < 0 || (R > 0 && !out)) return DBAZ_EINVAL;
@@ -1653,6 +1678,38 @@ extern "C" int dbaz_gumbel_target(int32_t n_actions, double c_visit, double c_sc
         !(c_scale > 0.0 && c_scale <= GUMBEL_C_SCALE_MAX) || !P || !W || !n_and_sign || !valid || !out)
         return DBAZ_EINVAL;
     gumbel_target_row(n_actions, c_visit, c_scale, P, W, n_and_sign, valid, out);
+    return DBAZ_OK;
+}
+
+// the full mode's rule on one node (argument checks: dbaz_gumbel_target's, and a finite v)
+static bool gumbel_node_args_ok(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                const uint32_t *n_and_sign, const uint8_t *valid, const void *out)
+{
+    return n_actions >= 1 && n_actions <= DBAZ_MAX_A && c_visit >= 0.0 && c_visit <= GUMBEL_C_VISIT_MAX && c_scale > 0.0 &&
+           c_scale <= GUMBEL_C_SCALE_MAX && v == v && v - v == 0.0 && P && W && n_and_sign && valid && out;
+}
+
+extern "C" int dbaz_gumbel_improved_policy(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                           const uint32_t *n_and_sign, const uint8_t *valid, double *pi_out)
+{
+    if (!gumbel_node_args_ok(n_actions, c_visit, c_scale, v, P, W, n_and_sign, valid, pi_out)) return DBAZ_EINVAL;
+    gumbel_policy_row(n_actions, c_visit, c_scale, true, v, P, W, n_and_sign, valid, pi_out, nullptr);
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_gumbel_nonroot_pick(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                        const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out)
+{
+    if (!gumbel_node_args_ok(n_actions, c_visit, c_scale, v, P, W, n_and_sign, valid, out)) return DBAZ_EINVAL;
+    *out = gumbel_nonroot_pick_row(n_actions, c_visit, c_scale, v, P, W, n_and_sign, valid); // -1: no valid child
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_gumbel_target_full(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                       const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out)
+{
+    if (!gumbel_node_args_ok(n_actions, c_visit, c_scale, v, P, W, n_and_sign, valid, out)) return DBAZ_EINVAL;
+    gumbel_target_row(n_actions, c_visit, c_scale, P, W, n_and_sign, valid, out, true, v);
     return DBAZ_OK;
 }
 

@@ -61,6 +61,16 @@ FORCED_HD inline double gumbel_sigma(double c_visit, double c_scale, int n_max, 
 
 FORCED_HD inline double gumbel_vmix(double num, double den) { return den != 0.0 ? num / den : 0.0; }
 
+// the full mode's mixed value of a node (dbaz_selfplay_set_gumbel_mode): anchored on v, the value the node got at its expansion;
+// S = the sum of its children's visits
+FORCED_HD inline double gumbel_vmix_full(double v, int S, double num, double den)
+{
+    return den != 0.0 ? (v + (double)S * (num / den)) / (1.0 + (double)S) : v;
+}
+
+// the full mode's score of a candidate below the root: pi'(a) - n(a) / (1 + S)
+FORCED_HD inline double gumbel_nonroot_score(double pi, int n, int S) { return pi - (double)n / (1.0 + (double)S); }
+
 // the row's count of a target probability
 FORCED_HD inline int32_t gumbel_count(double pi) { return (int32_t)floor(pi * GUMBEL_PI_ONE + 0.5); }
 
@@ -82,14 +92,15 @@ inline double gumbel_sum(const double *x, int n)
     return s[0];
 }
 
-// the whole target on one root (the host's dbaz_gumbel_target): out[i] = the row's visits of child i
-inline void gumbel_target_row(int n_actions, double c_visit, double c_scale, const double *P, const float *W, const uint32_t *ns,
-                              const uint8_t *valid, int32_t *out)
+// pi'(a) = softmax(logit + sigma(completed Q)) over the candidates of one node, 0.0 for every other child; full: the completed Q
+// of an unvisited child is the full v_mix around v, else the root-only one (v is not read).  Returns S; cand_out may be null.
+inline int gumbel_policy_row(int n_actions, double c_visit, double c_scale, bool full, double v, const double *P, const float *W,
+                             const uint32_t *ns, const uint8_t *valid, double *pi, bool *cand_out)
 {
     double a[GUMBEL_M_MAX], b[GUMBEL_M_MAX], x[GUMBEL_M_MAX];
     bool cand[GUMBEL_M_MAX];
     bool any = false;
-    int n_max = 0;
+    int n_max = 0, S = 0;
     for (int i = 0; i < n_actions; i++) {
         const int n = (int)(ns[i] & FORCED_VISITS_MASK);
         a[i] = b[i] = 0.0;
@@ -97,14 +108,17 @@ inline void gumbel_target_row(int n_actions, double c_visit, double c_scale, con
             a[i] = P[i] * forced_value(W[i], n, (ns[i] & FORCED_SAME_BIT) != 0);
             b[i] = P[i];
         }
+        S += n;
         if (valid[i] && n > n_max) n_max = n;
         if (valid[i] && P[i] > 0.0) any = true;
     }
-    const double vmix = gumbel_vmix(gumbel_sum(a, n_actions), gumbel_sum(b, n_actions));
+    const double num = gumbel_sum(a, n_actions), den = gumbel_sum(b, n_actions);
+    const double vmix = full ? gumbel_vmix_full(v, S, num, den) : gumbel_vmix(num, den);
     double M = -INFINITY;
     for (int i = 0; i < n_actions; i++) {
         const int n = (int)(ns[i] & FORCED_VISITS_MASK);
         cand[i] = valid[i] && (P[i] > 0.0 || !any);
+        if (cand_out) cand_out[i] = cand[i];
         if (!cand[i]) continue;
         const double cq = n > 0 ? forced_value(W[i], n, (ns[i] & FORCED_SAME_BIT) != 0) : vmix;
         x[i] = gumbel_logit(P[i]) + gumbel_sigma(c_visit, c_scale, n_max, cq);
@@ -112,5 +126,34 @@ inline void gumbel_target_row(int n_actions, double c_visit, double c_scale, con
     }
     for (int i = 0; i < n_actions; i++) a[i] = cand[i] ? exp(x[i] - M) : 0.0;
     const double se = gumbel_sum(a, n_actions);
-    for (int i = 0; i < n_actions; i++) out[i] = cand[i] ? gumbel_count(a[i] / se) : 0;
+    for (int i = 0; i < n_actions; i++) pi[i] = cand[i] ? a[i] / se : 0.0;
+    return S;
+}
+
+// the whole target on one root (the host's dbaz_gumbel_target and dbaz_gumbel_target_full): out[i] = the row's visits of child i
+inline void gumbel_target_row(int n_actions, double c_visit, double c_scale, const double *P, const float *W, const uint32_t *ns,
+                              const uint8_t *valid, int32_t *out, bool full = false, double v = 0.0)
+{
+    double pi[GUMBEL_M_MAX];
+    bool cand[GUMBEL_M_MAX];
+    gumbel_policy_row(n_actions, c_visit, c_scale, full, v, P, W, ns, valid, pi, cand);
+    for (int i = 0; i < n_actions; i++) out[i] = cand[i] ? gumbel_count(pi[i]) : 0;
+}
+
+// the full mode's pick below the root (the host's dbaz_gumbel_nonroot_pick): the first maximum of pi'(a) - n(a) / (1 + S) over the
+// candidates
+inline int gumbel_nonroot_pick_row(int n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                   const uint32_t *ns, const uint8_t *valid)
+{
+    double pi[GUMBEL_M_MAX];
+    bool cand[GUMBEL_M_MAX];
+    const int S = gumbel_policy_row(n_actions, c_visit, c_scale, true, v, P, W, ns, valid, pi, cand);
+    int best = -1;
+    double bs = -INFINITY;
+    for (int i = 0; i < n_actions; i++) {
+        if (!cand[i]) continue;
+        const double sc = gumbel_nonroot_score(pi[i], (int)(ns[i] & FORCED_VISITS_MASK), S);
+        if (best < 0 || sc > bs) { bs = sc; best = i; }
+    }
+    return best;
 }

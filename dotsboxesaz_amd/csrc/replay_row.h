@@ -11,6 +11,7 @@
 #define ROW_FLAG_FAST 1  //   bit 0: the row's search was a fast one (playout_cap.h): it moved the game on and is not a training target
 #define ROW_FLAG_PRUNED 2 //  bit 1: policy target pruning ran on the row (forced_playouts.h): its visits are the pruned ones
 #define ROW_FLAG_GUMBEL 4 //  bit 2: the row's search was a Gumbel search (gumbel.h): its visits are the target pi' in units of 2^-24
+#define ROW_FLAG_GUMBEL_FULL 8 // bit 3, beside bit 2: that search ran the full mode (dbaz_selfplay_set_gumbel_mode): the rule below the root too
 #define ROW_X_OFF 28    // sizeof(RowMeta)
 
 // row_bytes of a board with HW = (rows + 1) * (cols + 1) points

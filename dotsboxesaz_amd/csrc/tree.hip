@@ -25,6 +25,7 @@ static_assert(FORCED_VISITS_MASK == NS_MASK && FORCED_SAME_BIT == NS_SAME, "forc
 struct NodeMeta {
     GState st;
     int parent, move, flags, result, deepness;
+    float vhat; // load_meta<true> only (the full Gumbel mode's descent): dword 12, the value the node got at its expansion
 };
 
 __device__ __forceinline__ uint32_t *node_ptr(uint32_t *pool, const Geo &g, int idx)
@@ -32,6 +33,7 @@ __device__ __forceinline__ uint32_t *node_ptr(uint32_t *pool, const Geo &g, int 
     return pool + (size_t)idx * g.node_dw;
 }
 
+template <bool VHAT = false>
 __device__ __forceinline__ NodeMeta load_meta(uint32_t *pool, const Geo &g, int idx)
 {
     const uint32_t *nd = node_ptr(pool, g, idx);
@@ -39,6 +41,7 @@ __device__ __forceinline__ NodeMeta load_meta(uint32_t *pool, const Geo &g, int 
     const uint4 b = *reinterpret_cast<const uint4 *>(nd + 4);
     const uint4 c = *reinterpret_cast<const uint4 *>(nd + 8);
     NodeMeta m;
+    m.vhat = VHAT ? __uint_as_float(nd[12]) : 0.0f;
     m.st.e0 = (uint64_t)a.x | ((uint64_t)a.y << 32);
     m.st.e1 = (uint64_t)a.z | ((uint64_t)a.w << 32);
     m.st.e2 = (uint64_t)b.x | ((uint64_t)b.y << 32);
@@ -415,7 +418,7 @@ __device__ void gumbel_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &
 // root prior renormalisation + Dirichlet mix, mcts.py:211-226 (wave-cooperative)
 // ------------------------------------------------------------------------------------
 // GUMBEL: the instantiation a handle with the Gumbel rule on launches (gumbel.h); false compiles every trace of the rule out
-template <bool GUMBEL>
+template <int GUMBEL>
 __device__ __forceinline__ void root_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                           uint32_t *pool, float *ldsf, double *ldsd, int lane)
 {
@@ -531,7 +534,7 @@ __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, c
 // UCT_search prologue (mcts.py:205-226) for one slot; num_reads < 0 = driver rule
 // kind: SEARCH_FAST = a fast search of the playout cap, SEARCH_FORCED / SEARCH_PRUNE = forced playouts at the root and a pruned
 // row (start_move_search decides; explicit searches are of kind 0)
-template <bool GUMBEL>
+template <int GUMBEL>
 __device__ __forceinline__ void begin_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                              uint32_t *pool, int num_reads, const StartArgs &sa, float *ldsf, double *ldsd, int lane, int kind = 0)
 {
@@ -691,7 +694,9 @@ __device__ __forceinline__ void write_features(const Geo &g, const GState &st, f
 // rows as the descent holds them, rp: its float64 priors.  Four butterfly reductions (t, n_max and the two sums of v_mix) and the
 // argmax; the sums run in the rule's order -- this lane's children in index order, then o = 32 .. 1.  The child found gets
 // FORCED_PRIOR in rp, and the root level's pb_c terms become 1, under which that child's score is beyond every other one.
-template <int NPL>
+// FULL (dbaz_selfplay_set_gumbel_mode): v_mix is the full one, around the root's own value m.vhat (load_meta<true>) with S, the sum
+// of the children's visits, riding in the same butterfly.
+template <int NPL, bool FULL>
 __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const NodeMeta &m,
                                                  const NodeRows<NPL> &R, double (&rp)[NPL], double &pbc_cur, double &sq_cur, int lane)
 {
@@ -702,7 +707,7 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
     const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
     double gl[NPL];
     int nsr[NPL]; // n_s, the visits of this search
-    int t = 0, n_max = 0;
+    int t = 0, n_max = 0, Sn = 0;
     double num = 0.0, den = 0.0;
 #pragma unroll
     for (int j = 0; j < NPL; j++) {
@@ -713,19 +718,21 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
         gl[j] = in ? glrow[i] : -INFINITY;
         nsr[j] = in ? n - n0row[i] : 0;
         t += nsr[j];
+        if (FULL) Sn += n;
         n_max = (valid && n > n_max) ? n : n_max;
         num = num + (n > 0 ? rp[j] * forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : 0.0);
         den = den + (n > 0 ? rp[j] : 0.0);
     }
     for (int o = 32; o > 0; o >>= 1) {
         t += __shfl_xor(t, o);
+        if (FULL) Sn += __shfl_xor(Sn, o);
         n_max = max(n_max, __shfl_xor(n_max, o));
         num = num + __shfl_xor(num, o);
         den = den + __shfl_xor(den, o);
     }
     t = __builtin_amdgcn_readfirstlane(t);
     n_max = __builtin_amdgcn_readfirstlane(n_max);
-    const double vmix = gumbel_vmix(num, den);
+    const double vmix = FULL ? gumbel_vmix_full((double)m.vhat, Sn, num, den) : gumbel_vmix(num, den);
     int cv = gumbel_considered(m_eff, reads, t);
     // gl + sigma of the candidates at cv visits of this search, -inf for every other child
     double sc[NPL], mx;
@@ -760,15 +767,79 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
     sq_cur = 1.0;
 }
 
+// A level below the root in the full mode of a Gumbel search (dbaz_selfplay_set_gumbel_mode; the rule is in include/dbaz.h): the
+// score pi'(a) - n(a) / (1 + S) of this lane's children, -inf for every child that is no candidate.  R: the node's rows as the
+// descent holds them, m.vhat: its own value (load_meta<true>).  Three butterfly reductions -- S, n_max and the two sums of v_mix
+// fused, then M, then the sum of e -- in the rule's order; the descent's first-maximum argmax follows on sc.
+template <int NPL>
+__device__ __forceinline__ void gumbel_inner_scores(const Geo &g, const SearchCfg &cfg, const NodeMeta &m, const NodeRows<NPL> &R,
+                                                    double (&sc)[NPL], int lane)
+{
+    const int A = g.A;
+    const uint64_t ew[4] = {m.st.e0, m.st.e1, m.st.e2, m.st.e3};
+    int Sn = 0, n_max = 0;
+    double num = 0.0, den = 0.0;
+    bool pos = false;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const bool valid = lane + WAVE * j < A && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
+        const int n = (int)(R.NS[j] & NS_MASK);
+        const double P = (double)R.P[j];
+        Sn += n;
+        n_max = (valid && n > n_max) ? n : n_max;
+        num = num + (n > 0 ? P * forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : 0.0);
+        den = den + (n > 0 ? P : 0.0);
+        pos = pos || (valid && P > 0.0);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        Sn += __shfl_xor(Sn, o);
+        n_max = max(n_max, __shfl_xor(n_max, o));
+        num = num + __shfl_xor(num, o);
+        den = den + __shfl_xor(den, o);
+    }
+    Sn = __builtin_amdgcn_readfirstlane(Sn);
+    n_max = __builtin_amdgcn_readfirstlane(n_max);
+    const bool any = __ballot(pos) != 0ull;
+    const double vmix = gumbel_vmix_full((double)m.vhat, Sn, num, den);
+    double M = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const bool valid = lane + WAVE * j < A && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
+        const int n = (int)(R.NS[j] & NS_MASK);
+        const double P = (double)R.P[j];
+        const bool cand = valid && (P > 0.0 || !any);
+        const double cq = n > 0 ? forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : vmix;
+        sc[j] = cand ? gumbel_logit(P) + gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, cq) : -INFINITY;
+        M = fmax(M, sc[j]);
+    }
+    for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
+    double se = 0.0;
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        sc[j] = sc[j] > -INFINITY ? exp(sc[j] - M) : 0.0; // e(a); 0 for a non-candidate, told apart again below by its validity
+        se = se + sc[j];
+    }
+    for (int o = 32; o > 0; o >>= 1) se = se + __shfl_xor(se, o);
+#pragma unroll
+    for (int j = 0; j < NPL; j++) {
+        const bool valid = lane + WAVE * j < A && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
+        const int n = (int)(R.NS[j] & NS_MASK);
+        const bool cand = valid && ((double)R.P[j] > 0.0 || !any);
+        sc[j] = cand ? gumbel_nonroot_score(sc[j] / se, n, Sn) : -INFINITY;
+    }
+}
+
 struct Leaf {
     int cur, depth, in_move, err;
     int root_to_play;
     NodeMeta m;
 };
 
-// GUMBEL = false (a handle with the Gumbel rule off, and the K-pending search, which the rule never reaches) compiles the Gumbel
-// pre-pass out: the descent is then the parent's, instruction for instruction.
-template <int NPL, bool GUMBEL>
+// GUMBEL = 0 (a handle with the Gumbel rule off, and the K-pending search, which the rule never reaches) compiles the Gumbel
+// pre-pass out: the descent is then the parent's, instruction for instruction.  1: the rule at the root level.  2: the full mode
+// (dbaz_selfplay_set_gumbel_mode) -- the root level's v_mix is the full one, and every level below the root scores its children by
+// gumbel_inner_scores instead of the UCB; 0 and 1 hold no trace of that.
+template <int NPL, int GUMBEL>
 __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool,
                                         PoolState &q, PathEnt *path, const unsigned vv, int lane)
 {
@@ -778,7 +849,9 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     int cur = root, depth = 0, err = 0;
     const int root_N = S->root_N;
     const int kind = S->fast_search; // requested beside root_N, looked at once the root's rows are on their way
-    NodeMeta m = load_meta(pool, g, root);
+    // (full mode: the root's own value comes with its meta block.  A root made by tree reuse was expanded earlier in the same game
+    // under the same setting -- the setters are refused while games are being played -- so k_expand_backup<2> has left it there)
+    NodeMeta m = load_meta<GUMBEL == 2>(pool, g, root);
     NodeRows<NPL> R;
     load_rows<NPL>(R, pool, g, root, lane);
     double pbc_cur, sq_cur;
@@ -794,7 +867,9 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     // the forced pre-pass below does, through rp; it also makes the root level's pb_c a plain 1 / (n + 1) > 0, since a re-used root
     // starts its search at N = 0, where sqrt(N) would wipe FORCED_PRIOR out.  (Such a handle has no forced playouts.)
     if (GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) && is_inner(m.flags))
-        gumbel_root_pick<NPL>(g, cfg, B, slot, m, R, rp, pbc_cur, sq_cur, lane);
+        gumbel_root_pick<NPL, GUMBEL == 2>(g, cfg, B, slot, m, R, rp, pbc_cur, sq_cur, lane);
+    // full mode: the levels below the root of such a search take the rule's pick, not the UCB's
+    const bool ginner = GUMBEL == 2 && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) != 0;
     // forced playouts (forced_playouts.h): on for a full search of the self-play driver, and at the root level only
     const bool forced = !GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_FORCED) != 0;
     if (forced && is_inner(m.flags)) {
@@ -836,6 +911,9 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
         uint32_t bns = 0;
         int bc = -1;
         bool have = false;
+        double gsc[NPL]; // full Gumbel mode, below the root: the rule's scores in place of the UCB's
+        const bool gpick = GUMBEL == 2 && ginner && cur != root;
+        if (GUMBEL == 2 && gpick) gumbel_inner_scores<NPL>(g, cfg, m, R, gsc, lane);
 #pragma unroll
         for (int j = 0; j < NPL; j++) {
             const int i = lane + WAVE * j;
@@ -853,7 +931,7 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
             const double score = prior_score + value_score;
             const bool valid = in && !(((ew[j] | g.sentinel[j]) >> lane) & 1ull);
             const double inval = valid ? 0.0 : 1.0;
-            const double x = -1e12 * inval + score; // best_child, mcts.py:101-103
+            const double x = (GUMBEL == 2 && gpick) ? gsc[j] : -1e12 * inval + score; // best_child, mcts.py:101-103
             // numpy argmax order inside the lane: first maximum, a NaN already held wins
             const bool take = in && (!have || (bx == bx && !(x <= bx)));
             bx = take ? x : bx;
@@ -910,7 +988,7 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
             }
             init_node(pool, g, child, st, cur, bi, m.deepness + 1, lane);
             NodeMeta cm;
-            cm.st = st; cm.parent = cur; cm.move = bi;
+            cm.st = st; cm.parent = cur; cm.move = bi; cm.vhat = 0.0f;
             cm.result = gs_result(st);
             cm.flags = (cm.result != DBAZ_RESULT_NONE) ? NF_TERMINAL : 0;
             cm.deepness = m.deepness + 1;
@@ -920,11 +998,11 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
         // everything the next level needs is requested at once: the child's pb_c / sqrt terms (its visit count is
         // already known from this node's N row), its meta block and its four rows
         const int nchild = (int)(bns & NS_MASK);
-        double pbc_nx, sq_nx;
-        select_tab(cfg, B, nchild, pbc_nx, sq_nx);
-        NodeMeta cm = load_meta(pool, g, child);
+        double pbc_nx = 0.0, sq_nx = 0.0;
+        if (!(GUMBEL == 2 && ginner)) select_tab(cfg, B, nchild, pbc_nx, sq_nx); // (the full mode's levels below the root need no pb_c terms)
+        NodeMeta cm = load_meta<GUMBEL == 2>(pool, g, child);
         load_rows<NPL>(R, pool, g, child, lane); // rows of an unexpanded node are ignored
-        select_tab_fix(cfg, nchild, pbc_nx, sq_nx);
+        if (!(GUMBEL == 2 && ginner)) select_tab_fix(cfg, nchild, pbc_nx, sq_nx);
         if (lane == owner) {
             if (vv) NSrow[bi] = bns + 1u;                       // the visit of the edge into `child`, counted now
             if (is_inner(cm.flags)) Wrow[bi] = bw - 1.0f;      // VIRTUAL_LOSS on the node being left next iteration
@@ -1001,7 +1079,7 @@ __device__ __forceinline__ bool endgame_slot_waits(const SearchCfg &cfg, const E
 }
 
 // returns the route of this game's leaf (ROUTE_NONE: of no leaf, or of one that goes on no list), or SEL_DEFERRED
-template <int NPL, bool GUMBEL>
+template <int NPL, int GUMBEL>
 __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, const EndgameBufs &G, int slot, int lane)
 {
     Slot *S = B.slots + slot;
@@ -1099,7 +1177,7 @@ __device__ __forceinline__ int select_one(const Geo &g, const SearchCfg &cfg, co
 // ev_class[slot] for k_order_evals -- so nothing is left to share between the games of a workgroup: no LDS counters, no barrier,
 // and a game's registers are free the moment ITS descent ends instead of when the deepest of sixteen does.  The rare leaf of
 // ROUTE_TABLE or the leaf solver goes onto its list with the wave's own atomic.
-template <int NPL, bool ONE, bool GUMBEL>
+template <int NPL, bool ONE, int GUMBEL>
 __global__ void __launch_bounds__(ONE ? WAVE : WAVE * SELECT_WAVES) k_select(Geo g, SearchCfg cfg, TreeBufs B, int n_slots, EndgameBufs G)
 {
     if (ONE) {
@@ -1418,7 +1496,7 @@ __device__ __forceinline__ void count_sim(Slot *S, int term, bool served, bool e
 }
 
 // a slot's step ends: the root expansion (uncounted, mcts.py:207-208) hands over to the simulations, `sims` of which are done otherwise
-template <bool GUMBEL>
+template <int GUMBEL>
 __device__ __forceinline__ void end_step(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S, uint32_t *pool, int phase,
                                          int sims, float *ldsf, double *ldsd, int lane)
 {
@@ -1487,7 +1565,7 @@ __global__ void __launch_bounds__(WAVE) k_expand_backup_multi(Geo g, SearchCfg c
 // Four waves per SIMD (second launch bound: at most 128 registers), so that 8 192 slots are two rounds of one-wave workgroups
 // instead of 2.67.  What does not fit is the float64 pow / log / cos of the Dirichlet sampler inlined through end_step ->
 // root_prep -> rng_gamma: the allocator spills there, once per move, and nowhere on the path of an ordinary simulation.
-template <bool GUMBEL>
+template <int GUMBEL>
 __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg, TreeBufs B, EndgameBufs G)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1530,6 +1608,8 @@ __global__ void __launch_bounds__(WAVE, 4) k_expand_backup(Geo g, SearchCfg cfg,
         } else {
             v = expand_priors(g, lm.st, ev, eg, B.evalP + (size_t)slot * g.AS, B.evalV + slot, Prow, ldsf, lane);
         }
+        // full Gumbel mode: every expanded node keeps its value there, with or without a table -- the descent's v_mix reads it
+        if (GUMBEL == 2 && !B.tt && lane == 0) nd[12] = __float_as_uint(v);
         if (B.tt && lane == 0) {
             nd[12] = __float_as_uint(v); // a later twin reads the value here
             if (hit < 0 && !eg) {
@@ -1797,7 +1877,7 @@ __device__ bool try_emit(const Geo &g, const TreeBufs &B, int slot, Slot *S, uin
     return true;
 }
 
-template <bool GUMBEL>
+template <int GUMBEL>
 __device__ __forceinline__ void start_move_search(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, Slot *S,
                                   uint32_t *pool, const StartArgs &sa, float *ldsf, double *ldsd, int lane)
 {
@@ -1830,7 +1910,7 @@ __device__ __forceinline__ void start_move_search(const Geo &g, const SearchCfg 
 }
 
 
-template <bool GUMBEL>
+template <int GUMBEL>
 __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -1859,6 +1939,10 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
 // The end of a Gumbel search (gumbel.h; the rule is in include/dbaz.h), everything read after the search: the move -- the first
 // maximum of gl + sigma over the candidates with the most visits of this search -- is returned, and rv (if not null) gets the
 // row's visits, softmax(logit + sigma) over the candidates in units of 2^-24.  One wave; the sums run in the rule's order.
+// FULL (dbaz_selfplay_set_gumbel_mode): v_mix is the full one around the root's own value, dword 12 of its meta block.  It is always
+// there: the root was expanded by k_expand_backup<2> in this game, as a root or -- under tree reuse -- as an inner node earlier on,
+// since the setters are refused while games are being played.
+template <bool FULL>
 __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, uint32_t *pool, int root, const NodeMeta &rm,
                              int32_t *rv, double *ldsd, int lane)
 {
@@ -1868,11 +1952,12 @@ __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     const double *rprior = B.root_prior + (size_t)slot * g.AS;
     const double *gl = B.gumbel_gl + (size_t)slot * g.AS;
     const int32_t *n0 = B.gumbel_n0 + (size_t)slot * g.AS;
-    int n_max = 0, ns_max = -1;
+    int n_max = 0, ns_max = -1, Sn = 0;
     double num = 0.0, den = 0.0;
     for (int i = lane; i < A; i += WAVE) {
         const uint32_t ns = NS0[i];
         const int n = (int)(ns & NS_MASK);
+        if (FULL) Sn += n;
         if (gs_valid(g, rm.st, i) && n > n_max) n_max = n;
         if (gl[i] > -INFINITY && n - n0[i] > ns_max) ns_max = n - n0[i];
         num = num + (n > 0 ? rprior[i] * forced_value(W0[i], n, (ns & NS_SAME) != 0) : 0.0);
@@ -1881,10 +1966,11 @@ __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs 
     for (int o = 32; o > 0; o >>= 1) {
         n_max = max(n_max, __shfl_xor(n_max, o));
         ns_max = max(ns_max, __shfl_xor(ns_max, o));
+        if (FULL) Sn += __shfl_xor(Sn, o);
         num = num + __shfl_xor(num, o);
         den = den + __shfl_xor(den, o);
     }
-    const double vmix = gumbel_vmix(num, den);
+    const double vmix = FULL ? gumbel_vmix_full((double)__uint_as_float(node_ptr(pool, g, root)[12]), Sn, num, den) : gumbel_vmix(num, den);
     // the move, and x = logit + sigma with its maximum
     double bs = -INFINITY, M = -INFINITY;
     int bi = 0x7fffffff;
@@ -1928,7 +2014,7 @@ __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs 
 // here leaves the slot in PH_NEWGAME until the next pass.
 // (the slots come from k_driver_scan's list: a step in which no slot needs the driver costs two tiny launches instead
 // of one workgroup per game squeezing in between the network's workgroups)
-template <bool GUMBEL>
+template <int GUMBEL>
 __device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const StartArgs &sa, float *ldsf,
                             double *ldsd, int lane)
 {
@@ -1978,7 +2064,7 @@ __device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, 
     if (GUMBEL && gumbel) {
         // Gumbel root search (gumbel.h): the move by the rule -- no temperature, the move-draw stream is not consumed -- unless a
         // scripted one wins, and the row's visits, which are the target pi'
-        const int gmv = gumbel_finish(g, cfg, B, slot, pool, root, rm, r < rcap ? B.row_vis + ((size_t)slot * rcap + r) * A : nullptr, ldsd, lane);
+        const int gmv = gumbel_finish<GUMBEL == 2>(g, cfg, B, slot, pool, root, rm, r < rcap ? B.row_vis + ((size_t)slot * rcap + r) * A : nullptr, ldsd, lane);
         if (mv < 0) mv = gmv;
     }
     if (mv < 0) {
@@ -2073,7 +2159,7 @@ __device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, 
             mm.q_value = S->root_W / (float)(1 + S->root_N); // TreeRoot.get_tree_stats, mcts.py:33-36
             mm.player = (int8_t)rm.st.to_play;
             mm.z = 0;
-            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0) | (gumbel ? ROW_FLAG_GUMBEL : 0);
+            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0) | (gumbel ? ROW_FLAG_GUMBEL | (GUMBEL == 2 ? ROW_FLAG_GUMBEL_FULL : 0) : 0);
             B.row_meta[(size_t)slot * rcap + r] = mm;
         }
         S->n_rows = r + 1;
@@ -2166,7 +2252,7 @@ __global__ void __launch_bounds__(SCAN_T) k_driver_scan(SearchCfg cfg, TreeBufs 
     }
 }
 
-template <bool GUMBEL>
+template <int GUMBEL>
 __global__ void __launch_bounds__(WAVE) k_advance_auto(Geo g, SearchCfg cfg, TreeBufs B, StartArgs sa)
 {
     __shared__ float ldsf[DBAZ_MAX_A];
@@ -2360,7 +2446,7 @@ void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, c
 {
     hipLaunchKernelGGL(k_search_begin, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, num_reads_dev, sa);
 }
-template <bool GUMBEL>
+template <int GUMBEL>
 static void launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     const int npl = (g.A + WAVE - 1) / WAVE;
@@ -2381,11 +2467,13 @@ static void launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const
     default: hipLaunchKernelGGL((k_select<4, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
     }
 }
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G, int gumbel_full)
 {
-    // a handle with the Gumbel rule on launches the instantiations that hold its root pre-pass; every other handle the ones without
-    if (c.gumbel_m > 0) launch_select<true>(s, g, c, B, n_slots, G);
-    else launch_select<false>(s, g, c, B, n_slots, G);
+    // a handle with the Gumbel rule on launches the instantiations that hold its root pre-pass (in the full mode, those that hold the
+    // rule below the root too); every other handle the ones without
+    if (c.gumbel_m > 0 && gumbel_full) launch_select<2>(s, g, c, B, n_slots, G);
+    else if (c.gumbel_m > 0) launch_select<1>(s, g, c, B, n_slots, G);
+    else launch_select<0>(s, g, c, B, n_slots, G);
 }
 void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
@@ -2400,11 +2488,12 @@ void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCf
 {
     hipLaunchKernelGGL(k_expand_backup_multi, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
-void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
+void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G, int gumbel_full)
 {
     // (a handle with the Gumbel rule on launches the instantiations that hold it; every other handle the ones without a trace of it)
-    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_expand_backup<true>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
-    else hipLaunchKernelGGL(k_expand_backup<false>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    if (c.gumbel_m > 0 && gumbel_full) hipLaunchKernelGGL(k_expand_backup<2>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    else if (c.gumbel_m > 0) hipLaunchKernelGGL(k_expand_backup<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    else hipLaunchKernelGGL(k_expand_backup<0>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                const int16_t *moves_dev, const int32_t *offsets_dev)
@@ -2418,8 +2507,9 @@ void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c,
 }
 void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
-    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_selfplay_start<true>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
-    else hipLaunchKernelGGL(k_selfplay_start<false>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
+    // (the start of a search is the same in both modes of the rule)
+    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_selfplay_start<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
+    else hipLaunchKernelGGL(k_selfplay_start<0>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
 {
@@ -2427,13 +2517,14 @@ void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int 
     if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_order_evals<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
     else hipLaunchKernelGGL(k_order_evals<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
 }
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa, int gumbel_full)
 {
     hipLaunchKernelGGL(k_driver_flags, dim3((n_slots + WAVE - 1) / WAVE), dim3(WAVE), 0, s, B, n_slots);
     if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_driver_scan<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
     else hipLaunchKernelGGL(k_driver_scan<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
-    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_advance_auto<true>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
-    else hipLaunchKernelGGL(k_advance_auto<false>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    if (c.gumbel_m > 0 && gumbel_full) hipLaunchKernelGGL(k_advance_auto<2>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    else if (c.gumbel_m > 0) hipLaunchKernelGGL(k_advance_auto<1>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    else hipLaunchKernelGGL(k_advance_auto<0>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,

@@ -59,7 +59,7 @@ class Engine:
     forced_playouts=(k, prune): forced playouts and policy target pruning at the root of the self-play driver's full searches
     (selfplay_set_forced_playouts); None: off.
     gumbel=(m, c_visit, c_scale): Gumbel root search in every search of the self-play driver (selfplay_set_gumbel; the usual setting
-    is (16, 50.0, 1.0)); None: off.
+    is (16, 50.0, 1.0)); None: off.  gumbel=(m, c_visit, c_scale, True): the full mode -- the rule below the root too.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -524,7 +524,7 @@ class Engine:
         self._ck(self._L.dbaz_get_forced_playouts(self.h, C.byref(k), C.byref(p), C.byref(a), C.byref(b)))
         return dict(k=float(k.value), prune=bool(p.value), rows_pruned=int(a.value), visits_pruned=int(b.value))
 
-    def selfplay_set_gumbel(self, m=16, c_visit=50.0, c_scale=1.0):
+    def selfplay_set_gumbel(self, m=16, c_visit=50.0, c_scale=1.0, full=False):
         """dbaz_selfplay_set_gumbel: the Gumbel root search (Danihelka et al., ICLR 2022) for every later selfplay_start.  Every
         search of the self-play driver, full or fast, samples its candidates by Gumbel-top-m, spends its reads by sequential
         halving and records softmax(logits + sigma(completed Q)) as the row's target: visits = round(pi' * 2^24), bit 2 of "pad"
@@ -532,15 +532,34 @@ class Engine:
         selfplay_script is the search's g.  m = 0: off (the default).  The rule is stated in full in include/dbaz.h;
         gumbel.considered_visits and gumbel.target are its host mirrors.  DbazError: EINVAL for m outside [0, 256], c_visit outside
         [0, 1e6], c_scale outside (0, 1e3], a match_play handle, selfplay_pending or forced playouts on; ESTATE while games are
-        being played; a failed call changes nothing."""
+        being played; a failed call changes nothing.
+        full=True (dbaz_selfplay_set_gumbel_mode, looked at while m > 0): the paper's "Full Gumbel" -- below the root every level takes
+        argmax pi'(a) - n(a) / (1 + sum n) instead of the UCB's pick, and unvisited children are completed with the full v_mix around
+        the node's own value; the rows carry bit 3 beside bit 2 (fetch_samples()["gumbel_full"]).  gumbel.improved_policy,
+        gumbel.nonroot_pick and gumbel.target(..., v=) are its host mirrors.  The mode is set only once (m, c_visit, c_scale) was
+        accepted, and a mode the handle refuses leaves those as they were."""
+        mode, m0, cv0, cs0 = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        self._ck(self._L.dbaz_get_gumbel_mode(self.h, C.byref(mode)))
+        self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(m0), C.byref(cv0), C.byref(cs0), None, None))  # the setting alone: no device work
         self._ck(self._L.dbaz_selfplay_set_gumbel(self.h, int(m), C.c_double(float(c_visit)), C.c_double(float(c_scale))))
+        if bool(full) != bool(mode.value):
+            try:
+                self._ck(self._L.dbaz_selfplay_set_gumbel_mode(self.h, 1 if full else 0))
+            except _lib.DbazError:
+                self._L.dbaz_selfplay_set_gumbel(self.h, m0, cv0, cs0)
+                raise
 
     def gumbel(self):
         """dbaz_get_gumbel: dict(m, c_visit, c_scale, searches, rows) -- the setting (0, 0.0, 0.0 when off) and the Gumbel searches
-        started and rows written since the last selfplay_start, after the queued work is done."""
-        m, cv, cs, a, b = C.c_int32(), C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        started and rows written since the last selfplay_start, after the queued work is done.  On a handle with the full mode on
+        (dbaz_get_gumbel_mode) the dict also has full=True; a handle in the root-only mode reports what it always did."""
+        m, cv, cs, a, b, mode = C.c_int32(), C.c_double(), C.c_double(), C.c_int64(), C.c_int64(), C.c_int32()
         self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(m), C.byref(cv), C.byref(cs), C.byref(a), C.byref(b)))
-        return dict(m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value), searches=int(a.value), rows=int(b.value))
+        self._ck(self._L.dbaz_get_gumbel_mode(self.h, C.byref(mode)))
+        out = dict(m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value), searches=int(a.value), rows=int(b.value))
+        if mode.value:
+            out["full"] = True
+        return out
 
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
@@ -620,6 +639,10 @@ class Engine:
         self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(gm), None, None, None, None))  # the setting alone: no device work
         if gm.value or (flags & 4).any():
             out["gumbel"] = (flags & 4) != 0  # ROW_FLAG_GUMBEL: visits are the target pi' in units of 2^-24
+        mode = C.c_int32()
+        self._ck(self._L.dbaz_get_gumbel_mode(self.h, C.byref(mode)))
+        if (gm.value and mode.value) or (flags & 8).any():
+            out["gumbel_full"] = (flags & 8) != 0  # ROW_FLAG_GUMBEL_FULL: the search ran the rule below the root too
         return out
 
     def _fetch_once(self):

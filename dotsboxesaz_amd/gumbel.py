@@ -10,13 +10,21 @@ need.  The rule is stated in full in include/dbaz.h; its host mirrors (no device
     considered_visits(m_eff, R)                       the sequence of considered visits (dbaz_gumbel_considered)
     target(c_visit, c_scale, P, W, n, same, valid)    the row's visits of a root (dbaz_gumbel_target)
 
+Engine(gumbel=(m, c_visit, c_scale, True)) -- "full": True in the params -- is the paper's "Full Gumbel": every level below the root
+takes argmax pi'(a) - n(a) / (1 + sum n) instead of the UCB's pick, and unvisited children are completed with the full v_mix around
+the node's own value v (bit 3 of "pad" beside bit 2; fetch_samples()["gumbel_full"]).  Its host mirrors:
+
+    improved_policy(c_visit, c_scale, v, P, W, n, same, valid)    pi' of a node, float64 [A] (dbaz_gumbel_improved_policy)
+    nonroot_pick(c_visit, c_scale, v, P, W, n, same, valid)       the child a simulation takes below the root (dbaz_gumbel_nonroot_pick)
+    target(..., v=v)                                              the row's visits with the full v_mix (dbaz_gumbel_target_full)
+
 What the rule does to playing strength per GPU-hour has not been measured here.
 
     python -m dotsboxesaz_amd.gumbel --rows 6 --cols 6 --bench 8192 --slots 8192 --reads 32,64,100 [--full-prob 0.25 --fast-reads 100]
 
 plays the same game indices with a random-init ResNetZero with PUCT at --puct-reads and with the Gumbel root at each read count,
-in one process, and prints one JSON line: per mode games/s, recorded rows/s, network evaluations per game and the mean entropy
-(nats) of the recorded pi.
+in one process, and prints one JSON line: per mode games/s, recorded rows/s, network evaluations per game, the mean entropy
+(nats) of the recorded pi and the mean max_deepness of the searches.  --full adds the full mode at each read count.
 """
 import ctypes as C
 
@@ -36,11 +44,47 @@ def considered_visits(m_eff, R):
     return out
 
 
-def target(c_visit, c_scale, P, W, n, same, valid):
+def _node_arrays(P, W, n, same, valid):
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.int64)
+    A = P.shape[0]
+    if not (P.shape == W.shape == n.shape == (A,) == np.shape(same) == np.shape(valid)) or (n < 0).any() or (n > 0x3FFFFFFF).any():
+        raise ValueError("P, W, n, same and valid are [A] arrays, n in 0 .. 2^30 - 1")
+    ns = (n.astype(np.uint32) | np.where(np.asarray(same, dtype=bool), np.uint32(0x40000000), np.uint32(0))).astype(np.uint32)
+    return A, P, W, ns, np.ascontiguousarray(np.asarray(valid, dtype=bool), dtype=np.uint8)
+
+
+def _node_call(fn, out, c_visit, c_scale, v, P, W, n, same, valid):
+    A, P, W, ns, va = _node_arrays(P, W, n, same, valid)
+    rc = fn(A, C.c_double(float(c_visit)), C.c_double(float(c_scale)), C.c_double(float(v)), P.ctypes.data, W.ctypes.data, ns.ctypes.data,
+            va.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("%s refused its arguments (A = %d, c_visit = %r, c_scale = %r, v = %r)" % (fn.__name__, A, c_visit, c_scale, v))
+    return out
+
+
+def improved_policy(c_visit, c_scale, v, P, W, n, same, valid):
+    """float64 [A]: pi' = softmax(logit + sigma(completed Q)) over the candidates of a node in the full mode (0.0 elsewhere), the
+    completed Q of an unvisited child being the full v_mix around v, the float32 value the node got at its expansion.  The other
+    arguments are those of target().  ValueError for what dbaz_gumbel_improved_policy refuses."""
+    return _node_call(_lib.load().dbaz_gumbel_improved_policy, np.zeros(len(P), dtype=np.float64), c_visit, c_scale, v, P, W, n, same, valid)
+
+
+def nonroot_pick(c_visit, c_scale, v, P, W, n, same, valid):
+    """int: the child a simulation of the full mode takes at a node below the root, the first maximum over the candidates of
+    pi'(a) - n(a) / (1 + sum n); -1 if no child is valid.  ValueError for what dbaz_gumbel_nonroot_pick refuses."""
+    return int(_node_call(_lib.load().dbaz_gumbel_nonroot_pick, np.zeros(1, dtype=np.int32), c_visit, c_scale, v, P, W, n, same, valid)[0])
+
+
+def target(c_visit, c_scale, P, W, n, same, valid, v=None):
     """int32 [A]: the visits a Gumbel row records for a root with float64 priors P, float32 child_total_value W, visit counts n,
     same[i] = child i's player to move is the root's (sgn = +1), valid[i] = child i is a legal move: floor(pi' * 2^24 + 0.5) with
-    pi' = softmax(logit + sigma(completed Q)) over the candidates.  ValueError for what dbaz_gumbel_target refuses."""
+    pi' = softmax(logit + sigma(completed Q)) over the candidates.  v given: the full mode's row (dbaz_gumbel_target_full), with the
+    full v_mix around the root's own value v.  ValueError for what dbaz_gumbel_target refuses."""
     L = _lib.load()
+    if v is not None:
+        return _node_call(L.dbaz_gumbel_target_full, np.zeros(len(P), dtype=np.int32), c_visit, c_scale, v, P, W, n, same, valid)
     P = np.ascontiguousarray(P, dtype=np.float64)
     W = np.ascontiguousarray(W, dtype=np.float32)
     n = np.ascontiguousarray(n, dtype=np.int64)
@@ -96,7 +140,8 @@ def _bench(a):
                 games = max(1, c["games_finished"])
                 runs.append(dict(games_per_s=c["games_finished"] / dt, recorded_rows_per_s=int(full.sum()) / dt,
                                  nn_evals_per_game=c["nn_evals"] / games, gumbel_rows=gm["rows"], steps=c["steps"],
-                                 pi_entropy=_entropy(got["pi"][full]), pool_resets=c["pool_resets"], seconds=dt))
+                                 pi_entropy=_entropy(got["pi"][full]), mean_max_deepness=float(np.mean(got["max_deepness"])),
+                                 pool_resets=c["pool_resets"], seconds=dt))
         eng.close()
         return {k: float(np.median([r[k] for r in runs])) for k in runs[0]}
 
@@ -106,6 +151,8 @@ def _bench(a):
         out["puct"] = play("puct %d" % a.puct_reads, a.puct_reads, None)
     for r in a.reads:
         out["gumbel_%d" % r] = play("gumbel %d" % r, r, (a.m, a.c_visit, a.c_scale))
+        if a.full:
+            out["gumbel_full_%d" % r] = play("gumbel full %d" % r, r, (a.m, a.c_visit, a.c_scale, True))
     return out
 
 
@@ -123,6 +170,7 @@ def main(argv=None):
     ap.add_argument("--m", type=int, default=DEFAULT[0], help="candidates sampled without replacement")
     ap.add_argument("--c-visit", type=float, default=DEFAULT[1])
     ap.add_argument("--c-scale", type=float, default=DEFAULT[2])
+    ap.add_argument("--full", action="store_true", help="also play the full mode (the rule below the root too) at each read count")
     ap.add_argument("--full-prob", type=float, default=1.0, help="playout cap: share of full searches (1 = no cap)")
     ap.add_argument("--fast-reads", type=int, default=100)
     ap.add_argument("--channels", type=int, default=64)

@@ -64,8 +64,10 @@ def start_moves(game_state, rows, cols):
 
 
 def _gumbel_args(gum):
-    """params.self_play.gumbel -> (m, c_visit, c_scale) with the defaults of Engine.selfplay_set_gumbel"""
-    return (int(_get(gum, "m", 16)), float(_get(gum, "c_visit", 50.0)), float(_get(gum, "c_scale", 1.0)))
+    """params.self_play.gumbel -> (m, c_visit, c_scale) with the defaults of Engine.selfplay_set_gumbel; (m, c_visit, c_scale, True)
+    with "full": True (the rule below the root too)"""
+    args = (int(_get(gum, "m", 16)), float(_get(gum, "c_visit", 50.0)), float(_get(gum, "c_scale", 1.0)))
+    return args + (True,) if bool(_get(gum, "full", False)) else args
 
 
 def engine_kwargs_from_params(params, async_searches=False):
@@ -86,7 +88,7 @@ def engine_kwargs_from_params(params, async_searches=False):
     async_searches=True and max_async_searches > 1 (self-play in waves).
     params.self_play.gumbel = {"m": 16, "c_visit": 50, "c_scale": 1.0} (the same; absent = off) becomes Engine(gumbel=(m, c_visit,
     c_scale)): the Gumbel root search, Engine.selfplay_set_gumbel.  It is refused together with forced_playouts and with self-play
-    in waves."""
+    in waves.  "full": True in that dict makes it Engine(gumbel=(m, c_visit, c_scale, True)): the rule below the root too."""
     sp = _get(params, "self_play")
     m = _get(sp, "mcts")
     noise = _get(sp, "noise", [0.0, 0.0])
@@ -276,6 +278,7 @@ assert ROW_META.itemsize == 28
 ROW_FLAGS_OFF, ROW_FLAG_FAST = 26, 1  # csrc/replay_row.h: the int16 "pad"; bit 0 = the row of a fast search of the playout cap
 ROW_FLAG_PRUNED = 2  # bit 1 = policy target pruning ran on the row: its visits (and pi) are the pruned ones
 ROW_FLAG_GUMBEL = 4  # bit 2 = the row of a Gumbel search: its visits are the target pi' in units of 2^-24 (pi = visits / visits.sum())
+ROW_FLAG_GUMBEL_FULL = 8  # bit 3, beside bit 2 = that search ran the full mode: the rule below the root too
 
 
 def full_rows_only(samples):

@@ -334,7 +334,8 @@ int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double sq, int64_
  * rule off every row is what it was.
  * Scope: with m > 0 every search that the self-play driver starts is a Gumbel search, full and fast searches of the playout cap
  * alike (a fast search still has capped reads and its row still carries bit 0).  Explicit searches (dbaz_search*, dbaz_select)
- * and match play never see the rule.  Below the root nothing changes.
+ * and match play never see the rule.  Below the root nothing changes (unless the full mode is on: dbaz_selfplay_set_gumbel_mode,
+ * below).
  * All arithmetic below is float64, every operation rounded on its own (no fused multiply-add), in the order written.
  *
  * Root preparation -- where the root's priors are prepared for such a search (at its start, or after the root's expansion):
@@ -398,6 +399,52 @@ int dbaz_get_gumbel(dbaz_engine *e, int32_t *m, double *c_visit, double *c_scale
 int dbaz_gumbel_considered(int32_t m_eff, int32_t R, int32_t *out /*[R]*/);
 int dbaz_gumbel_target(int32_t n_actions, double c_visit, double c_scale, const double *P, const float *W,
                        const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
+/* The full mode of the Gumbel search (the paper's "Full Gumbel"): the rule below the root too, and the paper's whole mixed value.
+ * dbaz_selfplay_set_gumbel_mode(e, mode) is a setting of the handle like m: mode 0 (the state after dbaz_create) is the rule at the
+ * root as stated above, mode 1 is full.  It is only looked at while m > 0; with m = 0 every row is what it was, and with mode 0
+ * every kernel, row and counter of a Gumbel handle is what it was.
+ * Same arithmetic as above: float64, every operation rounded on its own, in the order written; the sums in the sum order above.
+ *
+ * At an inner node s of a search of such a handle, the root included -- with the children's n(a), W(a), sgn(a), valid(a) and P(a) as
+ * the simulation reads them; P(a) is the float64 root prior at the root and (double) of the child's float32 prior below it:
+ *   v^(s) = (double) of the float32 value the node received when it was expanded: the network's value, a table's or the leaf
+ *     solver's exact value, or the twin's on a transposition hit -- the value of the player to move at s, as the backup takes it.
+ *   q(a) = ((double)W / (double)(1 + n)) * sgn  for n(a) > 0, as above.
+ *   S = sum_a n(a), an integer, over the children's rows (not the root's own visit count).
+ *   num = sum_{n>0} P(a) q(a),  den = sum_{n>0} P(a).
+ *   v_mix = den != 0 ? (v^ + (double)S * (num / den)) / (1.0 + (double)S) : v^.
+ *   cq(a) = q(a) for n(a) > 0, else v_mix.   n_max = the maximum of n over the valid children.
+ *   sigma(a) = ((c_visit + (double)n_max) * c_scale) * cq(a).
+ *   C(s) = the valid children with P(a) > 0; if there are none, all valid children.  logit(a) = log(P(a)) for P(a) > 0, else -1e30.
+ *   x(a) = logit(a) + sigma(a) over C(s),  M = max x,  e(a) = exp(x(a) - M),  pi'(a) = e(a) / sum e.
+ * Below the root the simulation takes the first maximum over C(s) of  pi'(a) - (double)n(a) / (1.0 + (double)S).  There is no pb_c,
+ * no sqrt, no noise and no g: the pick is deterministic and needs neither c_puct nor the log / sqrt tables.
+ * At the root, selection, the move and the row's target are exactly those stated above with this v_mix in place of the root-only
+ * one; g, n0, considered() and the halving do not change.
+ * Values are not rescaled to [0, 1] by the minimum and maximum of the tree, as mctx does it: q stays in [-1, 1] as in the root rule,
+ * so that (c_visit, c_scale) mean the same in both modes.
+ * The rows of such searches carry bit 3 of the flag word (ROW_FLAG_GUMBEL_FULL, value 8) beside bit 2.
+ * A root made by tree reuse was expanded earlier in the same game under the same setting (both setters are refused while games
+ * are being played), so its v^ is always there.
+ *
+ *   mode other than 0 or 1                                               -> DBAZ_EINVAL
+ *   games of an earlier dbaz_selfplay_start still being played           -> DBAZ_ESTATE
+ * A failed call changes nothing.  The refusals of dbaz_selfplay_set_gumbel are unchanged, so the full mode is never reached in match
+ * play, in self-play in waves or beside forced playouts; explicit searches never see the rule in either mode.
+ * dbaz_get_gumbel_mode: the setting (mode may be NULL).
+ * The rule on the host -- no handle, no device -- from the very code the kernels run, for one node with value v, priors P, W,
+ * n_and_sign and valid as for dbaz_gumbel_target:  dbaz_gumbel_improved_policy: pi_out[i] = pi'(i), 0.0 for a non-candidate;
+ * dbaz_gumbel_nonroot_pick: *out = the child a simulation takes below the root (-1 if no child is valid);
+ * dbaz_gumbel_target_full: the row's visits with the full v_mix.  Argument checks: those of dbaz_gumbel_target, and a v that is NaN
+ * or infinite -> DBAZ_EINVAL. */
+int dbaz_selfplay_set_gumbel_mode(dbaz_engine *e, int32_t mode);
+int dbaz_get_gumbel_mode(dbaz_engine *e, int32_t *mode);
+int dbaz_gumbel_improved_policy(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                                const uint32_t *n_and_sign, const uint8_t *valid, double *pi_out);
+int dbaz_gumbel_nonroot_pick(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                             const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
+int dbaz_gumbel_target_full(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
+                            const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
 int dbaz_step(dbaz_engine *e, int32_t k);             /* k simulation steps, asynchronous */
 /* until all games are finished, max_steps (if > 0) are done, or every remaining slot is
  * blocked on a full output buffer (counters.blocked_slots == active_slots: fetch and call again) */
@@ -412,7 +459,7 @@ int dbaz_fetch_samples(dbaz_engine *e, int32_t max_rows, int32_t *n_rows,
                        int16_t *x /*[rows*3HW]*/, int32_t *visits /*[rows*A]*/, double *pi /*[rows*A]*/,
                        int8_t *z, int16_t *max_deepness, int32_t *tree_size, int32_t *terminal_count,
                        float *q_value, int16_t *played);
-/* The flag words (the int16 at byte 26 of a packed row: bit 0 = row of a fast search, bit 1 = pruned visits, bit 2 = row of a Gumbel search) of the rows
+/* The flag words (the int16 at byte 26 of a packed row: bit 0 = row of a fast search, bit 1 = pruned visits, bit 2 = row of a Gumbel search, bit 3 = in the full mode) of the rows
  * dbaz_fetch_samples would hand out now, in its order.  Drains nothing: call it first.  max_rows = 0: the count alone. */
 int dbaz_fetch_row_flags(dbaz_engine *e, int32_t max_rows, int32_t *n_rows, int16_t *flags);
 /* device-resident replay rows for the RCCL all-gather (multi-GPU iteration end):
