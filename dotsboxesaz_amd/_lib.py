@@ -29,6 +29,7 @@ SYMBOLS = [
     "dbaz_selfplay_set_forced_playouts", "dbaz_get_forced_playouts", "dbaz_prune_visits", "dbaz_fetch_row_flags",
     "dbaz_selfplay_set_gumbel", "dbaz_get_gumbel", "dbaz_gumbel_considered", "dbaz_gumbel_target",
     "dbaz_selfplay_set_gumbel_mode", "dbaz_get_gumbel_mode", "dbaz_gumbel_improved_policy", "dbaz_gumbel_nonroot_pick", "dbaz_gumbel_target_full",
+    "dbaz_match_set_search", "dbaz_match_get_search",
     "dbaz_step", "dbaz_run",
     "dbaz_get_counters", "dbaz_timing_begin", "dbaz_timing_end", "dbaz_fetch_samples", "dbaz_replay_rows_dev",
     "dbaz_replay_rows_clear", "dbaz_dataset_select", "dbaz_dataset_begin", "dbaz_dataset_add_rows", "dbaz_dataset_finish", "dbaz_dataset_fetch", "dbaz_dataset_batch", "dbaz_dataset_batch_on",
@@ -168,6 +169,9 @@ def load():
     L.dbaz_gumbel_target.argtypes = [i32, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.dbaz_selfplay_set_gumbel_mode.argtypes = [vp, i32]
     L.dbaz_get_gumbel_mode.argtypes = [vp, C.POINTER(i32)]
+    L.dbaz_match_set_search.argtypes = [vp, i32, i32, i32, C.c_double, C.c_double, i32, C.c_double]
+    L.dbaz_match_get_search.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32),
+                                        C.POINTER(C.c_double)]
     for f in (L.dbaz_gumbel_improved_policy, L.dbaz_gumbel_nonroot_pick, L.dbaz_gumbel_target_full):
         f.argtypes = [i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp]
     L.dbaz_step.argtypes = [vp, i32]

@@ -63,7 +63,7 @@ struct Slot {
                              // bit 0 (SEARCH_FAST) = a fast one of the playout cap (playout_cap.h): capped reads, no root noise, its row
                              // marked; bits 1, 2 (SEARCH_FORCED, SEARCH_PRUNE; forced_playouts.h) = a full search of the self-play driver
                              // with forced playouts at its root, and its row records the pruned visits; bit 3 (SEARCH_GUMBEL; gumbel.h)
-                             // = a search of the self-play driver with the Gumbel rule at its root
+                             // = a search of the driver with the Gumbel rule at its root; bit 4 (SEARCH_GUMBEL_FULL) = ... in the full mode
     int64_t game_idx;        // -1: no game
     double temperature;
     int32_t error;
@@ -142,10 +142,24 @@ struct SearchCfg {
     double forced_k;         // forced playouts (forced_playouts.h, dbaz_selfplay_set_forced_playouts): k, 0 = off.  Only searches whose
                              // Slot::fast_search carries SEARCH_FORCED see it
     int forced_prune;        // ... 1 = the rows of those searches record the pruned visits
-    int gumbel_m;            // Gumbel root search (gumbel.h, dbaz_selfplay_set_gumbel): m, 0 = off.  Only searches whose Slot::fast_search
-                             // carries SEARCH_GUMBEL see it
-    double gumbel_c_visit, gumbel_c_scale; // ... the two constants of sigma
+    // Gumbel root search (gumbel.h), per model: a self-play handle (dbaz_selfplay_set_gumbel, dbaz_selfplay_set_gumbel_mode) has model
+    // 0 alone, a match handle (dbaz_match_set_search) the two of search_model().  Only searches whose Slot::fast_search carries
+    // SEARCH_GUMBEL see the constants; the GUMBEL = 0 instantiations of tree.hip read none of these fields
+    int gumbel_m[2];         // m, 0 = this model's searches are without the rule
+    double gumbel_c_visit[2], gumbel_c_scale[2]; // ... the two constants of sigma
+    double gumbel_g_scale[2]; // ... the scale on g: gl = (g_scale * g) + logit; 1.0 on a self-play handle
+    int gumbel_mode[2];      // ... 1 = the full mode (the rule below the root, the full v_mix): the search carries SEARCH_GUMBEL_FULL
+    int match_reads[2];      // dbaz_match_set_search: this model's read budget, 0 = mcts_num_read
 };
+
+// which instantiations of tree.hip's templates on the rule a handle launches: the maximum over both models.  0: no trace of the rule
+// (every handle that never had it switched on), 1: the rule at the root (and a match model's own read budget), 2: the full mode too
+inline int gumbel_level(const SearchCfg &c)
+{
+    const bool full = (c.gumbel_m[0] > 0 && c.gumbel_mode[0]) || (c.gumbel_m[1] > 0 && c.gumbel_mode[1]);
+    const bool on = c.gumbel_m[0] > 0 || c.gumbel_m[1] > 0 || c.match_reads[0] > 0 || c.match_reads[1] > 0;
+    return full ? 2 : on ? 1 : 0;
+}
 
 // the two families of built-in evaluators (DBAZ_EVAL_EXTERNAL is neither)
 __host__ __device__ inline bool eval_is_nn(int ev) { return ev == DBAZ_EVAL_RESNET || ev == DBAZ_EVAL_SIMPLENN; }

@@ -43,8 +43,9 @@ struct dbaz_engine {
     ReadCaps read_caps = {{0, 0}, {0, 0}};
     PlayoutCap playout = {4294967296ull, 0, 0}; // dbaz_selfplay_set_playout_cap (off)
     double playout_prob = 1.0;                  // full_prob as the caller gave it
-    int gumbel_full = 0; // dbaz_selfplay_set_gumbel_mode: 1 = the rule below the root and the full v_mix too; looked at while sc.gumbel_m > 0.
-                         // The launchers pick the kernels' instantiation by it; the kernels' arguments do not change
+    int gumbel_full = 0; // dbaz_selfplay_set_gumbel_mode, as told; a self-play handle's sc.gumbel_mode[0] follows it.  (The setting itself
+                         // lives in sc, per model: dbaz_match_set_search writes either model's on a match handle; the launchers pick the
+                         // kernels' instantiation by gumbel_level(sc).)
     EndgameStart eg_start = {nullptr, {0, 0}};
     size_t eg_stride = 0; // bytes per slot of eg_tables as allocated: every attached handle must have this stride
     int eg_max_free = 0;  // the largest max_free attached so far: no header claims more compact edges, and 2^eg_max_free <= eg_stride
@@ -735,7 +736,7 @@ static int sim_wave(dbaz_engine *e, bool with_driver)
     e->sc.driver_concurrent = 0;
     e->sc.eval_round = 0;
     if (with_driver) {
-        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout}, e->gumbel_full);
+        tree_launch_advance_auto(s, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
         endgame_solve_tables(e, s);
     }
     tree_launch_select_multi(s, e->g, e->sc, e->B, e->n_slots, e->G);
@@ -773,7 +774,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         // every step and k_select is short) its few single-wave workgroups cost the network less than waiting for them.
         HIP_CHECK_RET(e, hipEventRecord(e->ev_fork, s));
         HIP_CHECK_RET(e, hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout}, e->gumbel_full);
+        tree_launch_advance_auto(e->stream2, e->g, e->sc, e->B, e->n_slots, StartArgs{e->read_caps, e->eg_start, e->playout});
         // the searches this pass starts do not select in this step; the join below orders their tables before the next k_select
         endgame_solve_tables(e, e->stream2);
         HIP_CHECK_RET(e, hipEventRecord(e->ev_join, e->stream2));
@@ -784,7 +785,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
         e->sc.eval_round = e->eval_round;
         e->sc.eval_defer_max = e->eval_defer_max;
     }
-    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots, e->G, e->gumbel_full); // (the lists' counters were zeroed by the previous k_expand_backup)
+    tree_launch_select(s, e->g, e->sc, e->B, e->n_slots, e->G); // (the lists' counters were zeroed by the previous k_expand_backup)
     if (e->sc.eval_round > 0) tree_launch_order_evals(s, e->B, e->n_slots, e->sc.step); // the list in slot order (deterministic cut)
     const bool late_join = with_driver && e->late_join;
     if (with_driver && !late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
@@ -811,7 +812,7 @@ static int sim_step(dbaz_engine *e, bool with_driver)
     // k_select, which skipped the slots the pass starts); k_expand_backup does (it clears the pass's slot list).
     // 3x3: 11.9 -> 13.2 M expansions/s, 6x6: +1.5 %, 9x9: +2.8 % against joining in front of the network
     if (late_join) HIP_CHECK_RET(e, hipStreamWaitEvent(s, e->ev_join, 0));
-    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots, e->G, e->gumbel_full);
+    tree_launch_expand_backup(s, e->g, e->sc, e->B, e->n_slots, e->G);
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     return DBAZ_OK;
@@ -1293,7 +1294,7 @@ extern "C" int dbaz_select(dbaz_engine *e, int32_t *n_active, int16_t *leaf_x, u
     int32_t *d_na = cv.take<int32_t>(4);
     e->sc.step = (e->sc.step & 0x3FFFFFFF) + 1;
     e->sc.driver_concurrent = 0;
-    tree_launch_select(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs(), e->gumbel_full);
+    tree_launch_select(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs());
     HIP_CHECK_RET(e, hipMemsetAsync(d_na, 0, 16, e->stream));
     tree_launch_get_leaves(e->stream, g, e->B, e->n_slots, d_x, d_ne, d_na);
     HIP_CHECK_RET(e, hipGetLastError());
@@ -1319,7 +1320,7 @@ extern "C" int dbaz_expand_backup(dbaz_engine *e, const float *p, const float *v
         memcpy(padded.data() + (size_t)i * g.AS, p + (size_t)i * g.A, (size_t)g.A * 4);
     HIP_CHECK_RET(e, hipMemcpyAsync(e->B.evalP, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, e->stream));
     HIP_CHECK_RET(e, hipMemcpyAsync(e->B.evalV, v, (size_t)e->n_slots * 4, hipMemcpyHostToDevice, e->stream));
-    tree_launch_expand_backup(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs(), e->gumbel_full);
+    tree_launch_expand_backup(e->stream, g, e->sc, e->B, e->n_slots, EndgameBufs());
     e->steps++;
     HIP_CHECK_RET(e, hipGetLastError());
     HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
@@ -1555,7 +1556,7 @@ extern "C" int dbaz_selfplay_set_forced_playouts(dbaz_engine *e, double k, int32
         if (r) return r;
         if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
     }
-    if (k > 0.0 && e->sc.gumbel_m > 0)
+    if (k > 0.0 && e->sc.gumbel_m[0] > 0)
         return set_error(e, DBAZ_EINVAL, "forced playouts and the Gumbel root search (dbaz_selfplay_set_gumbel) both own the root's pick: switch one off first");
     e->sc.forced_k = k > 0.0 ? k : 0.0;
     e->sc.forced_prune = k > 0.0 ? prune : 0;
@@ -1589,6 +1590,20 @@ extern "C" int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double
 
 // ---- Gumbel root search (gumbel.h; the rule is stated in full in include/dbaz.h)
 static_assert(GUMBEL_M_MAX == DBAZ_MAX_A, "gumbel.h sizes its host arrays by the most children a root has");
+// the per-slot state of a Gumbel search exists from the first time the rule is switched on
+static int gumbel_state_alloc(dbaz_engine *e)
+{
+    if (e->B.gumbel_gl) return DBAZ_OK;
+    const size_t ns = e->n_slots;
+    const size_t bytes[3] = {ns * e->g.AS * sizeof(double), ns * e->g.AS * sizeof(int32_t), ns * 2 * sizeof(int32_t)};
+    void *p[3] = {nullptr, nullptr, nullptr};
+    if (alloc_all(e, 3, bytes, 7u, p) != hipSuccess) return set_error(e, DBAZ_EDEVICE, "no device memory for the Gumbel search state");
+    e->B.gumbel_gl = (double *)p[0];
+    e->B.gumbel_n0 = (int32_t *)p[1];
+    e->B.gumbel_hdr = (int32_t *)p[2];
+    return DBAZ_OK;
+}
+
 extern "C" int dbaz_selfplay_set_gumbel(dbaz_engine *e, int32_t m, double c_visit, double c_scale)
 {
     if (!e) return DBAZ_EINVAL;
@@ -1608,19 +1623,11 @@ extern "C" int dbaz_selfplay_set_gumbel(dbaz_engine *e, int32_t m, double c_visi
         if (r) return r;
         if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
     }
-    if (m > 0 && !e->B.gumbel_gl) {
-        // the per-slot state of a Gumbel search exists from the first time the rule is switched on
-        const size_t ns = e->n_slots;
-        const size_t bytes[3] = {ns * e->g.AS * sizeof(double), ns * e->g.AS * sizeof(int32_t), ns * 2 * sizeof(int32_t)};
-        void *p[3] = {nullptr, nullptr, nullptr};
-        if (alloc_all(e, 3, bytes, 7u, p) != hipSuccess) return set_error(e, DBAZ_EDEVICE, "no device memory for the Gumbel search state");
-        e->B.gumbel_gl = (double *)p[0];
-        e->B.gumbel_n0 = (int32_t *)p[1];
-        e->B.gumbel_hdr = (int32_t *)p[2];
-    }
-    e->sc.gumbel_m = m;
-    e->sc.gumbel_c_visit = m > 0 ? c_visit : 0.0;
-    e->sc.gumbel_c_scale = m > 0 ? c_scale : 0.0;
+    if (m > 0 && gumbel_state_alloc(e)) return DBAZ_EDEVICE;
+    e->sc.gumbel_m[0] = m;
+    e->sc.gumbel_c_visit[0] = m > 0 ? c_visit : 0.0;
+    e->sc.gumbel_c_scale[0] = m > 0 ? c_scale : 0.0;
+    e->sc.gumbel_g_scale[0] = m > 0 ? 1.0 : 0.0; // self-play: g unscaled (the product with 1.0 is exact)
     return DBAZ_OK;
 }
 
@@ -1628,9 +1635,11 @@ extern "C" int dbaz_get_gumbel(dbaz_engine *e, int32_t *m, double *c_visit, doub
 {
     if (!e) return DBAZ_EINVAL;
     USE_DEVICE(e);
-    if (m) *m = e->sc.gumbel_m;
-    if (c_visit) *c_visit = e->sc.gumbel_c_visit;
-    if (c_scale) *c_scale = e->sc.gumbel_c_scale;
+    // (the self-play setting: a match handle's is per model, dbaz_match_get_search, and reads 0 here)
+    const bool mp = e->sc.match_play != 0;
+    if (m) *m = mp ? 0 : e->sc.gumbel_m[0];
+    if (c_visit) *c_visit = mp ? 0.0 : e->sc.gumbel_c_visit[0];
+    if (c_scale) *c_scale = mp ? 0.0 : e->sc.gumbel_c_scale[0];
     if (searches || rows) {
         long long c[7] = {0, 0, 0, 0, 0, 0, 0}; // ..., Gumbel searches started, Gumbel rows written
         HIP_CHECK_RET(e, hipStreamSynchronize(e->stream));
@@ -1654,6 +1663,7 @@ extern "C" int dbaz_selfplay_set_gumbel_mode(dbaz_engine *e, int32_t mode)
         if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "self-play in progress (%d games being played)", sm.active);
     }
     e->gumbel_full = mode;
+    if (!e->sc.match_play) e->sc.gumbel_mode[0] = mode; // (a match handle's modes are dbaz_match_set_search's)
     return DBAZ_OK;
 }
 
@@ -1661,6 +1671,53 @@ extern "C" int dbaz_get_gumbel_mode(dbaz_engine *e, int32_t *mode)
 {
     if (!e) return DBAZ_EINVAL;
     if (mode) *mode = e->gumbel_full;
+    return DBAZ_OK;
+}
+
+// ---- the search of each model of a match (the rule is stated in full in include/dbaz.h)
+extern "C" int dbaz_match_set_search(dbaz_engine *e, int32_t model, int32_t reads, int32_t m, double c_visit, double c_scale, int32_t mode,
+                                     double g_scale)
+{
+    if (!e) return DBAZ_EINVAL;
+    USE_DEVICE(e);
+    if (!e->sc.match_play) return set_error(e, DBAZ_EINVAL, "dbaz_match_set_search needs a handle that plays matches (match_play)");
+    // (no handle is both match_play and selfplay_pending: dbaz_create refuses max_pending_evals > 1 in match play)
+    if (model != 0 && model != 1) return set_error(e, DBAZ_EINVAL, "model = %d is neither 0 nor 1", model);
+    if (reads < 0 || reads > e->sc.mcts_num_read) return set_error(e, DBAZ_EINVAL, "reads = %d is outside [0, mcts_num_read = %d]", reads, e->sc.mcts_num_read);
+    if (m < 0 || m > DBAZ_MAX_A) return set_error(e, DBAZ_EINVAL, "m = %d is outside [0, %d]", m, DBAZ_MAX_A);
+    if (m > 0 && !(c_visit >= 0.0 && c_visit <= GUMBEL_C_VISIT_MAX)) return set_error(e, DBAZ_EINVAL, "c_visit = %g is outside [0, %g]", c_visit, GUMBEL_C_VISIT_MAX);
+    if (m > 0 && !(c_scale > 0.0 && c_scale <= GUMBEL_C_SCALE_MAX)) return set_error(e, DBAZ_EINVAL, "c_scale = %g is outside (0, %g]", c_scale, GUMBEL_C_SCALE_MAX);
+    if (m > 0 && mode != 0 && mode != 1) return set_error(e, DBAZ_EINVAL, "mode = %d is neither 0 (the rule at the root) nor 1 (full)", mode);
+    if (m > 0 && !(g_scale >= 0.0 && g_scale <= GUMBEL_C_SCALE_MAX)) return set_error(e, DBAZ_EINVAL, "g_scale = %g is outside [0, %g]", g_scale, GUMBEL_C_SCALE_MAX);
+    if (e->selfplay) {
+        // the driver's launches read the setting at every step: it changes only between runs
+        SlotSummary sm;
+        int r = device_summary(e, &sm);
+        if (r) return r;
+        if (sm.active > 0) return set_error(e, DBAZ_ESTATE, "match in progress (%d games being played)", sm.active);
+    }
+    if (m > 0 && gumbel_state_alloc(e)) return DBAZ_EDEVICE;
+    e->sc.match_reads[model] = reads;
+    e->sc.gumbel_m[model] = m;
+    e->sc.gumbel_c_visit[model] = m > 0 ? c_visit : 0.0;
+    e->sc.gumbel_c_scale[model] = m > 0 ? c_scale : 0.0;
+    e->sc.gumbel_mode[model] = m > 0 ? mode : 0;
+    e->sc.gumbel_g_scale[model] = m > 0 ? g_scale : 0.0;
+    return DBAZ_OK;
+}
+
+extern "C" int dbaz_match_get_search(dbaz_engine *e, int32_t model, int32_t *reads, int32_t *m, double *c_visit, double *c_scale, int32_t *mode,
+                                     double *g_scale)
+{
+    if (!e) return DBAZ_EINVAL;
+    if (!e->sc.match_play) return set_error(e, DBAZ_EINVAL, "dbaz_match_get_search needs a handle that plays matches (match_play)");
+    if (model != 0 && model != 1) return set_error(e, DBAZ_EINVAL, "model = %d is neither 0 nor 1", model);
+    if (reads) *reads = e->sc.match_reads[model];
+    if (m) *m = e->sc.gumbel_m[model];
+    if (c_visit) *c_visit = e->sc.gumbel_c_visit[model];
+    if (c_scale) *c_scale = e->sc.gumbel_c_scale[model];
+    if (mode) *mode = e->sc.gumbel_mode[model];
+    if (g_scale) *g_scale = e->sc.gumbel_g_scale[model];
     return DBAZ_OK;
 }
 

@@ -13,7 +13,8 @@
 
 #include "forced_playouts.h" // FORCED_HD, forced_value (the descent's value_score), FORCED_PRIOR, the SEARCH_* bits below 8
 
-#define SEARCH_GUMBEL 8 // Slot::fast_search: a search of the self-play driver with the Gumbel rule at its root (beside SEARCH_FAST)
+#define SEARCH_GUMBEL 8 // Slot::fast_search: a search of the driver with the Gumbel rule at its root (beside SEARCH_FAST)
+#define SEARCH_GUMBEL_FULL 16 // ... in the full mode of the searching model (beside SEARCH_GUMBEL; only the <2> instantiations look at it)
 
 #define GUMBEL_M_MAX 256         // DBAZ_MAX_A (engine.hip asserts it): the most children a root has
 #define GUMBEL_C_VISIT_MAX 1e6
@@ -34,6 +35,9 @@ FORCED_HD inline double gumbel_clamp_u(double u)
 FORCED_HD inline double gumbel_from_u(double u) { return -log(-log(gumbel_clamp_u(u))); }
 
 FORCED_HD inline double gumbel_logit(double P) { return P > 0.0 ? log(P) : GUMBEL_LOGIT_MIN; }
+
+// gl of a candidate: one product, then one sum.  g_scale = 1.0 (self-play) leaves g's bits; 0.0 is the deterministic search
+FORCED_HD inline double gumbel_noisy_logit(double g_scale, double gv, double logit) { return (g_scale * gv) + logit; }
 
 // mctx's sequence of considered visits at position t, in closed form per phase (integers only)
 FORCED_HD inline int gumbel_considered(int m_eff, int R, int t)

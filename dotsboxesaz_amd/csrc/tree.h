@@ -66,22 +66,20 @@ struct EndgameBufs {
 
 void tree_launch_search_begin(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                               const int32_t *num_reads_dev, StartArgs sa);
-// gumbel_full (tree_launch_select, _expand_backup, _advance_auto): the handle's Gumbel mode (dbaz_selfplay_set_gumbel_mode), looked at
-// while c.gumbel_m > 0 -- which instantiation is launched; the kernels themselves are told by their template argument alone
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs(),
-                        int gumbel_full = 0);
+// tree_launch_select, _expand_backup, _selfplay_start, _advance_auto: gumbel_level(c) (common.h), the maximum over both models of the
+// handle's Gumbel setting, says which instantiation is launched; level 0 launches the ones without a trace of the rule
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step);
 void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
 void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                      const EndgameBufs &G = EndgameBufs());
-void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs(),
-                               int gumbel_full = 0);
+void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G = EndgameBufs());
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                const int16_t *moves_dev, const int32_t *offsets_dev);
 void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
                                 const int32_t *moves_dev, int reuse);
 void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa);
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa, int gumbel_full = 0);
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa);
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,
                            int32_t *nv, int32_t *changed, int32_t *stats, float *q, float *root_tv, int32_t *root_nv,
                            uint64_t *edges, int16_t *b2c2, int8_t *to_play, int8_t *just_played, int8_t *result,

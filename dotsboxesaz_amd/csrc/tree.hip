@@ -365,6 +365,13 @@ __device__ __forceinline__ double rng_gamma(uint64_t seed, uint64_t game, uint32
     }
 }
 
+// to_play of a node alone (dword 9 of its meta block, common.h)
+__device__ __forceinline__ int node_to_play(uint32_t *pool, const Geo &g, int idx) { return (int)((node_ptr(pool, g, idx)[9] >> 16) & 0xffu); }
+
+// Match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the whole search of this move; odd
+// games swap the seats (the reference shuffles them by worker pid)
+__device__ __forceinline__ int search_model(const SearchCfg &cfg, int to_play, int64_t game_idx) { return cfg.match_play ? ((to_play ^ (int)(game_idx & 1)) & 1) : 0; }
+
 // ------------------------------------------------------------------------------------
 // Gumbel root search (gumbel.h; the rule is in include/dbaz.h): what a search keeps from its preparation.  Runs at the end of
 // root_prep, on the float64 root prior it has just written: the candidates, gl = g + logit (-inf for every other child), the
@@ -390,6 +397,9 @@ __device__ void gumbel_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &
         npos += __shfl_xor(npos, o);
     }
     const bool any = npos > 0; // no valid child with a positive prior: every valid child is a candidate
+    // the searching model's m and scale on g (one model on a self-play handle; dbaz_match_set_search); wave-uniform
+    const int model = __builtin_amdgcn_readfirstlane(search_model(cfg, rm.st.to_play, S->game_idx));
+    const double g_scale = cfg.gumbel_g_scale[model];
     const uint2 key = make_uint2((uint32_t)cfg.seed, (uint32_t)(cfg.seed >> 32));
     const uint64_t game = (uint64_t)S->game_idx;
     const uint32_t ply = (uint32_t)S->move_idx;
@@ -405,12 +415,12 @@ __device__ void gumbel_prep(const Geo &g, const SearchCfg &cfg, const TreeBufs &
                 const uint4 r = philox(make_uint4((uint32_t)game, (uint32_t)(game >> 32), ply + 65536u * (uint32_t)i, GUMBEL_TAG), key);
                 gv = gumbel_from_u(u01(r.x, r.y));
             }
-            x = gv + gumbel_logit(P);
+            x = gumbel_noisy_logit(g_scale, gv, gumbel_logit(P));
         }
         gl[i] = x;
         n0[i] = (int32_t)(NS0[i] & NS_MASK);
     }
-    if (lane == 0) B.gumbel_hdr[2 * slot + 1] = min(cfg.gumbel_m, any ? npos : nval);
+    if (lane == 0) B.gumbel_hdr[2 * slot + 1] = min(cfg.gumbel_m[model], any ? npos : nval);
     __syncthreads();
 }
 
@@ -517,10 +527,6 @@ __device__ __forceinline__ int rule_num_reads(const Geo &g, const SearchCfg &cfg
     return f < (double)cfg.mcts_num_read ? (int)f : cfg.mcts_num_read;
 }
 
-// Match play (self_play.py:59,237-239): the player to move at the ROOT selects the model for the whole search of this move; odd
-// games swap the seats (the reference shuffles them by worker pid)
-__device__ __forceinline__ int search_model(const SearchCfg &cfg, int to_play, int64_t game_idx) { return cfg.match_play ? ((to_play ^ (int)(game_idx & 1)) & 1) : 0; }
-
 // The slot's game is over.  With a pool of tables shared by the slots (EndgameStart::release) the region it holds goes back in
 // the pass that follows on this stream, whether or not the slot starts another game.
 __device__ __forceinline__ void endgame_release(const StartArgs &sa, int slot, const Slot *S, int lane)
@@ -550,8 +556,10 @@ __device__ __forceinline__ void begin_search(const Geo &g, const SearchCfg &cfg,
     if (num_reads < 0) {
         num_reads = rule_num_reads(g, cfg, rm.st);
         if (fast) num_reads = min(num_reads, sa.pc.fast_reads);
-        // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads)
         const int model = search_model(cfg, rm.st.to_play, S->game_idx);
+        // match play: the searching model's own read budget (dbaz_match_set_search), ahead of the caps below
+        if (GUMBEL && cfg.match_reads[model] > 0) num_reads = min(num_reads, cfg.match_reads[model]);
+        // a search that the solved table serves needs no more than a few reads (dbaz_attach_solver's solver_reads)
         if ((model ? cfg.evaluator2 : cfg.evaluator) == DBAZ_EVAL_SOLVER && sa.caps.cap[model] > 0) num_reads = min(num_reads, sa.caps.cap[model]);
         // the same for a search whose leaves the slot's endgame table will answer (dbaz_attach_endgame's endgame_reads)
         if (sa.caps.eg_cap[model] > 0 && gs_count_valid(g, rm.st) <= sa.eg.max_free[model]) num_reads = min(num_reads, sa.caps.eg_cap[model]);
@@ -694,10 +702,12 @@ __device__ __forceinline__ void write_features(const Geo &g, const GState &st, f
 // rows as the descent holds them, rp: its float64 priors.  Four butterfly reductions (t, n_max and the two sums of v_mix) and the
 // argmax; the sums run in the rule's order -- this lane's children in index order, then o = 32 .. 1.  The child found gets
 // FORCED_PRIOR in rp, and the root level's pb_c terms become 1, under which that child's score is beyond every other one.
-// FULL (dbaz_selfplay_set_gumbel_mode): v_mix is the full one, around the root's own value m.vhat (load_meta<true>) with S, the sum
-// of the children's visits, riding in the same butterfly.
+// FULL, the <2> instantiation, and full, the search's own SEARCH_GUMBEL_FULL (dbaz_selfplay_set_gumbel_mode, or the searching model's
+// mode in match play): v_mix is the full one, around the root's own value m.vhat (load_meta<true>) with S, the sum of the children's
+// visits, riding in the same butterfly.  c_visit, c_scale: the searching model's.
 template <int NPL, bool FULL>
-__device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, const NodeMeta &m,
+__device__ __forceinline__ void gumbel_root_pick(const Geo &g, double c_visit, double c_scale, bool full, const TreeBufs &B, int slot,
+                                                 const NodeMeta &m,
                                                  const NodeRows<NPL> &R, double (&rp)[NPL], double &pbc_cur, double &sq_cur, int lane)
 {
     const int A = g.A;
@@ -732,7 +742,7 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
     }
     t = __builtin_amdgcn_readfirstlane(t);
     n_max = __builtin_amdgcn_readfirstlane(n_max);
-    const double vmix = FULL ? gumbel_vmix_full((double)m.vhat, Sn, num, den) : gumbel_vmix(num, den);
+    const double vmix = (FULL && full) ? gumbel_vmix_full((double)m.vhat, Sn, num, den) : gumbel_vmix(num, den);
     int cv = gumbel_considered(m_eff, reads, t);
     // gl + sigma of the candidates at cv visits of this search, -inf for every other child
     double sc[NPL], mx;
@@ -742,7 +752,7 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
         for (int j = 0; j < NPL; j++) {
             const int n = (int)(R.NS[j] & NS_MASK);
             const double cq = n > 0 ? forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : vmix;
-            sc[j] = (gl[j] > -INFINITY && nsr[j] == cv) ? gl[j] + gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, cq) : -INFINITY;
+            sc[j] = (gl[j] > -INFINITY && nsr[j] == cv) ? gl[j] + gumbel_sigma(c_visit, c_scale, n_max, cq) : -INFINITY;
             mx = fmax(mx, sc[j]);
         }
         for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
@@ -772,7 +782,7 @@ __device__ __forceinline__ void gumbel_root_pick(const Geo &g, const SearchCfg &
 // descent holds them, m.vhat: its own value (load_meta<true>).  Three butterfly reductions -- S, n_max and the two sums of v_mix
 // fused, then M, then the sum of e -- in the rule's order; the descent's first-maximum argmax follows on sc.
 template <int NPL>
-__device__ __forceinline__ void gumbel_inner_scores(const Geo &g, const SearchCfg &cfg, const NodeMeta &m, const NodeRows<NPL> &R,
+__device__ __forceinline__ void gumbel_inner_scores(const Geo &g, double c_visit, double c_scale, const NodeMeta &m, const NodeRows<NPL> &R,
                                                     double (&sc)[NPL], int lane)
 {
     const int A = g.A;
@@ -809,7 +819,7 @@ __device__ __forceinline__ void gumbel_inner_scores(const Geo &g, const SearchCf
         const double P = (double)R.P[j];
         const bool cand = valid && (P > 0.0 || !any);
         const double cq = n > 0 ? forced_value(R.W[j], n, (R.NS[j] & NS_SAME) != 0) : vmix;
-        sc[j] = cand ? gumbel_logit(P) + gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, cq) : -INFINITY;
+        sc[j] = cand ? gumbel_logit(P) + gumbel_sigma(c_visit, c_scale, n_max, cq) : -INFINITY;
         M = fmax(M, sc[j]);
     }
     for (int o = 32; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
@@ -866,10 +876,15 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
     // handle with the rule on launches.  The pre-pass picks the root's child by sequential halving and hands it to the loop the way
     // the forced pre-pass below does, through rp; it also makes the root level's pb_c a plain 1 / (n + 1) > 0, since a re-used root
     // starts its search at N = 0, where sqrt(N) would wipe FORCED_PRIOR out.  (Such a handle has no forced playouts.)
+    // The constants are the searching model's (dbaz_match_set_search; a self-play handle has model 0 alone), and in the <2>
+    // instantiation the mode is the search's own bit: a root-only search of a handle whose other model is full stays root-only.
+    const int gmodel = GUMBEL ? __builtin_amdgcn_readfirstlane(search_model(cfg, root_to_play, S->game_idx)) : 0;
+    const double c_visit = GUMBEL ? cfg.gumbel_c_visit[gmodel] : 0.0, c_scale = GUMBEL ? cfg.gumbel_c_scale[gmodel] : 0.0;
+    const bool gfull = GUMBEL == 2 && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL_FULL) != 0;
     if (GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) && is_inner(m.flags))
-        gumbel_root_pick<NPL, GUMBEL == 2>(g, cfg, B, slot, m, R, rp, pbc_cur, sq_cur, lane);
+        gumbel_root_pick<NPL, GUMBEL == 2>(g, c_visit, c_scale, gfull, B, slot, m, R, rp, pbc_cur, sq_cur, lane);
     // full mode: the levels below the root of such a search take the rule's pick, not the UCB's
-    const bool ginner = GUMBEL == 2 && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) != 0;
+    const bool ginner = GUMBEL == 2 && gfull && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_GUMBEL) != 0;
     // forced playouts (forced_playouts.h): on for a full search of the self-play driver, and at the root level only
     const bool forced = !GUMBEL && (__builtin_amdgcn_readfirstlane(kind) & SEARCH_FORCED) != 0;
     if (forced && is_inner(m.flags)) {
@@ -913,7 +928,7 @@ __device__ __forceinline__ Leaf descend(const Geo &g, const SearchCfg &cfg, cons
         bool have = false;
         double gsc[NPL]; // full Gumbel mode, below the root: the rule's scores in place of the UCB's
         const bool gpick = GUMBEL == 2 && ginner && cur != root;
-        if (GUMBEL == 2 && gpick) gumbel_inner_scores<NPL>(g, cfg, m, R, gsc, lane);
+        if (GUMBEL == 2 && gpick) gumbel_inner_scores<NPL>(g, c_visit, c_scale, m, R, gsc, lane);
 #pragma unroll
         for (int j = 0; j < NPL; j++) {
             const int i = lane + WAVE * j;
@@ -1891,7 +1906,9 @@ __device__ __forceinline__ void start_move_search(const Geo &g, const SearchCfg 
     const bool fast = !playout_is_full(sa.pc, cfg.seed, S->game_idx, (uint32_t)i);
     if (lane == 0) atomicAdd((unsigned long long *)B.moves_played + (fast ? 2 : 1), 1ull);
     // (with the Gumbel rule on, a scripted vector is the search's g, whatever the noise setting, and for fast searches too)
-    const bool gumbel = GUMBEL && cfg.gumbel_m > 0;
+    // (the rule is the searching model's: dbaz_match_set_search gives each model of a match its own; wave-uniform)
+    const int model = GUMBEL ? __builtin_amdgcn_readfirstlane(search_model(cfg, node_to_play(pool, g, S->root), S->game_idx)) : 0;
+    const bool gumbel = GUMBEL && cfg.gumbel_m[model] > 0;
     if ((gumbel || (cfg.alpha > 0 && !fast)) && B.script_noise && gi >= 0 && gi < B.n_script && B.script_has_noise[gi] && i <= g.E) {
         const double *src = B.script_noise + ((size_t)gi * (g.E + 1) + i) * g.A;
         double *dst = B.noise_in + (size_t)slot * g.AS;
@@ -1905,7 +1922,7 @@ __device__ __forceinline__ void start_move_search(const Geo &g, const SearchCfg 
     if (GUMBEL && gumbel && lane == 0) atomicAdd((unsigned long long *)B.moves_played + 5, 1ull); // Gumbel searches started
     // forced playouts belong to the driver's full searches (with the cap off every search is one)
     // (the Gumbel rule belongs to every search of the driver, full or fast; a handle has it or forced playouts, never both)
-    const int kind = (fast ? SEARCH_FAST : (cfg.forced_k > 0.0 ? SEARCH_FORCED | (cfg.forced_prune ? SEARCH_PRUNE : 0) : 0)) | (gumbel ? SEARCH_GUMBEL : 0);
+    const int kind = (fast ? SEARCH_FAST : (cfg.forced_k > 0.0 ? SEARCH_FORCED | (cfg.forced_prune ? SEARCH_PRUNE : 0) : 0)) | (gumbel ? SEARCH_GUMBEL | (cfg.gumbel_mode[model] ? SEARCH_GUMBEL_FULL : 0) : 0);
     begin_search<GUMBEL>(g, cfg, B, slot, S, pool, -1, sa, ldsf, ldsd, lane, kind);
 }
 
@@ -1939,14 +1956,17 @@ __global__ void __launch_bounds__(WAVE) k_selfplay_start(Geo g, SearchCfg cfg, T
 // The end of a Gumbel search (gumbel.h; the rule is in include/dbaz.h), everything read after the search: the move -- the first
 // maximum of gl + sigma over the candidates with the most visits of this search -- is returned, and rv (if not null) gets the
 // row's visits, softmax(logit + sigma) over the candidates in units of 2^-24.  One wave; the sums run in the rule's order.
-// FULL (dbaz_selfplay_set_gumbel_mode): v_mix is the full one around the root's own value, dword 12 of its meta block.  It is always
-// there: the root was expanded by k_expand_backup<2> in this game, as a root or -- under tree reuse -- as an inner node earlier on,
-// since the setters are refused while games are being played.
+// FULL (the <2> instantiation) and full (the search's SEARCH_GUMBEL_FULL): v_mix is the full one around the root's own value,
+// dword 12 of its meta block.  It is always there: the root was expanded by k_expand_backup<2> in this game, whichever model
+// searched then, as a root or -- under tree reuse -- as an inner node earlier on, since the setters are refused while games
+// are being played.
 template <bool FULL>
 __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs &B, int slot, uint32_t *pool, int root, const NodeMeta &rm,
-                             int32_t *rv, double *ldsd, int lane)
+                             bool full, int32_t *rv, double *ldsd, int lane)
 {
     const int A = g.A;
+    const int model = __builtin_amdgcn_readfirstlane(search_model(cfg, rm.st.to_play, B.slots[slot].game_idx)); // whose constants
+    const double c_visit = cfg.gumbel_c_visit[model], c_scale = cfg.gumbel_c_scale[model];
     const uint32_t *NS0 = node_ptr(pool, g, root) + META_DW + 2 * g.AS;
     const float *W0 = reinterpret_cast<const float *>(node_ptr(pool, g, root) + META_DW + g.AS);
     const double *rprior = B.root_prior + (size_t)slot * g.AS;
@@ -1970,7 +1990,7 @@ __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs 
         num = num + __shfl_xor(num, o);
         den = den + __shfl_xor(den, o);
     }
-    const double vmix = FULL ? gumbel_vmix_full((double)__uint_as_float(node_ptr(pool, g, root)[12]), Sn, num, den) : gumbel_vmix(num, den);
+    const double vmix = (FULL && full) ? gumbel_vmix_full((double)__uint_as_float(node_ptr(pool, g, root)[12]), Sn, num, den) : gumbel_vmix(num, den);
     // the move, and x = logit + sigma with its maximum
     double bs = -INFINITY, M = -INFINITY;
     int bi = 0x7fffffff;
@@ -1981,7 +2001,7 @@ __device__ int gumbel_finish(const Geo &g, const SearchCfg &cfg, const TreeBufs 
         if (cand) {
             const uint32_t ns = NS0[i];
             const int n = (int)(ns & NS_MASK);
-            const double sg = gumbel_sigma(cfg.gumbel_c_visit, cfg.gumbel_c_scale, n_max, n > 0 ? forced_value(W0[i], n, (ns & NS_SAME) != 0) : vmix);
+            const double sg = gumbel_sigma(c_visit, c_scale, n_max, n > 0 ? forced_value(W0[i], n, (ns & NS_SAME) != 0) : vmix);
             const double s = gl[i] + sg;
             if (n - n0[i] == ns_max && s > bs) { bs = s; bi = i; }
             x = gumbel_logit(rprior[i]) + sg;
@@ -2064,7 +2084,7 @@ __device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, 
     if (GUMBEL && gumbel) {
         // Gumbel root search (gumbel.h): the move by the rule -- no temperature, the move-draw stream is not consumed -- unless a
         // scripted one wins, and the row's visits, which are the target pi'
-        const int gmv = gumbel_finish<GUMBEL == 2>(g, cfg, B, slot, pool, root, rm, r < rcap ? B.row_vis + ((size_t)slot * rcap + r) * A : nullptr, ldsd, lane);
+        const int gmv = gumbel_finish<GUMBEL == 2>(g, cfg, B, slot, pool, root, rm, (kind & SEARCH_GUMBEL_FULL) != 0, r < rcap ? B.row_vis + ((size_t)slot * rcap + r) * A : nullptr, ldsd, lane);
         if (mv < 0) mv = gmv;
     }
     if (mv < 0) {
@@ -2159,7 +2179,7 @@ __device__ __forceinline__ void advance_one(const Geo &g, const SearchCfg &cfg, 
             mm.q_value = S->root_W / (float)(1 + S->root_N); // TreeRoot.get_tree_stats, mcts.py:33-36
             mm.player = (int8_t)rm.st.to_play;
             mm.z = 0;
-            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0) | (gumbel ? ROW_FLAG_GUMBEL | (GUMBEL == 2 ? ROW_FLAG_GUMBEL_FULL : 0) : 0);
+            mm.flags = ((kind & SEARCH_FAST) ? ROW_FLAG_FAST : 0) | (prune ? ROW_FLAG_PRUNED : 0) | (gumbel ? ROW_FLAG_GUMBEL | ((GUMBEL == 2 && (kind & SEARCH_GUMBEL_FULL)) ? ROW_FLAG_GUMBEL_FULL : 0) : 0);
             B.row_meta[(size_t)slot * rcap + r] = mm;
         }
         S->n_rows = r + 1;
@@ -2467,12 +2487,12 @@ static void launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const
     default: hipLaunchKernelGGL((k_select<4, false, GUMBEL>), grid, block, 0, s, g, c, B, n_slots, G); break;
     }
 }
-void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G, int gumbel_full)
+void tree_launch_select(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     // a handle with the Gumbel rule on launches the instantiations that hold its root pre-pass (in the full mode, those that hold the
     // rule below the root too); every other handle the ones without
-    if (c.gumbel_m > 0 && gumbel_full) launch_select<2>(s, g, c, B, n_slots, G);
-    else if (c.gumbel_m > 0) launch_select<1>(s, g, c, B, n_slots, G);
+    if (gumbel_level(c) == 2) launch_select<2>(s, g, c, B, n_slots, G);
+    else if (gumbel_level(c) == 1) launch_select<1>(s, g, c, B, n_slots, G);
     else launch_select<0>(s, g, c, B, n_slots, G);
 }
 void tree_launch_select_multi(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
@@ -2488,11 +2508,11 @@ void tree_launch_expand_backup_multi(hipStream_t s, const Geo &g, const SearchCf
 {
     hipLaunchKernelGGL(k_expand_backup_multi, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
-void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G, int gumbel_full)
+void tree_launch_expand_backup(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, const EndgameBufs &G)
 {
     // (a handle with the Gumbel rule on launches the instantiations that hold it; every other handle the ones without a trace of it)
-    if (c.gumbel_m > 0 && gumbel_full) hipLaunchKernelGGL(k_expand_backup<2>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
-    else if (c.gumbel_m > 0) hipLaunchKernelGGL(k_expand_backup<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    if (gumbel_level(c) == 2) hipLaunchKernelGGL(k_expand_backup<2>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
+    else if (gumbel_level(c) == 1) hipLaunchKernelGGL(k_expand_backup<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
     else hipLaunchKernelGGL(k_expand_backup<0>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, G);
 }
 void tree_launch_set_positions(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots,
@@ -2508,7 +2528,7 @@ void tree_launch_advance_manual(hipStream_t s, const Geo &g, const SearchCfg &c,
 void tree_launch_selfplay_start(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
     // (the start of a search is the same in both modes of the rule)
-    if (c.gumbel_m > 0) hipLaunchKernelGGL(k_selfplay_start<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
+    if (gumbel_level(c) > 0) hipLaunchKernelGGL(k_selfplay_start<1>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
     else hipLaunchKernelGGL(k_selfplay_start<0>, dim3(n_slots), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int step)
@@ -2517,13 +2537,13 @@ void tree_launch_order_evals(hipStream_t s, const TreeBufs &B, int n_slots, int 
     if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_order_evals<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
     else hipLaunchKernelGGL(k_order_evals<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, B, n_slots, rot);
 }
-void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa, int gumbel_full)
+void tree_launch_advance_auto(hipStream_t s, const Geo &g, const SearchCfg &c, const TreeBufs &B, int n_slots, StartArgs sa)
 {
     hipLaunchKernelGGL(k_driver_flags, dim3((n_slots + WAVE - 1) / WAVE), dim3(WAVE), 0, s, B, n_slots);
     if (n_slots <= SCAN_T * SCAN_NG_SMALL) hipLaunchKernelGGL(k_driver_scan<SCAN_NG_SMALL>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
     else hipLaunchKernelGGL(k_driver_scan<SCAN_NG>, dim3(1), dim3(SCAN_T), 0, s, c, B, n_slots);
-    if (c.gumbel_m > 0 && gumbel_full) hipLaunchKernelGGL(k_advance_auto<2>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
-    else if (c.gumbel_m > 0) hipLaunchKernelGGL(k_advance_auto<1>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    if (gumbel_level(c) == 2) hipLaunchKernelGGL(k_advance_auto<2>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
+    else if (gumbel_level(c) == 1) hipLaunchKernelGGL(k_advance_auto<1>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
     else hipLaunchKernelGGL(k_advance_auto<0>, dim3(n_slots < 1024 ? n_slots : 1024), dim3(WAVE), 0, s, g, c, B, sa);
 }
 void tree_launch_get_roots(hipStream_t s, const Geo &g, const TreeBufs &B, int n_slots, double *priors, float *tv,

@@ -60,6 +60,8 @@ class Engine:
     (selfplay_set_forced_playouts); None: off.
     gumbel=(m, c_visit, c_scale): Gumbel root search in every search of the self-play driver (selfplay_set_gumbel; the usual setting
     is (16, 50.0, 1.0)); None: off.  gumbel=(m, c_visit, c_scale, True): the full mode -- the rule below the root too.
+    match_search=(spec0, spec1): the search of each model of a match_play handle (match_set_search); a spec is None (today's search)
+    or dict(reads=n, gumbel=(m, c_visit, c_scale[, full[, g_scale]])), either key optional.
     """
 
     EVALUATORS = {"formula": _lib.EVAL_FORMULA_HASH, "uniform": _lib.EVAL_FORMULA_UNIFORM,
@@ -71,7 +73,7 @@ class Engine:
                  max_out_rows=0, nn_precision=None, match_play=False, evaluator2="formula", transposition_cache=True,
                  max_pending_evals=1, selfplay_pending=False, eval_round=0, eval_defer_max=0, debug_flags=0, solver=None, solver_seed=0,
                  solver_reads=0, endgame=None, endgame_models=(0,), endgame_seed=0, endgame_reads=0, endgame_tables=None, playout_cap=None,
-                 forced_playouts=None, gumbel=None, endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
+                 forced_playouts=None, gumbel=None, endgame_wait=False, leaf_endgame=None, leaf_free=None, leaf_models=(0,), match_search=None):
         self._L = _lib.load()
         self.rows, self.cols = int(rows), int(cols)
         self.H, self.W = self.rows + 1, self.cols + 1
@@ -161,6 +163,14 @@ class Engine:
         if gumbel is not None:
             try:
                 self.selfplay_set_gumbel(*gumbel)
+            except Exception:
+                self.close()
+                raise
+        if match_search is not None:
+            try:
+                for model, spec in enumerate(match_search):
+                    spec = spec or {}
+                    self.match_set_search(model, spec.get("reads", 0), spec.get("gumbel"))
             except Exception:
                 self.close()
                 raise
@@ -561,6 +571,30 @@ class Engine:
             out["full"] = True
         return out
 
+    def match_set_search(self, model, reads=0, gumbel=None):
+        """dbaz_match_set_search: the search of one model of a match_play handle, for every later selfplay_start.  reads: the model's
+        read budget (0: mcts_num_read; a search runs min(rule, reads) reads, a PUCT model's too).  gumbel=(m, c_visit, c_scale[, full[,
+        g_scale]]): every search by this model is a Gumbel search with these constants, root-only or full, its noise g scaled by
+        g_scale (default 1.0; 0.0 is the paper's deterministic evaluation search); None: PUCT as today.  The model of a move is
+        root.to_play XOR (game_idx & 1).  The rule is stated in full in include/dbaz.h.  DbazError: EINVAL for a handle without
+        match_play, a model outside {0, 1} or an argument out of range; ESTATE while games are being played; a failed
+        call changes nothing."""
+        g = tuple(gumbel) if gumbel is not None else (0, 0.0, 0.0)
+        if not 3 <= len(g) <= 5:
+            raise _lib.DbazError(_lib.EINVAL, "gumbel=(m, c_visit, c_scale[, full[, g_scale]])")
+        full = int(bool(g[3])) if len(g) > 3 else 0
+        g_scale = float(g[4]) if len(g) > 4 else 1.0
+        self._ck(self._L.dbaz_match_set_search(self.h, int(model), int(reads), int(g[0]), C.c_double(float(g[1])), C.c_double(float(g[2])),
+                                               full, C.c_double(g_scale)))
+
+    def match_search(self, model):
+        """dbaz_match_get_search: dict(reads, m, c_visit, c_scale, full, g_scale) of one model of a match_play handle (all 0 for a
+        model never told; the Gumbel fields read 0 while m = 0)."""
+        r, m, mode, cv, cs, gs = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+        self._ck(self._L.dbaz_match_get_search(self.h, int(model), C.byref(r), C.byref(m), C.byref(cv), C.byref(cs), C.byref(mode), C.byref(gs)))
+        return dict(reads=int(r.value), m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value), full=bool(mode.value),
+                    g_scale=float(gs.value))
+
     def selfplay_start(self, n_games, first_game_idx=0):
         self._ck(self._L.dbaz_selfplay_start(self.h, int(n_games), int(first_game_idx)))
 
@@ -637,11 +671,16 @@ class Engine:
             out["pruned"] = (flags & 2) != 0  # ROW_FLAG_PRUNED, read from the rows themselves
         gm = C.c_int32()
         self._ck(self._L.dbaz_get_gumbel(self.h, C.byref(gm), None, None, None, None))  # the setting alone: no device work
+        mfull = False
+        if self.cfg.match_play:  # a match handle's setting is per model (match_set_search)
+            ms = [self.match_search(k) for k in (0, 1)]
+            gm.value = max(x["m"] for x in ms)
+            mfull = any(x["m"] > 0 and x["full"] for x in ms)
         if gm.value or (flags & 4).any():
             out["gumbel"] = (flags & 4) != 0  # ROW_FLAG_GUMBEL: visits are the target pi' in units of 2^-24
         mode = C.c_int32()
         self._ck(self._L.dbaz_get_gumbel_mode(self.h, C.byref(mode)))
-        if (gm.value and mode.value) or (flags & 8).any():
+        if mfull or (not self.cfg.match_play and gm.value and mode.value) or (flags & 8).any():
             out["gumbel_full"] = (flags & 8) != 0  # ROW_FLAG_GUMBEL_FULL: the search ran the rule below the root too
         return out
 

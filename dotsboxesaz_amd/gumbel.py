@@ -25,6 +25,15 @@ What the rule does to playing strength per GPU-hour has not been measured here.
 plays the same game indices with a random-init ResNetZero with PUCT at --puct-reads and with the Gumbel root at each read count,
 in one process, and prints one JSON line: per mode games/s, recorded rows/s, network evaluations per game, the mean entropy
 (nats) of the recorded pi and the mean max_deepness of the searches.  --full adds the full mode at each read count.
+
+In match play each of the two models has its own search (Engine.match_set_search, dbaz_match_set_search: read budget, PUCT or Gumbel,
+the Gumbel constants, root-only or full, and a scale on the Gumbel noise -- 0 is the paper's deterministic evaluation search):
+
+    python -m dotsboxesaz_amd.gumbel --rows 6 --cols 6 --match 8192 --seat0 gumbel:32[:full][:g0] --seat1 puct:800 [--openings 64 --opening-plies 4]
+
+plays N games of one random-init network against itself, seats swapped on odd games, from K random openings of P plies (two
+deterministic seats need a book), and prints one JSON line: games/s, evaluations per game, wins / draws / losses of seat 0 and the
+Elo difference they imply.  With --rows 3 --cols 3 --vs-solver seat 1 is the solved table and the line carries held_rate.
 """
 import ctypes as C
 
@@ -156,6 +165,105 @@ def _bench(a):
     return out
 
 
+def parse_seat(text, m=DEFAULT[0], c_visit=DEFAULT[1], c_scale=DEFAULT[2]):
+    """"puct:800", "gumbel:32", "gumbel:32:full", "gumbel:32:g0", "gumbel:32:full:g0" -> a spec of Engine(match_search=)"""
+    parts = str(text).split(":")
+    if len(parts) < 2 or parts[0] not in ("puct", "gumbel") or not parts[1].isdigit() or int(parts[1]) < 1:
+        raise ValueError("seat %r: puct:READS or gumbel:READS[:full][:g0]" % (text,))
+    opts = parts[2:]
+    if parts[0] == "puct":
+        if opts:
+            raise ValueError("seat %r: a PUCT seat takes no option" % (text,))
+        return dict(reads=int(parts[1]))
+    if any(o not in ("full", "g0") for o in opts):
+        raise ValueError("seat %r: the options of a Gumbel seat are full and g0" % (text,))
+    return dict(reads=int(parts[1]), gumbel=(int(m), float(c_visit), float(c_scale), "full" in opts, 0.0 if "g0" in opts else 1.0))
+
+
+def random_openings(rows, cols, n, plies, seed=0):
+    """n legal unfinished openings of `plies` random moves each (move sequences), by the rules of dotsboxesaz_amd.game"""
+    from .game import BoxesState
+    saved = BoxesState.BOARD_DIM
+    BoxesState.init_static_fields(((rows, cols),))
+    try:
+        rs = np.random.RandomState(seed)
+        book = []
+        while len(book) < n:
+            st, moves = BoxesState(), []
+            for _ in range(plies):
+                valid = np.asarray(st.get_valid_moves(as_indices=True))
+                if st.get_result() is not None or len(valid) == 0:
+                    break
+                mv = int(valid[rs.randint(len(valid))])
+                st.play_(mv)
+                moves.append(mv)
+            if len(moves) == plies and st.get_result() is None:
+                book.append(moves)
+    finally:
+        BoxesState.init_static_fields((saved,))
+    return book
+
+
+def elo_difference(wins, draws, losses):
+    """the Elo difference a score implies: -400 log10(1 / s - 1) with s = (wins + draws / 2) / games (+-inf at s = 1, 0)"""
+    n = wins + draws + losses
+    s = (wins + 0.5 * draws) / n if n else 0.5
+    if s <= 0.0 or s >= 1.0:
+        return float("inf") if s >= 1.0 else float("-inf")
+    return float(-400.0 * np.log10(1.0 / s - 1.0))
+
+
+def _match(a):
+    import time
+    import torch
+    from . import nn as dnn
+    from . import self_play as sp
+    from .engine import Engine
+
+    seats = (parse_seat(a.seat0, a.m, a.c_visit, a.c_scale), None if a.vs_solver else parse_seat(a.seat1, a.m, a.c_visit, a.c_scale))
+    reads = max(s["reads"] for s in seats if s)
+    solver = eng = None
+    try:
+        if a.vs_solver:
+            from .solver import Solver
+            solver = Solver(a.rows, a.cols, a.device).solve()
+            kw = dict(evaluator2="solver", solver=solver, solver_reads=a.solver_reads)
+        else:
+            kw = dict(evaluator2=a.evaluator)
+        eng = Engine(a.rows, a.cols, a.slots, mcts_num_read=reads, noise=(0.0, 0.0), reuse_tree=False, evaluator=a.evaluator, seed=1000,
+                     device=a.device, match_play=True, match_search=seats, **kw)
+        if a.evaluator == "resnet":
+            torch.manual_seed(0)
+            model = dnn.ResNetZero(dnn.resnet_params(a.rows, a.cols, a.channels, a.blocks))
+            for i in range(1 if a.vs_solver else 2):
+                eng.load_state_dict(model.state_dict(), "resnet", model=i, **model.shape)
+        if a.openings > 0:
+            eng.selfplay_set_start(random_openings(a.rows, a.cols, a.openings, a.opening_plies), 2)
+        eng.sync()
+        t0 = time.perf_counter()
+        eng.selfplay_start(a.match, 0)
+        eng.run()
+        dt = time.perf_counter() - t0
+        got = eng.fetch_samples()
+        c, gm = eng.counters(), eng.gumbel()
+        first = np.nonzero(got["move_idx"] == 0)[0]
+        z0 = got["z"][first].astype(np.int64) * np.where((got["player"][first] ^ (got["game_idx"][first] & 1)) == 0, 1, -1)  # seat 0's result
+        w, dr, l = int((z0 > 0).sum()), int((z0 == 0).sum()), int((z0 < 0).sum())
+        games = max(1, c["games_finished"])
+        out = dict(rows=a.rows, cols=a.cols, games=int(c["games_finished"]), slots=a.slots, evaluator=a.evaluator, seat0=a.seat0,
+                   seat1="solver" if a.vs_solver else a.seat1, openings=a.openings, opening_plies=a.opening_plies, games_per_s=c["games_finished"] / dt,
+                   evals_per_game=(c["nn_evals"] if a.evaluator == "resnet" else c["expansions"]) / games, gumbel_rows=gm["rows"],
+                   wins=w, draws=dr, losses=l, elo_diff=elo_difference(w, dr, l), seconds=dt)
+        if solver is not None:
+            out["held_rate"] = sp.match_vs_theory(got, solver)["held_rate"]
+        return out
+    finally:
+        if eng is not None:
+            eng.close()
+        if solver is not None:
+            solver.close()
+
+
 def main(argv=None):
     import argparse
     import json
@@ -177,7 +285,19 @@ def main(argv=None):
     ap.add_argument("--blocks", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=1, help="timed runs per mode (median)")
     ap.add_argument("--warmup-games", type=int, default=64, help="games of the one untimed run in front of them")
+    ap.add_argument("--match", type=int, default=0, metavar="N", help="match play instead of the bench: N games of one network against itself")
+    ap.add_argument("--seat0", default="gumbel:32", help="model 0's search: puct:READS or gumbel:READS[:full][:g0]")
+    ap.add_argument("--seat1", default="puct:800", help="model 1's search")
+    ap.add_argument("--openings", type=int, default=0, metavar="K", help="a book of K random openings, two games each per round (0: the empty board)")
+    ap.add_argument("--opening-plies", type=int, default=4, metavar="P")
+    ap.add_argument("--vs-solver", action="store_true", help="seat 1 is the solved table of the board (small boards); adds held_rate")
+    ap.add_argument("--solver-reads", type=int, default=2)
+    ap.add_argument("--evaluator", default="resnet", choices=("resnet", "formula", "uniform"), help="the network (random-init) or a formula evaluator")
     a = ap.parse_args(argv)
+    if a.match > 0:
+        a.slots = a.slots or max(1, min(a.match, 8192))
+        print(json.dumps(_match(a)))
+        return
     a.slots = a.slots or max(1, min(a.bench, 8192))
     print(json.dumps(_bench(a)))
 

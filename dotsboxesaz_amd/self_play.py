@@ -70,6 +70,20 @@ def _gumbel_args(gum):
     return args + (True,) if bool(_get(gum, "full", False)) else args
 
 
+def match_search_spec(spec):
+    """the search of one model of a match as compute_elo(search=) and solver_match(search=) take it -- None, or {"reads": n, "gumbel":
+    {...params.self_play.gumbel's dict..., "g_scale": s}}, either key optional -- as Engine(match_search=) takes it"""
+    if spec is None:
+        return None
+    out = {"reads": int(_get(spec, "reads", 0) or 0)}
+    gum = _get(spec, "gumbel")
+    if gum:
+        args = _gumbel_args(gum)
+        gs = _get(gum, "g_scale")
+        out["gumbel"] = args[:3] + (len(args) > 3, 1.0 if gs is None else float(gs))
+    return out
+
+
 def engine_kwargs_from_params(params, async_searches=False):
     """Pull the hot-path knobs out of a reference-style params dict (configuration.py:82-100).
 
@@ -427,7 +441,7 @@ def match_winners(samples, generations):
 
 def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=None, cols=None, n_slots=None, device=0,
                 nn_precision=None, openings=None, endgame=None, endgame_models=(0,), endgame_tables=None, endgame_wait=False,
-                leaf_endgame=None, leaf_free=None, leaf_models=(0,)):
+                leaf_endgame=None, leaf_free=None, leaf_models=(0,), search=None):
     """Reference: self_play.compute_elo(elo_params, [params0, params1], [gen0, gen1], (elo0, elo1)).
     The two models play elo_params.n_games games against each other on the GPU: the model of the
     player to move at the root runs that move's whole search (self_play.py:59,237-239), seats are
@@ -443,6 +457,10 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     waits for a table (Engine(endgame_wait=True)), so that the match does not depend on the pool's size.
     leaf_endgame, leaf_free, leaf_models: an endgame.Endgame that solves the leaves with at most leaf_free free edges of the listed
     models from scratch, whatever the root (Engine.attach_leaf_solver).
+    search: (spec0, spec1), the search of each model (Engine.match_set_search): a spec is None -- PUCT at the match's reads -- or
+    {"reads": n, "gumbel": {...params.self_play.gumbel's dict..., "g_scale": s}}, e.g. Gumbel at 32 reads against PUCT at 800 of the
+    same network.  reads is at most the match's mcts_num_read.  Absent, the match is what it always was: the params' own gumbel
+    key is dropped.
     Returns (elo0, elo1, n1 / number of decided games)."""
     from .engine import Engine
     p0, p1 = params
@@ -472,7 +490,7 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=models[0].kind, evaluator2=models[1].kind,
                  match_play=True, device=device, nn_precision=nn_precision, endgame=endgame, endgame_models=endgame_models,
                  endgame_tables=endgame_tables, endgame_wait=endgame_wait, leaf_endgame=leaf_endgame, leaf_free=leaf_free,
-                 leaf_models=leaf_models, **kw)
+                 leaf_models=leaf_models, match_search=None if search is None else tuple(match_search_spec(s) for s in search), **kw)
     try:
         for i, mdl in enumerate(models):
             eng.load_state_dict(mdl.state_dict(), mdl.kind, model=i, **mdl.shape)
@@ -490,12 +508,14 @@ def compute_elo(elo_params, params, generations, elos, nn_classes=None, rows=Non
 
 
 def solver_match(params, generation, n_games, rows, cols, openings=None, solver=None, solver_seed=0, solver_reads=2, nn_class=None,
-                 n_slots=None, device=0, nn_precision=None):
+                 n_slots=None, device=0, nn_precision=None, search=None):
     """The network against perfect play: the absolute measure next to compute_elo's relative one, on boards the exact solver
     holds (at most 31 edges).  The network of `params` / `generation` is model 0, the solved table (dotsboxesaz_amd.solver) model
     1; seats and book as in compute_elo: the network moves first in even games, games 2k and 2k+1 start from opening
     k % len(openings).  solver: a solved Solver of the board (reuse it: a solve costs 2^E bytes); solver_seed picks among the
     table's equally good moves; the table's searches run min(rule, solver_reads) reads (one already finds its move).
+    search: the spec of the network's seat, model 0, as in compute_elo (None or absent: PUCT at the params' reads); the table keeps
+    solver_reads.
     Returns dict(games, wins, draws, losses -- the network's --, theory = {"win", "draw", "loss"}: games whose start is that
     result for the network's seat under perfect play, held = games in which the network got at least that result, held_rate,
     f32_fallback_evals of the engine's counters, samples = the rows of the games)."""
@@ -517,7 +537,8 @@ def solver_match(params, generation, n_games, rows, cols, openings=None, solver=
     kw.pop("forced_playouts", None)
     kw.pop("gumbel", None)
     eng = Engine(rows, cols, n_slots or max(1, min(n_games, 4096)), evaluator=model.kind, evaluator2="solver", match_play=True,
-                 device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads, **kw)
+                 device=device, nn_precision=nn_precision, solver=solver, solver_seed=solver_seed, solver_reads=solver_reads,
+                 match_search=None if search is None else (match_search_spec(search), None), **kw)
     try:
         eng.load_state_dict(model.state_dict(), model.kind, model=0, **model.shape)
         if openings is not None and len(openings):

@@ -334,8 +334,8 @@ int dbaz_prune_visits(int32_t n_actions, double k, double pbc, double sq, int64_
  * rule off every row is what it was.
  * Scope: with m > 0 every search that the self-play driver starts is a Gumbel search, full and fast searches of the playout cap
  * alike (a fast search still has capped reads and its row still carries bit 0).  Explicit searches (dbaz_search*, dbaz_select)
- * and match play never see the rule.  Below the root nothing changes (unless the full mode is on: dbaz_selfplay_set_gumbel_mode,
- * below).
+ * never see the rule, and match play sees it only through dbaz_match_set_search (below).  Below the root nothing changes
+ * (unless the full mode is on: dbaz_selfplay_set_gumbel_mode, below).
  * All arithmetic below is float64, every operation rounded on its own (no fused multiply-add), in the order written.
  *
  * Root preparation -- where the root's priors are prepared for such a search (at its start, or after the root's expansion):
@@ -429,8 +429,9 @@ int dbaz_gumbel_target(int32_t n_actions, double c_visit, double c_scale, const 
  *
  *   mode other than 0 or 1                                               -> DBAZ_EINVAL
  *   games of an earlier dbaz_selfplay_start still being played           -> DBAZ_ESTATE
- * A failed call changes nothing.  The refusals of dbaz_selfplay_set_gumbel are unchanged, so the full mode is never reached in match
- * play, in self-play in waves or beside forced playouts; explicit searches never see the rule in either mode.
+ * A failed call changes nothing.  The refusals of dbaz_selfplay_set_gumbel are unchanged, so this call never brings the full mode
+ * to match play (dbaz_match_set_search does, per model), to self-play in waves or beside forced playouts; explicit searches never
+ * see the rule in either mode.
  * dbaz_get_gumbel_mode: the setting (mode may be NULL).
  * The rule on the host -- no handle, no device -- from the very code the kernels run, for one node with value v, priors P, W,
  * n_and_sign and valid as for dbaz_gumbel_target:  dbaz_gumbel_improved_policy: pi_out[i] = pi'(i), 0.0 for a non-candidate;
@@ -445,6 +446,51 @@ int dbaz_gumbel_nonroot_pick(int32_t n_actions, double c_visit, double c_scale, 
                              const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
 int dbaz_gumbel_target_full(int32_t n_actions, double c_visit, double c_scale, double v, const double *P, const float *W,
                             const uint32_t *n_and_sign, const uint8_t *valid, int32_t *out);
+/* The search of each model of a match.  On a match_play handle the model of a move is root.to_play XOR (game_idx & 1), as ever;
+ * dbaz_match_set_search(e, model, reads, m, c_visit, c_scale, mode, g_scale) gives that model its own read budget, its own rule (PUCT
+ * or Gumbel), Gumbel constants, mode and a scale on the Gumbel noise.  It is a setting of the handle for every later
+ * dbaz_selfplay_start; after dbaz_create both models have (0, 0, 0, 0, 0, 0), and a handle in that state plays every row it played
+ * before, bit for bit.  The other model's rows, moves and random streams are untouched by one model's setting.
+ *
+ * reads: 0 = the handle's mcts_num_read, as today.  Otherwise a search by this model runs min(rule, reads) reads, rule being the
+ *   driver's count min(4 * nb_valid_moves!, mcts_num_read).  The cap is applied where solver_reads and endgame_reads are, and before
+ *   them; R of the halving is still the reads the search was started with, after every cap.  Range 0 .. mcts_num_read: the node pool
+ *   and the reserve of a re-root stay sized by mcts_num_read.  reads holds for a PUCT model (m = 0) too.
+ * m = 0: this model's searches are what they are today except for the read count: Dirichlet noise, temperature, the move-draw
+ *   stream, visit counts as the row.  c_visit, c_scale, mode and g_scale are then ignored and read back 0.
+ * m > 0: every search by this model is a Gumbel search exactly as stated for dbaz_selfplay_set_gumbel, with this model's m, c_visit
+ *   and c_scale: no Dirichlet noise, no temperature, the move-draw stream not consumed, the row's visits the target pi' in units of
+ *   2^-24, flag bit 2 set (and bit 3 when mode = 1).
+ * g_scale: gl(a) = (g_scale * g(a)) + logit(a) -- one product, then one sum, each rounded on its own.  Range 0 .. 1e3.  1.0 gives
+ *   the bits of the self-play rule (the product is exact).  A scripted vector is scaled the same way.  0 is the paper's
+ *   deterministic evaluation search: the m' candidates are the top m' by logit, the candidates that survive each halving are decided
+ *   by logit + sigma alone, and the move is the argmax of logit + sigma(q) among the most visited; exact ties go to the first index
+ *   as everywhere else.
+ * mode: 0 = the rule at the root, 1 = full (dbaz_selfplay_set_gumbel_mode's rule), per model.  If either model is full, every node
+ *   any search of the handle expands keeps its v^, whichever model expanded it, so a full search always finds the v^ of a root and
+ *   of inner nodes that the other model's search made.  A root-only search on such a handle is root-only in everything: the
+ *   root-only v_mix, the UCB below the root, bit 3 clear.
+ * Tree reuse: n0 already covers a root that the other model's search has visited; the root prior is whatever the tree holds, the
+ *   existing semantics of match play.
+ *
+ *   a handle without match_play; model outside {0, 1}; reads outside 0 .. mcts_num_read;
+ *   m < 0 or m > DBAZ_MAX_A; for m > 0: c_visit NaN, negative or above 1e6, c_scale NaN, <= 0 or above 1e3, mode other than 0 or 1,
+ *   g_scale NaN, negative or above 1e3                                                               -> DBAZ_EINVAL
+ *   games of an earlier dbaz_selfplay_start still being played                                       -> DBAZ_ESTATE
+ * A failed call changes nothing.  (Self-play in waves needs no refusal here: dbaz_create refuses max_pending_evals > 1, which
+ * selfplay_pending requires, on a match_play handle.)
+ * The row's visits of a Gumbel model are the rule's arithmetic; an implementation whose log and exp are within 1 ulp reproduces
+ * them to the count wherever no decision and no rounding of pi' * 2^24 + 0.5 lies within that error of a tie.
+ * dbaz_selfplay_set_gumbel goes on refusing a match handle; the playout cap and forced playouts stay refused in match play.
+ * dbaz_get_gumbel's searches and rows count the Gumbel searches and rows of either model; its setting is the self-play
+ * one and reads 0 on a match handle.  Explicit searches (dbaz_search*, dbaz_select) and self-play in waves still
+ * never see the rule.
+ * dbaz_match_get_search: the model's setting; any output pointer may be NULL.  A handle without match_play or a model outside
+ * {0, 1} -> DBAZ_EINVAL. */
+int dbaz_match_set_search(dbaz_engine *e, int32_t model, int32_t reads, int32_t m, double c_visit, double c_scale, int32_t mode,
+                          double g_scale);
+int dbaz_match_get_search(dbaz_engine *e, int32_t model, int32_t *reads, int32_t *m, double *c_visit, double *c_scale, int32_t *mode,
+                          double *g_scale);
 int dbaz_step(dbaz_engine *e, int32_t k);             /* k simulation steps, asynchronous */
 /* until all games are finished, max_steps (if > 0) are done, or every remaining slot is
  * blocked on a full output buffer (counters.blocked_slots == active_slots: fetch and call again) */
